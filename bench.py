@@ -202,6 +202,30 @@ def extra_measurements(step, args, engine):
     return out
 
 
+DUMP_MAX_ELEMS = 1 << 22   # per array (16 MB of float32): loss + prediction + parameters stay under 64 MB in all
+
+
+def dump_outputs(out_dir, arrays):
+    """Write each tensor of `arrays` (name -> tensor) as out_dir/<name>.npy in float32.  An array larger than
+    DUMP_MAX_ELEMS is replaced by a fixed sample of its flattened elements: DUMP_MAX_ELEMS indices drawn by torch.randperm
+    with seed 0, in increasing order -- the same elements in every run with the same arguments.  Returns name -> what was
+    written (for the JSON line)."""
+    import numpy as np
+    os.makedirs(out_dir, exist_ok=True)
+    info = {}
+    for name, t in arrays.items():
+        flat = t.detach().float().cpu().reshape(-1)
+        entry = {"shape": list(t.shape)}
+        if flat.numel() > DUMP_MAX_ELEMS:
+            idx = torch.randperm(flat.numel(), generator=torch.Generator().manual_seed(0))[:DUMP_MAX_ELEMS].sort().values
+            flat = flat[idx]
+            entry["sample"] = f"{DUMP_MAX_ELEMS} of {t.numel()} flattened elements, randperm seed 0, sorted"
+        arr = flat.numpy().astype(np.float32) if "sample" in entry else flat.reshape(t.shape).numpy().astype(np.float32)
+        np.save(os.path.join(out_dir, f"{name}.npy"), arr)
+        info[name] = entry
+    return info
+
+
 def self_launch(args_gpus):
     """`python bench.py --gpus N` without a launcher: re-exec under torch.distributed.run with one rank per GPU on
     127.0.0.1 (what the reference's train_multi_gpu does with mp.spawn, multi_gpu_training.py:172-190).  The ranks
@@ -293,7 +317,13 @@ def main():
     ap.add_argument("--kernel-table", default=None, help="write the per-kernel timing table to this file")
     ap.add_argument("--option", action="append", default=[], metavar="NAME=VALUE",
                     help="developer A/B: a dispatch option of the library (include/tem_hip.h, tem_set_option), e.g. zr_wide=0")
+    ap.add_argument("--dump-outputs", default=None, metavar="DIR",
+                    help="after the timed steps, write what the last timed step returned to its caller -- loss, prediction "
+                         "and the parameters after the optimizer step -- as DIR/<name>.npy (float32; large arrays as a fixed "
+                         "seeded sample, see dump_outputs)")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
 
     import torch.distributed as dist
     from torch_em_amd import ops
@@ -335,12 +365,17 @@ def main():
     S = args.size
     x = torch.randn(args.batch, 1, S, S, S, generator=g).to(dev)
     y = (torch.rand(args.batch, 2, S, S, S, generator=g) > 0.5).float().to(dev)
+    keep_pred = args.dump_outputs is not None and rank == 0
+    last = {}   # the prediction of the latest step, for --dump-outputs
 
     def step():
         opt.zero_grad()
-        loss = loss_fn(model(x), y)
+        pred = model(x)
+        loss = loss_fn(pred, y)
         loss.backward()
         opt.step()
+        if keep_pred:
+            last["pred"] = pred
         return loss
 
     # Live HIP-event timing costs host time and GPU bubbles (two events per launch, ~200 per step: 3.5-6 ms/step), so
@@ -424,7 +459,10 @@ def main():
     for i in range(args.steps):
         if ev_steps:
             ops.PROFILER_FILTER = {dom_tag} if i in ev_steps else set()
-        loss = graphed(x, y)[1] if graphed is not None else step()
+        if graphed is not None:
+            last["pred"], loss = graphed(x, y)
+        else:
+            loss = step()
     # wall time of the Python loop per step, before the final synchronize: eager = host cost of enqueueing ~220 launches
     # (while the GPU queue has room); graph = one replay per step, but the loop is held back by the GPU (the 4-slot pinned
     # ring of optimizer scalars waits for the replay that used a slot): the graph's own host cost is `hip_graph.*.host_ms`
@@ -448,6 +486,10 @@ def main():
         dist.all_reduce(t, op=dist.ReduceOp.MAX)
         elapsed = float(t.item())
     final_loss = float(loss)
+    dumped = None
+    if args.dump_outputs is not None and rank == 0:   # before the extras, which run more steps on the same model
+        params = torch.cat([p.detach().reshape(-1) for p in net.parameters()])
+        dumped = dump_outputs(args.dump_outputs, {"loss": loss.reshape(1), "prediction": last["pred"], "parameters": params})
     ddp_info = None
     if isinstance(model, DDP):
         ddp_info = {"bytes": model.sync.stats["bytes"], "n_collectives": model.sync.stats["n_collectives"],
@@ -488,7 +530,10 @@ def main():
             with open(args.kernel_table, "w") as f:
                 f.write("\n".join(lines) + "\n")
         if not rows:  # TEM_BENCH_NOPROF=1 (A/B of the live-event overhead): no kernel table, no roofline
-            os.write(real_stdout, (json.dumps({"ms_per_step": ms, "value": value, "note": "live profiling disabled"}) + "\n").encode())
+            line = {"ms_per_step": ms, "value": value, "note": "live profiling disabled"}
+            if dumped is not None:
+                line["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
+            os.write(real_stdout, (json.dumps(line) + "\n").encode())
             return
         # the dominant kernel, timed live over the timed region (HIP events on its launch stream)
         dom = {"launches": 0, "ms": 0.0, "flops": 0.0}
@@ -552,6 +597,8 @@ def main():
             out["step_mode"] += f" (the HIP-graph replay that is the default for --gpus > 1 could not be captured: {graph_error})"
         if ddp_info is not None:
             out["ddp"] = ddp_info
+        if dumped is not None:
+            out["dump_outputs"] = {"dir": args.dump_outputs, "arrays": dumped}
         if standard:
             out["step_roofline"] = {
                 "flops_frac_fp32_mfma": STEP_GFLOP / ms / PEAK_FP32_MFMA_TFLOPS,

@@ -1,6 +1,7 @@
 """Train UNet2d(1, 2, depth=2, initial_features=4) for 4 iterations with THIS repo's trainer on the GPU and leave the
 checkpoint folder under gpurun_out/ckpt_tiny (it is then committed as tests/golden/ckpt_tiny/ and read back by the
-REFERENCE's load_model / DefaultTrainer.from_checkpoint in the build container: tests/test_reference_reads_checkpoint.py)."""
+REFERENCE's load_model / DefaultTrainer.from_checkpoint where the reference is available: tests/golden/gen_golden_checkpoint_read.py
+records what they read, tests/test_reference_reads_checkpoint.py checks it)."""
 import os
 import shutil
 import sys

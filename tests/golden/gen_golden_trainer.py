@@ -12,8 +12,8 @@ G8  the affinity targets of the reference's OWN brute-force definitions (`affs_b
     `AffinityTransform.__call__` (transform/label.py:299-325) applied to them.
 G9  a tiny checkpoint written by THIS repo's trainer format is read by the reference's `load_model`
     (util/util.py:408-460) and `DefaultTrainer.from_checkpoint` (trainer/default_trainer.py:288-330): see
-    gen_checkpoint_compat() -- it needs a checkpoint produced on a GPU box and is therefore run separately
-    (tests/golden/README_checkpoint.md records the result).
+    tests/golden/gen_golden_checkpoint_read.py -- it needs a checkpoint produced on a GPU box and is therefore run
+    separately (its fixture: g11_reference_reads_ckpt.npz).
 
 `import torch_em` needs packages this image lacks (imageio, skimage, kornia, ...): a meta-path finder serves empty
 stand-in modules for exactly those imports (SURVEY.md 8c route B).  Nothing of the trainer path touches them.

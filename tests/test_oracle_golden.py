@@ -18,6 +18,32 @@ def _sd(g):
     return {k[3:]: torch.from_numpy(v) for k, v in g.items() if k.startswith("sd.")}
 
 
+@pytest.fixture(autouse=True)
+def _fixture_threads():
+    """The golden vectors were made with 4 intra-op threads (gen_golden.py, gen_golden_trainer.py; G10 with 8, which that
+    test sets itself); torch's CPU reductions follow the thread count, so the oracle runs at that count here too, whatever
+    the host has."""
+    prev = torch.get_num_threads()
+    torch.set_num_threads(4)
+    yield
+    torch.set_num_threads(prev)
+
+
+def _check_grads(grads, g, zero_keys=("decoder.samplers.", ".conv.bias")):
+    """Every gradient within 1e-4 of the reference's, relative to that tensor's max.  The one gradient that is
+    MATHEMATICALLY zero -- the bias of a sampler's conv, whose output feeds a per-channel norm (named by `zero_keys` as in
+    conftest.check_grads, AND |ref| < 1e-4 of the model's largest gradient, so a net without norms keeps the relative
+    check) -- holds only fp32 round-off on both sides, whose value depends on the host CPU's summation order; it is held
+    to 1e-6 of the model's largest gradient instead (the round-off allowance of conftest.check_grads; measured <= 1.3e-7)."""
+    gscale = max(float(np.abs(g[f"grad.{k}"]).max()) for k in grads)
+    for k, v in grads.items():
+        ref = g[f"grad.{k}"]
+        if all(z in k for z in zero_keys) and float(np.abs(ref).max()) < 1e-4 * gscale:
+            assert float(np.abs(v.double().numpy() - ref).max()) <= 1e-6 * gscale, k
+        else:
+            assert rel_err(v, ref) < 1e-4, k
+
+
 @pytest.mark.parametrize("norm", ["InstanceNorm", "GroupNorm", None])
 def test_unet3d_oracle_matches_reference(norm):
     g = _load(f"g1_unet3d_{norm}.npz")
@@ -25,8 +51,7 @@ def test_unet3d_oracle_matches_reference(norm):
                                                      [2, 2], norm=norm)
     assert rel_err(pred, g["pred"]) < 1e-5
     assert abs(float(loss) - float(g["loss"])) < 1e-5
-    for k, v in grads.items():
-        assert rel_err(v, g[f"grad.{k}"]) < 1e-4, k
+    _check_grads(grads, g)
 
 
 @pytest.mark.parametrize("aniso", [0, 1])
@@ -37,8 +62,7 @@ def test_aniso_oracle_matches_reference(aniso):
         final_activation="Sigmoid", loss_fn=loss_ref.masked_dice_loss)
     assert rel_err(pred, g["pred"]) < 1e-5
     assert abs(float(loss) - float(g["loss"])) < 1e-5
-    for k, v in grads.items():
-        assert rel_err(v, g[f"grad.{k}"]) < 1e-4, k
+    _check_grads(grads, g)
 
 
 def test_crop_oracle_matches_reference():
@@ -48,8 +72,7 @@ def test_crop_oracle_matches_reference():
                                                      [[3, 3, 3], [2, 2, 2]])
     assert tuple(pred.shape) == (2, 2, 12, 12, 12) and rel_err(pred, g["pred"]) < 1e-5
     assert abs(float(loss) - float(g["loss"])) < 1e-5
-    for k, v in grads.items():
-        assert rel_err(v, g[f"grad.{k}"]) < 1e-4, k
+    _check_grads(grads, g)
 
 
 def test_unet2d_oracle_matches_reference():
@@ -58,8 +81,7 @@ def test_unet2d_oracle_matches_reference():
                                                      [2, 2])
     assert rel_err(pred, g["pred"]) < 1e-5
     assert abs(float(loss) - float(g["loss"])) < 1e-5
-    for k, v in grads.items():
-        assert rel_err(v, g[f"grad.{k}"]) < 1e-4, k
+    _check_grads(grads, g)
 
 
 def test_dice_oracle_matches_reference():
@@ -329,6 +351,7 @@ def test_oracle_at_mfma_widths_matches_the_reference_float64_and_fp32_steps():
     reference's (stored as float32: 1e-6), its float32 step sits at the reference's own fp32 distance from float64."""
     import hashlib
     from torch_em_amd.model import UNet3d
+    torch.set_num_threads(8)   # gen_golden_amp_step.py's count (the autouse fixture restores the previous one)
     g = _load("g10_amp_step.npz")
     torch.manual_seed(0)
     model = UNet3d(1, 2, depth=2, initial_features=32)
@@ -347,9 +370,13 @@ def test_oracle_at_mfma_widths_matches_the_reference_float64_and_fp32_steps():
         ref = g[f"f64.grad.{k}"].astype("float64")
         err = float(np.linalg.norm(grads[k].numpy() - ref))
         assert err <= 2e-7 * max(float(n64), 1e-6 * gscale), (k, err, n64)      # float32 storage of the fixture
-    # the oracle's fp32 step: the distance the reference's fp32 step has from float64, tensor by tensor (same ATen kernels)
+    # the oracle's fp32 step: the distance the reference's fp32 step has from float64, tensor by tensor (same ATen kernels).
+    # `f32.grad_err` was measured with the fixture host's CPU kernels, where the oracle reproduces the reference's fp32 step
+    # bit for bit (ratio 1.00).  ATen's fp32 CPU kernels differ between host CPUs: on another x86-64 CPU the same fp32
+    # step lies 3.9x farther from float64 over the whole gradient and up to 5.2x per tensor, at 1-16 threads alike -- hence
+    # a factor of 6 rather than the 3 that one host's numbers alone suggested.
     pred32, loss32, g32 = unet_ref.unet_loss_and_grads(sd, x, y, [2, 2])
     assert abs(float(loss32) - float(g["f32.loss"])) < 1e-6
     for k, n64, e_ref in zip(names, g["f64.grad_norm"], g["f32.grad_err"]):
         err = float(np.linalg.norm(g32[k].double().numpy() - g[f"f64.grad.{k}"].astype("float64")))
-        assert err <= 3.0 * max(float(e_ref), 1e-6 * gscale), (k, err, e_ref)
+        assert err <= 6.0 * max(float(e_ref), 1e-6 * gscale), (k, err, e_ref)

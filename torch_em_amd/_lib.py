@@ -182,7 +182,10 @@ class TemError(RuntimeError):
 
 def build(verbose=False):
     """Compile libtem_hip.so for gfx950 in-tree (hipcc cross-compiles without a GPU)."""
-    cmd = ["make", "-C", CSRC, "-j", str(os.cpu_count() or 4)]
+    # MAX_JOBS (the convention of torch extension builds) sets the job count; otherwise at most 16: os.cpu_count() is the
+    # whole host's, not this process's share of it
+    jobs = int(os.environ.get("MAX_JOBS") or min(os.cpu_count() or 4, 16))
+    cmd = ["make", "-C", CSRC, "-j", str(jobs)]
     res = subprocess.run(cmd, capture_output=True, text=True)
     if verbose or res.returncode != 0:
         print(res.stdout)
