@@ -195,15 +195,27 @@ int tem_conv3d_fwd(const float* x, int64_t x_ld, const float* scale, const float
  * stat_blocks = tem_conv3d_fwd_stat_blocks(...), which returns 0 for launches that cannot provide them (the generic VALU
  * kernels, the exact-fp32 PATCH kernels (use_mfma 1 on shapes the z-reuse kernel does not take, or option fp32_zr = 0),
  * the patch kernel's split-K launches; the split-K launches of the z-reuse kernel DO:
- * their epilogue writes the rows): use tem_norm_stats there.  tem_norm_finalize_partials (below) merges them. */
+ * their epilogue writes the rows): use tem_norm_stats there.  tem_norm_finalize_partials (below) merges them.
+ * tem_conv3d_fwd_stat_blocks answers for dense, 16-byte aligned x and y without ref; tem_conv3d_fwd_stat_blocks_ld for the
+ * layout of an actual launch: leading dimensions x_ld / y_ld / ref_ld (0: no ref) and `misaligned` != 0 when any pointer of
+ * the launch (x, y, ref, bias, scale, shift, packed weights) is not 16-byte aligned.  The team kernels address a halo with
+ * 32-bit byte offsets (H * W * 32 * max(x_ld, y_ld, ref_ld) < 2^31) and write 16-byte vectors (y / ref ld % 4 == 0): a
+ * layout they decline goes to the patch kernel, whose rows differ, or (when the team kernel's shape asks for it) gets no
+ * statistics at all.  tem_conv3d_fwd_stats checks stat_blocks against tem_conv3d_fwd_stat_blocks_ld() of its own
+ * arguments and returns TEM_EINVAL, with nothing enqueued, when they differ. */
 int64_t tem_conv3d_fwd_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma);
+int64_t tem_conv3d_fwd_stat_blocks_ld(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,
+                                      int64_t x_ld, int64_t y_ld, int64_t ref_ld, int misaligned);
 /* Which kernel family a tem_conv3d_fwd launch of this shape selects under the current options: 3 = the z-reuse team
  * kernel (csrc/conv_zr.hip: 3x3x3, 4x16x8 patches), 4 = the same kernel with the input channels split over several units
  * and a summing epilogue (16^3 / 32^3 levels: too few tiles otherwise; needs the tem_conv3d_fwd_ws() workspace, no fused
  * statistics), 1 or 2 = the ping-pong team kernel (csrc/conv_pp.hip: 3x3x3 / 1x3x3,
  * two-plane layouts, enough patches to fill the chip) with that many 32-column output tiles per team, 0 = everything else.  Profiling / test aid (kernel tables of bench.py, the per-
- * instantiation parity tests); alignment fall-backs of an individual launch are not reflected. */
+ * instantiation parity tests) for dense, aligned x and y without ref; tem_conv3d_fwd_kernel_ld answers for the layout of an
+ * actual launch (arguments as in tem_conv3d_fwd_stat_blocks_ld; the workspace given, no sigmoid). */
 int tem_conv3d_fwd_kernel(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma);
+int tem_conv3d_fwd_kernel_ld(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,
+                             int64_t x_ld, int64_t y_ld, int64_t ref_ld, int misaligned);
 int tem_conv3d_fwd_stats(const float* x, int64_t x_ld, const float* scale, const float* shift,
                          const float* w_packed, const float* bias, float* y, int64_t y_ld,
                          const float* ref, int64_t ref_ld, void* ws, int64_t ws_bytes,
@@ -344,14 +356,14 @@ int tem_absmax(const float* x, int64_t ld, int C, int64_t nvox, unsigned* amax, 
  * on w_packed = tem_conv_pack_weights(transpose = 1, use_mfma = 4), no bias / norm / activation, where the kernel first
  * multiplies x by the power of two that puts *in_amax (bit pattern of max |x|, e.g. from tem_conv3d_wgrad_gmax) into
  * [2^14, 2^15) and divides the result by it: exact, and nothing can leave fp16's range.  Only for launches that
- * tem_conv3d_fwd_kernel(..., 4) reports as 3. */
+ * tem_conv3d_fwd_kernel_ld(..., 4, <the launch's layout>) reports as 3. */
 int tem_conv3d_fwd_gscaled(const float* x, int64_t x_ld, const float* w_packed, float* y, int64_t y_ld,
                            const float* ref, int64_t ref_ld, const unsigned* in_amax, void* ws, int64_t ws_bytes,
                            int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, tem_stream_t stream);
 /* tem_conv3d_fwd of a data gradient that lands behind a ReLU + norm (the first conv of a block, seen from the second's
  * backward): y = ref > 0 ? a*conv(x) - m1 - (ref - mean)*m2r : 0 with coef[N][Cout][4] = (a, m1, m2r, mean) from
  * tem_norm_bwd_coef.  The epilogue of the z-reuse kernel replaces the elementwise pass of tem_norm_bwd_from_sums (the
- * reference: autograd's native_layer_norm / relu backward kernels).  Only for launches tem_conv3d_fwd_kernel() == 3. */
+ * reference: autograd's native_layer_norm / relu backward kernels).  Only for launches tem_conv3d_fwd_kernel_ld() == 3. */
 int tem_conv3d_fwd_refnorm(const float* x, int64_t x_ld, const float* w_packed, float* y, int64_t y_ld,
                            const float* ref, int64_t ref_ld, const float* coef, void* ws, int64_t ws_bytes,
                            int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,

@@ -38,6 +38,8 @@ SIGNATURES = {
                        + [c_int] * 11 + [c_vp]),
     "tem_conv3d_fwd_stat_blocks": (c_i64, [c_int] * 10),
     "tem_conv3d_fwd_kernel": (c_int, [c_int] * 10),
+    "tem_conv3d_fwd_stat_blocks_ld": (c_i64, [c_int] * 10 + [c_i64] * 3 + [c_int]),
+    "tem_conv3d_fwd_kernel_ld": (c_int, [c_int] * 10 + [c_i64] * 3 + [c_int]),
     "tem_conv3d_fwd_stats": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64]
                              + [c_int] * 11 + [c_vp, c_i64, c_vp]),
     "tem_conv3d_wgrad_ws": (c_i64, [c_int] * 10),

@@ -367,34 +367,87 @@ extern "C" int tem_conv3d_fwd(const float* x, int64_t x_ld, const float* scale, 
 
 static inline bool ref_free_cin1_ok(int Cout) { return Cout % 4 == 0; }
 
+// What a tem_conv3d_fwd launch of this shape AND layout does: the kernel family it takes (tem_conv3d_fwd_kernel) and the
+// statistics rows it writes (tem_conv3d_fwd_stat_blocks) -- the launch conditions of conv3d_fwd_impl, tem_conv_fwd_zr,
+// tem_conv_fwd_pp and tem_conv_fwd_zr_splitk as one function.  ref_ld 0: no ref.  misaligned: a pointer of the launch
+// (x, y, ref, bias, scale, shift, packed weights) is off a 16-byte boundary.  Assumes the tem_conv3d_fwd_ws() workspace and
+// no sigmoid.  Shapes whose team kernel declines the layout get no statistics (the team launches raise when asked for
+// rows they cannot write; the caller runs tem_norm_stats).
+struct FwdPlan {
+    int family;
+    int64_t stat_blocks;
+};
+static FwdPlan fwd_plan(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, int64_t x_ld,
+                        int64_t y_ld, int64_t ref_ld, int misaligned) {
+    FwdPlan p = {0, 0};
+    int64_t max_ld = x_ld > y_ld ? x_ld : y_ld;
+    if (ref_ld > max_ld) max_ld = ref_ld;
+    // the team kernels' 16-byte epilogue (and the cin1 kernel's): y / ref with ld % 4 == 0, aligned pointers
+    const bool vec = y_ld % 4 == 0 && ref_ld % 4 == 0 && !misaligned;
+    if (use_mfma == 0) {   // VALU kernels: only the small-Cin first-layer kernel (conv_small.hip) provides statistics
+        if (vec && !ref_ld && ref_free_cin1_ok(Cout)) p.stat_blocks = tem_conv_fwd_cin1_stat_blocks(D, H, W, Cin, Cout, kd, kh, kw);
+        return p;
+    }
+    if (use_mfma < 1 || use_mfma > 7 || Cin % 16 || Cout % 32) return p;
+    // split-K launch of the z-reuse kernel: 32-bit offsets over x and its Cout-wide workspace
+    const bool sk_ok = vec && (int64_t)H * W * 8 * 4 * (x_ld > Cout ? x_ld : Cout) < (1ll << 31);
+    if (use_mfma == 1) {   // exact fp32: only the z-reuse kernel (direct or split-K) writes statistics
+        if (x_ld % 4 || misaligned) return p;   // -> the exact-fp32 patch kernel
+        const int64_t zrb = tem_conv_zr_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, 1, max_ld);
+        if (zrb >= 0) {
+            if (vec) p = FwdPlan{3, ref_ld ? 0 : zrb};
+        } else if (tem_conv_zr_splitk_ks(N, D, H, W, Cin, Cout, kd, kh, kw, 1) && sk_ok) {
+            const int64_t skb = tem_conv_zr_splitk_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, 1);
+            p = FwdPlan{4, skb > 0 ? skb : 0};
+        }
+        return p;
+    }
+    if (x_ld % (tem_call_st.x ? 8 : 4)) return p;   // a precondition of the split-precision launches: they raise
+    const int64_t zrb = tem_conv_zr_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld);
+    const int64_t ppb = zrb >= 0 ? -1 : tem_conv_pp_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld);
+    if (zrb >= 0 || ppb >= 0) {
+        if (vec)
+            p = FwdPlan{zrb >= 0 ? 3 : tem_conv_pp_tiles(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld),
+                        ref_ld ? 0 : (zrb >= 0 ? zrb : ppb)};
+        return p;
+    }
+    if (tem_conv_zr_splitk_ks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)) {
+        if (sk_ok) {
+            const int64_t skb = tem_conv_zr_splitk_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma);
+            p = FwdPlan{4, skb > 0 ? skb : 0};
+        }
+        return p;   // (declined: the patch kernel runs it, without statistics)
+    }
+    p.stat_blocks = tem_conv_fwd_patch_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw);
+    return p;
+}
+
+static int fwd_misaligned(const void* x, const void* scale, const void* shift, const void* w, const void* bias, const void* y,
+                          const void* ref) {
+    return (int)(((uintptr_t)x | (uintptr_t)scale | (uintptr_t)shift | (uintptr_t)w | (uintptr_t)bias | (uintptr_t)y |
+                  (uintptr_t)ref) % 16 != 0);
+}
+
+extern "C" int64_t tem_conv3d_fwd_stat_blocks_ld(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
+                                                 int use_mfma, int64_t x_ld, int64_t y_ld, int64_t ref_ld, int misaligned) {
+    TEM_MODE_SCOPE(use_mfma);
+    return fwd_plan(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld, misaligned).stat_blocks;
+}
+
+extern "C" int tem_conv3d_fwd_kernel_ld(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,
+                                        int64_t x_ld, int64_t y_ld, int64_t ref_ld, int misaligned) {
+    TEM_MODE_SCOPE(use_mfma);
+    return fwd_plan(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld, misaligned).family;
+}
+
+// the shape-only queries: dense, aligned x and y, no ref
 extern "C" int64_t tem_conv3d_fwd_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                                               int use_mfma) {
-    TEM_MODE_SCOPE(use_mfma);
-    if (use_mfma == 0)  // VALU kernels: only the small-Cin first-layer kernel (conv_small.hip) provides them
-        return (ref_free_cin1_ok(Cout)) ? tem_conv_fwd_cin1_stat_blocks(D, H, W, Cin, Cout, kd, kh, kw) : 0;
-    if (use_mfma == 1) {   // exact fp32: only the z-reuse kernel (direct or split-K) writes statistics
-        if (Cin % 16 || Cout % 32) return 0;
-        const int64_t zrb = tem_conv_zr_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, 1);
-        if (zrb >= 0) return zrb;
-        const int64_t skb = tem_conv_zr_splitk_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, 1);
-        return skb > 0 ? skb : 0;
-    }
-    if (use_mfma < 2 || use_mfma > 7) return 0;
-    return tem_conv_fwd_bf16x3_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma);
+    return tem_conv3d_fwd_stat_blocks_ld(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, Cin, Cout, 0, 0);
 }
 
 extern "C" int tem_conv3d_fwd_kernel(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
-    TEM_MODE_SCOPE(use_mfma);
-    if (use_mfma >= 2 && use_mfma <= 7 && Cin % 16 == 0 && Cout % 32 == 0) {
-        if (tem_conv_zr_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma) >= 0) return 3;
-        if (tem_conv_zr_splitk_ks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)) return 4;   // z-reuse kernel, split input channels
-        return tem_conv_pp_tiles(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma);
-    }
-    if (use_mfma == 1 && Cin % 16 == 0 && Cout % 32 == 0) {
-        if (tem_conv_zr_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, 1) >= 0) return 3;
-        if (tem_conv_zr_splitk_ks(N, D, H, W, Cin, Cout, kd, kh, kw, 1)) return 4;
-    }
-    return 0;
+    return tem_conv3d_fwd_kernel_ld(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, Cin, Cout, 0, 0);
 }
 
 extern "C" int tem_conv3d_fwd_stats(const float* x, int64_t x_ld, const float* scale, const float* shift,
@@ -404,8 +457,11 @@ extern "C" int tem_conv3d_fwd_stats(const float* x, int64_t x_ld, const float* s
                                     int64_t stat_blocks, tem_stream_t stream) {
     TEM_MODE_SCOPE(use_mfma);
     TEM_REQUIRE(stat_part, "tem_conv3d_fwd_stats: null statistics buffer");
-    TEM_REQUIRE(stat_blocks > 0 && stat_blocks == tem_conv3d_fwd_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma),
-                "tem_conv3d_fwd_stats: stat_blocks must be tem_conv3d_fwd_stat_blocks() of this launch (and > 0)");
+    const int64_t nblk = fwd_plan(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref ? ref_ld : 0,
+                                  fwd_misaligned(x, scale, shift, w_packed, bias, y, ref)).stat_blocks;
+    TEM_REQUIRE(stat_blocks > 0 && stat_blocks == nblk,
+                "tem_conv3d_fwd_stats: stat_blocks must be tem_conv3d_fwd_stat_blocks_ld() of this launch's layout (and > 0): "
+                "got %lld, the launch writes %lld", (long long)stat_blocks, (long long)nblk);
     return conv3d_fwd_impl(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
                            Cout, kd, kh, kw, act, use_mfma, stat_part, stream);
 }
@@ -800,8 +856,9 @@ extern "C" int tem_conv3d_fwd_gscaled(const float* x, int64_t x_ld, const float*
                                       int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh,
                                       int kw, tem_stream_t stream) {
     TEM_REQUIRE(in_amax, "tem_conv3d_fwd_gscaled: null in_amax");
-    TEM_REQUIRE(Cin % 16 == 0 && Cout % 32 == 0 && tem_conv3d_fwd_kernel(N, D, H, W, Cin, Cout, kd, kh, kw, 4) == 3,
-                "tem_conv3d_fwd_gscaled: only launches that tem_conv3d_fwd_kernel() reports as 3 (z-reuse kernel) take a "
+    TEM_REQUIRE(tem_conv3d_fwd_kernel_ld(N, D, H, W, Cin, Cout, kd, kh, kw, 4, x_ld, y_ld, ref ? ref_ld : 0,
+                                         fwd_misaligned(x, nullptr, nullptr, w_packed, nullptr, y, ref)) == 3,
+                "tem_conv3d_fwd_gscaled: only launches that tem_conv3d_fwd_kernel_ld() reports as 3 (z-reuse kernel) take a "
                 "device-side prescale");
     tem_zr_in_amax = in_amax;
     const int rc = conv3d_fwd_impl(x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H,
@@ -817,15 +874,16 @@ extern "C" int tem_conv3d_fwd_gscaled(const float* x, int64_t x_ld, const float*
 
 // Data gradient that lands behind a ReLU + norm: y = ref > 0 ? a*(conv) - m1 - (ref - mean)*m2r : 0 with coef[N][Cout][4] =
 // (a, m1, m2r, mean) from tem_norm_bwd_coef -- the epilogue of the z-reuse kernel replaces tem_norm_bwd_from_sums' pass over
-// g and ref.  Only for launches tem_conv3d_fwd_kernel() reports as 3.
+// g and ref.  Only for launches tem_conv3d_fwd_kernel_ld() reports as 3.
 extern "C" int tem_conv3d_fwd_refnorm(const float* x, int64_t x_ld, const float* w_packed, float* y, int64_t y_ld,
                                       const float* ref, int64_t ref_ld, const float* coef, void* ws, int64_t ws_bytes,
                                       int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,
                                       tem_stream_t stream) {
     TEM_MODE_SCOPE(use_mfma);
     TEM_REQUIRE(ref && coef, "tem_conv3d_fwd_refnorm: null ref / coef");
-    TEM_REQUIRE(Cin % 16 == 0 && Cout % 32 == 0 && tem_conv3d_fwd_kernel(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma) == 3,
-                "tem_conv3d_fwd_refnorm: only launches that tem_conv3d_fwd_kernel() reports as 3 (z-reuse kernel) apply a "
+    TEM_REQUIRE(fwd_plan(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld,
+                         fwd_misaligned(x, nullptr, nullptr, w_packed, coef, y, ref)).family == 3,
+                "tem_conv3d_fwd_refnorm: only launches that tem_conv3d_fwd_kernel_ld() reports as 3 (z-reuse kernel) apply a "
                 "norm backward in their epilogue");
     tem_zr_ref_coef = coef;
     const int rc = conv3d_fwd_impl(x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H,

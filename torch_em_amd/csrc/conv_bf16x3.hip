@@ -766,18 +766,11 @@ int tem_conv_fwd_bf16x3(const float* x, int64_t x_ld, const float* scale, const 
 
 // ---------------------------------------------------------------------------
 
-// number of per-sample statistic blocks (= patches) the fused-statistics forward writes, 0 when this shape cannot
-// produce them (split-K over the input channels, or no MFMA instantiation)
-int64_t tem_conv_fwd_bf16x3_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit) {
+// number of per-sample statistic blocks (= patches) the fused-statistics patch kernel writes, 0 when this shape cannot
+// produce them (split-K over the input channels, or no MFMA instantiation).  The team kernels answer for their own
+// launches first (tem_conv3d_fwd_stat_blocks_ld, conv.hip).
+int64_t tem_conv_fwd_patch_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
     if (Cin % 16 || Cout % 32) return 0;
-    const int64_t zrb = tem_conv_zr_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit);
-    if (zrb >= 0) return zrb;
-    const int64_t ppb = tem_conv_pp_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit);
-    if (ppb >= 0) return ppb;
-    if (tem_conv_zr_splitk_ks(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit)) {   // z-reuse kernel with split input channels: its epilogue
-        const int64_t skb = tem_conv_zr_splitk_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit);
-        return skb > 0 ? skb : 0;
-    }
     const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
     if (key != 7 && key != 3 && key != 0) return 0;
     const bool flat = (D == 1 && kd == 1);

@@ -1088,8 +1088,8 @@ static ZrGeom zr_geometry(int N, int D, int H, int W, int Cin, int Cout, int kd,
     return g;
 }
 
-int64_t tem_conv_zr_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit) {
-    const ZrGeom g = zr_geometry(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, 1);
+int64_t tem_conv_zr_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
+    const ZrGeom g = zr_geometry(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
     if (!g.ok) return -1;
     return (int64_t)g.nZ * g.nY * g.nX * 4;
 }
@@ -1145,7 +1145,7 @@ int tem_conv_zr_splitk_ks(int N, int D, int H, int W, int Cin, int Cout, int kd,
     const bool t16 = tem_call_st.x != 0;   // 16-bit storage: slices of whole 32-channel chunks
     if (t16 && (Cin % 32 || !(nsplit == 5 || nsplit == 7))) return 0;
     if (zr_geometry(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, 1).ok) return 0;
-    if (tem_conv_pp_tiles(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit)) return 0;
+    if (tem_conv_pp_tiles(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, 1)) return 0;
     static int ncu = 0;
     if (!ncu) {
         ncu = tem_device_cus();

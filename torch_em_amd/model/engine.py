@@ -188,9 +188,9 @@ class ConvSpec:
 _DGRAD16 = os.environ.get("TEM_DGRAD16", "0") == "1"
 
 
-def _dgrad16_ok(spec, g) -> bool:
+def _dgrad16_ok(spec, g, gx) -> bool:
     return _DGRAD16 and PRECISION == "split16" and not _FORCE_GENERIC and not _OVERLAP_WGRAD and spec.k == (3, 3, 3) and \
-        spec.cin % 32 == 0 and spec.cout % 32 == 0 and ops.conv_fwd_family(g, spec.k, spec.cout, spec.cin, 4) == 3 and \
+        spec.cin % 32 == 0 and spec.cout % 32 == 0 and ops.conv_fwd_family(g, spec.k, spec.cout, spec.cin, 4, y=gx) == 3 and \
         ops.conv_wgrad_gmax_ok(g, spec.k, spec.cin, spec.cout, 2)
 
 
@@ -485,8 +485,8 @@ def _dgrad(spec: ConvSpec, g, gx, ref=None, gmax=None, refnorm=None, grads=None,
     if sums_for is not None and _FUSE_DGRAD_SUMS and ref is None and gmax is None and refnorm is None and not _FORCE_GENERIC:
         x, stats = sums_for
         mode = spec.packed()["dgrad_mfma"]
-        if stats is not None and stats[4] == "sample" and ops.conv_fwd_family(g, spec.k, spec.cout, spec.cin, mode) == 4:
-            nblk = ops.conv_fwd_stat_blocks(g, spec.k, spec.cout, spec.cin, mode)
+        if stats is not None and stats[4] == "sample" and ops.conv_fwd_family(g, spec.k, spec.cout, spec.cin, mode, y=gx) == 4:
+            nblk = ops.conv_fwd_stat_blocks(g, spec.k, spec.cout, spec.cin, mode, y=gx)
             if nblk > 0:
                 part = torch.empty((x.shape[0], nblk, spec.cin, 2), dtype=torch.float32, device=x.device)
                 bp = ops.Byproducts(norm_sums=(x, spec.norm_args()[0], stats[0], stats[1], part))
@@ -612,8 +612,8 @@ def _planar_concat_ok(adt, c_up, enc_blk, dec_blk, shape, dev, floor) -> bool:
     N, D, H, W = shape
     ent = c1.packed()
     x64, g = ops.Probe(N, D, H, W, 64, adt), ops.Probe(N, D, H, W, c1.cout, adt)
-    return ops.conv_fwd_family(x64, c1.k, 64, c1.cout, ent["fwd_mfma"]) == 3 and \
-        ops.conv_fwd_family(g, c1.k, c1.cout, 64, ent["dgrad_mfma"]) == 3 and \
+    return ops.conv_fwd_family(x64, c1.k, 64, c1.cout, ent["fwd_mfma"], y=g) == 3 and \
+        ops.conv_fwd_family(g, c1.k, c1.cout, 64, ent["dgrad_mfma"], y=x64) == 3 and \
         ops.conv_wgrad_cs_ok(x64, c1.k, 64, c1.cout, N * D * H * W * 32)   # the stride ops.Planar gives its two planes
 
 
@@ -751,9 +751,9 @@ def _block_bwd(bs, gout, gin, grads: _Grads, defer_input_norm=False):
     ga1 = torch.empty_like(a1)
     affine1 = bs["s1"] is not None and c1.norm_args()[1] is not None
     if bs["s2"] is not None and _FUSE_NORM_BWD_DGRAD and bs["s2"][4] == "sample" and not _OVERLAP_WGRAD and \
-            not (gin is None and not affine1) and not _dgrad16_ok(c2, gout) and c2.conv.bias is not None and \
+            not (gin is None and not affine1) and not _dgrad16_ok(c2, gout, ga1) and c2.conv.bias is not None and \
             ops.conv_wgrad_sums_ok(a1, c2.k, c2.cin, c2.cout, c2.packed()["wgrad_mfma"]) and \
-            ops.conv_fwd_family(gout, c2.k, c2.cout, c2.cin, c2.packed()["dgrad_mfma"]) == 3:
+            ops.conv_fwd_family(gout, c2.k, c2.cout, c2.cin, c2.packed()["dgrad_mfma"], y=ga1, ref=a1) == 3:
         # The weight gradient runs FIRST and delivers the sums of norm2's backward (tem_conv3d_wgrad_sums) without the data
         # gradient existing yet; with the coefficients known, the data-gradient kernel applies norm2's backward and the
         # ReLU mask of a1 in its epilogue: no elementwise pass over ga1 and a1 (0.28 ms at 2 x 128^3 x 32)
@@ -761,7 +761,7 @@ def _block_bwd(bs, gout, gin, grads: _Grads, defer_input_norm=False):
         coef = _norm_bwd_inplace(c2, gout, a1, bs["s2"], True, grads, sums=sums, coef_only=True)
         _dgrad(c2, gout, ga1, ref=a1, refnorm=coef, grads=grads)
     elif bs["s2"] is not None:
-        if _dgrad16_ok(c2, gout):   # weight gradient first: it delivers max |gout| for the prescale of the data gradient
+        if _dgrad16_ok(c2, gout, ga1):   # weight gradient first: it delivers max |gout| for the prescale of the data gradient
             gm = grads.amax_slot()
             sums = _wgrad(c2, a1, gout, grads, bs["s2"], want_sums=True, gmax=gm)
             _dgrad(c2, gout, ga1, gmax=gm)
@@ -781,7 +781,7 @@ def _block_bwd(bs, gout, gin, grads: _Grads, defer_input_norm=False):
                                  shift=None if s1 is None else s1[3])
             return None
         _norm_bwd_inplace(c2, ga1, a1, bs["s2"], True, grads, sums=sums, amax=True)  # a1 is a ReLU output: mask fused
-    elif _dgrad16_ok(c2, gout):
+    elif _dgrad16_ok(c2, gout, ga1):
         gm = grads.amax_slot()
         _wgrad(c2, a1, gout, grads, bs["s2"], gmax=gm)
         _dgrad(c2, gout, ga1, ref=a1, gmax=gm)
@@ -794,7 +794,7 @@ def _block_bwd(bs, gout, gin, grads: _Grads, defer_input_norm=False):
     if gin is None:
         N, D, H, W, _ = xin.shape
         gin = ops.new_act(N, D, H, W, c1.cin, xin.device, xin.dtype)
-    if _dgrad16_ok(c1, ga1):
+    if _dgrad16_ok(c1, ga1, gin):
         gm = grads.amax_slot()
         sums = _wgrad(c1, xin, ga1, grads, bs["s1"], want_sums=bs["s1"] is not None, gmax=gm)
         _dgrad(c1, ga1, gin, gmax=gm)

@@ -107,7 +107,7 @@ def _act5(t: torch.Tensor) -> Tuple[int, int, int, int, int, int]:
     if isinstance(t, Planar):
         return (*t.shape, 32)
     if isinstance(t, Probe):
-        return (*t.shape, t.shape[4])
+        return (*t.shape, t.ld)
     if t.dim() != 5:
         raise ValueError(f"expected a 5-D NDHWC tensor, got shape {tuple(t.shape)}")
     if t.dtype not in _ST:
@@ -176,10 +176,11 @@ def _cs(t) -> int:
 
 
 class Probe:
-    """shape + storage type of a dense activation, for the query functions (conv_fwd_family, ..._ok) only"""
+    """shape + storage type (+ leading dimension: default dense) of an activation, for the query functions
+    (conv_fwd_family, ..._ok) only; a Probe counts as 16-byte aligned"""
 
-    def __init__(self, N, D, H, W, C, dtype):
-        self.shape, self.dtype = (N, D, H, W, C), dtype
+    def __init__(self, N, D, H, W, C, dtype, ld=None):
+        self.shape, self.dtype, self.ld = (N, D, H, W, C), dtype, C if ld is None else int(ld)
 
 
 # ---------------------------------------------------------------- layout ----
@@ -292,9 +293,11 @@ def conv_fwd(x, w_packed, bias, y, k, cin, cout, scale=None, shift=None, act=Non
     ws = _workspace(nws, x.device) if nws else None
     kind = None
     if PROFILER is not None:
-        pp = lib.tem_conv3d_fwd_kernel(N, D, H, W, cin, cout, k[0], k[1], k[2], mode) if mfma else 0
+        pp = lib.tem_conv3d_fwd_kernel_ld(N, D, H, W, cin, cout, k[0], k[1], k[2], mode, x_ld, y_ld, ref_ld,
+                                          _misaligned(x, w_packed, bias, y, ref, scale, shift)) if mfma else 0
         kind = _fwd_tag(mfma, k, cout, pp)
-    nblk = lib.tem_conv3d_fwd_stat_blocks(N, D, H, W, cin, cout, k[0], k[1], k[2], mode) if want_stats else 0
+    nblk = lib.tem_conv3d_fwd_stat_blocks_ld(N, D, H, W, cin, cout, k[0], k[1], k[2], mode, x_ld, y_ld, ref_ld,
+                                             _misaligned(x, w_packed, bias, y, ref, scale, shift)) if want_stats else 0
     ev0 = _prof_begin(x, kind)
     part = None
     if _cs(x) or _cs(y):
@@ -590,16 +593,33 @@ def conv_fwd_refnorm(x, w_packed, y, k, cin, cout, ref, coef, mfma, bp=None):
     return y
 
 
-def conv_fwd_stat_blocks(x, k, cin, cout, mfma) -> int:
-    """tem_conv3d_fwd_stat_blocks: statistics partial rows per sample this launch writes (0: it cannot)"""
-    N, D, H, W, _, _ = _act5(x)
-    return int(_lib.load().tem_conv3d_fwd_stat_blocks(N, D, H, W, cin, cout, k[0], k[1], k[2], _mode(mfma, x, x)))
+def _misaligned(*ts) -> int:
+    """1 when a tensor of a launch is off a 16-byte boundary (Probe / Planar / None count as aligned)"""
+    return int(any(isinstance(t, torch.Tensor) and t.data_ptr() % 16 for t in ts))
 
 
-def conv_fwd_family(x, k, cin, cout, mfma) -> int:
-    """tem_conv3d_fwd_kernel: 0 patch / other kernels, 1 / 2 ping-pong teams, 3 z-reuse teams, 4 z-reuse teams with split-K"""
+def _fwd_layout(x, cout, y, ref):
+    """(x_ld, y_ld, ref_ld, misaligned) of a launch that reads x and writes y (default: dense, aligned) with ref"""
+    x_ld = _act5(x)[5]
+    y_ld = _act5(y)[5] if y is not None else cout
+    ref_ld = _act5(ref)[5] if ref is not None else 0
+    return x_ld, y_ld, ref_ld, _misaligned(x, y, ref)
+
+
+def conv_fwd_stat_blocks(x, k, cin, cout, mfma, y=None, ref=None) -> int:
+    """tem_conv3d_fwd_stat_blocks_ld: statistics partial rows per sample the launch from x into y (None: a dense output)
+    writes (0: it cannot)"""
     N, D, H, W, _, _ = _act5(x)
-    return int(_lib.load().tem_conv3d_fwd_kernel(N, D, H, W, cin, cout, k[0], k[1], k[2], _mode(mfma, x, x)))
+    return int(_lib.load().tem_conv3d_fwd_stat_blocks_ld(N, D, H, W, cin, cout, k[0], k[1], k[2], _mode(mfma, x, x),
+                                                         *_fwd_layout(x, cout, y, ref)))
+
+
+def conv_fwd_family(x, k, cin, cout, mfma, y=None, ref=None) -> int:
+    """tem_conv3d_fwd_kernel_ld of the launch from x into y (None: a dense output) with ref: 0 patch / other kernels, 1 / 2
+    ping-pong teams, 3 z-reuse teams, 4 z-reuse teams with split-K"""
+    N, D, H, W, _, _ = _act5(x)
+    return int(_lib.load().tem_conv3d_fwd_kernel_ld(N, D, H, W, cin, cout, k[0], k[1], k[2], _mode(mfma, x, x),
+                                                    *_fwd_layout(x, cout, y, ref)))
 
 
 def _conv_wgrad(x, g, k, cin, cout, dw_out, db_out=None, scale=None, shift=None, mfma=False):
