@@ -647,6 +647,49 @@ int tem_affinity_target(const int64_t* labels, float* out, int D, int H, int W,
                         int add_binary_target, int add_mask, int include_ignore_transitions,
                         tem_stream_t stream);
 
+/* ---- distance-based instance segmentation (csrc/distance.hip) --------------------------
+ * PerObjectDistanceTransform (transform/label.py:454-633) on a batch of N samples [N][D][H][W] (2-D: D == 1).
+ * labels int64, ids / parent / flag / rank / keep / newid int32, all device memory; N*D*H*W < 2^31.  Per-object buffers
+ * are sized [N][V+1] from the voxel count V = D*H*W, so the object count never reaches the host.
+ * Labels (:597-606, bioimage_cpp segmentation.label / relabel_sequential): connected components of equal nonzero labels,
+ * face connectivity, numbered in first-occurrence order -- tem_pod_cc_roots (root flags), inclusive prefix sum of
+ * the flags over the whole batch (caller; rank, newid: the consumers subtract the previous sample's total),
+ * tem_pod_cc_assign.  Sequential relabel: values sorted per sample (caller),
+ * tem_pod_seq_flag, prefix sum, tem_pod_seq_assign (order: the sort's per-sample indices).
+ * min_size (:608-613): tem_pod_size_keep (cnt, keep: [N][V+1]), prefix sum of keep -> newid,
+ * tem_pod_size_apply. */
+int tem_pod_cc_roots(const int64_t* labels, int* parent, int* flag, int N, int D, int H, int W, tem_stream_t stream);
+int tem_pod_cc_assign(const int64_t* labels, const int* parent, const int* rank, int* ids, int N, int64_t V,
+                      tem_stream_t stream);
+int tem_pod_seq_flag(const int64_t* sorted, int* flag, int N, int64_t V, tem_stream_t stream);
+int tem_pod_seq_assign(const int64_t* sorted, const int64_t* order, const int* rank, int* ids, int N, int64_t V,
+                       tem_stream_t stream);
+int tem_pod_size_keep(const int* ids, int* cnt, int* keep, int N, int64_t V, int min_size, tem_stream_t stream);
+int tem_pod_size_apply(int* ids, const int* keep, const int* newid, int N, int64_t V, tem_stream_t stream);
+/* targets from ids 0..n (:615-633 and compute_normalized_object_distances :491-568): inner boundaries
+ * (skimage find_boundaries mode="inner", :617), one exact EDT of them over the whole sample (replaces the per-object
+ * bounding-box crops, equal on every object voxel: csrc/distance.hip), centers (regionprops centroid rounded, corrected
+ * to the boundary-distance arg-max when outside the object, :499-517), normalised channels (:527-566).
+ * sampling: HOST float[3] (z, y, x).  flags: 1 distances, 2 boundary_distances, 4 directed_distances, 8 foreground,
+ * 16 instances.  out float [N][C][D][H][W], channels [ids?][foreground?][distance?][directed x ndim?][boundary?].
+ * ws: tem_pod_ws bytes of device memory. */
+int64_t tem_pod_ws(int N, int64_t V, int ndim, int flags);
+int tem_pod_targets(const int* ids, float* out, int N, int D, int H, int W, int ndim, const float* sampling, int flags,
+                    float fill, void* ws, int64_t ws_bytes, tem_stream_t stream);
+/* DistanceLoss / DiceBasedDistanceLoss (loss/distance_based.py:7-68) on p, t: float [N][3][V] with strides
+ * (sn, sc, sv).  Channel 0: Dice (eps_fg); channels 1, 2: Dice (eps_dist) or, mse != 0, MSELoss(reduction="mean"),
+ * of p*m and t*m with m = t[:, 0] if mask_bg else 1.  sums: device double[12] (per channel: sum pm*tm, sum pm^2,
+ * sum tm^2, sum (pm-tm)^2), loss: device float[1], coef: device float[6] (d loss / d p_k = m (coef[k] tm + coef[3+k] pm)).
+ * Fixed-order double reduction: bitwise reproducible.  ws: tem_dist_loss_ws bytes.  gout: device float[1];
+ * gp is written with p's strides. */
+int64_t tem_dist_loss_ws(void);
+int tem_dist_loss_fwd(const float* p, int64_t p_sn, int64_t p_sc, int64_t p_sv, const float* t, int64_t t_sn,
+                      int64_t t_sc, int64_t t_sv, int N, int64_t V, int mask_bg, int mse, double eps_fg, double eps_dist,
+                      double* sums, float* loss, float* coef, void* ws, int64_t ws_bytes, tem_stream_t stream);
+int tem_dist_loss_grad(const float* p, int64_t p_sn, int64_t p_sc, int64_t p_sv, const float* t, int64_t t_sn,
+                       int64_t t_sc, int64_t t_sv, const float* coef, const float* gout, float* gp, int N, int64_t V,
+                       int mask_bg, tem_stream_t stream);
+
 /* ---- SPOCO / contrastive embedding losses --------------------
  * Embeddings: float [E][V] planes of ONE sample, voxel-fastest, channel stride cs (>= V); labels int64 [V],
  * consecutive ids 0..C-1.  E <= 32.  Per-slice Dice terms see the volume as [nz][V/nz] (nz = first spatial

@@ -119,6 +119,20 @@ SIGNATURES = {
     "tem_boundary_target_mode": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_vp]),
     "tem_affinity_target": (c_int, [c_vp, c_vp, c_int, c_int, c_int, ctypes.POINTER(c_int), c_int, c_int, c_i64,
                                     c_int, c_int, c_int, c_vp]),
+    "tem_pod_cc_roots": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "tem_pod_cc_assign": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_vp]),
+    "tem_pod_seq_flag": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp]),
+    "tem_pod_seq_assign": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_i64, c_vp]),
+    "tem_pod_size_keep": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_vp]),
+    "tem_pod_size_apply": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_vp]),
+    "tem_pod_ws": (c_i64, [c_int, c_i64, c_int, c_int]),
+    "tem_pod_targets": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_float), c_int, c_float,
+                                c_vp, c_i64, c_vp]),
+    "tem_dist_loss_ws": (c_i64, []),
+    "tem_dist_loss_fwd": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_int, c_int,
+                                  c_double, c_double, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "tem_dist_loss_grad": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_int, c_i64,
+                                   c_int, c_vp]),
     "tem_nchw_to_nhwc": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_vp]),
     "tem_nhwc_to_nchw": (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_i64, c_vp]),
     "tem_standardize": (c_int, [c_vp, c_vp, c_int, c_i64, c_float, c_vp, c_i64, c_vp]),

@@ -5,3 +5,4 @@ from .affinity_side_loss import AffinitySideLoss
 from .spoco_loss import (ExtendedContrastiveLoss, GaussianKernel, SPOCOConsistencyLoss, SPOCOLoss,
                          compute_cluster_means)
 from .contrastive import ContrastiveLoss
+from .distance_based import DiceBasedDistanceLoss, DistanceLoss

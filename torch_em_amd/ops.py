@@ -1205,3 +1205,104 @@ def standardize(x: torch.Tensor, eps: float = 1e-7) -> torch.Tensor:
     ws = _workspace(nws, x.device)
     _lib.check(lib.tem_standardize(_p(x), _p(y), N, L, eps, _p(ws), nws, _stream(x)), "tem_standardize")
     return y
+
+
+# ---- distance-based instance segmentation (csrc/distance.hip) ----
+POD_DIST, POD_BOUNDARY, POD_DIRECTED, POD_FOREGROUND, POD_INSTANCES = 1, 2, 4, 8, 16
+
+
+def _flat_cumsum(flag: torch.Tensor) -> torch.Tensor:
+    """inclusive prefix sum of int32 flags over the whole batch, on the device (no host synchronisation); the kernels
+    that read it subtract the previous sample's total.  One flat scan: torch's per-row scan of [N, V] is ~50x slower."""
+    return torch.cumsum(flag, dim=0, dtype=torch.int32)
+
+
+def pod_ids(labels: torch.Tensor, apply_label: bool, min_size: int) -> torch.Tensor:
+    """int64 [N, D, H, W] labels -> int32 object ids 1..n per sample (0 background): connected components in
+    first-occurrence order (apply_label) or ascending original ids; objects below min_size voxels dropped, the rest
+    renumbered in order (tem_pod_cc_* / tem_pod_seq_* / tem_pod_size_*)."""
+    _req_cuda(labels)
+    labels = labels.to(torch.int64).contiguous()
+    N, D, H, W = labels.shape
+    V = D * H * W
+    lib = _lib.load()
+    ids = torch.empty((N * V,), dtype=torch.int32, device=labels.device)
+    flag = torch.empty((N * V,), dtype=torch.int32, device=labels.device)
+    if apply_label:
+        parent = torch.empty((N * V,), dtype=torch.int32, device=labels.device)
+        _lib.check(lib.tem_pod_cc_roots(_p(labels), _p(parent), _p(flag), N, D, H, W, _stream(labels)), "tem_pod_cc_roots")
+        rank = _flat_cumsum(flag)
+        _lib.check(lib.tem_pod_cc_assign(_p(labels), _p(parent), _p(rank), _p(ids), N, V, _stream(labels)),
+                   "tem_pod_cc_assign")
+    else:
+        srt, order = torch.sort(labels.view(N, V), dim=1)
+        _lib.check(lib.tem_pod_seq_flag(_p(srt), _p(flag), N, V, _stream(labels)), "tem_pod_seq_flag")
+        rank = _flat_cumsum(flag)
+        _lib.check(lib.tem_pod_seq_assign(_p(srt), _p(order), _p(rank), _p(ids), N, V, _stream(labels)),
+                   "tem_pod_seq_assign")
+    if min_size > 0:
+        cnt = torch.empty((N * (V + 1),), dtype=torch.int32, device=labels.device)
+        keep = torch.empty_like(cnt)
+        _lib.check(lib.tem_pod_size_keep(_p(ids), _p(cnt), _p(keep), N, V, int(min_size), _stream(labels)),
+                   "tem_pod_size_keep")
+        newid = _flat_cumsum(keep)
+        _lib.check(lib.tem_pod_size_apply(_p(ids), _p(keep), _p(newid), N, V, _stream(labels)), "tem_pod_size_apply")
+    return ids.view(N, D, H, W)
+
+
+def pod_targets(ids: torch.Tensor, ndim: int, sampling, flags: int, fill: float) -> torch.Tensor:
+    """int32 ids [N, D, H, W] -> float32 [N, C, D, H, W] per-object distance targets (tem_pod_targets)."""
+    _req_cuda(ids)
+    N, D, H, W = ids.shape
+    V = D * H * W
+    nch = (1 if flags & POD_DIST else 0) + (ndim if flags & POD_DIRECTED else 0) + (1 if flags & POD_BOUNDARY else 0)
+    nc = nch + (1 if flags & POD_INSTANCES else 0) + (1 if flags & POD_FOREGROUND else 0)
+    out = torch.empty((N, nc, D, H, W), dtype=torch.float32, device=ids.device)
+    lib = _lib.load()
+    nws = lib.tem_pod_ws(N, V, ndim, flags)
+    ws = torch.empty((nws,), dtype=torch.uint8, device=ids.device)
+    samp = (ctypes.c_float * 3)(*[float(s) for s in sampling])
+    _lib.check(lib.tem_pod_targets(_p(ids), _p(out), N, D, H, W, ndim, samp, int(flags), float(fill), _p(ws), nws,
+                                   _stream(ids)), "tem_pod_targets")
+    return out
+
+
+def _ncv_or_contiguous(t):
+    s = _ncv_strides(t)
+    if s is None:
+        t = t.contiguous()
+        s = _ncv_strides(t)
+    return t, s
+
+
+def dist_loss_fwd(p, t, mask_bg: bool, mse: bool, eps_fg: float, eps_dist: float):
+    """-> (loss float[], coef float[6], p, t) of DistanceLoss / DiceBasedDistanceLoss on [N, 3, *spatial]
+    (tem_dist_loss_fwd: one pass over both tensors, fixed-order double sums)."""
+    _req_cuda(p, t)
+    p, ps = _ncv_or_contiguous(p)
+    t, ts = _ncv_or_contiguous(t)
+    N, C, V = ps[3:]
+    dev = p.device
+    sums = torch.empty((12,), dtype=torch.float64, device=dev)
+    loss = torch.empty((), dtype=torch.float32, device=dev)
+    coef = torch.empty((6,), dtype=torch.float32, device=dev)
+    lib = _lib.load()
+    nws = lib.tem_dist_loss_ws()
+    ws = _workspace(nws, dev)
+    _lib.check(lib.tem_dist_loss_fwd(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], N, V, int(mask_bg), int(mse),
+                                     float(eps_fg), float(eps_dist), _p(sums), _p(loss), _p(coef), _p(ws), nws,
+                                     _stream(p)), "tem_dist_loss_fwd")
+    return loss, coef, p, t
+
+
+def dist_loss_grad(p, t, coef, gout, mask_bg: bool) -> torch.Tensor:
+    """d loss / d p with p's strides (tem_dist_loss_grad); gout: device scalar"""
+    ps = _ncv_strides(p)
+    ts = _ncv_strides(t)
+    gp = torch.empty_like(p)
+    if _ncv_strides(gp)[:3] != ps[:3]:
+        raise RuntimeError("dist_loss_grad: the gradient does not share the prediction's strides")
+    N, C, V = ps[3:]
+    _lib.check(_lib.load().tem_dist_loss_grad(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], _p(coef), _p(gout),
+                                              _p(gp), N, V, int(mask_bg), _stream(p)), "tem_dist_loss_grad")
+    return gp

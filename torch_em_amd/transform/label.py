@@ -12,7 +12,7 @@ batch right after the H2D copy (`DefaultTrainer(target_transform=...)`), so the 
 (8 B/voxel) instead of float targets (up to 96 B/voxel for 12 affinity channels + masks).  CUDA tensors in ->
 CUDA tensors out; numpy in -> numpy out (via the device; main process only).
 """
-from typing import List, Optional
+from typing import List, Optional, Tuple
 
 import numpy as np
 import torch
@@ -80,6 +80,79 @@ class AffinityTransform:
                                   add_binary_target=self.add_binary_target, add_mask=self.add_mask,
                                   include_ignore_transitions=self.include_ignore_transitions)
         return out.cpu().numpy() if is_np else out
+
+
+class PerObjectDistanceTransform:
+    """Instance labels -> normalised per-object distance targets (reference `:454-633`), in HIP (csrc/distance.hip).
+
+    Same constructor arguments, defaults and `ValueError` as the reference, and its channel order
+    `[instances?] [foreground?] [distance?] [directed x ndim?] [boundary?]`.  Per object: the center is the rounded
+    centroid (round half to even), or -- where that voxel lies outside the object -- the arg-max of the distance to the
+    object's inner boundary (first in C order on ties); the reference ignores `correct_centers` and always corrects,
+    and so does this.  distance = |center - x| and directed = (center - x) per axis, both scaled by `sampling`;
+    boundary = b(center candidate) - b(x) with b the distance to the nearest inner-boundary voxel.  Each channel is
+    divided by its maximum |value| over the object + 1e-7; background gets `distance_fill_value`.
+
+    Inputs: 2-D or 3-D labels (numpy or torch), or a batch `[N, 1, *spatial]` (4-D: 2-D samples, 5-D: 3-D samples),
+    which returns `[N, C, *spatial]` from one launch per phase with samples independent -- the form to hand to
+    `DefaultTrainer(target_transform=...)`.  CUDA in -> CUDA out, float32 (the `instances` channel holds the ids as
+    float32: exact below 2^24 objects).  numpy in -> numpy out, float32, or float64 with `instances=True` (the
+    reference's concatenation of uint32 ids and float32 distances).  No host synchronisation: every buffer is sized
+    from the voxel count.
+
+    Conventions the reference takes from bioimage_cpp, which no fixture pins yet (assumptions, like row T1):
+    `apply_label` numbers face-connected components of equal nonzero labels in first-occurrence (raster) order; the
+    directed distances point from the voxel to the center (center - x, vigra's vector-distance sign); a sample that
+    one object fills entirely has no boundary voxel, and its boundary channel is 0.  Degenerate samples: no objects ->
+    fill value everywhere and foreground 0; a one-voxel object -> all distances 0.
+    """
+    eps = 1e-7
+
+    def __init__(self, distances: bool = True, boundary_distances: bool = True, directed_distances: bool = False,
+                 foreground: bool = True, instances: bool = False, apply_label: bool = True, correct_centers: bool = True,
+                 min_size: int = 0, distance_fill_value: float = 1.0, sampling: Optional[Tuple[float, ...]] = None):
+        if sum([distances, directed_distances, boundary_distances]) == 0:
+            raise ValueError("At least one of distances or directed distances has to be passed.")
+        self.distances = distances
+        self.boundary_distances = boundary_distances
+        self.directed_distances = directed_distances
+        self.foreground = foreground
+        self.instances = instances
+        self.apply_label = apply_label
+        self.correct_centers = correct_centers
+        self.min_size = min_size
+        self.distance_fill_value = distance_fill_value
+        self.sampling = sampling
+
+    def _flags(self) -> int:
+        return ((ops.POD_DIST if self.distances else 0) | (ops.POD_BOUNDARY if self.boundary_distances else 0)
+                | (ops.POD_DIRECTED if self.directed_distances else 0) | (ops.POD_FOREGROUND if self.foreground else 0)
+                | (ops.POD_INSTANCES if self.instances else 0))
+
+    def __call__(self, labels):
+        t, is_np = _to_device(labels, None)
+        if t.dim() in (2, 3):
+            batched, ndim, sp = False, t.dim(), tuple(t.shape)
+            t = t[None]
+        elif t.dim() in (4, 5) and t.shape[1] == 1:
+            batched, ndim, sp = True, t.dim() - 2, tuple(t.shape[2:])
+            t = t[:, 0]
+        else:
+            raise ValueError(f"expected 2-D or 3-D labels or a batch [N, 1, *spatial], got shape {tuple(t.shape)}")
+        N = t.shape[0]
+        t = t.reshape((N,) + (1,) * (3 - ndim) + sp)
+        sampling = (1.0,) * ndim if self.sampling is None else tuple(float(s) for s in self.sampling)
+        if len(sampling) != ndim:
+            raise ValueError(f"sampling {self.sampling} does not match the {ndim}-D labels")
+        ids = ops.pod_ids(t, self.apply_label, self.min_size)
+        out = ops.pod_targets(ids, ndim, (1.0,) * (3 - ndim) + sampling, self._flags(), self.distance_fill_value)
+        out = out.reshape((N, out.shape[1]) + sp)
+        if not batched:
+            out = out[0]
+        if is_np:
+            out = out.cpu().numpy()
+            return out.astype("float64") if self.instances else out
+        return out
 
 
 class BatchTargets:
