@@ -5,13 +5,17 @@ depth=4, InstanceNorm) on synthetic 2x1x128^3 batches per GPU (cfg 2; cfg 4 = th
 rank under data parallelism, weak scaling).
 
     python bench.py --gpus 1 --steps 10 --warmup 3
+    python bench.py --gpus 1 --steps 10 --warmup 3 --full
     python -m torch.distributed.run --nnodes=1 --nproc-per-node N --master-addr 127.0.0.1 \
         --master-port P bench.py --gpus N --steps K --warmup W
 
 Rank 0 prints ONE JSON line.  `roofline` is for the dominant kernel (the fp32-MFMA 3x3x3
 implicit-GEMM convolution), its duration measured live with HIP events on the launch stream
-inside the timed region; `cpu_baseline` times the oracle (oracle/unet_ref.py, a torch-CPU
-restatement pinned to the reference) on this box's host cores on a bounded sample.
+inside the timed region.  A plain run measures the headline and nothing else.  With --full
+(single GPU), the line also carries the runs of their own that follow the timed region: the
+same step in the other arithmetics (`modes`), the other BASELINE configs, the HIP-graph host
+overhead (see extra_measurements), and `cpu_baseline`, which times the oracle
+(oracle/unet_ref.py, a torch-CPU restatement pinned to the reference) on the host's cores.
 """
 import argparse
 import json
@@ -123,7 +127,7 @@ def cpu_baseline(max_threads):
 
 
 def extra_measurements(step, args, engine):
-    """Driver-visible numbers for what DESIGN.md claims besides the headline (rank 0, N = 1, after the timed region):
+    """Driver-visible numbers for what DESIGN.md claims besides the headline (--full; rank 0, N = 1, after the timed region):
     the SAME cfg-2 step with exact-fp32 MFMA arithmetic and with the opt-in mixed-precision arithmetic (3 steps each
     after 2 warm-ups; `step` is the benchmark's own closure, the packed weights follow the precision switch), and the
     training steps of the other BASELINE configs (scripts/bench_workloads.py).  None of these is `value`."""
@@ -309,9 +313,13 @@ def main():
     ap.add_argument("--batch", type=int, default=2, help="per-GPU batch (cfg 2: 2)")
     ap.add_argument("--size", type=int, default=128)
     ap.add_argument("--norm", default="InstanceNorm")
-    ap.add_argument("--no-cpu-baseline", action="store_true")
+    ap.add_argument("--full", action="store_true",
+                    help="after the headline, also measure what it does not need (single GPU): the extra keys and the "
+                         "CPU baseline")
+    ap.add_argument("--no-cpu-baseline", action="store_true", help="with --full: skip the CPU baseline")
     ap.add_argument("--no-extras", action="store_true",
-                    help="skip the extra keys (exact-fp32 / mixed-precision step times of cfg 2, cfg 1/3/5 step times)")
+                    help="with --full: skip the extra keys (exact-fp32 / mixed-precision step times of cfg 2, cfg 1/3/5 "
+                         "step times, HIP-graph host overhead)")
     ap.add_argument("--precision", default=None, choices=["fp32", "mixed", "split", "split16", "bf16x3", "amp", "amp_bf16"],
                     help="MFMA conv arithmetic (default: engine default = split16)")
     ap.add_argument("--kernel-table", default=None, help="write the per-kernel timing table to this file")
@@ -604,9 +612,9 @@ def main():
                 "flops_frac_fp32_mfma": STEP_GFLOP / ms / PEAK_FP32_MFMA_TFLOPS,
                 "hbm_frac_8TBs": (STEP_GB / (ms / 1e3)) / (PEAK_HBM_TBS * 1e3),
                 "note": "5700.8 GFLOP and 25.58 GB algorithmic per step (SURVEY.md 8d); fp32 arithmetic => MFMA-bound"}
-        if world == 1 and not args.no_extras:
+        if args.full and world == 1 and not args.no_extras:
             out.update(extra_measurements(step, args, engine))
-        if world == 1 and not args.no_cpu_baseline:
+        if args.full and world == 1 and not args.no_cpu_baseline:
             out["cpu_baseline"] = cpu_baseline(os.cpu_count() or 1)
         sys.stdout.flush()
         os.write(real_stdout, (json.dumps(out) + "\n").encode())

@@ -1,5 +1,5 @@
 """Step times of the BASELINE configs that are parity-test cases rather than bench lines (cfg 1, 3, 5), as functions:
-bench.py reports them as extra keys next to the cfg-2 headline; `python scripts/bench_workloads.py [1|3|5]` prints one.
+bench.py --full reports them as extra keys next to the cfg-2 headline; `python scripts/bench_workloads.py [1|3|5]` prints one.
 Every workload computes its label targets on the device inside the step (the loader ships int labels)."""
 import os
 import sys

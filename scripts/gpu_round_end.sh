@@ -31,6 +31,6 @@ for m in amp fp32; do
 done
 bash scripts/collect_stalls.sh $tag >> $O/collect.log 2>&1
 find $O -name "*.csv" -size +2M -delete
-timeout 1500 python bench.py --kernel-table $O/${tag}_bench_kernel_table.txt > $O/${tag}_bench.json 2> $O/bench.err
+timeout 1500 python bench.py --full --kernel-table $O/${tag}_bench_kernel_table.txt > $O/${tag}_bench.json 2> $O/bench.err
 timeout 2400 python -m pytest tests -q -m gpu 2>&1 | tail -15 > $O/${tag}_pytest_gpu.txt
 ls -la $O
