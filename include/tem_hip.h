@@ -285,7 +285,8 @@ int tem_conv3d_wgrad_gscaled(const float* x, int64_t x_ld, const float* scale, c
  * launch" through tem_arm_* / tem_disarm_* -- those entry points are gone) ------------------------------------------------
  * A caller that wants one fills the matching fields of a TemByproducts (the others zero), passes it to the *_ex entry point
  * and reads `delivered` afterwards: the call sets the bit of every by-product it wrote and leaves the others untouched (the
- * caller then runs the separate stage).  Never affects the values of the call's main outputs.
+ * caller then runs the separate stage).  Never affects the values of the call's main outputs.  The struct is read and
+ * `delivered` written only during that call, through the pointer the call was given: the library keeps no copy of it.
  *
  *  TEM_BP_OUT_AMAX   out_amax (device word, cleared by the caller) receives the bit pattern of max |y| of the tensor the call
  *                    writes (integer atomicMax; saves tem_absmax's pass) -- tem_conv3d_fwd_ex on the 1x1x1 streaming /

@@ -84,16 +84,17 @@ int main(int argc, char** argv) {
     const int64_t wsb = tem_conv_fwd_mfma_ws(N, D, H, W, Cin, Cout, 3, 3, 3);
     if (wsb) CK(hipMalloc(&ws, wsb));
     auto run = [&]() {
-        TemStScope sc_(st, st);
+        TemConvCall c;
+        c.stx = c.sty = st;
         float* stp = use_norm && !use_ref ? stat : nullptr;
         // variants >= 1: straight into THIS executable's copy of conv_pp.hip (calls inside libtem_hip.so bind locally)
-        if (variant == 2 && tem_conv_fwd_zr(x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, N, D,
+        if (variant == 2 && tem_conv_fwd_zr(c, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, N, D,
                                             H, W, Cin, Cout, 3, 3, 3, TEM_ACT_RELU, mode, stp, s) > 0)
             return;
-        if (variant == 1 && tem_conv_fwd_pp(x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, N, D,
+        if (variant == 1 && tem_conv_fwd_pp(c, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, N, D,
                                             H, W, Cin, Cout, 3, 3, 3, TEM_ACT_RELU, mode, stp, s))
             return;
-        int rc = tem_conv_fwd_bf16x3(x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, ws, wsb, N,
+        int rc = tem_conv_fwd_bf16x3(c, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, ws, wsb, N,
                                      D, H, W, Cin, Cout, 3, 3, 3, TEM_ACT_RELU, mode, stp, s);
         if (rc) { printf("launch failed: %s\n", tem_last_error()); exit(1); }
     };
@@ -104,8 +105,8 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(ya.data(), y, ya.size() * 4, hipMemcpyDeviceToHost));
         CK(hipMemset(y, 0xff, V * Cout * 4));
         tem_set_option("conv_fwd_variant", 0);
-        int rc = tem_conv_fwd_bf16x3(x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, ws, wsb, N,
-                                     D, H, W, Cin, Cout, 3, 3, 3, TEM_ACT_RELU, mode, nullptr, s);
+        int rc = tem_conv_fwd_bf16x3(TemConvCall{}, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, ws,
+                                     wsb, N, D, H, W, Cin, Cout, 3, 3, 3, TEM_ACT_RELU, mode, nullptr, s);
         if (rc) { printf("reference launch failed: %s\n", tem_last_error()); exit(1); }
         CK(hipDeviceSynchronize());
         tem_set_option("conv_fwd_variant", variant);

@@ -64,11 +64,11 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(x, x16.data(), x16.size() * 2, hipMemcpyHostToDevice)); CK(hipMemcpy(g, g16.data(), g16.size() * 2, hipMemcpyHostToDevice));
     }
     auto run = [&]() {
-        TemStScope sc_(st, st);
-        tem_wgrad_gscale_source = h16 == 3 ? amax : nullptr;
-        int rc = tem_conv_wgrad_bf16x3(x, Cin, sc, sf, g, Cout, dw, db, ws, wsb, N, D, H, W, Cin, Cout, 3, 3, 3, 1, h16, nullptr, nullptr,
+        TemConvCall c;
+        c.stx = c.sty = st;
+        c.g_amax_in = h16 == 3 ? amax : nullptr;
+        int rc = tem_conv_wgrad_bf16x3(c, x, Cin, sc, sf, g, Cout, dw, db, ws, wsb, N, D, H, W, Cin, Cout, 3, 3, 3, 1, h16, nullptr, nullptr,
                                        nullptr, nullptr, s);
-        tem_wgrad_gscale_source = nullptr;
         if (rc) { printf("launch failed: %s\n", tem_last_error()); exit(1); }
     };
     if (getenv("HARNESS_CHECK_ARITH")) {   // the arithmetic variant WG_ONE against bf16x3 (expected: the rounding of the variant)

@@ -74,3 +74,19 @@ def test_cfg2_layers_select_the_team_kernels():
                 # 4 rows of 256 / (Cout / 4) voxels)
                 vb = 4 * (256 // (b // 4))
                 assert blocks > 0 and (fam == 3 or blocks == (s ** 3 + vb - 1) // vb), (s, a, b, mode, blocks)
+
+
+def test_error_buffer_is_the_only_thread_local():
+    """Per-call state of the library travels in arguments (csrc/conv_internal.h: TemConvCall), never in globals that an entry
+    point installs for its launchers to find: the only `thread_local` under csrc/ is the buffer behind tem_last_error()."""
+    csrc = os.path.join(ROOT, "torch_em_amd", "csrc")
+    found = []
+    for name in sorted(os.listdir(csrc)):
+        if not name.endswith((".hip", ".h", ".inc", ".cpp", ".hpp")):
+            continue
+        text = open(os.path.join(csrc, name)).read()
+        text = re.sub(r"/\*.*?\*/", "", text, flags=re.S)
+        for no, line in enumerate(text.splitlines(), 1):
+            if re.search(r"\bthread_local\b", line.split("//")[0]):
+                found.append((name, no, line.strip()))
+    assert len(found) == 1 and found[0][0] == "capi.hip" and re.match(r"static thread_local char g_err\[\d+\]", found[0][2]), found

@@ -5,11 +5,7 @@
 #include <stdarg.h>
 #include <string.h>
 
-static thread_local char g_err[512] = "";
-
-// storage types of the call in flight on this thread (tem_act.h): set and restored by the entry point itself
-thread_local TemCallSt tem_call_st = {0, 0};
-thread_local TemCallCs tem_call_cs = {0, 0};
+static thread_local char g_err[512] = "";   // tem_last_error(): the only state the library keeps between calls
 
 void tem_set_error(const char* fmt, ...) {
     va_list ap;
@@ -76,27 +72,6 @@ extern "C" int tem_get_option(const char* name, int64_t* value) {
     return TEM_OK;
 }
 extern "C" int tem_version(void) { return 100; }
-
-// ---- by-products of the call in flight (include/tem_hip.h: TemByproducts) ----------------------------------------------------
-// The *_ex entry points install the struct their caller passed for the duration of the call (TemBpScope restores the previous
-// pointer on exit: nothing survives a call, and a call without by-products sees NULL); a launch site that can deliver one
-// takes it here, which records it in `delivered`.  Same standing as tem_call_st: plumbing between an entry point and the
-// launchers it reaches, not state of the C-ABI.
-thread_local TemByproducts* tem_call_bp = nullptr;
-unsigned* tem_take_output_amax() {
-    TemByproducts* bp = tem_call_bp;
-    if (!bp || !bp->out_amax || (bp->delivered & TEM_BP_OUT_AMAX)) return nullptr;
-    bp->delivered |= TEM_BP_OUT_AMAX;
-    return bp->out_amax;
-}
-bool tem_bp_wants(unsigned bit) {
-    const TemByproducts* bp = tem_call_bp;
-    if (!bp || (bp->delivered & bit)) return false;
-    return bit == TEM_BP_NORM_COEF ? bp->coef != nullptr : bit == TEM_BP_NORM_SUMS ? bp->sums_part != nullptr : bp->out_amax != nullptr;
-}
-void tem_bp_delivered(unsigned bit) {
-    if (tem_call_bp) tem_call_bp->delivered |= bit;
-}
 
 extern "C" int tem_device_cus(void) {
     int dev = 0;

@@ -7,13 +7,14 @@
 #include "conv_internal.h"
 #include "tem_act.h"
 
-// `use_mfma` of the conv entry points carries the storage types of the call in its high bits (tem_hip.h: TEM_MFMA_STX / _STY);
-// every entry point strips them first and keeps them in tem_call_st for the duration of the call
-// (a call that arrives WITHOUT storage bits from inside another entry point inherits that call's types)
-#define TEM_MODE_SCOPE(use_mfma)                                                                        \
-    TemStScope st_scope__(((use_mfma) >> 8) ? (((use_mfma) >> 8) & 15) : tem_call_st.x,                 \
-                          ((use_mfma) >> 8) ? (((use_mfma) >> 12) & 15) : tem_call_st.y);               \
-    use_mfma &= 0xff
+// `use_mfma` of the conv entry points carries the storage types of the call in its high bits (tem_hip.h: TEM_MFMA_STX / _STY):
+// every entry point splits it ONCE, into the arithmetic mode (left in use_mfma) and the call descriptor that goes down to the
+// launchers and dispatch queries (conv_internal.h: TemConvCall); the entry point adds what else its arguments carry
+static TemConvCall conv_call(int& use_mfma) {
+    const TemConvCall c = {(use_mfma >> 8) & 15, (use_mfma >> 12) & 15};
+    use_mfma &= 0xff;
+    return c;
+}
 
 // ---------------------------------------------------------------------------
 // weight packing
@@ -222,11 +223,11 @@ __global__ __launch_bounds__(256) void k_conv1x1_smallcout(const TX* __restrict_
 }
 
 template <int KD, int KH, int KW>
-static void launch_fwd_generic(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
+static void launch_fwd_generic(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
                                const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D,
                                int H, int W, int Cin, int Cout, int act, hipStream_t s) {
     int64_t items = (int64_t)N * D * H * W * Cout;
-    TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TY, (void)0,
+    TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, (void)0,
                    hipLaunchKernelGGL((k_conv_fwd_generic<KD, KH, KW, TX, TY>), dim3(tem_grid_1d(items, 256, 256 * 16)), dim3(256), 0, s,
                                       (const TX*)x, x_ld, scale, shift, w, bias, (TY*)y, y_ld, (const TY*)ref, ref_ld, N, D, H, W, Cin,
                                       Cout, act));
@@ -249,37 +250,37 @@ static void launch_fwd_generic(const float* x, int64_t x_ld, const float* scale,
 
 extern "C" int64_t tem_conv3d_fwd_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                                      int use_mfma) {
-    TEM_MODE_SCOPE(use_mfma);
+    const TemConvCall c = conv_call(use_mfma);
     if (!use_mfma || Cin % 16 || Cout % 32) return 0;
     int64_t ws = tem_conv_fwd_mfma_ws(N, D, H, W, Cin, Cout, kd, kh, kw);
     if (use_mfma >= 1 && use_mfma <= 7) {   // the z-reuse kernel's split-K launch may want more slices than the patch kernel's
-        const int64_t zk = (int64_t)tem_conv_zr_splitk_ks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma) * N * D * H * W * Cout * 4;
+        const int64_t zk = (int64_t)tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma) * N * D * H * W * Cout * 4;
         if (zk > ws) ws = zk;
     }
     return ws;
 }
 
-static int conv3d_fwd_impl(const float* x, int64_t x_ld, const float* scale, const float* shift,
+static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift,
                            const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref,
                            int64_t ref_ld, void* ws, int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout,
                            int kd, int kh, int kw, int act, int use_mfma, float* stat, tem_stream_t stream) {
     TEM_REQUIRE(x && w_packed && y, "tem_conv3d_fwd: null pointer");
-    TEM_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && x_ld >= (tem_call_cs.x ? 32 : Cin) &&
-                    y_ld >= (tem_call_cs.y ? 32 : Cout),
+    TEM_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && x_ld >= (c.x_cs ? 32 : Cin) &&
+                    y_ld >= (c.y_cs ? 32 : Cout),
                 "tem_conv3d_fwd: bad shape");
     TEM_REQUIRE((kd == 1 || kd == 3) && (kh == 1 || kh == 3) && (kw == 1 || kw == 3),
                 "tem_conv3d_fwd: kernel size (%d,%d,%d) not supported (1 or 3 per axis)", kd, kh, kw);
     TEM_REQUIRE((scale == nullptr) == (shift == nullptr), "tem_conv3d_fwd: scale and shift must both be given");
     TEM_REQUIRE(act >= 0 && act <= 2, "tem_conv3d_fwd: Invalid activation: %d", act);
     TEM_REQUIRE(!ref || ref_ld >= Cout, "tem_conv3d_fwd: bad ref_ld");
-    const int stx = tem_call_st.x, sty = tem_call_st.y;
+    const int stx = c.stx, sty = c.sty;
     TEM_REQUIRE(stx >= 0 && stx <= 2 && sty >= 0 && sty <= 2 && (stx == 0 || sty == 0 || stx == sty),
                 "tem_conv3d_fwd: unsupported storage types (x %d, y %d)", stx, sty);
     TEM_REQUIRE(!(stx || sty) || use_mfma != 1, "tem_conv3d_fwd: the exact-fp32 MFMA kernels take fp32 tensors only");
     hipStream_t s = (hipStream_t)stream;
-    TEM_REQUIRE(!(tem_call_cs.x || tem_call_cs.y) || use_mfma == 5 || use_mfma == 7, "tem_conv3d_fwd_ex: chunk strides need use_mfma 5 / 7");
+    TEM_REQUIRE(!(c.x_cs || c.y_cs) || use_mfma == 5 || use_mfma == 7, "tem_conv3d_fwd_ex: chunk strides need use_mfma 5 / 7");
     if (use_mfma >= 2 && use_mfma <= 7) {
-        int rc = tem_conv_fwd_bf16x3(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H,
+        int rc = tem_conv_fwd_bf16x3(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H,
                                      W, Cin, Cout, kd, kh, kw, act, use_mfma, stat, s);
         if (rc != TEM_OK) return rc;
         TEM_CHECK_LAUNCH("tem_conv3d_fwd(bf16x3)");
@@ -289,10 +290,10 @@ static int conv3d_fwd_impl(const float* x, int64_t x_ld, const float* scale, con
         (!scale || (((uintptr_t)scale % 16 == 0) && ((uintptr_t)shift % 16 == 0)))) {
         // exact fp32 on the z-reuse team kernel (k_conv_zr<..., X32>, round 6): the levels with enough units directly, the
         // 16^3 / 8^3 levels with split input channels; other shapes stay with k_conv_fwd_mfma[_p] below
-        const int zr = tem_conv_fwd_zr(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw,
+        const int zr = tem_conv_fwd_zr(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw,
                                        act, 1, stat, s);
         if (zr < 0) return TEM_EINVAL;
-        if (!zr && tem_conv_fwd_zr_splitk(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
+        if (!zr && tem_conv_fwd_zr_splitk(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
                                           Cout, kd, kh, kw, act, 1, stat, s)) {
             TEM_CHECK_LAUNCH("tem_conv3d_fwd(fp32, z-reuse split-K)");
             return TEM_OK;
@@ -311,24 +312,24 @@ static int conv3d_fwd_impl(const float* x, int64_t x_ld, const float* scale, con
         return TEM_OK;
     }
     const int64_t NV = (int64_t)N * D * H * W;
-    if (tem_conv_fwd_cin1(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, N, D, H, W, Cin, Cout, kd, kh, kw, act,
+    if (tem_conv_fwd_cin1(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, N, D, H, W, Cin, Cout, kd, kh, kw, act,
                           stat, s)) {
         TEM_CHECK_LAUNCH("tem_conv3d_fwd(cin1)");
         return TEM_OK;
     }
     TEM_REQUIRE(!stat, "tem_conv3d_fwd_stats: this launch cannot write statistics (tem_conv3d_fwd_stat_blocks() == 0)");
-    if (tem_conv_fwd_cout1(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, N, D, H, W, Cin, Cout, kd, kh, kw, act,
+    if (tem_conv_fwd_cout1(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, N, D, H, W, Cin, Cout, kd, kh, kw, act,
                            s)) {
         TEM_CHECK_LAUNCH("tem_conv3d_fwd(cout1)");
         return TEM_OK;
     }
     if (kd == 1 && kh == 1 && kw == 1 &&
-        tem_conv1x1_proj(x, x_ld, scale, w_packed, bias, y, y_ld, ref, NV, Cin, Cout, act, s)) {
+        tem_conv1x1_proj(c, x, x_ld, scale, w_packed, bias, y, y_ld, ref, NV, Cin, Cout, act, s)) {
         TEM_CHECK_LAUNCH("tem_conv3d_fwd(proj)");
         return TEM_OK;
     }
     if (kd == 1 && kh == 1 && kw == 1 &&
-        tem_conv1x1_expand(x, x_ld, scale, w_packed, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s)) {
+        tem_conv1x1_expand(c, x, x_ld, scale, w_packed, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s)) {
         TEM_CHECK_LAUNCH("tem_conv3d_fwd(expand)");
         return TEM_OK;
     }
@@ -337,7 +338,7 @@ static int conv3d_fwd_impl(const float* x, int64_t x_ld, const float* scale, con
         dim3 grid(tem_grid_1d(NV, 256, 256 * 16));
 #define SC(CO)                                                                                                   \
     case CO:                                                                                                     \
-        TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TY, (void)0,                                            \
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, (void)0,                                            \
                        hipLaunchKernelGGL((k_conv1x1_smallcout<CO, TX, TY>), grid, dim3(256), 0, s, (const TX*)x, x_ld, scale, shift, \
                                           w_packed, bias, (TY*)y, y_ld, (const TY*)ref, ref_ld, (int64_t)D * H * W, NV, Cin, act)); \
         break;
@@ -349,7 +350,7 @@ static int conv3d_fwd_impl(const float* x, int64_t x_ld, const float* scale, con
         return TEM_OK;
     }
 #define CALL(A, B, C) \
-    launch_fwd_generic<A, B, C>(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, s)
+    launch_fwd_generic<A, B, C>(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, s)
     DISPATCH_K(kd, kh, kw, CALL);
 #undef CALL
     TEM_CHECK_LAUNCH("tem_conv3d_fwd(generic)");
@@ -360,8 +361,8 @@ extern "C" int tem_conv3d_fwd(const float* x, int64_t x_ld, const float* scale, 
                               const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref,
                               int64_t ref_ld, void* ws, int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout,
                               int kd, int kh, int kw, int act, int use_mfma, tem_stream_t stream) {
-    TEM_MODE_SCOPE(use_mfma);
-    return conv3d_fwd_impl(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
+    const TemConvCall c = conv_call(use_mfma);
+    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
                            Cout, kd, kh, kw, act, use_mfma, nullptr, stream);
 }
 
@@ -377,7 +378,7 @@ struct FwdPlan {
     int family;
     int64_t stat_blocks;
 };
-static FwdPlan fwd_plan(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, int64_t x_ld,
+static FwdPlan fwd_plan(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, int64_t x_ld,
                         int64_t y_ld, int64_t ref_ld, int misaligned) {
     FwdPlan p = {0, 0};
     int64_t max_ld = x_ld > y_ld ? x_ld : y_ld;
@@ -393,27 +394,27 @@ static FwdPlan fwd_plan(int N, int D, int H, int W, int Cin, int Cout, int kd, i
     const bool sk_ok = vec && (int64_t)H * W * 8 * 4 * (x_ld > Cout ? x_ld : Cout) < (1ll << 31);
     if (use_mfma == 1) {   // exact fp32: only the z-reuse kernel (direct or split-K) writes statistics
         if (x_ld % 4 || misaligned) return p;   // -> the exact-fp32 patch kernel
-        const int64_t zrb = tem_conv_zr_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, 1, max_ld);
+        const int64_t zrb = tem_conv_zr_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, 1, max_ld);
         if (zrb >= 0) {
             if (vec) p = FwdPlan{3, ref_ld ? 0 : zrb};
-        } else if (tem_conv_zr_splitk_ks(N, D, H, W, Cin, Cout, kd, kh, kw, 1) && sk_ok) {
-            const int64_t skb = tem_conv_zr_splitk_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, 1);
+        } else if (tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, 1) && sk_ok) {
+            const int64_t skb = tem_conv_zr_splitk_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, 1);
             p = FwdPlan{4, skb > 0 ? skb : 0};
         }
         return p;
     }
-    if (x_ld % (tem_call_st.x ? 8 : 4)) return p;   // a precondition of the split-precision launches: they raise
-    const int64_t zrb = tem_conv_zr_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld);
-    const int64_t ppb = zrb >= 0 ? -1 : tem_conv_pp_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld);
+    if (x_ld % (c.stx ? 8 : 4)) return p;   // a precondition of the split-precision launches: they raise
+    const int64_t zrb = tem_conv_zr_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld);
+    const int64_t ppb = zrb >= 0 ? -1 : tem_conv_pp_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld);
     if (zrb >= 0 || ppb >= 0) {
         if (vec)
-            p = FwdPlan{zrb >= 0 ? 3 : tem_conv_pp_tiles(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld),
+            p = FwdPlan{zrb >= 0 ? 3 : tem_conv_pp_tiles(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld),
                         ref_ld ? 0 : (zrb >= 0 ? zrb : ppb)};
         return p;
     }
-    if (tem_conv_zr_splitk_ks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)) {
+    if (tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)) {
         if (sk_ok) {
-            const int64_t skb = tem_conv_zr_splitk_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma);
+            const int64_t skb = tem_conv_zr_splitk_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma);
             p = FwdPlan{4, skb > 0 ? skb : 0};
         }
         return p;   // (declined: the patch kernel runs it, without statistics)
@@ -430,14 +431,14 @@ static int fwd_misaligned(const void* x, const void* scale, const void* shift, c
 
 extern "C" int64_t tem_conv3d_fwd_stat_blocks_ld(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                                                  int use_mfma, int64_t x_ld, int64_t y_ld, int64_t ref_ld, int misaligned) {
-    TEM_MODE_SCOPE(use_mfma);
-    return fwd_plan(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld, misaligned).stat_blocks;
+    const TemConvCall c = conv_call(use_mfma);
+    return fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld, misaligned).stat_blocks;
 }
 
 extern "C" int tem_conv3d_fwd_kernel_ld(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,
                                         int64_t x_ld, int64_t y_ld, int64_t ref_ld, int misaligned) {
-    TEM_MODE_SCOPE(use_mfma);
-    return fwd_plan(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld, misaligned).family;
+    const TemConvCall c = conv_call(use_mfma);
+    return fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld, misaligned).family;
 }
 
 // the shape-only queries: dense, aligned x and y, no ref
@@ -450,19 +451,29 @@ extern "C" int tem_conv3d_fwd_kernel(int N, int D, int H, int W, int Cin, int Co
     return tem_conv3d_fwd_kernel_ld(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, Cin, Cout, 0, 0);
 }
 
+// the argument checks of tem_conv3d_fwd_stats (also a tem_conv3d_fwd_ex with stat_part)
+static int fwd_stats_check(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                           const float* w_packed, const float* bias, const float* y, int64_t y_ld, const float* ref, int64_t ref_ld,
+                           int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,
+                           const float* stat_part, int64_t stat_blocks) {
+    TEM_REQUIRE(stat_part, "tem_conv3d_fwd_stats: null statistics buffer");
+    const int64_t nblk = fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref ? ref_ld : 0,
+                                  fwd_misaligned(x, scale, shift, w_packed, bias, y, ref)).stat_blocks;
+    TEM_REQUIRE(stat_blocks > 0 && stat_blocks == nblk,
+                "tem_conv3d_fwd_stats: stat_blocks must be tem_conv3d_fwd_stat_blocks_ld() of this launch's layout (and > 0): "
+                "got %lld, the launch writes %lld", (long long)stat_blocks, (long long)nblk);
+    return TEM_OK;
+}
+
 extern "C" int tem_conv3d_fwd_stats(const float* x, int64_t x_ld, const float* scale, const float* shift,
                                     const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref,
                                     int64_t ref_ld, void* ws, int64_t ws_bytes, int N, int D, int H, int W, int Cin,
                                     int Cout, int kd, int kh, int kw, int act, int use_mfma, float* stat_part,
                                     int64_t stat_blocks, tem_stream_t stream) {
-    TEM_MODE_SCOPE(use_mfma);
-    TEM_REQUIRE(stat_part, "tem_conv3d_fwd_stats: null statistics buffer");
-    const int64_t nblk = fwd_plan(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref ? ref_ld : 0,
-                                  fwd_misaligned(x, scale, shift, w_packed, bias, y, ref)).stat_blocks;
-    TEM_REQUIRE(stat_blocks > 0 && stat_blocks == nblk,
-                "tem_conv3d_fwd_stats: stat_blocks must be tem_conv3d_fwd_stat_blocks_ld() of this launch's layout (and > 0): "
-                "got %lld, the launch writes %lld", (long long)stat_blocks, (long long)nblk);
-    return conv3d_fwd_impl(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
+    const TemConvCall c = conv_call(use_mfma);
+    TEM_TRY(fwd_stats_check(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma,
+                            stat_part, stat_blocks));
+    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
                            Cout, kd, kh, kw, act, use_mfma, stat_part, stream);
 }
 
@@ -599,7 +610,7 @@ static WgradGenericPlan wgrad_generic_plan(int64_t NV, int Cin, int Cout, int nt
 
 extern "C" int64_t tem_conv3d_wgrad_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                                        int use_mfma) {
-    TEM_MODE_SCOPE(use_mfma);
+    use_mfma &= 0xff;   // (the storage types do not change the workspace)
     int64_t NV = (int64_t)N * D * H * W;
     int ntaps = kd * kh * kw;
     WgradGenericPlan p = wgrad_generic_plan(NV, Cin, Cout, ntaps);
@@ -624,28 +635,28 @@ extern "C" int64_t tem_conv3d_wgrad_ws(int N, int D, int H, int W, int Cin, int 
 }
 
 template <int KD, int KH, int KW>
-static void launch_wgrad_generic(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
+static void launch_wgrad_generic(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
                                  int64_t g_ld, int N, int D, int H, int W, int Cin, int Cout,
                                  const WgradGenericPlan& p, float* part, hipStream_t s) {
     constexpr int NT = KD * KH * KW;
     size_t lds = (size_t)NT * p.rows * p.npairs_blk * sizeof(float);
-    TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TG, (void)0,
+    TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, (void)0,
                    hipLaunchKernelGGL((k_conv_wgrad_generic<KD, KH, KW, TX, TG>), dim3(p.nchunks, p.npb), dim3(256), lds, s, (const TX*)x,
                                       x_ld, scale, shift, (const TG*)g, g_ld, N, D, H, W, Cin, Cout, p.npairs_blk, p.rows, p.vper, part));
 }
 
-static int conv3d_wgrad_impl(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
+static int conv3d_wgrad_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
                              int64_t g_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H,
                              int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, int sd_layout,
                              const float* w_sd, const float* gamma, const float* beta, float* norm_sums,
                              const float* gnx, int64_t gnx_ld, const float* gcoef, tem_stream_t stream) {
     TEM_REQUIRE(x && g && dw && ws, "tem_conv3d_wgrad: null pointer");
-    TEM_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && x_ld >= (tem_call_cs.x ? 32 : Cin) && g_ld >= Cout,
+    TEM_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && x_ld >= (c.x_cs ? 32 : Cin) && g_ld >= Cout,
                 "tem_conv3d_wgrad: bad shape");
     TEM_REQUIRE((kd == 1 || kd == 3) && (kh == 1 || kh == 3) && (kw == 1 || kw == 3),
                 "tem_conv3d_wgrad: kernel size (%d,%d,%d) not supported (1 or 3 per axis)", kd, kh, kw);
     TEM_REQUIRE((scale == nullptr) == (shift == nullptr), "tem_conv3d_wgrad: scale and shift must both be given");
-    const int stx = tem_call_st.x, sty = tem_call_st.y;
+    const int stx = c.stx, sty = c.sty;
     TEM_REQUIRE(stx >= 0 && stx <= 2 && sty >= 0 && sty <= 2 && (stx == 0 || sty == 0 || stx == sty),
                 "tem_conv3d_wgrad: unsupported storage types (x %d, g %d)", stx, sty);
     TEM_REQUIRE(!(stx || sty) || !(use_mfma == 1 || use_mfma == 3 || use_mfma == 4 || use_mfma == 6),
@@ -661,11 +672,11 @@ static int conv3d_wgrad_impl(const float* x, int64_t x_ld, const float* scale, c
     float* dbpart = (float*)ws;
     float* rest = dbpart + tem_align_up(p.db_floats, 64);
     TEM_REQUIRE(!gcoef || !use_mfma, "tem_conv3d_wgrad_gnorm: use_mfma must be 0");
-    TEM_REQUIRE(!tem_call_cs.x || use_mfma == 5 || use_mfma == 7, "tem_conv3d_wgrad_ex: a chunk stride needs use_mfma 5 / 7");
+    TEM_REQUIRE(!c.x_cs || use_mfma == 5 || use_mfma == 7, "tem_conv3d_wgrad_ex: a chunk stride needs use_mfma 5 / 7");
     if (use_mfma == 2 || use_mfma == 5 || use_mfma == 7 || use_mfma == 8) {
         // 5: single fp16 product in the z-sliding kernel (autocast-equivalent); the other shapes keep bf16x3
         // 8: fp16 2x1 (tem_conv3d_wgrad_gscaled; z-sliding kernel only)
-        int rc = tem_conv_wgrad_bf16x3(x, x_ld, scale, shift, g, g_ld, dw, db, rest,
+        int rc = tem_conv_wgrad_bf16x3(c, x, x_ld, scale, shift, g, g_ld, dw, db, rest,
                                        ws_bytes - (int64_t)((char*)rest - (char*)ws), N, D, H, W, Cin, Cout, kd, kh, kw,
                                        sd_layout, use_mfma == 5 ? 1 : (use_mfma == 7 ? 2 : (use_mfma == 8 ? 3 : 0)), w_sd, gamma,
                                        beta, norm_sums, s);
@@ -677,7 +688,7 @@ static int conv3d_wgrad_impl(const float* x, int64_t x_ld, const float* scale, c
         ((uintptr_t)x % 16 == 0) && ((uintptr_t)g % 16 == 0)) {
         // exact fp32 on the z-sliding staging-team kernel (round 4): fp32 records in LDS, v_mfma_f32_32x32x2_f32; the slab
         // merge delivers the norm sums as in the split modes (round 6: the merge does not care which arithmetic filled the slabs)
-        int rc = tem_conv_wgrad_bf16x3(x, x_ld, scale, shift, g, g_ld, dw, db, rest,
+        int rc = tem_conv_wgrad_bf16x3(c, x, x_ld, scale, shift, g, g_ld, dw, db, rest,
                                        ws_bytes - (int64_t)((char*)rest - (char*)ws), N, D, H, W, Cin, Cout, kd, kh, kw,
                                        sd_layout, 4, w_sd, gamma, beta, norm_sums, s);
         if (rc != TEM_OK) return rc;
@@ -693,13 +704,13 @@ static int conv3d_wgrad_impl(const float* x, int64_t x_ld, const float* scale, c
         TEM_CHECK_LAUNCH("tem_conv3d_wgrad(mfma)");
         return TEM_OK;
     }
-    if (tem_conv_wgrad_cin1(x, x_ld, scale, shift, g, g_ld, dw, db, rest, N, D, H, W, Cin, Cout, kd, kh, kw, sd_layout,
+    if (tem_conv_wgrad_cin1(c, x, x_ld, scale, shift, g, g_ld, dw, db, rest, N, D, H, W, Cin, Cout, kd, kh, kw, sd_layout,
                             gnx, gnx_ld, gcoef, s)) {
         TEM_CHECK_LAUNCH("tem_conv3d_wgrad(cin1)");
         return TEM_OK;
     }
     TEM_REQUIRE(!gcoef, "tem_conv3d_wgrad_gnorm: only the small-Cin first-layer kernel applies a norm backward to g");
-    if (ntaps == 1 && tem_conv1x1_proj_wgrad(x, x_ld, scale, g, g_ld, dw, db, rest, NV, Cin, Cout, sd_layout, s)) {
+    if (ntaps == 1 && tem_conv1x1_proj_wgrad(c, x, x_ld, scale, g, g_ld, dw, db, rest, NV, Cin, Cout, sd_layout, s)) {
         TEM_CHECK_LAUNCH("tem_conv3d_wgrad(proj)");
         return TEM_OK;
     }
@@ -707,12 +718,12 @@ static int conv3d_wgrad_impl(const float* x, int64_t x_ld, const float* scale, c
         int Cb = Cout < 256 ? Cout : 256;
         int rows = 256 / Cb;
         int64_t vper = tem_cdiv(NV, p.db_chunks);
-        TEM_ST_SWITCH(tem_call_st.y, TG,
+        TEM_ST_SWITCH(c.sty, TG,
                       hipLaunchKernelGGL(k_colsum_partial<TG>, dim3(p.db_chunks), dim3(256), (size_t)rows * Cb * sizeof(float), s,
                                          (const TG*)g, g_ld, NV, Cout, rows, vper, dbpart));
         tem_reduce_slabs(dbpart, p.db_chunks, (int64_t)Cout, (int64_t)Cout, db, s);
     }
-#define CALL(A, B, C) launch_wgrad_generic<A, B, C>(x, x_ld, scale, shift, g, g_ld, N, D, H, W, Cin, Cout, p, rest, s)
+#define CALL(A, B, C) launch_wgrad_generic<A, B, C>(c, x, x_ld, scale, shift, g, g_ld, N, D, H, W, Cin, Cout, p, rest, s)
     DISPATCH_K(kd, kh, kw, CALL);
 #undef CALL
     int64_t n = (int64_t)ntaps * Cin * Cout;
@@ -725,8 +736,8 @@ extern "C" int tem_conv3d_wgrad(const float* x, int64_t x_ld, const float* scale
                                 int64_t g_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H,
                                 int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, int sd_layout,
                                 tem_stream_t stream) {
-    TEM_MODE_SCOPE(use_mfma);
-    return conv3d_wgrad_impl(x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw,
+    const TemConvCall c = conv_call(use_mfma);
+    return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw,
                              use_mfma, sd_layout, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, stream);
 }
 
@@ -736,19 +747,24 @@ extern "C" int tem_conv3d_wgrad(const float* x, int64_t x_ld, const float* scale
 extern "C" int tem_conv1x1_out_bwd_ok(int Cin, int Cout) {
     return Cin % 32 == 0 && Cin <= 64 && Cout >= 1 && Cout <= 4 && (Cin / 32) * Cout <= 8;
 }
-extern "C" int tem_conv1x1_out_bwd(const float* x, int64_t x_ld, const float* g, int64_t g_ld, const float* w, float* gx,
-                                   int64_t gx_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int64_t NV, int Cin,
-                                   int Cout, tem_stream_t stream) {
+static int conv1x1_out_bwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* g, int64_t g_ld, const float* w,
+                                float* gx, int64_t gx_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int64_t NV, int Cin,
+                                int Cout, tem_stream_t stream) {
     TEM_REQUIRE(x && g && w && gx && dw && ws && NV > 0 && x_ld >= Cin && gx_ld >= Cin && g_ld >= Cout,
                 "tem_conv1x1_out_bwd: bad arguments");
     TEM_REQUIRE(tem_conv1x1_out_bwd_ok(Cin, Cout), "tem_conv1x1_out_bwd: tem_conv1x1_out_bwd_ok() == 0 for %d -> %d", Cin, Cout);
     TEM_REQUIRE(ws_bytes >= tem_conv1x1_proj_wgrad_ws(Cin, Cout), "tem_conv1x1_out_bwd: workspace too small");
-    if (!tem_conv1x1_out_bwd(x, x_ld, g, g_ld, w, gx, gx_ld, dw, db, ws, NV, Cin, Cout, 1, (hipStream_t)stream)) {
+    if (!tem_conv1x1_out_bwd(c, x, x_ld, g, g_ld, w, gx, gx_ld, dw, db, ws, NV, Cin, Cout, 1, (hipStream_t)stream)) {
         tem_set_error("tem_conv1x1_out_bwd: x / gx / w need 16-byte alignment and ld %% 4 == 0");
         return TEM_EINVAL;
     }
     TEM_CHECK_LAUNCH("tem_conv1x1_out_bwd");
     return TEM_OK;
+}
+extern "C" int tem_conv1x1_out_bwd(const float* x, int64_t x_ld, const float* g, int64_t g_ld, const float* w, float* gx,
+                                   int64_t gx_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int64_t NV, int Cin,
+                                   int Cout, tem_stream_t stream) {
+    return conv1x1_out_bwd_impl(TemConvCall{}, x, x_ld, g, g_ld, w, gx, gx_ld, dw, db, ws, ws_bytes, NV, Cin, Cout, stream);
 }
 extern "C" int64_t tem_conv1x1_out_bwd_ws(int Cin, int Cout) { return tem_conv1x1_proj_wgrad_ws(Cin, Cout); }
 
@@ -758,18 +774,50 @@ extern "C" int tem_conv1x1_out_bwd_st(const void* x, int64_t x_ld, const void* g
                                       int64_t gx_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int64_t NV, int Cin,
                                       int Cout, unsigned* out_amax, int st_x, int st_g, tem_stream_t stream) {
     TEM_REQUIRE(st_x >= 0 && st_x <= 2 && st_g >= 0 && st_g <= 2, "tem_conv1x1_out_bwd_st: unknown storage type");
-    TemStScope sc(st_x, st_g);
     TemByproducts bp = {};
     bp.out_amax = out_amax;
-    TemBpScope bsc(&bp);
-    return tem_conv1x1_out_bwd((const float*)x, x_ld, (const float*)g, g_ld, w, (float*)gx, gx_ld, dw, db, ws, ws_bytes, NV, Cin,
-                               Cout, stream);
+    const TemConvCall c = {st_x, st_g, 0, 0, &bp};
+    return conv1x1_out_bwd_impl(c, (const float*)x, x_ld, (const float*)g, g_ld, w, (float*)gx, gx_ld, dw, db, ws, ws_bytes, NV, Cin,
+                                Cout, stream);
 }
 
 extern "C" int tem_conv3d_wgrad_gmax_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                                         int use_mfma) {
-    TEM_MODE_SCOPE(use_mfma);
-    return use_mfma == 2 && tem_conv_wgrad_gmax_ok(N, D, H, W, Cin, Cout, kd, kh, kw);
+    return (use_mfma & 0xff) == 2 && tem_conv_wgrad_gmax_ok(N, D, H, W, Cin, Cout, kd, kh, kw);
+}
+
+// tem_conv3d_wgrad_sums_ok for a decoded call
+static int wgrad_sums_ok(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
+    if (use_mfma == 1)   // exact fp32: the layers k_conv_wgrad_tr<4> takes (option fp32_zr: the data gradient that consumes the sums)
+        return tem_option(TEM_OPT_FP32_ZR) && !c.stx && !c.sty && tem_conv_wgrad_tr_fp32_ok(N, D, H, W, Cin, Cout, kd, kh, kw) &&
+               tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, c.x_cs);
+    if (use_mfma != 2 && use_mfma != 5 && use_mfma != 7 && use_mfma != 8) return 0;
+    return tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, c.x_cs);
+}
+
+// the argument checks of tem_conv3d_wgrad_gmax / _gscaled / _sums (also tem_conv3d_wgrad_ex with g_amax_out / g_amax_in / norm_sums)
+static int wgrad_gmax_check(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, const float* w, const float* db,
+                            const float* norm_sums) {
+    TEM_REQUIRE(c.g_amax_out, "tem_conv3d_wgrad_gmax: null g_amax");
+    TEM_REQUIRE(use_mfma == 2 && tem_conv_wgrad_gmax_ok(N, D, H, W, Cin, Cout, kd, kh, kw),
+                "tem_conv3d_wgrad_gmax: tem_conv3d_wgrad_gmax_ok() == 0 for this layer");
+    TEM_REQUIRE(!norm_sums || (w && db && wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)),
+                "tem_conv3d_wgrad_gmax: norm_sums needs weights, a bias gradient and tem_conv3d_wgrad_sums_ok() != 0");
+    return TEM_OK;
+}
+static int wgrad_gscaled_check(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, const float* w, const float* db, const float* norm_sums) {
+    TEM_REQUIRE(c.g_amax_in, "tem_conv3d_wgrad_gscaled: null g_amax");
+    TEM_REQUIRE(tem_conv_wgrad_gscaled_ok(N, D, H, W, Cin, Cout, kd, kh, kw),
+                "tem_conv3d_wgrad_gscaled: tem_conv3d_wgrad_gscaled_ok() == 0 for this layer");
+    TEM_REQUIRE(!norm_sums || (w && db && wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, 8)),
+                "tem_conv3d_wgrad_gscaled: norm_sums needs weights, a bias gradient and tem_conv3d_wgrad_sums_ok() != 0");
+    return TEM_OK;
+}
+static int wgrad_sums_check(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, const float* w, const float* db,
+                            const float* norm_sums) {
+    TEM_REQUIRE(w && norm_sums && db, "tem_conv3d_wgrad_sums: null pointer (weights, sums and bias gradient are required)");
+    TEM_REQUIRE(wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma), "tem_conv3d_wgrad_sums: tem_conv3d_wgrad_sums_ok() == 0 for this layer");
+    return TEM_OK;
 }
 
 extern "C" int tem_conv3d_wgrad_gmax(const float* x, int64_t x_ld, const float* scale, const float* shift,
@@ -777,18 +825,11 @@ extern "C" int tem_conv3d_wgrad_gmax(const float* x, int64_t x_ld, const float* 
                                      const float* beta, float* dw, float* db, float* norm_sums, unsigned* g_amax,
                                      void* ws, int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd,
                                      int kh, int kw, int use_mfma, tem_stream_t stream) {
-    TEM_MODE_SCOPE(use_mfma);
-    TEM_REQUIRE(g_amax, "tem_conv3d_wgrad_gmax: null g_amax");
-    TEM_REQUIRE(tem_conv3d_wgrad_gmax_ok(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma),
-                "tem_conv3d_wgrad_gmax: tem_conv3d_wgrad_gmax_ok() == 0 for this layer");
-    TEM_REQUIRE(!norm_sums || (w && db && tem_conv3d_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)),
-                "tem_conv3d_wgrad_gmax: norm_sums needs weights, a bias gradient and tem_conv3d_wgrad_sums_ok() != 0");
-    tem_wgrad_gmax_target = g_amax;
-    const int rc = conv3d_wgrad_impl(x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
-                                     kw, use_mfma, 1, norm_sums ? w : nullptr, gamma, beta, norm_sums, nullptr, 0, nullptr,
-                                     stream);
-    tem_wgrad_gmax_target = nullptr;
-    return rc;
+    TemConvCall c = conv_call(use_mfma);
+    c.g_amax_out = g_amax;
+    TEM_TRY(wgrad_gmax_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, w, db, norm_sums));
+    return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, 1,
+                             norm_sums ? w : nullptr, gamma, beta, norm_sums, nullptr, 0, nullptr, stream);
 }
 
 // ---- weight gradient with 16-bit-class x^ and an 11-bit g (two MFMAs per product instead of three) -----------------------
@@ -838,38 +879,43 @@ extern "C" int tem_conv3d_wgrad_gscaled(const float* x, int64_t x_ld, const floa
                                         const float* beta, float* dw, float* db, float* norm_sums,
                                         const unsigned* g_amax, void* ws, int64_t ws_bytes, int N, int D, int H, int W,
                                         int Cin, int Cout, int kd, int kh, int kw, tem_stream_t stream) {
-    TEM_REQUIRE(g_amax, "tem_conv3d_wgrad_gscaled: null g_amax");
-    TEM_REQUIRE(tem_conv3d_wgrad_gscaled_ok(N, D, H, W, Cin, Cout, kd, kh, kw),
-                "tem_conv3d_wgrad_gscaled: tem_conv3d_wgrad_gscaled_ok() == 0 for this layer");
-    TEM_REQUIRE(!norm_sums || (w && db && tem_conv3d_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, 8)),
-                "tem_conv3d_wgrad_gscaled: norm_sums needs weights, a bias gradient and tem_conv3d_wgrad_sums_ok() != 0");
-    tem_wgrad_gscale_source = g_amax;
-    const int rc = conv3d_wgrad_impl(x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
-                                     kw, 8, 1, norm_sums ? w : nullptr, gamma, beta, norm_sums, nullptr, 0, nullptr,
-                                     stream);
-    tem_wgrad_gscale_source = nullptr;
-    return rc;
+    TemConvCall c;
+    c.g_amax_in = g_amax;
+    TEM_TRY(wgrad_gscaled_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, w, db, norm_sums));
+    return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, 8, 1,
+                             norm_sums ? w : nullptr, gamma, beta, norm_sums, nullptr, 0, nullptr, stream);
+}
+
+// the argument checks of tem_conv3d_fwd_gscaled / _refnorm (also tem_conv3d_fwd_ex with in_amax / ref_coef).  Whether the launch
+// then really takes the z-reuse kernel is tem_conv_fwd_zr's answer: it fails a call that carries one and that it cannot run.
+static int fwd_gscaled_check(const TemConvCall& c, const float* x, int64_t x_ld, const float* w_packed, const float* y, int64_t y_ld,
+                             const float* ref, int64_t ref_ld, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
+    TEM_REQUIRE(c.in_amax, "tem_conv3d_fwd_gscaled: null in_amax");
+    TEM_REQUIRE(fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, 4, x_ld, y_ld, ref ? ref_ld : 0,
+                         fwd_misaligned(x, nullptr, nullptr, w_packed, nullptr, y, ref)).family == 3,
+                "tem_conv3d_fwd_gscaled: only launches that tem_conv3d_fwd_kernel_ld() reports as 3 (z-reuse kernel) take a "
+                "device-side prescale");
+    return TEM_OK;
+}
+static int fwd_refnorm_check(const TemConvCall& c, const float* x, int64_t x_ld, const float* w_packed, const float* y, int64_t y_ld,
+                             const float* ref, int64_t ref_ld, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
+    TEM_REQUIRE(ref && c.ref_coef, "tem_conv3d_fwd_refnorm: null ref / coef");
+    TEM_REQUIRE(fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld,
+                         fwd_misaligned(x, nullptr, nullptr, w_packed, c.ref_coef, y, ref)).family == 3,
+                "tem_conv3d_fwd_refnorm: only launches that tem_conv3d_fwd_kernel_ld() reports as 3 (z-reuse kernel) apply a "
+                "norm backward in their epilogue");
+    return TEM_OK;
 }
 
 extern "C" int tem_conv3d_fwd_gscaled(const float* x, int64_t x_ld, const float* w_packed, float* y, int64_t y_ld,
                                       const float* ref, int64_t ref_ld, const unsigned* in_amax, void* ws,
                                       int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh,
                                       int kw, tem_stream_t stream) {
-    TEM_REQUIRE(in_amax, "tem_conv3d_fwd_gscaled: null in_amax");
-    TEM_REQUIRE(tem_conv3d_fwd_kernel_ld(N, D, H, W, Cin, Cout, kd, kh, kw, 4, x_ld, y_ld, ref ? ref_ld : 0,
-                                         fwd_misaligned(x, nullptr, nullptr, w_packed, nullptr, y, ref)) == 3,
-                "tem_conv3d_fwd_gscaled: only launches that tem_conv3d_fwd_kernel_ld() reports as 3 (z-reuse kernel) take a "
-                "device-side prescale");
-    tem_zr_in_amax = in_amax;
-    const int rc = conv3d_fwd_impl(x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H,
-                                   W, Cin, Cout, kd, kh, kw, TEM_ACT_NONE, 4, nullptr, stream);
-    const bool consumed = tem_zr_in_amax == nullptr;
-    tem_zr_in_amax = nullptr;
-    if (rc == TEM_OK && !consumed) {
-        tem_set_error("tem_conv3d_fwd_gscaled: the launch did not take the z-reuse kernel (alignment of y / ref?)");
-        return TEM_EINVAL;
-    }
-    return rc;
+    TemConvCall c;
+    c.in_amax = in_amax;
+    TEM_TRY(fwd_gscaled_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw));
+    return conv3d_fwd_impl(c, x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout,
+                           kd, kh, kw, TEM_ACT_NONE, 4, nullptr, stream);
 }
 
 // Data gradient that lands behind a ReLU + norm: y = ref > 0 ? a*(conv) - m1 - (ref - mean)*m2r : 0 with coef[N][Cout][4] =
@@ -879,32 +925,17 @@ extern "C" int tem_conv3d_fwd_refnorm(const float* x, int64_t x_ld, const float*
                                       const float* ref, int64_t ref_ld, const float* coef, void* ws, int64_t ws_bytes,
                                       int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,
                                       tem_stream_t stream) {
-    TEM_MODE_SCOPE(use_mfma);
-    TEM_REQUIRE(ref && coef, "tem_conv3d_fwd_refnorm: null ref / coef");
-    TEM_REQUIRE(fwd_plan(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld,
-                         fwd_misaligned(x, nullptr, nullptr, w_packed, coef, y, ref)).family == 3,
-                "tem_conv3d_fwd_refnorm: only launches that tem_conv3d_fwd_kernel_ld() reports as 3 (z-reuse kernel) apply a "
-                "norm backward in their epilogue");
-    tem_zr_ref_coef = coef;
-    const int rc = conv3d_fwd_impl(x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H,
-                                   W, Cin, Cout, kd, kh, kw, TEM_ACT_NONE, use_mfma, nullptr, stream);
-    const bool consumed = tem_zr_ref_coef == nullptr;
-    tem_zr_ref_coef = nullptr;
-    if (rc == TEM_OK && !consumed) {
-        tem_set_error("tem_conv3d_fwd_refnorm: the launch did not take the z-reuse kernel (alignment of y / ref?)");
-        return TEM_EINVAL;
-    }
-    return rc;
+    TemConvCall c = conv_call(use_mfma);
+    c.ref_coef = coef;
+    TEM_TRY(fwd_refnorm_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma));
+    return conv3d_fwd_impl(c, x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout,
+                           kd, kh, kw, TEM_ACT_NONE, use_mfma, nullptr, stream);
 }
 
 extern "C" int tem_conv3d_wgrad_sums_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                                         int use_mfma) {
-    TEM_MODE_SCOPE(use_mfma);
-    if (use_mfma == 1)   // exact fp32: the layers k_conv_wgrad_tr<4> takes (option fp32_zr: the data gradient that consumes the sums)
-        return tem_option(TEM_OPT_FP32_ZR) && !tem_call_st.x && !tem_call_st.y && tem_conv_wgrad_tr_fp32_ok(N, D, H, W, Cin, Cout, kd, kh, kw) &&
-               tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw);
-    if (use_mfma != 2 && use_mfma != 5 && use_mfma != 7 && use_mfma != 8) return 0;
-    return tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw);
+    const TemConvCall c = conv_call(use_mfma);
+    return wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma);
 }
 
 extern "C" int tem_conv3d_wgrad_sums(const float* x, int64_t x_ld, const float* scale, const float* shift,
@@ -912,12 +943,10 @@ extern "C" int tem_conv3d_wgrad_sums(const float* x, int64_t x_ld, const float* 
                                      const float* beta, float* dw, float* db, float* norm_sums, void* ws,
                                      int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh,
                                      int kw, int use_mfma, tem_stream_t stream) {
-    TEM_MODE_SCOPE(use_mfma);
-    TEM_REQUIRE(w && norm_sums && db, "tem_conv3d_wgrad_sums: null pointer (weights, sums and bias gradient are required)");
-    TEM_REQUIRE(tem_conv3d_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma),
-                "tem_conv3d_wgrad_sums: tem_conv3d_wgrad_sums_ok() == 0 for this layer");
-    return conv3d_wgrad_impl(x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw,
-                             use_mfma, 1, w, gamma, beta, norm_sums, nullptr, 0, nullptr, stream);
+    const TemConvCall c = conv_call(use_mfma);
+    TEM_TRY(wgrad_sums_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, w, db, norm_sums));
+    return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, 1,
+                             w, gamma, beta, norm_sums, nullptr, 0, nullptr, stream);
 }
 
 // ---- every variant and by-product of the forward / data-gradient convolution as explicit arguments (tem_hip.h) -----------------
@@ -926,31 +955,34 @@ extern "C" int tem_conv3d_fwd_ex(const float* x, int64_t x_ld, const float* scal
                                  int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
                                  int use_mfma, const unsigned* in_amax, const float* ref_coef, float* stat_part,
                                  int64_t stat_blocks, int64_t x_cs, int64_t y_cs, TemByproducts* bp, tem_stream_t stream) {
+    TemConvCall c = conv_call(use_mfma);
     TEM_REQUIRE(!stat_part || (!in_amax && !ref_coef && !bp), "tem_conv3d_fwd_ex: stat_part excludes in_amax / ref_coef / by-products");
     TEM_REQUIRE(!(in_amax && ref_coef), "tem_conv3d_fwd_ex: in_amax and ref_coef exclude each other");
-    TEM_REQUIRE(x_cs >= 0 && y_cs >= 0 && (!(x_cs || y_cs) || (!in_amax && !ref_coef && ((use_mfma & 0xff) == 5 || (use_mfma & 0xff) == 7))),
+    TEM_REQUIRE(x_cs >= 0 && y_cs >= 0 && (!(x_cs || y_cs) || (!in_amax && !ref_coef && (use_mfma == 5 || use_mfma == 7))),
                 "tem_conv3d_fwd_ex: chunk strides go with the one-term modes on 16-bit tensors (use_mfma 5 / 7), no in_amax / ref_coef");
-    TemCsScope csc(x_cs, y_cs);
     TEM_REQUIRE(!bp || (!bp->coef && (!bp->sums_part || (bp->sums_x && bp->sums_mean && bp->sums_rstd && bp->sums_G > 0 && bp->sums_nblk > 0))),
                 "tem_conv3d_fwd_ex: bad by-product request (TEM_BP_NORM_COEF belongs to tem_conv3d_wgrad_ex; TEM_BP_NORM_SUMS needs "
                 "sums_x / sums_mean / sums_rstd / sums_G / sums_nblk)");
-    TemBpScope bsc(bp);
+    c.x_cs = x_cs;
+    c.y_cs = y_cs;
+    c.bp = bp;
+    if (bp) bp->delivered = 0;
     if (in_amax) {
-        TEM_REQUIRE(!scale && !shift && !bias && act == TEM_ACT_NONE && (use_mfma & 0xff) == 4,
+        TEM_REQUIRE(!scale && !shift && !bias && act == TEM_ACT_NONE && use_mfma == 4,
                     "tem_conv3d_fwd_ex: in_amax (the fp16 two-term data gradient) takes use_mfma 4 and no scale / shift / bias / act");
-        return tem_conv3d_fwd_gscaled(x, x_ld, w_packed, y, y_ld, ref, ref_ld, in_amax, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
-                                      kw, stream);
-    }
-    if (ref_coef) {
+        c.stx = c.sty = TEM_ST_F32;   // as tem_conv3d_fwd_gscaled: an fp32-tensor mode
+        c.in_amax = in_amax;
+        TEM_TRY(fwd_gscaled_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw));
+    } else if (ref_coef) {
         TEM_REQUIRE(!scale && !shift && !bias && act == TEM_ACT_NONE, "tem_conv3d_fwd_ex: ref_coef takes no scale / shift / bias / act");
-        return tem_conv3d_fwd_refnorm(x, x_ld, w_packed, y, y_ld, ref, ref_ld, ref_coef, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
-                                      kw, use_mfma, stream);
+        c.ref_coef = ref_coef;
+        TEM_TRY(fwd_refnorm_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma));
+    } else if (stat_part) {
+        TEM_TRY(fwd_stats_check(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma,
+                                stat_part, stat_blocks));
     }
-    if (stat_part)
-        return tem_conv3d_fwd_stats(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout,
-                                    kd, kh, kw, act, use_mfma, stat_part, stat_blocks, stream);
-    return tem_conv3d_fwd(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
-                          kw, act, use_mfma, stream);
+    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
+                           kw, act, use_mfma, stat_part, stream);
 }
 
 extern "C" int tem_conv3d_wgrad_ex(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
@@ -958,45 +990,54 @@ extern "C" int tem_conv3d_wgrad_ex(const float* x, int64_t x_ld, const float* sc
                                    float* norm_sums, const unsigned* g_amax_in, unsigned* g_amax_out, void* ws, int64_t ws_bytes,
                                    int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,
                                    int64_t x_cs, TemByproducts* bp, tem_stream_t stream) {
+    TemConvCall c = conv_call(use_mfma);
     TEM_REQUIRE(!(g_amax_in && g_amax_out), "tem_conv3d_wgrad_ex: g_amax_in and g_amax_out exclude each other");
-    TEM_REQUIRE(x_cs >= 0 && (!x_cs || (!g_amax_in && !g_amax_out && ((use_mfma & 0xff) == 5 || (use_mfma & 0xff) == 7))),
+    TEM_REQUIRE(x_cs >= 0 && (!x_cs || (!g_amax_in && !g_amax_out && (use_mfma == 5 || use_mfma == 7))),
                 "tem_conv3d_wgrad_ex: a chunk stride goes with the one-term modes on 16-bit tensors (use_mfma 5 / 7)");
-    TemCsScope csc(x_cs, 0);
     TEM_REQUIRE(!bp || (!bp->out_amax && !bp->sums_part && (!bp->coef || (norm_sums && bp->coef_mean && bp->coef_rstd && bp->coef_G > 0))),
                 "tem_conv3d_wgrad_ex: bad by-product request (only TEM_BP_NORM_COEF, which needs norm_sums, coef_mean, coef_rstd, coef_G)");
-    TemBpScope bsc(bp);
+    c.x_cs = x_cs;
+    c.bp = bp;
+    if (bp) bp->delivered = 0;
     if (g_amax_in) {
-        TEM_REQUIRE((use_mfma & 0xff) == 8, "tem_conv3d_wgrad_ex: g_amax_in (the fp16 2x1 arithmetic) takes use_mfma 8");
-        return tem_conv3d_wgrad_gscaled(x, x_ld, scale, shift, g, g_ld, w, gamma, beta, dw, db, norm_sums, g_amax_in, ws, ws_bytes, N, D,
-                                        H, W, Cin, Cout, kd, kh, kw, stream);
+        TEM_REQUIRE(use_mfma == 8, "tem_conv3d_wgrad_ex: g_amax_in (the fp16 2x1 arithmetic) takes use_mfma 8");
+        c.stx = c.sty = TEM_ST_F32;   // as tem_conv3d_wgrad_gscaled: an fp32-tensor mode
+        c.g_amax_in = g_amax_in;
+        TEM_TRY(wgrad_gscaled_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, w, db, norm_sums));
+    } else if (g_amax_out) {
+        c.g_amax_out = g_amax_out;
+        TEM_TRY(wgrad_gmax_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, w, db, norm_sums));
+    } else if (norm_sums) {
+        TEM_TRY(wgrad_sums_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, w, db, norm_sums));
     }
-    if (g_amax_out)
-        return tem_conv3d_wgrad_gmax(x, x_ld, scale, shift, g, g_ld, w, gamma, beta, dw, db, norm_sums, g_amax_out, ws, ws_bytes, N, D,
-                                     H, W, Cin, Cout, kd, kh, kw, use_mfma, stream);
-    if (norm_sums)
-        return tem_conv3d_wgrad_sums(x, x_ld, scale, shift, g, g_ld, w, gamma, beta, dw, db, norm_sums, ws, ws_bytes, N, D, H, W, Cin,
-                                     Cout, kd, kh, kw, use_mfma, stream);
-    return tem_conv3d_wgrad(x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, 1,
-                            stream);
+    return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, 1,
+                             norm_sums ? w : nullptr, gamma, beta, norm_sums, nullptr, 0, nullptr, stream);   // (w, gamma, beta: read for the sums only)
 }
 
 // tem_conv3d_wgrad of a FIRST layer (small Cin, VALU kernel) whose output gradient g is still the raw data gradient
 // behind the norm that follows this conv's ReLU: the norm backward (coefficients from tem_norm_bwd_coef) and the ReLU
 // mask are applied while g is loaded -- y (this conv's output, the norm's input) is read instead of a rewritten g.
 extern "C" int tem_conv3d_wgrad_gnorm_ok(int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
-    TEM_MODE_SCOPE(use_mfma);
+    use_mfma &= 0xff;
     const int cq = Cout / 4, key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
     return use_mfma == 0 && Cin >= 1 && Cin <= 4 && Cout % 4 == 0 && cq <= 16 && (cq & (cq - 1)) == 0 && (key == 7 || key == 3);
 }
 
+static int wgrad_gnorm_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
+                            int64_t g_ld, const float* y, int64_t y_ld, const float* gcoef, float* dw, float* db, void* ws,
+                            int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int sd_layout,
+                            tem_stream_t stream) {
+    TEM_REQUIRE(y && gcoef && y_ld >= Cout, "tem_conv3d_wgrad_gnorm: null pointer");
+    TEM_REQUIRE(tem_conv3d_wgrad_gnorm_ok(Cin, Cout, kd, kh, kw, 0), "tem_conv3d_wgrad_gnorm: tem_conv3d_wgrad_gnorm_ok() == 0");
+    return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, 0,
+                             sd_layout, nullptr, nullptr, nullptr, nullptr, y, y_ld, gcoef, stream);
+}
 extern "C" int tem_conv3d_wgrad_gnorm(const float* x, int64_t x_ld, const float* scale, const float* shift,
                                       const float* g, int64_t g_ld, const float* y, int64_t y_ld, const float* gcoef,
                                       float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H, int W,
                                       int Cin, int Cout, int kd, int kh, int kw, int sd_layout, tem_stream_t stream) {
-    TEM_REQUIRE(y && gcoef && y_ld >= Cout, "tem_conv3d_wgrad_gnorm: null pointer");
-    TEM_REQUIRE(tem_conv3d_wgrad_gnorm_ok(Cin, Cout, kd, kh, kw, 0), "tem_conv3d_wgrad_gnorm: tem_conv3d_wgrad_gnorm_ok() == 0");
-    return conv3d_wgrad_impl(x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, 0,
-                             sd_layout, nullptr, nullptr, nullptr, nullptr, y, y_ld, gcoef, stream);
+    return wgrad_gnorm_impl(TemConvCall{}, x, x_ld, scale, shift, g, g_ld, y, y_ld, gcoef, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout,
+                            kd, kh, kw, sd_layout, stream);
 }
 
 // tem_conv3d_wgrad_gnorm for x of storage type st_x and g / y of storage type st_g (TEM_ST_*)
@@ -1005,7 +1046,7 @@ extern "C" int tem_conv3d_wgrad_gnorm_st(const void* x, int64_t x_ld, const floa
                                          void* ws, int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh,
                                          int kw, int sd_layout, int st_x, int st_g, tem_stream_t stream) {
     TEM_REQUIRE(st_x >= 0 && st_x <= 2 && st_g >= 0 && st_g <= 2, "tem_conv3d_wgrad_gnorm_st: unknown storage type");
-    TemStScope sc(st_x, st_g);
-    return tem_conv3d_wgrad_gnorm((const float*)x, x_ld, scale, shift, (const float*)g, g_ld, (const float*)y, y_ld, gcoef, dw, db,
-                                  ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, sd_layout, stream);
+    const TemConvCall c = {st_x, st_g};
+    return wgrad_gnorm_impl(c, (const float*)x, x_ld, scale, shift, (const float*)g, g_ld, (const float*)y, y_ld, gcoef, dw, db, ws,
+                            ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, sd_layout, stream);
 }

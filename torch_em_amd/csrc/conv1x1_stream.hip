@@ -119,7 +119,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_stream(const T* __restrict__ x,
 }
 
 template <int NS, bool F16, typename T>
-static void stream_launch(const T* x, int64_t x_ld, const float* wp, const float* bias, T* y, int64_t y_ld,
+static void stream_launch(const TemConvCall& c, const T* x, int64_t x_ld, const float* wp, const float* bias, T* y, int64_t y_ld,
                           const T* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act, hipStream_t s) {
     const int64_t nmt = (NV + 31) / 32;
     const int ntile = Cout / 32;
@@ -128,7 +128,7 @@ static void stream_launch(const T* x, int64_t x_ld, const float* wp, const float
     int64_t gx = (nmt + 3) / 4;
     if (gx > 8192) gx = 8192;   // grid-stride: 8 workgroups per CU keep the loads in flight
     const dim3 grid((unsigned)gx, (unsigned)ngroups);
-    unsigned* const amax = tem_take_output_amax();
+    unsigned* const amax = c.take_output_amax();
     if (CT == 2)
         hipLaunchKernelGGL((k_conv1x1_stream<NS, F16, 2, T>), grid, dim3(256), 0, s, x, x_ld, (const unsigned short*)wp, bias, y, y_ld,
                            ref, ref_ld, NV, Cin, Cout, act, nmt, amax);
@@ -138,13 +138,13 @@ static void stream_launch(const T* x, int64_t x_ld, const float* wp, const float
 }
 
 // nsplit as in tem_conv_fwd_bf16x3: 2 = bf16x3, 3 = bf16x6, 5 = one fp16 term, 7 = one bf16 term.  false: not taken (pre-norm, statistics, the
-// scaled fp16x3 layouts, sigmoid -- the patch kernel handles those).  Storage types (tem_call_st): fp32, or the 16-bit type
+// scaled fp16x3 layouts, sigmoid -- the patch kernel handles those).  Storage types (c.stx / c.sty): fp32, or the 16-bit type
 // that IS the operand type of the mode (fp16 with nsplit 5, bf16 with nsplit 7).
-bool tem_conv1x1_stream(const float* x, int64_t x_ld, const float* scale, const float* wp, const float* bias, float* y,
+bool tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* wp, const float* bias, float* y,
                         int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act, int nsplit,
                         const float* stat, hipStream_t s) {
-    const int st = tem_call_st.x;
-    if (tem_call_st.y != st) return false;
+    const int st = c.stx;
+    if (c.sty != st) return false;
     if (st && !((st == 1 && nsplit == 5) || (st == 2 && nsplit == 7))) return false;
     const uintptr_t a8 = st ? 15 : 15, a4 = tem_st_align4(st) - 1;   // x: 16-byte loads either way; y / ref: vectors of 4 elements
     if (scale || stat || act == TEM_ACT_SIGMOID) return false;
@@ -154,17 +154,17 @@ bool tem_conv1x1_stream(const float* x, int64_t x_ld, const float* scale, const 
         (ref && ((ref_ld & 3) || (reinterpret_cast<uintptr_t>(ref) & a4))))
         return false;
     if (st == 1)
-        stream_launch<1, true, tem_f16>((const tem_f16*)x, x_ld, wp, bias, (tem_f16*)y, y_ld, (const tem_f16*)ref, ref_ld, NV, Cin, Cout, act, s);
+        stream_launch<1, true, tem_f16>(c, (const tem_f16*)x, x_ld, wp, bias, (tem_f16*)y, y_ld, (const tem_f16*)ref, ref_ld, NV, Cin, Cout, act, s);
     else if (st == 2)
-        stream_launch<1, false, tem_bf16>((const tem_bf16*)x, x_ld, wp, bias, (tem_bf16*)y, y_ld, (const tem_bf16*)ref, ref_ld, NV, Cin, Cout, act, s);
+        stream_launch<1, false, tem_bf16>(c, (const tem_bf16*)x, x_ld, wp, bias, (tem_bf16*)y, y_ld, (const tem_bf16*)ref, ref_ld, NV, Cin, Cout, act, s);
     else if (nsplit == 2)
-        stream_launch<2, false, float>(x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
+        stream_launch<2, false, float>(c, x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
     else if (nsplit == 3)
-        stream_launch<3, false, float>(x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
+        stream_launch<3, false, float>(c, x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
     else if (nsplit == 5)
-        stream_launch<1, true, float>(x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
+        stream_launch<1, true, float>(c, x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
     else if (nsplit == 7)
-        stream_launch<1, false, float>(x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
+        stream_launch<1, false, float>(c, x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
     else
         return false;
     return true;

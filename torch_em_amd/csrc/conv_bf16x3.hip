@@ -638,18 +638,18 @@ static void launch_b(const float* x_, int64_t x_ld, const float* scale, const fl
                        Cout, act, nZ, nY, nX, ksplit, part, ksplit > 1 ? nullptr : stat);
     if (ksplit > 1) {
         const int64_t NV = (int64_t)N * D * H * W;
-        tem_splitk_epilogue(part, ksplit, NV, Cout, bias, act, ref_, ref_ld, y_, y_ld, s);
+        tem_splitk_epilogue(TemSt<T>::id, part, ksplit, NV, Cout, bias, act, ref_, ref_ld, y_, y_ld, s);
     }
 }
 
-int tem_conv_fwd_bf16x3(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
+int tem_conv_fwd_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                         const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
                         int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
                         int nsplit, float* stat, hipStream_t s) {
     TEM_REQUIRE(Cin % 16 == 0 && Cout % 32 == 0, "tem_conv3d_fwd(split-bf16): needs Cin%%16==0 and Cout%%32==0 (got %d,%d)",
                 Cin, Cout);
-    const int st = tem_call_st.x;
-    TEM_REQUIRE(st == tem_call_st.y, "tem_conv3d_fwd(split-bf16): x and y must have the same storage type");
+    const int st = c.stx;
+    TEM_REQUIRE(st == c.sty, "tem_conv3d_fwd(split-bf16): x and y must have the same storage type");
     TEM_REQUIRE(st == 0 || (st == 1 && nsplit == 5) || (st == 2 && nsplit == 7),
                 "tem_conv3d_fwd(split-bf16): 16-bit storage goes with the one-term mode of the same type (fp16: use_mfma 5, "
                 "bf16: use_mfma 7), got storage %d with use_mfma %d", st, nsplit);
@@ -657,22 +657,22 @@ int tem_conv_fwd_bf16x3(const float* x, int64_t x_ld, const float* scale, const 
                 "tem_conv3d_fwd(split-bf16): x / packed weights must be 16-byte aligned with ld%%4==0 (16-bit storage: ld%%8==0)");
     TEM_REQUIRE(!scale || (((uintptr_t)scale % 16 == 0) && ((uintptr_t)shift % 16 == 0)),
                 "tem_conv3d_fwd(split-bf16): scale/shift must be 16-byte aligned");
-    const int zr = tem_conv_fwd_zr(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, act,
+    const int zr = tem_conv_fwd_zr(c, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, act,
                                    nsplit, stat, s);
     if (zr < 0) return TEM_EINVAL;
     if (zr) return TEM_OK;
-    const int pp = tem_conv_fwd_pp(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, act,
+    const int pp = tem_conv_fwd_pp(c, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, act,
                                    nsplit, stat, s);
     if (pp < 0) return TEM_EINVAL;
     if (pp) return TEM_OK;
-    if (tem_conv_fwd_zr_splitk(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
+    if (tem_conv_fwd_zr_splitk(c, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
                                kw, act, nsplit, stat, s))
         return TEM_OK;
-    TEM_REQUIRE(!stat || tem_conv_zr_splitk_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit) < 0,
+    TEM_REQUIRE(!stat || tem_conv_zr_splitk_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit) < 0,
                 "tem_conv3d_fwd_stats: the split-K launch that writes the statistics needs its workspace "
                 "(tem_conv3d_fwd_ws) and 16-byte aligned y / ref / bias");
     if (kd == 1 && kh == 1 && kw == 1 && tem_option(TEM_OPT_CONV1X1_STREAM) &&
-        tem_conv1x1_stream(x, x_ld, scale, wp, bias, y, y_ld, ref, ref_ld, (int64_t)N * D * H * W, Cin, Cout, act, nsplit, stat, s))
+        tem_conv1x1_stream(c, x, x_ld, scale, wp, bias, y, y_ld, ref, ref_ld, (int64_t)N * D * H * W, Cin, Cout, act, nsplit, stat, s))
         return TEM_OK;
     const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
     const bool flat = (D == 1 && kd == 1);
@@ -1843,11 +1843,11 @@ static WbPlan wb_plan(int N, int D, int H, int W, int Cin, int Cout, int ntaps) 
 
 // Can this weight gradient also deliver the norm-backward sums (wgrad_sums.hip)?  z-sliding kernel, a few samples,
 // widths whose [27][Cout] tables fit a block's LDS
-int tem_conv_wgrad_sums_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
+int tem_conv_wgrad_sums_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int64_t x_cs) {
     const int enable = (int)tem_option(TEM_OPT_WGRAD_SUMS);
     if (!enable || Cin % 32 || Cout % 32) return 0;
     const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
-    TEM_REQUIRE(!tem_call_cs.x || z.use, "tem_conv3d_wgrad_ex: a chunk stride (x_cs) needs the z-sliding kernel (3x3x3, D >= 8)");
+    TEM_REQUIRE(!x_cs || z.use, "tem_conv3d_wgrad_ex: a chunk stride (x_cs) needs the z-sliding kernel (3x3x3, D >= 8)");
     const int cq = Cout / 4;
     // four small launches replace one pass over gz and x: only worth it where that pass is long (>= 128 MB tensors by default)
     const int64_t min_bytes = (int64_t)tem_option(TEM_OPT_WGRAD_SUMS_MIN_MB) << 20;
@@ -1860,7 +1860,7 @@ int64_t tem_conv_wgrad_bf16x3_ws(int N, int D, int H, int W, int Cin, int Cout, 
     const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
     if (z.use)
         return tem_align_up((int64_t)z.S * z.ks2 * 27 * Cin * Cout, 64) * 4 + tem_align_up((int64_t)z.S * Cout, 64) * 4 +
-               (tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw) ? tem_wgrad_sums_ws_floats(N, D, H, Cin, Cout) * 4 : 0) +
+               (tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, 0) ? tem_wgrad_sums_ws_floats(N, D, H, Cin, Cout) * 4 : 0) +
                256;
     WbPlan p = wb_plan(N, D, H, W, Cin, Cout, kd * kh * kw);
     return tem_align_up((int64_t)p.S * p.ks2 * kd * kh * kw * Cin * Cout, 64) * 4 + (int64_t)p.S * Cout * 4 + 256;
@@ -1884,30 +1884,25 @@ static void launch_wb_tt(const float* x, int64_t x_ld, const float* scale, const
                        Cin, Cout, p.T, p.S, p.P, p.nZ, p.nY, p.nX);
 }
 template <int KD, int KH, int KW, int NCO, int KS2, int PTZ>
-static void launch_wb_t(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g, int64_t g_ld,
+static void launch_wb_t(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g, int64_t g_ld,
                         float* part, float* dbpart, int N, int D, int H, int W, int Cin, int Cout, const WbPlan& p,
                         hipStream_t s) {
-    TEM_ST_SWITCH(tem_call_st.x, T,
+    TEM_ST_SWITCH(c.stx, T,
                   (launch_wb_tt<KD, KH, KW, NCO, KS2, PTZ, T>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s)));
 }
 template <int KD, int KH, int KW, int NCO, int KS2 = 1>
-static void launch_wb(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g, int64_t g_ld,
+static void launch_wb(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g, int64_t g_ld,
                       float* part, float* dbpart, int N, int D, int H, int W, int Cin, int Cout, const WbPlan& p,
                       hipStream_t s) {
     if constexpr (KD == 1) {
         if (p.ptz == 1) {
-            launch_wb_t<KD, KH, KW, NCO, KS2, 1>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
+            launch_wb_t<KD, KH, KW, NCO, KS2, 1>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
             return;
         }
     }
-    launch_wb_t<KD, KH, KW, NCO, KS2, 2>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
+    launch_wb_t<KD, KH, KW, NCO, KS2, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
 }
 
-// tem_conv3d_wgrad_gmax (conv.hip) parks its output pointer here around its call into tem_conv_wgrad_bf16x3: one more
-// positional argument would have to thread through four internal signatures for the one kernel that honours it
-thread_local unsigned* tem_wgrad_gmax_target = nullptr;
-// tem_conv3d_wgrad_gscaled (conv.hip) parks the device word with max |g| here the same way (h16 == 3 reads it)
-thread_local const unsigned* tem_wgrad_gscale_source = nullptr;
 int tem_conv_wgrad_gscaled_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
     const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
     return Cin % 32 == 0 && Cout % 32 == 0 && z.use && (!z.teams || z.tr);
@@ -1927,14 +1922,14 @@ int tem_conv_wgrad_gmax_ok(int N, int D, int H, int W, int Cin, int Cout, int kd
     return Cin % 32 == 0 && Cout % 32 == 0 && zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw).use;
 }
 
-int tem_conv_wgrad_bf16x3(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
+int tem_conv_wgrad_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
                           int64_t g_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H, int W,
                           int Cin, int Cout, int kd, int kh, int kw, int sd_layout, int h16, const float* w_sd,
                           const float* gamma, const float* beta, float* norm_sums, hipStream_t s) {
     TEM_REQUIRE(Cin % 32 == 0 && Cout % 32 == 0, "tem_conv3d_wgrad(bf16x3): needs Cin%%32==0 and Cout%%32==0 (got %d,%d)",
                 Cin, Cout);
-    const int st = tem_call_st.x;
-    TEM_REQUIRE(st == tem_call_st.y, "tem_conv3d_wgrad(split-bf16): x and g must have the same storage type");
+    const int st = c.stx;
+    TEM_REQUIRE(st == c.sty, "tem_conv3d_wgrad(split-bf16): x and g must have the same storage type");
     TEM_REQUIRE(st == 0 || (st == 1 && h16 == 1) || (st == 2 && h16 == 2),
                 "tem_conv3d_wgrad(split-bf16): 16-bit storage goes with the one-term mode of the same type (fp16: use_mfma 5, "
                 "bf16: use_mfma 7), got storage %d", st);
@@ -1949,9 +1944,9 @@ int tem_conv_wgrad_bf16x3(const float* x, int64_t x_ld, const float* scale, cons
         return TEM_EWS;
     }
     const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
-    unsigned* const gmax = tem_wgrad_gmax_target;   // set by tem_conv3d_wgrad_gmax for the duration of this call
+    unsigned* const gmax = c.g_amax_out;   // tem_conv3d_wgrad_gmax
     TEM_REQUIRE(!gmax || (z.use && !h16), "tem_conv3d_wgrad_gmax: tem_conv3d_wgrad_gmax_ok() == 0 for this layer");
-    const unsigned* const g_amax = tem_wgrad_gscale_source;   // set by tem_conv3d_wgrad_gscaled for the duration of this call
+    const unsigned* const g_amax = c.g_amax_in;   // tem_conv3d_wgrad_gscaled (h16 == 3 reads it)
     TEM_REQUIRE(h16 != 4 || (z.use && z.tr), "tem_conv3d_wgrad(fp32 on k_conv_wgrad_tr): tem_conv_wgrad_tr_fp32_ok() == 0 for this layer");
     TEM_REQUIRE(h16 != 3 || (g_amax && z.use && (!z.teams || z.tr)),
                 "tem_conv3d_wgrad_gscaled: tem_conv3d_wgrad_gscaled_ok() == 0 for this layer (or no g_amax)");
@@ -1960,7 +1955,7 @@ int tem_conv_wgrad_bf16x3(const float* x, int64_t x_ld, const float* scale, cons
                     "tem_conv3d_wgrad(bf16x3): one z-plane of x / g must stay below 2 GiB (32-bit offsets inside a plane)");
         float* zpart = (float*)ws;
         float* zdb = db ? zpart + tem_align_up((int64_t)z.S * z.ks2 * 27 * Cin * Cout, 64) : nullptr;
-        TEM_REQUIRE(!norm_sums || (db && w_sd && sd_layout && tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw)),
+        TEM_REQUIRE(!norm_sums || (db && w_sd && sd_layout && tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, c.x_cs)),
                     "tem_conv3d_wgrad_sums: this layer cannot deliver the norm sums (tem_conv3d_wgrad_sums_ok() == 0)");
         const unsigned nblk = (unsigned)((int64_t)z.T * z.S);
         // h16: 0 bf16x3 (hi + lo planes, 3 MFMAs per product), 1 one fp16 term, 2 one bf16 term (the mixed-precision modes)
@@ -1981,11 +1976,11 @@ int tem_conv_wgrad_bf16x3(const float* x, int64_t x_ld, const float* scale, cons
             else launch(k0, lb);
         };
         TEM_REQUIRE(!st || z.tr, "tem_conv3d_wgrad: 16-bit storage needs the transposing z-sliding kernel (option wgrad_zs = 3)");
-        TEM_REQUIRE(!tem_call_cs.x || (st && z.tr && tem_call_cs.x % 8 == 0),
+        TEM_REQUIRE(!c.x_cs || (st && z.tr && c.x_cs % 8 == 0),
                     "tem_conv3d_wgrad_ex: a chunk stride (x_cs) needs 16-bit tensors on the transposing z-sliding kernel, x_cs %% 8 == 0");
         if (z.tr)
-            tem_conv_wgrad_tr_launch(h16, nblk, x, x_ld, scale, shift, g, g_ld, zpart, zdb, N, D, H, W, Cin, Cout, z.T, z.nY, z.nX,
-                                     z.zsegs, z.Ss, z.ncz, gmax, g_amax, s);
+            tem_conv_wgrad_tr_launch(c, h16, nblk, x, x_ld, scale, shift, g, g_ld, zpart, zdb, N, D, H, W, Cin, Cout, z.T, z.nY, z.nX,
+                                     z.zsegs, z.Ss, z.ncz, s);
         else if (z.teams)
             go(&k_conv_wgrad_zt<0>, &k_conv_wgrad_zt<1>, &k_conv_wgrad_zt<2>, &k_conv_wgrad_zt<0>,
                2 * (size_t)32 * ZS_CIS + 4 * (size_t)32 * ZS_GS);
@@ -1997,7 +1992,7 @@ int tem_conv_wgrad_bf16x3(const float* x, int64_t x_ld, const float* scale, cons
                2 * (size_t)32 * ZS_CIS + 4 * (size_t)32 * ZS_GS);
         if (norm_sums) {
             float* extra = zdb + tem_align_up((int64_t)z.S * Cout, 64);
-            tem_wgrad_sums_launch(zpart, z.Ss, z.ks2, zdb, g, g_ld, w_sd, gamma, beta, dw, extra, N, D, H, W, Cin, Cout,
+            tem_wgrad_sums_launch(c, zpart, z.Ss, z.ks2, zdb, g, g_ld, w_sd, gamma, beta, dw, extra, N, D, H, W, Cin, Cout,
                                   norm_sums, z.S, db, s);
         } else {
             tem_reduce_slabs_w_db(zpart, z.S * z.ks2, 27, Cin, Cout, (int64_t)27 * Cin * Cout, dw, sd_layout, zdb, z.S, db, s);
@@ -2011,22 +2006,22 @@ int tem_conv_wgrad_bf16x3(const float* x, int64_t x_ld, const float* scale, cons
 #define WGO(KD, KH, KW)                                                                                              \
     do {                                                                                                             \
         if (p.nco == 4)                                                                                              \
-            launch_wb<KD, KH, KW, 4>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);     \
+            launch_wb<KD, KH, KW, 4>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);     \
         else if (p.nco == 2)                                                                                         \
-            launch_wb<KD, KH, KW, 2>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);     \
+            launch_wb<KD, KH, KW, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);     \
         else                                                                                                         \
-            launch_wb<KD, KH, KW, 1>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);     \
+            launch_wb<KD, KH, KW, 1>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);     \
     } while (0)
     if (key == 7) {
         if (p.nco == 2)
-            launch_wb<3, 3, 3, 2>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
+            launch_wb<3, 3, 3, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
         else
-            launch_wb<3, 3, 3, 1, 2>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
+            launch_wb<3, 3, 3, 1, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
     } else if (key == 3) {
         if (p.nco == 2)
-            launch_wb<1, 3, 3, 2>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
+            launch_wb<1, 3, 3, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
         else
-            launch_wb<1, 3, 3, 1, 2>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
+            launch_wb<1, 3, 3, 1, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
     } else if (key == 0) {
         WGO(1, 1, 1);
     } else {

@@ -739,21 +739,21 @@ int64_t tem_splitk_stat_blocks(int64_t V, int Cout) {
     return (V + VB - 1) / VB;
 }
 
-void tem_splitk_epilogue_stats(const float* part, int ksplit, int N, int64_t V, int Cout, const float* bias, int act,
+void tem_splitk_epilogue_stats(int sty, const float* part, int ksplit, int N, int64_t V, int Cout, const float* bias, int act,
                                const float* ref, int64_t ref_ld, float* y, int64_t y_ld, float* stat, hipStream_t s) {
     const int VB = 4 * (256 / (Cout >> 2));
-    TEM_ST_SWITCH(tem_call_st.y, T,
+    TEM_ST_SWITCH(sty, T,
                   hipLaunchKernelGGL((k_splitk_epilogue_stats<false, T>), dim3((unsigned)tem_splitk_stat_blocks(V, Cout), (unsigned)N),
                                      dim3(256), 0, s, part, ksplit, V, Cout, bias, act, (const T*)ref, ref_ld, (T*)y, y_ld, VB, stat,
                                      SplitkNormIn{nullptr, 0, nullptr, nullptr, 1}));
 }
 
 // the epilogue of a DATA GRADIENT that also writes the first stage of the backward of the norm its output lands behind
-void tem_splitk_epilogue_bwd_sums(const float* part, int ksplit, int N, int64_t V, int Cout, const float* bias, int act,
+void tem_splitk_epilogue_bwd_sums(int sty, const float* part, int ksplit, int N, int64_t V, int Cout, const float* bias, int act,
                                   const float* ref, int64_t ref_ld, float* y, int64_t y_ld, const TemDgradSumsReq& rq,
                                   hipStream_t s) {
     const int VB = 4 * (256 / (Cout >> 2));
-    TEM_ST_SWITCH(tem_call_st.y, T,
+    TEM_ST_SWITCH(sty, T,
                   hipLaunchKernelGGL((k_splitk_epilogue_stats<true, T>), dim3((unsigned)tem_splitk_stat_blocks(V, Cout), (unsigned)N),
                                      dim3(256), 0, s, part, ksplit, V, Cout, bias, act, (const T*)ref, ref_ld, (T*)y, y_ld, VB, rq.part,
                                      SplitkNormIn{rq.x, rq.x_ld, rq.mean, rq.rstd, rq.G}));
@@ -777,9 +777,9 @@ int tem_fwd_ksplit(int64_t nblk, int nchunks) {
     return ks;
 }
 
-void tem_splitk_epilogue(const float* part, int ksplit, int64_t NV, int Cout, const float* bias, int act,
+void tem_splitk_epilogue(int sty, const float* part, int ksplit, int64_t NV, int Cout, const float* bias, int act,
                          const float* ref, int64_t ref_ld, float* y, int64_t y_ld, hipStream_t s) {
-    TEM_ST_SWITCH(tem_call_st.y, T,
+    TEM_ST_SWITCH(sty, T,
                   hipLaunchKernelGGL(k_splitk_epilogue<T>, dim3(tem_grid_1d(NV * (Cout / 4), 256)), dim3(256), 0, s, part, ksplit, NV,
                                      Cout, bias, act, (const T*)ref, ref_ld, (T*)y, y_ld));
 }

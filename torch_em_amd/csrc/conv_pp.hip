@@ -531,11 +531,11 @@ struct PpGeom {
 
 // Which shapes run on the ping-pong kernel: 3x3x3 (and 1x3x3 with depth) kernels, two 16-bit planes per operand, and
 // enough (patch, column group) units to give every team of every CU at least one.
-static PpGeom pp_geometry(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
+static PpGeom pp_geometry(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
     PpGeom g = {};
     const long long opt = tem_option(TEM_OPT_CONV_FWD_VARIANT);
     if (opt == 0) return g;   // (2 = z-reuse kernel forced: shapes it does not take still come here)
-    if (tem_call_st.x || tem_call_st.y) return g;   // 16-bit activation storage: the z-reuse / patch kernels carry the element type
+    if (c.stx || c.sty) return g;   // 16-bit activation storage: the z-reuse / patch kernels carry the element type
     if (!(nsplit == 2 || nsplit == 4 || nsplit == 5 || nsplit == 7)) return g;   // bf16x3, fp16x3 (scaled lo), one fp16 / bf16 term (mixed modes)
     if (!(kh == 3 && kw == 3 && (kd == 3 || kd == 1))) return g;
     if (D < 4 || Cin % 16 || Cout % 32) return g;
@@ -559,15 +559,15 @@ static PpGeom pp_geometry(int N, int D, int H, int W, int Cin, int Cout, int kd,
     return g;
 }
 
-int64_t tem_conv_pp_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
-    const PpGeom g = pp_geometry(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
+int64_t tem_conv_pp_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
+    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
     if (!g.variant) return -1;
     return (int64_t)g.nZ * g.nY * g.nX * g.WM;
 }
 
 // 32-column tiles per team of the instantiation this shape selects (1 or 2), 0 when the shape is not handled here
-int tem_conv_pp_tiles(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
-    const PpGeom g = pp_geometry(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
+int tem_conv_pp_tiles(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
+    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
     return g.variant ? g.CT : 0;
 }
 
@@ -600,12 +600,12 @@ static void pp_launch(const PpGeom& g, const float* x, int64_t x_ld, const float
 // -> 1 when the launch was taken, 0 when the shape belongs to another kernel, -1 when the caller sized a statistics
 // buffer for this kernel (tem_conv_pp_stat_blocks) but an alignment condition of the launch fails: falling through to the
 // patch kernel would write a differently shaped partials buffer (tem_last_error is set)
-int tem_conv_fwd_pp(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
+int tem_conv_fwd_pp(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                      const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H,
                      int W, int Cin, int Cout, int kd, int kh, int kw, int act, int nsplit, float* stat, hipStream_t s) {
     int64_t max_ld = x_ld > y_ld ? x_ld : y_ld;
     if (ref && ref_ld > max_ld) max_ld = ref_ld;
-    const PpGeom g = pp_geometry(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
+    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
     if (!g.variant) return 0;
     // 16-byte epilogue accesses; statistics of a masked output are the patch kernel's business (never asked for together)
     if ((y_ld % 4) || ((uintptr_t)y % 16) || (ref && ((ref_ld % 4) || ((uintptr_t)ref % 16))) || (stat && ref) ||

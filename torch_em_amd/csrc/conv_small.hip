@@ -290,11 +290,11 @@ int64_t tem_conv_fwd_cin1_stat_blocks(int D, int H, int W, int Cin, int Cout, in
     return (int64_t)((D + 3) / 4) * ((H + 7) / 8) * ((W + tx - 1) / tx);
 }
 
-bool tem_conv_fwd_cin1(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
+bool tem_conv_fwd_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
                        const float* bias, float* y, int64_t y_ld, const float* ref, int N, int D, int H, int W,
                        int Cin, int Cout, int kd, int kh, int kw, int act, float* stat, hipStream_t s) {
     // Cin 2..4 (RGB / multi-channel raw data) share the kernel; weights stay in LDS, so Cin * Cout is bounded
-    if (Cin > 4 || Cout % 4 || Cin * Cout > 128 || ref || y_ld % 4 || ((uintptr_t)y % tem_st_align4(tem_call_st.y)) ||
+    if (Cin > 4 || Cout % 4 || Cin * Cout > 128 || ref || y_ld % 4 || ((uintptr_t)y % tem_st_align4(c.sty)) ||
         (bias && ((uintptr_t)bias % 16)))
         return false;
     const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
@@ -304,7 +304,7 @@ bool tem_conv_fwd_cin1(const float* x, int64_t x_ld, const float* scale, const f
         const int64_t nblk = (int64_t)N * nZ * nY * nX;
         const int kdv = key == 7 ? 3 : 1;
         const size_t ldsb = (size_t)((kdv + 3) * 10 * (C1R_TXW + 4) + kdv * 9 * Cout) * sizeof(float);
-        TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TY, return false, {
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false, {
             if (key == 7)
                 hipLaunchKernelGGL((k_conv_fwd_c1rows<3, TX, TY>), dim3((unsigned)nblk), dim3(256), ldsb, s, (const TX*)x, x_ld, scale,
                                    shift, w, bias, (TY*)y, y_ld, N, D, H, W, Cout, act, nZ, nY, nX, stat);
@@ -319,7 +319,7 @@ bool tem_conv_fwd_cin1(const float* x, int64_t x_ld, const float* scale, const f
 #define C1(KD_, CI)                                                                                                   \
     case CI: {                                                                                                        \
         size_t ldsb = (size_t)(CI * ((KD_ + 3) * 10 * 12) + KD_ * 9 * CI * Cout) * sizeof(float);                    \
-        TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TY, return false,                                            \
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false,                                            \
                        hipLaunchKernelGGL((k_conv_fwd_cin1<KD_, 3, 3, CI, TX, TY>), dim3((unsigned)nblk), dim3(256), ldsb, s, \
                                           (const TX*)x, x_ld, scale, shift, w, bias, (TY*)y, y_ld, N, D, H, W, Cout, act, nZ, nY, nX, stat)); \
     } break;
@@ -399,7 +399,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_cout1(const EX* __restrict__ x
     }
 }
 
-bool tem_conv_fwd_cout1(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
+bool tem_conv_fwd_cout1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
                         const float* bias, float* y, int64_t y_ld, const float* ref, int N, int D, int H, int W,
                         int Cin, int Cout, int kd, int kh, int kw, int act, hipStream_t s) {
     (void)shift;
@@ -408,7 +408,7 @@ bool tem_conv_fwd_cout1(const float* x, int64_t x_ld, const float* scale, const 
     if (key != 7 && key != 3) return false;
     const int nZ = (D + 3) / 4, nY = (H + 7) / 8, nX = (W + 7) / 8;
     const int64_t nblk = (int64_t)N * nZ * nY * nX;
-    TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TY, return false, {
+    TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false, {
         if (key == 7)
             hipLaunchKernelGGL((k_conv_fwd_cout1<3, 3, 3, TX, TY>), dim3((unsigned)nblk), dim3(256), 0, s, (const TX*)x, x_ld, w, bias,
                                (TY*)y, y_ld, N, D, H, W, Cin, act, nZ, nY, nX);
@@ -855,7 +855,7 @@ void tem_reduce_slabs_w(const float* part, int nchunks, int ntaps, int Cin, int 
 
 int64_t tem_conv_wgrad_cin1_ws(int Cout, int ntaps) { return (int64_t)CIN1_GRID * (ntaps + 1) * Cout * 4; }
 
-bool tem_conv_wgrad_cin1(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
+bool tem_conv_wgrad_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
                          int64_t g_ld, float* dw, float* db, void* ws, int N, int D, int H, int W, int Cin, int Cout,
                          int kd, int kh, int kw, int sd_layout, const float* gnx, int64_t gnx_ld, const float* gcoef,
                          hipStream_t s) {
@@ -874,7 +874,7 @@ bool tem_conv_wgrad_cin1(const float* x, int64_t x_ld, const float* scale, const
     for (int ci = 0; ci < Cin; ++ci) {
         const float* sc = scale ? scale + ci : nullptr;
         const float* sf = scale ? shift + ci : nullptr;
-        TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TG, return false, {
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, return false, {
             if (key == 7) {
                 size_t ldsf = 6 * 10 * 12 > 4 * (NT + 1) * Cout ? 6 * 10 * 12 : 4 * (NT + 1) * Cout;
                 hipLaunchKernelGGL((k_conv_wgrad_cin1<3, 3, 3, TX, TG>), dim3(grid), dim3(256), ldsf * sizeof(float), s, (const TX*)x + ci,
@@ -1013,14 +1013,14 @@ __global__ __launch_bounds__(256) void k_conv1x1_proj_r(const EX* __restrict__ x
     }
 }
 
-bool tem_conv1x1_proj(const float* x, int64_t x_ld, const float* scale, const float* w, const float* bias, float* y,
+bool tem_conv1x1_proj(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* w, const float* bias, float* y,
                       int64_t y_ld, const float* ref, int64_t NV, int Cin, int Cout, int act, hipStream_t s) {
     if (scale || ref || Cin % 32 || x_ld % 4 || ((uintptr_t)x % 16)) return false;
     dim3 grid(tem_grid_1d(NV, 32, 256 * 16));
     // weights in registers where they fit (NJ * COUT <= 32 values per 16-byte piece and lane)
 #define PJR(CO, NJ_)                                                                                                 \
     if (Cout == CO && Cin == 32 * NJ_) {                                                                             \
-        TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TY, return false,                                           \
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false,                                           \
                        hipLaunchKernelGGL((k_conv1x1_proj_r<CO, NJ_, TX, TY>), grid, dim3(256), 0, s, (const TX*)x, x_ld, w, bias, \
                                           (TY*)y, y_ld, NV, act));                                                   \
         return true;                                                                                                 \
@@ -1031,7 +1031,7 @@ bool tem_conv1x1_proj(const float* x, int64_t x_ld, const float* scale, const fl
 #undef PJR
 #define PJ(CO)                                                                                                     \
     case CO:                                                                                                       \
-        TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TY, return false,                                         \
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false,                                         \
                        hipLaunchKernelGGL((k_conv1x1_proj<CO, TX, TY>), grid, dim3(256), 0, s, (const TX*)x, x_ld, w, bias, (TY*)y, \
                                           y_ld, NV, Cin, act));                                                    \
         return true;
@@ -1159,7 +1159,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_proj_wgrad(const EX* __restrict
 #define PROJ_GRID 1024
 int64_t tem_conv1x1_proj_wgrad_ws(int Cin, int Cout) { return (int64_t)PROJ_GRID * (Cin + 1) * Cout * 4; }
 
-bool tem_conv1x1_proj_wgrad(const float* x, int64_t x_ld, const float* scale, const float* g, int64_t g_ld, float* dw,
+bool tem_conv1x1_proj_wgrad(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* g, int64_t g_ld, float* dw,
                             float* db, void* ws, int64_t NV, int Cin, int Cout, int sd_layout, hipStream_t s) {
     if (scale || Cin % 32 || Cin > 128 || x_ld % 4 || ((uintptr_t)x % 16)) return false;
     const int njr = Cin / 32;
@@ -1169,7 +1169,7 @@ bool tem_conv1x1_proj_wgrad(const float* x, int64_t x_ld, const float* scale, co
     float* part = (float*)ws;
     size_t ldsb = (size_t)4 * (Cin + 1) * Cout * sizeof(float);
 #define PWJ(CO, J)                                                                                                \
-    TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TG, return false,                                            \
+    TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, return false,                                            \
                    hipLaunchKernelGGL((k_conv1x1_proj_wgrad<CO, J, false, TX, TG>), dim3(grid), dim3(256), ldsb, s, (const TX*)x, x_ld, \
                                       (const TG*)g, g_ld, part, NV, Cin))
 #define PW(CO)                                                                                                    \
@@ -1200,7 +1200,7 @@ bool tem_conv1x1_proj_wgrad(const float* x, int64_t x_ld, const float* scale, co
 
 // out_conv backward in ONE pass over x: weight / bias gradient of the projection AND its masked data gradient
 // (w: state_dict layout [Cout][Cin]).  false: shape not covered (the caller runs the two separate kernels).
-bool tem_conv1x1_out_bwd(const float* x, int64_t x_ld, const float* g, int64_t g_ld, const float* w, float* gx, int64_t gx_ld,
+bool tem_conv1x1_out_bwd(const TemConvCall& c, const float* x, int64_t x_ld, const float* g, int64_t g_ld, const float* w, float* gx, int64_t gx_ld,
                          float* dw, float* db, void* ws, int64_t NV, int Cin, int Cout, int sd_layout, hipStream_t s) {
     if (Cin % 32 || Cin > 64 || x_ld % 4 || ((uintptr_t)x % 16) || gx_ld % 4 || ((uintptr_t)gx % 16) || ((uintptr_t)w % 16)) return false;
     const int njr = Cin / 32;
@@ -1209,10 +1209,10 @@ bool tem_conv1x1_out_bwd(const float* x, int64_t x_ld, const float* g, int64_t g
     const int grid = (int)(nb < PROJ_GRID ? nb : PROJ_GRID);
     float* part = (float*)ws;
     size_t ldsb = (size_t)4 * (Cin + 1) * Cout * sizeof(float);
-    if (!tem_st2_ok(tem_call_st.x, tem_call_st.y)) return false;
-    unsigned* const amax = tem_take_output_amax();
+    if (!tem_st2_ok(c.stx, c.sty)) return false;
+    unsigned* const amax = c.take_output_amax();
 #define OBJ(CO, J)                                                                                                     \
-    TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TG, return false,                                                 \
+    TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, return false,                                                 \
                    hipLaunchKernelGGL((k_conv1x1_proj_wgrad<CO, J, true, TX, TG>), dim3(grid), dim3(256), ldsb, s, (const TX*)x, x_ld, \
                                       (const TG*)g, g_ld, part, NV, Cin, w, (TX*)gx, gx_ld, amax))
 #define OB(CO)                \
@@ -1282,14 +1282,14 @@ __global__ __launch_bounds__(256) void k_conv1x1_expand(const EX* __restrict__ x
     if (amax) tem_amax_commit(amax, amx);
 }
 
-bool tem_conv1x1_expand(const float* x, int64_t x_ld, const float* scale, const float* w, const float* bias, float* y,
+bool tem_conv1x1_expand(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* w, const float* bias, float* y,
                         int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act,
                         hipStream_t s) {
     if (scale || Cin > 16 || Cout % 4 || y_ld % 4 || ((uintptr_t)y % 16) || ((uintptr_t)w % 16) ||
-        (bias && (uintptr_t)bias % 16) || (ref && (ref_ld % 4 || (uintptr_t)ref % 16)) || !tem_st2_ok(tem_call_st.x, tem_call_st.y))
+        (bias && (uintptr_t)bias % 16) || (ref && (ref_ld % 4 || (uintptr_t)ref % 16)) || !tem_st2_ok(c.stx, c.sty))
         return false;
-    unsigned* const amax = tem_take_output_amax();
-    TEM_ST2_SWITCH(tem_call_st.x, tem_call_st.y, TX, TY, return false,
+    unsigned* const amax = c.take_output_amax();
+    TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false,
                    hipLaunchKernelGGL((k_conv1x1_expand<TX, TY>), dim3(tem_grid_1d(NV * (Cout / 4), 256, 256 * 16)), dim3(256), 0, s,
                                       (const TX*)x, x_ld, w, bias, (TY*)y, y_ld, (const TY*)ref, ref_ld, NV, Cin, Cout, act, amax));
     return true;

@@ -955,10 +955,11 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
 
 // h16: 0 bf16x3, 1 one fp16 term, 2 one bf16 term, 3 fp16 2x1 (g_amax required), 4 exact fp32.  Same arguments, partial-slab format and
 // plan (teams: one (Cin tile, Cout tile) pair per workgroup, KS2 = 1) as k_conv_wgrad_zt.
-void tem_conv_wgrad_tr_launch(int h16, unsigned nblk, const float* x, int64_t x_ld, const float* scale, const float* shift,
+void tem_conv_wgrad_tr_launch(const TemConvCall& c, int h16, unsigned nblk, const float* x, int64_t x_ld, const float* scale, const float* shift,
                               const float* g, int64_t g_ld, float* zpart, float* zdb, int N, int D, int H, int W, int Cin,
-                              int Cout, int T, int nY, int nX, int zsegs, int Ss, int ncz, unsigned* gmax,
-                              const unsigned* g_amax, hipStream_t s) {
+                              int Cout, int T, int nY, int nX, int zsegs, int Ss, int ncz, hipStream_t s) {
+    unsigned* const gmax = c.g_amax_out;
+    const unsigned* const g_amax = c.g_amax_in;
     auto launch = [&](auto kern, size_t lb) {
         static std::set<const void*> sized;   // kernels whose dynamic-LDS limit was raised already
         const void* key = reinterpret_cast<const void*>(kern);
@@ -980,10 +981,10 @@ void tem_conv_wgrad_tr_launch(int h16, unsigned nblk, const float* x, int64_t x_
         }
         hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lb, s, reinterpret_cast<const TS*>(x), x_ld, scale, shift,
                            reinterpret_cast<const TS*>(g), g_ld, zpart, zdb, N, D, H, W, Cin, Cout, T, nY, nX, zsegs, Ss, ncz, gmax, g_amax,
-                           tem_call_cs.x);
+                           c.x_cs);
     };
-    if (tem_call_st.x == 1) launch16(&k_conv_wgrad_tr<1, tem_f16>, XT + GT + 4096, tem_f16{});
-    else if (tem_call_st.x == 2) launch16(&k_conv_wgrad_tr<2, tem_bf16>, XT + GT + 4096, tem_bf16{});
+    if (c.stx == 1) launch16(&k_conv_wgrad_tr<1, tem_f16>, XT + GT + 4096, tem_f16{});
+    else if (c.stx == 2) launch16(&k_conv_wgrad_tr<2, tem_bf16>, XT + GT + 4096, tem_bf16{});
     else if (h16 == 1) launch(&k_conv_wgrad_tr<1>, XT + GT);
     else if (h16 == 2) launch(&k_conv_wgrad_tr<2>, XT + GT);
     else if (h16 == 3) launch(&k_conv_wgrad_tr<3>, 2 * XT + GT);

@@ -1063,14 +1063,14 @@ struct ZrGeom {
 
 // 3x3x3 kernels with two-plane (or the one-term mixed) layouts, 16-byte-vector friendly channel counts and at least one
 // unit per team of every CU (smaller launches stay with k_conv_pp / the split-K patch kernel).
-static ZrGeom zr_geometry(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
+static ZrGeom zr_geometry(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
     ZrGeom g = {};
     const long long opt = tem_option(TEM_OPT_CONV_FWD_VARIANT);
     if (opt == 0 || opt == 1) return g;
-    if (!(nsplit == 2 || nsplit == 4 || nsplit == 5 || nsplit == 7 || (nsplit == 1 && tem_option(TEM_OPT_FP32_ZR) && !tem_call_st.x))) return g;
+    if (!(nsplit == 2 || nsplit == 4 || nsplit == 5 || nsplit == 7 || (nsplit == 1 && tem_option(TEM_OPT_FP32_ZR) && !c.stx))) return g;
     if (!(kd == 3 && kh == 3 && kw == 3)) return g;
     if (D < 4 || Cin % 16 || Cout % 32) return g;
-    if (tem_call_st.x && (Cin % 32 || !(nsplit == 5 || nsplit == 7))) return g;   // 16-bit storage: whole 64-byte records per phase
+    if (c.stx && (Cin % 32 || !(nsplit == 5 || nsplit == 7))) return g;   // 16-bit storage: whole 64-byte records per phase
     if ((int64_t)H * W * 8 * 4 * max_ld >= (1ll << 31)) return g;   // 32-bit byte offsets inside one halo / one patch
     static int ncu = 0;
     if (!ncu) {
@@ -1088,8 +1088,8 @@ static ZrGeom zr_geometry(int N, int D, int H, int W, int Cin, int Cout, int kd,
     return g;
 }
 
-int64_t tem_conv_zr_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
-    const ZrGeom g = zr_geometry(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
+int64_t tem_conv_zr_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
+    const ZrGeom g = zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
     if (!g.ok) return -1;
     return (int64_t)g.nZ * g.nY * g.nX * 4;
 }
@@ -1102,7 +1102,7 @@ static int zr_tile_blocks(const ZrGeom& g) {
 }
 
 template <int NS, bool F16, int MODE, bool KSPLIT = false, bool WIDE = false, typename T = float, bool X32 = false, bool XS = false>
-static void zr_launch(const ZrGeom& g, const float* x_, int64_t x_ld, const float* scale, const float* shift, const float* wp,
+static void zr_launch(const TemConvCall& c, const ZrGeom& g, const float* x_, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                       const float* bias, float* y_, int64_t y_ld, const float* ref_, int64_t ref_ld, int N, int D, int H, int W,
                       int Cin, int Cout, int act, float* stat, const unsigned* in_amax, hipStream_t s, int ks = 1) {
     constexpr size_t ldsb = (size_t)2 * NS * 1080 * 32 + 4 * 32 * 144;   // two tiles + the epilogue's transpose scratch
@@ -1123,10 +1123,10 @@ static void zr_launch(const ZrGeom& g, const float* x_, int64_t x_ld, const floa
     }
     int64_t grid = XS ? g.nunits : (g.nunits + 1) / 2;   // (XS: one team per workgroup)
     if (grid > ncu) grid = ncu;
-    unsigned* const out_amax = (MODE == 2 || MODE == 3) ? tem_take_output_amax() : nullptr;
+    unsigned* const out_amax = (MODE == 2 || MODE == 3) ? c.take_output_amax() : nullptr;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(XS ? 256 : 512), ldsb, s, x, x_ld, scale, shift, reinterpret_cast<const uint4*>(wp),
                        bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, g.nZ, g.nY, g.nX, stat, (int)g.nunits, in_amax, ks,
-                       zr_tile_blocks(g), out_amax, (int64_t)(sizeof(T) == 2 ? tem_call_cs.x : 0), (int64_t)(sizeof(T) == 2 && !KSPLIT ? tem_call_cs.y : 0));
+                       zr_tile_blocks(g), out_amax, (int64_t)(sizeof(T) == 2 ? c.x_cs : 0), (int64_t)(sizeof(T) == 2 && !KSPLIT ? c.y_cs : 0));
 }
 
 // Split-K launch for shapes zr_geometry() declines only because they have too few (tile, column tile) units: the input
@@ -1137,15 +1137,15 @@ static void zr_launch(const ZrGeom& g, const float* x_, int64_t x_ld, const floa
 #endif
 // ks of the split-K launch for this shape (0: not taken): only shapes that zr_geometry() / pp_geometry() decline for
 // their unit count, tiles that are not mostly padding, at least two 16-channel chunks per slice
-int tem_conv_zr_splitk_ks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit) {
+int tem_conv_zr_splitk_ks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit) {
     const long long opt = tem_option(TEM_OPT_CONV_FWD_VARIANT);
     if (opt == 0 || opt == 1 || !tem_option(TEM_OPT_ZR_SPLITK)) return 0;
-    if (!(nsplit == 2 || nsplit == 4 || nsplit == 5 || nsplit == 7 || (nsplit == 1 && tem_option(TEM_OPT_FP32_ZR) && !tem_call_st.x))) return 0;
+    if (!(nsplit == 2 || nsplit == 4 || nsplit == 5 || nsplit == 7 || (nsplit == 1 && tem_option(TEM_OPT_FP32_ZR) && !c.stx))) return 0;
     if (!(kd == 3 && kh == 3 && kw == 3) || D < 4 || Cin % 16 || Cout % 32) return 0;
-    const bool t16 = tem_call_st.x != 0;   // 16-bit storage: slices of whole 32-channel chunks
+    const bool t16 = c.stx != 0;   // 16-bit storage: slices of whole 32-channel chunks
     if (t16 && (Cin % 32 || !(nsplit == 5 || nsplit == 7))) return 0;
-    if (zr_geometry(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, 1).ok) return 0;
-    if (tem_conv_pp_tiles(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, 1)) return 0;
+    if (zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, 1).ok) return 0;
+    if (tem_conv_pp_tiles(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, 1)) return 0;
     static int ncu = 0;
     if (!ncu) {
         ncu = tem_device_cus();
@@ -1161,12 +1161,12 @@ int tem_conv_zr_splitk_ks(int N, int D, int H, int W, int Cin, int Cout, int kd,
     return 0;
 }
 
-int tem_conv_fwd_zr_splitk(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
+int tem_conv_fwd_zr_splitk(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                            const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
                            int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
                            int nsplit, float* stat, hipStream_t s) {
     // stat: [N][tem_conv_zr_splitk_stat_blocks()][Cout][2] -- the epilogue also writes the statistics partials of y
-    const int ks = ws ? tem_conv_zr_splitk_ks(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit) : 0;
+    const int ks = ws ? tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit) : 0;
     if (!ks) return 0;
     if (stat && !tem_splitk_stat_blocks((int64_t)D * H * W, Cout)) return 0;
     if ((int64_t)H * W * 8 * 4 * (x_ld > Cout ? x_ld : Cout) >= (1ll << 31)) return 0;
@@ -1182,20 +1182,20 @@ int tem_conv_fwd_zr_splitk(const float* x, int64_t x_ld, const float* scale, con
     g.ok = 1;
     float* part = (float*)ws;
 #define ZRKS(NS, F16, WIDE)                                                                                            \
-    zr_launch<NS, F16, 0, true, WIDE>(g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,  \
+    zr_launch<NS, F16, 0, true, WIDE>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,  \
                                       TEM_ACT_NONE, nullptr, nullptr, s, ks)
-    const bool wide = (nsplit == 5 || nsplit == 7) && (Cin / 16 / ks) % 2 == 0 && (tem_option(TEM_OPT_ZR_WIDE) || tem_call_st.x);   // slices of whole 32-channel chunks
-    if (tem_call_st.x == 1)
-        zr_launch<2, true, 0, true, true, tem_f16>(g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
+    const bool wide = (nsplit == 5 || nsplit == 7) && (Cin / 16 / ks) % 2 == 0 && (tem_option(TEM_OPT_ZR_WIDE) || c.stx);   // slices of whole 32-channel chunks
+    if (c.stx == 1)
+        zr_launch<2, true, 0, true, true, tem_f16>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
                                                    TEM_ACT_NONE, nullptr, nullptr, s, ks);
-    else if (tem_call_st.x == 2)
-        zr_launch<2, false, 0, true, true, tem_bf16>(g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
+    else if (c.stx == 2)
+        zr_launch<2, false, 0, true, true, tem_bf16>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
                                                      TEM_ACT_NONE, nullptr, nullptr, s, ks);
     else if (nsplit == 1 && tem_option(TEM_OPT_FP32_ZR) == 2)
-        zr_launch<2, false, 0, true, false, float, true, true>(g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
+        zr_launch<2, false, 0, true, false, float, true, true>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
                                                                TEM_ACT_NONE, nullptr, nullptr, s, ks);
     else if (nsplit == 1)
-        zr_launch<2, false, 0, true, false, float, true>(g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
+        zr_launch<2, false, 0, true, false, float, true>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
                                                          TEM_ACT_NONE, nullptr, nullptr, s, ks);
     else if (nsplit == 5 && wide) ZRKS(2, true, true);
     else if (nsplit == 7 && wide) ZRKS(2, false, true);
@@ -1205,49 +1205,50 @@ int tem_conv_fwd_zr_splitk(const float* x, int64_t x_ld, const float* scale, con
     else ZRKS(2, false, false);
 #undef ZRKS
     TemDgradSumsReq rq = {nullptr, 0, nullptr, nullptr, 0, nullptr, 0};
-    if (!stat && tem_bp_wants(TEM_BP_NORM_SUMS)) {
-        const TemByproducts* bp = tem_call_bp;
+    if (!stat && c.wants(TEM_BP_NORM_SUMS)) {
+        const TemByproducts* bp = c.bp;
         rq = TemDgradSumsReq{bp->sums_x, bp->sums_x_ld, bp->sums_mean, bp->sums_rstd, bp->sums_G, bp->sums_part, bp->sums_nblk};
     }
     if (stat)
-        tem_splitk_epilogue_stats(part, ks, N, (int64_t)D * H * W, Cout, bias, act, ref, ref_ld, y, y_ld, stat, s);
+        tem_splitk_epilogue_stats(c.sty, part, ks, N, (int64_t)D * H * W, Cout, bias, act, ref, ref_ld, y, y_ld, stat, s);
     else if (rq.part && rq.x && rq.mean && rq.rstd && rq.nblk == tem_splitk_stat_blocks((int64_t)D * H * W, Cout) && rq.G > 0 &&
              Cout % rq.G == 0 && rq.x_ld % 4 == 0 && ((uintptr_t)rq.x % 16 == 0)) {
-        tem_bp_delivered(TEM_BP_NORM_SUMS);
-        tem_splitk_epilogue_bwd_sums(part, ks, N, (int64_t)D * H * W, Cout, bias, act, ref, ref_ld, y, y_ld, rq, s);
+        c.delivered(TEM_BP_NORM_SUMS);
+        tem_splitk_epilogue_bwd_sums(c.sty, part, ks, N, (int64_t)D * H * W, Cout, bias, act, ref, ref_ld, y, y_ld, rq, s);
     } else
-        tem_splitk_epilogue(part, ks, NV, Cout, bias, act, ref, ref_ld, y, y_ld, s);
+        tem_splitk_epilogue(c.sty, part, ks, NV, Cout, bias, act, ref, ref_ld, y, y_ld, s);
     return 1;
 }
 
 // statistics partial rows per sample when tem_conv_fwd_zr_splitk takes the launch with stat != NULL (-1: it does not)
-int64_t tem_conv_zr_splitk_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit) {
-    if (!tem_conv_zr_splitk_ks(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit)) return -1;
+int64_t tem_conv_zr_splitk_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit) {
+    if (!tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit)) return -1;
     const int64_t nb = tem_splitk_stat_blocks((int64_t)D * H * W, Cout);
     return nb > 0 ? nb : -1;
 }
 
-// tem_conv3d_fwd_gscaled (conv.hip) parks the device pointer of max |input| here around its call; the launch that honours
-// it clears it (so the caller can tell that the prescale really happened)
-thread_local const unsigned* tem_zr_in_amax = nullptr;
-// tem_conv3d_fwd_refnorm parks coef[N][Cout][4] here the same way: the launch applies the ReLU mask of `ref` AND the backward
-// of the norm behind it in its epilogue (MODE 3)
-thread_local const float* tem_zr_ref_coef = nullptr;
-
+// c.in_amax (tem_conv3d_fwd_gscaled): device word with max |input|, the launch prescales its input by a power of two derived from
+// it.  c.ref_coef (tem_conv3d_fwd_refnorm): coef[N][Cout][4], the launch applies the ReLU mask of `ref` AND the backward of the
+// norm behind it in its epilogue (MODE 3).  Only this launcher honours them: a caller that passes one must see 1 come back.
 // -> 1 launched, 0 shape not taken, -1 error (statistics sized for this kernel but the launch cannot take it)
-int tem_conv_fwd_zr(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp, const float* bias,
+static int zr_not_taken(const TemConvCall& c) {
+    if (c.in_amax) tem_set_error("tem_conv3d_fwd_gscaled: the launch did not take the z-reuse kernel (alignment of y / ref?)");
+    if (c.ref_coef) tem_set_error("tem_conv3d_fwd_refnorm: the launch did not take the z-reuse kernel (alignment of y / ref?)");
+    return c.in_amax || c.ref_coef ? -1 : 0;
+}
+int tem_conv_fwd_zr(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp, const float* bias,
                     float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H, int W, int Cin, int Cout,
                     int kd, int kh, int kw, int act, int nsplit, float* stat, hipStream_t s) {
     int64_t max_ld = x_ld > y_ld ? x_ld : y_ld;
     if (ref && ref_ld > max_ld) max_ld = ref_ld;
-    const ZrGeom g = zr_geometry(N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
-    const bool strided = tem_call_cs.x != 0 || tem_call_cs.y != 0;
-    if (strided && (!g.ok || !tem_call_st.x || ref || (tem_call_cs.x && Cin % 32) || (tem_call_cs.x % 8) || (tem_call_cs.y % 8))) {
+    const ZrGeom g = zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
+    const bool strided = c.x_cs != 0 || c.y_cs != 0;
+    if (strided && (!g.ok || !c.stx || ref || (c.x_cs && Cin % 32) || (c.x_cs % 8) || (c.y_cs % 8))) {
         tem_set_error("tem_conv3d_fwd_ex: chunk strides (x_cs / y_cs) need 16-bit tensors on the z-reuse kernel (tem_conv3d_fwd_kernel() "
                       "== 3), no ref, strides %% 8 == 0");
         return -1;
     }
-    if (!g.ok) return 0;
+    if (!g.ok) return zr_not_taken(c);
     if ((y_ld % 4) || ((uintptr_t)y % 16) || (ref && ((ref_ld % 4) || ((uintptr_t)ref % 16))) || (stat && ref) ||
         (bias && ((uintptr_t)bias % 16)) || act == TEM_ACT_SIGMOID) {
         if (stat || strided) {
@@ -1255,76 +1256,74 @@ int tem_conv_fwd_zr(const float* x, int64_t x_ld, const float* scale, const floa
                           "cannot take it (y / ref / bias need 16-byte alignment and ld %% 4 == 0, no ref, no sigmoid)");
             return -1;
         }
-        return 0;
+        return zr_not_taken(c);
     }
 #define ZRGO(NS, F16, WIDE)                                                                                                   \
     do {                                                                                                                      \
         if (stat)                                                                                                             \
-            zr_launch<NS, F16, 1, false, WIDE>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<NS, F16, 1, false, WIDE>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
         else if (ref && rcoef)                                                                                                \
-            zr_launch<NS, F16, 3, false, WIDE>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
+            zr_launch<NS, F16, 3, false, WIDE>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
                                   const_cast<float*>(rcoef), in_amax, s);                                                     \
         else if (ref)                                                                                                         \
-            zr_launch<NS, F16, 2, false, WIDE>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<NS, F16, 2, false, WIDE>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
         else                                                                                                                  \
-            zr_launch<NS, F16, 0, false, WIDE>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<NS, F16, 0, false, WIDE>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
     } while (0)
-    const float* rcoef = tem_zr_ref_coef;
+    const float* rcoef = c.ref_coef;
     if (rcoef) {
         if (!ref || stat || ((uintptr_t)rcoef % 16)) {
             tem_set_error("tem_conv3d_fwd_refnorm: needs ref, no statistics, 16-byte aligned coefficients");
             return -1;
         }
-        tem_zr_ref_coef = nullptr;   // consumed
     }
-    const unsigned* in_amax = tem_zr_in_amax;
+    const unsigned* in_amax = c.in_amax;
     if (in_amax) {
         if (nsplit != 4 || bias || scale || stat) {
             tem_set_error("tem_conv3d_fwd_gscaled: fp16 two-term layout, no bias / norm / statistics");
             return -1;
         }
-        tem_zr_in_amax = nullptr;   // consumed
     }
     // one-term modes: 32 channels per phase whenever the channel count allows it (whole 128-byte lines per staging phase)
     const bool wide = (nsplit == 5 || nsplit == 7) && Cin % 32 == 0 && tem_option(TEM_OPT_ZR_WIDE);
 #define ZRGO16(F16, T)                                                                                                        \
     do {                                                                                                                      \
         if (stat)                                                                                                             \
-            zr_launch<2, F16, 1, false, true, T>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<2, F16, 1, false, true, T>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
         else if (ref && rcoef)                                                                                                \
-            zr_launch<2, F16, 3, false, true, T>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
+            zr_launch<2, F16, 3, false, true, T>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
                                   const_cast<float*>(rcoef), in_amax, s);                                                     \
         else if (ref)                                                                                                         \
-            zr_launch<2, F16, 2, false, true, T>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<2, F16, 2, false, true, T>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
         else                                                                                                                  \
-            zr_launch<2, F16, 0, false, true, T>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<2, F16, 0, false, true, T>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
     } while (0)
 #define ZRGO32S()                                                                                                               \
     do {                                                                                                                      \
         if (stat)                                                                                                             \
-            zr_launch<2, false, 1, false, false, float, true, true>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<2, false, 1, false, false, float, true, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
         else if (ref && rcoef)                                                                                                \
-            zr_launch<2, false, 3, false, false, float, true, true>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
+            zr_launch<2, false, 3, false, false, float, true, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
                                   const_cast<float*>(rcoef), in_amax, s);                                                     \
         else if (ref)                                                                                                         \
-            zr_launch<2, false, 2, false, false, float, true, true>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<2, false, 2, false, false, float, true, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
         else                                                                                                                  \
-            zr_launch<2, false, 0, false, false, float, true, true>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<2, false, 0, false, false, float, true, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
     } while (0)
 #define ZRGO32()                                                                                                                \
     do {                                                                                                                      \
         if (stat)                                                                                                             \
-            zr_launch<2, false, 1, false, false, float, true>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<2, false, 1, false, false, float, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
         else if (ref && rcoef)                                                                                                \
-            zr_launch<2, false, 3, false, false, float, true>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
+            zr_launch<2, false, 3, false, false, float, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
                                   const_cast<float*>(rcoef), in_amax, s);                                                     \
         else if (ref)                                                                                                         \
-            zr_launch<2, false, 2, false, false, float, true>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<2, false, 2, false, false, float, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
         else                                                                                                                  \
-            zr_launch<2, false, 0, false, false, float, true>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
+            zr_launch<2, false, 0, false, false, float, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
     } while (0)
-    if (tem_call_st.x == 1) ZRGO16(true, tem_f16);
-    else if (tem_call_st.x == 2) ZRGO16(false, tem_bf16);
+    if (c.stx == 1) ZRGO16(true, tem_f16);
+    else if (c.stx == 2) ZRGO16(false, tem_bf16);
     else
 #undef ZRGO16
     if (nsplit == 1 && tem_option(TEM_OPT_FP32_ZR) == 2) ZRGO32S();

@@ -39,6 +39,12 @@ long long tem_option(int id);
         }                                      \
     } while (0)
 
+#define TEM_TRY(call)                          \
+    do {                                       \
+        const int rc__ = (call);               \
+        if (rc__ != TEM_OK) return rc__;       \
+    } while (0)
+
 #define TEM_CHECK_LAUNCH(name)                                                   \
     do {                                                                         \
         hipError_t e__ = hipGetLastError();                                      \
@@ -61,23 +67,10 @@ static inline int tem_grid_1d(int64_t work_items, int block, int max_blocks = 25
 
 #define TEM_WAVE 64
 
-// By-products of the call in flight (tem_hip.h: TemByproducts, an explicit argument of the *_ex entry points; capi.hip).
-extern thread_local TemByproducts* tem_call_bp;
-struct TemBpScope {
-    TemByproducts* prev;
-    explicit TemBpScope(TemByproducts* bp) : prev(tem_call_bp) {
-        tem_call_bp = bp;
-        if (bp) bp->delivered = 0;
-    }
-    ~TemBpScope() { tem_call_bp = prev; }
-};
-bool tem_bp_wants(unsigned bit);        // the call in flight asks for by-product `bit` and nothing has delivered it yet
-void tem_bp_delivered(unsigned bit);
 // "output amax": max |y| of the tensor a launch writes, as a by-product (TEM_BP_OUT_AMAX).  A launch site that supports it
-// takes the caller's device word with tem_take_output_amax() (NULL: not asked for); its kernel keeps a per-thread maximum
-// (tem_amax4) and ends with tem_amax_commit() -- wave reduction, then an integer atomicMax of the bit pattern (exact,
-// order-independent) that most waves skip after one plain read of the word.
-unsigned* tem_take_output_amax();
+// takes the caller's device word from its call descriptor (conv_internal.h: TemConvCall::take_output_amax(); NULL: not asked
+// for); its kernel keeps a per-thread maximum (tem_amax4) and ends with tem_amax_commit() -- wave reduction, then an integer
+// atomicMax of the bit pattern (exact, order-independent) that most waves skip after one plain read of the word.
 __device__ __forceinline__ float tem_amax4(float m, float a, float b, float c, float d) {
     return __builtin_fmaxf(__builtin_fmaxf(m, __builtin_fmaxf(__builtin_fabsf(a), __builtin_fabsf(b))),
                            __builtin_fmaxf(__builtin_fabsf(c), __builtin_fabsf(d)));

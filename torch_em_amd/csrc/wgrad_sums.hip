@@ -411,7 +411,7 @@ int64_t tem_wgrad_sums_ws_floats(int N, int D, int H, int Cin, int Cout) {
     return tem_align_up((int64_t)N * 27 * Cin * Cout / 32, 64) + (int64_t)N * (D - 2 + 2 * H) * 9 * Cout;
 }
 
-void tem_wgrad_sums_launch(const float* zpart, int Ss, int ks2, const float* zdb, const float* g, int64_t g_ld,
+void tem_wgrad_sums_launch(const TemConvCall& c, const float* zpart, int Ss, int ks2, const float* zdb, const float* g, int64_t g_ld,
                            const float* w, const float* gamma, const float* beta, float* dw, float* extra, int N, int D,
                            int H, int W, int Cin, int Cout, float* sums, int db_chunks, float* db, hipStream_t s) {
     float* P = extra;
@@ -420,16 +420,16 @@ void tem_wgrad_sums_launch(const float* zpart, int Ss, int ks2, const float* zdb
     int64_t nb = tem_cdiv(n_out, 64);
     if (nb > 4096) nb = 4096;
     const int nb_db = db ? (Cout + 63) / 64 : 0;   // zdb: [db_chunks][Cout] rows -> db
-    const ShellArgs sa = {g, tem_call_st.y, g_ld, D, H, W, planepart};
+    const ShellArgs sa = {g, c.sty, g_ld, D, H, W, planepart};
     hipLaunchKernelGGL(k_reduce_slabs_wsum, dim3((unsigned)(nb + nb_db + ((int64_t)(D - 2 + 2 * H) * N + 1) / 2)), dim3(512),
                        (size_t)2 * 4 * 9 * Cout * sizeof(float), s, zpart,
                        Ss * ks2, N, 27, Cin, Cout, n_out, dw, w, P, (int)nb, zdb, db_chunks, db, nb_db, sa);
     NormCoef nc = {0, 0, 0.0, nullptr, nullptr, nullptr};
     TemWgradCoefReq rq = {0, nullptr, nullptr, nullptr};
-    if (tem_bp_wants(TEM_BP_NORM_COEF)) rq = TemWgradCoefReq{tem_call_bp->coef_G, tem_call_bp->coef_mean, tem_call_bp->coef_rstd, tem_call_bp->coef};
+    if (c.wants(TEM_BP_NORM_COEF)) rq = TemWgradCoefReq{c.bp->coef_G, c.bp->coef_mean, c.bp->coef_rstd, c.bp->coef};
     const int cgn = (rq.coef && rq.mean && rq.rstd && rq.G > 0 && Cin % rq.G == 0) ? Cin / rq.G : 0;
     if (cgn >= 1 && cgn <= 32 && (cgn & (cgn - 1)) == 0 && Cin % cgn == 0) {   // else: not delivered, the caller runs tem_norm_bwd_coef
-        tem_bp_delivered(TEM_BP_NORM_COEF);
+        c.delivered(TEM_BP_NORM_COEF);
         nc.cgn = cgn;
         nc.G = rq.G;
         nc.cnt = (double)((int64_t)D * H * W) * (double)nc.cgn;
