@@ -691,6 +691,53 @@ int tem_dist_loss_grad(const float* p, int64_t p_sn, int64_t p_sc, int64_t p_sv,
                        int64_t t_sc, int64_t t_sv, const float* coef, const float* gout, float* gp, int N, int64_t V,
                        int mask_bg, tem_stream_t stream);
 
+/* ---- clDice: soft skeletonisation and the clDice score (loss/cldice.py:25-108; csrc/cldice.hip) ----------------
+ * Tensors are float [N][C][D][H][W] (ndim 3) or [N][C][1][H][W] (ndim 2: D must be 1 -- 2-D has its own erosion and
+ * tie rules).  "strided": element (n, c, v) at n*sn + c*sc + v*sv (in floats), v the row-major (d, h, w) index, so NCDHW
+ * tensors, NDHWC tensors and channel-sliced views are read in place.  "planar": contiguous [N][C][D][H][W].
+ * Inputs are assumed finite (NaN propagation is out of scope).  Every launch is deterministic (gather form, no
+ * floating-point atomics).
+ *
+ * tem_cldice_ws(what): bytes of 0 the partials of tem_cldice_sums, 1 the erosion ping-pong of a forward that saves
+ * nothing (2 planar tensors), 2 what a forward saves for the backward (e_1..e_{K+1}, skel_0..skel_{K-1}: 2K+1 planar
+ * tensors), 3 the backward scratch (4 planar tensors); -1 for an unknown `what`.
+ *
+ * tem_cldice_step: one fused launch on e (strided, read with a 2-voxel halo; never an output).  mode:
+ *   0 first round   e_next = erode(e), out = relu(e - dilate(e_next))            (skel_0)
+ *   1 round         same, a_in = skel: out = skel + relu(delta - skel*delta)     (multiply, then subtract; out may be a_in)
+ *   2 erode         e_next = erode(e)          3 open  out = dilate(erode(e))    4 dilate  out = dilate(e)
+ *   5 / 6 the pointwise part of the backward of round 0 / round j > 0: b_in = d/d skel_j (6: a_in = skel_{j-1});
+ *     out = h = -(d/d delta_j)[delta_j > 0], the gradient arriving at dilate(e_{j+1}) (-h arrives at e_j directly);
+ *     6: out2 = d/d skel_{j-1} (may be b_in).
+ *   a_in, b_in, e_next, out, out2 are planar; those a mode does not use may be NULL (e_next too: the erosion is not kept).
+ * tem_cldice_dilate_bwd: out = add + (backward of dilate at e applied to h); the gradient of a window goes to its FIRST
+ *   maximum in (d, h, w) scan order.  h, add (may be NULL, may be out), out planar; e strided.
+ * tem_cldice_erode_bwd: out = -h + cdir*direct + (backward of erode at e applied to g); per axis the gradient goes to the
+ *   FIRST minimum of the line; min(a, b) gives the smaller operand everything and on equality each half (3-D
+ *   min(min(p_z, p_y), p_x): 1/4, 1/4, 1/2 when all are equal).  g, h (may be NULL), direct (may be NULL) planar; with
+ *   direct, cdir = coef[2] * gout[0] (device floats).  out strided (on, oc, ov): the prediction's own layout.
+ * tem_cldice_sums + tem_cldice_finalize: sums = { sum skel_x*t, sum skel_x, sum skel_t*x, sum skel_t } (device double[4],
+ *   fixed-order double reduction), out = score (invert: 1 - score) with both clamp(min=eps) (loss/cldice.py:101-106),
+ *   coef float[4]: d out / d skel_x = coef[0]*t + coef[1], d out / d x = coef[2]*skel_t (+ through skel_x), coef[3] = 0;
+ *   clamp gradients included.  No host sync.  ws: tem_cldice_ws(.., 0) bytes, shared by the two calls.
+ * tem_cldice_grad: gs = gout[0] * (coef[0]*t + coef[1]) (planar): the upstream of the skeleton backward. */
+int64_t tem_cldice_ws(int N, int C, int64_t V, int num_iter, int what);
+int tem_cldice_step(const float* e, int64_t sn, int64_t sc, int64_t sv, const float* a_in, const float* b_in,
+                    float* e_next, float* out, float* out2, int N, int C, int D, int H, int W, int ndim, int mode,
+                    tem_stream_t stream);
+int tem_cldice_dilate_bwd(const float* e, int64_t sn, int64_t sc, int64_t sv, const float* h, const float* add, float* out,
+                          int N, int C, int D, int H, int W, int ndim, tem_stream_t stream);
+int tem_cldice_erode_bwd(const float* e, int64_t sn, int64_t sc, int64_t sv, const float* g, const float* h,
+                         const float* direct, const float* coef, const float* gout, float* out, int64_t on, int64_t oc,
+                         int64_t ov, int N, int C, int D, int H, int W, int ndim, tem_stream_t stream);
+int tem_cldice_sums(const float* skel_x, const float* skel_t, const float* x, int64_t x_sn, int64_t x_sc, int64_t x_sv,
+                    const float* t, int64_t t_sn, int64_t t_sc, int64_t t_sv, int N, int C, int64_t V, void* ws,
+                    int64_t ws_bytes, tem_stream_t stream);
+int tem_cldice_finalize(const void* ws, double eps, int invert, double* sums, float* out, float* coef,
+                        tem_stream_t stream);
+int tem_cldice_grad(const float* t, int64_t t_sn, int64_t t_sc, int64_t t_sv, const float* coef, const float* gout,
+                    float* gs, int N, int C, int64_t V, tem_stream_t stream);
+
 /* ---- SPOCO / contrastive embedding losses --------------------
  * Embeddings: float [E][V] planes of ONE sample, voxel-fastest, channel stride cs (>= V); labels int64 [V],
  * consecutive ids 0..C-1.  E <= 32.  Per-slice Dice terms see the volume as [nz][V/nz] (nz = first spatial

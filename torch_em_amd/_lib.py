@@ -133,6 +133,15 @@ SIGNATURES = {
                                   c_double, c_double, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),
     "tem_dist_loss_grad": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_int, c_i64,
                                    c_int, c_vp]),
+    "tem_cldice_ws": (c_i64, [c_int, c_int, c_i64, c_int, c_int]),
+    "tem_cldice_step": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp] + [c_int] * 7 + [c_vp]),
+    "tem_cldice_dilate_bwd": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp] + [c_int] * 6 + [c_vp]),
+    "tem_cldice_erode_bwd": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_i64, c_i64]
+                             + [c_int] * 6 + [c_vp]),
+    "tem_cldice_sums": (c_int, [c_vp, c_vp, c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_i64,
+                                c_vp, c_i64, c_vp]),
+    "tem_cldice_finalize": (c_int, [c_vp, c_double, c_int, c_vp, c_vp, c_vp, c_vp]),
+    "tem_cldice_grad": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_int, c_int, c_i64, c_vp]),
     "tem_nchw_to_nhwc": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_i64, c_vp]),
     "tem_nhwc_to_nchw": (c_int, [c_vp, c_i64, c_vp, c_int, c_int, c_i64, c_vp]),
     "tem_standardize": (c_int, [c_vp, c_vp, c_int, c_i64, c_float, c_vp, c_i64, c_vp]),

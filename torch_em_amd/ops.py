@@ -1072,6 +1072,197 @@ def dice_grad(p, t, mask, ca, cb, gout, gout_per_channel, channels_last: bool):
     return gp
 
 
+# ---------------------------------------------------------------- clDice ----
+# modes of tem_cldice_step (include/tem_hip.h)
+CLD_ROUND0, CLD_ROUND, CLD_ERODE, CLD_OPEN, CLD_DILATE, CLD_BWD_POINT0, CLD_BWD_POINT = range(7)
+
+
+def _cld_geo(x: torch.Tensor):
+    """x [N, C, (D,) H, W] -> (x, (sn, sc, sv), (N, C, D, H, W, ndim)); read in place when its spatial dims collapse to
+    one voxel stride (NCDHW, NDHWC, channel-sliced views), copied otherwise"""
+    if x.dim() not in (4, 5):
+        raise ValueError(f"cldice: expected a 4d [N,C,H,W] or 5d [N,C,D,H,W] tensor, got {tuple(x.shape)}")
+    if x.dtype != torch.float32:
+        raise ValueError(f"cldice: expected float32, got {x.dtype}")
+    _req_cuda(x)
+    st = _ncv_strides(x)
+    if st is None:
+        x = x.contiguous()
+        st = _ncv_strides(x)
+    N, C = x.shape[:2]
+    D = x.shape[2] if x.dim() == 5 else 1
+    H, W = x.shape[-2:]
+    if min(N, C, D, H, W) < 1:
+        raise ValueError(f"cldice: empty tensor {tuple(x.shape)}")
+    return x, st[:3], (N, C, D, H, W, x.dim() - 2)
+
+
+def _cld_scratch(count: int, like_shape, device, numel: int):
+    """`count` planar fp32 tensors carved from the stream's static workspace"""
+    ws = _workspace(count * numel * 4, device)
+    return [ws[i * numel * 4:(i + 1) * numel * 4].view(torch.float32).view(like_shape) for i in range(count)]
+
+
+def _cld_step(lib, e, st, geo, a_in, b_in, e_next, out, out2, mode):
+    _lib.check(lib.tem_cldice_step(_p(e), st[0], st[1], st[2], _p(a_in), _p(b_in), _p(e_next), _p(out), _p(out2), *geo,
+                                   mode, _stream(e)), "tem_cldice_step")
+
+
+def _planar_st(geo):
+    N, C, D, H, W, _ = geo
+    V = D * H * W
+    return (C * V, V, 1)
+
+
+def cldice_morph(x: torch.Tensor, mode: int):
+    """soft_erode / soft_open / soft_dilate of x (one fused launch); -> (out, e1) with e1 = erode(x), kept for the
+    backward of the opening (None otherwise)"""
+    x, st, geo = _cld_geo(x)
+    out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    e1 = None
+    if mode == CLD_ERODE:
+        _cld_step(lib, x, st, geo, None, None, out, None, None, CLD_ERODE)
+    elif mode == CLD_OPEN:
+        e1 = torch.empty_like(out)
+        _cld_step(lib, x, st, geo, None, None, e1, None, None, CLD_ERODE)
+        _cld_step(lib, x, st, geo, None, None, None, out, None, CLD_OPEN)
+    elif mode == CLD_DILATE:
+        _cld_step(lib, x, st, geo, None, None, None, out, None, CLD_DILATE)
+    else:
+        raise ValueError(f"cldice_morph: mode {mode}")
+    return out, e1
+
+
+def _cld_out(x, channels_last: bool):
+    """an empty gradient laid out like the prediction: channels-last memory when it is, planar otherwise"""
+    N, C = x.shape[:2]
+    V = x[0, 0].numel()
+    if channels_last:
+        phys = torch.empty((N,) + tuple(x.shape[2:]) + (C,), dtype=torch.float32, device=x.device)
+        return phys.permute(0, phys.dim() - 1, *range(1, phys.dim() - 1)), (V * C, 1, C)
+    return torch.empty(x.shape, dtype=torch.float32, device=x.device), (C * V, V, 1)
+
+
+def cldice_morph_bwd(x: torch.Tensor, e1, g: torch.Tensor, mode: int, channels_last: bool = False) -> torch.Tensor:
+    """gradient of cldice_morph's output w.r.t. x for the upstream g (gather form, PyTorch's tie rules)"""
+    x, st, geo = _cld_geo(x)
+    g = g.to(torch.float32).contiguous()
+    lib = _lib.load()
+    out, os_ = _cld_out(x, channels_last)
+    if mode == CLD_DILATE:
+        if os_[2] != 1:   # the dilation backward writes planar
+            out, os_ = _cld_out(x, False)
+        _lib.check(lib.tem_cldice_dilate_bwd(_p(x), st[0], st[1], st[2], _p(g), None, _p(out), *geo, _stream(x)),
+                   "tem_cldice_dilate_bwd")
+        return out
+    if mode == CLD_OPEN:
+        g1 = torch.empty_like(g)
+        pst = _planar_st(geo)
+        _lib.check(lib.tem_cldice_dilate_bwd(_p(e1), pst[0], pst[1], pst[2], _p(g), None, _p(g1), *geo, _stream(x)),
+                   "tem_cldice_dilate_bwd")
+        g = g1
+    _lib.check(lib.tem_cldice_erode_bwd(_p(x), st[0], st[1], st[2], _p(g), None, None, None, None, _p(out), os_[0], os_[1],
+                                        os_[2], *geo, _stream(x)), "tem_cldice_erode_bwd")
+    return out
+
+
+def cldice_skel_fwd(x: torch.Tensor, num_iter: int, save: bool):
+    """soft skeleton of x: num_iter + 1 fused rounds (tem_cldice_step).  -> (skel planar [N, C, ...], saved) with
+    saved = (x as read, estack [K+1, ...] = e_1..e_{K+1}, sstack [K, ...] = skel_0..skel_{K-1}) from torch's allocator
+    when `save`, else None (the erosions then ping-pong in the stream's workspace)"""
+    K = int(num_iter)
+    if K < 0:
+        raise ValueError("cldice: num_iter must not be negative")
+    x, st, geo = _cld_geo(x)
+    lib = _lib.load()
+    pst = _planar_st(geo)
+    skel = torch.empty(x.shape, dtype=torch.float32, device=x.device)
+    if save:
+        estack = torch.empty((K + 1,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+        sstack = torch.empty((K,) + tuple(x.shape), dtype=torch.float32, device=x.device)
+        enext = [estack[j] for j in range(K + 1)]
+        souts = [sstack[j] for j in range(K)] + [skel]
+    else:
+        pp = _cld_scratch(2, x.shape, x.device, x.numel())
+        enext = [pp[j % 2] for j in range(K)] + [None]   # the last erosion is not kept
+        souts = [skel] * (K + 1)                          # updated in place
+    e, est = x, st
+    for j in range(K + 1):
+        _cld_step(lib, e, est, geo, souts[j - 1] if j else None, None, enext[j], souts[j], None, CLD_ROUND if j else CLD_ROUND0)
+        e, est = enext[j], pst
+    return skel, ((x, estack, sstack) if save else None)
+
+
+def cldice_skel_bwd(saved, gs: torch.Tensor, channels_last: bool, direct=None, coef=None, gout=None,
+                    gs_is_scratch: bool = False) -> torch.Tensor:
+    """d / d x of the soft skeleton for the upstream gs (planar), rounds in reverse: point, dilate, erode (gather
+    form).  direct / coef / gout: the clDice term coef[2] * gout * direct added in the last launch.  The gradient is
+    laid out like the prediction (channels-last memory when `channels_last`)."""
+    x, estack, sstack = saved
+    x, st, geo = _cld_geo(x)
+    lib = _lib.load()
+    K = sstack.shape[0]
+    pst = _planar_st(geo)
+    n = x.numel()
+    bufs = _cld_scratch(4, x.shape, x.device, n)
+    h, b0, b1 = bufs[0], bufs[1], bufs[2]
+    if gs_is_scratch:
+        gsb = gs                      # already ours to overwrite
+    else:
+        gsb = bufs[3]
+        gsb.copy_(gs.to(torch.float32))
+    out, os_ = _cld_out(x, channels_last)
+    stream = _stream(x)
+    for j in range(K, -1, -1):
+        e, est = (estack[j - 1], pst) if j else (x, st)
+        if j:
+            _cld_step(lib, e, est, geo, sstack[j - 1], gsb, None, h, gsb, CLD_BWD_POINT)
+        else:
+            _cld_step(lib, e, est, geo, None, gsb, None, h, None, CLD_BWD_POINT0)
+        _lib.check(lib.tem_cldice_dilate_bwd(_p(estack[j]), pst[0], pst[1], pst[2], _p(h), _p(b0) if j < K else None,
+                                             _p(b1), *geo, stream), "tem_cldice_dilate_bwd")
+        if j:
+            _lib.check(lib.tem_cldice_erode_bwd(_p(e), est[0], est[1], est[2], _p(b1), _p(h), None, None, None, _p(b0),
+                                                pst[0], pst[1], pst[2], *geo, stream), "tem_cldice_erode_bwd")
+        else:
+            _lib.check(lib.tem_cldice_erode_bwd(_p(e), est[0], est[1], est[2], _p(b1), _p(h), _p(direct), _p(coef), _p(gout),
+                                                _p(out), os_[0], os_[1], os_[2], *geo, stream), "tem_cldice_erode_bwd")
+    return out
+
+
+def cldice_score_fwd(x, t, skel_x, skel_t, eps: float, invert: bool):
+    """-> (out float[1], coef float[4], sums double[4]) of the clDice score (tem_cldice_sums + tem_cldice_finalize)"""
+    x, xs, geo = _cld_geo(x)
+    t, ts, _ = _cld_geo(t)
+    N, C, D, H, W, _ = geo
+    V = D * H * W
+    lib = _lib.load()
+    nws = lib.tem_cldice_ws(N, C, V, 0, 0)
+    ws = _workspace(nws, x.device)
+    sums = torch.empty((4,), dtype=torch.float64, device=x.device)
+    out = torch.empty((1,), dtype=torch.float32, device=x.device)
+    coef = torch.empty((4,), dtype=torch.float32, device=x.device)
+    _lib.check(lib.tem_cldice_sums(_p(skel_x), _p(skel_t), _p(x), xs[0], xs[1], xs[2], _p(t), ts[0], ts[1], ts[2], N, C, V,
+                                   _p(ws), nws, _stream(x)), "tem_cldice_sums")
+    _lib.check(lib.tem_cldice_finalize(_p(ws), float(eps), int(invert), _p(sums), _p(out), _p(coef), _stream(x)),
+               "tem_cldice_finalize")
+    return out, coef, sums
+
+
+def cldice_score_bwd(saved, t, skel_t, coef, gout, channels_last: bool) -> torch.Tensor:
+    """d score / d x: the seed gout * (coef[0] t + coef[1]) (tem_cldice_grad) through the skeleton backward, plus the
+    direct part coef[2] * gout * skel_t"""
+    x = saved[0]
+    t, ts, geo = _cld_geo(t)
+    N, C, D, H, W, _ = geo
+    V = D * H * W
+    gs = _cld_scratch(4, x.shape, x.device, x.numel())[3]
+    _lib.check(_lib.load().tem_cldice_grad(_p(t), ts[0], ts[1], ts[2], _p(coef), _p(gout), _p(gs), N, C, V, _stream(t)),
+               "tem_cldice_grad")
+    return cldice_skel_bwd(saved, gs, channels_last, direct=skel_t, coef=coef, gout=gout, gs_is_scratch=True)
+
+
 # ------------------------------------------------------------- optimizer ----
 def bump_versions(tensors):
     """The kernels below write parameters through raw pointers, which autograd's version counters do not see;
