@@ -120,15 +120,28 @@ int tem_get_option(const char* name, int64_t* value);
  * transpose==1 packs the data-gradient operator: taps flipped, Cin<->Cout
  * swapped, so that dgrad is again a tem_conv3d_fwd call.
  */
-#define TEM_WL_GENERIC 0
-#define TEM_WL_MFMA 1
-#define TEM_WL_BF16X3 2
-#define TEM_WL_BF16X6 3
-#define TEM_WL_F16X3 4  /* like BF16X3 with two fp16 terms per weight (22 mantissa bits), lo plane stored x 2^12 */
-#define TEM_WL_F16 5    /* ONE fp16 term per weight (half the bytes): the mixed-precision mode, use_mfma 5 */
-#define TEM_WL_BF16 7   /* ONE bf16 term per weight: mixed precision with mixed_precision_dtype="bfloat16", use_mfma 7 */
-#define TEM_WL_F16X3S 6 /* two fp16 terms of the weight x 2^7 (both terms carry the prescale; activations are staged x 2^5,
-                           the kernel's epilogue multiplies by 2^-12): one accumulator for all three products, use_mfma 6 */
+/* The arithmetic mode of a convolution call: the low byte of `use_mfma` (tem_conv3d_fwd below describes each).  What a mode
+ * means to the kernels -- weight planes, pack kind, operand element, native 16-bit storage, weight-gradient kind -- is ONE
+ * table, csrc/conv_arith.h. */
+#define TEM_ARITH_VALU 0
+#define TEM_ARITH_FP32 1    /* exact fp32 */
+#define TEM_ARITH_BF16X3 2
+#define TEM_ARITH_BF16X6 3
+#define TEM_ARITH_F16X3 4
+#define TEM_ARITH_F16 5     /* one fp16 term */
+#define TEM_ARITH_F16X3S 6  /* fp16x3 with prescaled operands */
+#define TEM_ARITH_BF16 7    /* one bf16 term */
+#define TEM_ARITH_F16X2 8   /* fp16 2x1: weight gradient only */
+/* Every mode but the last reads its own weight layout: a layout IS the mode it serves. */
+#define TEM_WL_GENERIC TEM_ARITH_VALU
+#define TEM_WL_MFMA TEM_ARITH_FP32
+#define TEM_WL_BF16X3 TEM_ARITH_BF16X3
+#define TEM_WL_BF16X6 TEM_ARITH_BF16X6
+#define TEM_WL_F16X3 TEM_ARITH_F16X3   /* like BF16X3 with two fp16 terms per weight (22 mantissa bits), lo plane stored x 2^12 */
+#define TEM_WL_F16 TEM_ARITH_F16       /* ONE fp16 term per weight (half the bytes): the mixed-precision mode, use_mfma 5 */
+#define TEM_WL_BF16 TEM_ARITH_BF16     /* ONE bf16 term per weight: mixed precision with mixed_precision_dtype="bfloat16", use_mfma 7 */
+#define TEM_WL_F16X3S TEM_ARITH_F16X3S /* two fp16 terms of the weight x 2^7 (both terms carry the prescale; activations are staged x 2^5,
+                                          the kernel's epilogue multiplies by 2^-12): one accumulator for all three products, use_mfma 6 */
 #define TEM_ACT_NONE 0
 #define TEM_ACT_RELU 1
 #define TEM_ACT_SIGMOID 2
@@ -136,8 +149,11 @@ int tem_get_option(const char* name, int64_t* value);
 int64_t tem_conv_packed_size(int Cout, int Cin, int kd, int kh, int kw); /* floats */
 int tem_conv_pack_weights(const float* w, float* dst, int Cout, int Cin, int kd, int kh, int kw,
                           int transpose, int layout, tem_stream_t stream);
-/* All split-layout (TEM_WL_BF16X3 / BF16X6 / F16X3) packs of a model in ONE launch.  descs_dev: device array of n
- * records { const float* w; void* dst; int32 Cout, Cin, kd, kh, kw, transpose, nsplit(1|2|3), fp16(0 bf16 | 1 fp16 | 2 fp16 with the lo plane scaled by 2^12 = TEM_WL_F16X3); int64 begin }
+/* All packs of a model in ONE launch.  descs_dev: device array of n
+ * records { const float* w; void* dst; int32 Cout, Cin, kd, kh, kw, transpose, planes(0 generic fp32 layout | 1 | 2 | 3),
+ * kind(0 bf16 | 1 fp16 | 2 fp16 with the lo plane scaled by 2^12 = TEM_WL_F16X3 | 3 fp16 of the weight prescaled by 2^7 =
+ * TEM_WL_F16X3S | 4 raw fp32 = TEM_WL_MFMA, tem_conv_pack_weights_tiles only); int64 begin } -- (planes, kind) of a mode: the
+ * table in csrc/conv_arith.h
  * (56 bytes each, `begin` = running offset in units of 8 weights, ascending); total = sum of Cout*Cin*taps/8.  Same result as n calls
  * of tem_conv_pack_weights. */
 int tem_conv_pack_weights_batch(const void* descs_dev, int n, int64_t total, tem_stream_t stream);

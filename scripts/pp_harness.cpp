@@ -76,10 +76,8 @@ int main(int argc, char** argv) {
         }
     }
     hipStream_t s = 0;
-    if (mode == 1) {   // exact fp32 on the z-reuse kernel (round 6): the TEM_WL_MFMA pack
-        if (tem_conv_pack_weights(w, wp, Cout, Cin, 3, 3, 3, 0, TEM_WL_MFMA, s)) { printf("pack failed: %s\n", tem_last_error()); return 1; }
-    } else
-    tem_pack_weights_bf16x3(w, wp, Cout, Cin, 3, 3, 3, 0, mode, s);
+    // the layout of a mode is the mode (tem_hip.h: TEM_WL_* are defined as TEM_ARITH_*)
+    if (tem_conv_pack_weights(w, wp, Cout, Cin, 3, 3, 3, 0, mode, s)) { printf("pack failed: %s\n", tem_last_error()); return 1; }
     void* ws = nullptr;
     const int64_t wsb = tem_conv_fwd_mfma_ws(N, D, H, W, Cin, Cout, 3, 3, 3);
     if (wsb) CK(hipMalloc(&ws, wsb));

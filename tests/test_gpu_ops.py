@@ -1388,6 +1388,7 @@ def test_masked_dice_broadcast_mask_and_ignore_label():
 def test_batched_weight_repack_is_bit_identical():
     """The one-launch re-pack after an optimizer step (tem_conv_pack_weights_tiles: coalesced tile reads through LDS, and
     tem_conv_pack_weights_batch for the rest) writes exactly what the per-tensor tem_conv_pack_weights writes."""
+    from torch_em_amd.arith import Arith
     ops = _ops()
     g = torch.Generator().manual_seed(11)
     shapes = [(32, 16, (3, 3, 3)), (64, 32, (1, 3, 3)), (32, 32, (1, 1, 1)), (96, 48, (3, 3, 3)), (256, 128, (3, 3, 3)),
@@ -1399,12 +1400,14 @@ def test_batched_weight_repack_is_bit_identical():
             cin_e, cout_e = (cout, cin) if transpose else (cin, cout)
             if cin_e % 16 or cout_e % 32:
                 continue
-            for mode in (1, 2, 3, 4, 5):   # 1 (round 6): the exact-fp32 layout TEM_WL_MFMA through the tile kernel (code 4)
+            for mode in (1, 2, 3, 4, 5, 6, 7):   # 1 (round 6): the exact-fp32 layout TEM_WL_MFMA through the tile kernel (code 4)
                 if mode == 1 and k[0] * k[1] * k[2] > 27:
                     continue
                 ref = ops.pack_weights(w, transpose=transpose, mfma=mode)
                 dst = torch.full_like(ref, float("nan"))
-                nsplit, fp16 = (3 if mode == 3 else 1 if mode == 5 else 2), {4: 2, 5: 1, 1: 4}.get(mode, 0)
+                # (planes, pack kind) as literals: an independent pin of the table every caller reads (torch_em_amd/arith.py)
+                nsplit, fp16 = (3 if mode == 3 else 1 if mode in (5, 7) else 2), {4: 2, 5: 1, 6: 3, 1: 4}.get(mode, 0)
+                assert Arith(mode).pack == (nsplit, fp16), mode
                 jobs.append((w, dst, cout, cin, k, int(transpose), nsplit, fp16))
                 expect.append((ref, dst, (cout, cin, k, transpose, mode)))
     tab = ops.pack_table(jobs)

@@ -5,6 +5,7 @@
 // (HBM-bound, 0.9 flop/B) and the small test networks.
 #include "tem_common.h"
 #include "conv_internal.h"
+#include "conv_arith.h"
 #include "tem_act.h"
 
 // `use_mfma` of the conv entry points carries the storage types of the call in its high bits (tem_hip.h: TEM_MFMA_STX / _STY):
@@ -60,10 +61,8 @@ extern "C" int tem_conv_pack_weights(const float* w, float* dst, int Cout, int C
     TEM_REQUIRE(w && dst && Cout > 0 && Cin > 0, "tem_conv_pack_weights: bad arguments");
     TEM_REQUIRE((kd == 1 || kd == 3) && (kh == 1 || kh == 3) && (kw == 1 || kw == 3),
                 "tem_conv_pack_weights: kernel size (%d,%d,%d) not supported (1 or 3 per axis)", kd, kh, kw);
-    if (layout == TEM_WL_BF16X3 || layout == TEM_WL_BF16X6 || layout == TEM_WL_F16X3 || layout == TEM_WL_F16 || layout == TEM_WL_F16X3S ||
-        layout == TEM_WL_BF16) {
-        int rc = tem_pack_weights_bf16x3(w, dst, Cout, Cin, kd, kh, kw, transpose,
-                                         layout == TEM_WL_BF16X6 ? 3 : (layout == TEM_WL_F16X3 ? 4 : (layout == TEM_WL_F16 ? 5 : (layout == TEM_WL_F16X3S ? 6 : (layout == TEM_WL_BF16 ? 7 : 2)))),
+    if (tem_layout_is_split(layout)) {
+        int rc = tem_pack_weights_bf16x3(w, dst, Cout, Cin, kd, kh, kw, transpose, tem_arith(layout).planes, tem_arith(layout).pack,
                                          (hipStream_t)stream);
         if (rc != TEM_OK) return rc;
         TEM_CHECK_LAUNCH("tem_conv_pack_weights(bf16x3)");
@@ -253,7 +252,7 @@ extern "C" int64_t tem_conv3d_fwd_ws(int N, int D, int H, int W, int Cin, int Co
     const TemConvCall c = conv_call(use_mfma);
     if (!use_mfma || Cin % 16 || Cout % 32) return 0;
     int64_t ws = tem_conv_fwd_mfma_ws(N, D, H, W, Cin, Cout, kd, kh, kw);
-    if (use_mfma >= 1 && use_mfma <= 7) {   // the z-reuse kernel's split-K launch may want more slices than the patch kernel's
+    if (tem_arith_mfma_fwd(use_mfma)) {   // the z-reuse kernel's split-K launch may want more slices than the patch kernel's
         const int64_t zk = (int64_t)tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma) * N * D * H * W * Cout * 4;
         if (zk > ws) ws = zk;
     }
@@ -276,25 +275,25 @@ static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, c
     const int stx = c.stx, sty = c.sty;
     TEM_REQUIRE(stx >= 0 && stx <= 2 && sty >= 0 && sty <= 2 && (stx == 0 || sty == 0 || stx == sty),
                 "tem_conv3d_fwd: unsupported storage types (x %d, y %d)", stx, sty);
-    TEM_REQUIRE(!(stx || sty) || use_mfma != 1, "tem_conv3d_fwd: the exact-fp32 MFMA kernels take fp32 tensors only");
+    TEM_REQUIRE(!(stx || sty) || use_mfma != TEM_ARITH_FP32, "tem_conv3d_fwd: the exact-fp32 MFMA kernels take fp32 tensors only");
     hipStream_t s = (hipStream_t)stream;
-    TEM_REQUIRE(!(c.x_cs || c.y_cs) || use_mfma == 5 || use_mfma == 7, "tem_conv3d_fwd_ex: chunk strides need use_mfma 5 / 7");
-    if (use_mfma >= 2 && use_mfma <= 7) {
+    TEM_REQUIRE(!(c.x_cs || c.y_cs) || tem_arith_one_term(use_mfma), "tem_conv3d_fwd_ex: chunk strides need use_mfma 5 / 7");
+    if (tem_arith_split_fwd(use_mfma)) {
         int rc = tem_conv_fwd_bf16x3(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H,
                                      W, Cin, Cout, kd, kh, kw, act, use_mfma, stat, s);
         if (rc != TEM_OK) return rc;
         TEM_CHECK_LAUNCH("tem_conv3d_fwd(bf16x3)");
         return TEM_OK;
     }
-    if (use_mfma == 1 && Cin % 16 == 0 && Cout % 32 == 0 && x_ld % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w_packed % 16 == 0) &&
+    if (use_mfma == TEM_ARITH_FP32 && Cin % 16 == 0 && Cout % 32 == 0 && x_ld % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w_packed % 16 == 0) &&
         (!scale || (((uintptr_t)scale % 16 == 0) && ((uintptr_t)shift % 16 == 0)))) {
         // exact fp32 on the z-reuse team kernel (k_conv_zr<..., X32>, round 6): the levels with enough units directly, the
         // 16^3 / 8^3 levels with split input channels; other shapes stay with k_conv_fwd_mfma[_p] below
         const int zr = tem_conv_fwd_zr(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw,
-                                       act, 1, stat, s);
+                                       act, TEM_ARITH_FP32, stat, s);
         if (zr < 0) return TEM_EINVAL;
         if (!zr && tem_conv_fwd_zr_splitk(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
-                                          Cout, kd, kh, kw, act, 1, stat, s)) {
+                                          Cout, kd, kh, kw, act, TEM_ARITH_FP32, stat, s)) {
             TEM_CHECK_LAUNCH("tem_conv3d_fwd(fp32, z-reuse split-K)");
             return TEM_OK;
         }
@@ -385,20 +384,20 @@ static FwdPlan fwd_plan(const TemConvCall& c, int N, int D, int H, int W, int Ci
     if (ref_ld > max_ld) max_ld = ref_ld;
     // the team kernels' 16-byte epilogue (and the cin1 kernel's): y / ref with ld % 4 == 0, aligned pointers
     const bool vec = y_ld % 4 == 0 && ref_ld % 4 == 0 && !misaligned;
-    if (use_mfma == 0) {   // VALU kernels: only the small-Cin first-layer kernel (conv_small.hip) provides statistics
+    if (use_mfma == TEM_ARITH_VALU) {   // VALU kernels: only the small-Cin first-layer kernel (conv_small.hip) provides statistics
         if (vec && !ref_ld && ref_free_cin1_ok(Cout)) p.stat_blocks = tem_conv_fwd_cin1_stat_blocks(D, H, W, Cin, Cout, kd, kh, kw);
         return p;
     }
-    if (use_mfma < 1 || use_mfma > 7 || Cin % 16 || Cout % 32) return p;
+    if (!tem_arith_mfma_fwd(use_mfma) || Cin % 16 || Cout % 32) return p;
     // split-K launch of the z-reuse kernel: 32-bit offsets over x and its Cout-wide workspace
     const bool sk_ok = vec && (int64_t)H * W * 8 * 4 * (x_ld > Cout ? x_ld : Cout) < (1ll << 31);
-    if (use_mfma == 1) {   // exact fp32: only the z-reuse kernel (direct or split-K) writes statistics
+    if (use_mfma == TEM_ARITH_FP32) {   // exact fp32: only the z-reuse kernel (direct or split-K) writes statistics
         if (x_ld % 4 || misaligned) return p;   // -> the exact-fp32 patch kernel
-        const int64_t zrb = tem_conv_zr_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, 1, max_ld);
+        const int64_t zrb = tem_conv_zr_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld);
         if (zrb >= 0) {
             if (vec) p = FwdPlan{3, ref_ld ? 0 : zrb};
-        } else if (tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, 1) && sk_ok) {
-            const int64_t skb = tem_conv_zr_splitk_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, 1);
+        } else if (tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma) && sk_ok) {
+            const int64_t skb = tem_conv_zr_splitk_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma);
             p = FwdPlan{4, skb > 0 ? skb : 0};
         }
         return p;
@@ -615,7 +614,9 @@ extern "C" int64_t tem_conv3d_wgrad_ws(int N, int D, int H, int W, int Cin, int 
     int ntaps = kd * kh * kw;
     WgradGenericPlan p = wgrad_generic_plan(NV, Cin, Cout, ntaps);
     int64_t bytes = tem_align_up(p.db_floats, 64) * 4;
-    if (use_mfma == 2 || use_mfma == 5 || use_mfma == 7 || use_mfma == 8) {
+    // an MFMA mode asked about channel counts its launch refuses: the plans below divide by Cin / 32 -- answer for the VALU path
+    if (Cin % 32 || Cout % 32) use_mfma = TEM_ARITH_VALU;
+    if (tem_arith_split_wgrad(use_mfma)) {
         bytes += tem_conv_wgrad_bf16x3_ws(N, D, H, W, Cin, Cout, kd, kh, kw);
     } else if (use_mfma) {
         int64_t b = tem_conv_wgrad_mfma_ws(N, D, H, W, Cin, Cout, kd, kh, kw);
@@ -659,7 +660,7 @@ static int conv3d_wgrad_impl(const TemConvCall& c, const float* x, int64_t x_ld,
     const int stx = c.stx, sty = c.sty;
     TEM_REQUIRE(stx >= 0 && stx <= 2 && sty >= 0 && sty <= 2 && (stx == 0 || sty == 0 || stx == sty),
                 "tem_conv3d_wgrad: unsupported storage types (x %d, g %d)", stx, sty);
-    TEM_REQUIRE(!(stx || sty) || !(use_mfma == 1 || use_mfma == 3 || use_mfma == 4 || use_mfma == 6),
+    TEM_REQUIRE(!(stx || sty) || tem_arith(use_mfma).wgrad != TEM_WG_FP32,
                 "tem_conv3d_wgrad: the exact-fp32 MFMA kernels take fp32 tensors only");
     if (ws_bytes < tem_conv3d_wgrad_ws(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)) {
         tem_set_error("tem_conv3d_wgrad: workspace too small");
@@ -672,13 +673,13 @@ static int conv3d_wgrad_impl(const TemConvCall& c, const float* x, int64_t x_ld,
     float* dbpart = (float*)ws;
     float* rest = dbpart + tem_align_up(p.db_floats, 64);
     TEM_REQUIRE(!gcoef || !use_mfma, "tem_conv3d_wgrad_gnorm: use_mfma must be 0");
-    TEM_REQUIRE(!c.x_cs || use_mfma == 5 || use_mfma == 7, "tem_conv3d_wgrad_ex: a chunk stride needs use_mfma 5 / 7");
-    if (use_mfma == 2 || use_mfma == 5 || use_mfma == 7 || use_mfma == 8) {
-        // 5: single fp16 product in the z-sliding kernel (autocast-equivalent); the other shapes keep bf16x3
-        // 8: fp16 2x1 (tem_conv3d_wgrad_gscaled; z-sliding kernel only)
+    TEM_REQUIRE(!c.x_cs || tem_arith_one_term(use_mfma), "tem_conv3d_wgrad_ex: a chunk stride needs use_mfma 5 / 7");
+    if (tem_arith_split_wgrad(use_mfma)) {
+        // F16 / BF16: single product in the z-sliding kernel (autocast-equivalent); the other shapes keep bf16x3
+        // F16X2: fp16 2x1 (tem_conv3d_wgrad_gscaled; z-sliding kernel only)
         int rc = tem_conv_wgrad_bf16x3(c, x, x_ld, scale, shift, g, g_ld, dw, db, rest,
                                        ws_bytes - (int64_t)((char*)rest - (char*)ws), N, D, H, W, Cin, Cout, kd, kh, kw,
-                                       sd_layout, use_mfma == 5 ? 1 : (use_mfma == 7 ? 2 : (use_mfma == 8 ? 3 : 0)), w_sd, gamma,
+                                       sd_layout, tem_arith(use_mfma).wgrad, w_sd, gamma,
                                        beta, norm_sums, s);
         if (rc != TEM_OK) return rc;
         TEM_CHECK_LAUNCH("tem_conv3d_wgrad(bf16x3)");
@@ -690,7 +691,7 @@ static int conv3d_wgrad_impl(const TemConvCall& c, const float* x, int64_t x_ld,
         // merge delivers the norm sums as in the split modes (round 6: the merge does not care which arithmetic filled the slabs)
         int rc = tem_conv_wgrad_bf16x3(c, x, x_ld, scale, shift, g, g_ld, dw, db, rest,
                                        ws_bytes - (int64_t)((char*)rest - (char*)ws), N, D, H, W, Cin, Cout, kd, kh, kw,
-                                       sd_layout, 4, w_sd, gamma, beta, norm_sums, s);
+                                       sd_layout, TEM_WG_FP32, w_sd, gamma, beta, norm_sums, s);
         if (rc != TEM_OK) return rc;
         TEM_CHECK_LAUNCH("tem_conv3d_wgrad(fp32, z-sliding)");
         return TEM_OK;
@@ -783,15 +784,15 @@ extern "C" int tem_conv1x1_out_bwd_st(const void* x, int64_t x_ld, const void* g
 
 extern "C" int tem_conv3d_wgrad_gmax_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                                         int use_mfma) {
-    return (use_mfma & 0xff) == 2 && tem_conv_wgrad_gmax_ok(N, D, H, W, Cin, Cout, kd, kh, kw);
+    return (use_mfma & 0xff) == TEM_ARITH_BF16X3 && tem_conv_wgrad_gmax_ok(N, D, H, W, Cin, Cout, kd, kh, kw);
 }
 
 // tem_conv3d_wgrad_sums_ok for a decoded call
 static int wgrad_sums_ok(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
-    if (use_mfma == 1)   // exact fp32: the layers k_conv_wgrad_tr<4> takes (option fp32_zr: the data gradient that consumes the sums)
+    if (use_mfma == TEM_ARITH_FP32)   // exact fp32: the layers k_conv_wgrad_tr<TEM_WG_FP32> takes (option fp32_zr: the data gradient that consumes the sums)
         return tem_option(TEM_OPT_FP32_ZR) && !c.stx && !c.sty && tem_conv_wgrad_tr_fp32_ok(N, D, H, W, Cin, Cout, kd, kh, kw) &&
                tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, c.x_cs);
-    if (use_mfma != 2 && use_mfma != 5 && use_mfma != 7 && use_mfma != 8) return 0;
+    if (!tem_arith_split_wgrad(use_mfma)) return 0;
     return tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, c.x_cs);
 }
 
@@ -799,7 +800,7 @@ static int wgrad_sums_ok(const TemConvCall& c, int N, int D, int H, int W, int C
 static int wgrad_gmax_check(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, const float* w, const float* db,
                             const float* norm_sums) {
     TEM_REQUIRE(c.g_amax_out, "tem_conv3d_wgrad_gmax: null g_amax");
-    TEM_REQUIRE(use_mfma == 2 && tem_conv_wgrad_gmax_ok(N, D, H, W, Cin, Cout, kd, kh, kw),
+    TEM_REQUIRE(use_mfma == TEM_ARITH_BF16X3 && tem_conv_wgrad_gmax_ok(N, D, H, W, Cin, Cout, kd, kh, kw),
                 "tem_conv3d_wgrad_gmax: tem_conv3d_wgrad_gmax_ok() == 0 for this layer");
     TEM_REQUIRE(!norm_sums || (w && db && wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)),
                 "tem_conv3d_wgrad_gmax: norm_sums needs weights, a bias gradient and tem_conv3d_wgrad_sums_ok() != 0");
@@ -809,7 +810,7 @@ static int wgrad_gscaled_check(const TemConvCall& c, int N, int D, int H, int W,
     TEM_REQUIRE(c.g_amax_in, "tem_conv3d_wgrad_gscaled: null g_amax");
     TEM_REQUIRE(tem_conv_wgrad_gscaled_ok(N, D, H, W, Cin, Cout, kd, kh, kw),
                 "tem_conv3d_wgrad_gscaled: tem_conv3d_wgrad_gscaled_ok() == 0 for this layer");
-    TEM_REQUIRE(!norm_sums || (w && db && wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, 8)),
+    TEM_REQUIRE(!norm_sums || (w && db && wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, TEM_ARITH_F16X2)),
                 "tem_conv3d_wgrad_gscaled: norm_sums needs weights, a bias gradient and tem_conv3d_wgrad_sums_ok() != 0");
     return TEM_OK;
 }
@@ -882,7 +883,7 @@ extern "C" int tem_conv3d_wgrad_gscaled(const float* x, int64_t x_ld, const floa
     TemConvCall c;
     c.g_amax_in = g_amax;
     TEM_TRY(wgrad_gscaled_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, w, db, norm_sums));
-    return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, 8, 1,
+    return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, TEM_ARITH_F16X2, 1,
                              norm_sums ? w : nullptr, gamma, beta, norm_sums, nullptr, 0, nullptr, stream);
 }
 
@@ -891,7 +892,7 @@ extern "C" int tem_conv3d_wgrad_gscaled(const float* x, int64_t x_ld, const floa
 static int fwd_gscaled_check(const TemConvCall& c, const float* x, int64_t x_ld, const float* w_packed, const float* y, int64_t y_ld,
                              const float* ref, int64_t ref_ld, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
     TEM_REQUIRE(c.in_amax, "tem_conv3d_fwd_gscaled: null in_amax");
-    TEM_REQUIRE(fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, 4, x_ld, y_ld, ref ? ref_ld : 0,
+    TEM_REQUIRE(fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, TEM_ARITH_F16X3, x_ld, y_ld, ref ? ref_ld : 0,
                          fwd_misaligned(x, nullptr, nullptr, w_packed, nullptr, y, ref)).family == 3,
                 "tem_conv3d_fwd_gscaled: only launches that tem_conv3d_fwd_kernel_ld() reports as 3 (z-reuse kernel) take a "
                 "device-side prescale");
@@ -915,7 +916,7 @@ extern "C" int tem_conv3d_fwd_gscaled(const float* x, int64_t x_ld, const float*
     c.in_amax = in_amax;
     TEM_TRY(fwd_gscaled_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw));
     return conv3d_fwd_impl(c, x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout,
-                           kd, kh, kw, TEM_ACT_NONE, 4, nullptr, stream);
+                           kd, kh, kw, TEM_ACT_NONE, TEM_ARITH_F16X3, nullptr, stream);
 }
 
 // Data gradient that lands behind a ReLU + norm: y = ref > 0 ? a*(conv) - m1 - (ref - mean)*m2r : 0 with coef[N][Cout][4] =
@@ -958,7 +959,7 @@ extern "C" int tem_conv3d_fwd_ex(const float* x, int64_t x_ld, const float* scal
     TemConvCall c = conv_call(use_mfma);
     TEM_REQUIRE(!stat_part || (!in_amax && !ref_coef && !bp), "tem_conv3d_fwd_ex: stat_part excludes in_amax / ref_coef / by-products");
     TEM_REQUIRE(!(in_amax && ref_coef), "tem_conv3d_fwd_ex: in_amax and ref_coef exclude each other");
-    TEM_REQUIRE(x_cs >= 0 && y_cs >= 0 && (!(x_cs || y_cs) || (!in_amax && !ref_coef && (use_mfma == 5 || use_mfma == 7))),
+    TEM_REQUIRE(x_cs >= 0 && y_cs >= 0 && (!(x_cs || y_cs) || (!in_amax && !ref_coef && tem_arith_one_term(use_mfma))),
                 "tem_conv3d_fwd_ex: chunk strides go with the one-term modes on 16-bit tensors (use_mfma 5 / 7), no in_amax / ref_coef");
     TEM_REQUIRE(!bp || (!bp->coef && (!bp->sums_part || (bp->sums_x && bp->sums_mean && bp->sums_rstd && bp->sums_G > 0 && bp->sums_nblk > 0))),
                 "tem_conv3d_fwd_ex: bad by-product request (TEM_BP_NORM_COEF belongs to tem_conv3d_wgrad_ex; TEM_BP_NORM_SUMS needs "
@@ -968,7 +969,7 @@ extern "C" int tem_conv3d_fwd_ex(const float* x, int64_t x_ld, const float* scal
     c.bp = bp;
     if (bp) bp->delivered = 0;
     if (in_amax) {
-        TEM_REQUIRE(!scale && !shift && !bias && act == TEM_ACT_NONE && use_mfma == 4,
+        TEM_REQUIRE(!scale && !shift && !bias && act == TEM_ACT_NONE && use_mfma == TEM_ARITH_F16X3,
                     "tem_conv3d_fwd_ex: in_amax (the fp16 two-term data gradient) takes use_mfma 4 and no scale / shift / bias / act");
         c.stx = c.sty = TEM_ST_F32;   // as tem_conv3d_fwd_gscaled: an fp32-tensor mode
         c.in_amax = in_amax;
@@ -992,7 +993,7 @@ extern "C" int tem_conv3d_wgrad_ex(const float* x, int64_t x_ld, const float* sc
                                    int64_t x_cs, TemByproducts* bp, tem_stream_t stream) {
     TemConvCall c = conv_call(use_mfma);
     TEM_REQUIRE(!(g_amax_in && g_amax_out), "tem_conv3d_wgrad_ex: g_amax_in and g_amax_out exclude each other");
-    TEM_REQUIRE(x_cs >= 0 && (!x_cs || (!g_amax_in && !g_amax_out && (use_mfma == 5 || use_mfma == 7))),
+    TEM_REQUIRE(x_cs >= 0 && (!x_cs || (!g_amax_in && !g_amax_out && tem_arith_one_term(use_mfma))),
                 "tem_conv3d_wgrad_ex: a chunk stride goes with the one-term modes on 16-bit tensors (use_mfma 5 / 7)");
     TEM_REQUIRE(!bp || (!bp->out_amax && !bp->sums_part && (!bp->coef || (norm_sums && bp->coef_mean && bp->coef_rstd && bp->coef_G > 0))),
                 "tem_conv3d_wgrad_ex: bad by-product request (only TEM_BP_NORM_COEF, which needs norm_sums, coef_mean, coef_rstd, coef_G)");
@@ -1000,7 +1001,7 @@ extern "C" int tem_conv3d_wgrad_ex(const float* x, int64_t x_ld, const float* sc
     c.bp = bp;
     if (bp) bp->delivered = 0;
     if (g_amax_in) {
-        TEM_REQUIRE(use_mfma == 8, "tem_conv3d_wgrad_ex: g_amax_in (the fp16 2x1 arithmetic) takes use_mfma 8");
+        TEM_REQUIRE(use_mfma == TEM_ARITH_F16X2, "tem_conv3d_wgrad_ex: g_amax_in (the fp16 2x1 arithmetic) takes use_mfma 8");
         c.stx = c.sty = TEM_ST_F32;   // as tem_conv3d_wgrad_gscaled: an fp32-tensor mode
         c.g_amax_in = g_amax_in;
         TEM_TRY(wgrad_gscaled_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, w, db, norm_sums));
@@ -1020,7 +1021,7 @@ extern "C" int tem_conv3d_wgrad_ex(const float* x, int64_t x_ld, const float* sc
 extern "C" int tem_conv3d_wgrad_gnorm_ok(int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
     use_mfma &= 0xff;
     const int cq = Cout / 4, key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
-    return use_mfma == 0 && Cin >= 1 && Cin <= 4 && Cout % 4 == 0 && cq <= 16 && (cq & (cq - 1)) == 0 && (key == 7 || key == 3);
+    return use_mfma == TEM_ARITH_VALU && Cin >= 1 && Cin <= 4 && Cout % 4 == 0 && cq <= 16 && (cq & (cq - 1)) == 0 && (key == 7 || key == 3);
 }
 
 static int wgrad_gnorm_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
@@ -1028,8 +1029,8 @@ static int wgrad_gnorm_impl(const TemConvCall& c, const float* x, int64_t x_ld, 
                             int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int sd_layout,
                             tem_stream_t stream) {
     TEM_REQUIRE(y && gcoef && y_ld >= Cout, "tem_conv3d_wgrad_gnorm: null pointer");
-    TEM_REQUIRE(tem_conv3d_wgrad_gnorm_ok(Cin, Cout, kd, kh, kw, 0), "tem_conv3d_wgrad_gnorm: tem_conv3d_wgrad_gnorm_ok() == 0");
-    return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, 0,
+    TEM_REQUIRE(tem_conv3d_wgrad_gnorm_ok(Cin, Cout, kd, kh, kw, TEM_ARITH_VALU), "tem_conv3d_wgrad_gnorm: tem_conv3d_wgrad_gnorm_ok() == 0");
+    return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, TEM_ARITH_VALU,
                              sd_layout, nullptr, nullptr, nullptr, nullptr, y, y_ld, gcoef, stream);
 }
 extern "C" int tem_conv3d_wgrad_gnorm(const float* x, int64_t x_ld, const float* scale, const float* shift,

@@ -10,6 +10,7 @@
 #include "tem_act.h"
 #include "conv_split.h"
 #include "conv_internal.h"
+#include "conv_arith.h"
 
 // T: element type of x, y and ref.  A 16-bit T is also the operand type of the one-term modes (fp16 storage <-> fp16 operands,
 // bf16 <-> bf16; the launcher checks): a lane's 8 channels of a k-step are ONE 16-byte load and go to the MFMA as loaded.
@@ -137,15 +138,14 @@ static void stream_launch(const TemConvCall& c, const T* x, int64_t x_ld, const 
                            ref, ref_ld, NV, Cin, Cout, act, nmt, amax);
 }
 
-// nsplit as in tem_conv_fwd_bf16x3: 2 = bf16x3, 3 = bf16x6, 5 = one fp16 term, 7 = one bf16 term.  false: not taken (pre-norm, statistics, the
-// scaled fp16x3 layouts, sigmoid -- the patch kernel handles those).  Storage types (c.stx / c.sty): fp32, or the 16-bit type
-// that IS the operand type of the mode (fp16 with nsplit 5, bf16 with nsplit 7).
+// false: not taken (a mode without an instantiation here: tem_stream1x1_takes; pre-norm, statistics, sigmoid -- the patch kernel
+// handles those).  Storage types (c.stx / c.sty): fp32, or the 16-bit type that IS the operand type of the mode (tem_storage_ok).
 bool tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* wp, const float* bias, float* y,
-                        int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act, int nsplit,
+                        int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act, int mode,
                         const float* stat, hipStream_t s) {
     const int st = c.stx;
     if (c.sty != st) return false;
-    if (st && !((st == 1 && nsplit == 5) || (st == 2 && nsplit == 7))) return false;
+    if (!tem_stream1x1_takes(mode) || !tem_storage_ok(mode, st)) return false;
     const uintptr_t a8 = st ? 15 : 15, a4 = tem_st_align4(st) - 1;   // x: 16-byte loads either way; y / ref: vectors of 4 elements
     if (scale || stat || act == TEM_ACT_SIGMOID) return false;
     if (NV < 16384) return false;   // too few 32-voxel tiles to hide the k-loop's load latency: the split-K patch kernel wins
@@ -153,19 +153,15 @@ bool tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, cons
     if ((y_ld & 3) || (reinterpret_cast<uintptr_t>(y) & a4) || (bias && (reinterpret_cast<uintptr_t>(bias) & 15)) ||
         (ref && ((ref_ld & 3) || (reinterpret_cast<uintptr_t>(ref) & a4))))
         return false;
-    if (st == 1)
-        stream_launch<1, true, tem_f16>(c, (const tem_f16*)x, x_ld, wp, bias, (tem_f16*)y, y_ld, (const tem_f16*)ref, ref_ld, NV, Cin, Cout, act, s);
-    else if (st == 2)
-        stream_launch<1, false, tem_bf16>(c, (const tem_bf16*)x, x_ld, wp, bias, (tem_bf16*)y, y_ld, (const tem_bf16*)ref, ref_ld, NV, Cin, Cout, act, s);
-    else if (nsplit == 2)
-        stream_launch<2, false, float>(c, x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
-    else if (nsplit == 3)
-        stream_launch<3, false, float>(c, x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
-    else if (nsplit == 5)
-        stream_launch<1, true, float>(c, x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
-    else if (nsplit == 7)
-        stream_launch<1, false, float>(c, x, x_ld, wp, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
-    else
-        return false;
+    auto go = [&](auto ns, auto f16, auto t) {
+        using T = decltype(t);
+        stream_launch<ns(), f16(), T>(c, (const T*)x, x_ld, wp, bias, (T*)y, y_ld, (const T*)ref, ref_ld, NV, Cin, Cout, act, s);
+    };
+    const TemArith& a = tem_arith(mode);
+    if (st == TEM_ST_F16) go(TemInt<1>{}, TemBool<true>{}, tem_f16{});
+    else if (st == TEM_ST_BF16) go(TemInt<1>{}, TemBool<false>{}, tem_bf16{});
+    else if (a.planes == 3) go(TemInt<3>{}, TemBool<false>{}, float{});
+    else if (a.planes == 2) go(TemInt<2>{}, TemBool<false>{}, float{});
+    else tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) { go(TemInt<1>{}, f16, float{}); });
     return true;
 }

@@ -57,6 +57,7 @@ __device__ __forceinline__ float4 ld4_nt(const float* p) {
 
 #include "conv_split.h"
 #include "tem_act.h"
+#include "conv_arith.h"
 
 // ---------------------------------------------------------------------------
 // weight packing: [Cout][Cin][kd][kh][kw] fp32 -> [co/32][tap][ci/16][NS planes][64 lanes][8 bf16]
@@ -69,7 +70,7 @@ __device__ __forceinline__ unsigned short bf16_bits(float v) {
 
 __global__ __launch_bounds__(256) void k_pack_weights_bfsplit(const float* __restrict__ w, unsigned short* __restrict__ dst,
                                                               int Cout, int Cin, int KD, int KH, int KW, int transpose,
-                                                              int NS, int fp16) {
+                                                              int NS, int kind) {
     const int ntaps = KD * KH * KW;
     const int64_t total = (int64_t)Cout * Cin * ntaps;
     const int CoutL = transpose ? Cin : Cout, CinL = transpose ? Cout : Cin;
@@ -87,13 +88,13 @@ __global__ __launch_bounds__(256) void k_pack_weights_bfsplit(const float* __res
         const int nt = co >> 5, col = co & 31, c16 = ci >> 4, kh = (ci >> 3) & 1, j = ci & 7;
         const int64_t base = ((((int64_t)nt * ntaps + tap) * (CinL >> 4) + c16) * NS) * 512;  // 512 bf16 per plane
         float rem = val;
-        if (fp16 == 3) rem = __builtin_amdgcn_fmed3f(val * F16_W_PRESCALE, -64000.f, 64000.f);
+        if (kind == TEM_PK_F16_PRE) rem = __builtin_amdgcn_fmed3f(val * F16_W_PRESCALE, -64000.f, 64000.f);
         for (int p = 0; p < NS; ++p) {
-            if (fp16) {
+            if (kind != TEM_PK_BF16) {
                 const _Float16 hv = (_Float16)rem;
                 dst[base + p * 512 + (kh * 32 + col) * 8 + j] = __builtin_bit_cast(unsigned short, hv);
                 rem -= (float)hv;
-                if (fp16 == 2) rem *= F16_LO_SCALE;
+                if (kind == TEM_PK_F16_LO12) rem *= F16_LO_SCALE;
             } else {
                 const unsigned short hb = bf16_bits(rem);
                 dst[base + p * 512 + (kh * 32 + col) * 8 + j] = hb;
@@ -104,19 +105,44 @@ __global__ __launch_bounds__(256) void k_pack_weights_bfsplit(const float* __res
 }
 
 int tem_pack_weights_bf16x3(const float* w, float* dst, int Cout, int Cin, int kd, int kh, int kw, int transpose,
-                            int nsplit, hipStream_t s) {
-    // nsplit 4 = fp16x3: two fp16 planes, the lo plane scaled by 2^12 (fp16 = 2); 5 = fp16: one plane (fp16 = 1);
-    // 6 = fp16x3 with the whole weight prescaled by 2^7 (fp16 = 3, conv_split.h)
-    // 7 = one bf16 term (the counterpart of torch.autocast(bfloat16)): one plane, bf16 bits
-    const int fp16 = nsplit == 4 ? 2 : (nsplit == 5 ? 1 : (nsplit == 6 ? 3 : 0));
-    if (fp16) nsplit = nsplit == 5 ? 1 : 2;
-    if (nsplit == 7) nsplit = 1;
+                            int planes, int kind, hipStream_t s) {
     int CoutL = transpose ? Cin : Cout, CinL = transpose ? Cout : Cin;
     TEM_REQUIRE(CinL % 16 == 0 && CoutL % 32 == 0, "tem_conv_pack_weights: split-bf16 layout needs Cin%%16==0, Cout%%32==0");
     int64_t total = (int64_t)Cout * Cin * kd * kh * kw;
     hipLaunchKernelGGL(k_pack_weights_bfsplit, dim3(tem_grid_1d(total, 256)), dim3(256), 0, s, w, (unsigned short*)dst,
-                       Cout, Cin, kd, kh, kw, transpose, nsplit, fp16);
+                       Cout, Cin, kd, kh, kw, transpose, planes, kind);
     return TEM_OK;
+}
+
+// One MFMA lane slot of a packed weight: the 8 values of `rem` become NS planes of 8 packed 16-bit terms (one 16-byte vector per
+// plane, 64 vectors apart); every plane holds the rounded remainder of the planes before it.
+__device__ __forceinline__ void pack_lane_planes(float (&rem)[8], int NS, int kind, uint4* out) {
+    if (kind == TEM_PK_F16_PRE) {
+#pragma unroll
+        for (int j = 0; j < 8; ++j) rem[j] = __builtin_amdgcn_fmed3f(rem[j] * F16_W_PRESCALE, -64000.f, 64000.f);
+    }
+    for (int p = 0; p < NS; ++p) {
+        unsigned pk[4];
+#pragma unroll
+        for (int q = 0; q < 4; ++q) {
+            if (kind != TEM_PK_BF16) {
+                const _Float16 a = (_Float16)rem[2 * q], b = (_Float16)rem[2 * q + 1];
+                pk[q] = (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
+                rem[2 * q] -= (float)a;
+                rem[2 * q + 1] -= (float)b;
+                if (kind == TEM_PK_F16_LO12) {
+                    rem[2 * q] *= F16_LO_SCALE;
+                    rem[2 * q + 1] *= F16_LO_SCALE;
+                }
+            } else {
+                const unsigned short a = bf16_bits(rem[2 * q]), b = bf16_bits(rem[2 * q + 1]);
+                pk[q] = (unsigned)a | ((unsigned)b << 16);
+                rem[2 * q] -= __builtin_bit_cast(float, (unsigned)a << 16);
+                rem[2 * q + 1] -= __builtin_bit_cast(float, (unsigned)b << 16);
+            }
+        }
+        out[(long long)p * 64] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
+    }
 }
 
 // One launch for every split-layout weight tensor of a model (after an optimizer step all of them are stale:
@@ -124,7 +150,7 @@ int tem_pack_weights_bf16x3(const float* w, float* dst, int Cout, int Cin, int k
 struct PackDesc {
     const float* w;
     unsigned short* dst;
-    int Cout, Cin, KD, KH, KW, transpose, NS, fp16;
+    int Cout, Cin, KD, KH, KW, transpose, NS, kind;   // NS planes of TemPackKind `kind` (NS 0: the generic fp32 layout)
     long long begin;  // first global work item (8-channel lane slot) of this tensor: running sum of Cout*Cin*taps/8
 };
 __global__ __launch_bounds__(256) void k_pack_weights_batch(const PackDesc* __restrict__ descs, int n, long long total) {
@@ -172,31 +198,9 @@ __global__ __launch_bounds__(256) void k_pack_weights_batch(const PackDesc* __re
         for (int j = 0; j < 8; ++j) {
             const int ci = ci0 + j;
             rem[j] = d.transpose ? d.w[((long long)ci * d.Cin + co) * ntaps + ftap] : d.w[((long long)co * d.Cin + ci) * ntaps + tap];
-            if (d.fp16 == 3) rem[j] = __builtin_amdgcn_fmed3f(rem[j] * F16_W_PRESCALE, -64000.f, 64000.f);
         }
         uint4* out = reinterpret_cast<uint4*>(d.dst) + ((((long long)nt * ntaps + tap) * c16n + c16) * d.NS) * 64 + lane;
-        for (int p = 0; p < d.NS; ++p) {
-            unsigned pk[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (d.fp16) {
-                    const _Float16 a = (_Float16)rem[2 * q], b = (_Float16)rem[2 * q + 1];
-                    pk[q] = (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-                    rem[2 * q] -= (float)a;
-                    rem[2 * q + 1] -= (float)b;
-                    if (d.fp16 == 2) {
-                        rem[2 * q] *= F16_LO_SCALE;
-                        rem[2 * q + 1] *= F16_LO_SCALE;
-                    }
-                } else {
-                    const unsigned short a = bf16_bits(rem[2 * q]), b = bf16_bits(rem[2 * q + 1]);
-                    pk[q] = (unsigned)a | ((unsigned)b << 16);
-                    rem[2 * q] -= __builtin_bit_cast(float, (unsigned)a << 16);
-                    rem[2 * q + 1] -= __builtin_bit_cast(float, (unsigned)b << 16);
-                }
-            }
-            out[(long long)p * 64] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-        }
+        pack_lane_planes(rem, d.NS, d.kind, out);
     }
 }
 // The same re-pack with COALESCED reads: a workgroup stages one [32 out][32 in][taps] tile of a weight tensor (rows of
@@ -206,7 +210,7 @@ __global__ __launch_bounds__(256) void k_pack_weights_batch(const PackDesc* __re
 struct PackTileDesc {
     const float* w;
     unsigned short* dst;
-    int Cout, Cin, KD, KH, KW, transpose, NS, fp16;
+    int Cout, Cin, KD, KH, KW, transpose, NS, kind;
     long long tbegin;
 };
 #define PT_MAXF 28672   // LDS floats of a tile: 32 rows x (32 x 27 + 4) = 27776
@@ -252,11 +256,10 @@ __global__ __launch_bounds__(1024) void k_pack_weights_tiles(const PackTileDesc*
         for (int j = 0; j < 8; ++j) {
             const int k = fr * 16 + kh * 8 + j;   // in-channel of the executed conv inside the tile
             rem[j] = d.transpose ? tile[k * pitch + col * ntaps + ftap] : tile[col * pitch + k * ntaps + tap];
-            if (d.fp16 == 3) rem[j] = __builtin_amdgcn_fmed3f(rem[j] * F16_W_PRESCALE, -64000.f, 64000.f);
         }
         const int c16 = (d.transpose ? cob * 2 : cib * 2) + fr;
         uint4* out = reinterpret_cast<uint4*>(d.dst) + ((((long long)ntL * ntaps + tap) * c16n + c16) * d.NS) * 64 + lane;
-        if (d.fp16 == 4) {
+        if (d.kind == TEM_PK_FP32) {
             // exact fp32 (TEM_WL_MFMA, round 6: the exact mode re-packed 43 tensors with one launch each): the two 64-lane groups
             // of a 16-channel chunk hold channels 8 p + 4 kh + (0..3) as they are -- rem[] has 8 kh + j: gather the other four
 #pragma unroll
@@ -272,28 +275,7 @@ __global__ __launch_bounds__(1024) void k_pack_weights_tiles(const PackTileDesc*
             }
             continue;
         }
-        for (int p = 0; p < d.NS; ++p) {
-            unsigned pk[4];
-#pragma unroll
-            for (int q = 0; q < 4; ++q) {
-                if (d.fp16) {
-                    const _Float16 a = (_Float16)rem[2 * q], b = (_Float16)rem[2 * q + 1];
-                    pk[q] = (unsigned)__builtin_bit_cast(unsigned short, a) | ((unsigned)__builtin_bit_cast(unsigned short, b) << 16);
-                    rem[2 * q] -= (float)a;
-                    rem[2 * q + 1] -= (float)b;
-                    if (d.fp16 == 2) {
-                        rem[2 * q] *= F16_LO_SCALE;
-                        rem[2 * q + 1] *= F16_LO_SCALE;
-                    }
-                } else {
-                    const unsigned short a = bf16_bits(rem[2 * q]), b = bf16_bits(rem[2 * q + 1]);
-                    pk[q] = (unsigned)a | ((unsigned)b << 16);
-                    rem[2 * q] -= __builtin_bit_cast(float, (unsigned)a << 16);
-                    rem[2 * q + 1] -= __builtin_bit_cast(float, (unsigned)b << 16);
-                }
-            }
-            out[(long long)p * 64] = make_uint4(pk[0], pk[1], pk[2], pk[3]);
-        }
+        pack_lane_planes(rem, d.NS, d.kind, out);
     }
 }
 extern "C" int tem_conv_pack_weights_tiles(const void* descs_dev, int n, int64_t total_tiles, tem_stream_t stream) {
@@ -642,37 +624,57 @@ static void launch_b(const float* x_, int64_t x_ld, const float* scale, const fl
     }
 }
 
+// The instantiation of the patch kernel a mode runs on: weight planes, fp16 or bf16 operands, prescaled operands, element type of
+// the tensors (a 16-bit storage type goes with the one-term mode of that type: tem_storage_ok).
+template <int NS_, bool F16_, bool PS_ = false, typename T_ = float>
+struct FwdVariant {
+    static constexpr int NS = NS_;
+    static constexpr bool F16 = F16_, PS = PS_;
+    using T = T_;
+};
+template <typename F>
+static void fwd_variant(int mode, int st, F&& f) {
+    const TemArith& a = tem_arith(mode);
+    if (a.planes == 3) f(FwdVariant<3, false>{});
+    else if (a.pack == TEM_PK_F16_LO12) f(FwdVariant<2, true>{});
+    else if (a.pack == TEM_PK_F16_PRE) f(FwdVariant<2, true, true>{});
+    else if (a.planes == 1 && st == TEM_ST_F16) f(FwdVariant<1, true, false, tem_f16>{});
+    else if (a.planes == 1 && st == TEM_ST_BF16) f(FwdVariant<1, false, false, tem_bf16>{});
+    else if (a.planes == 1) tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) { f(FwdVariant<1, f16()>{}); });
+    else f(FwdVariant<2, false>{});
+}
+
 int tem_conv_fwd_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                         const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
                         int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
-                        int nsplit, float* stat, hipStream_t s) {
+                        int mode, float* stat, hipStream_t s) {
     TEM_REQUIRE(Cin % 16 == 0 && Cout % 32 == 0, "tem_conv3d_fwd(split-bf16): needs Cin%%16==0 and Cout%%32==0 (got %d,%d)",
                 Cin, Cout);
     const int st = c.stx;
     TEM_REQUIRE(st == c.sty, "tem_conv3d_fwd(split-bf16): x and y must have the same storage type");
-    TEM_REQUIRE(st == 0 || (st == 1 && nsplit == 5) || (st == 2 && nsplit == 7),
+    TEM_REQUIRE(tem_storage_ok(mode, st),
                 "tem_conv3d_fwd(split-bf16): 16-bit storage goes with the one-term mode of the same type (fp16: use_mfma 5, "
-                "bf16: use_mfma 7), got storage %d with use_mfma %d", st, nsplit);
+                "bf16: use_mfma 7), got storage %d with use_mfma %d", st, mode);
     TEM_REQUIRE(x_ld % (st ? 8 : 4) == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)wp % 16 == 0),
                 "tem_conv3d_fwd(split-bf16): x / packed weights must be 16-byte aligned with ld%%4==0 (16-bit storage: ld%%8==0)");
     TEM_REQUIRE(!scale || (((uintptr_t)scale % 16 == 0) && ((uintptr_t)shift % 16 == 0)),
                 "tem_conv3d_fwd(split-bf16): scale/shift must be 16-byte aligned");
     const int zr = tem_conv_fwd_zr(c, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, act,
-                                   nsplit, stat, s);
+                                   mode, stat, s);
     if (zr < 0) return TEM_EINVAL;
     if (zr) return TEM_OK;
     const int pp = tem_conv_fwd_pp(c, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, act,
-                                   nsplit, stat, s);
+                                   mode, stat, s);
     if (pp < 0) return TEM_EINVAL;
     if (pp) return TEM_OK;
     if (tem_conv_fwd_zr_splitk(c, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
-                               kw, act, nsplit, stat, s))
+                               kw, act, mode, stat, s))
         return TEM_OK;
-    TEM_REQUIRE(!stat || tem_conv_zr_splitk_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit) < 0,
+    TEM_REQUIRE(!stat || tem_conv_zr_splitk_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode) < 0,
                 "tem_conv3d_fwd_stats: the split-K launch that writes the statistics needs its workspace "
                 "(tem_conv3d_fwd_ws) and 16-byte aligned y / ref / bias");
     if (kd == 1 && kh == 1 && kw == 1 && tem_option(TEM_OPT_CONV1X1_STREAM) &&
-        tem_conv1x1_stream(c, x, x_ld, scale, wp, bias, y, y_ld, ref, ref_ld, (int64_t)N * D * H * W, Cin, Cout, act, nsplit, stat, s))
+        tem_conv1x1_stream(c, x, x_ld, scale, wp, bias, y, y_ld, ref, ref_ld, (int64_t)N * D * H * W, Cin, Cout, act, mode, stat, s))
         return TEM_OK;
     const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
     const bool flat = (D == 1 && kd == 1);
@@ -685,82 +687,33 @@ int tem_conv_fwd_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, cons
     if (ks > 1 && (!ws || !vec_ok || ws_bytes < (int64_t)ks * N * D * H * W * Cout * 4)) ks = 1;
     TEM_REQUIRE(!stat || ks == 1, "tem_conv3d_fwd_stats: this shape runs split-K (tem_conv3d_fwd_stat_blocks() == 0)");
     float* part = (float*)ws;
-#define GO2(KD, KH, KW, TZ, TY, TX, NS)                                                                             \
-    do {                                                                                                            \
-        if (nr2)                                                                                                    \
-            launch_b<KD, KH, KW, TZ, TY, TX, 2, NS>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, \
-                                                    Cin, Cout, act, ks, part, stat, s);                                   \
-        else                                                                                                        \
-            launch_b<KD, KH, KW, TZ, TY, TX, 1, NS>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, \
-                                                    Cin, Cout, act, ks, part, stat, s);                                   \
-    } while (0)
-#define GO(KD, KH, KW, TZ, TY, TX)                                                                                    \
-    do {                                                                                                              \
-        if (nsplit == 3)                                                                                              \
-            GO2(KD, KH, KW, TZ, TY, TX, 3);                                                                           \
-        else if (nsplit == 4) {                                                                                       \
-            if (nr2)                                                                                                  \
-                launch_b<KD, KH, KW, TZ, TY, TX, 2, 2, true>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, \
-                                                             W, Cin, Cout, act, ks, part, stat, s);                         \
-            else                                                                                                      \
-                launch_b<KD, KH, KW, TZ, TY, TX, 1, 2, true>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, \
-                                                             W, Cin, Cout, act, ks, part, stat, s);                         \
-        } else if (nsplit == 6) {                                                                                     \
-            if (nr2)                                                                                                  \
-                launch_b<KD, KH, KW, TZ, TY, TX, 2, 2, true, true>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, \
-                                                                   H, W, Cin, Cout, act, ks, part, stat, s);               \
-            else                                                                                                      \
-                launch_b<KD, KH, KW, TZ, TY, TX, 1, 2, true, true>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, \
-                                                                   H, W, Cin, Cout, act, ks, part, stat, s);               \
-        } else if (nsplit == 5 && st == 1) {                                                                          \
-            if (nr2)                                                                                                  \
-                launch_b<KD, KH, KW, TZ, TY, TX, 2, 1, true, false, tem_f16>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, \
-                                                             W, Cin, Cout, act, ks, part, stat, s);                         \
-            else                                                                                                      \
-                launch_b<KD, KH, KW, TZ, TY, TX, 1, 1, true, false, tem_f16>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, \
-                                                             W, Cin, Cout, act, ks, part, stat, s);                         \
-        } else if (nsplit == 7 && st == 2) {                                                                          \
-            if (nr2)                                                                                                  \
-                launch_b<KD, KH, KW, TZ, TY, TX, 2, 1, false, false, tem_bf16>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, \
-                                                              W, Cin, Cout, act, ks, part, stat, s);                        \
-            else                                                                                                      \
-                launch_b<KD, KH, KW, TZ, TY, TX, 1, 1, false, false, tem_bf16>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, \
-                                                              W, Cin, Cout, act, ks, part, stat, s);                        \
-        } else if (nsplit == 5) {                                                                                     \
-            if (nr2)                                                                                                  \
-                launch_b<KD, KH, KW, TZ, TY, TX, 2, 1, true>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, \
-                                                             W, Cin, Cout, act, ks, part, stat, s);                         \
-            else                                                                                                      \
-                launch_b<KD, KH, KW, TZ, TY, TX, 1, 1, true>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, \
-                                                             W, Cin, Cout, act, ks, part, stat, s);                         \
-        } else if (nsplit == 7) {                                                                                     \
-            if (nr2)                                                                                                  \
-                launch_b<KD, KH, KW, TZ, TY, TX, 2, 1, false>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, \
-                                                              W, Cin, Cout, act, ks, part, stat, s);                        \
-            else                                                                                                      \
-                launch_b<KD, KH, KW, TZ, TY, TX, 1, 1, false>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, \
-                                                              W, Cin, Cout, act, ks, part, stat, s);                        \
-        } else                                                                                                        \
-            GO2(KD, KH, KW, TZ, TY, TX, 2);                                                                           \
-    } while (0)
+    // one argument list for every instantiation: the mode's variant x column tiles per workgroup x (kernel, patch) shape
+    auto go = [&](auto KD, auto KH, auto KW, auto TZ, auto TY, auto TX) {
+        fwd_variant(mode, st, [&](auto v) {
+            using V = decltype(v);
+            tem_select_bool(nr2, [&](auto two) {
+                launch_b<KD(), KH(), KW(), TZ(), TY(), TX(), two() ? 2 : 1, V::NS, V::F16, V::PS, typename V::T>(
+                    x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, ks, part, stat, s);
+            });
+        });
+    };
+    using I1 = TemInt<1>; using I3 = TemInt<3>; using I4 = TemInt<4>; using I8 = TemInt<8>; using I16 = TemInt<16>;
     if (key == 7) {
-        GO(3, 3, 3, 4, 8, 8);
+        go(I3{}, I3{}, I3{}, I4{}, I8{}, I8{});
     } else if (key == 3) {
         if (flat)
-            GO(1, 3, 3, 1, 16, 16);
+            go(I1{}, I3{}, I3{}, I1{}, I16{}, I16{});
         else
-            GO(1, 3, 3, 4, 8, 8);
+            go(I1{}, I3{}, I3{}, I4{}, I8{}, I8{});
     } else if (key == 0) {
         if (flat)
-            GO(1, 1, 1, 1, 16, 16);
+            go(I1{}, I1{}, I1{}, I1{}, I16{}, I16{});
         else
-            GO(1, 1, 1, 4, 8, 8);
+            go(I1{}, I1{}, I1{}, I4{}, I8{}, I8{});
     } else {
         tem_set_error("tem_conv3d_fwd(split-bf16): kernel (%d,%d,%d) has no MFMA instantiation", kd, kh, kw);
         return TEM_EINVAL;
     }
-#undef GO
-#undef GO2
     return TEM_OK;
 }
 
@@ -1904,13 +1857,15 @@ static void launch_wb(const TemConvCall& c, const float* x, int64_t x_ld, const 
 }
 
 int tem_conv_wgrad_gscaled_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
+    if (Cin % 32 || Cout % 32) return 0;   // (before the plan: it divides by Cin / 32)
     const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
-    return Cin % 32 == 0 && Cout % 32 == 0 && z.use && (!z.teams || z.tr);
+    return z.use && (!z.teams || z.tr);
 }
 // exact-fp32 weight gradient on k_conv_wgrad_tr<4> (TEM_PRECISION=fp32): the layers the z-sliding plan takes, option wgrad_zs >= 3
 int tem_conv_wgrad_tr_fp32_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
+    if (Cin % 32 || Cout % 32) return 0;
     const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
-    return Cin % 32 == 0 && Cout % 32 == 0 && z.use && z.tr;
+    return z.use && z.tr;
 }
 // the chunk-stride conditions of the launch below (x_cs != 0), as a query
 int tem_conv_wgrad_cs_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int st, int64_t x_cs) {
@@ -1924,13 +1879,14 @@ int tem_conv_wgrad_gmax_ok(int N, int D, int H, int W, int Cin, int Cout, int kd
 
 int tem_conv_wgrad_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
                           int64_t g_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H, int W,
-                          int Cin, int Cout, int kd, int kh, int kw, int sd_layout, int h16, const float* w_sd,
+                          int Cin, int Cout, int kd, int kh, int kw, int sd_layout, int wg_kind, const float* w_sd,
                           const float* gamma, const float* beta, float* norm_sums, hipStream_t s) {
     TEM_REQUIRE(Cin % 32 == 0 && Cout % 32 == 0, "tem_conv3d_wgrad(bf16x3): needs Cin%%32==0 and Cout%%32==0 (got %d,%d)",
                 Cin, Cout);
     const int st = c.stx;
     TEM_REQUIRE(st == c.sty, "tem_conv3d_wgrad(split-bf16): x and g must have the same storage type");
-    TEM_REQUIRE(st == 0 || (st == 1 && h16 == 1) || (st == 2 && h16 == 2),
+    const TemWgradKind kind = (TemWgradKind)wg_kind;
+    TEM_REQUIRE(tem_wgrad_storage_ok(kind, st),
                 "tem_conv3d_wgrad(split-bf16): 16-bit storage goes with the one-term mode of the same type (fp16: use_mfma 5, "
                 "bf16: use_mfma 7), got storage %d", st);
     TEM_REQUIRE(x_ld % (st ? 8 : 4) == 0 && g_ld % (st ? 8 : 4) == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)g % 16 == 0),
@@ -1945,10 +1901,10 @@ int tem_conv_wgrad_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, co
     }
     const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
     unsigned* const gmax = c.g_amax_out;   // tem_conv3d_wgrad_gmax
-    TEM_REQUIRE(!gmax || (z.use && !h16), "tem_conv3d_wgrad_gmax: tem_conv3d_wgrad_gmax_ok() == 0 for this layer");
-    const unsigned* const g_amax = c.g_amax_in;   // tem_conv3d_wgrad_gscaled (h16 == 3 reads it)
-    TEM_REQUIRE(h16 != 4 || (z.use && z.tr), "tem_conv3d_wgrad(fp32 on k_conv_wgrad_tr): tem_conv_wgrad_tr_fp32_ok() == 0 for this layer");
-    TEM_REQUIRE(h16 != 3 || (g_amax && z.use && (!z.teams || z.tr)),
+    TEM_REQUIRE(!gmax || (z.use && kind == TEM_WG_BF16X3), "tem_conv3d_wgrad_gmax: tem_conv3d_wgrad_gmax_ok() == 0 for this layer");
+    const unsigned* const g_amax = c.g_amax_in;   // tem_conv3d_wgrad_gscaled (TEM_WG_F16X2 reads it)
+    TEM_REQUIRE(kind != TEM_WG_FP32 || (z.use && z.tr), "tem_conv3d_wgrad(fp32 on k_conv_wgrad_tr): tem_conv_wgrad_tr_fp32_ok() == 0 for this layer");
+    TEM_REQUIRE(kind != TEM_WG_F16X2 || (g_amax && z.use && (!z.teams || z.tr)),
                 "tem_conv3d_wgrad_gscaled: tem_conv3d_wgrad_gscaled_ok() == 0 for this layer (or no g_amax)");
     if (z.use) {
         TEM_REQUIRE((int64_t)H * W * (x_ld > g_ld ? x_ld : g_ld) * 4 < (1ll << 31),
@@ -1958,7 +1914,6 @@ int tem_conv_wgrad_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, co
         TEM_REQUIRE(!norm_sums || (db && w_sd && sd_layout && tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, c.x_cs)),
                     "tem_conv3d_wgrad_sums: this layer cannot deliver the norm sums (tem_conv3d_wgrad_sums_ok() == 0)");
         const unsigned nblk = (unsigned)((int64_t)z.T * z.S);
-        // h16: 0 bf16x3 (hi + lo planes, 3 MFMAs per product), 1 one fp16 term, 2 one bf16 term (the mixed-precision modes)
         auto launch = [&](auto kern, size_t lb) {
             static std::set<const void*> sized;   // kernels whose dynamic-LDS limit was raised already
             const void* key = reinterpret_cast<const void*>(kern);
@@ -1969,26 +1924,28 @@ int tem_conv_wgrad_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, co
             hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lb, s, x, x_ld, scale, shift, g, g_ld, zpart, zdb, N, D, H, W, Cin,
                                Cout, z.T, z.nY, z.nX, z.zsegs, z.Ss, z.ncz, gmax, g_amax);
         };
-        auto go = [&](auto k0, auto k1, auto k2, auto k3, size_t lb) {
-            if (h16 == 1) launch(k1, lb);
-            else if (h16 == 2) launch(k2, lb);
-            else if (h16 == 3) launch(k3, lb);
-            else launch(k0, lb);
+        // the kernel of this call's arithmetic out of a family's four (k_conv_wgrad_zt has no fp16 2x1 variant: the requirement above
+        // keeps that kind off it)
+        auto go = [&](auto bf16x3, auto f16, auto bf16, auto f16x2, size_t lb) {
+            if (kind == TEM_WG_F16) launch(f16, lb);
+            else if (kind == TEM_WG_BF16) launch(bf16, lb);
+            else if (kind == TEM_WG_F16X2) launch(f16x2, lb);
+            else launch(bf16x3, lb);
         };
         TEM_REQUIRE(!st || z.tr, "tem_conv3d_wgrad: 16-bit storage needs the transposing z-sliding kernel (option wgrad_zs = 3)");
         TEM_REQUIRE(!c.x_cs || (st && z.tr && c.x_cs % 8 == 0),
                     "tem_conv3d_wgrad_ex: a chunk stride (x_cs) needs 16-bit tensors on the transposing z-sliding kernel, x_cs %% 8 == 0");
         if (z.tr)
-            tem_conv_wgrad_tr_launch(c, h16, nblk, x, x_ld, scale, shift, g, g_ld, zpart, zdb, N, D, H, W, Cin, Cout, z.T, z.nY, z.nX,
+            tem_conv_wgrad_tr_launch(c, kind, nblk, x, x_ld, scale, shift, g, g_ld, zpart, zdb, N, D, H, W, Cin, Cout, z.T, z.nY, z.nX,
                                      z.zsegs, z.Ss, z.ncz, s);
         else if (z.teams)
-            go(&k_conv_wgrad_zt<0>, &k_conv_wgrad_zt<1>, &k_conv_wgrad_zt<2>, &k_conv_wgrad_zt<0>,
+            go(&k_conv_wgrad_zt<TEM_WG_BF16X3>, &k_conv_wgrad_zt<TEM_WG_F16>, &k_conv_wgrad_zt<TEM_WG_BF16>, &k_conv_wgrad_zt<TEM_WG_BF16X3>,
                2 * (size_t)32 * ZS_CIS + 4 * (size_t)32 * ZS_GS);
         else if (z.nco == 2)
-            go(&k_conv_wgrad_zs<2, 0>, &k_conv_wgrad_zs<2, 1>, &k_conv_wgrad_zs<2, 2>, &k_conv_wgrad_zs<2, 3>,
+            go(&k_conv_wgrad_zs<2, TEM_WG_BF16X3>, &k_conv_wgrad_zs<2, TEM_WG_F16>, &k_conv_wgrad_zs<2, TEM_WG_BF16>, &k_conv_wgrad_zs<2, TEM_WG_F16X2>,
                2 * (size_t)32 * ZS_CIS + 4 * (size_t)64 * ZS_GS);
         else
-            go(&k_conv_wgrad_zs<1, 0>, &k_conv_wgrad_zs<1, 1>, &k_conv_wgrad_zs<1, 2>, &k_conv_wgrad_zs<1, 3>,
+            go(&k_conv_wgrad_zs<1, TEM_WG_BF16X3>, &k_conv_wgrad_zs<1, TEM_WG_F16>, &k_conv_wgrad_zs<1, TEM_WG_BF16>, &k_conv_wgrad_zs<1, TEM_WG_F16X2>,
                2 * (size_t)32 * ZS_CIS + 4 * (size_t)32 * ZS_GS);
         if (norm_sums) {
             float* extra = zdb + tem_align_up((int64_t)z.S * Cout, 64);

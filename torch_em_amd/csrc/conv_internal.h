@@ -16,10 +16,10 @@ struct TemConvCall {
     // z-sliding weight gradient on 16-bit tensors take them; every other launch site refuses a call that carries one.
     int64_t x_cs = 0, y_cs = 0;
     TemByproducts* bp = nullptr;           // by-products the caller asks for (tem_hip.h); the launch site sets `delivered`
-    const unsigned* in_amax = nullptr;     // forward: device-side prescale of the input (use_mfma 4), z-reuse kernel only
+    const unsigned* in_amax = nullptr;     // forward: device-side prescale of the input (TEM_ARITH_F16X3), z-reuse kernel only
     const float* ref_coef = nullptr;       // forward: coef[N][Cout][4], norm backward in the epilogue, z-reuse kernel only
     unsigned* g_amax_out = nullptr;        // weight gradient: largest |g| as a by-product of the z-sliding kernels
-    const unsigned* g_amax_in = nullptr;   // weight gradient: prescale of g in the fp16 2x1 arithmetic (h16 == 3)
+    const unsigned* g_amax_in = nullptr;   // weight gradient: prescale of g in the fp16 2x1 arithmetic (TEM_WG_F16X2)
 
     bool wants(unsigned bit) const {       // the call asks for by-product `bit` and no launch has delivered it yet
         if (!bp || (bp->delivered & bit)) return false;
@@ -74,34 +74,36 @@ void tem_reduce_slabs_w_db(const float* part, int nchunks, int ntaps, int Cin, i
 void tem_reduce_slabs(const float* part, int nchunks, int64_t n, int64_t chunk_stride, float* out, hipStream_t s);
 
 // conv_bf16x3.hip: split-bf16 ("bf16x3") MFMA path
+// `mode` of the launchers and queries below: the arithmetic mode, TEM_ARITH_* (conv_arith.h says what each means)
+// planes, kind: TemArith::planes / ::pack of the layout
 int tem_pack_weights_bf16x3(const float* w, float* dst, int Cout, int Cin, int kd, int kh, int kw, int transpose,
-                            int nsplit, hipStream_t s);
+                            int planes, int kind, hipStream_t s);
 int tem_conv_fwd_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                         const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
                         int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
-                        int nsplit, float* stat, hipStream_t s);
+                        int mode, float* stat, hipStream_t s);
 // statistics rows of the patch kernel (the launches the team kernels leave to it), 0 when it runs split-K
 int64_t tem_conv_fwd_patch_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
 // conv_pp.hip: ping-pong team kernel for the levels with many patches (1 launched, 0 shape not taken, -1 error set)
 int tem_conv_fwd_pp(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                      const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H,
-                     int W, int Cin, int Cout, int kd, int kh, int kw, int act, int nsplit, float* stat, hipStream_t s);
+                     int W, int Cin, int Cout, int kd, int kh, int kw, int act, int mode, float* stat, hipStream_t s);
 // max_ld: the largest leading dimension of x / y / ref (1: the shape alone)
-int64_t tem_conv_pp_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld);
-int tem_conv_pp_tiles(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld);
+int64_t tem_conv_pp_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld);
+int tem_conv_pp_tiles(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld);
 // conv_zr.hip: z-reuse ping-pong kernel, 3x3x3 only (same return convention as tem_conv_fwd_pp)
 int tem_conv_fwd_zr(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp, const float* bias,
                     float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H, int W, int Cin, int Cout,
-                    int kd, int kh, int kw, int act, int nsplit, float* stat, hipStream_t s);
+                    int kd, int kh, int kw, int act, int mode, float* stat, hipStream_t s);
 int tem_conv_fwd_zr_splitk(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                            const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
                            int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
-                           int nsplit, float* stat, hipStream_t s);
-int tem_conv_zr_splitk_ks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit);
-int64_t tem_conv_zr_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld);
+                           int mode, float* stat, hipStream_t s);
+int tem_conv_zr_splitk_ks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode);
+int64_t tem_conv_zr_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld);
 // conv1x1_stream.hip: 1x1x1 convolution / data gradient as a streaming GEMM (false: not taken)
 bool tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* wp, const float* bias, float* y,
-                        int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act, int nsplit,
+                        int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act, int mode,
                         const float* stat, hipStream_t s);
 // shared with conv_mfma.hip
 int tem_fwd_ksplit(int64_t nblk, int nchunks);
@@ -121,22 +123,22 @@ void tem_splitk_epilogue_bwd_sums(int sty, const float* part, int ksplit, int N,
                                   const float* ref, int64_t ref_ld, float* y, int64_t y_ld, const TemDgradSumsReq& rq,
                                   hipStream_t s);
 int64_t tem_splitk_stat_blocks(int64_t V, int Cout);
-int64_t tem_conv_zr_splitk_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit);
+int64_t tem_conv_zr_splitk_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode);
 void tem_splitk_epilogue_stats(int sty, const float* part, int ksplit, int N, int64_t V, int Cout, const float* bias, int act,
                                const float* ref, int64_t ref_ld, float* y, int64_t y_ld, float* stat, hipStream_t s);
 int64_t tem_conv_wgrad_bf16x3_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
 int tem_conv_wgrad_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
                           int64_t g_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H, int W,
-                          int Cin, int Cout, int kd, int kh, int kw, int sd_layout, int h16, const float* w_sd,
+                          int Cin, int Cout, int kd, int kh, int kw, int sd_layout, int wg_kind /* TemWgradKind */, const float* w_sd,
                           const float* gamma, const float* beta, float* norm_sums, hipStream_t s);
 // largest |g| as a by-product of the z-sliding weight gradient (tem_conv3d_wgrad_gmax: TemConvCall::g_amax_out)
 int tem_conv_wgrad_gmax_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
-// h16 == 3 of tem_conv_wgrad_bf16x3 ("fp16 2x1": x^ two fp16 terms, g one fp16 term prescaled from TemConvCall::g_amax_in)
+// wg_kind TEM_WG_F16X2 of tem_conv_wgrad_bf16x3 ("fp16 2x1": x^ two fp16 terms, g one fp16 term prescaled from TemConvCall::g_amax_in)
 int tem_conv_wgrad_gscaled_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
 int tem_conv_wgrad_cs_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int st, int64_t x_cs);
-int tem_conv_wgrad_tr_fp32_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);   // h16 == 4
+int tem_conv_wgrad_tr_fp32_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);   // TEM_WG_FP32
 // conv_wgrad_tr.hip: z-sliding weight gradient with a staging team and transposing LDS reads (option wgrad_zs = 3)
-void tem_conv_wgrad_tr_launch(const TemConvCall& c, int h16, unsigned nblk, const float* x, int64_t x_ld, const float* scale, const float* shift,
+void tem_conv_wgrad_tr_launch(const TemConvCall& c, int wg_kind, unsigned nblk, const float* x, int64_t x_ld, const float* scale, const float* shift,
                               const float* g, int64_t g_ld, float* zpart, float* zdb, int N, int D, int H, int W, int Cin,
                               int Cout, int T, int nY, int nX, int zsegs, int Ss, int ncz, hipStream_t s);
 // TEM_BP_NORM_COEF of a call, as tem_wgrad_sums_launch reads it (delivered when the layer's group layout allows it)

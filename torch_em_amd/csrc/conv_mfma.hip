@@ -21,6 +21,7 @@
 //   merged by a deterministic fp64 reduction (no atomics).
 #include "tem_common.h"
 #include "conv_internal.h"
+#include "conv_arith.h"
 #include "tem_act.h"
 #include <type_traits>
 
@@ -869,32 +870,29 @@ int tem_conv_fwd_mfma(const float* x, int64_t x_ld, const float* scale, const fl
                         (!bias || (uintptr_t)bias % 16 == 0);
     if (ks > 1 && (!ws || !vec_ok || ws_bytes < (int64_t)ks * N * D * H * W * Cout * 4)) ks = 1;
     float* part = (float*)ws;
-#define GO(KD, KH, KW, TZ, TY, TX)                                                                                 \
-    do {                                                                                                           \
-        if (nr2)                                                                                                   \
-            launch_fwd<KD, KH, KW, TZ, TY, TX, 2>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, \
-                                                  Cin, Cout, act, ks, part, s);                                    \
-        else                                                                                                       \
-            launch_fwd<KD, KH, KW, TZ, TY, TX, 1>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, \
-                                                  Cin, Cout, act, ks, part, s);                                    \
-    } while (0)
+    auto go = [&](auto KD, auto KH, auto KW, auto TZ, auto TY, auto TX) {
+        tem_select_bool(nr2, [&](auto two) {
+            launch_fwd<KD(), KH(), KW(), TZ(), TY(), TX(), two() ? 2 : 1>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W,
+                                                                          Cin, Cout, act, ks, part, s);
+        });
+    };
+    using I1 = TemInt<1>; using I3 = TemInt<3>; using I4 = TemInt<4>; using I8 = TemInt<8>; using I16 = TemInt<16>;
     if (key == 7) {
-        GO(3, 3, 3, 4, 8, 8);
+        go(I3{}, I3{}, I3{}, I4{}, I8{}, I8{});
     } else if (key == 3) {
         if (flat)
-            GO(1, 3, 3, 1, 16, 16);
+            go(I1{}, I3{}, I3{}, I1{}, I16{}, I16{});
         else
-            GO(1, 3, 3, 4, 8, 8);
+            go(I1{}, I3{}, I3{}, I4{}, I8{}, I8{});
     } else if (key == 0) {
         if (flat)
-            GO(1, 1, 1, 1, 16, 16);
+            go(I1{}, I1{}, I1{}, I1{}, I16{}, I16{});
         else
-            GO(1, 1, 1, 4, 8, 8);
+            go(I1{}, I1{}, I1{}, I4{}, I8{}, I8{});
     } else {
         tem_set_error("tem_conv3d_fwd(mfma): kernel (%d,%d,%d) has no MFMA instantiation", kd, kh, kw);
         return TEM_EINVAL;
     }
-#undef GO
     return TEM_OK;
 }
 

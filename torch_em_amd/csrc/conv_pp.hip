@@ -18,6 +18,7 @@
 // contiguous unit ranges per XCD.
 #include "tem_common.h"
 #include "conv_internal.h"
+#include "conv_arith.h"
 #include "conv_split.h"
 #include "tem_act.h"
 #include <type_traits>
@@ -531,12 +532,11 @@ struct PpGeom {
 
 // Which shapes run on the ping-pong kernel: 3x3x3 (and 1x3x3 with depth) kernels, two 16-bit planes per operand, and
 // enough (patch, column group) units to give every team of every CU at least one.
-static PpGeom pp_geometry(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
+static PpGeom pp_geometry(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld) {
     PpGeom g = {};
     const long long opt = tem_option(TEM_OPT_CONV_FWD_VARIANT);
     if (opt == 0) return g;   // (2 = z-reuse kernel forced: shapes it does not take still come here)
-    if (c.stx || c.sty) return g;   // 16-bit activation storage: the z-reuse / patch kernels carry the element type
-    if (!(nsplit == 2 || nsplit == 4 || nsplit == 5 || nsplit == 7)) return g;   // bf16x3, fp16x3 (scaled lo), one fp16 / bf16 term (mixed modes)
+    if (!tem_pp_takes(mode, c)) return g;   // bf16x3, fp16x3 (scaled lo), one fp16 / bf16 term (mixed modes); fp32 tensors
     if (!(kh == 3 && kw == 3 && (kd == 3 || kd == 1))) return g;
     if (D < 4 || Cin % 16 || Cout % 32) return g;
     if ((int64_t)H * W * 8 * 4 * max_ld >= (1ll << 31)) return g;  // 32-bit byte offsets inside one halo / one patch
@@ -559,15 +559,15 @@ static PpGeom pp_geometry(const TemConvCall& c, int N, int D, int H, int W, int 
     return g;
 }
 
-int64_t tem_conv_pp_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
-    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
+int64_t tem_conv_pp_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld) {
+    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, max_ld);
     if (!g.variant) return -1;
     return (int64_t)g.nZ * g.nY * g.nX * g.WM;
 }
 
 // 32-column tiles per team of the instantiation this shape selects (1 or 2), 0 when the shape is not handled here
-int tem_conv_pp_tiles(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
-    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
+int tem_conv_pp_tiles(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld) {
+    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, max_ld);
     return g.variant ? g.CT : 0;
 }
 
@@ -602,10 +602,10 @@ static void pp_launch(const PpGeom& g, const float* x, int64_t x_ld, const float
 // patch kernel would write a differently shaped partials buffer (tem_last_error is set)
 int tem_conv_fwd_pp(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                      const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H,
-                     int W, int Cin, int Cout, int kd, int kh, int kw, int act, int nsplit, float* stat, hipStream_t s) {
+                     int W, int Cin, int Cout, int kd, int kh, int kw, int act, int mode, float* stat, hipStream_t s) {
     int64_t max_ld = x_ld > y_ld ? x_ld : y_ld;
     if (ref && ref_ld > max_ld) max_ld = ref_ld;
-    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
+    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, max_ld);
     if (!g.variant) return 0;
     // 16-byte epilogue accesses; statistics of a masked output are the patch kernel's business (never asked for together)
     if ((y_ld % 4) || ((uintptr_t)y % 16) || (ref && ((ref_ld % 4) || ((uintptr_t)ref % 16))) || (stat && ref) ||
@@ -617,29 +617,16 @@ int tem_conv_fwd_pp(const TemConvCall& c, const float* x, int64_t x_ld, const fl
         }
         return 0;
     }
-    const bool f16 = nsplit == 4;
-#define PPGO(KD, CT)                                                                                                  \
-    do {                                                                                                              \
-        if (nsplit == 5)                                                                                              \
-            pp_launch<KD, 3, 3, 4, CT, true, 1>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, \
-                                                Cout, act, stat, s);                                                  \
-        else if (nsplit == 7)                                                                                         \
-            pp_launch<KD, 3, 3, 4, CT, false, 1>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, \
-                                                 Cout, act, stat, s);                                                 \
-        else if (f16)                                                                                                 \
-            pp_launch<KD, 3, 3, 4, CT, true>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin,  \
-                                             Cout, act, stat, s);                                                     \
-        else                                                                                                          \
-            pp_launch<KD, 3, 3, 4, CT, false>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, \
-                                              Cout, act, stat, s);                                                    \
-    } while (0)
-    if (kd == 3) {
-        if (g.CT == 1) PPGO(3, 1);
-        else PPGO(3, 2);
-    } else {
-        if (g.CT == 1) PPGO(1, 1);
-        else PPGO(1, 2);
-    }
-#undef PPGO
+    const TemArith& a = tem_arith(mode);
+    tem_select_bool(kd == 3, [&](auto k3) {
+        tem_select_bool(g.CT == 2, [&](auto ct2) {
+            tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) {
+                tem_select_bool(a.planes == 1, [&](auto one) {
+                    pp_launch<k3() ? 3 : 1, 3, 3, 4, ct2() ? 2 : 1, f16(), one() ? 1 : 2>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld,
+                                                                                    N, D, H, W, Cin, Cout, act, stat, s);
+                });
+            });
+        });
+    });
     return 1;
 }

@@ -29,6 +29,7 @@
 // channel value per operand, so fp32 voxel-major records (128 B) ARE the operand layout -- plain ds_read_b32, no transpose.
 #include "tem_common.h"
 #include "conv_internal.h"
+#include "conv_arith.h"
 #include "conv_split.h"
 #include "tem_act.h"
 #include <set>
@@ -953,9 +954,9 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
     }
 }
 
-// h16: 0 bf16x3, 1 one fp16 term, 2 one bf16 term, 3 fp16 2x1 (g_amax required), 4 exact fp32.  Same arguments, partial-slab format and
+// wg_kind: TemWgradKind (TEM_WG_F16X2 needs c.g_amax_in).  Same arguments, partial-slab format and
 // plan (teams: one (Cin tile, Cout tile) pair per workgroup, KS2 = 1) as k_conv_wgrad_zt.
-void tem_conv_wgrad_tr_launch(const TemConvCall& c, int h16, unsigned nblk, const float* x, int64_t x_ld, const float* scale, const float* shift,
+void tem_conv_wgrad_tr_launch(const TemConvCall& c, int wg_kind, unsigned nblk, const float* x, int64_t x_ld, const float* scale, const float* shift,
                               const float* g, int64_t g_ld, float* zpart, float* zdb, int N, int D, int H, int W, int Cin,
                               int Cout, int T, int nY, int nX, int zsegs, int Ss, int ncz, hipStream_t s) {
     unsigned* const gmax = c.g_amax_out;
@@ -983,11 +984,11 @@ void tem_conv_wgrad_tr_launch(const TemConvCall& c, int h16, unsigned nblk, cons
                            reinterpret_cast<const TS*>(g), g_ld, zpart, zdb, N, D, H, W, Cin, Cout, T, nY, nX, zsegs, Ss, ncz, gmax, g_amax,
                            c.x_cs);
     };
-    if (c.stx == 1) launch16(&k_conv_wgrad_tr<1, tem_f16>, XT + GT + 4096, tem_f16{});
-    else if (c.stx == 2) launch16(&k_conv_wgrad_tr<2, tem_bf16>, XT + GT + 4096, tem_bf16{});
-    else if (h16 == 1) launch(&k_conv_wgrad_tr<1>, XT + GT);
-    else if (h16 == 2) launch(&k_conv_wgrad_tr<2>, XT + GT);
-    else if (h16 == 3) launch(&k_conv_wgrad_tr<3>, 2 * XT + GT);
-    else if (h16 == 4) launch(&k_conv_wgrad_tr<4>, (size_t)TR_XT_OF(128) + TR_GT_OF(128));
-    else launch(&k_conv_wgrad_tr<0>, 2 * XT + 2 * GT);
+    if (c.stx == TEM_ST_F16) launch16(&k_conv_wgrad_tr<TEM_WG_F16, tem_f16>, XT + GT + 4096, tem_f16{});
+    else if (c.stx == TEM_ST_BF16) launch16(&k_conv_wgrad_tr<TEM_WG_BF16, tem_bf16>, XT + GT + 4096, tem_bf16{});
+    else if (wg_kind == TEM_WG_F16) launch(&k_conv_wgrad_tr<TEM_WG_F16>, XT + GT);
+    else if (wg_kind == TEM_WG_BF16) launch(&k_conv_wgrad_tr<TEM_WG_BF16>, XT + GT);
+    else if (wg_kind == TEM_WG_F16X2) launch(&k_conv_wgrad_tr<TEM_WG_F16X2>, 2 * XT + GT);
+    else if (wg_kind == TEM_WG_FP32) launch(&k_conv_wgrad_tr<TEM_WG_FP32>, (size_t)TR_XT_OF(128) + TR_GT_OF(128));
+    else launch(&k_conv_wgrad_tr<TEM_WG_BF16X3>, 2 * XT + 2 * GT);
 }

@@ -28,6 +28,7 @@
 // epilogue of the previous unit (halo 1080 voxels, 18 16-byte loads per thread; epilogue 64 outputs per lane).
 #include "tem_common.h"
 #include "conv_internal.h"
+#include "conv_arith.h"
 #include "conv_split.h"
 #include "tem_act.h"
 #include <type_traits>
@@ -1063,14 +1064,13 @@ struct ZrGeom {
 
 // 3x3x3 kernels with two-plane (or the one-term mixed) layouts, 16-byte-vector friendly channel counts and at least one
 // unit per team of every CU (smaller launches stay with k_conv_pp / the split-K patch kernel).
-static ZrGeom zr_geometry(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
+static ZrGeom zr_geometry(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld) {
     ZrGeom g = {};
     const long long opt = tem_option(TEM_OPT_CONV_FWD_VARIANT);
     if (opt == 0 || opt == 1) return g;
-    if (!(nsplit == 2 || nsplit == 4 || nsplit == 5 || nsplit == 7 || (nsplit == 1 && tem_option(TEM_OPT_FP32_ZR) && !c.stx))) return g;
+    if (!tem_zr_takes(mode, c, Cin)) return g;
     if (!(kd == 3 && kh == 3 && kw == 3)) return g;
     if (D < 4 || Cin % 16 || Cout % 32) return g;
-    if (c.stx && (Cin % 32 || !(nsplit == 5 || nsplit == 7))) return g;   // 16-bit storage: whole 64-byte records per phase
     if ((int64_t)H * W * 8 * 4 * max_ld >= (1ll << 31)) return g;   // 32-bit byte offsets inside one halo / one patch
     static int ncu = 0;
     if (!ncu) {
@@ -1088,8 +1088,8 @@ static ZrGeom zr_geometry(const TemConvCall& c, int N, int D, int H, int W, int 
     return g;
 }
 
-int64_t tem_conv_zr_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit, int64_t max_ld) {
-    const ZrGeom g = zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
+int64_t tem_conv_zr_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld) {
+    const ZrGeom g = zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, max_ld);
     if (!g.ok) return -1;
     return (int64_t)g.nZ * g.nY * g.nX * 4;
 }
@@ -1129,6 +1129,27 @@ static void zr_launch(const TemConvCall& c, const ZrGeom& g, const float* x_, in
                        zr_tile_blocks(g), out_amax, (int64_t)(sizeof(T) == 2 ? c.x_cs : 0), (int64_t)(sizeof(T) == 2 && !KSPLIT ? c.y_cs : 0));
 }
 
+// The instantiation of k_conv_zr a call runs on -- NS planes per staged operand, fp16 or bf16 MFMAs, WIDE: 32 channels per
+// phase, T: element type of the tensors, X32: exact fp32 (v_mfma_f32_32x32x2_f32), XS: one team per workgroup.  One
+// selector for the direct and the split-K launch; `wide` is the launch's own answer for the one-term modes on fp32 tensors.
+template <int NS_, bool F16_, bool WIDE_ = false, typename T_ = float, bool X32_ = false, bool XS_ = false>
+struct ZrVariant {
+    static constexpr int NS = NS_;
+    static constexpr bool F16 = F16_, WIDE = WIDE_, X32 = X32_, XS = XS_;
+    using T = T_;
+};
+template <typename F>
+static void zr_variant(const TemConvCall& c, int mode, bool wide, F&& f) {
+    const TemArith& a = tem_arith(mode);
+    if (c.stx == TEM_ST_F16) f(ZrVariant<2, true, true, tem_f16>{});
+    else if (c.stx == TEM_ST_BF16) f(ZrVariant<2, false, true, tem_bf16>{});
+    else if (mode == TEM_ARITH_FP32 && tem_option(TEM_OPT_FP32_ZR) == 2) f(ZrVariant<2, false, false, float, true, true>{});
+    else if (mode == TEM_ARITH_FP32) f(ZrVariant<2, false, false, float, true>{});
+    else if (a.planes == 1 && wide) tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) { f(ZrVariant<2, f16(), true>{}); });
+    else if (a.planes == 1) tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) { f(ZrVariant<1, f16()>{}); });
+    else tem_select_bool(a.pack == TEM_PK_F16_LO12, [&](auto f16) { f(ZrVariant<2, f16()>{}); });
+}
+
 // Split-K launch for shapes zr_geometry() declines only because they have too few (tile, column tile) units: the input
 // channels are cut into ks slices so that ks x units >= two per CU, the partial sums go to the workspace and the common
 // split-K epilogue (conv_mfma.hip) applies bias / activation / ReLU mask.  -> 1 launched, 0 not taken.
@@ -1137,15 +1158,14 @@ static void zr_launch(const TemConvCall& c, const ZrGeom& g, const float* x_, in
 #endif
 // ks of the split-K launch for this shape (0: not taken): only shapes that zr_geometry() / pp_geometry() decline for
 // their unit count, tiles that are not mostly padding, at least two 16-channel chunks per slice
-int tem_conv_zr_splitk_ks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit) {
+int tem_conv_zr_splitk_ks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode) {
     const long long opt = tem_option(TEM_OPT_CONV_FWD_VARIANT);
     if (opt == 0 || opt == 1 || !tem_option(TEM_OPT_ZR_SPLITK)) return 0;
-    if (!(nsplit == 2 || nsplit == 4 || nsplit == 5 || nsplit == 7 || (nsplit == 1 && tem_option(TEM_OPT_FP32_ZR) && !c.stx))) return 0;
+    if (!tem_zr_takes(mode, c, Cin)) return 0;
     if (!(kd == 3 && kh == 3 && kw == 3) || D < 4 || Cin % 16 || Cout % 32) return 0;
     const bool t16 = c.stx != 0;   // 16-bit storage: slices of whole 32-channel chunks
-    if (t16 && (Cin % 32 || !(nsplit == 5 || nsplit == 7))) return 0;
-    if (zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, 1).ok) return 0;
-    if (tem_conv_pp_tiles(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, 1)) return 0;
+    if (zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, 1).ok) return 0;
+    if (tem_conv_pp_tiles(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, 1)) return 0;
     static int ncu = 0;
     if (!ncu) {
         ncu = tem_device_cus();
@@ -1164,9 +1184,9 @@ int tem_conv_zr_splitk_ks(const TemConvCall& c, int N, int D, int H, int W, int 
 int tem_conv_fwd_zr_splitk(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                            const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
                            int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
-                           int nsplit, float* stat, hipStream_t s) {
+                           int mode, float* stat, hipStream_t s) {
     // stat: [N][tem_conv_zr_splitk_stat_blocks()][Cout][2] -- the epilogue also writes the statistics partials of y
-    const int ks = ws ? tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit) : 0;
+    const int ks = ws ? tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode) : 0;
     if (!ks) return 0;
     if (stat && !tem_splitk_stat_blocks((int64_t)D * H * W, Cout)) return 0;
     if ((int64_t)H * W * 8 * 4 * (x_ld > Cout ? x_ld : Cout) >= (1ll << 31)) return 0;
@@ -1181,29 +1201,12 @@ int tem_conv_fwd_zr_splitk(const TemConvCall& c, const float* x, int64_t x_ld, c
     g.nunits = (int64_t)N * g.nZ * g.nY * g.nX * (Cout / 32) * ks;
     g.ok = 1;
     float* part = (float*)ws;
-#define ZRKS(NS, F16, WIDE)                                                                                            \
-    zr_launch<NS, F16, 0, true, WIDE>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,  \
-                                      TEM_ACT_NONE, nullptr, nullptr, s, ks)
-    const bool wide = (nsplit == 5 || nsplit == 7) && (Cin / 16 / ks) % 2 == 0 && (tem_option(TEM_OPT_ZR_WIDE) || c.stx);   // slices of whole 32-channel chunks
-    if (c.stx == 1)
-        zr_launch<2, true, 0, true, true, tem_f16>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
-                                                   TEM_ACT_NONE, nullptr, nullptr, s, ks);
-    else if (c.stx == 2)
-        zr_launch<2, false, 0, true, true, tem_bf16>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
-                                                     TEM_ACT_NONE, nullptr, nullptr, s, ks);
-    else if (nsplit == 1 && tem_option(TEM_OPT_FP32_ZR) == 2)
-        zr_launch<2, false, 0, true, false, float, true, true>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
-                                                               TEM_ACT_NONE, nullptr, nullptr, s, ks);
-    else if (nsplit == 1)
-        zr_launch<2, false, 0, true, false, float, true>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D, H, W, Cin, Cout,
-                                                         TEM_ACT_NONE, nullptr, nullptr, s, ks);
-    else if (nsplit == 5 && wide) ZRKS(2, true, true);
-    else if (nsplit == 7 && wide) ZRKS(2, false, true);
-    else if (nsplit == 5) ZRKS(1, true, false);
-    else if (nsplit == 7) ZRKS(1, false, false);
-    else if (nsplit == 4) ZRKS(2, true, false);
-    else ZRKS(2, false, false);
-#undef ZRKS
+    const bool wide = tem_arith_one_term(mode) && (Cin / 16 / ks) % 2 == 0 && (tem_option(TEM_OPT_ZR_WIDE) || c.stx);   // slices of whole 32-channel chunks
+    zr_variant(c, mode, wide, [&](auto v) {
+        using V = decltype(v);
+        zr_launch<V::NS, V::F16, 0, true, V::WIDE, typename V::T, V::X32, V::XS>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D,
+                                                                             H, W, Cin, Cout, TEM_ACT_NONE, nullptr, nullptr, s, ks);
+    });
     TemDgradSumsReq rq = {nullptr, 0, nullptr, nullptr, 0, nullptr, 0};
     if (!stat && c.wants(TEM_BP_NORM_SUMS)) {
         const TemByproducts* bp = c.bp;
@@ -1221,8 +1224,8 @@ int tem_conv_fwd_zr_splitk(const TemConvCall& c, const float* x, int64_t x_ld, c
 }
 
 // statistics partial rows per sample when tem_conv_fwd_zr_splitk takes the launch with stat != NULL (-1: it does not)
-int64_t tem_conv_zr_splitk_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int nsplit) {
-    if (!tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit)) return -1;
+int64_t tem_conv_zr_splitk_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode) {
+    if (!tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode)) return -1;
     const int64_t nb = tem_splitk_stat_blocks((int64_t)D * H * W, Cout);
     return nb > 0 ? nb : -1;
 }
@@ -1238,10 +1241,10 @@ static int zr_not_taken(const TemConvCall& c) {
 }
 int tem_conv_fwd_zr(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp, const float* bias,
                     float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H, int W, int Cin, int Cout,
-                    int kd, int kh, int kw, int act, int nsplit, float* stat, hipStream_t s) {
+                    int kd, int kh, int kw, int act, int mode, float* stat, hipStream_t s) {
     int64_t max_ld = x_ld > y_ld ? x_ld : y_ld;
     if (ref && ref_ld > max_ld) max_ld = ref_ld;
-    const ZrGeom g = zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, nsplit, max_ld);
+    const ZrGeom g = zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, max_ld);
     const bool strided = c.x_cs != 0 || c.y_cs != 0;
     if (strided && (!g.ok || !c.stx || ref || (c.x_cs && Cin % 32) || (c.x_cs % 8) || (c.y_cs % 8))) {
         tem_set_error("tem_conv3d_fwd_ex: chunk strides (x_cs / y_cs) need 16-bit tensors on the z-reuse kernel (tem_conv3d_fwd_kernel() "
@@ -1258,18 +1261,6 @@ int tem_conv_fwd_zr(const TemConvCall& c, const float* x, int64_t x_ld, const fl
         }
         return zr_not_taken(c);
     }
-#define ZRGO(NS, F16, WIDE)                                                                                                   \
-    do {                                                                                                                      \
-        if (stat)                                                                                                             \
-            zr_launch<NS, F16, 1, false, WIDE>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-        else if (ref && rcoef)                                                                                                \
-            zr_launch<NS, F16, 3, false, WIDE>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
-                                  const_cast<float*>(rcoef), in_amax, s);                                                     \
-        else if (ref)                                                                                                         \
-            zr_launch<NS, F16, 2, false, WIDE>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-        else                                                                                                                  \
-            zr_launch<NS, F16, 0, false, WIDE>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-    } while (0)
     const float* rcoef = c.ref_coef;
     if (rcoef) {
         if (!ref || stat || ((uintptr_t)rcoef % 16)) {
@@ -1279,63 +1270,24 @@ int tem_conv_fwd_zr(const TemConvCall& c, const float* x, int64_t x_ld, const fl
     }
     const unsigned* in_amax = c.in_amax;
     if (in_amax) {
-        if (nsplit != 4 || bias || scale || stat) {
+        if (mode != TEM_ARITH_F16X3 || bias || scale || stat) {
             tem_set_error("tem_conv3d_fwd_gscaled: fp16 two-term layout, no bias / norm / statistics");
             return -1;
         }
     }
     // one-term modes: 32 channels per phase whenever the channel count allows it (whole 128-byte lines per staging phase)
-    const bool wide = (nsplit == 5 || nsplit == 7) && Cin % 32 == 0 && tem_option(TEM_OPT_ZR_WIDE);
-#define ZRGO16(F16, T)                                                                                                        \
-    do {                                                                                                                      \
-        if (stat)                                                                                                             \
-            zr_launch<2, F16, 1, false, true, T>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-        else if (ref && rcoef)                                                                                                \
-            zr_launch<2, F16, 3, false, true, T>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
-                                  const_cast<float*>(rcoef), in_amax, s);                                                     \
-        else if (ref)                                                                                                         \
-            zr_launch<2, F16, 2, false, true, T>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-        else                                                                                                                  \
-            zr_launch<2, F16, 0, false, true, T>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-    } while (0)
-#define ZRGO32S()                                                                                                               \
-    do {                                                                                                                      \
-        if (stat)                                                                                                             \
-            zr_launch<2, false, 1, false, false, float, true, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-        else if (ref && rcoef)                                                                                                \
-            zr_launch<2, false, 3, false, false, float, true, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
-                                  const_cast<float*>(rcoef), in_amax, s);                                                     \
-        else if (ref)                                                                                                         \
-            zr_launch<2, false, 2, false, false, float, true, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-        else                                                                                                                  \
-            zr_launch<2, false, 0, false, false, float, true, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-    } while (0)
-#define ZRGO32()                                                                                                                \
-    do {                                                                                                                      \
-        if (stat)                                                                                                             \
-            zr_launch<2, false, 1, false, false, float, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-        else if (ref && rcoef)                                                                                                \
-            zr_launch<2, false, 3, false, false, float, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act,        \
-                                  const_cast<float*>(rcoef), in_amax, s);                                                     \
-        else if (ref)                                                                                                         \
-            zr_launch<2, false, 2, false, false, float, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-        else                                                                                                                  \
-            zr_launch<2, false, 0, false, false, float, true>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, stat, in_amax, s); \
-    } while (0)
-    if (c.stx == 1) ZRGO16(true, tem_f16);
-    else if (c.stx == 2) ZRGO16(false, tem_bf16);
-    else
-#undef ZRGO16
-    if (nsplit == 1 && tem_option(TEM_OPT_FP32_ZR) == 2) ZRGO32S();
-    else if (nsplit == 1) ZRGO32();
-    else if (nsplit == 5 && wide) ZRGO(2, true, true);
-    else if (nsplit == 7 && wide) ZRGO(2, false, true);
-    else if (nsplit == 5) ZRGO(1, true, false);
-    else if (nsplit == 7) ZRGO(1, false, false);
-    else if (nsplit == 4) ZRGO(2, true, false);
-    else ZRGO(2, false, false);
-#undef ZRGO
-#undef ZRGO32
-#undef ZRGO32S
+    const bool wide = tem_arith_one_term(mode) && Cin % 32 == 0 && tem_option(TEM_OPT_ZR_WIDE);
+    zr_variant(c, mode, wide, [&](auto v) {
+        using V = decltype(v);
+        // epilogue MODE: 1 statistics, 3 ReLU mask of ref + norm backward from rcoef (in the `stat` slot), 2 ReLU mask of ref, 0 plain
+        auto go = [&](auto m, float* st) {
+            zr_launch<V::NS, V::F16, m(), false, V::WIDE, typename V::T, V::X32, V::XS>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N,
+                                                                                D, H, W, Cin, Cout, act, st, in_amax, s);
+        };
+        if (stat) go(TemInt<1>{}, stat);
+        else if (ref && rcoef) go(TemInt<3>{}, const_cast<float*>(rcoef));
+        else if (ref) go(TemInt<2>{}, stat);
+        else go(TemInt<0>{}, stat);
+    });
     return 1;
 }

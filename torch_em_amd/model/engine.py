@@ -29,6 +29,7 @@ import torch
 import torch.nn as nn
 
 from .. import ops
+from ..arith import Arith, PackKind, pack_is_tiled
 
 _FORCE_GENERIC = os.environ.get("TEM_DISABLE_MFMA", "0") == "1"
 
@@ -63,7 +64,7 @@ _FORCE_GENERIC = os.environ.get("TEM_DISABLE_MFMA", "0") == "1"
 # The backward convolutions are LINEAR in the incoming gradient with masks fixed by the forward
 # pass, so their 1e-5 error is not amplified.
 PRECISION = os.environ.get("TEM_PRECISION", "split16")
-_F16X3_MODE = int(os.environ.get("TEM_F16X3_LAYOUT", "4"))
+_F16X3_MODE = Arith(int(os.environ.get("TEM_F16X3_LAYOUT", int(Arith.F16X3))))
 # Activation STORAGE of the two mixed modes (round 5): every tensor between two kernels of the step -- activations, saved
 # tensors, data gradients -- is fp16 ("amp") / bf16 ("amp_bf16") in HBM, as under torch.autocast in the reference trainer
 # (trainer/default_trainer.py:134-142, 781-794); the network input, the prediction, statistics, coefficients, parameters and
@@ -140,17 +141,18 @@ class ConvSpec:
 
     # --- packed weights (cached until the parameter changes) -----------------------
     def _modes(self):
-        mode_f = {"bf16x3": 2, "split": 3, "split16": 3, "amp": 5, "amp_bf16": 7}.get(PRECISION, 1)
+        mode_f = {"bf16x3": Arith.BF16X3, "split": Arith.BF16X6, "split16": Arith.BF16X6, "amp": Arith.F16,
+                  "amp_bf16": Arith.BF16}.get(PRECISION, Arith.FP32)
         if PRECISION == "split16" and self.norm is not None and self.k != (1, 1, 1):
             # fp16x3: the conv reads pre-normalised activations (|x^| of order 1..100 << 65504; clamped at 6e4).
             # TEM_F16X3_LAYOUT=6 selects the single-accumulator variant with prescaled operands (csrc/conv_split.h), which
             # fails the GroupNorm parity test (one-sided accumulation error): experiments only.
             mode_f = _F16X3_MODE
-        mode_d = 5 if PRECISION == "amp" else 7 if PRECISION == "amp_bf16" else \
-            2 if PRECISION in ("bf16x3", "mixed", "split", "split16") else 1
-        mf = mode_f if (not _FORCE_GENERIC) and ops.mfma_ok(self.cin, self.cout, self.k) else 0
-        md = mode_d if (not _FORCE_GENERIC) and ops.mfma_ok(self.cout, self.cin, self.k) else 0
-        mw = mode_d if (not _FORCE_GENERIC) and ops.mfma_ok(self.cin, self.cout, self.k, wgrad=True) else 0
+        mode_d = Arith.F16 if PRECISION == "amp" else Arith.BF16 if PRECISION == "amp_bf16" else \
+            Arith.BF16X3 if PRECISION in ("bf16x3", "mixed", "split", "split16") else Arith.FP32
+        mf = mode_f if (not _FORCE_GENERIC) and ops.mfma_ok(self.cin, self.cout, self.k) else Arith.VALU
+        md = mode_d if (not _FORCE_GENERIC) and ops.mfma_ok(self.cout, self.cin, self.k) else Arith.VALU
+        mw = mode_d if (not _FORCE_GENERIC) and ops.mfma_ok(self.cin, self.cout, self.k, wgrad=True) else Arith.VALU
         return mf, md, mw
 
     def packed(self):
@@ -190,8 +192,8 @@ _DGRAD16 = os.environ.get("TEM_DGRAD16", "0") == "1"
 
 def _dgrad16_ok(spec, g, gx) -> bool:
     return _DGRAD16 and PRECISION == "split16" and not _FORCE_GENERIC and not _OVERLAP_WGRAD and spec.k == (3, 3, 3) and \
-        spec.cin % 32 == 0 and spec.cout % 32 == 0 and ops.conv_fwd_family(g, spec.k, spec.cout, spec.cin, 4, y=gx) == 3 and \
-        ops.conv_wgrad_gmax_ok(g, spec.k, spec.cin, spec.cout, 2)
+        spec.cin % 32 == 0 and spec.cout % 32 == 0 and ops.conv_fwd_family(g, spec.k, spec.cout, spec.cin, Arith.F16X3, y=gx) == 3 and \
+        ops.conv_wgrad_gmax_ok(g, spec.k, spec.cin, spec.cout, Arith.BF16X3)
 
 
 # Weight gradients of the pre-normalised 3x3x3 convolutions in the "fp16 2x1" arithmetic (round 4, VERDICT r3 item 2:
@@ -271,6 +273,22 @@ def _generic_batchable(conv, k) -> bool:
     return _PACK_BATCH and (conv.out_channels * conv.in_channels * k[0] * k[1] * k[2]) % 8 == 0 and conv.weight.is_contiguous()
 
 
+def _pack_job(conv, ent, key, k, transpose):
+    """The job (ops.pack_table) that re-packs ent[key] in the batched launch, or None when the tensor needs a
+    tem_conv_pack_weights launch of its own."""
+    planes, kind = Arith(ent[key + "_mfma"]).pack
+    cout, cin = conv.out_channels, conv.in_channels
+    if kind == PackKind.FP32:
+        # exact fp32 (TEM_WL_MFMA): two 64-lane groups per 16-channel chunk, written by the tile kernel only
+        batched = _PACK_BATCH and pack_is_tiled(planes, k, cout, cin)
+    elif planes == 0:
+        # the generic fp32 layout (first conv, out_conv) rides along in the batched launch
+        batched = _generic_batchable(conv, k)
+    else:
+        batched = True
+    return (conv.weight, ent[key], cout, cin, k, transpose, planes, kind) if batched else None
+
+
 def _repack_stale(prepare_only: bool = False):
     """Re-pack the weights of every registered conv whose parameter changed in place (same storage, new version):
     all split-layout packs go into ONE tem_conv_pack_weights_batch launch, written into the existing buffers.
@@ -289,15 +307,9 @@ def _repack_stale(prepare_only: bool = False):
             if key not in ent:
                 continue
             if prepare_only:
-                if ent.get(key + "_mfma") in (2, 3, 4, 5, 6, 7) and not (key == "fwd_inf" and not ent.get("fwd_inf_used", False)):
-                    mode = ent[key + "_mfma"]
-                    jobs.append((w, ent[key], conv.out_channels, conv.in_channels, k, transpose,
-                                 3 if mode == 3 else 1 if mode in (5, 7) else 2, {4: 2, 5: 1, 6: 3}.get(mode, 0)))
-                elif ent.get(key + "_mfma") == 1 and _PACK_BATCH and k[0] * k[1] * k[2] <= 27 and conv.out_channels % 16 == 0 and \
-                        conv.in_channels % 16 == 0:
-                    jobs.append((w, ent[key], conv.out_channels, conv.in_channels, k, transpose, 2, 4))
-                elif ent.get(key + "_mfma") == 0 and _generic_batchable(conv, k):
-                    jobs.append((w, ent[key], conv.out_channels, conv.in_channels, k, transpose, 0, 0))
+                job = None if key == "fwd_inf" and not ent.get("fwd_inf_used", False) else _pack_job(conv, ent, key, k, transpose)
+                if job is not None:
+                    jobs.append(job)
                 continue
             if key == "dgrad" and "dgrad16" in ent and ent.pop("dgrad16_used", False) and not ent.pop("dgrad_used", False):
                 # this layer's data gradient runs in the fp16 layout: the bf16 pack is re-made lazily if ever needed again
@@ -307,18 +319,11 @@ def _repack_stale(prepare_only: bool = False):
                 # not used since the last refresh (a model that went back to training): drop it, it is re-packed lazily
                 del ent["fwd_inf"], ent["fwd_inf_mfma"]
                 continue
-            mode = ent[key + "_mfma"]
-            if mode in (2, 3, 4, 5, 6, 7):
-                jobs.append((w, ent[key], conv.out_channels, conv.in_channels, k, transpose,
-                             3 if mode == 3 else 1 if mode in (5, 7) else 2, {4: 2, 5: 1, 6: 3}.get(mode, 0)))
-            elif mode == 1 and _PACK_BATCH and k[0] * k[1] * k[2] <= 27 and conv.out_channels % 16 == 0 and conv.in_channels % 16 == 0:
-                # exact fp32 (TEM_WL_MFMA): two 64-lane groups per 16-channel chunk, written by the tile kernel (code 4)
-                jobs.append((w, ent[key], conv.out_channels, conv.in_channels, k, transpose, 2, 4))
-            elif mode == 0 and _generic_batchable(conv, k):
-                # the generic fp32 layout (first conv, out_conv) rides along in the batched launch: nsplit 0
-                jobs.append((w, ent[key], conv.out_channels, conv.in_channels, k, transpose, 0, 0))
+            job = _pack_job(conv, ent, key, k, transpose)
+            if job is not None:
+                jobs.append(job)
             else:
-                rest.append((ent, key, w, bool(transpose), mode))
+                rest.append((ent, key, w, bool(transpose), ent[key + "_mfma"]))
         if not prepare_only:
             ent["version"] = w._version
     for ent, key, w, transpose, mode in rest:
@@ -378,18 +383,18 @@ def _conv(spec: ConvSpec, x, y, stats=None, act=None, want_stats=False):
     ent = spec.packed()
     scale, shift = (stats[2], stats[3]) if stats is not None else (None, None)
     wpk, mode = ent["fwd"], ent["fwd_mfma"]
-    if _EXACT_FWD_MAX_VOXELS and not _TLS.no_grad_forward and mode in (2, 3, 4) and \
+    if _EXACT_FWD_MAX_VOXELS and not _TLS.no_grad_forward and mode in (Arith.BF16X3, Arith.BF16X6, Arith.F16X3) and \
             x.shape[1] * x.shape[2] * x.shape[3] <= _EXACT_FWD_MAX_VOXELS:
         if ent.get("fwd_exact_version") != spec.conv.weight._version:
-            ent["fwd_exact"] = ops.pack_weights(spec.conv.weight, transpose=False, mfma=1)
+            ent["fwd_exact"] = ops.pack_weights(spec.conv.weight, transpose=False, mfma=Arith.FP32)
             ent["fwd_exact_version"] = spec.conv.weight._version
-        ops.conv_fwd(x, ent["fwd_exact"], spec.conv.bias, y, spec.k, spec.cin, spec.cout, scale=scale, shift=shift, act=act, mfma=1)
+        ops.conv_fwd(x, ent["fwd_exact"], spec.conv.bias, y, spec.k, spec.cin, spec.cout, scale=scale, shift=shift, act=act, mfma=Arith.FP32)
         return None if want_stats else y   # the exact kernel writes no statistics: the caller runs norm_stats
-    if _TLS.no_grad_forward and _INFER_BF16X3 and mode == 3:
+    if _TLS.no_grad_forward and _INFER_BF16X3 and mode == Arith.BF16X6:
         if "fwd_inf" not in ent:  # packed on first use, refreshed with the others by _repack_stale
-            ent["fwd_inf"], ent["fwd_inf_mfma"] = ops.pack_weights(spec.conv.weight, transpose=False, mfma=2), 2
+            ent["fwd_inf"], ent["fwd_inf_mfma"] = ops.pack_weights(spec.conv.weight, transpose=False, mfma=Arith.BF16X3), Arith.BF16X3
         ent["fwd_inf_used"] = True
-        wpk, mode = ent["fwd_inf"], 2
+        wpk, mode = ent["fwd_inf"], Arith.BF16X3
     return ops.conv_fwd(x, wpk, spec.conv.bias, y, spec.k, spec.cin, spec.cout, scale=scale, shift=shift, act=act,
                         mfma=mode, want_stats=want_stats)
 
@@ -508,7 +513,7 @@ def _dgrad_launch(spec: ConvSpec, g, gx, ref, gmax, refnorm, bp=None):
         return
     if gmax is not None:
         if "dgrad16" not in ent:
-            ent["dgrad16"], ent["dgrad16_mfma"] = ops.pack_weights(spec.conv.weight, transpose=True, mfma=4), 4
+            ent["dgrad16"], ent["dgrad16_mfma"] = ops.pack_weights(spec.conv.weight, transpose=True, mfma=Arith.F16X3), Arith.F16X3
         ent["dgrad16_used"] = True
         ops.conv_fwd_gscaled(g, ent["dgrad16"], gx, spec.k, spec.cout, spec.cin, gmax, ref=ref, bp=bp)
         return
@@ -538,7 +543,7 @@ def _wgrad(spec: ConvSpec, x, g, grads: _Grads, stats=None, want_sums=False, gma
         rq = _sums_coef(spec, stats, x, on=sums_from is not None)
         return rq.attach(ops.conv_wgrad_gmax(x, g, spec.k, spec.cin, spec.cout, dw, db, gmax, scale=scale, shift=shift,
                                              mfma=ent["wgrad_mfma"], sums_from=sums_from, bp=rq.bp))
-    if ent["wgrad_mfma"] == 2 and _wgrad_f16x2_ok(spec, x, stats):
+    if ent["wgrad_mfma"] == Arith.BF16X3 and _wgrad_f16x2_ok(spec, x, stats):
         sums_from = None
         if want_sums and stats[4] == "sample" and db is not None and \
                 ops.conv_wgrad_sums_ok(x, spec.k, spec.cin, spec.cout, ent["wgrad_mfma"]):

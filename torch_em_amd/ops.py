@@ -12,6 +12,7 @@ from typing import Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from .arith import Arith, PackKind, pack_is_tiled
 
 ACT = {None: 0, "none": 0, "relu": 1, "sigmoid": 2}
 
@@ -25,22 +26,20 @@ PROFILER_FILTER = None
 
 
 def _fwd_tag(mfma, k, cout, pp=False):
+    mode = Arith(int(mfma))
     if pp in (3, 4):  # the z-reuse team kernel (csrc/conv_zr.hip); 4 = its split-K launch (16^3 / 32^3 levels)
-        return f"k_conv_zr_{'f16x3' if int(mfma) == 4 else 'f16' if int(mfma) == 5 else 'bf16' if int(mfma) == 7 else 'fp32' if int(mfma) == 1 else 'bf16x3'}<3,3,3>"
-    if pp:  # the ping-pong team kernel (csrc/conv_pp.hip)
-        return f"k_conv_pp_{'f16x3' if int(mfma) == 4 else 'bf16x3'}<{k[0]},{k[1]},{k[2]},CT={2 if cout % 64 == 0 else 1}>"
-    kind = ({2: "k_conv_fwd_bf16x3", 3: "k_conv_fwd_bf16x6", 4: "k_conv_fwd_f16x3", 5: "k_conv_fwd_f16",
-             6: "k_conv_fwd_f16x3", 7: "k_conv_fwd_bf16"}.get(int(mfma)) or
-            ("k_conv_fwd_mfma" if mfma else "k_conv_fwd_valu")) + f"<{k[0]},{k[1]},{k[2]}"
-    return kind + (f",NR={2 if cout % 64 == 0 else 1}>" if mfma else ">")
+        return f"k_conv_zr_{mode.facts.zr}<3,3,3>"
+    if pp:  # the ping-pong team kernel (csrc/conv_pp.hip): the one-term modes run under the bf16x3 tag
+        return f"k_conv_pp_{'f16x3' if mode is Arith.F16X3 else 'bf16x3'}<{k[0]},{k[1]},{k[2]},CT={2 if cout % 64 == 0 else 1}>"
+    kind = "k_conv_fwd_" + (mode.facts.fwd or ("mfma" if mode else "valu")) + f"<{k[0]},{k[1]},{k[2]}"
+    return kind + (f",NR={2 if cout % 64 == 0 else 1}>" if mode else ">")
 
 
 def _wgrad_tag(mfma, k, cout):
-    ntaps = k[0] * k[1] * k[2]
-    return ("k_conv_wgrad_bf16x3" if int(mfma) == 2 else "k_conv_wgrad_f16" if int(mfma) == 5 else
-            "k_conv_wgrad_bf16" if int(mfma) == 7 else "k_conv_wgrad_f16x2" if int(mfma) == 8 else
-            "k_conv_wgrad_mfma" if mfma else "k_conv_wgrad_valu") + \
-        f"<{k[0]},{k[1]},{k[2]}" + (f",NCO={2 if cout >= 64 else 1}" if int(mfma) in (2, 5, 7, 8) and ntaps > 1 else "") + ">(+reduce)"
+    mode = Arith(int(mfma))
+    split = mode.facts.wgrad
+    nco = f",NCO={2 if cout >= 64 else 1}" if split and k[0] * k[1] * k[2] > 1 else ""
+    return "k_conv_wgrad_" + (split or ("mfma" if mode else "valu")) + f"<{k[0]},{k[1]},{k[2]}{nco}>(+reduce)"
 
 
 def _prof_begin(t, tag=None):
@@ -222,9 +221,8 @@ def mfma_ok(cin: int, cout: int, k: Sequence[int], wgrad: bool = False) -> bool:
 
 def pack_weights(w: torch.Tensor, transpose: bool, mfma) -> torch.Tensor:
     """state_dict layout [Cout, Cin, (kd,) kh, kw] -> kernel layout (see tem_hip.h).
-    mfma: False/0 generic, True/1 exact-fp32 MFMA fragments, 2 / 3 split-bf16 fragments (2 / 3 terms), 4 split-fp16
-    (lo plane scaled), 5 one fp16 term (mixed precision), 6 split-fp16 with prescaled operands, 7 one bf16 term
-    (mixed precision with dtype bfloat16)."""
+    mfma: the arithmetic mode whose layout is written (arith.Arith; False / True: VALU / exact fp32) -- a TEM_WL_* layout
+    IS the mode it serves."""
     _req_cuda(w)
     w = w.detach().contiguous()
     cout, cin = w.shape[:2]
@@ -233,26 +231,30 @@ def pack_weights(w: torch.Tensor, transpose: bool, mfma) -> torch.Tensor:
     lib = _lib.load()
     dst = torch.empty(lib.tem_conv_packed_size(cout, cin, k[0], k[1], k[2]), dtype=torch.float32, device=w.device)
     _lib.check(lib.tem_conv_pack_weights(_p(w), _p(dst), cout, cin, k[0], k[1], k[2], int(transpose),
-                                         int(mfma), _stream(w)), "tem_conv_pack_weights")
+                                         int(Arith(int(mfma))), _stream(w)), "tem_conv_pack_weights")
     return dst
 
 
 def pack_table(jobs):
     """Device descriptor tables for tem_conv_pack_weights_tiles (all tensors whose kernel has <= 27 taps: one workgroup per
-    32 x 32 x taps tile) and tem_conv_pack_weights_batch (the rest).  jobs: (w, dst, cout, cin, k3, transpose, nsplit, fp16)."""
+    32 x 32 x taps tile) and tem_conv_pack_weights_batch (the rest).  jobs: (w, dst, cout, cin, k3, transpose, planes, kind)
+    with (planes, kind) = Arith.pack of the layout."""
     import struct
     tiled, gather = b"", b""
     ntile = nitem = n_t = n_g = 0
-    for w, dst, cout, cin, k, transpose, nsplit, fp16 in jobs:
+    for w, dst, cout, cin, k, transpose, planes, kind in jobs:
         taps = k[0] * k[1] * k[2]
-        if nsplit != 0 and taps <= 27 and cout % 16 == 0 and cin % 16 == 0:   # nsplit 0 = generic fp32 layout: gather kernel only
-            tiled += struct.pack("<qq8iq", w.data_ptr(), dst.data_ptr(), cout, cin, k[0], k[1], k[2], int(transpose), nsplit,
-                                 fp16, ntile)
+        if pack_is_tiled(planes, k, cout, cin):   # (planes 0 = generic fp32 layout: gather kernel only)
+            tiled += struct.pack("<qq8iq", w.data_ptr(), dst.data_ptr(), cout, cin, k[0], k[1], k[2], int(transpose), planes,
+                                 int(kind), ntile)
             ntile += ((cout + 31) // 32) * ((cin + 31) // 32)
             n_t += 1
         else:
+            if kind == PackKind.FP32:
+                raise ValueError(f"pack_table: the exact-fp32 layout of a {cout} x {cin} x {k} weight is not tileable and the "
+                                 "gather kernel cannot write it (use pack_weights)")
             gather += struct.pack("<qq8iq", w.data_ptr(), dst.data_ptr(), cout, cin, k[0], k[1], k[2], int(transpose),
-                                  nsplit, fp16, nitem)
+                                  planes, int(kind), nitem)
             nitem += cout * cin * taps // 8
             n_g += 1
     dev = jobs[0][0].device
@@ -357,9 +359,9 @@ def conv_wgrad_gnorm(x, g, y, coef, k, cin, cout, dw_out, db_out=None, scale=Non
     g_ld, y_ld = _act5(g)[5], _act5(y)[5]
     _same_st(g, y)
     lib = _lib.load()
-    nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], 0)
+    nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], Arith.VALU)
     ws = _workspace(nws, x.device)
-    kind = _wgrad_tag(0, k, cout) if PROFILER is not None else None
+    kind = _wgrad_tag(Arith.VALU, k, cout) if PROFILER is not None else None
     ev0 = _prof_begin(x, kind)
     if _st(x) or _st(g):
         _lib.check(lib.tem_conv3d_wgrad_gnorm_st(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(y), y_ld, _p(coef), _p(dw_out),
@@ -411,7 +413,7 @@ def conv_wgrad_gmax_ok(x, k, cin, cout, mfma) -> bool:
     return bool(_lib.load().tem_conv3d_wgrad_gmax_ok(N, D, H, W, cin, cout, k[0], k[1], k[2], int(mfma)))
 
 
-def conv_wgrad_gmax(x, g, k, cin, cout, dw_out, db_out, gmax, scale=None, shift=None, mfma=2, sums_from=None, bp=None):
+def conv_wgrad_gmax(x, g, k, cin, cout, dw_out, db_out, gmax, scale=None, shift=None, mfma=Arith.BF16X3, sums_from=None, bp=None):
     """conv_wgrad that also leaves the bit pattern of max |g| in `gmax` (int32[1], cleared by the caller) -- the prescale
     of the fp16 two-term data gradient (conv_fwd_gscaled).  sums_from as in conv_wgrad -> sums[N, cin, 2] or None."""
     _req_cuda(x, g, dw_out, gmax)
@@ -521,18 +523,18 @@ def conv_wgrad_gscaled(x, g, k, cin, cout, dw_out, db_out, amax, scale=None, shi
     N, D, H, W, C, x_ld = _act5(x)
     g_ld = _act5(g)[5]
     lib = _lib.load()
-    nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], 8)
+    nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], Arith.F16X2)
     ws = _workspace(nws, x.device)
     w = gamma = beta = sums = None
     if sums_from is not None:
         w, gamma, beta = sums_from
         w = w.detach()
         sums = torch.empty((N, cin, 2), dtype=torch.float32, device=x.device)
-    kind = _wgrad_tag(8, k, cout) if PROFILER is not None else None
+    kind = _wgrad_tag(Arith.F16X2, k, cout) if PROFILER is not None else None
     ev0 = _prof_begin(x, kind)
     _lib.check(lib.tem_conv3d_wgrad_ex(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(w), _p(gamma), _p(beta),
                                        _p(dw_out), _p(db_out), _p(sums), _p(amax), None, _p(ws), nws, N, D, H, W, cin, cout,
-                                       k[0], k[1], k[2], 8, 0, bp.ref() if bp is not None else None, _stream(x)), "tem_conv3d_wgrad_ex")
+                                       k[0], k[1], k[2], Arith.F16X2, 0, bp.ref() if bp is not None else None, _stream(x)), "tem_conv3d_wgrad_ex")
     if ev0 is not None:
         _prof_end(x, ev0, (kind, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2])
     return sums
@@ -540,7 +542,7 @@ def conv_wgrad_gscaled(x, g, k, cin, cout, dw_out, db_out, amax, scale=None, shi
 
 def conv_fwd_gscaled(x, w_packed, y, k, cin, cout, amax, ref=None, bp=None):
     """Data gradient with fp32-class products (tem_conv3d_fwd_gscaled): x an unnormalised gradient, w_packed =
-    pack_weights(w, transpose=True, mfma=4), amax = int32[1] holding the bit pattern of max |x| (conv_wgrad_gmax)."""
+    pack_weights(w, transpose=True, mfma=Arith.F16X3), amax = int32[1] holding the bit pattern of max |x| (conv_wgrad_gmax)."""
     _req_cuda(x, w_packed, y, amax)
     N, D, H, W, C, x_ld = _act5(x)
     Ny, Dy, Hy, Wy, Cy, y_ld = _act5(y)
@@ -548,13 +550,13 @@ def conv_fwd_gscaled(x, w_packed, y, k, cin, cout, amax, ref=None, bp=None):
         raise ValueError(f"conv_fwd_gscaled: shape mismatch x{tuple(x.shape)} y{tuple(y.shape)} cin={cin} cout={cout}")
     ref_ld = _act5(ref)[5] if ref is not None else 0
     lib = _lib.load()
-    nws = lib.tem_conv3d_fwd_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], 1)
+    nws = lib.tem_conv3d_fwd_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], Arith.FP32)
     ws = _workspace(nws, x.device) if nws else None
-    kind = _fwd_tag(4, k, cout, 3) if PROFILER is not None else None
+    kind = _fwd_tag(Arith.F16X3, k, cout, 3) if PROFILER is not None else None
     ev0 = _prof_begin(x, kind)
     if bp is not None:
         _lib.check(lib.tem_conv3d_fwd_ex(_p(x), x_ld, None, None, _p(w_packed), None, _p(y), y_ld, _p(ref), ref_ld, _p(ws), nws,
-                                         N, D, H, W, cin, cout, k[0], k[1], k[2], ACT[None], 4, _p(amax), None, None, 0, 0, 0,
+                                         N, D, H, W, cin, cout, k[0], k[1], k[2], ACT[None], Arith.F16X3, _p(amax), None, None, 0, 0, 0,
                                          bp.ref(), _stream(x)), "tem_conv3d_fwd_ex")
     else:
         _lib.check(lib.tem_conv3d_fwd_gscaled(_p(x), x_ld, _p(w_packed), _p(y), y_ld, _p(ref), ref_ld, _p(amax), _p(ws), nws,
@@ -576,7 +578,7 @@ def conv_fwd_refnorm(x, w_packed, y, k, cin, cout, ref, coef, mfma, bp=None):
     ref_ld = _act5(ref)[5]
     _same_st(x, y, ref)
     lib = _lib.load()
-    nws = lib.tem_conv3d_fwd_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], 1)
+    nws = lib.tem_conv3d_fwd_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], Arith.FP32)
     ws = _workspace(nws, x.device) if nws else None
     kind = _fwd_tag(mfma, k, cout, 3) if PROFILER is not None else None
     ev0 = _prof_begin(x, kind)
