@@ -211,7 +211,7 @@ _WGRAD_F16X2 = os.environ.get("TEM_WGRAD_ARITH", "f16x2") == "f16x2"
 
 _FUSE_OUT_BWD = os.environ.get("TEM_FUSE_OUT_BWD", "1") != "0"   # out_conv: weight gradient + masked data gradient in one kernel
 _FUSE_AMAX = os.environ.get("TEM_FUSE_AMAX", "1") != "0"   # 0: every fp16 2x1 weight gradient runs its own absmax pass
-# the weight gradient that delivers the norm sums also finishes them into the norm-backward coefficients; 0: tem_norm_bwd_coef
+# the weight gradient that delivers the norm sums also finishes them into the norm-backward coefficients; 0: ops.norm_bwd_coef
 _FUSE_COEF = os.environ.get("TEM_FUSE_NORM_COEF", "1") != "0"
 _FUSE_POOL_STATS = os.environ.get("TEM_FUSE_POOL_STATS", "1") != "0"   # max-pool forward writes the statistics partials of its output
 
@@ -366,7 +366,7 @@ _TLS = _ThreadFlags()
 
 
 # Forward statistics of a conv output that feeds the next norm directly (conv1 -> norm2 of every ConvBlock) come out of
-# the conv's epilogue instead of a separate pass over the tensor (tem_conv3d_fwd_stats); TEM_FUSE_STATS=0 disables.
+# the conv's epilogue instead of a separate pass over the tensor (ops.conv_fwd(want_stats=True)); TEM_FUSE_STATS=0 disables.
 _FUSE_STATS = os.environ.get("TEM_FUSE_STATS", "1") != "0"
 _FUSE_CONCAT_STATS = os.environ.get("TEM_FUSE_CONCAT_STATS", "1") != "0"
 
@@ -523,7 +523,7 @@ def _dgrad_launch(spec: ConvSpec, g, gx, ref, gmax, refnorm, bp=None):
     ops.conv_fwd(g, ent["dgrad"], None, gx, spec.k, spec.cout, spec.cin, ref=ref, mfma=ent["dgrad_mfma"], bp=bp)
 
 
-# Norm-backward sums from the weight gradient (csrc/wgrad_sums.hip, tem_conv3d_wgrad_sums): the reduction pass over the
+# Norm-backward sums from the weight gradient (csrc/wgrad_sums.hip, ops.conv_wgrad(sums_from=...)): the reduction pass over the
 # data gradient and the norm input disappears for the layers that qualify.  tem_set_option("wgrad_sums", 0) disables.
 def _wgrad(spec: ConvSpec, x, g, grads: _Grads, stats=None, want_sums=False, gmax=None, amax=None):
     """-> sums[N, Cin, 2] for _norm_bwd_inplace when want_sums and the layer qualifies, else None.
@@ -534,21 +534,22 @@ def _wgrad(spec: ConvSpec, x, g, grads: _Grads, stats=None, want_sums=False, gma
     dw = grads.view(spec.conv.weight)
     db = grads.view(spec.conv.bias) if spec.conv.bias is not None else None
     vox = x.shape[0] * x.shape[1] * x.shape[2] * x.shape[3]
-    if gmax is not None:
-        sums_from = None
+
+    def sums_args():
+        """(weight, gamma, beta) for `sums_from` when the caller wants the sums and this layer's weight gradient delivers them"""
         if want_sums and stats is not None and stats[4] == "sample" and db is not None and \
                 ops.conv_wgrad_sums_ok(x, spec.k, spec.cin, spec.cout, ent["wgrad_mfma"]):
             _, gamma, beta, _ = spec.norm_args()
-            sums_from = (spec.conv.weight, gamma, beta)
+            return spec.conv.weight, gamma, beta
+        return None
+
+    if gmax is not None:
+        sums_from = sums_args()
         rq = _sums_coef(spec, stats, x, on=sums_from is not None)
         return rq.attach(ops.conv_wgrad_gmax(x, g, spec.k, spec.cin, spec.cout, dw, db, gmax, scale=scale, shift=shift,
                                              mfma=ent["wgrad_mfma"], sums_from=sums_from, bp=rq.bp))
     if ent["wgrad_mfma"] == Arith.BF16X3 and _wgrad_f16x2_ok(spec, x, stats):
-        sums_from = None
-        if want_sums and stats[4] == "sample" and db is not None and \
-                ops.conv_wgrad_sums_ok(x, spec.k, spec.cin, spec.cout, ent["wgrad_mfma"]):
-            _, gamma, beta, _ = spec.norm_args()
-            sums_from = (spec.conv.weight, gamma, beta)
+        sums_from = sums_args()
         if amax is None:
             amax = getattr(g, "_tem_amax", None)
             if amax is not None and getattr(g, "_tem_amax_ver", None) != g._version:
@@ -558,12 +559,11 @@ def _wgrad(spec: ConvSpec, x, g, grads: _Grads, stats=None, want_sums=False, gma
         rq = _sums_coef(spec, stats, x, on=sums_from is not None)
         return rq.attach(ops.conv_wgrad_gscaled(x, g, spec.k, spec.cin, spec.cout, dw, db, amax, scale=scale, shift=shift,
                                                 sums_from=sums_from, bp=rq.bp))
-    if want_sums and stats is not None and stats[4] == "sample" and db is not None and not _OVERLAP_WGRAD and \
-            ops.conv_wgrad_sums_ok(x, spec.k, spec.cin, spec.cout, ent["wgrad_mfma"]):
-        _, gamma, beta, _ = spec.norm_args()
+    sums_from = None if _OVERLAP_WGRAD else sums_args()
+    if sums_from is not None:
         rq = _sums_coef(spec, stats, x)
         return rq.attach(ops.conv_wgrad(x, g, spec.k, spec.cin, spec.cout, dw, db, scale=scale, shift=shift,
-                                        mfma=ent["wgrad_mfma"], sums_from=(spec.conv.weight, gamma, beta), bp=rq.bp))
+                                        mfma=ent["wgrad_mfma"], sums_from=sums_from, bp=rq.bp))
     if not _OVERLAP_WGRAD or (_OVERLAP_WGRAD == 1 and vox > _OVERLAP_MAX_VOXELS):
         ops.conv_wgrad(x, g, spec.k, spec.cin, spec.cout, dw, db, scale=scale, shift=shift, mfma=ent["wgrad_mfma"])
         return
@@ -713,11 +713,11 @@ def _block_fwd(blk, xin, out, in_partials2=None, out_stats=False, in_partials=No
 
 # The norm in front of a decoder block reads concat(upsample(u), skip).  Its backward needs no elementwise pass over that
 # (largest) tensor: the two kernels that consume the gradient next -- upsample backward and the encoder's max-pool
-# backward -- apply gx = a*g - m1 - (x - mean)*m2r on the fly (ops.norm_bwd_coef / tem_upsample_bwd_norm /
-# tem_maxpool3d_bwd_norm).  TEM_DEFER_CONCAT_NORM=0 restores the in-place pass.
+# backward -- apply gx = a*g - m1 - (x - mean)*m2r on the fly (ops.norm_bwd_coef / ops.upsample_bwd(norm=...) /
+# ops.maxpool_bwd(gskip_coef=...)).  TEM_DEFER_CONCAT_NORM=0 restores the in-place pass.
 _DEFER_CONCAT_NORM = os.environ.get("TEM_DEFER_CONCAT_NORM", "1") != "0"
-# norm backward + ReLU mask in the epilogue of the data-gradient kernel (tem_conv3d_fwd_refnorm); TEM_FUSE_NORM_BWD_DGRAD=0:
-# the elementwise pass of tem_norm_bwd_from_sums
+# norm backward + ReLU mask in the epilogue of the data-gradient kernel (ops.conv_fwd_refnorm); TEM_FUSE_NORM_BWD_DGRAD=0:
+# the elementwise pass of ops.norm_bwd(sums=...)
 _FUSE_NORM_BWD_DGRAD = os.environ.get("TEM_FUSE_NORM_BWD_DGRAD", "1") != "0"
 
 
@@ -759,7 +759,7 @@ def _block_bwd(bs, gout, gin, grads: _Grads, defer_input_norm=False):
             not (gin is None and not affine1) and not _dgrad16_ok(c2, gout, ga1) and c2.conv.bias is not None and \
             ops.conv_wgrad_sums_ok(a1, c2.k, c2.cin, c2.cout, c2.packed()["wgrad_mfma"]) and \
             ops.conv_fwd_family(gout, c2.k, c2.cout, c2.cin, c2.packed()["dgrad_mfma"], y=ga1, ref=a1) == 3:
-        # The weight gradient runs FIRST and delivers the sums of norm2's backward (tem_conv3d_wgrad_sums) without the data
+        # The weight gradient runs FIRST and delivers the sums of norm2's backward (ops.conv_wgrad(sums_from=...)) without the data
         # gradient existing yet; with the coefficients known, the data-gradient kernel applies norm2's backward and the
         # ReLU mask of a1 in its epilogue: no elementwise pass over ga1 and a1 (0.28 ms at 2 x 128^3 x 32)
         sums = _wgrad(c2, a1, gout, grads, bs["s2"], want_sums=True)
@@ -918,8 +918,8 @@ def _forward_impl_body(model, x: torch.Tensor, keep: bool):
             lv["cat_c"], lv["crop"] = cat, off
         # statistics of the concat for the block's first norm without reading it: the skip half's partial sums were
         # written by the encoder conv that produced it, the upsampled half's come out of the upsampling kernel (factor 2:
-        # tem_upsample_fwd_stats) or follow from the low-resolution t (sum y = sum (U^T 1) t, sum y^2 = sum t (U^T U t):
-        # tem_upsample_stats)
+        # ops.upsample_fwd(stats=True)) or follow from the low-resolution t (sum y = sum (U^T 1) t, sum y^2 = sum t (U^T U t):
+        # ops.upsample_stats)
         p2 = None
         skip_part = None if cropped else lv["bs"].get("out_part")
         want_stats = False

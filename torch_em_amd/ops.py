@@ -42,20 +42,28 @@ def _wgrad_tag(mfma, k, cout):
     return "k_conv_wgrad_" + (split or ("mfma" if mode else "valu")) + f"<{k[0]},{k[1]},{k[2]}{nco}>(+reduce)"
 
 
-def _prof_begin(t, tag=None):
-    if PROFILER is None or (PROFILER_FILTER is not None and tag not in PROFILER_FILTER):
-        return None
-    ev = torch.cuda.Event(enable_timing=True)
-    ev.record(torch.cuda.current_stream(t.device))
-    return ev
+class _Timed:
+    """`with _Timed(t, tag, (N, D, H, W), cin, cout, k): <launch>` -- the PROFILER bracket of one convolution launch: two events
+    on the stream of `t` around the body and one (tag, flops, start, end) entry; nothing when the launch is not timed."""
+    __slots__ = ("args", "ev0")
 
+    def __init__(self, *args):
+        self.args = args
 
-def _prof_end(t, ev0, tag, flops):
-    if ev0 is None:
-        return
-    ev1 = torch.cuda.Event(enable_timing=True)
-    ev1.record(torch.cuda.current_stream(t.device))
-    PROFILER.append((tag, flops, ev0, ev1))
+    def __enter__(self):
+        t, tag = self.args[:2]
+        self.ev0 = None
+        if PROFILER is not None and (PROFILER_FILTER is None or tag in PROFILER_FILTER):
+            self.ev0 = torch.cuda.Event(enable_timing=True)
+            self.ev0.record(torch.cuda.current_stream(t.device))
+
+    def __exit__(self, exc_type, exc, tb):
+        if self.ev0 is None or exc_type is not None:
+            return
+        t, tag, (N, D, H, W), cin, cout, k = self.args
+        ev1 = torch.cuda.Event(enable_timing=True)
+        ev1.record(torch.cuda.current_stream(t.device))
+        PROFILER.append(((tag, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2], self.ev0, ev1))
 
 
 def _stream(t: torch.Tensor):
@@ -273,10 +281,25 @@ def pack_weights_batch(tab):
                    "tem_conv_pack_weights_batch")
 
 
+def _launch_fwd(x, x_ld, w_packed, y, y_ld, ref, ref_ld, dims, cin, cout, k, mode, ws_mode, tag, scale=None, shift=None,
+                bias=None, act=None, in_amax=None, ref_coef=None, part=None, x_cs=0, y_cs=0, bp=None):
+    """The one tem_conv3d_fwd_ex call of the forward / data-gradient wrappers.  mode: the use_mfma word of the launch;
+    ws_mode: the one the workspace is sized for (None: no workspace); tag: the profiler's kernel tag (None: not timed)."""
+    N, D, H, W = dims
+    lib = _lib.load()
+    nws = lib.tem_conv3d_fwd_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], ws_mode) if ws_mode is not None else 0
+    ws = _workspace(nws, x.device) if nws else None
+    with _Timed(x, tag, dims, cin, cout, k):
+        _lib.check(lib.tem_conv3d_fwd_ex(_p(x), x_ld, _p(scale), _p(shift), _p(w_packed), _p(bias), _p(y), y_ld, _p(ref),
+                                         ref_ld, _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], ACT[act], mode,
+                                         _p(in_amax), _p(ref_coef), _p(part), part.shape[1] if part is not None else 0,
+                                         x_cs, y_cs, bp.ref() if bp is not None else None, _stream(x)), "tem_conv3d_fwd_ex")
+
+
 def conv_fwd(x, w_packed, bias, y, k, cin, cout, scale=None, shift=None, act=None, ref=None, mfma=False,
              want_stats=False, bp=None):
-    """want_stats: also emit the first stage of the statistics of y (tem_conv3d_fwd_stats) when this launch can; returns
-    (partials [N, nblk, cout, 2], nblk) then, else y (and `None` for launches that cannot: use norm_stats).
+    """want_stats: also emit the first stage of the statistics of y (stat_part of tem_conv3d_fwd_ex) when this launch can;
+    returns (partials [N, nblk, cout, 2], nblk) then, else y (and `None` for launches that cannot: use norm_stats).
     bp: Byproducts of this call (tem_conv3d_fwd_ex), not together with want_stats."""
     if bp is not None and want_stats:
         raise ValueError("conv_fwd: by-products and want_stats exclude each other")
@@ -291,8 +314,6 @@ def conv_fwd(x, w_packed, bias, y, k, cin, cout, scale=None, shift=None, act=Non
         _same_st(y, ref)
     lib = _lib.load()
     mode = _mode(mfma, x, y)
-    nws = lib.tem_conv3d_fwd_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], mode) if mfma else 0
-    ws = _workspace(nws, x.device) if nws else None
     kind = None
     if PROFILER is not None:
         pp = lib.tem_conv3d_fwd_kernel_ld(N, D, H, W, cin, cout, k[0], k[1], k[2], mode, x_ld, y_ld, ref_ld,
@@ -300,32 +321,11 @@ def conv_fwd(x, w_packed, bias, y, k, cin, cout, scale=None, shift=None, act=Non
         kind = _fwd_tag(mfma, k, cout, pp)
     nblk = lib.tem_conv3d_fwd_stat_blocks_ld(N, D, H, W, cin, cout, k[0], k[1], k[2], mode, x_ld, y_ld, ref_ld,
                                              _misaligned(x, w_packed, bias, y, ref, scale, shift)) if want_stats else 0
-    ev0 = _prof_begin(x, kind)
-    part = None
-    if _cs(x) or _cs(y):
-        if want_stats and nblk <= 0:
-            raise RuntimeError("conv_fwd: a planar tensor needs the z-reuse kernel (statistics rows expected)")
-        if nblk > 0:
-            part = torch.empty((N, nblk, cout, 2), dtype=torch.float32, device=x.device)
-        _lib.check(lib.tem_conv3d_fwd_ex(_p(x), x_ld, _p(scale), _p(shift), _p(w_packed), _p(bias), _p(y), y_ld, _p(ref),
-                                         ref_ld, _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], ACT[act], mode,
-                                         None, None, _p(part), nblk if part is not None else 0, _cs(x), _cs(y),
-                                         bp.ref() if bp is not None else None, _stream(x)), "tem_conv3d_fwd_ex")
-    elif nblk > 0:
-        part = torch.empty((N, nblk, cout, 2), dtype=torch.float32, device=x.device)
-        _lib.check(lib.tem_conv3d_fwd_stats(_p(x), x_ld, _p(scale), _p(shift), _p(w_packed), _p(bias), _p(y), y_ld,
-                                            _p(ref), ref_ld, _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2],
-                                            ACT[act], mode, _p(part), nblk, _stream(x)), "tem_conv3d_fwd_stats")
-    elif bp is not None:
-        _lib.check(lib.tem_conv3d_fwd_ex(_p(x), x_ld, _p(scale), _p(shift), _p(w_packed), _p(bias), _p(y), y_ld, _p(ref),
-                                         ref_ld, _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], ACT[act], mode,
-                                         None, None, None, 0, 0, 0, bp.ref(), _stream(x)), "tem_conv3d_fwd_ex")
-    else:
-        _lib.check(lib.tem_conv3d_fwd(_p(x), x_ld, _p(scale), _p(shift), _p(w_packed), _p(bias), _p(y), y_ld, _p(ref),
-                                      ref_ld, _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], ACT[act], mode,
-                                      _stream(x)), "tem_conv3d_fwd")
-    if ev0 is not None:
-        _prof_end(x, ev0, (kind, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2])
+    if want_stats and nblk <= 0 and (_cs(x) or _cs(y)):
+        raise RuntimeError("conv_fwd: a planar tensor needs the z-reuse kernel (statistics rows expected)")
+    part = torch.empty((N, nblk, cout, 2), dtype=torch.float32, device=x.device) if nblk > 0 else None
+    _launch_fwd(x, x_ld, w_packed, y, y_ld, ref, ref_ld, (N, D, H, W), cin, cout, k, mode, mode if mfma else None, kind,
+                scale=scale, shift=shift, bias=bias, act=act, part=part, x_cs=_cs(x), y_cs=_cs(y), bp=bp)
     if want_stats:
         return None if part is None else (part, int(nblk))
     return y
@@ -353,7 +353,7 @@ def conv_wgrad_gnorm_ok(k, cin, cout, mfma) -> bool:
 
 def conv_wgrad_gnorm(x, g, y, coef, k, cin, cout, dw_out, db_out=None, scale=None, shift=None):
     """First-layer weight gradient with the backward of the norm behind this conv's ReLU applied to g on load
-    (tem_conv3d_wgrad_gnorm): g raw data gradient, y this conv's output, coef from norm_bwd_coef."""
+    (tem_conv3d_wgrad_gnorm_st): g raw data gradient, y this conv's output, coef from norm_bwd_coef."""
     _req_cuda(x, g, y, coef, dw_out)
     N, D, H, W, C, x_ld = _act5(x)
     g_ld, y_ld = _act5(g)[5], _act5(y)[5]
@@ -362,17 +362,10 @@ def conv_wgrad_gnorm(x, g, y, coef, k, cin, cout, dw_out, db_out=None, scale=Non
     nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], Arith.VALU)
     ws = _workspace(nws, x.device)
     kind = _wgrad_tag(Arith.VALU, k, cout) if PROFILER is not None else None
-    ev0 = _prof_begin(x, kind)
-    if _st(x) or _st(g):
+    with _Timed(x, kind, (N, D, H, W), cin, cout, k):
         _lib.check(lib.tem_conv3d_wgrad_gnorm_st(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(y), y_ld, _p(coef), _p(dw_out),
                                                  _p(db_out), _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], 1, _st(x), _st(g),
                                                  _stream(x)), "tem_conv3d_wgrad_gnorm_st")
-    else:
-        _lib.check(lib.tem_conv3d_wgrad_gnorm(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(y), y_ld, _p(coef), _p(dw_out),
-                                              _p(db_out), _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], 1, _stream(x)),
-                   "tem_conv3d_wgrad_gnorm")
-    if ev0 is not None:
-        _prof_end(x, ev0, (kind, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2])
 
 
 def conv_wgrad_sums_ok(x, k, cin, cout, mfma) -> bool:
@@ -380,32 +373,50 @@ def conv_wgrad_sums_ok(x, k, cin, cout, mfma) -> bool:
     return bool(_lib.load().tem_conv3d_wgrad_sums_ok(N, D, H, W, cin, cout, k[0], k[1], k[2], _mode(mfma, x, x)))
 
 
+def _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, arith, mode, sums_from=None, amax_in=None, amax_out=None,
+                  x_cs=0, bp=None, match_channels=False):
+    """The one tem_conv3d_wgrad_ex call of the weight-gradient wrappers -> sums[N, cin, 2] with sums_from, else None.
+    arith: the arithmetic mode the profiler tag names; mode: the use_mfma word of the launch and of its workspace."""
+    N, D, H, W, C, x_ld = _act5(x)
+    Cg, g_ld = _act5(g)[4:]
+    if match_channels and (C != cin or Cg != cout):
+        raise ValueError("conv_wgrad: channel mismatch")
+    lib = _lib.load()
+    nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], mode)
+    ws = _workspace(nws, x.device)
+    w = gamma = beta = sums = None
+    if sums_from is not None:
+        w, gamma, beta = sums_from
+        w = w.detach()
+        sums = torch.empty((N, cin, 2), dtype=torch.float32, device=x.device)
+    kind = _wgrad_tag(arith, k, cout) if PROFILER is not None else None
+    with _Timed(x, kind, (N, D, H, W), cin, cout, k):
+        _lib.check(lib.tem_conv3d_wgrad_ex(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(w), _p(gamma), _p(beta),
+                                           _p(dw_out), _p(db_out), _p(sums), _p(amax_in), _p(amax_out), _p(ws), nws, N, D, H, W,
+                                           cin, cout, k[0], k[1], k[2], mode, x_cs, bp.ref() if bp is not None else None,
+                                           _stream(x)), "tem_conv3d_wgrad_ex")
+    return sums
+
+
 def conv_wgrad(x, g, k, cin, cout, dw_out, db_out=None, scale=None, shift=None, mfma=False, sums_from=None, bp=None):
     """sums_from = (weight [state_dict layout], gamma, beta): also return sums[N, cin, 2] = (sum gz, sum gz*xn) of the
-    norm in front of this conv (tem_conv3d_wgrad_sums; check conv_wgrad_sums_ok first)."""
+    norm in front of this conv (norm_sums of tem_conv3d_wgrad_ex; check conv_wgrad_sums_ok first)."""
     if sums_from is not None:
         return _conv_wgrad_sums(x, g, k, cin, cout, dw_out, db_out, scale, shift, mfma, sums_from, bp)
     return _conv_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, mfma)
 
 
+def _conv_wgrad(x, g, k, cin, cout, dw_out, db_out=None, scale=None, shift=None, mfma=False):
+    """dw_out: flat [ntaps*cin*cout] in the reference's [Cout,Cin,kd,kh,kw] order; db_out: [cout]."""
+    _req_cuda(x, g, dw_out)
+    _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, mfma, _mode(mfma, x, g), x_cs=_cs(x), match_channels=True)
+    return dw_out
+
+
 def _conv_wgrad_sums(x, g, k, cin, cout, dw_out, db_out, scale, shift, mfma, sums_from, bp=None):
     _req_cuda(x, g, dw_out, db_out)
-    w, gamma, beta = sums_from
-    N, D, H, W, C, x_ld = _act5(x)
-    g_ld = _act5(g)[5]
-    lib = _lib.load()
-    mode = _mode(mfma, x, g)
-    nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], mode)
-    ws = _workspace(nws, x.device)
-    sums = torch.empty((N, cin, 2), dtype=torch.float32, device=x.device)
-    kind = _wgrad_tag(mfma, k, cout) if PROFILER is not None else None
-    ev0 = _prof_begin(x, kind)
-    _lib.check(lib.tem_conv3d_wgrad_ex(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(w.detach()), _p(gamma), _p(beta),
-                                       _p(dw_out), _p(db_out), _p(sums), None, None, _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1],
-                                       k[2], mode, _cs(x), bp.ref() if bp is not None else None, _stream(x)), "tem_conv3d_wgrad_ex")
-    if ev0 is not None:
-        _prof_end(x, ev0, (kind, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2])
-    return sums
+    return _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, mfma, _mode(mfma, x, g), sums_from=sums_from,
+                         x_cs=_cs(x), bp=bp)
 
 
 def conv_wgrad_gmax_ok(x, k, cin, cout, mfma) -> bool:
@@ -417,25 +428,7 @@ def conv_wgrad_gmax(x, g, k, cin, cout, dw_out, db_out, gmax, scale=None, shift=
     """conv_wgrad that also leaves the bit pattern of max |g| in `gmax` (int32[1], cleared by the caller) -- the prescale
     of the fp16 two-term data gradient (conv_fwd_gscaled).  sums_from as in conv_wgrad -> sums[N, cin, 2] or None."""
     _req_cuda(x, g, dw_out, gmax)
-    N, D, H, W, C, x_ld = _act5(x)
-    g_ld = _act5(g)[5]
-    lib = _lib.load()
-    nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], int(mfma))
-    ws = _workspace(nws, x.device)
-    w = gamma = beta = sums = None
-    if sums_from is not None:
-        w, gamma, beta = sums_from
-        w = w.detach()
-        sums = torch.empty((N, cin, 2), dtype=torch.float32, device=x.device)
-    kind = _wgrad_tag(mfma, k, cout) if PROFILER is not None else None
-    ev0 = _prof_begin(x, kind)
-    _lib.check(lib.tem_conv3d_wgrad_ex(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(w), _p(gamma), _p(beta),
-                                       _p(dw_out), _p(db_out), _p(sums), None, _p(gmax), _p(ws), nws, N, D, H, W, cin, cout,
-                                       k[0], k[1], k[2], int(mfma), 0, bp.ref() if bp is not None else None, _stream(x)),
-               "tem_conv3d_wgrad_ex")
-    if ev0 is not None:
-        _prof_end(x, ev0, (kind, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2])
-    return sums
+    return _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, mfma, int(mfma), sums_from=sums_from, amax_out=gmax, bp=bp)
 
 
 def conv1x1_out_bwd_ok(cin, cout) -> bool:
@@ -443,7 +436,7 @@ def conv1x1_out_bwd_ok(cin, cout) -> bool:
 
 
 def conv1x1_out_bwd(x, g, w, gx, dw_out, db_out=None, out_amax=None):
-    """Backward of the output projection in one pass over its input x (tem_conv1x1_out_bwd): dw [cout, cin, 1, 1, 1]-ordered, db,
+    """Backward of the output projection in one pass over its input x (tem_conv1x1_out_bwd_st): dw [cout, cin, 1, 1, 1]-ordered, db,
     and gx = (x > 0) * (g . w).  x, gx: [N, D, H, W, cin(ld)]; g: [N, D, H, W, cout(ld)]; w: the conv's weight (state_dict)."""
     _req_cuda(x, g, w, gx, dw_out)
     N, D, H, W, cin, x_ld = _act5(x)
@@ -453,13 +446,9 @@ def conv1x1_out_bwd(x, g, w, gx, dw_out, db_out=None, out_amax=None):
     nws = lib.tem_conv1x1_out_bwd_ws(cin, cout)
     ws = _workspace(nws, x.device)
     _same_st(x, gx)
-    if _st(x) or _st(g) or out_amax is not None:
-        _lib.check(lib.tem_conv1x1_out_bwd_st(_p(x), x_ld, _p(g), g_ld, _p(w.detach()), _p(gx), gx_ld, _p(dw_out), _p(db_out),
-                                              _p(ws), nws, N * D * H * W, cin, cout, _p(out_amax), _st(x), _st(g), _stream(x)),
-                   "tem_conv1x1_out_bwd_st")
-        return gx
-    _lib.check(lib.tem_conv1x1_out_bwd(_p(x), x_ld, _p(g), g_ld, _p(w.detach()), _p(gx), gx_ld, _p(dw_out), _p(db_out), _p(ws), nws,
-                                       N * D * H * W, cin, cout, _stream(x)), "tem_conv1x1_out_bwd")
+    _lib.check(lib.tem_conv1x1_out_bwd_st(_p(x), x_ld, _p(g), g_ld, _p(w.detach()), _p(gx), gx_ld, _p(dw_out), _p(db_out),
+                                          _p(ws), nws, N * D * H * W, cin, cout, _p(out_amax), _st(x), _st(g), _stream(x)),
+               "tem_conv1x1_out_bwd_st")
     return gx
 
 
@@ -508,7 +497,6 @@ class Byproducts:
         self.c = c
 
     def ref(self):
-        import ctypes
         return ctypes.cast(ctypes.pointer(self.c), ctypes.c_void_p)
 
     amax = property(lambda self: bool(self.c.delivered & _lib.BP_OUT_AMAX))
@@ -517,31 +505,15 @@ class Byproducts:
 
 
 def conv_wgrad_gscaled(x, g, k, cin, cout, dw_out, db_out, amax, scale=None, shift=None, sums_from=None, bp=None):
-    """Weight gradient in the fp16 2x1 arithmetic (tem_conv3d_wgrad_gscaled): x^ two fp16 terms, g one fp16 term prescaled
+    """Weight gradient in the fp16 2x1 arithmetic (g_amax_in of tem_conv3d_wgrad_ex): x^ two fp16 terms, g one fp16 term prescaled
     from amax = int32[1] with the bit pattern of max |g| (absmax or a producer of g).  sums_from as in conv_wgrad."""
     _req_cuda(x, g, dw_out, amax)
-    N, D, H, W, C, x_ld = _act5(x)
-    g_ld = _act5(g)[5]
-    lib = _lib.load()
-    nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], Arith.F16X2)
-    ws = _workspace(nws, x.device)
-    w = gamma = beta = sums = None
-    if sums_from is not None:
-        w, gamma, beta = sums_from
-        w = w.detach()
-        sums = torch.empty((N, cin, 2), dtype=torch.float32, device=x.device)
-    kind = _wgrad_tag(Arith.F16X2, k, cout) if PROFILER is not None else None
-    ev0 = _prof_begin(x, kind)
-    _lib.check(lib.tem_conv3d_wgrad_ex(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(w), _p(gamma), _p(beta),
-                                       _p(dw_out), _p(db_out), _p(sums), _p(amax), None, _p(ws), nws, N, D, H, W, cin, cout,
-                                       k[0], k[1], k[2], Arith.F16X2, 0, bp.ref() if bp is not None else None, _stream(x)), "tem_conv3d_wgrad_ex")
-    if ev0 is not None:
-        _prof_end(x, ev0, (kind, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2])
-    return sums
+    return _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, Arith.F16X2, Arith.F16X2, sums_from=sums_from,
+                         amax_in=amax, bp=bp)
 
 
 def conv_fwd_gscaled(x, w_packed, y, k, cin, cout, amax, ref=None, bp=None):
-    """Data gradient with fp32-class products (tem_conv3d_fwd_gscaled): x an unnormalised gradient, w_packed =
+    """Data gradient with fp32-class products (in_amax of tem_conv3d_fwd_ex): x an unnormalised gradient, w_packed =
     pack_weights(w, transpose=True, mfma=Arith.F16X3), amax = int32[1] holding the bit pattern of max |x| (conv_wgrad_gmax)."""
     _req_cuda(x, w_packed, y, amax)
     N, D, H, W, C, x_ld = _act5(x)
@@ -549,25 +521,14 @@ def conv_fwd_gscaled(x, w_packed, y, k, cin, cout, amax, ref=None, bp=None):
     if C != cin or Cy != cout or (N, D, H, W) != (Ny, Dy, Hy, Wy):
         raise ValueError(f"conv_fwd_gscaled: shape mismatch x{tuple(x.shape)} y{tuple(y.shape)} cin={cin} cout={cout}")
     ref_ld = _act5(ref)[5] if ref is not None else 0
-    lib = _lib.load()
-    nws = lib.tem_conv3d_fwd_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], Arith.FP32)
-    ws = _workspace(nws, x.device) if nws else None
     kind = _fwd_tag(Arith.F16X3, k, cout, 3) if PROFILER is not None else None
-    ev0 = _prof_begin(x, kind)
-    if bp is not None:
-        _lib.check(lib.tem_conv3d_fwd_ex(_p(x), x_ld, None, None, _p(w_packed), None, _p(y), y_ld, _p(ref), ref_ld, _p(ws), nws,
-                                         N, D, H, W, cin, cout, k[0], k[1], k[2], ACT[None], Arith.F16X3, _p(amax), None, None, 0, 0, 0,
-                                         bp.ref(), _stream(x)), "tem_conv3d_fwd_ex")
-    else:
-        _lib.check(lib.tem_conv3d_fwd_gscaled(_p(x), x_ld, _p(w_packed), _p(y), y_ld, _p(ref), ref_ld, _p(amax), _p(ws), nws,
-                                              N, D, H, W, cin, cout, k[0], k[1], k[2], _stream(x)), "tem_conv3d_fwd_gscaled")
-    if ev0 is not None:
-        _prof_end(x, ev0, (kind, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2])
+    _launch_fwd(x, x_ld, w_packed, y, y_ld, ref, ref_ld, (N, D, H, W), cin, cout, k, Arith.F16X3, Arith.FP32, kind, in_amax=amax,
+                bp=bp)
     return y
 
 
 def conv_fwd_refnorm(x, w_packed, y, k, cin, cout, ref, coef, mfma, bp=None):
-    """Data gradient that lands behind a ReLU + norm (tem_conv3d_fwd_refnorm): y = ref > 0 ? a*conv(x) - m1 - (ref - mean)*m2r
+    """Data gradient that lands behind a ReLU + norm (ref_coef of tem_conv3d_fwd_ex): y = ref > 0 ? a*conv(x) - m1 - (ref - mean)*m2r
     : 0, coef [N, cout, 4] from norm_bwd_coef.  Only where conv_fwd_family(...) == 3."""
     _req_cuda(x, w_packed, y, ref, coef)
     N, D, H, W, C, x_ld = _act5(x)
@@ -577,21 +538,9 @@ def conv_fwd_refnorm(x, w_packed, y, k, cin, cout, ref, coef, mfma, bp=None):
         raise ValueError(f"conv_fwd_refnorm: shape mismatch x{tuple(x.shape)} y{tuple(y.shape)} coef{tuple(coef.shape)}")
     ref_ld = _act5(ref)[5]
     _same_st(x, y, ref)
-    lib = _lib.load()
-    nws = lib.tem_conv3d_fwd_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], Arith.FP32)
-    ws = _workspace(nws, x.device) if nws else None
     kind = _fwd_tag(mfma, k, cout, 3) if PROFILER is not None else None
-    ev0 = _prof_begin(x, kind)
-    if bp is not None:
-        _lib.check(lib.tem_conv3d_fwd_ex(_p(x), x_ld, None, None, _p(w_packed), None, _p(y), y_ld, _p(ref), ref_ld, _p(ws), nws,
-                                         N, D, H, W, cin, cout, k[0], k[1], k[2], ACT[None], _mode(mfma, x, y), None, _p(coef),
-                                         None, 0, 0, 0, bp.ref(), _stream(x)), "tem_conv3d_fwd_ex")
-    else:
-        _lib.check(lib.tem_conv3d_fwd_refnorm(_p(x), x_ld, _p(w_packed), _p(y), y_ld, _p(ref), ref_ld, _p(coef), _p(ws), nws,
-                                              N, D, H, W, cin, cout, k[0], k[1], k[2], _mode(mfma, x, y), _stream(x)),
-                   "tem_conv3d_fwd_refnorm")
-    if ev0 is not None:
-        _prof_end(x, ev0, (kind, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2])
+    _launch_fwd(x, x_ld, w_packed, y, y_ld, ref, ref_ld, (N, D, H, W), cin, cout, k, _mode(mfma, x, y), Arith.FP32, kind,
+                ref_coef=coef, bp=bp)
     return y
 
 
@@ -624,53 +573,25 @@ def conv_fwd_family(x, k, cin, cout, mfma, y=None, ref=None) -> int:
                                                     *_fwd_layout(x, cout, y, ref)))
 
 
-def _conv_wgrad(x, g, k, cin, cout, dw_out, db_out=None, scale=None, shift=None, mfma=False):
-    """dw_out: flat [ntaps*cin*cout] in the reference's [Cout,Cin,kd,kh,kw] order; db_out: [cout]."""
-    _req_cuda(x, g, dw_out)
-    N, D, H, W, C, x_ld = _act5(x)
-    _, _, _, _, Cg, g_ld = _act5(g)
-    if C != cin or Cg != cout:
-        raise ValueError("conv_wgrad: channel mismatch")
-    lib = _lib.load()
-    mode = _mode(mfma, x, g)
-    nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], mode)
-    ntaps = k[0] * k[1] * k[2]
-    ws = _workspace(nws, x.device)
-    kind = _wgrad_tag(mfma, k, cout) if PROFILER is not None else None
-    ev0 = _prof_begin(x, kind)
-    if _cs(x):
-        _lib.check(lib.tem_conv3d_wgrad_ex(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, None, None, None, _p(dw_out), _p(db_out),
-                                           None, None, None, _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], mode, _cs(x), None,
-                                           _stream(x)), "tem_conv3d_wgrad_ex")
-    else:
-        _lib.check(lib.tem_conv3d_wgrad(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(dw_out), _p(db_out), _p(ws), nws,
-                                        N, D, H, W, cin, cout, k[0], k[1], k[2], mode, 1, _stream(x)),
-                   "tem_conv3d_wgrad")
-    if ev0 is not None:
-        _prof_end(x, ev0, (kind, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2])
-    return dw_out
-
-
 # ------------------------------------------------------------------ norm ----
+def _stats_out(rows, groups, C, dev):
+    """the (mean[rows,G], rstd[rows,G], scale[rows,C], shift[rows,C]) a statistics call fills"""
+    shapes = ((rows, groups), (rows, groups), (rows, C), (rows, C))
+    return tuple(torch.empty(sh, dtype=torch.float32, device=dev) for sh in shapes)
+
+
 def norm_stats(x, groups: int, gamma=None, beta=None, eps: float = 1e-5):
     """-> (mean[N,G], rstd[N,G], scale[N,C], shift[N,C])"""
     _req_cuda(x)
     N, D, H, W, C, ld = _act5(x)
     dev = x.device
-    mean = torch.empty((N, groups), dtype=torch.float32, device=dev)
-    rstd = torch.empty((N, groups), dtype=torch.float32, device=dev)
-    scale = torch.empty((N, C), dtype=torch.float32, device=dev)
-    shift = torch.empty((N, C), dtype=torch.float32, device=dev)
+    mean, rstd, scale, shift = _stats_out(N, groups, C, dev)
     lib = _lib.load()
     V = D * H * W
     nws = lib.tem_norm_ws(N, V, C)
     ws = _workspace(nws, dev)
-    if _st(x):
-        _lib.check(lib.tem_norm_stats_st(_p(x), ld, N, V, C, groups, _p(gamma), _p(beta), eps, _p(mean), _p(rstd), _p(scale),
-                                         _p(shift), _p(ws), nws, _st(x), _stream(x)), "tem_norm_stats_st")
-        return mean, rstd, scale, shift
-    _lib.check(lib.tem_norm_stats(_p(x), ld, N, V, C, groups, _p(gamma), _p(beta), eps, _p(mean), _p(rstd), _p(scale),
-                                  _p(shift), _p(ws), nws, _stream(x)), "tem_norm_stats")
+    _lib.check(lib.tem_norm_stats_st(_p(x), ld, N, V, C, groups, _p(gamma), _p(beta), eps, _p(mean), _p(rstd), _p(scale),
+                                     _p(shift), _p(ws), nws, _st(x), _stream(x)), "tem_norm_stats_st")
     return mean, rstd, scale, shift
 
 
@@ -685,15 +606,24 @@ def norm_stats_from_partials(part, rows: int, voxels: int, C: int, groups: int, 
     elif rows != N:
         raise ValueError("norm_stats_from_partials: rows must be N or 1")
     dev = part.device
-    mean = torch.empty((rows, groups), dtype=torch.float32, device=dev)
-    rstd = torch.empty((rows, groups), dtype=torch.float32, device=dev)
-    scale = torch.empty((rows, C), dtype=torch.float32, device=dev)
-    shift = torch.empty((rows, C), dtype=torch.float32, device=dev)
+    mean, rstd, scale, shift = _stats_out(rows, groups, C, dev)
     lib = _lib.load()
     _lib.check(lib.tem_norm_finalize_partials(_p(part), nblk, rows, voxels, C, groups, _p(gamma), _p(beta), eps,
                                               _p(mean), _p(rstd), _p(scale), _p(shift), _stream(part)),
                "tem_norm_finalize_partials")
     return mean, rstd, scale, shift
+
+
+def _launch_norm_bwd(gy, gy_ld, x, x_ld, N, V, C, groups, gamma, mean, rstd, relu_mask, gx, gx_ld, dgamma, dbeta, sums, coef, out_amax):
+    """The one tem_norm_bwd_st call.  sums: None = reduce gy and x here, [N, C, 2] from a weight gradient (one row) or partial rows
+    [N, nblk, C, 2] from a data gradient (Byproducts.norm_sums); coef: reduction only -> coef [N, C, 4], gx is not written."""
+    lib = _lib.load()
+    nws = lib.tem_norm_ws(N, V, C)
+    ws = _workspace(nws, x.device)
+    nrow = 0 if sums is None else (sums.shape[1] if sums.dim() == 4 else 1)
+    _lib.check(lib.tem_norm_bwd_st(_p(gy), gy_ld, _p(x), x_ld, N, V, C, groups, _p(gamma), _p(mean), _p(rstd), int(relu_mask),
+                                   _p(gx), gx_ld, _p(dgamma), _p(dbeta), _p(sums), nrow, _p(coef), _p(out_amax), _p(ws), nws, _st(x),
+                                   _stream(x)), "tem_norm_bwd_st")
 
 
 def norm_bwd_coef(gy, x, groups, gamma, mean, rstd, dgamma=None, dbeta=None, sums=None):
@@ -712,26 +642,9 @@ def norm_bwd_coef(gy, x, groups, gamma, mean, rstd, dgamma=None, dbeta=None, sum
     gy_ld = _act5(gy)[5]
     if isinstance(x, Planar):   # with the sums given the tensors are not read: any valid leading dimension
         x_ld = gy_ld = C
-    lib = _lib.load()
-    V = D * H * W
-    nws = lib.tem_norm_ws(N, V, C)
-    ws = _workspace(nws, x.device)
+    _same_st(gy, x)
     coef = torch.empty((N, C, 4), dtype=torch.float32, device=x.device)
-    if _st(x) or _st(gy):
-        _same_st(gy, x)
-        nrow = 0 if sums is None else (sums.shape[1] if sums.dim() == 4 else 1)
-        _lib.check(lib.tem_norm_bwd_st(_p(gy), gy_ld, _p(x), x_ld, N, V, C, groups, _p(gamma), _p(mean), _p(rstd), 0, None, C,
-                                       _p(dgamma), _p(dbeta), _p(sums), nrow, _p(coef), None, _p(ws), nws, _st(x), _stream(x)),
-                   "tem_norm_bwd_st")
-        return coef
-    if sums is not None and sums.dim() == 4:   # partial rows [N, nblk, C, 2] from a data gradient (Byproducts.norm_sums of the data gradient)
-        _lib.check(lib.tem_norm_bwd_from_partials(_p(gy), gy_ld, _p(x), x_ld, N, V, C, groups, _p(gamma), _p(mean), _p(rstd), 0,
-                                                  None, C, _p(dgamma), _p(dbeta), _p(sums), sums.shape[1], _p(coef), _p(ws), nws,
-                                                  _stream(x)), "tem_norm_bwd_from_partials")
-        return coef
-    _lib.check(lib.tem_norm_bwd_coef(_p(gy), gy_ld, _p(x), x_ld, N, V, C, groups, _p(gamma), _p(mean), _p(rstd),
-                                     _p(dgamma), _p(dbeta), _p(sums), _p(coef), _p(ws), nws, _stream(x)),
-               "tem_norm_bwd_coef")
+    _launch_norm_bwd(gy, gy_ld, x, x_ld, N, D * H * W, C, groups, gamma, mean, rstd, 0, None, C, dgamma, dbeta, sums, coef, None)
     return coef
 
 
@@ -742,65 +655,42 @@ def norm_bwd(gy, x, groups, gamma, mean, rstd, relu_mask: bool, gx, dgamma=None,
     N, D, H, W, C, x_ld = _act5(x)
     gy_ld = _act5(gy)[5]
     gx_ld = _act5(gx)[5]
-    lib = _lib.load()
-    V = D * H * W
-    nws = lib.tem_norm_ws(N, V, C)
-    ws = _workspace(nws, x.device)
-    if _st(x) or _st(gy) or _st(gx) or out_amax is not None:
-        _same_st(gy, x, gx)
-        nrow = 0 if sums is None else (sums.shape[1] if sums.dim() == 4 else 1)
-        _lib.check(lib.tem_norm_bwd_st(_p(gy), gy_ld, _p(x), x_ld, N, V, C, groups, _p(gamma), _p(mean), _p(rstd), int(relu_mask),
-                                       _p(gx), gx_ld, _p(dgamma), _p(dbeta), _p(sums), nrow, None, _p(out_amax), _p(ws), nws, _st(x),
-                                       _stream(x)), "tem_norm_bwd_st")
-        return gx
-    if sums is not None and sums.dim() == 4:   # partial rows [N, nblk, C, 2] from a data gradient (Byproducts.norm_sums of the data gradient)
-        _lib.check(lib.tem_norm_bwd_from_partials(_p(gy), gy_ld, _p(x), x_ld, N, V, C, groups, _p(gamma), _p(mean), _p(rstd),
-                                                  int(relu_mask), _p(gx), gx_ld, _p(dgamma), _p(dbeta), _p(sums), sums.shape[1],
-                                                  None, _p(ws), nws, _stream(x)), "tem_norm_bwd_from_partials")
-        return gx
-    if sums is not None:
-        _lib.check(lib.tem_norm_bwd_from_sums(_p(gy), gy_ld, _p(x), x_ld, N, V, C, groups, _p(gamma), _p(mean), _p(rstd),
-                                              int(relu_mask), _p(gx), gx_ld, _p(dgamma), _p(dbeta), _p(sums), _p(ws), nws,
-                                              _stream(x)), "tem_norm_bwd_from_sums")
-        return gx
-    _lib.check(lib.tem_norm_bwd(_p(gy), gy_ld, _p(x), x_ld, N, V, C, groups, _p(gamma), _p(mean), _p(rstd),
-                                int(relu_mask), _p(gx), gx_ld, _p(dgamma), _p(dbeta), _p(ws), nws, _stream(x)),
-               "tem_norm_bwd")
+    _same_st(gy, x, gx)
+    _launch_norm_bwd(gy, gy_ld, x, x_ld, N, D * H * W, C, groups, gamma, mean, rstd, relu_mask, gx, gx_ld, dgamma, dbeta, sums, None,
+                     out_amax)
     return gx
 
 
 # --------------------------------------------------------- pool / upsample ----
+def _rows_vec4(x, x_ld, y, y_ld) -> bool:
+    """may the launch from x into y get a statistics buffer: leading dimensions % 4 == 0 and 16-byte aligned pointers"""
+    return x_ld % 4 == 0 and y_ld % 4 == 0 and x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0
+
+
 def maxpool_fwd(x, y, f, want_stats=False):
     """want_stats: also return (partials [N, nblk, C, 2], nblk) -- the first stage of the statistics of y (what
-    conv_fwd(want_stats=True) returns for a conv output; tem_maxpool3d_fwd_stats) -- or None when this channel count cannot."""
+    conv_fwd(want_stats=True) returns for a conv output; stat_part of tem_maxpool3d_fwd_st) -- or None when this channel count
+    cannot."""
     _req_cuda(x, y)
     N, D, H, W, C, x_ld = _act5(x)
     y_ld = _act5(y)[5]
     lib = _lib.load()
     nblk = int(lib.tem_maxpool3d_fwd_stat_blocks(D, H, C, f[0], f[1])) if want_stats else 0
-    if _st(x) or _st(y):
-        _same_st(x, y)
-        part = None
-        if nblk > 0 and x_ld % 4 == 0 and y_ld % 4 == 0 and x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0:
-            part = torch.empty((N, nblk, C, 2), dtype=torch.float32, device=x.device)
-        _lib.check(lib.tem_maxpool3d_fwd_st(_p(x), x_ld, _p(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part),
-                                            nblk if part is not None else 0, _st(x), _stream(x)), "tem_maxpool3d_fwd_st")
-        if want_stats:
-            return None if part is None else (part, nblk)
-        return y
-    if nblk > 0 and x_ld % 4 == 0 and y_ld % 4 == 0 and x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0:
+    _same_st(x, y)
+    part = None
+    if nblk > 0 and _rows_vec4(x, x_ld, y, y_ld):
         part = torch.empty((N, nblk, C, 2), dtype=torch.float32, device=x.device)
-        _lib.check(lib.tem_maxpool3d_fwd_stats(_p(x), x_ld, _p(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part), nblk,
-                                               _stream(x)), "tem_maxpool3d_fwd_stats")
-        return part, nblk
-    _lib.check(lib.tem_maxpool3d_fwd(_p(x), x_ld, _p(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], _stream(x)),
-               "tem_maxpool3d_fwd")
-    return None if want_stats else y
+    _lib.check(lib.tem_maxpool3d_fwd_st(_p(x), x_ld, _p(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part),
+                                        nblk if part is not None else 0, _st(x), _stream(x)), "tem_maxpool3d_fwd_st")
+    if want_stats:
+        return None if part is None else (part, nblk)
+    return y
 
 
 def maxpool_bwd(gy, x, gx, f, gskip=None, relu_mask=False, gskip_coef=None, gy_coef=None, out_amax=None):
     """gskip_coef: [N, C, 4] view (row stride = multiple of 4 floats) of norm_bwd_coef() -- gskip is then the raw data
-    gradient behind that norm and the norm backward is applied on the fly (tem_maxpool3d_bwd_norm)."""
+    gradient behind that norm and the norm backward is applied on the fly (gcoef of tem_maxpool3d_bwd_st).
+    gy_coef: dense [N, C, 4] coefficients of the norm whose input is the pooled tensor (gy raw as well)."""
     _req_cuda(gy, x, gx)
     N, D, H, W, C, x_ld = _act5(x)
     gy_ld = _act5(gy)[5]
@@ -809,56 +699,29 @@ def maxpool_bwd(gy, x, gx, f, gskip=None, relu_mask=False, gskip_coef=None, gy_c
     lib = _lib.load()
     if gy_coef is not None and not gy_coef.is_contiguous():
         raise ValueError("maxpool_bwd: gy_coef must be contiguous")
-    if _st(x) or _st(gy) or _st(gx) or out_amax is not None:
-        _same_st(gy, x, gx, gskip)
-        _lib.check(lib.tem_maxpool3d_bwd_st(_p(gy), gy_ld, _p(x), x_ld, _p(gskip), gs_ld, int(relu_mask), _p(gx), gx_ld,
-                                            N, D, H, W, C, f[0], f[1], f[2], _p(gskip_coef),
-                                            gskip_coef.stride(0) if gskip_coef is not None else 0, _p(gy_coef), _p(out_amax), _st(x),
-                                            _stream(x)), "tem_maxpool3d_bwd_st")
-        return gx
-    if gskip_coef is not None or gy_coef is not None:
-        # gy_coef: dense [N, C, 4] coefficients of the norm whose input is the pooled tensor (gy raw as well)
-        if gy_coef is not None and not gy_coef.is_contiguous():
-            raise ValueError("maxpool_bwd: gy_coef must be contiguous")
-        _lib.check(lib.tem_maxpool3d_bwd_norm(_p(gy), gy_ld, _p(x), x_ld, _p(gskip), gs_ld, int(relu_mask), _p(gx), gx_ld,
-                                              N, D, H, W, C, f[0], f[1], f[2], _p(gskip_coef),
-                                              gskip_coef.stride(0) if gskip_coef is not None else 0, _p(gy_coef),
-                                              _stream(x)), "tem_maxpool3d_bwd_norm")
-        return gx
-    _lib.check(lib.tem_maxpool3d_bwd(_p(gy), gy_ld, _p(x), x_ld, _p(gskip), gs_ld, int(relu_mask), _p(gx), gx_ld,
-                                     N, D, H, W, C, f[0], f[1], f[2], _stream(x)), "tem_maxpool3d_bwd")
+    _same_st(gy, x, gx, gskip)
+    _lib.check(lib.tem_maxpool3d_bwd_st(_p(gy), gy_ld, _p(x), x_ld, _p(gskip), gs_ld, int(relu_mask), _p(gx), gx_ld,
+                                        N, D, H, W, C, f[0], f[1], f[2], _p(gskip_coef),
+                                        gskip_coef.stride(0) if gskip_coef is not None else 0, _p(gy_coef), _p(out_amax), _st(x),
+                                        _stream(x)), "tem_maxpool3d_bwd_st")
     return gx
 
 
 def upsample_fwd(x, y, f, stats: bool = False):
     """y = interpolate(x, scale_factor=f, trilinear).  stats=True: also return the first stage of y's statistics,
-    part [N, D*H, C, 2] (tem_upsample_fwd_stats), or None when the factor-2 kernel does not take the shape -- then
+    part [N, D*H, C, 2] (part of tem_upsample_fwd_st), or None when the factor-2 kernel does not take the shape -- then
     `upsample_stats` derives them from x."""
     _req_cuda(x, y)
     N, D, H, W, C, x_ld = _act5(x)
     y_ld = _act5(y)[5]
     lib = _lib.load()
-    if _st(x) or _st(y):
-        _same_st(x, y)
-        part = None
-        if stats and lib.tem_upsample_fwd_stats_ok(C, f[0], f[1], f[2]) and x_ld % 4 == 0 and y_ld % 4 == 0 and \
-                x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0:
-            part = torch.empty((N, D * H, C, 2), dtype=torch.float32, device=x.device)
-        _lib.check(lib.tem_upsample_fwd_st(_p(x), x_ld, _p(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part), _st(x),
-                                           _stream(x)), "tem_upsample_fwd_st")
-        return part if stats else y
-    if stats:
-        if not (lib.tem_upsample_fwd_stats_ok(C, f[0], f[1], f[2]) and x_ld % 4 == 0 and y_ld % 4 == 0 and
-                x.data_ptr() % 16 == 0 and y.data_ptr() % 16 == 0):
-            upsample_fwd(x, y, f)
-            return None
+    _same_st(x, y)
+    part = None
+    if stats and lib.tem_upsample_fwd_stats_ok(C, f[0], f[1], f[2]) and _rows_vec4(x, x_ld, y, y_ld):
         part = torch.empty((N, D * H, C, 2), dtype=torch.float32, device=x.device)
-        _lib.check(lib.tem_upsample_fwd_stats(_p(x), x_ld, _p(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part),
-                                              _stream(x)), "tem_upsample_fwd_stats")
-        return part
-    _lib.check(lib.tem_upsample_fwd(_p(x), x_ld, _p(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], _stream(x)),
-               "tem_upsample_fwd")
-    return y
+    _lib.check(lib.tem_upsample_fwd_st(_p(x), x_ld, _p(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part), _st(x),
+                                       _stream(x)), "tem_upsample_fwd_st")
+    return part if stats else y
 
 
 def upsample_stats_ok(u) -> bool:
@@ -868,17 +731,12 @@ def upsample_stats_ok(u) -> bool:
 
 
 def upsample_stats(u, f):
-    """First stage of the statistics of upsample(u, f), from u alone -> part [N, D*H, C, 2] (tem_upsample_stats)."""
+    """First stage of the statistics of upsample(u, f), from u alone -> part [N, D*H, C, 2] (tem_upsample_stats_st)."""
     _req_cuda(u)
     N, D, H, W, C, u_ld = _act5(u)
     part = torch.empty((N, D * H, C, 2), dtype=torch.float32, device=u.device)
-    lib = _lib.load()
-    if _st(u):
-        _lib.check(lib.tem_upsample_stats_st(_p(u), u_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part), _st(u), _stream(u)),
-                   "tem_upsample_stats_st")
-        return part
-    _lib.check(lib.tem_upsample_stats(_p(u), u_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part), _stream(u)),
-               "tem_upsample_stats")
+    _lib.check(_lib.load().tem_upsample_stats_st(_p(u), u_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part), _st(u), _stream(u)),
+               "tem_upsample_stats_st")
     return part
 
 
@@ -895,10 +753,7 @@ def norm_stats_from_partials2(part_a, part_b, rows: int, voxels: int, groups: in
     elif rows != N:
         raise ValueError("norm_stats_from_partials2: rows must be N or 1")
     dev = part_a.device
-    mean = torch.empty((rows, groups), dtype=torch.float32, device=dev)
-    rstd = torch.empty((rows, groups), dtype=torch.float32, device=dev)
-    scale = torch.empty((rows, C), dtype=torch.float32, device=dev)
-    shift = torch.empty((rows, C), dtype=torch.float32, device=dev)
+    mean, rstd, scale, shift = _stats_out(rows, groups, C, dev)
     lib = _lib.load()
     _lib.check(lib.tem_norm_finalize_partials2(_p(part_a), nba, ca, _p(part_b), nbb, rows, voxels, C, groups, _p(gamma),
                                                _p(beta), eps, _p(mean), _p(rstd), _p(scale), _p(shift), _stream(part_a)),
@@ -912,21 +767,11 @@ def upsample_bwd(gy, gx, f, norm=None):
     _req_cuda(gy, gx)
     N, D, H, W, C, gx_ld = _act5(gx)
     gy_ld = _act5(gy)[5]
-    lib = _lib.load()
-    if _st(gy) or _st(gx):
-        u, coef = norm if norm is not None else (None, None)
-        _same_st(gy, gx, u)
-        _lib.check(lib.tem_upsample_bwd_st(_p(gy), gy_ld, _p(gx), gx_ld, N, D, H, W, C, f[0], f[1], f[2], _p(u),
-                                           _act5(u)[5] if u is not None else 0, _p(coef), coef.stride(0) if coef is not None else 0,
-                                           _st(gy), _stream(gx)), "tem_upsample_bwd_st")
-        return gx
-    if norm is not None:
-        u, coef = norm
-        _lib.check(lib.tem_upsample_bwd_norm(_p(gy), gy_ld, _p(gx), gx_ld, N, D, H, W, C, f[0], f[1], f[2], _p(u),
-                                             _act5(u)[5], _p(coef), coef.stride(0), _stream(gx)), "tem_upsample_bwd_norm")
-        return gx
-    _lib.check(lib.tem_upsample_bwd(_p(gy), gy_ld, _p(gx), gx_ld, N, D, H, W, C, f[0], f[1], f[2], _stream(gx)),
-               "tem_upsample_bwd")
+    u, coef = norm if norm is not None else (None, None)
+    _same_st(gy, gx, u)
+    _lib.check(_lib.load().tem_upsample_bwd_st(_p(gy), gy_ld, _p(gx), gx_ld, N, D, H, W, C, f[0], f[1], f[2], _p(u),
+                                               _act5(u)[5] if u is not None else 0, _p(coef), coef.stride(0) if coef is not None else 0,
+                                               _st(gy), _stream(gx)), "tem_upsample_bwd_st")
     return gx
 
 

@@ -201,7 +201,7 @@ class GradScaler:
     `_backprop_mixed` :789-794: `scale(loss).backward(); step(optimizer); update()`).
 
     Why it is needed here although activations and gradients are stored in fp32: in mixed-precision mode the MFMA
-    convolutions round their OPERANDS to fp16 (tem_conv3d_fwd / _wgrad use_mfma = 5), so an incoming gradient below
+    convolutions round their OPERANDS to fp16 (tem_conv3d_fwd_ex / _wgrad_ex use_mfma = 5), so an incoming gradient below
     6e-8 would vanish and one above 65504 becomes inf.  The loss is multiplied by `scale` before backward; `step`
     divides the gradients by it again with one HIP launch over the flat gradient arena (`tem_amp_unscale`, which also
     raises the found-inf flag), reads that flag (the one host sync per step, as in torch) and skips the optimizer
