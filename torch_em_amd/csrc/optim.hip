@@ -8,10 +8,30 @@
 #include "tem_common.h"
 #include <math.h>
 
-__global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const float* __restrict__ g,
-                                               float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
-                                               float b1, float b2, float eps, float wd, float step_size,
-                                               float inv_sqrt_bc2, float gscale) {
+// One element of the update, shared by the float4 body and the scalar tail of all three kernels below.  Every fused
+// multiply-add is spelled out: left to the compiler's contraction, the same source line was rounded in three different
+// ways (body, tail of k_adamw, tail of k_adamw_dev), so a launch with n % 4 != 0 was not bit-equal between the variants
+// (tests/test_gpu_optim.py holds them bit-equal now).
+struct AdamwScalars {
+    float b2, eps, neg_step_size, inv_sqrt_bc2, gscale;
+    float decay, gain1, gain2;  // 1 - lr*wd, 1 - b1, 1 - b2
+};
+
+__device__ __forceinline__ AdamwScalars adamw_scalars(float lr, float b1, float b2, float eps, float wd, float step_size,
+                                                      float inv_sqrt_bc2, float gscale) {
+    return {b2, eps, -step_size, inv_sqrt_bc2, gscale, fmaf(-lr, wd, 1.f), 1.f - b1, 1.f - b2};
+}
+
+__device__ __forceinline__ void adamw_elem(float& p, float g, float& m, float& v, const AdamwScalars& k) {
+    const float gr = g * k.gscale;
+    m = fmaf(k.gain1, fmaf(k.gscale, g, -m), m);                   // lerp_: m + (1-b1) * (gr - m)
+    v = fmaf(k.b2, v, gr * (k.gain2 * gr));                        // mul_ + addcmul_: b2*v + (1-b2)*gr*gr
+    const float denom = fmaf(sqrtf(v), k.inv_sqrt_bc2, k.eps);
+    p = fmaf(k.decay, p, k.neg_step_size * (m / denom));            // p*(1 - lr*wd) - step_size * m / denom
+}
+
+__device__ __forceinline__ void adamw_range(float* __restrict__ p, const float* __restrict__ g, float* __restrict__ m,
+                                            float* __restrict__ v, int64_t n, const AdamwScalars& k) {
     const int64_t n4 = n >> 2;
     const int64_t stride = (int64_t)gridDim.x * 256;
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
@@ -22,29 +42,26 @@ __global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const floa
         float pp[4] = {p4.x, p4.y, p4.z, p4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
         float mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
 #pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gr = gg[j] * gscale;
-            pp[j] *= (1.f - lr * wd);
-            mm[j] = mm[j] + (1.f - b1) * (gr - mm[j]);          // lerp_
-            vv[j] = b2 * vv[j] + (1.f - b2) * gr * gr;            // mul_ + addcmul_
-            float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
-            pp[j] -= step_size * (mm[j] / denom);
-        }
+        for (int j = 0; j < 4; ++j) adamw_elem(pp[j], gg[j], mm[j], vv[j], k);
         reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
         reinterpret_cast<float4*>(m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
         reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
     }
     // tail
     for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        float gr = g[i] * gscale;
-        float pp = p[i] * (1.f - lr * wd);
-        float mm = m[i] + (1.f - b1) * (gr - m[i]);
-        float vv = b2 * v[i] + (1.f - b2) * gr * gr;
-        float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
-        p[i] = pp - step_size * (mm / denom);
+        float pp = p[i], mm = m[i], vv = v[i];
+        adamw_elem(pp, g[i], mm, vv, k);
+        p[i] = pp;
         m[i] = mm;
         v[i] = vv;
     }
+}
+
+__global__ __launch_bounds__(256) void k_adamw(float* __restrict__ p, const float* __restrict__ g,
+                                               float* __restrict__ m, float* __restrict__ v, int64_t n, float lr,
+                                               float b1, float b2, float eps, float wd, float step_size,
+                                               float inv_sqrt_bc2, float gscale) {
+    adamw_range(p, g, m, v, n, adamw_scalars(lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gscale));
 }
 
 extern "C" int tem_adamw_step(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n, float lr,
@@ -75,38 +92,7 @@ __global__ __launch_bounds__(256) void k_adamw_dev(float* __restrict__ p, const 
     const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], step_size = hyper[5],
                 inv_sqrt_bc2 = hyper[6], gscale = hyper[7];
     if (hyper[8] != 0.f) return;
-    const int64_t n4 = n >> 2;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        float4 p4 = reinterpret_cast<float4*>(p)[i];
-        float4 g4 = reinterpret_cast<const float4*>(g)[i];
-        float4 m4 = reinterpret_cast<float4*>(m)[i];
-        float4 v4 = reinterpret_cast<float4*>(v)[i];
-        float pp[4] = {p4.x, p4.y, p4.z, p4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
-        float mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gr = gg[j] * gscale;
-            pp[j] *= (1.f - lr * wd);
-            mm[j] = mm[j] + (1.f - b1) * (gr - mm[j]);
-            vv[j] = b2 * vv[j] + (1.f - b2) * gr * gr;
-            float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
-            pp[j] -= step_size * (mm[j] / denom);
-        }
-        reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
-        reinterpret_cast<float4*>(m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-    }
-    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        float gr = g[i] * gscale;
-        float pp = p[i] * (1.f - lr * wd);
-        float mm = m[i] + (1.f - b1) * (gr - m[i]);
-        float vv = b2 * v[i] + (1.f - b2) * gr * gr;
-        float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
-        p[i] = pp - step_size * (mm / denom);
-        m[i] = mm;
-        v[i] = vv;
-    }
+    adamw_range(p, g, m, v, n, adamw_scalars(lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gscale));
 }
 
 // ... and under dynamic loss scaling, where a step may be SKIPPED on the device (overflow) without the host knowing
@@ -130,38 +116,7 @@ __global__ __launch_bounds__(256) void k_adamw_tab(float* __restrict__ p, const 
     const float* hyper = table + 4 + 12 * row;
     const float lr = hyper[0], b1 = hyper[1], b2 = hyper[2], eps = hyper[3], wd = hyper[4], step_size = hyper[5],
                 inv_sqrt_bc2 = hyper[6], gscale = hyper[7];
-    const int64_t n4 = n >> 2;
-    const int64_t stride = (int64_t)gridDim.x * 256;
-    for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < n4; i += stride) {
-        float4 p4 = reinterpret_cast<float4*>(p)[i];
-        float4 g4 = reinterpret_cast<const float4*>(g)[i];
-        float4 m4 = reinterpret_cast<float4*>(m)[i];
-        float4 v4 = reinterpret_cast<float4*>(v)[i];
-        float pp[4] = {p4.x, p4.y, p4.z, p4.w}, gg[4] = {g4.x, g4.y, g4.z, g4.w};
-        float mm[4] = {m4.x, m4.y, m4.z, m4.w}, vv[4] = {v4.x, v4.y, v4.z, v4.w};
-#pragma unroll
-        for (int j = 0; j < 4; ++j) {
-            float gr = gg[j] * gscale;
-            pp[j] *= (1.f - lr * wd);
-            mm[j] = mm[j] + (1.f - b1) * (gr - mm[j]);
-            vv[j] = b2 * vv[j] + (1.f - b2) * gr * gr;
-            float denom = sqrtf(vv[j]) * inv_sqrt_bc2 + eps;
-            pp[j] -= step_size * (mm[j] / denom);
-        }
-        reinterpret_cast<float4*>(p)[i] = make_float4(pp[0], pp[1], pp[2], pp[3]);
-        reinterpret_cast<float4*>(m)[i] = make_float4(mm[0], mm[1], mm[2], mm[3]);
-        reinterpret_cast<float4*>(v)[i] = make_float4(vv[0], vv[1], vv[2], vv[3]);
-    }
-    for (int64_t i = (n4 << 2) + (int64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += stride) {
-        float gr = g[i] * gscale;
-        float pp = p[i] * (1.f - lr * wd);
-        float mm = m[i] + (1.f - b1) * (gr - m[i]);
-        float vv = b2 * v[i] + (1.f - b2) * gr * gr;
-        float denom = sqrtf(vv) * inv_sqrt_bc2 + eps;
-        p[i] = pp - step_size * (mm / denom);
-        m[i] = mm;
-        v[i] = vv;
-    }
+    adamw_range(p, g, m, v, n, adamw_scalars(lr, b1, b2, eps, wd, step_size, inv_sqrt_bc2, gscale));
 }
 
 extern "C" int tem_adamw_step_tab(float* param, const float* grad, float* exp_avg, float* exp_avg_sq, int64_t n,
