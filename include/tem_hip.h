@@ -857,6 +857,37 @@ int tem_act_bwd(const float* gy, const float* y, float* gx, int64_t n, int act, 
 /* per-sample standardize (transform/raw.py:40-65): (x-mean)/(std+eps) over each of N rows of length L */
 int tem_standardize(const float* x, float* y, int N, int64_t L, float eps, void* ws, int64_t ws_bytes, tem_stream_t stream);
 
+/* ---- raw normalisation and contrast (transform/raw.py: normalize :88-116, normalize_percentile :119-140,
+ * RandomPercentileNormalization :143-297, RandomContrast :305-334; csrc/rawnorm.hip) -------------------------------
+ * x, y: N contiguous float32 rows of length L (any L >= 1, any 4-byte aligned row offset; N <= 65535).  Nothing here reads
+ * device memory back, allocates or synchronises: host-side values (ranks, weights, scalars) travel as kernel arguments, and
+ * every workspace is the caller's (`ws`, `ws_bytes`; too small: TEM_EWS and the size in tem_last_error()).  NaN input is
+ * undefined.  All results are bitwise reproducible (min / max, integer counts; no float atomics). */
+/* bytes of workspace tem_row_minmax (K = 0) or tem_row_select (K ranks per row) needs; the select takes 2 KiB + 16 B per
+ * row and rank (one 256-bin table of 64-bit counts, cleared before each of the four passes) */
+int64_t tem_rawnorm_ws(int N, int64_t L, int K);
+/* mn[n], mx[n] (device) = minimum and maximum of row n */
+int tem_row_minmax(const float* x, int N, int64_t L, float* mn, float* mx, void* ws, int64_t ws_bytes, tem_stream_t stream);
+/* exact order statistics: out[n*K + k] (device) = the element of 0-based rank ranks[n*K + k] (HOST array, 0 <= rank < L) of
+ * the ascending-sorted row n; 1 <= K <= 8.  MSB-first radix select over the order-preserving key of the float bits. */
+int tem_row_select(const float* x, int N, int64_t L, const int64_t* ranks, int K, float* out, void* ws, int64_t ws_bytes,
+                   tem_stream_t stream);
+/* dst[0..n) (device) = values[0..n) (HOST), carried in kernel arguments */
+int tem_rawnorm_fill(float* dst, const float* values, int64_t n, tem_stream_t stream);
+/* min-max coefficients: sub = mn, div = fl32(fl32(mx - mn) + eps) */
+int tem_rawnorm_minmax_coef(const float* mn, const float* mx, int N, float eps, float* sub, float* div, tem_stream_t stream);
+/* percentile coefficients from os[n*4 + 0..3] (device: order statistics lower, lower's upper neighbour, upper, upper's upper
+ * neighbour) and the HOST weights t[n*2 + 0..1]: v = numpy's _lerp in float32 (a + (b-a)*t; b - (b-a)*(1-t) where t >= 0.5),
+ * sub = v_lower, div = fl32(fl32(v_upper - v_lower) + eps); v (device [N][2], may be NULL) receives v_lower, v_upper */
+int tem_rawnorm_percentile_coef(const float* os, const float* t, int N, float eps, float* sub, float* div, float* v,
+                                tem_stream_t stream);
+/* y = fl32(fl32(x - sub[n]) / div[n]) (IEEE division), then min(max(y, lo), hi) if clip; sub, div: device [N] */
+int tem_rawnorm_apply(const float* x, float* y, int N, int64_t L, const float* sub, const float* div, int clip, float lo,
+                      float hi, tem_stream_t stream);
+/* y = fl32(mean + fl32(alpha[n] * fl32(x - mean))) (no fma contraction), then the clip; alpha: device [N] */
+int tem_rawnorm_contrast(const float* x, float* y, int N, int64_t L, const float* alpha, float mean, int clip, float lo,
+                         float hi, tem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

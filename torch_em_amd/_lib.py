@@ -186,6 +186,15 @@ SIGNATURES = {
                                   + [c_int] * 12 + [c_vp]),
     "tem_conv1x1_out_bwd_st": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int,
                                        c_vp, c_int, c_int, c_vp]),
+    # raw normalisation and contrast (csrc/rawnorm.hip); `ranks`, `values`, `t` are HOST arrays
+    "tem_rawnorm_ws": (c_i64, [c_int, c_i64, c_int]),
+    "tem_row_minmax": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp]),
+    "tem_row_select": (c_int, [c_vp, c_int, c_i64, ctypes.POINTER(c_i64), c_int, c_vp, c_vp, c_i64, c_vp]),
+    "tem_rawnorm_fill": (c_int, [c_vp, ctypes.POINTER(c_float), c_i64, c_vp]),
+    "tem_rawnorm_minmax_coef": (c_int, [c_vp, c_vp, c_int, c_float, c_vp, c_vp, c_vp]),
+    "tem_rawnorm_percentile_coef": (c_int, [c_vp, ctypes.POINTER(c_float), c_int, c_float, c_vp, c_vp, c_vp, c_vp]),
+    "tem_rawnorm_apply": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_float, c_float, c_vp]),
+    "tem_rawnorm_contrast": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_float, c_int, c_float, c_float, c_vp]),
 }
 
 _lib = None

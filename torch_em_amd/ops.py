@@ -1245,6 +1245,159 @@ def standardize(x: torch.Tensor, eps: float = 1e-7) -> torch.Tensor:
     return y
 
 
+# ---- min-max / percentile normalisation and contrast of raw data (csrc/rawnorm.hip) ----
+def _rows(x: torch.Tensor):
+    """-> (x as contiguous float32, N, L): rows are the entries of the first axis"""
+    _req_cuda(x)
+    if x.dim() < 1 or x.numel() == 0:
+        raise ValueError(f"expected a non-empty tensor of rows, got shape {tuple(x.shape)}")
+    x = x.float().contiguous()
+    N = x.shape[0]
+    return x, N, x.numel() // N
+
+
+def _host_floats(values, n: int, what: str):
+    """a python number or a sequence of n of them -> ctypes float[n] (HOST values, carried in kernel arguments)"""
+    vals = [float(v) for v in values] if isinstance(values, (list, tuple)) or hasattr(values, "__len__") else [float(values)] * n
+    if len(vals) != n:
+        raise ValueError(f"{what}: expected one value or {n} (one per row), got {len(vals)}")
+    return (ctypes.c_float * n)(*vals)
+
+
+def _fill(values, n: int, device, what: str) -> torch.Tensor:
+    """host values -> a device float32 [n] without a copy or a synchronisation (tem_rawnorm_fill)"""
+    out = torch.empty((n,), dtype=torch.float32, device=device)
+    _lib.check(_lib.load().tem_rawnorm_fill(_p(out), _host_floats(values, n, what), n, _stream(out)), "tem_rawnorm_fill")
+    return out
+
+
+def _clip(clip):
+    """None | (lo, hi) with None for an open side -> (flag, lo, hi)"""
+    if clip is None:
+        return 0, 0.0, 0.0
+    lo, hi = clip
+    return 1, float("-inf") if lo is None else float(lo), float("inf") if hi is None else float(hi)
+
+
+def row_minmax(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """(min, max) per entry of the first axis, float32 [N] on the device (tem_row_minmax; exact, bitwise reproducible)"""
+    x, N, L = _rows(x)
+    mn = torch.empty((N,), dtype=torch.float32, device=x.device)
+    mx = torch.empty_like(mn)
+    lib = _lib.load()
+    nws = lib.tem_rawnorm_ws(N, L, 0)
+    ws = _workspace(nws, x.device)
+    _lib.check(lib.tem_row_minmax(_p(x), N, L, _p(mn), _p(mx), _p(ws), nws, _stream(x)), "tem_row_minmax")
+    return mn, mx
+
+
+_SELECT_KMAX = 8  # ranks per row and call of tem_row_select
+
+
+def row_order_statistics(x: torch.Tensor, ranks) -> torch.Tensor:
+    """out[n, k] = sorted(row n)[ranks[n][k]] exactly (0-based ranks, HOST integers: one list for every row or one list per
+    row), float32 [N, K] on the device; radix select, no sort, no read-back (tem_row_select).  NaN input is undefined."""
+    x, N, L = _rows(x)
+    ranks = [list(r) for r in ranks] if len(ranks) and hasattr(ranks[0], "__len__") else [list(ranks)] * N
+    K = len(ranks[0]) if ranks else 0
+    if len(ranks) != N or K == 0 or any(len(r) != K for r in ranks):
+        raise ValueError(f"row_order_statistics: expected {N} equally long, non-empty rank lists")
+    out = torch.empty((N, K), dtype=torch.float32, device=x.device)
+    lib = _lib.load()
+    for k0 in range(0, K, _SELECT_KMAX):
+        kk = min(K - k0, _SELECT_KMAX)
+        part = out if kk == K else torch.empty((N, kk), dtype=torch.float32, device=x.device)
+        flat = (ctypes.c_int64 * (N * kk))(*[int(v) for r in ranks for v in r[k0:k0 + kk]])
+        nws = lib.tem_rawnorm_ws(N, L, kk)
+        ws = _workspace(nws, x.device)
+        _lib.check(lib.tem_row_select(_p(x), N, L, flat, kk, _p(part), _p(ws), nws, _stream(x)), "tem_row_select")
+        if part is not out:
+            out[:, k0:k0 + kk] = part
+    return out
+
+
+def _apply(x, N, L, sub, div, clip) -> torch.Tensor:
+    y = torch.empty_like(x)
+    flag, lo, hi = _clip(clip)
+    _lib.check(_lib.load().tem_rawnorm_apply(_p(x), _p(y), N, L, _p(sub), _p(div), flag, lo, hi, _stream(x)), "tem_rawnorm_apply")
+    return y
+
+
+def normalize(x: torch.Tensor, eps: float = 1e-7, clip=None, minval=None, maxval=None) -> torch.Tensor:
+    """(x - min) / (fl32(max - min) + eps) per entry of the first axis, every step one float32 operation in the reference's
+    order (`normalize`, transform/raw.py:88-116).  `minval` / `maxval` (HOST numbers) replace the row's own: with `minval`
+    alone the divisor is fl32(fl32(max - minval) + eps), with `maxval` it is fl32(maxval + eps), the sum formed in double as
+    the reference forms it; with both the apply kernel runs alone."""
+    x, N, L = _rows(x)
+    mn = mx = None
+    if minval is None or maxval is None:
+        mn, mx = row_minmax(x)
+    if minval is not None:
+        mn = _fill(minval, N, x.device, "minval")
+    if maxval is not None:
+        return _apply(x, N, L, mn, _fill(float(maxval) + float(eps), N, x.device, "maxval"), clip)
+    sub, div = torch.empty_like(mn), torch.empty_like(mn)
+    _lib.check(_lib.load().tem_rawnorm_minmax_coef(_p(mn), _p(mx), N, eps, _p(sub), _p(div), _stream(x)), "tem_rawnorm_minmax_coef")
+    return _apply(x, N, L, sub, div, clip)
+
+
+def percentile_plan(L: int, q: float):
+    """(lower rank, upper rank, weight) of numpy's linear-interpolation percentile q of L float32 values, computed as the
+    installed numpy computes them for float32 data: q / 100, the virtual index (L - 1) * q and the weight are FLOAT32
+    (`np.percentile` divides by `a.dtype.type(100)`), and an index at or past the end takes the last element twice."""
+    import numpy as np
+    quant = np.asanyarray(np.true_divide(float(q), np.float32(100)))
+    if not (0.0 <= quant <= 1.0):
+        raise ValueError("Percentiles must be in the range [0, 100]")
+    virt = np.asanyarray((L - 1) * quant)
+    prev = np.floor(virt)
+    if virt >= L - 1:
+        lo = hi = L - 1
+        t = virt - np.float32(-1)   # numpy indexes the last element as -1 before it forms the weight
+    else:
+        lo, hi, t = int(prev), int(prev) + 1, virt - prev
+    return lo, hi, float(np.float32(t))
+
+
+def normalize_percentile(x: torch.Tensor, lower=1.0, upper=99.0, eps: float = 1e-7, clip=None, return_percentiles: bool = False):
+    """(x - v_lower) / (fl32(v_upper - v_lower) + eps) per entry of the first axis, v = np.percentile of the row (`normalize_percentile`,
+    transform/raw.py:119-140): four exact order statistics per row from the radix select, numpy's float32 interpolation
+    and the apply kernel; nothing leaves the device.  `lower` / `upper`: numbers, or one per row.  return_percentiles: also
+    the device tensor [N, 2] of (v_lower, v_upper)."""
+    x, N, L = _rows(x)
+    lows = [float(v) for v in lower] if hasattr(lower, "__len__") else [float(lower)] * N
+    ups = [float(v) for v in upper] if hasattr(upper, "__len__") else [float(upper)] * N
+    if len(lows) != N or len(ups) != N:
+        raise ValueError(f"normalize_percentile: expected one percentile or {N} (one per row)")
+    ranks, weights = [], []
+    for ql, qu in zip(lows, ups):
+        a = percentile_plan(L, ql)
+        b = percentile_plan(L, qu)
+        ranks.append([a[0], a[1], b[0], b[1]])
+        weights += [a[2], b[2]]
+    os_ = row_order_statistics(x, ranks)
+    sub = torch.empty((N,), dtype=torch.float32, device=x.device)
+    div = torch.empty_like(sub)
+    v = torch.empty((N, 2), dtype=torch.float32, device=x.device) if return_percentiles else None
+    t = (ctypes.c_float * (2 * N))(*weights)
+    _lib.check(_lib.load().tem_rawnorm_percentile_coef(_p(os_), t, N, eps, _p(sub), _p(div), _p(v), _stream(x)),
+               "tem_rawnorm_percentile_coef")
+    y = _apply(x, N, L, sub, div, clip)
+    return (y, v) if return_percentiles else y
+
+
+def contrast(x: torch.Tensor, alpha, mean: float, clip=None) -> torch.Tensor:
+    """fl32(mean + fl32(alpha[n] * fl32(x - mean))) per entry of the first axis, then the clip (`RandomContrast`,
+    transform/raw.py:305-334); alpha: a number or one per row (HOST values)."""
+    x, N, L = _rows(x)
+    a = _fill(alpha, N, x.device, "alpha")
+    y = torch.empty_like(x)
+    flag, lo, hi = _clip(clip)
+    _lib.check(_lib.load().tem_rawnorm_contrast(_p(x), _p(y), N, L, _p(a), float(mean), flag, lo, hi, _stream(x)),
+               "tem_rawnorm_contrast")
+    return y
+
+
 # ---- distance-based instance segmentation (csrc/distance.hip) ----
 POD_DIST, POD_BOUNDARY, POD_DIRECTED, POD_FOREGROUND, POD_INSTANCES = 1, 2, 4, 8, 16
 

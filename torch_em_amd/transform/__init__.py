@@ -1,5 +1,6 @@
 """Transforms of the MI355X path that belong to the hot path (reference torch_em/transform/)."""
 from .label import AffinityTransform, BoundaryTransform, PerObjectDistanceTransform, labels_to_binary
-from .raw import standardize
+from .raw import (RandomContrast, RandomPercentileNormalization, RawTransform, get_raw_transform, normalize, normalize_percentile,
+                  standardize)
 from .augmentation import (KorniaAugmentationPipeline, RandomAffine, RandomAffine3D, RandomElasticDeformation, RandomRotation,
                            RandomElasticDeformationStacked, RandomRotation3D, get_augmentations)

@@ -1,4 +1,18 @@
-"""Raw-data transforms on the hot path (reference torch_em/transform/raw.py)."""
+"""Raw-data transforms on the hot path (reference torch_em/transform/raw.py).
+
+Built: `standardize`, `normalize`, `normalize_percentile`, `RandomPercentileNormalization`, `RandomContrast`, `RawTransform`,
+`get_raw_transform`.  Each dispatches on its input: a CUDA tensor runs through the HIP kernels of csrc/rawnorm.hip (nothing
+is read back, so they run inside the input pipeline's side stream and as `predict_with_halo(preprocess=...)`); numpy input
+takes the reference's numpy expression, which is also the CPU oracle of the device path -- the two agree bit for bit on
+float32 data.  A CPU torch tensor counts as numpy input and comes back as a numpy array (the reference returns a tensor
+there): on this path tensors live on the device.
+
+Out of scope: the noise transforms (`AdditiveGaussianNoise`, `AdditivePoissonNoise`, `PoissonNoise`: their random streams
+have no device counterpart that could be pinned to the reference's), `GaussianBlur` (defined by torchvision, which this
+package does not depend on) and `get_default_mean_teacher_augmentations` (needs both).
+"""
+from typing import Callable, Dict, Optional, Tuple
+
 import numpy as np
 import torch
 
@@ -23,3 +37,251 @@ def standardize(raw, mean=None, std=None, axis=None, eps: float = 1e-7, per_samp
     mean = raw.mean(axis=axis, keepdims=True) if mean is None else mean
     std = raw.std(axis=axis, keepdims=True) if std is None else std
     return (raw - mean) / (std + eps)
+
+
+def _on_device(raw) -> bool:
+    return torch.is_tensor(raw) and raw.is_cuda
+
+
+def _as_rows(raw: torch.Tensor, axis, per_sample: bool, what: str) -> torch.Tensor:
+    """The device tensor as [rows, ...]: `axis` None -> one row (the whole array); a trailing run of axes -> one row per
+    entry of the leading axes (per sample, per channel); per_sample -> all axes but the first."""
+    nd = raw.dim()
+    if per_sample:
+        if axis is not None:
+            raise ValueError(f"{what}: give axis or per_sample=True, not both")
+        lead = min(1, nd)
+    elif axis is None:
+        lead = 0
+    else:
+        axes = sorted(int(a) % nd for a in np.atleast_1d(axis))
+        lead = axes[0]
+        if axes != list(range(lead, nd)):
+            raise NotImplementedError(f"{what} on the device: axis must be None or a trailing run of axes (got {axis} for "
+                                      f"{nd} dimensions); reduce over other axes on the host or permute the tensor first")
+    n = 1
+    for s in raw.shape[:lead]:
+        n *= int(s)
+    return raw.reshape(n, -1)
+
+
+def _numpy_axis(raw, axis, per_sample: bool):
+    return tuple(range(1, raw.ndim)) if per_sample and axis is None else axis
+
+
+def normalize(raw, minval=None, maxval=None, axis=None, eps: float = 1e-7, per_sample: bool = False):
+    """(raw - min) / (max(raw - min) + eps): into [0, 1] (reference `:88-116`).
+    CUDA tensor: row min / max, coefficients and the apply run as HIP kernels; `axis` is None (whole array) or a trailing
+    run of axes (one min / max per entry of the leading axes: per sample, per channel), `per_sample=True` (not in the
+    reference) is all axes but the first; anything else raises NotImplementedError.  `minval` / `maxval` may be python
+    numbers (both: the apply kernel alone; one: the other comes from the row min / max as in the reference).  Integer and 16-bit tensors are cast to float32 first.  The result equals the numpy
+    branch on the same float32 data bit for bit.  NaN input is undefined on the device.
+    numpy input: the reference's expression."""
+    if _on_device(raw):
+        rows = _as_rows(raw, axis, per_sample, "normalize")
+        for name, v in (("minval", minval), ("maxval", maxval)):
+            if v is not None and (isinstance(v, bool) or not isinstance(v, (int, float))):
+                raise NotImplementedError(f"normalize on the device: {name} must be a python number or None")
+        return ops.normalize(rows, eps, minval=minval, maxval=maxval).reshape(raw.shape)
+    raw = np.asarray(raw).astype("float32")   # always a copy: the steps below work in place, in float32
+    axis = _numpy_axis(raw, axis, per_sample)
+    np.subtract(raw, raw.min(axis=axis, keepdims=True) if minval is None else minval, out=raw)
+    np.divide(raw, (raw.max(axis=axis, keepdims=True) if maxval is None else maxval) + eps, out=raw)
+    return raw
+
+
+def normalize_percentile(raw, lower=1.0, upper=99.0, axis=None, eps: float = 1e-7, per_sample: bool = False):
+    """(raw - p_lower) / (p_upper - p_lower + eps) with `np.percentile`'s linear interpolation (reference `:119-140`).
+    CUDA tensor: exact order statistics from a radix select (no sort, no read-back), numpy's float32 interpolation and the
+    apply kernel; `axis` / `per_sample` as in `normalize`; `lower` / `upper` may be sequences with one entry per row.
+    Integer and 16-bit tensors are cast to float32 first, so the result is the reference's for `raw.astype("float32")` --
+    on integer input the reference itself interpolates the percentiles in float64 and differs from that in the last bits.
+    NaN input is undefined on the device.  numpy input: the reference's expression."""
+    if _on_device(raw):
+        rows = _as_rows(raw, axis, per_sample, "normalize_percentile")
+        return ops.normalize_percentile(rows, lower, upper, eps).reshape(raw.shape)
+    raw = np.asarray(raw)
+    axis = _numpy_axis(raw, axis, per_sample)
+    if np.ndim(lower) or np.ndim(upper):   # one pair per entry of the first axis
+        lower, upper = np.broadcast_to(lower, raw.shape[:1]), np.broadcast_to(upper, raw.shape[:1])
+        return np.stack([normalize_percentile(r, float(lo), float(up), eps=eps) for r, lo, up in zip(raw, lower, upper)])
+    v_lower = np.percentile(raw, lower, axis=axis, keepdims=True)
+    return normalize(raw, v_lower, np.percentile(raw, upper, axis=axis, keepdims=True) - v_lower, eps=eps)
+
+
+def _check_bounds(values, upper: bool):
+    name = "upper_percentile_bounds" if upper else "lower_percentile_bounds"
+    if not isinstance(values, (tuple, list)) or len(values) != 2:
+        raise ValueError(f"{name} must contain exactly two values.")
+    lo, hi = float(values[0]), float(values[1])
+    ok = np.isfinite(lo) and np.isfinite(hi) and ((50.0 < lo <= hi <= 100.0) if upper else (0.0 <= lo <= hi < 50.0))
+    if not ok:
+        raise ValueError(f"{name} must be a finite interval within {'(50, 100]' if upper else '[0, 50)'}.")
+    return lo, hi
+
+
+def _uniform_kwargs(kwargs, bounds):
+    if kwargs is not None:
+        raise ValueError("Uniform sampling does not accept distribution_kwargs.")
+    return None
+
+
+def _normal_kwargs(kwargs, bounds):
+    """{"mean", "std"} exactly, as floats; the mean inside the lower bounds, the width finite and not negative"""
+    if not isinstance(kwargs, dict) or sorted(kwargs) != ["mean", "std"]:
+        raise ValueError("Normal sampling requires exactly the distribution_kwargs 'mean' and 'std'.")
+    out = {key: float(kwargs[key]) for key in ("mean", "std")}
+    if not (np.isfinite(out["mean"]) and bounds[0] <= out["mean"] <= bounds[1]):
+        raise ValueError("The normal distribution mean must be finite and within lower_percentile_bounds.")
+    if not (np.isfinite(out["std"]) and out["std"] >= 0.0):
+        raise ValueError("The normal distribution std must be finite and non-negative.")
+    return out
+
+
+_SAMPLERS = {"uniform": _uniform_kwargs, "normal": _normal_kwargs}
+
+
+def _check_seed(seed):
+    if seed is None:
+        return None
+    if isinstance(seed, bool) or not isinstance(seed, (int, np.integer)):   # True is an int, and is not a seed
+        raise TypeError("seed must be an integer or None.")
+    if seed < 0:
+        raise ValueError("seed must be non-negative.")
+    return int(seed)
+
+
+class RandomPercentileNormalization:
+    """Percentile normalisation with randomly drawn percentiles, output clipped to [0, 1] (reference `:143-297`; same
+    arguments, validation, seeding and draws).  `lower` is drawn from `lower_percentile_bounds`, `upper` from
+    `upper_percentile_bounds` (default: the lower bounds mirrored around 50), uniformly or -- `distribution="normal"`,
+    `distribution_kwargs={"mean": m, "std": s}` -- from a normal distribution (the upper one mirrored) clipped to the bounds,
+    rounded to `rounding_decimals`.  `seed`: a private generator per DataLoader worker, else numpy's global state.
+    `per_sample=True` (not in the reference): one pair per entry of the first axis, drawn in order from the same generator,
+    percentiles over all other axes -- a batch then equals the reference called sample by sample."""
+
+    def __init__(self, lower_percentile_bounds: Tuple[float, float] = (0.0, 5.0),
+                 upper_percentile_bounds: Optional[Tuple[float, float]] = None, distribution: str = "uniform",
+                 distribution_kwargs: Optional[Dict[str, float]] = None, rounding_decimals: Optional[int] = 1, axis=None,
+                 seed: Optional[int] = None, eps: float = 1e-7, per_sample: bool = False):
+        lower_percentile_bounds = _check_bounds(lower_percentile_bounds, upper=False)
+        if upper_percentile_bounds is None:
+            upper_percentile_bounds = (100.0 - lower_percentile_bounds[1], 100.0 - lower_percentile_bounds[0])
+        upper_percentile_bounds = _check_bounds(upper_percentile_bounds, upper=True)
+        if distribution not in _SAMPLERS:
+            raise ValueError("distribution must be 'uniform' or 'normal'.")
+        distribution_kwargs = _SAMPLERS[distribution](distribution_kwargs, lower_percentile_bounds)
+        decimals_ok = rounding_decimals is None or (type(rounding_decimals) is int and rounding_decimals >= 0)
+        if not decimals_ok:
+            raise ValueError("rounding_decimals must be a non-negative integer or None.")
+        if not np.isfinite(eps) or eps <= 0.0:
+            raise ValueError("eps must be finite and greater than zero.")
+        seed = _check_seed(seed)
+        if per_sample and axis is not None:
+            raise ValueError("give axis or per_sample=True, not both")
+        self.lower_percentile_bounds = lower_percentile_bounds
+        self.upper_percentile_bounds = upper_percentile_bounds
+        self.distribution = distribution
+        self.distribution_kwargs = distribution_kwargs
+        self.rounding_decimals = rounding_decimals
+        self.axis = axis
+        self.seed = seed
+        self.eps = float(eps)
+        self.per_sample = bool(per_sample)
+        self._random_generator = None
+        self._random_generator_worker_id = None
+
+    def _generator(self):
+        if self.seed is None:
+            return np.random
+        info = torch.utils.data.get_worker_info()
+        worker = None if info is None else info.id
+        if self._random_generator is None or self._random_generator_worker_id != worker:
+            self._random_generator = np.random.default_rng(np.random.SeedSequence([self.seed, worker or 0]))
+            self._random_generator_worker_id = worker
+        return self._random_generator
+
+    def _rounded(self, value) -> float:
+        return float(value) if self.rounding_decimals is None else round(float(value), self.rounding_decimals)
+
+    def sample_percentiles(self) -> Tuple[float, float]:
+        """Draw one valid (lower, upper) percentile pair."""
+        rng = self._generator()
+        if self.distribution == "uniform":
+            lower = rng.uniform(*self.lower_percentile_bounds)
+            upper = rng.uniform(*self.upper_percentile_bounds)
+        else:
+            def draw(mean, std):   # a zero width draws nothing from the generator
+                return rng.normal(mean, std) if std != 0.0 else mean
+            lower = draw(**self.distribution_kwargs)
+            upper = 100.0 - draw(**self.distribution_kwargs)   # the lower distribution mirrored around 50
+        # the tails of the normal distribution may leave the bounds
+        return (float(np.clip(self._rounded(lower), *self.lower_percentile_bounds)),
+                float(np.clip(self._rounded(upper), *self.upper_percentile_bounds)))
+
+    def __call__(self, raw):
+        if self.per_sample:
+            pairs = [self.sample_percentiles() for _ in range(len(raw))]
+            lower, upper = [p[0] for p in pairs], [p[1] for p in pairs]
+        else:
+            lower, upper = self.sample_percentiles()
+        if _on_device(raw):
+            rows = _as_rows(raw, self.axis, self.per_sample, "RandomPercentileNormalization")
+            return ops.normalize_percentile(rows, lower, upper, self.eps, clip=(0.0, 1.0)).reshape(raw.shape)
+        out = normalize_percentile(raw, lower, upper, axis=self.axis, eps=self.eps, per_sample=self.per_sample)
+        return np.clip(out, 0.0, 1.0)
+
+
+class RandomContrast:
+    """mean + alpha * (img - mean) with alpha drawn uniformly from `alpha` by `np.random.uniform`, then clipped with
+    `clip_kwargs` (reference `:305-334`).  A CUDA tensor runs through the contrast kernel in float32 (multiply and add are
+    rounded separately, as numpy does); `per_sample=True` (not in the reference) draws one alpha per entry of the first
+    axis, in order.  On the device `clip_kwargs` may hold `a_min` and `a_max` only (None: that side stays open); any other
+    np.clip keyword raises."""
+
+    def __init__(self, alpha: Tuple[float, float] = (0.5, 2), mean: float = 0.5,
+                 clip_kwargs: Optional[Dict] = {"a_min": 0, "a_max": 1}, per_sample: bool = False):
+        self.alpha = alpha
+        self.mean = mean
+        self.clip_kwargs = clip_kwargs
+        self.per_sample = bool(per_sample)
+
+    def __call__(self, img):
+        n = len(img) if self.per_sample else 1
+        alpha = [np.random.uniform(self.alpha[0], self.alpha[1]) for _ in range(n)]
+        if _on_device(img):
+            clip = None
+            if self.clip_kwargs:
+                unknown = set(self.clip_kwargs) - {"a_min", "a_max"}
+                if unknown:
+                    raise ValueError(f"RandomContrast on the device: clip_kwargs takes a_min and a_max only, got {sorted(unknown)}")
+                clip = (self.clip_kwargs.get("a_min"), self.clip_kwargs.get("a_max"))
+            rows = img.reshape(n, -1)
+            return ops.contrast(rows, alpha, self.mean, clip).reshape(img.shape)
+        img = np.asarray(img)
+        if self.per_sample:
+            res = np.stack([self.mean + a * (r - self.mean) for a, r in zip(alpha, img)])
+        else:
+            res = self.mean + alpha[0] * (img - self.mean)
+        return np.clip(res, **self.clip_kwargs) if self.clip_kwargs else res
+
+
+class RawTransform:
+    """The raw transform of training: `augmentation1`, then `normalizer`, then `augmentation2` (reference `:461-492`)."""
+
+    def __init__(self, normalizer: Callable, augmentation1: Optional[Callable] = None, augmentation2: Optional[Callable] = None):
+        self.normalizer = normalizer
+        self.augmentation1 = augmentation1
+        self.augmentation2 = augmentation2
+
+    def __call__(self, raw):
+        for step in (self.augmentation1, self.normalizer, self.augmentation2):
+            if step is not None:
+                raw = step(raw)
+        return raw
+
+
+def get_raw_transform(normalizer: Callable = standardize, augmentation1: Optional[Callable] = None,
+                      augmentation2: Optional[Callable] = None) -> Callable:
+    """`RawTransform(normalizer, augmentation1, augmentation2)` (reference `:495-510`)."""
+    return RawTransform(normalizer, augmentation1=augmentation1, augmentation2=augmentation2)
