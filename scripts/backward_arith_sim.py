@@ -146,7 +146,7 @@ VARIANTS = [
     ("dgrad h1xh2-2 (g one term, w two)", ("h1", "h2", 2), ("b2", "b2", 3)),
     ("dgrad h1xh1-1", ("h1", "h1", 1), ("b2", "b2", 3)),
     ("dgrad b2xb1-2", ("b2", "b1", 2), ("b2", "b2", 3)),
-    ("dgrad h2xh2-3 (TEM_DGRAD16)", ("h2", "h2", 3), ("b2", "b2", 3)),
+    ("dgrad h2xh2-3", ("h2", "h2", 3), ("b2", "b2", 3)),
     ("dgrad h2xh1-2 + wgrad h1xh1-1", ("h2", "h1", 2), ("h1", "h1", 1)),
     ("dgrad b2xb2-3 + wgrad h1xh1-1 >= 2^17 voxels else b2xb2-3", ("b2", "b2", 3), ("h1", "h1", 1)),
     ("wgrad h1(s*x)xh1-1 + exact shift term", ("b2", "b2", 3), ("h1s", "h1", 1)),

@@ -46,7 +46,7 @@ def main():
     args = sys.argv[1:]
     cfg3 = "--cfg3" in args
     seeds = [int(s) for s in ([a for a in args if a != "--cfg3"] or ["0", "1", "2", "3", "4", "5"])]
-    print(f"# TEM_PRECISION={os.environ.get('TEM_PRECISION', 'split16')}  TEM_DGRAD16={os.environ.get('TEM_DGRAD16', 'default')}")
+    print(f"# TEM_PRECISION={os.environ.get('TEM_PRECISION', 'split16')}")
     print("# seed  global_L2(hip)  global_L2(fp32 ref)  worst tensor (hip)  its L2 hip / ref   entries > 1e-2 of max (hip / ref)")
     for seed in seeds:
         model, sf, x, y, okw, loss_fn = case(seed, cfg3)

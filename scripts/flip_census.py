@@ -55,11 +55,11 @@ def hip_run(model, x, y, mode):
     model.zero_grad(set_to_none=True)
     with engine.precision_scope(mode):
         _, st = engine._forward_impl(model, x.cuda(), keep=True)
-        blocks = [lv["bs"] for lv in st["levels"]] + [st["base"]] + [d["bs"] for d in st["dec"]]
+        blocks = [lv.bs for lv in st.levels] + [st.base] + [d.bs for d in st.dec]
         relus = []
         for bs in blocks:
-            relus += [bs["a1"].permute(0, 4, 1, 2, 3).float().cpu(), bs["out"].permute(0, 4, 1, 2, 3).float().cpu()]
-        pools = [lv["skip"].permute(0, 4, 1, 2, 3).float().cpu() for lv in st["levels"]]
+            relus += [bs.a1.permute(0, 4, 1, 2, 3).float().cpu(), bs.out.permute(0, 4, 1, 2, 3).float().cpu()]
+        pools = [lv.skip.permute(0, 4, 1, 2, 3).float().cpu() for lv in st.levels]
         del st
         pred = model(x.cuda())
         loss = DiceLoss()(pred, y.cuda())

@@ -475,7 +475,7 @@ def test_model_step_is_bit_identical_with_planar_concat(mode, norm, monkeypatch)
     monkeypatch.setattr(engine, "_PLANAR_CONCAT", True)
     with engine.precision_scope(mode):
         _, st = engine._forward_impl(model, x, keep=True)
-    assert isinstance(st["levels"][0]["cat"], ops.Planar) and not isinstance(st["levels"][1]["cat"], ops.Planar)
+    assert isinstance(st.levels[0].cat, ops.Planar) and not isinstance(st.levels[1].cat, ops.Planar)
     del st
     pa, la, ga = _step(model, x, y, mode)
     monkeypatch.setattr(engine, "_PLANAR_CONCAT", False)
@@ -500,7 +500,7 @@ def test_graphed_step_with_16bit_storage_and_planar_concat_equals_eager():
     m0.load_state_dict(sd0)
     with engine.precision_scope("amp"):
         _, st = engine._forward_impl(m0, xs[0], keep=True)
-    assert isinstance(st["levels"][0]["cat"], ops.Planar)
+    assert isinstance(st.levels[0].cat, ops.Planar)
     del st
     opt0, sc0, l0 = FusedAdamW(m0.parameters(), lr=1e-3), GradScaler(init_scale=2.0 ** 10), []
     for x, y in zip(xs, ys):

@@ -236,7 +236,7 @@ def test_unet3d_benchmark_widths_depth4_match_fp64_oracle(dispatch_mix):
     relative L2 error: fp32 reference path 1.4e-3 ... 3.9e-3 (median 1.8e-3), this library (default arithmetic) 1.3e-3 ...
     3.0e-3 with one 1.5e-2 outlier (median 1.9e-3), its exact-fp32 build 2.3e-3 ... 6.2e-3.  Round 2 looked at ONE seed
     (4.5e-3 vs 1.3e-3), widened the bound to 6x / 5x and blamed the 16-bit backward products; fp32-class data gradients
-    (TEM_DGRAD16=1) leave that number unchanged."""
+    (an experiment of round 3, since removed: profiles/r03_depth4_error_*.txt) left that number unchanged."""
     from torch_em_amd.loss import DiceLoss
     from torch_em_amd.model import UNet3d
 
@@ -256,9 +256,9 @@ def _library_decisions(model, x):
     from torch_em_amd.model import engine
     _, st = engine._forward_impl(model, x.to(DEV), keep=True)
     nchw = lambda t: t.permute(0, 4, 1, 2, 3).float().cpu()  # noqa: E731
-    blocks = [lv["bs"] for lv in st["levels"]] + [st["base"]] + [d["bs"] for d in st["dec"]]
-    masks = [nchw(bs[k]) > 0 for bs in blocks for k in ("a1", "out")]
-    pools = [F.max_pool3d_with_indices(nchw(lv["skip"]), tuple(lv["f"]))[1] for lv in st["levels"]]
+    blocks = [lv.bs for lv in st.levels] + [st.base] + [d.bs for d in st.dec]
+    masks = [nchw(t) > 0 for bs in blocks for t in (bs.a1, bs.out)]
+    pools = [F.max_pool3d_with_indices(nchw(lv.skip), tuple(lv.f))[1] for lv in st.levels]
     return {"relu": masks, "pool": pools}
 
 
@@ -402,6 +402,32 @@ def test_default_arithmetic_is_bit_identical_to_round4():
             assert digest_default.run_case(kw, shape) == want[name], name
     finally:
         _lib.set_option("wgrad_sums_min_mb", old)
+
+
+def test_engine_steps_and_op_calls_are_identical_to_the_fixture():
+    """The host side of the step (model/engine.py, model/pack.py) on the routes the default fixture above does not take: the
+    mixed and exact precision modes, BatchNorm, no norm + Sigmoid, anisotropic factors and kernels, 2-D, side outputs, crop
+    + floor, a no-grad forward before training.  tests/golden/engine_step_digest.json holds, per case of
+    scripts/digest_default.py::ENGINE_CASES and for TWO steps (every parameter is scaled in place in between: the second
+    step runs on the batched re-pack), the SHA-256 of prediction and flat gradient, the loss, and the ORDERED list of
+    `ops` functions the engine called; it was written by the tree before the engine's state became named records, with
+    the same library.  A change of the engine that is meant to move neither a bit nor a launch must reproduce it exactly."""
+    import json
+    import sys
+    sys.path.insert(0, os.path.join(os.path.dirname(os.path.abspath(__file__)), "..", "scripts"))
+    import digest_default
+    with open(os.path.join(GOLDEN, "engine_step_digest.json")) as f:
+        want = json.load(f)
+    assert set(want) == set(digest_default.ENGINE_CASES)
+    reached = set()
+    for name, case in digest_default.ENGINE_CASES.items():
+        got = digest_default.run_engine_case(*case)
+        assert set(got) == set(want[name]), name
+        for step, res in got.items():
+            reached.update(res["calls"])
+            for key, val in res.items():
+                assert val == want[name][step][key], (name, step, key)
+    assert not set(digest_default.ENGINE_MUST_REACH) - reached
 
 
 def _median_over_seeds(make, seeds):

@@ -121,9 +121,9 @@ class GraphedTrainStep:
                 b.copy_(old)
         torch.cuda.set_rng_state(rng_state, x.device)
         ops.bump_versions(self.params)
-        from .model import engine
+        from .model import engine, pack
         with self._scope():
-            engine._repack_stale(prepare_only=True)   # the weight-packing job table: its upload cannot be captured
+            pack.repack_stale(engine.PRECISION, prepare_only=True)   # the weight-packing job table: its upload cannot be captured
         self.graph = torch.cuda.CUDAGraph()
         sync = getattr(getattr(model, "module", model), "_tem_grad_sync", None)
         measure = None
@@ -140,8 +140,7 @@ class GraphedTrainStep:
         # the graph's memory pool) must outlive the graph even if the engine later replaces its own reference -- a new
         # pack-job table after an eager validation pass, new packed-weight buffers under another precision mode, a
         # re-homed gradient arena: hold them here.
-        self._keepalive = [dict(engine._PACK_TABLES), [dict(c._tem_pack) for c in list(engine._PACKED_CONVS)
-                                                        if getattr(c, "_tem_pack", None) is not None],
+        self._keepalive = [pack.keepalive(),
                            getattr(self.params[0], "_tem_grad_flat", None), ar.flat, optimizer._m, optimizer._v,
                            optimizer._hyper, optimizer._table]
         self.replays = 0

@@ -22,14 +22,15 @@ sequenced MI355X-first:
 """
 import os
 import threading
-import weakref
-from typing import List, Optional
+from dataclasses import dataclass
+from typing import Any, List, NamedTuple, Optional
 
 import torch
 import torch.nn as nn
 
 from .. import ops
-from ..arith import Arith, PackKind, pack_is_tiled
+from ..arith import Arith
+from . import pack
 
 _FORCE_GENERIC = os.environ.get("TEM_DISABLE_MFMA", "0") == "1"
 
@@ -64,7 +65,6 @@ _FORCE_GENERIC = os.environ.get("TEM_DISABLE_MFMA", "0") == "1"
 # The backward convolutions are LINEAR in the incoming gradient with masks fixed by the forward
 # pass, so their 1e-5 error is not amplified.
 PRECISION = os.environ.get("TEM_PRECISION", "split16")
-_F16X3_MODE = Arith(int(os.environ.get("TEM_F16X3_LAYOUT", int(Arith.F16X3))))
 # Activation STORAGE of the two mixed modes (round 5): every tensor between two kernels of the step -- activations, saved
 # tensors, data gradients -- is fp16 ("amp") / bf16 ("amp_bf16") in HBM, as under torch.autocast in the reference trainer
 # (trainer/default_trainer.py:134-142, 781-794); the network input, the prediction, statistics, coefficients, parameters and
@@ -108,11 +108,6 @@ class precision_scope:
         return False
 
 
-def _k3(k):
-    k = tuple(int(v) for v in k)
-    return (1,) * (3 - len(k)) + k
-
-
 def _f3(f, dim):
     if isinstance(f, int):
         f = (f,) * dim
@@ -125,7 +120,7 @@ class ConvSpec:
 
     def __init__(self, conv: nn.Module, norm: Optional[nn.Module]):
         self.conv, self.norm = conv, norm
-        self.k = _k3(conv.kernel_size)
+        self.k = pack.k3(conv.kernel_size)
         self.cin, self.cout = conv.in_channels, conv.out_channels
 
     # --- norm description -------------------------------------------------------
@@ -144,10 +139,8 @@ class ConvSpec:
         mode_f = {"bf16x3": Arith.BF16X3, "split": Arith.BF16X6, "split16": Arith.BF16X6, "amp": Arith.F16,
                   "amp_bf16": Arith.BF16}.get(PRECISION, Arith.FP32)
         if PRECISION == "split16" and self.norm is not None and self.k != (1, 1, 1):
-            # fp16x3: the conv reads pre-normalised activations (|x^| of order 1..100 << 65504; clamped at 6e4).
-            # TEM_F16X3_LAYOUT=6 selects the single-accumulator variant with prescaled operands (csrc/conv_split.h), which
-            # fails the GroupNorm parity test (one-sided accumulation error): experiments only.
-            mode_f = _F16X3_MODE
+            # fp16x3: the conv reads pre-normalised activations (|x^| of order 1..100 << 65504; clamped at 6e4)
+            mode_f = Arith.F16X3
         mode_d = Arith.F16 if PRECISION == "amp" else Arith.BF16 if PRECISION == "amp_bf16" else \
             Arith.BF16X3 if PRECISION in ("bf16x3", "mixed", "split", "split16") else Arith.FP32
         mf = mode_f if (not _FORCE_GENERIC) and ops.mfma_ok(self.cin, self.cout, self.k) else Arith.VALU
@@ -155,45 +148,79 @@ class ConvSpec:
         mw = mode_d if (not _FORCE_GENERIC) and ops.mfma_ok(self.cin, self.cout, self.k, wgrad=True) else Arith.VALU
         return mf, md, mw
 
-    def packed(self):
-        w = self.conv.weight
-        ent = getattr(self.conv, "_tem_pack", None)
-        if ent is not None and ent["version"] == w._version and ent["ptr"] == w.data_ptr() and ent["prec"] == PRECISION:
-            return ent
-        if _PACK_BATCH and ent is not None and ent["ptr"] == w.data_ptr() and ent["prec"] == PRECISION:
-            # only the values changed (an optimizer step): refresh EVERY stale registered conv in one launch
-            _repack_stale()
-            ent = self.conv._tem_pack
-            if ent["version"] == w._version:
-                return ent
-        mf, md, mw = self._modes()
-        ent = {
-            "version": w._version, "ptr": w.data_ptr(), "prec": PRECISION,
-            "fwd": ops.pack_weights(w, transpose=False, mfma=mf), "fwd_mfma": mf,
-            "dgrad": ops.pack_weights(w, transpose=True, mfma=md), "dgrad_mfma": md,
-            "wgrad_mfma": mw,
-        }
-        object.__setattr__(self.conv, "_tem_pack", ent)
-        _PACKED_CONVS.add(self.conv)
-        return ent
+    def packed(self) -> pack.PackEntry:
+        return pack.packed(self.conv, PRECISION, self._modes)
 
 
-# Data gradients with fp32-class products.  The backward convolutions run bf16x3 (16-bit operands); at
-# benchmark widths / depth 4 the gradient of the deep levels is 3.5x further from float64 than the fp32 reference path,
-# and round 2 blamed those products.  The layers on the z-reuse kernel can run the fp16 two-term layout (22 bits, same three MFMAs): the gradient has no norm in front of
-# it, so the kernel prescales it by a power of two taken from max |g| -- which the weight gradient of the same layer, that
-# reads all of g anyway, delivers as a by-product (so it runs FIRST).
-# MEASURED (round 3, profiles/r03_depth4_error_*.txt): it does not move the depth-4 gradient error (4.48e-3 with and
-# without, the same with every admissible layer on it) -- exact-fp32 FORWARD convolutions with bf16x3 backward
-# ("mixed") reach the 2.2e-3 of the all-exact build, i.e. the gap was never the backward's 16-bit products.  The path
-# stays (op-level parity 2e-5, tests/test_gpu_ops.py) as an opt-in: TEM_DGRAD16=1; the default keeps bf16x3 (6-17 % faster).
-_DGRAD16 = os.environ.get("TEM_DGRAD16", "0") == "1"
+class NormStats(NamedTuple):
+    """Statistics of the norm in front of a conv (_stats).  mode "sample": InstanceNorm / GroupNorm per sample; "batch":
+    BatchNorm in training mode; "frozen": a norm with running statistics in eval mode (mean / rstd are None)."""
+    mean: Optional[torch.Tensor]
+    rstd: Optional[torch.Tensor]
+    scale: torch.Tensor   # [N, C]: the conv applies x * scale + shift while it stages its input
+    shift: torch.Tensor
+    mode: str
+
+    @property
+    def per_sample(self) -> bool:
+        return self.mode == "sample"
 
 
-def _dgrad16_ok(spec, g, gx) -> bool:
-    return _DGRAD16 and PRECISION == "split16" and not _FORCE_GENERIC and not _OVERLAP_WGRAD and spec.k == (3, 3, 3) and \
-        spec.cin % 32 == 0 and spec.cout % 32 == 0 and ops.conv_fwd_family(g, spec.k, spec.cout, spec.cin, Arith.F16X3, y=gx) == 3 and \
-        ops.conv_wgrad_gmax_ok(g, spec.k, spec.cin, spec.cout, Arith.BF16X3)
+@dataclass(slots=True)
+class BlockState:
+    """What the backward of a ConvBlock needs from its forward (_block_fwd)."""
+    xin: Any            # block input (a tensor or an ops.Planar concat)
+    a1: torch.Tensor    # ReLU output of conv1
+    out: torch.Tensor   # ReLU output of conv2
+    s1: Optional[NormStats]
+    s2: Optional[NormStats]
+    c1: ConvSpec
+    c2: ConvSpec
+    out_part: Any       # first-stage statistics of `out` (partials, nblk) when asked for and delivered
+
+
+@dataclass(slots=True)
+class Level:
+    """One encoder level: its block and the concat buffer it shares with the decoder stage of the same resolution."""
+    cat: Any            # [.., c_up + Cskip] concat buffer (tensor or ops.Planar)
+    skip: torch.Tensor  # its skip half = the block's output
+    bs: BlockState
+    f: tuple            # pooling factor
+    c_up: int
+    floor_sub: Optional[torch.Tensor] = None   # dense copy of the sub-volume whole pooling windows cover (check_shape = False)
+    cat_c: Optional[torch.Tensor] = None       # concat buffer of the decoder stage when the skip is centre-cropped
+    crop: Optional[list] = None                # ... and the crop offsets
+
+
+@dataclass(slots=True)
+class DecStage:
+    """One decoder stage: 1x1 conv at low resolution (low -> t), upsampling into the concat buffer, block (-> out)."""
+    low: torch.Tensor
+    sspec: ConvSpec
+    bs: BlockState
+    f: tuple
+    out: torch.Tensor
+    t: torch.Tensor
+
+
+class SideOut(NamedTuple):
+    ospec: ConvSpec
+    y: torch.Tensor
+
+
+@dataclass(slots=True)
+class Step:
+    """Everything a forward pass keeps for its backward (_forward_impl(keep=True))."""
+    levels: List[Level]
+    dec: List[DecStage]
+    base: BlockState
+    last: torch.Tensor            # output of the last decoder block
+    act: Optional[str]            # final activation fused into the output conv(s)
+    y: torch.Tensor               # prediction (NDHWC)
+    dim: int
+    x_shape: tuple
+    ospec: Optional[ConvSpec] = None        # output conv of a plain network
+    side: Optional[List[SideOut]] = None    # return_side_outputs: one per decoder stage, coarse .. fine
 
 
 # Weight gradients of the pre-normalised 3x3x3 convolutions in the "fp16 2x1" arithmetic (round 4, VERDICT r3 item 2:
@@ -216,130 +243,29 @@ _FUSE_COEF = os.environ.get("TEM_FUSE_NORM_COEF", "1") != "0"
 _FUSE_POOL_STATS = os.environ.get("TEM_FUSE_POOL_STATS", "1") != "0"   # max-pool forward writes the statistics partials of its output
 
 
-class _sums_coef:
-    """`rq = _sums_coef(spec, stats, x); sums = <weight gradient with sums_from>(..., bp=rq.bp); rq.attach(sums)` -- the
-    launch also writes the coefficients of the norm backward (ops.Byproducts.norm_coef: an explicit argument of the call)
-    when the layer allows it; they travel on the sums tensor (`_tem_coef`) to _norm_bwd_inplace(coef_only=True).  Norms with
-    affine parameters keep the separate stage: their dgamma / dbeta come from it."""
-
-    def __init__(self, spec, stats, x, on=True):
-        groups, gamma, beta, _ = spec.norm_args()
-        self.coef = self.bp = None
-        if on and _FUSE_COEF and gamma is None and beta is None and stats is not None and stats[4] == "sample":
-            self.coef = torch.empty((x.shape[0], spec.cin, 4), dtype=torch.float32, device=x.device)
-            self.bp = ops.Byproducts(norm_coef=(groups, stats[0], stats[1], self.coef))
-
-    def attach(self, sums):
-        if self.bp is not None and self.bp.coef and sums is not None:
-            sums._tem_coef = self.coef
-        return sums
+def _coef_request(spec, stats, x):
+    """-> (coef [N, Cin, 4], bp): a weight gradient that delivers the norm sums (sums_from=...) also finishes them into the
+    coefficients of the norm backward when given bp (ops.Byproducts.norm_coef) and the layer allows it, else (None, None).
+    Norms with affine parameters keep the separate stage: their dgamma / dbeta come from it."""
+    groups, gamma, beta, _ = spec.norm_args()
+    if _FUSE_COEF and gamma is None and beta is None and stats is not None and stats.per_sample:
+        coef = torch.empty((x.shape[0], spec.cin, 4), dtype=torch.float32, device=x.device)
+        return coef, ops.Byproducts(norm_coef=(groups, stats.mean, stats.rstd, coef))
+    return None, None
 
 
-class _output_amax:
-    """`rq = _output_amax(grads, out); <launch that writes the data gradient out>(..., out_amax=rq.slot | bp=rq.bp);
-    rq.done(delivered)` -- the launch also delivers max |out| for the fp16 2x1 weight gradient that reads `out` next; when
-    no kernel of the launch supports it the consumer falls back to one absmax pass.  `out` must not be modified afterwards
-    (callers that do drop the entry)."""
-
-    def __init__(self, grads, out, bp=None):
-        on = grads is not None and _FUSE_AMAX and _WGRAD_F16X2 and PRECISION == "split16" and not _FORCE_GENERIC
-        self.out = out
-        self.slot = grads.amax_slot() if on else None
-        self.bp = bp
-        if on and bp is None:
-            self.bp = ops.Byproducts(out_amax=self.slot)
-        elif on:
-            bp.c.out_amax = self.slot.data_ptr()
-
-    def done(self, delivered=None):
-        if self.slot is not None and (self.bp.amax if delivered is None else delivered):
-            self.out._tem_amax = self.slot   # on the tensor OBJECT: dies with it (an address could be reused by another tensor)
-            self.out._tem_amax_ver = self.out._version   # ... and with any torch in-place op on it (ADVICE r4: no manual clearing needed)
+def _amax_slot(grads):
+    """A cleared word for `out_amax=` of the launch that writes a data gradient: the launch also delivers max |out| for the
+    fp16 2x1 weight gradient that reads `out` next (_wgrad(amax=)); None when no such weight gradient runs.  The word
+    describes `out` as written: it travels next to it and is dropped where `out` is modified."""
+    on = grads is not None and _FUSE_AMAX and _WGRAD_F16X2 and PRECISION == "split16" and not _FORCE_GENERIC
+    return grads.amax_slot() if on else None
 
 
 def _wgrad_f16x2_ok(spec, x, stats) -> bool:
-    return _WGRAD_F16X2 and PRECISION == "split16" and stats is not None and not _FORCE_GENERIC and not _OVERLAP_WGRAD and \
+    return _WGRAD_F16X2 and PRECISION == "split16" and stats is not None and not _FORCE_GENERIC and \
         spec.k == (3, 3, 3) and spec.cin % 32 == 0 and spec.cout % 32 == 0 and \
         ops.conv_wgrad_gscaled_ok(x, spec.k, spec.cin, spec.cout)
-
-
-_PACKED_CONVS = weakref.WeakSet()
-_PACK_BATCH = os.environ.get("TEM_PACK_BATCH", "1") != "0"
-_PACK_TABLES = {}
-
-
-def _generic_batchable(conv, k) -> bool:
-    """k_pack_weights_batch writes the generic layout in items of 8 elements"""
-    return _PACK_BATCH and (conv.out_channels * conv.in_channels * k[0] * k[1] * k[2]) % 8 == 0 and conv.weight.is_contiguous()
-
-
-def _pack_job(conv, ent, key, k, transpose):
-    """The job (ops.pack_table) that re-packs ent[key] in the batched launch, or None when the tensor needs a
-    tem_conv_pack_weights launch of its own."""
-    planes, kind = Arith(ent[key + "_mfma"]).pack
-    cout, cin = conv.out_channels, conv.in_channels
-    if kind == PackKind.FP32:
-        # exact fp32 (TEM_WL_MFMA): two 64-lane groups per 16-channel chunk, written by the tile kernel only
-        batched = _PACK_BATCH and pack_is_tiled(planes, k, cout, cin)
-    elif planes == 0:
-        # the generic fp32 layout (first conv, out_conv) rides along in the batched launch
-        batched = _generic_batchable(conv, k)
-    else:
-        batched = True
-    return (conv.weight, ent[key], cout, cin, k, transpose, planes, kind) if batched else None
-
-
-def _repack_stale(prepare_only: bool = False):
-    """Re-pack the weights of every registered conv whose parameter changed in place (same storage, new version):
-    all split-layout packs go into ONE tem_conv_pack_weights_batch launch, written into the existing buffers.
-    prepare_only: build (and upload) the job table for the currently stale set without launching or marking anything
-    fresh -- HIP-graph capture cannot upload it, so torch_em_amd/graph.py does that just before capturing."""
-    jobs, rest = [], []
-    # a WeakSet has no stable order: sort, so that the same stale set always gives the same table
-    for conv in sorted(_PACKED_CONVS, key=lambda c: c.weight.data_ptr()):
-        ent = getattr(conv, "_tem_pack", None)
-        w = conv.weight
-        if ent is None or not w.is_cuda or ent["ptr"] != w.data_ptr() or ent["prec"] != PRECISION \
-                or ent["version"] == w._version:
-            continue
-        k = _k3(conv.kernel_size)
-        for key, transpose in (("fwd", 0), ("dgrad", 1), ("fwd_inf", 0), ("dgrad16", 1)):
-            if key not in ent:
-                continue
-            if prepare_only:
-                job = None if key == "fwd_inf" and not ent.get("fwd_inf_used", False) else _pack_job(conv, ent, key, k, transpose)
-                if job is not None:
-                    jobs.append(job)
-                continue
-            if key == "dgrad" and "dgrad16" in ent and ent.pop("dgrad16_used", False) and not ent.pop("dgrad_used", False):
-                # this layer's data gradient runs in the fp16 layout: the bf16 pack is re-made lazily if ever needed again
-                del ent["dgrad"]
-                continue
-            if key == "fwd_inf" and not ent.pop("fwd_inf_used", False):
-                # not used since the last refresh (a model that went back to training): drop it, it is re-packed lazily
-                del ent["fwd_inf"], ent["fwd_inf_mfma"]
-                continue
-            job = _pack_job(conv, ent, key, k, transpose)
-            if job is not None:
-                jobs.append(job)
-            else:
-                rest.append((ent, key, w, bool(transpose), ent[key + "_mfma"]))
-        if not prepare_only:
-            ent["version"] = w._version
-    for ent, key, w, transpose, mode in rest:
-        ent[key] = ops.pack_weights(w, transpose=transpose, mfma=mode)
-    by_dev = {}
-    for j in jobs:  # one table / launch per device (a process normally drives one GPU)
-        by_dev.setdefault(j[0].device, []).append(j)
-    for dev, dj in by_dev.items():
-        sig = tuple((j[0].data_ptr(), j[1].data_ptr()) for j in dj)
-        ent = _PACK_TABLES.get(dev)
-        if ent is None or ent[0] != sig:
-            ent = _PACK_TABLES[dev] = (sig, ops.pack_table(dj))
-        if prepare_only:
-            continue
-        with torch.cuda.device(dev):
-            ops.pack_weights_batch(ent[1])
 
 
 def fused_activation(act: nn.Module) -> Optional[str]:
@@ -371,32 +297,12 @@ _FUSE_STATS = os.environ.get("TEM_FUSE_STATS", "1") != "0"
 _FUSE_CONCAT_STATS = os.environ.get("TEM_FUSE_CONCAT_STATS", "1") != "0"
 
 
-# experiment knob (round 3): training-mode forward convolutions of levels with at most this many voxels per
-# sample run the EXACT fp32 MFMA instead of the split-precision kernels.  Measured on the depth-4 benchmark network: the
-# global gradient error against float64 jumps between 1.5e-3 and 4.5e-3 as the threshold moves (64: 4.5e-3, 4096: 1.5e-3,
-# 32768: 4.4e-3, all levels: 2.2e-3) -- it is decided by a handful of near-tie ReLU / arg-max decisions, not by a precision
-# class.  Default 0 = off.
-_EXACT_FWD_MAX_VOXELS = int(os.environ.get("TEM_EXACT_FWD_MAX_VOXELS", "0"))
-
-
 def _conv(spec: ConvSpec, x, y, stats=None, act=None, want_stats=False):
     ent = spec.packed()
-    scale, shift = (stats[2], stats[3]) if stats is not None else (None, None)
-    wpk, mode = ent["fwd"], ent["fwd_mfma"]
-    if _EXACT_FWD_MAX_VOXELS and not _TLS.no_grad_forward and mode in (Arith.BF16X3, Arith.BF16X6, Arith.F16X3) and \
-            x.shape[1] * x.shape[2] * x.shape[3] <= _EXACT_FWD_MAX_VOXELS:
-        if ent.get("fwd_exact_version") != spec.conv.weight._version:
-            ent["fwd_exact"] = ops.pack_weights(spec.conv.weight, transpose=False, mfma=Arith.FP32)
-            ent["fwd_exact_version"] = spec.conv.weight._version
-        ops.conv_fwd(x, ent["fwd_exact"], spec.conv.bias, y, spec.k, spec.cin, spec.cout, scale=scale, shift=shift, act=act, mfma=Arith.FP32)
-        return None if want_stats else y   # the exact kernel writes no statistics: the caller runs norm_stats
-    if _TLS.no_grad_forward and _INFER_BF16X3 and mode == Arith.BF16X6:
-        if "fwd_inf" not in ent:  # packed on first use, refreshed with the others by _repack_stale
-            ent["fwd_inf"], ent["fwd_inf_mfma"] = ops.pack_weights(spec.conv.weight, transpose=False, mfma=Arith.BF16X3), Arith.BF16X3
-        ent["fwd_inf_used"] = True
-        wpk, mode = ent["fwd_inf"], Arith.BF16X3
-    return ops.conv_fwd(x, wpk, spec.conv.bias, y, spec.k, spec.cin, spec.cout, scale=scale, shift=shift, act=act,
-                        mfma=mode, want_stats=want_stats)
+    scale, shift = (stats.scale, stats.shift) if stats is not None else (None, None)
+    wp = ent.get("fwd_inf" if _TLS.no_grad_forward and _INFER_BF16X3 and ent.fwd.mode == Arith.BF16X6 else "fwd")
+    return ops.conv_fwd(x, wp.buf, spec.conv.bias, y, spec.k, spec.cin, spec.cout, scale=scale, shift=shift, act=act,
+                        mfma=wp.mode, want_stats=want_stats)
 
 
 class _Grads:
@@ -411,7 +317,7 @@ class _Grads:
         self.flat = torch.zeros(total, dtype=torch.float32, device=params[0].device)
         self.written = set()
         self._new = []
-        self._amax = None     # int32 words for max |g| of the data gradients that run in the fp16 two-term layout
+        self._amax = None     # int32 words for max |g| of data gradients (_amax_slot, ops.absmax)
         self._amax_used = 0
 
     def amax_slot(self) -> torch.Tensor:
@@ -445,137 +351,69 @@ class _Grads:
         return [tuple(r) for r in out]
 
 
-# Weight gradients are leaves of the backward pass (nothing downstream in it reads dw), so they can run on a second HIP
-# stream.  Two schedules were measured (TEM_OVERLAP_WGRAD):
-#   1  "free": wgrad starts as soon as its inputs exist, i.e. next to the dgrad of the same layer: +1.3 ms/step -- the
-#      two MFMA kernels cannot co-reside on a CU (101 KB + 2 x 67 KB of LDS) and fight for the same pipes;
-#   2  "deferred": a layer's dgrad runs first, ALONE; its wgrad then runs on the side stream next to the HBM-bound
-#      kernels that follow on the main stream (norm backward: two passes; pool / upsample backward), which need neither
-#      LDS nor the matrix pipe; the next dgrad waits for the side stream.  On paper the critical path becomes
-#      sum(dgrad) + sum(max(wgrad, norm/pool backward)); measured +0.4 ms/step (24.9 vs 24.5): the z-sliding wgrad
-#      kernel owns a CU's whole register file (2 waves/SIMD x 256 VGPRs) and >100 KB of its LDS, so no norm-kernel
-#      wave can co-reside -- the two kernels time-slice CUs instead of sharing them;
-#   0  (default) everything on one stream.
-_OVERLAP_WGRAD = int(os.environ.get("TEM_OVERLAP_WGRAD", "0"))
-_OVERLAP_MAX_VOXELS = int(os.environ.get("TEM_OVERLAP_MAX_VOXELS", str(2 * 32 ** 3)))  # mode 1 only
-_SIDE_STREAMS = {}
-
-
-def _side_stream(device):
-    key = device.index if device.index is not None else torch.cuda.current_device()
-    st = _SIDE_STREAMS.get(key)
-    if st is None:
-        st = _SIDE_STREAMS[key] = torch.cuda.Stream(device=device)
-    return st
-
-
-def _join_side(device):
-    """main stream waits for every weight gradient launched so far"""
-    if _OVERLAP_WGRAD and (device.index if device.index is not None else torch.cuda.current_device()) in _SIDE_STREAMS:
-        torch.cuda.current_stream(device).wait_stream(_side_stream(device))
-
-
 # the split-K epilogue of a data gradient also writes the first stage of the backward of the norm in front of the conv
 # (TEM_BP_NORM_SUMS of tem_conv3d_fwd_ex: k_norm_partial<.,1> disappears for the 16^3 / 8^3 levels); 0: the pass over gx and x
 _FUSE_DGRAD_SUMS = os.environ.get("TEM_FUSE_DGRAD_SUMS", "1") != "0"
 
 
-def _dgrad(spec: ConvSpec, g, gx, ref=None, gmax=None, refnorm=None, grads=None, sums_for=None):
-    """gmax: int32[1] with max |g| (from _wgrad(..., gmax=) of the same layer) -> fp16 two-term layout, else bf16x3.
+def _dgrad(spec: ConvSpec, g, gx, ref=None, refnorm=None, grads=None, sums_for=None):
+    """-> (sums, amax), each None when not asked for or not delivered.
     refnorm: coef [N, C, 4] of the norm behind `ref` -- its backward (and ref's ReLU mask) run in the kernel's epilogue.
-    grads: gx is FINAL after this call (nothing rewrites it): ask the kernel for max |gx| as a by-product.
+    grads: gx is FINAL after this call (nothing rewrites it): ask the kernel for max |gx| as a by-product (_amax_slot).
     sums_for = (x, stats): gx lands behind the norm whose input is x -> partial rows [N, nblk, C, 2] of its backward's first
-    stage when this launch can deliver them (plain launch on the split-K z-reuse kernel), else None."""
-    part = bp = None
-    if sums_for is not None and _FUSE_DGRAD_SUMS and ref is None and gmax is None and refnorm is None and not _FORCE_GENERIC:
+    stage when this launch can deliver them (plain launch on the split-K z-reuse kernel).  Not together with grads."""
+    assert grads is None or sums_for is None
+    ent = spec.packed()
+    part = slot = bp = None
+    if sums_for is not None and _FUSE_DGRAD_SUMS and ref is None and refnorm is None and not _FORCE_GENERIC:
         x, stats = sums_for
-        mode = spec.packed()["dgrad_mfma"]
-        if stats is not None and stats[4] == "sample" and ops.conv_fwd_family(g, spec.k, spec.cout, spec.cin, mode, y=gx) == 4:
+        mode = ent.dgrad.mode
+        if stats is not None and stats.per_sample and ops.conv_fwd_family(g, spec.k, spec.cout, spec.cin, mode, y=gx) == 4:
             nblk = ops.conv_fwd_stat_blocks(g, spec.k, spec.cout, spec.cin, mode, y=gx)
             if nblk > 0:
                 part = torch.empty((x.shape[0], nblk, spec.cin, 2), dtype=torch.float32, device=x.device)
-                bp = ops.Byproducts(norm_sums=(x, spec.norm_args()[0], stats[0], stats[1], part))
-    rq = _output_amax(grads, gx, bp)
-    _dgrad_launch(spec, g, gx, ref, gmax, refnorm, rq.bp)
-    rq.done()
-    return part if bp is not None and bp.sums else None
-
-
-def _dgrad_launch(spec: ConvSpec, g, gx, ref, gmax, refnorm, bp=None):
-    if _OVERLAP_WGRAD == 2:
-        _join_side(g.device)  # MFMA kernels never overlap each other: wait for the weight gradient in flight
-    ent = spec.packed()
+                bp = ops.Byproducts(norm_sums=(x, spec.norm_args()[0], stats.mean, stats.rstd, part))
+    else:
+        slot = _amax_slot(grads)
+        if slot is not None:
+            bp = ops.Byproducts(out_amax=slot)
+    wp = ent.get("dgrad")
     if refnorm is not None:
-        if "dgrad" not in ent:
-            ent["dgrad"] = ops.pack_weights(spec.conv.weight, transpose=True, mfma=ent["dgrad_mfma"])
-        ent["dgrad_used"] = True
-        ops.conv_fwd_refnorm(g, ent["dgrad"], gx, spec.k, spec.cout, spec.cin, ref, refnorm, ent["dgrad_mfma"], bp=bp)
-        return
-    if gmax is not None:
-        if "dgrad16" not in ent:
-            ent["dgrad16"], ent["dgrad16_mfma"] = ops.pack_weights(spec.conv.weight, transpose=True, mfma=Arith.F16X3), Arith.F16X3
-        ent["dgrad16_used"] = True
-        ops.conv_fwd_gscaled(g, ent["dgrad16"], gx, spec.k, spec.cout, spec.cin, gmax, ref=ref, bp=bp)
-        return
-    if "dgrad" not in ent:
-        ent["dgrad"] = ops.pack_weights(spec.conv.weight, transpose=True, mfma=ent["dgrad_mfma"])
-    ent["dgrad_used"] = True
-    ops.conv_fwd(g, ent["dgrad"], None, gx, spec.k, spec.cout, spec.cin, ref=ref, mfma=ent["dgrad_mfma"], bp=bp)
+        ops.conv_fwd_refnorm(g, wp.buf, gx, spec.k, spec.cout, spec.cin, ref, refnorm, wp.mode, bp=bp)
+    else:
+        ops.conv_fwd(g, wp.buf, None, gx, spec.k, spec.cout, spec.cin, ref=ref, mfma=wp.mode, bp=bp)
+    return (part if part is not None and bp.sums else None), (slot if slot is not None and bp.amax else None)
 
 
 # Norm-backward sums from the weight gradient (csrc/wgrad_sums.hip, ops.conv_wgrad(sums_from=...)): the reduction pass over the
 # data gradient and the norm input disappears for the layers that qualify.  tem_set_option("wgrad_sums", 0) disables.
-def _wgrad(spec: ConvSpec, x, g, grads: _Grads, stats=None, want_sums=False, gmax=None, amax=None):
-    """-> sums[N, Cin, 2] for _norm_bwd_inplace when want_sums and the layer qualifies, else None.
-    gmax: int32[1] that receives max |g| (only for layers with _dgrad16_ok).
-    amax: int32[1] that HOLDS max |g| already (a producer of g delivered it) for the fp16 2x1 arithmetic."""
+def _wgrad(spec: ConvSpec, x, g, grads: _Grads, stats=None, want_sums=False, amax=None):
+    """-> (sums [N, Cin, 2], coef [N, Cin, 4]) for _norm_bwd_inplace: the sums when want_sums and the layer qualifies, the
+    finished coefficients when the launch delivered them too (_coef_request); each None otherwise.
+    amax: int32[1] that HOLDS max |g| (a producer of g delivered it, _amax_slot) for the fp16 2x1 arithmetic, else None."""
     ent = spec.packed()
-    scale, shift = (stats[2], stats[3]) if stats is not None else (None, None)
+    scale, shift = (stats.scale, stats.shift) if stats is not None else (None, None)
     dw = grads.view(spec.conv.weight)
     db = grads.view(spec.conv.bias) if spec.conv.bias is not None else None
-    vox = x.shape[0] * x.shape[1] * x.shape[2] * x.shape[3]
-
-    def sums_args():
-        """(weight, gamma, beta) for `sums_from` when the caller wants the sums and this layer's weight gradient delivers them"""
-        if want_sums and stats is not None and stats[4] == "sample" and db is not None and \
-                ops.conv_wgrad_sums_ok(x, spec.k, spec.cin, spec.cout, ent["wgrad_mfma"]):
-            _, gamma, beta, _ = spec.norm_args()
-            return spec.conv.weight, gamma, beta
-        return None
-
-    if gmax is not None:
-        sums_from = sums_args()
-        rq = _sums_coef(spec, stats, x, on=sums_from is not None)
-        return rq.attach(ops.conv_wgrad_gmax(x, g, spec.k, spec.cin, spec.cout, dw, db, gmax, scale=scale, shift=shift,
-                                             mfma=ent["wgrad_mfma"], sums_from=sums_from, bp=rq.bp))
-    if ent["wgrad_mfma"] == Arith.BF16X3 and _wgrad_f16x2_ok(spec, x, stats):
-        sums_from = sums_args()
-        if amax is None:
-            amax = getattr(g, "_tem_amax", None)
-            if amax is not None and getattr(g, "_tem_amax_ver", None) != g._version:
-                amax = None   # g was rewritten in place by a torch op after its producer delivered max |g|
-        if amax is None:   # no producer of g delivered max |g|: one pass over g
-            amax = ops.absmax(g, grads.amax_slot())
-        rq = _sums_coef(spec, stats, x, on=sums_from is not None)
-        return rq.attach(ops.conv_wgrad_gscaled(x, g, spec.k, spec.cin, spec.cout, dw, db, amax, scale=scale, shift=shift,
-                                                sums_from=sums_from, bp=rq.bp))
-    sums_from = None if _OVERLAP_WGRAD else sums_args()
+    f16x2 = ent.wgrad == Arith.BF16X3 and _wgrad_f16x2_ok(spec, x, stats)
+    sums_from = coef = bp = None
+    if want_sums and stats is not None and stats.per_sample and db is not None and \
+            ops.conv_wgrad_sums_ok(x, spec.k, spec.cin, spec.cout, ent.wgrad):
+        _, gamma, beta, _ = spec.norm_args()
+        sums_from = spec.conv.weight, gamma, beta
+    if f16x2 and amax is None:   # no producer of g delivered max |g|: one pass over g
+        amax = ops.absmax(g, grads.amax_slot())
     if sums_from is not None:
-        rq = _sums_coef(spec, stats, x)
-        return rq.attach(ops.conv_wgrad(x, g, spec.k, spec.cin, spec.cout, dw, db, scale=scale, shift=shift,
-                                        mfma=ent["wgrad_mfma"], sums_from=sums_from, bp=rq.bp))
-    if not _OVERLAP_WGRAD or (_OVERLAP_WGRAD == 1 and vox > _OVERLAP_MAX_VOXELS):
-        ops.conv_wgrad(x, g, spec.k, spec.cin, spec.cout, dw, db, scale=scale, shift=shift, mfma=ent["wgrad_mfma"])
-        return
-    side = _side_stream(x.device)
-    # x, g, scale/shift were produced on the main stream; in mode 2 this also orders the wgrad BEHIND the dgrad of the
-    # same layer, which the callers launch first
-    side.wait_stream(torch.cuda.current_stream(x.device))
-    with torch.cuda.stream(side):
-        ops.conv_wgrad(x, g, spec.k, spec.cin, spec.cout, dw, db, scale=scale, shift=shift, mfma=ent["wgrad_mfma"])
-    for t in (x, g, scale, shift):  # the caching allocator must not recycle them while the side stream reads
-        if t is not None:
-            t.record_stream(side)
+        coef, bp = _coef_request(spec, stats, x)
+    if f16x2:
+        sums = ops.conv_wgrad_gscaled(x, g, spec.k, spec.cin, spec.cout, dw, db, amax, scale=scale, shift=shift,
+                                      sums_from=sums_from, bp=bp)
+    else:
+        sums = ops.conv_wgrad(x, g, spec.k, spec.cin, spec.cout, dw, db, scale=scale, shift=shift, mfma=ent.wgrad,
+                              sums_from=sums_from, bp=bp)
+    if sums_from is None:
+        return None, None
+    return sums, (coef if bp is not None and bp.coef else None)
 
 
 def _is_batchnorm(n) -> bool:
@@ -608,7 +446,7 @@ _PLANAR_CONCAT = os.environ.get("TEM_PLANAR_CONCAT", "1") != "0"
 
 def _planar_concat_ok(adt, c_up, enc_blk, dec_blk, shape, dev, floor) -> bool:
     if not _PLANAR_CONCAT or adt == torch.float32 or c_up != 32 or enc_blk.out_channels != 32 or floor or _FORCE_GENERIC or \
-            _OVERLAP_WGRAD or not _DEFER_CONCAT_NORM:
+            not _DEFER_CONCAT_NORM:
         return False
     c1 = dec_blk.conv_specs()[0]
     n = c1.norm
@@ -617,8 +455,8 @@ def _planar_concat_ok(adt, c_up, enc_blk, dec_blk, shape, dev, floor) -> bool:
     N, D, H, W = shape
     ent = c1.packed()
     x64, g = ops.Probe(N, D, H, W, 64, adt), ops.Probe(N, D, H, W, c1.cout, adt)
-    return ops.conv_fwd_family(x64, c1.k, 64, c1.cout, ent["fwd_mfma"], y=g) == 3 and \
-        ops.conv_fwd_family(g, c1.k, c1.cout, 64, ent["dgrad_mfma"], y=x64) == 3 and \
+    return ops.conv_fwd_family(x64, c1.k, 64, c1.cout, ent.fwd.mode, y=g) == 3 and \
+        ops.conv_fwd_family(g, c1.k, c1.cout, 64, ent.dgrad.mode, y=x64) == 3 and \
         ops.conv_wgrad_cs_ok(x64, c1.k, 64, c1.cout, N * D * H * W * 32)   # the stride ops.Planar gives its two planes
 
 
@@ -644,10 +482,9 @@ def _planar_stats(x, groups, gamma, beta, eps):
 
 
 def _stats(spec: ConvSpec, x, partials=None, partials2=None):
-    """Statistics of the norm in front of a conv -> (mean, rstd, scale[N,C], shift[N,C], mode).
-    partials: (part, nblk) from the producing conv's epilogue (ops.conv_fwd(want_stats=True)) or None.
-    mode "sample": InstanceNorm / GroupNorm per sample; "batch": BatchNorm in training mode (reference
-    `get_norm_layer`, model/unet.py:391-406); "frozen": a norm with running statistics in eval mode."""
+    """Statistics of the norm in front of a conv -> NormStats, or None without a norm (reference `get_norm_layer`,
+    model/unet.py:391-406).
+    partials: (part, nblk) from the producing conv's epilogue (ops.conv_fwd(want_stats=True)) or None."""
     na = spec.norm_args()
     if na is None:
         return None
@@ -662,7 +499,7 @@ def _stats(spec: ConvSpec, x, partials=None, partials2=None):
         shift = -n.running_mean.float() * scale
         if beta is not None:
             shift = shift + beta.detach().float()
-        return None, None, scale.expand(N, -1).contiguous(), shift.expand(N, -1).contiguous(), "frozen"
+        return NormStats(None, None, scale.expand(N, -1).contiguous(), shift.expand(N, -1).contiguous(), "frozen")
     vox = x.shape[1] * x.shape[2] * x.shape[3]
     if _is_batchnorm(n):
         xb = _flat_batch(x)
@@ -674,7 +511,7 @@ def _stats(spec: ConvSpec, x, partials=None, partials2=None):
             mean, rstd, scale, shift = ops.norm_stats(xb, groups, gamma, beta, eps)
         if tracked:
             _update_running(n, mean, 1.0 / (rstd * rstd) - eps, xb.shape[1] * xb.shape[2] * xb.shape[3])
-        return mean, rstd, scale.expand(N, -1).contiguous(), shift.expand(N, -1).contiguous(), "batch"
+        return NormStats(mean, rstd, scale.expand(N, -1).contiguous(), shift.expand(N, -1).contiguous(), "batch")
     if partials2 is not None:
         mean, rstd, scale, shift = ops.norm_stats_from_partials2(partials2[0], partials2[1], N, vox, groups, gamma, beta, eps)
     elif partials is not None:
@@ -685,7 +522,7 @@ def _stats(spec: ConvSpec, x, partials=None, partials2=None):
         mean, rstd, scale, shift = ops.norm_stats(x, groups, gamma, beta, eps)
     if tracked:  # InstanceNormTrackStats: per-instance statistics, running averages of their batch means
         _update_running(n, mean, 1.0 / (rstd * rstd) - eps, x.shape[1] * x.shape[2] * x.shape[3])
-    return mean, rstd, scale, shift, "sample"
+    return NormStats(mean, rstd, scale, shift, "sample")
 
 
 def _norm_is_live(n) -> bool:
@@ -698,7 +535,7 @@ def _block_fwd(blk, xin, out, in_partials2=None, out_stats=False, in_partials=No
     """ConvBlock (reference model/unet.py:429-438): [norm->conv->ReLU] x 2.  Returns what backward needs.
     in_partials2: first-stage statistics of the two channel halves of xin (decoder concat) or None.
     in_partials: first-stage statistics of xin from its producer (the max-pool kernel) or None.
-    out_stats: also return the first-stage statistics of `out` (key "out_part"; None when conv2 cannot provide them)."""
+    out_stats: also return the first-stage statistics of `out` (out_part; None when conv2 cannot provide them)."""
     c1, c2 = blk.conv_specs()
     N, D, H, W, _ = xin.shape
     s1 = _stats(c1, xin, partials=in_partials, partials2=in_partials2)
@@ -707,8 +544,7 @@ def _block_fwd(blk, xin, out, in_partials2=None, out_stats=False, in_partials=No
     part = _conv(c1, xin, a1, s1, act="relu", want_stats=_FUSE_STATS and live)
     s2 = _stats(c2, a1, partials=part if (_FUSE_STATS and live) else None)
     out_part = _conv(c2, a1, out, s2, act="relu", want_stats=bool(out_stats))
-    return {"xin": xin, "a1": a1, "out": out, "s1": s1, "s2": s2, "c1": c1, "c2": c2,
-            "out_part": out_part if out_stats else None}
+    return BlockState(xin, a1, out, s1, s2, c1, c2, out_part if out_stats else None)
 
 
 # The norm in front of a decoder block reads concat(upsample(u), skip).  Its backward needs no elementwise pass over that
@@ -721,97 +557,93 @@ _DEFER_CONCAT_NORM = os.environ.get("TEM_DEFER_CONCAT_NORM", "1") != "0"
 _FUSE_NORM_BWD_DGRAD = os.environ.get("TEM_FUSE_NORM_BWD_DGRAD", "1") != "0"
 
 
-def _norm_bwd_inplace(spec: ConvSpec, g, x, stats, relu_mask, grads: _Grads, sums=None, coef_only=False, amax=False):
-    """coef_only: return the [N, C, 4] coefficients instead of applying them (g stays the raw data gradient)
-    amax: a weight gradient reads the rewritten g next -- the elementwise pass delivers max |g| (see _output_amax)"""
+def _norm_bwd_inplace(spec: ConvSpec, g, x, stats, relu_mask, grads: _Grads, sums=None, coef=None, coef_only=False, amax=False):
+    """coef_only: return the [N, C, 4] coefficients instead of applying them (g stays the raw data gradient); `coef`: the
+    weight gradient behind `sums` finished them already (_wgrad)
+    amax: a weight gradient reads the rewritten g next -- the elementwise pass delivers max |g| (_amax_slot): returned"""
     groups, gamma, beta, _ = spec.norm_args()
     dgamma = grads.view(gamma) if gamma is not None else None
     dbeta = grads.view(beta) if beta is not None else None
-    mode = stats[4]
     if coef_only:
-        assert mode == "sample"
-        ready = getattr(sums, "_tem_coef", None)   # the weight gradient behind `sums` finished them already (_sums_coef)
-        if ready is not None:
-            return ready
-        return ops.norm_bwd_coef(g, x, groups, gamma, stats[0], stats[1], dgamma, dbeta, sums=sums)
-    if mode == "frozen":
+        assert stats.per_sample
+        if coef is not None:
+            return coef
+        return ops.norm_bwd_coef(g, x, groups, gamma, stats.mean, stats.rstd, dgamma, dbeta, sums=sums)
+    if stats.mode == "frozen":
         raise NotImplementedError("backward through a norm with frozen running statistics (model.eval()) is not "
                                   "supported; call model.train() for training")
-    if mode == "batch":
+    if stats.mode == "batch":
         gb = _flat_batch(g)
-        ops.norm_bwd(gb, _flat_batch(x), groups, gamma, stats[0], stats[1], relu_mask, gb, dgamma, dbeta)
-        return
-    rq = _output_amax(grads if amax else None, g)
-    ops.norm_bwd(g, x, groups, gamma, stats[0], stats[1], relu_mask, g, dgamma, dbeta, sums=sums, out_amax=rq.slot)
-    rq.done(True)
+        ops.norm_bwd(gb, _flat_batch(x), groups, gamma, stats.mean, stats.rstd, relu_mask, gb, dgamma, dbeta)
+        return None
+    slot = _amax_slot(grads if amax else None)
+    ops.norm_bwd(g, x, groups, gamma, stats.mean, stats.rstd, relu_mask, g, dgamma, dbeta, sums=sums, out_amax=slot)
+    return slot
 
 
-def _block_bwd(bs, gout, gin, grads: _Grads, defer_input_norm=False):
-    """gout: gradient w.r.t. the block's pre-ReLU conv2 output (i.e. already ReLU-masked).
+def _norm2_in_dgrad_ok(bs: BlockState, gout, ga1, need_ga1: bool) -> bool:
+    """weight gradient of conv2 first (it delivers the sums of norm2's backward), norm2's backward in the data-gradient epilogue"""
+    c2, a1 = bs.c2, bs.a1
+    return bs.s2 is not None and _FUSE_NORM_BWD_DGRAD and bs.s2.per_sample and need_ga1 and c2.conv.bias is not None and \
+        ops.conv_wgrad_sums_ok(a1, c2.k, c2.cin, c2.cout, c2.packed().wgrad) and \
+        ops.conv_fwd_family(gout, c2.k, c2.cout, c2.cin, c2.packed().dgrad.mode, y=ga1, ref=a1) == 3
+
+
+def _norm2_in_wgrad1_ok(bs: BlockState) -> bool:
+    """first block of the net (nothing but conv1's weight gradient reads ga1): that kernel applies norm2's backward on load"""
+    c1 = bs.c1
+    return _DEFER_CONCAT_NORM and bs.s2.per_sample and c1.conv.bias is not None and \
+        ops.conv_wgrad_gnorm_ok(c1.k, c1.cin, c1.cout, c1.packed().wgrad)
+
+
+def _block_bwd(bs: BlockState, gout, gout_amax, gin, grads: _Grads, defer_input_norm=False):
+    """gout: gradient w.r.t. the block's pre-ReLU conv2 output (i.e. already ReLU-masked); gout_amax: max |gout| from the
+    kernel that wrote it (_amax_slot) or None.
     gin: buffer for the gradient w.r.t. the block input, or None when not needed.
     defer_input_norm: leave the backward of the block's FIRST norm to the consumers of gin: returns its coefficients
     ([N, C, 4], see _DEFER_CONCAT_NORM) and gin holds the raw data gradient; returns None when it was applied here."""
-    c1, c2, xin, a1 = bs["c1"], bs["c2"], bs["xin"], bs["a1"]
-    # per layer: dgrad first (alone), then the weight gradient (side stream, see _OVERLAP_WGRAD) next to the norm backward
+    c1, c2, xin, a1, s1, s2 = bs.c1, bs.c2, bs.xin, bs.a1, bs.s1, bs.s2
     ga1 = torch.empty_like(a1)
-    affine1 = bs["s1"] is not None and c1.norm_args()[1] is not None
-    if bs["s2"] is not None and _FUSE_NORM_BWD_DGRAD and bs["s2"][4] == "sample" and not _OVERLAP_WGRAD and \
-            not (gin is None and not affine1) and not _dgrad16_ok(c2, gout, ga1) and c2.conv.bias is not None and \
-            ops.conv_wgrad_sums_ok(a1, c2.k, c2.cin, c2.cout, c2.packed()["wgrad_mfma"]) and \
-            ops.conv_fwd_family(gout, c2.k, c2.cout, c2.cin, c2.packed()["dgrad_mfma"], y=ga1, ref=a1) == 3:
+    ga1_amax = None
+    affine1 = s1 is not None and c1.norm_args()[1] is not None
+    only_dw1 = gin is None and not affine1    # nothing but conv1's weight gradient reads ga1
+    if _norm2_in_dgrad_ok(bs, gout, ga1, not only_dw1):
         # The weight gradient runs FIRST and delivers the sums of norm2's backward (ops.conv_wgrad(sums_from=...)) without the data
         # gradient existing yet; with the coefficients known, the data-gradient kernel applies norm2's backward and the
         # ReLU mask of a1 in its epilogue: no elementwise pass over ga1 and a1 (0.28 ms at 2 x 128^3 x 32)
-        sums = _wgrad(c2, a1, gout, grads, bs["s2"], want_sums=True)
-        coef = _norm_bwd_inplace(c2, gout, a1, bs["s2"], True, grads, sums=sums, coef_only=True)
-        _dgrad(c2, gout, ga1, ref=a1, refnorm=coef, grads=grads)
-    elif bs["s2"] is not None:
-        if _dgrad16_ok(c2, gout, ga1):   # weight gradient first: it delivers max |gout| for the prescale of the data gradient
-            gm = grads.amax_slot()
-            sums = _wgrad(c2, a1, gout, grads, bs["s2"], want_sums=True, gmax=gm)
-            _dgrad(c2, gout, ga1, gmax=gm)
-        else:
-            dsums = _dgrad(c2, gout, ga1, sums_for=(a1, bs["s2"]))
-            sums = _wgrad(c2, a1, gout, grads, bs["s2"], want_sums=True)
-            if sums is None:
-                sums = dsums
-        if gin is None and not affine1 and _DEFER_CONCAT_NORM and bs["s2"][4] == "sample" and not _OVERLAP_WGRAD and \
-                c1.conv.bias is not None and ops.conv_wgrad_gnorm_ok(c1.k, c1.cin, c1.cout, c1.packed()["wgrad_mfma"]):
-            # first block of the net: nothing but conv1's weight gradient reads the gradient behind norm2, and that
-            # kernel applies norm2's backward (+ the ReLU mask of a1) while it loads g: no pass that rewrites ga1
-            coef = _norm_bwd_inplace(c2, ga1, a1, bs["s2"], True, grads, sums=sums, coef_only=True)
-            s1 = bs["s1"]
+        sums, coef = _wgrad(c2, a1, gout, grads, s2, want_sums=True, amax=gout_amax)
+        coef = _norm_bwd_inplace(c2, gout, a1, s2, True, grads, sums=sums, coef=coef, coef_only=True)
+        _, ga1_amax = _dgrad(c2, gout, ga1, ref=a1, refnorm=coef, grads=grads)
+    elif s2 is not None:
+        dsums, _ = _dgrad(c2, gout, ga1, sums_for=(a1, s2))
+        sums, coef = _wgrad(c2, a1, gout, grads, s2, want_sums=True, amax=gout_amax)
+        if sums is None:
+            sums = dsums
+        if only_dw1 and _norm2_in_wgrad1_ok(bs):
+            # no pass that rewrites ga1: conv1's weight gradient applies norm2's backward (+ the ReLU mask of a1) while it loads g
+            coef = _norm_bwd_inplace(c2, ga1, a1, s2, True, grads, sums=sums, coef=coef, coef_only=True)
             ops.conv_wgrad_gnorm(xin, ga1, a1, coef, c1.k, c1.cin, c1.cout, grads.view(c1.conv.weight),
-                                 grads.view(c1.conv.bias), scale=None if s1 is None else s1[2],
-                                 shift=None if s1 is None else s1[3])
+                                 grads.view(c1.conv.bias), scale=None if s1 is None else s1.scale,
+                                 shift=None if s1 is None else s1.shift)
             return None
-        _norm_bwd_inplace(c2, ga1, a1, bs["s2"], True, grads, sums=sums, amax=True)  # a1 is a ReLU output: mask fused
-    elif _dgrad16_ok(c2, gout, ga1):
-        gm = grads.amax_slot()
-        _wgrad(c2, a1, gout, grads, bs["s2"], gmax=gm)
-        _dgrad(c2, gout, ga1, ref=a1, gmax=gm)
+        ga1_amax = _norm_bwd_inplace(c2, ga1, a1, s2, True, grads, sums=sums, amax=True)  # a1 is a ReLU output: mask fused
     else:
         _dgrad(c2, gout, ga1, ref=a1)
-        _wgrad(c2, a1, gout, grads, bs["s2"])
-    if gin is None and not affine1:
-        _wgrad(c1, xin, ga1, grads, bs["s1"])
-        return
+        _wgrad(c2, a1, gout, grads, s2, amax=gout_amax)
+    if only_dw1:
+        _wgrad(c1, xin, ga1, grads, s1, amax=ga1_amax)
+        return None
     if gin is None:
         N, D, H, W, _ = xin.shape
         gin = ops.new_act(N, D, H, W, c1.cin, xin.device, xin.dtype)
-    if _dgrad16_ok(c1, ga1, gin):
-        gm = grads.amax_slot()
-        sums = _wgrad(c1, xin, ga1, grads, bs["s1"], want_sums=bs["s1"] is not None, gmax=gm)
-        _dgrad(c1, ga1, gin, gmax=gm)
-    else:
-        dsums = _dgrad(c1, ga1, gin, sums_for=(xin, bs["s1"]) if bs["s1"] is not None else None)
-        sums = _wgrad(c1, xin, ga1, grads, bs["s1"], want_sums=bs["s1"] is not None)
-        if sums is None:
-            sums = dsums
-    if bs["s1"] is not None:
-        if defer_input_norm and _DEFER_CONCAT_NORM and bs["s1"][4] == "sample":
-            return _norm_bwd_inplace(c1, gin, xin, bs["s1"], False, grads, sums=sums, coef_only=True)
-        _norm_bwd_inplace(c1, gin, xin, bs["s1"], False, grads, sums=sums)
+    dsums, _ = _dgrad(c1, ga1, gin, sums_for=(xin, s1) if s1 is not None else None)
+    sums, coef = _wgrad(c1, xin, ga1, grads, s1, want_sums=s1 is not None, amax=ga1_amax)
+    if sums is None:
+        sums = dsums
+    if s1 is not None:
+        if defer_input_norm and _DEFER_CONCAT_NORM and s1.per_sample:
+            return _norm_bwd_inplace(c1, gin, xin, s1, False, grads, sums=sums, coef=coef, coef_only=True)
+        _norm_bwd_inplace(c1, gin, xin, s1, False, grads, sums=sums)
     return None
 
 
@@ -844,7 +676,7 @@ def _forward_impl_body(model, x: torch.Tensor, keep: bool):
     N = xin.shape[0]
     dev = xin.device
     adt = act_dtype()   # fp32, or the 16-bit storage type of the mixed modes (the network input and the prediction stay fp32)
-    st = {"levels": [], "dim": dim, "x_shape": tuple(x.shape)}
+    levels, stages = [], []
     cur = xin
     cur_part = None   # first-stage statistics of `cur` from the kernel that produced it (the max-pool), if any
     for l in range(depth):
@@ -866,13 +698,13 @@ def _forward_impl_body(model, x: torch.Tensor, keep: bool):
         dnorm = dec.blocks[depth - 1 - l].conv_specs()[0].norm
         bs = _block_fwd(blk, cur, skip, out_stats=_FUSE_STATS and _FUSE_CONCAT_STATS and _norm_is_live(dnorm), in_partials=cur_part)
         pooled = ops.new_act(N, D // f[0], H // f[1], W // f[2], blk.out_channels, dev, adt)
-        lvl = {"cat": cat, "skip": skip, "bs": bs, "f": f, "c_up": c_up}
+        lv = Level(cat, skip, bs, f, c_up)
         if floor:
             # model.check_shape = False and a size the factor does not divide: nn.MaxPool3d drops the remainder.  The pooling
             # kernels take whole windows, so they get a dense copy of the covered sub-volume (not the fast path; the
             # decoder then crops this level's skip tensor, reference Decoder._crop)
-            lvl["floor_sub"] = skip[:, :D // f[0] * f[0], :H // f[1] * f[1], :W // f[2] * f[2]].contiguous()
-            ops.maxpool_fwd(lvl["floor_sub"], pooled, f)
+            lv.floor_sub = skip[:, :D // f[0] * f[0], :H // f[1] * f[1], :W // f[2] * f[2]].contiguous()
+            ops.maxpool_fwd(lv.floor_sub, pooled, f)
             cur_part = None
         else:
             # the statistics of the pooled tensor (norm of the next block's first conv) as a by-product of the pooling pass
@@ -882,24 +714,23 @@ def _forward_impl_body(model, x: torch.Tensor, keep: bool):
             else:
                 ops.maxpool_fwd(skip, pooled, f)
                 cur_part = None
-        st["levels"].append(lvl)
+        levels.append(lv)
         cur = pooled
     _, D, H, W, _ = cur.shape
     base_out = ops.new_act(N, D, H, W, model.base.out_channels, dev, adt)
-    st["base"] = _block_fwd(model.base, cur, base_out, in_partials=cur_part)
+    base = _block_fwd(model.base, cur, base_out, in_partials=cur_part)
     cur = base_out
-    st["dec"] = []
     for i in range(depth):
-        lv = st["levels"][depth - 1 - i]
+        lv = levels[depth - 1 - i]
         sampler, blk = dec.samplers[i], dec.blocks[i]
         f = _f3(dec.scale_factors[i], dim)
-        if f != lv["f"]:
+        if f != lv.f:
             raise ValueError("decoder scale factors must mirror the encoder's")
         sspec = ConvSpec(sampler.conv, None)
         _, d, h, w, _ = cur.shape
         t = ops.new_act(N, d, h, w, sspec.cout, dev, adt)
         _conv(sspec, cur, t)                       # 1x1 conv at low resolution ...
-        cat = lv["cat"]
+        cat = lv.cat
         up_sp, sk_sp = (d * f[0], h * f[1], w * f[2]), tuple(cat.shape[1:4])
         cropped = up_sp != sk_sp
         if cropped:
@@ -913,56 +744,56 @@ def _forward_impl_body(model, x: torch.Tensor, keep: bool):
                                    f"skip connection {sk_sp} (Decoder._crop removes (difference // 2) per side, which only "
                                    "fits even differences; the reference fails in torch.cat the same way)")
             off = [v // 2 for v in diff]
-            cat = ops.new_act(N, up_sp[0], up_sp[1], up_sp[2], lv["cat"].shape[4], dev, adt)
-            cat[..., lv["c_up"]:] = lv["skip"][:, off[0]:off[0] + up_sp[0], off[1]:off[1] + up_sp[1], off[2]:off[2] + up_sp[2]]
-            lv["cat_c"], lv["crop"] = cat, off
+            cat = ops.new_act(N, up_sp[0], up_sp[1], up_sp[2], lv.cat.shape[4], dev, adt)
+            cat[..., lv.c_up:] = lv.skip[:, off[0]:off[0] + up_sp[0], off[1]:off[1] + up_sp[1], off[2]:off[2] + up_sp[2]]
+            lv.cat_c, lv.crop = cat, off
         # statistics of the concat for the block's first norm without reading it: the skip half's partial sums were
         # written by the encoder conv that produced it, the upsampled half's come out of the upsampling kernel (factor 2:
         # ops.upsample_fwd(stats=True)) or follow from the low-resolution t (sum y = sum (U^T 1) t, sum y^2 = sum t (U^T U t):
         # ops.upsample_stats)
         p2 = None
-        skip_part = None if cropped else lv["bs"].get("out_part")
+        skip_part = None if cropped else lv.bs.out_part
         want_stats = False
         if skip_part is not None:
             na = blk.conv_specs()[0].norm_args()
             cpg = cat.shape[4] // na[0]
-            want_stats = lv["c_up"] % cpg == 0 and ops.upsample_stats_ok(t)
-        up_part = ops.upsample_fwd(t, _half(cat, lv["c_up"], 0), f, stats=want_stats)  # ... interpolated straight into the concat buffer
+            want_stats = lv.c_up % cpg == 0 and ops.upsample_stats_ok(t)
+        up_part = ops.upsample_fwd(t, _half(cat, lv.c_up, 0), f, stats=want_stats)  # ... interpolated straight into the concat buffer
         out = ops.new_act(N, cat.shape[1], cat.shape[2], cat.shape[3], blk.out_channels, dev, adt)
         if want_stats:
             p2 = (up_part if up_part is not None else ops.upsample_stats(t, f), skip_part[0])
         bs = _block_fwd(blk, cat, out, in_partials2=p2)
-        st["dec"].append({"low": cur, "sspec": sspec, "bs": bs, "f": f, "out": out, "t": t})
+        stages.append(DecStage(cur, sspec, bs, f, out, t))
         cur = out
-    st["last"] = cur
     act = fused_activation(model.final_activation) if model.final_activation is not None else None
-    st["act"] = act
+
+    def step(y, ospec=None, side=None):
+        return Step(levels, stages, base, cur, act, y, dim, tuple(x.shape), ospec, side) if keep else None
+
     if isinstance(model.out_conv, nn.ModuleList):
         # return_side_outputs (reference model/unet.py:211-228): a 1x1 conv (+ activation) on every decoder level
         if act == "sigmoid" and any(c is None for c in model.out_conv):
             raise NotImplementedError("final Sigmoid without out_conv is not supported")
-        st["side"] = []
+        side = []
         for i, conv in enumerate(model.out_conv):
             if conv is None:
                 raise NotImplementedError("side outputs without an output convolution are not supported")
-            feat = st["dec"][i]["out"]
+            feat = stages[i].out
             ospec = ConvSpec(conv, None)
             yi = ops.new_act(N, feat.shape[1], feat.shape[2], feat.shape[3], ospec.cout, dev)
             _conv(ospec, feat, yi, act=act)
-            st["side"].append({"ospec": ospec, "y": yi})
-        st["y"] = st["side"][-1]["y"]
-        return [sd["y"] for sd in st["side"]][::-1], (st if keep else None)  # full resolution first
+            side.append(SideOut(ospec, yi))
+        return [sd.y for sd in side][::-1], step(side[-1].y, side=side)  # full resolution first
+    ospec = None
     if model.out_conv is not None:
         ospec = ConvSpec(model.out_conv, None)
         y = ops.new_act(N, cur.shape[1], cur.shape[2], cur.shape[3], ospec.cout, dev)
         _conv(ospec, cur, y, act=act)
-        st["ospec"] = ospec
     else:
         y = cur if cur.dtype == torch.float32 else cur.float()   # the prediction is fp32 in every mode
         if act == "sigmoid":
             raise NotImplementedError("final Sigmoid without out_conv is not supported")
-    st["y"] = y
-    return y, (st if keep else None)
+    return y, step(y, ospec)
 
 
 def _to_logical(y5: torch.Tensor, dim: int) -> torch.Tensor:
@@ -981,28 +812,26 @@ def _from_logical(g: torch.Tensor, dim: int) -> torch.Tensor:
     return ops.nchw_to_nhwc(g.contiguous())
 
 
-def _backward_impl(model, st, gy: torch.Tensor, params: List[torch.Tensor], need_input_grad: bool):
-    dim = st["dim"]
-    depth = len(st["levels"])
+def _backward_impl(model, st: Step, gy: torch.Tensor, params: List[torch.Tensor], need_input_grad: bool):
+    dim = st.dim
+    depth = len(st.levels)
     grads = _Grads(params)
-    gy_dev = params[0].device if params else (gy[0] if isinstance(gy, (list, tuple)) else gy).device
     sync = getattr(model, "_tem_grad_sync", None)  # data-parallel gradient exchange (multi_gpu_training.DDP)
 
     def stage_done():
         if sync is not None:
-            _join_side(gy_dev)  # the weight gradients of this stage run on the side stream
             for lo, hi in grads.take_new_ranges():
                 sync.ready(grads.flat, lo, hi)
 
-    side = st.get("side")
+    side, ospec = st.side, st.ospec
     side_g = None
     if side is not None:
         # gy: gradients of the side outputs, full resolution first -> decoder order (coarse .. fine)
         side_g = list(gy)[::-1]
         gy = side_g[-1]
-        st = dict(st, ospec=side[-1]["ospec"])
+        ospec = side[-1].ospec
         if gy is None:
-            gy = torch.zeros_like(_to_logical(side[-1]["y"], dim))
+            gy = torch.zeros_like(_to_logical(side[-1].y, dim))
 
     def side_grad(i, feat):
         """dL/d(decoder level i output) through its side conv (ReLU-masked like every gradient of a block output)."""
@@ -1010,92 +839,88 @@ def _backward_impl(model, st, gy: torch.Tensor, params: List[torch.Tensor], need
         if gi is None:
             return None
         gs = _from_logical(gi.float(), dim)
-        if st["act"] is not None:
-            gs = ops.act_bwd(gs, side[i]["y"], st["act"])
+        if st.act is not None:
+            gs = ops.act_bwd(gs, side[i].y, st.act)
         out = torch.empty_like(feat)
-        _dgrad(side[i]["ospec"], gs, out, ref=feat)
-        _wgrad(side[i]["ospec"], feat, gs, grads)
+        _dgrad(side[i].ospec, gs, out, ref=feat)
+        _wgrad(side[i].ospec, feat, gs, grads)
         return out
 
     g = _from_logical(gy.float(), dim)
-    y = st["y"]
-    if st["act"] is not None:
-        g = ops.act_bwd(g, y, st["act"])
-    last = st["last"]
-    if "ospec" in st:
-        g_cur = torch.empty_like(last)
-        osp = st["ospec"]
-        if _FUSE_OUT_BWD and not _FORCE_GENERIC and not _OVERLAP_WGRAD and osp.k == (1, 1, 1) and osp.conv.weight.is_contiguous() and \
-                ops.conv1x1_out_bwd_ok(osp.cin, osp.cout):
+    if st.act is not None:
+        g = ops.act_bwd(g, st.y, st.act)
+    last = st.last
+    g_cur = torch.empty_like(last)
+    g_amax = None    # max |g_cur| from the kernel that wrote g_cur (_amax_slot), None once g_cur is modified
+    if ospec is not None:
+        if _FUSE_OUT_BWD and not _FORCE_GENERIC and ospec.k == (1, 1, 1) and ospec.conv.weight.is_contiguous() and \
+                ops.conv1x1_out_bwd_ok(ospec.cin, ospec.cout):
             # weight / bias gradient of out_conv and its masked data gradient in one pass over `last`
-            rq = _output_amax(grads, g_cur)
-            ops.conv1x1_out_bwd(last, g, osp.conv.weight, g_cur, grads.view(osp.conv.weight),
-                                grads.view(osp.conv.bias) if osp.conv.bias is not None else None, out_amax=rq.slot)
-            rq.done(True)
+            g_amax = _amax_slot(grads)
+            ops.conv1x1_out_bwd(last, g, ospec.conv.weight, g_cur, grads.view(ospec.conv.weight),
+                                grads.view(ospec.conv.bias) if ospec.conv.bias is not None else None, out_amax=g_amax)
         else:
-            _dgrad(osp, g, g_cur, ref=last, grads=grads)
-            _wgrad(osp, last, g, grads)
+            _, g_amax = _dgrad(ospec, g, g_cur, ref=last, grads=grads)
+            _wgrad(ospec, last, g, grads)
     else:
-        g_cur = torch.empty_like(last)
         ops.maxpool_bwd(g.to(last.dtype), last, g_cur, (1, 1, 1), relu_mask=True)
+    g_skip, g_skip_coef = [None] * depth, [None] * depth   # per level: the decoder's gradient of the skip tensor
     for i in reversed(range(depth)):
-        d = st["dec"][i]
-        lv = st["levels"][depth - 1 - i]
-        g_cat = _like(lv.get("cat_c", lv["cat"]))
-        coef = _block_bwd(d["bs"], g_cur, g_cat, grads, defer_input_norm="crop" not in lv)
-        low, sspec = d["low"], d["sspec"]
+        d = st.dec[i]
+        l = depth - 1 - i
+        lv = st.levels[l]
+        g_cat = _like(lv.cat if lv.crop is None else lv.cat_c)
+        coef = _block_bwd(d.bs, g_cur, g_amax, g_cat, grads, defer_input_norm=lv.crop is None)
+        low, sspec = d.low, d.sspec
         g_t = ops.new_act(low.shape[0], low.shape[1], low.shape[2], low.shape[3], sspec.cout, low.device, low.dtype)
-        ops.upsample_bwd(_half(g_cat, lv["c_up"], 0), g_t, d["f"],
-                         norm=None if coef is None else (d["t"], coef[:, :lv["c_up"]]))
-        lv["g_skip_coef"] = None if coef is None else coef[:, lv["c_up"]:]
+        ops.upsample_bwd(_half(g_cat, lv.c_up, 0), g_t, d.f,
+                         norm=None if coef is None else (d.t, coef[:, :lv.c_up]))
+        g_skip_coef[l] = None if coef is None else coef[:, lv.c_up:]
         g_low = torch.empty_like(low)
-        _dgrad(sspec, g_t, g_low, ref=low, grads=grads)  # `low` is the ReLU output of the previous block
+        _, g_amax = _dgrad(sspec, g_t, g_low, ref=low, grads=grads)  # `low` is the ReLU output of the previous block
         _wgrad(sspec, low, g_t, grads)
         if side is not None and i > 0:
             extra = side_grad(i - 1, low)  # `low` is decoder level i-1's output
             if extra is not None:
                 g_low.add_(extra)
-                g_low._tem_amax = None   # rewritten: the producer's max |g_low| no longer holds
-        lv["g_skip"] = _half(g_cat, lv["c_up"], 1)
-        if "crop" in lv:   # the adjoint of the centre crop: zeros around the gradient of the cropped window
-            o, sk = lv["crop"], lv["skip"]
+                g_amax = None
+        g_skip[l] = _half(g_cat, lv.c_up, 1)
+        if lv.crop is not None:   # the adjoint of the centre crop: zeros around the gradient of the cropped window
+            o, sk = lv.crop, lv.skip
             gs = torch.zeros(sk.shape, dtype=sk.dtype, device=sk.device)
-            gs[:, o[0]:o[0] + g_cat.shape[1], o[1]:o[1] + g_cat.shape[2], o[2]:o[2] + g_cat.shape[3]] = lv["g_skip"]
-            lv["g_skip"] = gs
+            gs[:, o[0]:o[0] + g_cat.shape[1], o[1]:o[1] + g_cat.shape[2], o[2]:o[2] + g_cat.shape[3]] = g_skip[l]
+            g_skip[l] = gs
         g_cur = g_low
         stage_done()
-    bb = st["base"]
-    g_pooled = torch.empty_like(bb["xin"])
+    g_pooled = torch.empty_like(st.base.xin)
     # the input of this block (and of every encoder block below level 0) is a max-pooled tensor: the backward of its
     # first norm is applied by the max-pool backward that consumes the gradient (it recomputes the pooled value anyway)
-    pool_coef = _block_bwd(bb, g_cur, g_pooled, grads, defer_input_norm=True)
+    pool_coef = _block_bwd(st.base, g_cur, g_amax, g_pooled, grads, defer_input_norm=True)
     g_cur = g_pooled
     stage_done()
     for l in reversed(range(depth)):
-        lv = st["levels"][l]
-        skip = lv["skip"]
+        lv = st.levels[l]
+        skip = lv.skip
         g_skip_full = ops.new_act(skip.shape[0], skip.shape[1], skip.shape[2], skip.shape[3], skip.shape[4],
                                   skip.device, skip.dtype)
-        if "floor_sub" in lv:
+        if lv.floor_sub is not None:
             # remainder voxels outside every pooling window only receive the (zero-padded, cropped) decoder gradient
-            sub = lv["floor_sub"]
+            sub = lv.floor_sub
             g_sub = torch.empty_like(sub)
-            ops.maxpool_bwd(g_cur, sub, g_sub, lv["f"], gy_coef=pool_coef)
-            g_skip_full.copy_(lv["g_skip"])
+            ops.maxpool_bwd(g_cur, sub, g_sub, lv.f, gy_coef=pool_coef)
+            g_skip_full.copy_(g_skip[l])
             g_skip_full[:, :sub.shape[1], :sub.shape[2], :sub.shape[3]] += g_sub
             g_skip_full.mul_(skip > 0)
+            g_amax = None
         else:
-            rq = _output_amax(grads, g_skip_full)
-            ops.maxpool_bwd(g_cur, skip, g_skip_full, lv["f"], gskip=lv["g_skip"], relu_mask=True,
-                            gskip_coef=lv.get("g_skip_coef"), gy_coef=pool_coef, out_amax=rq.slot)
-            rq.done(True)
+            g_amax = _amax_slot(grads)
+            ops.maxpool_bwd(g_cur, skip, g_skip_full, lv.f, gskip=g_skip[l], relu_mask=True,
+                            gskip_coef=g_skip_coef[l], gy_coef=pool_coef, out_amax=g_amax)
         need_in = (l > 0) or need_input_grad
-        xin = lv["bs"]["xin"]
-        g_in = torch.empty_like(xin) if need_in else None
-        pool_coef = _block_bwd(lv["bs"], g_skip_full, g_in, grads, defer_input_norm=l > 0)
+        g_in = torch.empty_like(lv.bs.xin) if need_in else None
+        pool_coef = _block_bwd(lv.bs, g_skip_full, g_amax, g_in, grads, defer_input_norm=l > 0)
         g_cur = g_in
         stage_done()
-    _join_side(gy_dev)  # the optimizer (main stream) reads every weight gradient
     if sync is not None:
         sync.finish(grads.flat)
     gx = None

@@ -29,6 +29,7 @@ import numpy as np
 import torch
 
 from .. import _lib, ops
+from ..model import pack
 from ..transform.raw import standardize
 
 
@@ -172,8 +173,7 @@ class _Setup:
             else:
                 from copy import deepcopy
                 copy = deepcopy(model)
-                for mod in copy.modules():   # the packed weights are device buffers of the source model: the copy builds its own
-                    mod.__dict__.pop("_tem_pack", None)
+                pack.forget(copy)   # the packed weights are device buffers of the source model: the copy builds its own
                 self.models.append(copy.to(d))
         # Every worker runs on a stream of its own, and a fresh torch.cuda.Stream does not wait for anything: whatever the
         # CALLER still has in flight on its current stream of a device (the peer copies just above, an optimizer step or a
