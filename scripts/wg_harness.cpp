@@ -9,9 +9,6 @@
 #include "../torch_em_amd/csrc/tem_common.h"
 #include "../torch_em_amd/csrc/conv_internal.h"
 #include "../torch_em_amd/csrc/tem_act.h"
-#ifdef TEM_ZS_TRACE
-void tem_zs_trace_read(unsigned long long* dst);
-#endif
 #ifdef TEM_TR_TRACE
 void tem_tr_trace_read(unsigned long long* dst);
 #endif
@@ -125,20 +122,6 @@ int main(int argc, char** argv) {
                 printf("  %2d: %6lld %6lld %6lld   %6lld\n", it, (long long)(t[1] - t[0]), (long long)(t[2] - t[1]), (long long)(t[3] - t[2]),
                        (long long)(t[0] - tp[0]));
             }
-        }
-    }
-#endif
-#ifdef TEM_ZS_TRACE
-    std::vector<unsigned long long> tr(8 * 64 * 8);
-    tem_zs_trace_read(tr.data());
-    const unsigned long long base = tr[0];
-    for (int wv : {0, 1, 4, 7}) {
-        printf("wave %d: iter   mfma  stores  loads  barrier   (shader cycles)\n", wv);
-        for (int it = 0; it < 24; ++it) {
-            const unsigned long long* t = &tr[(wv * 64 + it) * 8];
-            if (!t[0]) break;
-            printf("  %2d @%8llu: %6lld %6lld %6lld %6lld\n", it, t[0] - base, (long long)(t[1] - t[0]), (long long)(t[2] - t[1]),
-                   (long long)(t[3] - t[2]), (long long)(t[4] - t[3]));
         }
     }
 #endif

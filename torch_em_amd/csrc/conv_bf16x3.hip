@@ -11,11 +11,9 @@
 #include <set>
 #include "conv_internal.h"
 
-#ifndef TEM_SPLIT_N
-#define TEM_SPLIT_N 1  // NR == 2 workgroups: waves tiled 2 (voxel halves) x 2 (column tiles) instead of 4 x (64 voxels, 64 columns)
-#endif
+// ---- tunables (numbers; variant builds override them with -D) ----
 #ifndef TEM_SC_RD
-#define TEM_SC_RD 1   // weight ring depth of that kernel (must divide the tap count: 1, 3 or 9); 3 spills 11 VGPRs: +1.5 % step time
+#define TEM_SC_RD 1   // weight ring depth of the fp16x3 forward kernel (must divide the tap count: 1, 3 or 9); 3 spills 11 VGPRs: +1.5 % step time
 #endif
 #ifndef TEM_X3_RD1
 #define TEM_X3_RD1 3   // bf16x3 kernel (dgrad / no-grad forward), 32-column tiles
@@ -26,34 +24,16 @@
 #ifndef TEM_SC2_RD
 #define TEM_SC2_RD 3
 #endif
-#ifndef TEM_SETPRIO
-#define TEM_SETPRIO 0
-#endif
-#ifndef TEM_ZS_NT
-#define TEM_ZS_NT 0
-#endif
-typedef float floatx4n __attribute__((ext_vector_type(4)));
-__device__ __forceinline__ float4 ld4_nt(const float* p) {
-    floatx4n v = __builtin_nontemporal_load(reinterpret_cast<const floatx4n*>(p));
-    return make_float4(v.x, v.y, v.z, v.w);
-}
-#if TEM_ZS_NT
-#define ZS_GLOAD(p) ld4_nt(p)
-#else
-#define ZS_GLOAD(p) (*reinterpret_cast<const float4*>(p))
-#endif
-#ifndef TEM_NT_STORE
-#define TEM_NT_STORE 1   // epilogue stores bypass the write-allocate path: the output is not re-read by this kernel (-0.3 ms/step)
-#endif
 #ifndef TEM_SC_WPC
 #define TEM_SC_WPC 3   // resident workgroups per CU of the fp16x3 forward kernel with 32-column tiles
-#endif
-#ifndef TEM_SC_CLAMP
-#define TEM_SC_CLAMP 1
 #endif
 #ifndef TEM_NS1_WPC
 #define TEM_NS1_WPC 4  // resident workgroups per CU of the single-product (mixed precision) forward kernel
 #endif
+#ifndef TEM_ZS_MIN_D
+#define TEM_ZS_MIN_D 8   // shortest z column of the z-sliding kernels (16 until round 4: a column of 8 .. 15 planes pays six priming
+#endif                   // iterations for its planes and still beats the patch kernel; k_conv_wgrad_zs is wrong below 8)
+// ---- harness instruments (default off; wrong results when set): none in this file ----
 
 #include "conv_split.h"
 #include "tem_act.h"
@@ -319,7 +299,7 @@ __global__ __launch_bounds__(256, NS == 1 ? TEM_NS1_WPC : (F16 && NR == 1) ? TEM
     // (NR == 2) the waves are arranged 2 (voxel halves) x 2 (column tiles): a wave owns 4 M-tiles x 1 column tile, so it
     // loads HALF the weight fragments per MFMA and reads twice the A fragments from LDS instead (LDS reads are not the
     // limiter: serving the three tx taps from one read changed nothing).  NR == 1: 4 waves x (2 M-tiles x 1 tile).
-    constexpr bool SN = (NR == 2) && TEM_SPLIT_N;
+    constexpr bool SN = NR == 2;   // waves tiled 2 (voxel halves) x 2 (column tiles) instead of 4 x (64 voxels, 64 columns)
     constexpr int MT = SN ? 4 : 2;             // M-tiles (32 voxels) per wave
     constexpr int NW = SN ? 1 : NR;            // column tiles per wave
     static_assert(TZ * TY * TX == 256, "patch must hold 256 voxels");
@@ -423,7 +403,7 @@ __global__ __launch_bounds__(256, NS == 1 ? TEM_NS1_WPC : (F16 && NR == 1) ? TEM
 #pragma unroll
                     for (int c = 0; c < 4; ++c) e[c] *= F16_A_PRESCALE;
                 }
-                if (F16 && TEM_SC_CLAMP) {
+                if (F16) {
                     // an activation beyond the fp16 range (|x^| > 6e4 after the norm: not a training state) saturates
                     // instead of turning the whole receptive field into NaN
 #pragma unroll
@@ -452,7 +432,6 @@ __global__ __launch_bounds__(256, NS == 1 ? TEM_NS1_WPC : (F16 && NR == 1) ? TEM
 
         int ts = tapstride;
         asm volatile("" : "+s"(ts));
-        if (TEM_SETPRIO) __builtin_amdgcn_s_setprio(TEM_SETPRIO);
 #pragma unroll
         for (int tap = 0; tap < NT; ++tap) {
             const int tz = tap / (KH * KW), ty = (tap / KW) % KH, tx = tap % KW;
@@ -504,7 +483,6 @@ __global__ __launch_bounds__(256, NS == 1 ? TEM_NS1_WPC : (F16 && NR == 1) ? TEM
                         }
                 }
         }
-        if (TEM_SETPRIO) __builtin_amdgcn_s_setprio(0);
     }
 
     if (SC) {
@@ -553,10 +531,8 @@ __global__ __launch_bounds__(256, NS == 1 ? TEM_NS1_WPC : (F16 && NR == 1) ? TEM
                         const T ot = (T)o;
                         o = (float)ot;
                         y[v * y_ld + co] = ot;
-                    } else if (TEM_NT_STORE)
+                    } else   // bypasses the write-allocate path: the output is not re-read by this kernel (-0.3 ms/step)
                         __builtin_nontemporal_store(o, y + v * y_ld + co);
-                    else
-                        y[v * y_ld + co] = o;
                     ssum[nn] += o;
                     ssq[nn] = fmaf(o, o, ssq[nn]);
                 }
@@ -1025,16 +1001,7 @@ __global__ __launch_bounds__(256, 1) void k_conv_wgrad_bf16x3(const TS* __restri
 //   * ONE barrier per plane; a column accumulates over up to D planes, so far fewer partial slabs are written.
 // Ring slot of plane z is (z + 4) & 3; planes -1 and D are stored as zeros (padding applies after the pre-norm).
 // ---------------------------------------------------------------------------
-#ifndef TEM_ZS_BALANCE
-#define TEM_ZS_BALANCE 1   // z-sliding wgrad: units 16, 17 cut in halves over waves 0..3 (4.5 units per SIMD instead of 5/5/4/4)
-#endif
 #define ZS_NPL 4
-#ifndef TEM_ZS_LD_AUX
-#define TEM_ZS_LD_AUX 0   // cache policy of the x / g plane loads (2 = nt: measured +0.03 ms / step, not used)
-#endif
-#ifndef TEM_ZS_L2HIT
-#define TEM_ZS_L2HIT 0   // harness only: loads of all planes hit the first four (L2-resident) planes; wrong results
-#endif
 #define ZS_PLB 320                       // bytes per ci per plane: 10 halo rows x 32 B (16 bf16 slots, 10 used)
 #define ZS_CIS (ZS_NPL * ZS_PLB + 16)    // bytes per ci (padded like the patch kernel: conflict-free b128 reads)
 #define ZS_GS 144                        // bytes per co row of one g plane: 64 bf16 + 16 pad
@@ -1046,7 +1013,7 @@ __device__ __forceinline__ zs_rsrc_t zs_rsrc(const void* base) {
     return __builtin_amdgcn_make_buffer_rsrc(const_cast<void*>(base), 0, 0x7fffffff, 0x00020000);
 }
 __device__ __forceinline__ float4 zs_load4(zs_rsrc_t r, unsigned voff, unsigned soff) {
-    const zs_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, TEM_ZS_LD_AUX);
+    const zs_u4 v = __builtin_amdgcn_raw_buffer_load_b128(r, voff, soff, 0);
     const zs_f4 f = __builtin_bit_cast(zs_f4, v);   // whole-vector cast (element-wise bit casts get the load narrowed, conv_pp.hip)
     return make_float4(f.x, f.y, f.z, f.w);
 }
@@ -1114,8 +1081,8 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_zs(const float* __restric
     // after two rounds (16, 17) are therefore cut in halves along their k-slabs: waves 0 and 2 each take half the slabs of
     // unit 16, waves 1 and 3 of unit 17 -- 4.5 units per SIMD -- and the partial accumulators of waves 2, 3 are added to
     // those of waves 0, 1 through LDS once, before the slabs are written.
-    const int sh2 = TEM_ZS_BALANCE ? (wv >> 1) & 1 : 0;   // which half of the third unit's slabs
-    if (TEM_ZS_BALANCE) {
+    const int sh2 = (wv >> 1) & 1;   // which half of the third unit's slabs
+    {
         const int u = 16 + (wv & 1);
         uok[MAXU - 1] = wv < 4;
         urg[MAXU - 1] = u % NRG;
@@ -1199,7 +1166,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_zs(const float* __restric
                 const int xbase = r * ZS_CIS + (tz == 0 ? slot[0] : (tz == 1 ? slot[1] : slot[2])) + ty * 32;
 #pragma unroll
                 for (int sl = 0; sl < SPU; ++sl) {
-                    if (TEM_ZS_BALANCE && i == MAXU - 1 && (sl / (SPU / 2)) != sh2) continue;   // the other wave's slabs
+                    if (i == MAXU - 1 && (sl / (SPU / 2)) != sh2) continue;   // the other wave's slabs
                     const int prow = 2 * (sl0 + sl) + kh;  // this lane half's patch row (0..7)
                     const int goff = (ct * 32 + r) * ZS_GS + prow * 16;
                     const int xoff = xbase + prow * 32;
@@ -1324,7 +1291,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_zs(const float* __restric
             xa = make_float4(0.f, 0.f, 0.f, 0.f);
             xb = xa;
             if (zxok) {
-                const zs_rsrc_t rsx = zs_rsrc(xn + (TEM_ZS_L2HIT ? (zx & 3) : zx) * xplane);   // (harness experiment: every column reads the first planes)
+                const zs_rsrc_t rsx = zs_rsrc(xn + zx * xplane);
                 if (okxa) xa = zs_load4(rsx, offx, 0);
                 if (okxb) xb = zs_load4(rsx, offxb, 0);
             }
@@ -1332,7 +1299,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_zs(const float* __restric
             ga = make_float4(0.f, 0.f, 0.f, 0.f);
             gb = ga;
             if (zg >= za && zg < zb) {
-                const zs_rsrc_t rsg = zs_rsrc(gn + (TEM_ZS_L2HIT ? (zg & 3) : zg) * gplane);
+                const zs_rsrc_t rsg = zs_rsrc(gn + zg * gplane);
                 if (okga) ga = zs_load4(rsg, offg, 0);
                 if (okgb) gb = zs_load4(rsg, offgb, 0);
             }
@@ -1363,7 +1330,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_zs(const float* __restric
         }
     }
     // ---- the halves of units 16 / 17: waves 2, 3 hand their partial sums to waves 0, 1 ----
-    if (TEM_ZS_BALANCE) {
+    {
         __syncthreads();
         float* xch = reinterpret_cast<float*>(ldsb);   // [2][KW][16][64]
         if (wv == 2 || wv == 3) {
@@ -1724,9 +1691,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_wgrad_zt(const float* __restric
     }
 }
 
-#ifndef TEM_ZS_MIN_D
-#define TEM_ZS_MIN_D 8   // shortest z column of the z-sliding kernels (16 until round 4: a column of 8 .. 15 planes pays six priming
-#endif                   // iterations for its planes and still beats the patch kernel; k_conv_wgrad_zs is wrong below 8)
 struct ZsPlan {
     bool use;
     bool teams;   // k_conv_wgrad_zt (staging team) instead of k_conv_wgrad_zs

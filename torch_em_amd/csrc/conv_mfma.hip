@@ -27,30 +27,11 @@
 
 typedef float floatx16 __attribute__((ext_vector_type(16)));
 
-#ifndef TEM_MF_RD
-#define TEM_MF_RD 0      // weight ring depth of the forward kernels (0: 3 for 32-column tiles, 2 for 64-column tiles)
-#endif
-#ifndef TEM_MF_KOUTER
-#define TEM_MF_KOUTER 1  // MFMA order inside a k-group: k-step outermost (1) or the four k-steps of one accumulator back to back (0, rounds 1-5)
-#endif
-#ifndef TEM_MF_APF
-#define TEM_MF_APF 1     // A fragments of k-group g + 1 are requested before the MFMAs of k-group g
-#endif
-#ifndef TEM_MF_EARLY_HALO
-#define TEM_MF_EARLY_HALO 0   // persistent forward kernel: the next step's halo is requested in front of the first k-group (1) or behind the last
-                              // ring load of the step (0).  Measured (profiles/r06_fp32_variants.txt): early is SLOWER (0.646 against 0.631 ms per
-                              // launch) -- vmcnt counts in order, so every wait for a ring load issued after the prefetch waits for the ten
-                              // HBM loads in front of it; deeper rings (6 / 9 k-groups of cover) do not buy it back
-#endif
-#ifndef TEM_MF_RD1
-#define TEM_MF_RD1 0     // persistent kernel, 32-column tiles: weight ring depth (0: as TEM_MF_RD)
-#endif
-#ifndef TEM_MF_RD2
-#define TEM_MF_RD2 0     // persistent kernel, 64-column tiles
-#endif
+// ---- tunables (numbers; variant builds override them with -D) ----
 #ifndef TEM_MF_OCC2
 #define TEM_MF_OCC2 2    // workgroups per CU of the 64-column instantiations
 #endif
+// ---- harness instruments (default off; wrong results when set): none in this file ----
 #define CK 16      // input channels per staged chunk (fwd)
 #define LSF 20     // LDS floats per halo voxel (16 + 4 pad -> 80 B, keeps b128 alignment)
 
@@ -61,12 +42,9 @@ typedef float floatx16 __attribute__((ext_vector_type(16)));
 // (SQ_LDS_BANK_CONFLICT = 65 % of SQ_LDS_IDX_ACTIVE, profiles/r06_pmc_stalls_fp32.txt).  Rows y and y + 4 are 8 quads apart --
 // exactly the complement -- so the lanes are numbered such that every service group holds the two complete x-rows y, y + 4
 // (conv_zr.hip uses the same lane numbering for its footprint).  8 x 8 (y, x) shares only; other tiles keep lane order.
-#ifndef TEM_MF_LANEMAP
-#define TEM_MF_LANEMAP 1
-#endif
 template <int TY, int TX>
 __device__ __forceinline__ int mf_row_voxel(int m, int row) {
-    if constexpr (TY == 8 && TX == 8 && TEM_MF_LANEMAP) {
+    if constexpr (TY == 8 && TX == 8) {
         const int vu = (int)((0x73261540u >> (4 * (row >> 2))) & 7u) * 4 + (row & 3);   // service group -> two complete rows
         const int t = vu >> 3;                                                          // 0..3 -> y rows 0, 4, 1, 5 (+ 2 m)
         return ((t >> 1) + 4 * (t & 1) + 2 * m) * 8 + (vu & 7);
@@ -74,6 +52,9 @@ __device__ __forceinline__ int mf_row_voxel(int m, int row) {
         return m * 32 + row;
     }
 }
+
+// component c (compile-time after unrolling) of a fragment
+__device__ __forceinline__ float mf_comp(const float4& q, int c) { return c == 0 ? q.x : (c == 1 ? q.y : (c == 2 ? q.z : q.w)); }
 
 __device__ __forceinline__ float act_apply(float v, int act) {
     if (act == TEM_ACT_RELU) return v > 0.f ? v : 0.f;
@@ -217,7 +198,7 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : (NR == 2 ? TEM_MF_OCC2 : 3))
     const int chunk_begin = ks * cpk, chunk_end = (ks + 1) * cpk;
     constexpr int NG = 2 * NT;                       // k-groups (8 input channels each) per chunk
     // ring depth (NG % RD == 0 keeps the phase across chunks); one k-group is 8*NR MFMAs = 512*NR cycles
-    constexpr int RD = (TEM_MF_RD && NG % TEM_MF_RD == 0) ? TEM_MF_RD : (NR == 1 && NG % 3 == 0) ? 3 : 2;
+    constexpr int RD = (NR == 1 && NG % 3 == 0) ? 3 : 2;
     const int tapstride = cin8 * 64;
     const float4* wq[NR];  // this lane's slot in the first fragment of each column tile
 #pragma unroll
@@ -273,15 +254,10 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : (NR == 2 ? TEM_MF_OCC2 : 3))
         int ts = tapstride;
         asm volatile("" : "+s"(ts));  // opaque per chunk: keeps LICM from hoisting 2*NT address pairs out of the loop
         float4 apf[2];
-        if (TEM_MF_APF) {
 #pragma unroll
-            for (int m = 0; m < 2; ++m) apf[m] = *reinterpret_cast<const float4*>(lds + abase[m]);   // tap 0, k-group 0
-        }
+        for (int m = 0; m < 2; ++m) apf[m] = *reinterpret_cast<const float4*>(lds + abase[m]);   // tap 0, k-group 0
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
-            const int tap = g >> 1, kg = g & 1;
-            const int tz = tap / (KH * KW), ty = (tap / KW) % KH, tx = tap % KW;
-            const int toff = ((tz * HY + ty) * HX + tx) * LSF;
             {   // prefetch
                 const int gp = g + RD - 1;
                 if (gp < NG) {
@@ -295,37 +271,27 @@ __global__ __launch_bounds__(NW * 64, NW == 8 ? 4 : (NR == 2 ? TEM_MF_OCC2 : 3))
                 }
                 __builtin_amdgcn_sched_barrier(0x38F);  // everything but VMEM may cross: keep the loads early
             }
-            // A fragments one k-group AHEAD (TEM_MF_APF, round 6): left to itself hipcc issues the two ds_read_b128 of a k-group one MFMA
+            // A fragments one k-group AHEAD (round 6): left to itself hipcc issues the two ds_read_b128 of a k-group one MFMA
             // before the MFMAs that consume them -- an LDS round trip in front of every 8 NR MFMAs of the wave
             float4 a[2];
-            if (TEM_MF_APF) {
 #pragma unroll
-                for (int m = 0; m < 2; ++m) a[m] = apf[m];
-                if (g + 1 < NG) {
-                    const int tap1 = (g + 1) >> 1, kg1 = (g + 1) & 1;
-                    const int toff1 = (((tap1 / (KH * KW)) * HY + (tap1 / KW) % KH) * HX + tap1 % KW) * LSF;
+            for (int m = 0; m < 2; ++m) a[m] = apf[m];
+            if (g + 1 < NG) {
+                const int tap1 = (g + 1) >> 1, kg1 = (g + 1) & 1;
+                const int toff1 = (((tap1 / (KH * KW)) * HY + (tap1 / KW) % KH) * HX + tap1 % KW) * LSF;
 #pragma unroll
-                    for (int m = 0; m < 2; ++m) apf[m] = *reinterpret_cast<const float4*>(lds + abase[m] + toff1 + kg1 * 8);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            } else {
-#pragma unroll
-                for (int m = 0; m < 2; ++m) a[m] = *reinterpret_cast<const float4*>(lds + abase[m] + toff + kg * 8);
+                for (int m = 0; m < 2; ++m) apf[m] = *reinterpret_cast<const float4*>(lds + abase[m] + toff1 + kg1 * 8);
             }
-            // k-step outermost (TEM_MF_KOUTER): consecutive MFMAs go to DIFFERENT accumulators -- a dependent v_mfma_f32_32x32x2_f32
+            __builtin_amdgcn_sched_barrier(0);
+            // k-step outermost: consecutive MFMAs go to DIFFERENT accumulators -- a dependent v_mfma_f32_32x32x2_f32
             // cannot start before its predecessor's 16 passes have written back
 #pragma unroll
-            for (int kq = 0; kq < (TEM_MF_KOUTER ? 4 : 1); ++kq)
+            for (int kq = 0; kq < 4; ++kq)
 #pragma unroll
-            for (int m = 0; m < 2; ++m)
+                for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int nn = 0; nn < NR; ++nn) {
-                    const float4 bb = bq[g % RD][nn];
-                    if (!TEM_MF_KOUTER || kq == 0) acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].x, bb.x, acc[m][nn], 0, 0, 0);
-                    if (!TEM_MF_KOUTER || kq == 1) acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].y, bb.y, acc[m][nn], 0, 0, 0);
-                    if (!TEM_MF_KOUTER || kq == 2) acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].z, bb.z, acc[m][nn], 0, 0, 0);
-                    if (!TEM_MF_KOUTER || kq == 3) acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].w, bb.w, acc[m][nn], 0, 0, 0);
-                }
+                    for (int nn = 0; nn < NR; ++nn)
+                        acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(mf_comp(a[m], kq), mf_comp(bq[g % RD][nn], kq), acc[m][nn], 0, 0, 0);
         }
     }
 
@@ -358,9 +324,8 @@ __global__ __launch_bounds__(256, NR == 1 ? 3 : TEM_MF_OCC2) void k_conv_fwd_mfm
     constexpr int NG = 2 * NT;
     // ring depth of the persistent kernel: the waits for ring loads issued BEFORE the halo prefetch are the ones that do not wait
     // for it (vmcnt counts in order), i.e. RD k-groups of cover for the prefetch
-    constexpr int RDP = NR == 1 ? TEM_MF_RD1 : TEM_MF_RD2;
-    constexpr int RD = (RDP && NG % RDP == 0) ? RDP : (TEM_MF_RD && NG % TEM_MF_RD == 0) ? TEM_MF_RD : (NR == 1 && NG % 3 == 0) ? 3 : 2;
-    constexpr int GH = TEM_MF_EARLY_HALO ? 0 : (NG - RD + 1 > 0 ? NG - RD + 1 : 0);  // k-group after whose ring issue the halo prefetch goes out
+    constexpr int RD = (NR == 1 && NG % 3 == 0) ? 3 : 2;
+    constexpr int GH = NG - RD + 1 > 0 ? NG - RD + 1 : 0;  // k-group after whose ring issue the halo prefetch goes out
     static_assert(TZ * TY * TX == 256, "patch must hold 256 voxels");
     extern __shared__ __attribute__((aligned(16))) float lds[];  // [HV][LSF]
 
@@ -402,8 +367,9 @@ __global__ __launch_bounds__(256, NR == 1 ? 3 : TEM_MF_OCC2) void k_conv_fwd_mfm
     // Halo loads of one step (raw values; the fused norm is applied at LDS-write time).  Round 6: UNCONDITIONAL buffer loads with
     // per-thread constant 32-bit offsets from the halo origin (an item outside the volume, or beyond the tile, reads with an offset
     // beyond the buffer: zeros) -- rounds 1-5 kept every load inside `if (voxel in range)`, so the compiler could not count what was
-    // in flight at the join points.  The prefetch is still issued behind the LAST weight-ring load of a step (TEM_MF_EARLY_HALO
-    // above says why not earlier); the straight-line loads alone are worth 1.7 % of the launch.  Needs the halo of a patch inside
+    // in flight at the join points.  The prefetch is still issued behind the LAST weight-ring load of a step (in front of the
+    // first k-group it was slower, 0.646 against 0.631 ms per launch: vmcnt counts in order, so every wait for a ring load issued
+    // after the prefetch waits for the ten HBM loads in front of it; profiles/r06_fp32_variants.txt); the straight-line loads alone are worth 1.7 % of the launch.  Needs the halo of a patch inside
     // 2 GiB (launcher).
     constexpr unsigned OOB = 0x80000000u;
     unsigned hoff[NIT];
@@ -511,15 +477,10 @@ __global__ __launch_bounds__(256, NR == 1 ? 3 : TEM_MF_OCC2) void k_conv_fwd_mfm
         const int64_t wo_n = (int64_t)(n_cot * NR) * NT * cin8 * 64 + (int64_t)n_chunk * 128;
         const int64_t wnn = (int64_t)NT * cin8 * 64;
         float4 apf[2];
-        if (TEM_MF_APF) {
 #pragma unroll
-            for (int m = 0; m < 2; ++m) apf[m] = *reinterpret_cast<const float4*>(lds + abase[m]);   // tap 0, k-group 0
-        }
+        for (int m = 0; m < 2; ++m) apf[m] = *reinterpret_cast<const float4*>(lds + abase[m]);   // tap 0, k-group 0
 #pragma unroll
         for (int g = 0; g < NG; ++g) {
-            const int tap = g >> 1, kg = g & 1;
-            const int tz = tap / (KH * KW), ty = (tap / KW) % KH, tx = tap % KW;
-            const int toff = ((tz * HY + ty) * HX + tx) * LSF;
             {
                 const int gp = g + RD - 1;
                 if (gp < NG) {
@@ -538,37 +499,27 @@ __global__ __launch_bounds__(256, NR == 1 ? 3 : TEM_MF_OCC2) void k_conv_fwd_mfm
                 LOAD_HALO(n_n, n_z0, n_y0, n_x0, n_chunk);
                 __builtin_amdgcn_sched_barrier(0x38F);
             }
-            // A fragments one k-group AHEAD (TEM_MF_APF, round 6): left to itself hipcc issues the two ds_read_b128 of a k-group one MFMA
+            // A fragments one k-group AHEAD (round 6): left to itself hipcc issues the two ds_read_b128 of a k-group one MFMA
             // before the MFMAs that consume them -- an LDS round trip in front of every 8 NR MFMAs of the wave
             float4 a[2];
-            if (TEM_MF_APF) {
 #pragma unroll
-                for (int m = 0; m < 2; ++m) a[m] = apf[m];
-                if (g + 1 < NG) {
-                    const int tap1 = (g + 1) >> 1, kg1 = (g + 1) & 1;
-                    const int toff1 = (((tap1 / (KH * KW)) * HY + (tap1 / KW) % KH) * HX + tap1 % KW) * LSF;
+            for (int m = 0; m < 2; ++m) a[m] = apf[m];
+            if (g + 1 < NG) {
+                const int tap1 = (g + 1) >> 1, kg1 = (g + 1) & 1;
+                const int toff1 = (((tap1 / (KH * KW)) * HY + (tap1 / KW) % KH) * HX + tap1 % KW) * LSF;
 #pragma unroll
-                    for (int m = 0; m < 2; ++m) apf[m] = *reinterpret_cast<const float4*>(lds + abase[m] + toff1 + kg1 * 8);
-                }
-                __builtin_amdgcn_sched_barrier(0);
-            } else {
-#pragma unroll
-                for (int m = 0; m < 2; ++m) a[m] = *reinterpret_cast<const float4*>(lds + abase[m] + toff + kg * 8);
+                for (int m = 0; m < 2; ++m) apf[m] = *reinterpret_cast<const float4*>(lds + abase[m] + toff1 + kg1 * 8);
             }
-            // k-step outermost (TEM_MF_KOUTER): consecutive MFMAs go to DIFFERENT accumulators -- a dependent v_mfma_f32_32x32x2_f32
+            __builtin_amdgcn_sched_barrier(0);
+            // k-step outermost: consecutive MFMAs go to DIFFERENT accumulators -- a dependent v_mfma_f32_32x32x2_f32
             // cannot start before its predecessor's 16 passes have written back
 #pragma unroll
-            for (int kq = 0; kq < (TEM_MF_KOUTER ? 4 : 1); ++kq)
+            for (int kq = 0; kq < 4; ++kq)
 #pragma unroll
-            for (int m = 0; m < 2; ++m)
+                for (int m = 0; m < 2; ++m)
 #pragma unroll
-                for (int nn = 0; nn < NR; ++nn) {
-                    const float4 bb = bq[g % RD][nn];
-                    if (!TEM_MF_KOUTER || kq == 0) acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].x, bb.x, acc[m][nn], 0, 0, 0);
-                    if (!TEM_MF_KOUTER || kq == 1) acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].y, bb.y, acc[m][nn], 0, 0, 0);
-                    if (!TEM_MF_KOUTER || kq == 2) acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].z, bb.z, acc[m][nn], 0, 0, 0);
-                    if (!TEM_MF_KOUTER || kq == 3) acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(a[m].w, bb.w, acc[m][nn], 0, 0, 0);
-                }
+                    for (int nn = 0; nn < NR; ++nn)
+                        acc[m][nn] = __builtin_amdgcn_mfma_f32_32x32x2f32(mf_comp(a[m], kq), mf_comp(bq[g % RD][nn], kq), acc[m][nn], 0, 0, 0);
         }
         first = false;
         // ---- epilogue of a finished (patch, Cout tile) ----

@@ -23,24 +23,36 @@
 #include "tem_act.h"
 #include <type_traits>
 
+// ---- tunables (numbers; variant builds override them with -D) ----
 #ifndef TEM_PP_RD
 #define TEM_PP_RD 3      // weight-fragment ring depth over taps
 #endif
 #ifndef TEM_PP_PRIO
 #define TEM_PP_PRIO 1    // s_setprio of the team in its MFMA phase
 #endif
-#ifndef TEM_PP_SCHED
-#define TEM_PP_SCHED 1   // tap loop: 0 = loads of the next tap | MFMAs of this tap, pinned; 1 = one load between two MFMAs
-#endif
-#ifndef TEM_PP_LF
-#define TEM_PP_LF -1     // staging order: 1 halo loads before the epilogue, 0 after it, -1 by tile size (see LOADS_FIRST)
-#endif
 #ifndef TEM_PP_ST_AUX
 #define TEM_PP_ST_AUX 2  // cache policy of the epilogue stores: 2 = nt (the output is not re-read by this kernel), 0 = default
 #endif
+// ---- harness instruments (default off; wrong results when set) ----
 #ifndef TEM_PP_ABL
-#define TEM_PP_ABL 0     // harness-only ablations (scripts/pp_harness.cpp): 1 no halo loads, 2 no stores, 4 no weight loads in
+#define TEM_PP_ABL 0     // ablations (scripts/pp_harness.cpp): 1 no halo loads, 2 no stores, 4 no weight loads in
 #endif                   // the tap loop, 8 no split / LDS writes, 16 no MFMAs
+#ifdef TEM_PP_TRACE   // developer build (scripts/pp_harness.cpp): shader-clock stamps of the phases of one workgroup
+#ifndef TEM_PP_TRACE_BLOCK
+#define TEM_PP_TRACE_BLOCK 0
+#endif
+__device__ unsigned long long tem_pp_trace_buf[2][64][8];
+#define PP_STAMP(i)                                                                           \
+    do {                                                                                      \
+        if (blockIdx.x == TEM_PP_TRACE_BLOCK && tw == 0 && lane == 0 && s < 64)               \
+            tem_pp_trace_buf[team][s][i] = __builtin_amdgcn_s_memtime();                      \
+    } while (0)
+void tem_pp_trace_read(unsigned long long* dst) {
+    (void)hipMemcpyFromSymbol(dst, HIP_SYMBOL(tem_pp_trace_buf), sizeof(unsigned long long) * 2 * 64 * 8);
+}
+#else
+#define PP_STAMP(i)
+#endif
 
 struct PpUnit {
     int cot, n, z0, y0, x0;
@@ -73,23 +85,6 @@ __device__ __forceinline__ void pp_store4_nt(__amdgpu_buffer_rsrc_t r, unsigned 
     // after a 16-byte store on gfx950 (see zr_store4 in conv_zr.hip)
     __builtin_amdgcn_raw_buffer_store_b128(d, r, voff + soff, 0, TEM_PP_ST_AUX);
 }
-
-#ifdef TEM_PP_TRACE   // developer build (scripts/pp_harness.cpp): shader-clock stamps of the phases of one workgroup
-#ifndef TEM_PP_TRACE_BLOCK
-#define TEM_PP_TRACE_BLOCK 0
-#endif
-__device__ unsigned long long tem_pp_trace_buf[2][64][8];
-#define PP_STAMP(i)                                                                           \
-    do {                                                                                      \
-        if (blockIdx.x == TEM_PP_TRACE_BLOCK && tw == 0 && lane == 0 && s < 64)               \
-            tem_pp_trace_buf[team][s][i] = __builtin_amdgcn_s_memtime();                      \
-    } while (0)
-void tem_pp_trace_read(unsigned long long* dst) {
-    (void)hipMemcpyFromSymbol(dst, HIP_SYMBOL(tem_pp_trace_buf), sizeof(unsigned long long) * 2 * 64 * 8);
-}
-#else
-#define PP_STAMP(i)
-#endif
 
 // KD,KH,KW kernel; TZ,TY,TX voxel patch of a TEAM (TX == 8); CT 32-column tiles per team; WN waves side by side over
 // the columns (WM = 4 / WN waves over the voxels); NS planes per operand; F16: fp16 terms, lo planes stored x 2^12 and the
@@ -232,7 +227,7 @@ __global__ __launch_bounds__(512, 2) void k_conv_pp(
             bool interior = true;
             // With 2 M-tiles per wave the loads go first and fly during the epilogue; with 4 the tap loop of the partner is
             // twice as long as a staging phase, so the epilogue runs first and the 40 load registers are not live beside it.
-            constexpr bool LOADS_FIRST = TEM_PP_LF < 0 ? (MT <= 2) : (TEM_PP_LF != 0);
+            constexpr bool LOADS_FIRST = MT <= 2;
             auto issue_loads = [&]() {
                 if (scale) {
                     sc4 = *reinterpret_cast<const float4*>(scale + (int64_t)cu.n * Cin + ci * BCK + c4 * 4);
@@ -456,7 +451,6 @@ __global__ __launch_bounds__(512, 2) void k_conv_pp(
                             for (int p = 0; p < NS; ++p)
                                 bq[gp % RD][nn][p] = pp_load4u(rw, woff_lane, wsoff[nn] + (unsigned)(gp * ts + p * 64) * 16u);
                     }
-                    if (TEM_PP_SCHED == 0) __builtin_amdgcn_sched_barrier(0);
 #pragma unroll
                     for (int m = 0; m < MT; ++m)
 #pragma unroll
@@ -478,18 +472,16 @@ __global__ __launch_bounds__(512, 2) void k_conv_pp(
                                         acc[m][nn] = mfma16<F16>(af[tap & 1][m][i], bq[tap % RD][nn][sum - i], acc[m][nn]);
                                 }
                         }
-                    if (TEM_PP_SCHED == 1) {
-                        // an in-order wave issues the next tap's loads in the shadow of this tap's MFMAs only if they sit
-                        // BETWEEN them: a block of 6+ memory instructions after the last MFMA outlasts its 32 cycles
-                        constexpr int NM = MT * NW * (NS * (NS + 1) / 2), NL = MT * NS, NV = NW * NS;
+                    // one load between two MFMAs: an in-order wave issues the next tap's loads in the shadow of this tap's MFMAs
+                    // only if they sit BETWEEN them: a block of 6+ memory instructions after the last MFMA outlasts its 32 cycles
+                    constexpr int NM = MT * NW * (NS * (NS + 1) / 2), NL = MT * NS, NV = NW * NS;
 #pragma unroll
-                        for (int k = 0; k < NM; ++k) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            if (k < NL)
-                                __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                            else if (k - NL < NV)
-                                __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
-                        }
+                    for (int k = 0; k < NM; ++k) {
+                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                        if (k < NL)
+                            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
+                        else if (k - NL < NV)
+                            __builtin_amdgcn_sched_group_barrier(0x020, 1, 0);
                     }
                     __builtin_amdgcn_sched_barrier(0);
                 }

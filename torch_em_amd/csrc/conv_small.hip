@@ -7,17 +7,6 @@
 #include "conv_internal.h"
 #include "tem_act.h"
 
-#ifndef TEM_SMALL_NT
-#define TEM_SMALL_NT 0
-#endif
-template <typename T>
-__device__ __forceinline__ void ST4(T* p, float4 v) {
-#if TEM_SMALL_NT
-    act_st4_nt(p, v);
-#else
-    act_st4(p, v);
-#endif
-}
 // v rounded to the storage type T (the statistics by-products describe the tensor AS STORED)
 template <typename T>
 __device__ __forceinline__ float4 act_round4(float4 v) {
@@ -29,9 +18,6 @@ __device__ __forceinline__ float4 act_round4(float4 v) {
 }
 
 typedef float f2 __attribute__((ext_vector_type(2)));
-#ifndef TEM_C1_ABL
-#define TEM_C1_ABL 0   // profiling ablations of the Cin = 1 forward row path: 1 = no output stores, 2 = 3 taps instead of 27
-#endif
 
 __device__ __forceinline__ float act_apply_s(float v, int act) {
     if (act == TEM_ACT_RELU) return v > 0.f ? v : 0.f;
@@ -111,7 +97,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_cin1(const EX* __restrict__ x,
         acc.w = act_apply_s(acc.w, act);
         acc = act_round4<EY>(acc);
         const int64_t v = (((int64_t)n * D + gz) * H + gy) * W + gx;
-        ST4(y + v * y_ld + q * 4, acc);
+        act_st4(y + v * y_ld + q * 4, acc);
         ssum.x += acc.x; ssum.y += acc.y; ssum.z += acc.z; ssum.w += acc.w;
         ssq.x = fmaf(acc.x, acc.x, ssq.x); ssq.y = fmaf(acc.y, acc.y, ssq.y);
         ssq.z = fmaf(acc.z, acc.z, ssq.z); ssq.w = fmaf(acc.w, acc.w, ssq.w);
@@ -212,9 +198,9 @@ __global__ __launch_bounds__(256) void k_conv_fwd_c1rows(const EX* __restrict__ 
 #pragma unroll
             for (int px = 0; px < TX; ++px) acc[px] = b2;
 #pragma unroll
-            for (int tz = 0; tz < ((TEM_C1_ABL & 2) ? 1 : KD); ++tz)
+            for (int tz = 0; tz < KD; ++tz)
 #pragma unroll
-                for (int ty = 0; ty < ((TEM_C1_ABL & 2) ? 1 : 3); ++ty) {
+                for (int ty = 0; ty < 3; ++ty) {
                     const float* xr = lx + ((pz + tz) * HY + py + ty) * HXP + xs;
                     const float4 a = *reinterpret_cast<const float4*>(xr);
                     const float4 b = *reinterpret_cast<const float4*>(xr + 4);
@@ -239,9 +225,7 @@ __global__ __launch_bounds__(256) void k_conv_fwd_c1rows(const EX* __restrict__ 
                     const unsigned pk = act_pk<EY>(o.x, o.y);
                     o = f2{act_lo<EY>(pk), act_hi<EY>(pk)};
                 }
-#if !(TEM_C1_ABL & 1)
                 act_st2_nt(y + (v0 + px) * y_ld + q * 2, o);
-#endif
                 ss += o;
                 sq = __builtin_elementwise_fma(o, o, sq);
             }
@@ -1108,7 +1092,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_proj_wgrad(const EX* __restrict
                         for (int co = 0; co < COUT; ++co) t2 = fmaf(gv[co], wq[a][co][j], t2);   // same order as k_conv1x1_expand
                         o[j] = xv[j] > 0.f ? t2 : 0.f;
                     }
-                    ST4(gx + v * gx_ld + a * 32 + l8 * 4, make_float4(o[0], o[1], o[2], o[3]));
+                    act_st4(gx + v * gx_ld + a * 32 + l8 * 4, make_float4(o[0], o[1], o[2], o[3]));
                     amx = tem_amax4(amx, o[0], o[1], o[2], o[3]);
                 }
             }
@@ -1276,7 +1260,7 @@ __global__ __launch_bounds__(256) void k_conv1x1_expand(const EX* __restrict__ x
             if (!(rr.z > 0.f)) a.z = 0.f;
             if (!(rr.w > 0.f)) a.w = 0.f;
         }
-        ST4(y + v * y_ld + q * 4, a);
+        act_st4(y + v * y_ld + q * 4, a);
         amx = tem_amax4(amx, a.x, a.y, a.z, a.w);
     }
     if (amax) tem_amax_commit(amax, amx);

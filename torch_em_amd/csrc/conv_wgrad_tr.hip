@@ -35,15 +35,52 @@
 #include <set>
 #include <type_traits>
 
-#define TR_REC16 64                // bytes per voxel record: 32 channels x 16 bit (ARITH 4, exact fp32: 128)
-#define TR_NXS 5                   // ring slots of x^ halo planes: 3 being multiplied + 1 prefetched by the multiplying team + 1 being written
-#define TR_NGS 3                   // g planes: multiplied, prefetched, being written
+// ---- tunables (numbers; variant builds override them with -D) ----
 #ifndef TR_UNROLL
 #define TR_UNROLL 8                // iterations per trip of the 16-bit staging loop (even: two register sets alternate)
 #endif
 #ifndef TR_UNROLL32
 #define TR_UNROLL32 4              // the same for the fp32-tensor staging loop (round 6; 8 and 16 measured: more idle padding at D = 32)
 #endif
+#ifndef TEM_TR_SYNC
+#define TEM_TR_SYNC 0              // 1: the multiplying team's per-plane barrier is __syncthreads() again (tr_barrier_mult; same results)
+#endif
+// ---- harness instruments (default off; wrong results when set) ----
+#ifndef TEM_TR_ABL
+#define TEM_TR_ABL 0   // ablations: 1 staging team idle, 2 multiplying team idle, 4 fragments read once per plane (no LDS reads in
+#endif                 // the MFMA stream), 8 staging without global loads, 16 every plane read from z = 0 (no HBM traffic)
+#ifdef TEM_TR_TRACE   // developer build (scripts/wg_harness_fast.sh ... -DTEM_TR_TRACE): shader-clock stamps of one workgroup's plane loop
+#ifndef TEM_TR_TRACE_BLOCK
+#define TEM_TR_TRACE_BLOCK 100
+#endif
+__device__ unsigned long long tem_tr_trace_buf[8][64][4];
+#define TR_STAMP(it, i)                                                                               \
+    do {                                                                                              \
+        if (blockIdx.x == TEM_TR_TRACE_BLOCK && lane == 0 && (it) >= 0 && (it) < 64)                  \
+            tem_tr_trace_buf[wv][it][i] = __builtin_amdgcn_s_memtime();                               \
+    } while (0)
+void tem_tr_trace_read(unsigned long long* dst) {
+    (void)hipMemcpyFromSymbol(dst, HIP_SYMBOL(tem_tr_trace_buf), sizeof(unsigned long long) * 8 * 64 * 4);
+}
+#else
+#define TR_STAMP(it, i)
+#endif
+
+#define TR_REC16 64                // bytes per voxel record: 32 channels x 16 bit (ARITH 4, exact fp32: 128)
+#define TR_NXS 5                   // ring slots of x^ halo planes: 3 being multiplied + 1 prefetched by the multiplying team + 1 being written
+#define TR_NGS 3                   // g planes: multiplied, prefetched, being written
+// Plane distances of iteration t (the code between barrier t - 1 and barrier t; x^ planes count from halo plane -1 = index -1):
+#define TR_MX_AHEAD 2              // the multiplying team reads x^ planes t - 1 .. t + 1 and, for plane t + 1, t .. t + TR_MX_AHEAD
+#define TR_MG_AHEAD 1              // ... and g planes t and t + TR_MG_AHEAD
+#define TR_SX_AHEAD 3              // the staging team (16-bit and fp32 loops alike) writes x^ plane t + TR_SX_AHEAD into the ring
+#define TR_SG_AHEAD 2              // ... and g plane t + TR_SG_AHEAD
+#define TR_LD_AHEAD 2              // its global loads run this many planes ahead of its LDS writes (two register sets)
+// a plane is written, and its writer has waited for the write, before the barrier in front of the iteration that first reads it
+static_assert(TR_SX_AHEAD >= TR_MX_AHEAD + 1 && TR_SG_AHEAD >= TR_MG_AHEAD + 1, "staging must lead the multiplying team's read-ahead");
+// the slot written in iteration t holds none of the planes read in it: (t + TR_SX_AHEAD) - (t - 1) < TR_NXS, (t + TR_SG_AHEAD) - t < TR_NGS
+static_assert(TR_NXS >= TR_SX_AHEAD + 2, "x ring too short for the staging look-ahead");
+static_assert(TR_NGS >= TR_SG_AHEAD + 1, "g ring too short for the staging look-ahead");
+static_assert(TR_LD_AHEAD == 2, "the staging loops alternate two register sets");
 #define TR_XT_OF(rec) (TR_NXS * 100 * (rec))   // one term of x^: ring of 10 x 10 halo planes
 #define TR_GT_OF(rec) (TR_NGS * 64 * (rec))    // one term of g: 8 x 8 planes
 
@@ -57,12 +94,14 @@ typedef unsigned int tr_u4 __attribute__((ext_vector_type(4)));
 // costs `s_waitcnt lgkmcnt(0)`: every transposing read in flight -- the fragments of the NEXT plane, requested during the last
 // MFMAs of this one precisely so that they travel across the barrier -- had to land first: one exposed LDS round trip per
 // plane (round 6, found in the ISA: lgkmcnt(0) in front of every s_barrier of the plane loop).  This team writes nothing to
-// LDS inside the plane loop, so it has nothing to release; what it reads after the barrier was written (and waited for) by the
-// staging team before it, and the LDS serves requests in arrival order.  The empty asm keeps the compiler from moving a
-// read across the barrier.  TEM_TR_SYNC=1 restores __syncthreads().
-#ifndef TEM_TR_SYNC
-#define TEM_TR_SYNC 0
-#endif
+// LDS inside the plane loop, so it has nothing to release; what it reads was written by the staging team, whose own barrier
+// is a full __syncthreads(): its writes have landed before it arrives.  What is new without the wait is that reads of this
+// team are still IN FLIGHT when the staging team starts iteration t + 1: x^ planes t .. t + TR_MX_AHEAD and g plane
+// t + TR_MG_AHEAD.  That iteration writes x^ plane t + 1 + TR_SX_AHEAD into slot (t - 1) % TR_NXS and g plane t + 1 + TR_SG_AHEAD
+// into slot t % TR_NGS -- slots that hold none of the planes in flight, because these are among the planes this team reads
+// during iteration t + 1 anyway and the ring is long enough for that (the static_asserts next to TR_NXS).  So no order of
+// service inside the LDS is assumed: the reads in flight and the writes that follow never touch the same bytes.  The empty asm
+// keeps the compiler from moving a read across the barrier.  TEM_TR_SYNC=1 restores __syncthreads().
 __device__ __forceinline__ void tr_barrier_mult() {
     if (TEM_TR_SYNC) {
         __syncthreads();
@@ -124,45 +163,6 @@ __device__ __forceinline__ unsigned tr_mix_scale(float g0, float g1, float sc) {
     return q;
 }
 
-#ifndef TEM_TR_TX1_DIRECT
-#define TEM_TR_TX1_DIRECT 1   // the tx = 1 fragment of a row group by two more transposing reads (0: four v_alignbyte on the window; measured +2 % kernel time: the SIMD is issue-bound at ~5 non-MFMA instructions per MFMA over both waves)
-#endif
-#ifndef TEM_TR_PF2
-#define TEM_TR_PF2 1   // one-term modes: fragments of slab s + 2 are read during the MFMAs of slab s (four register sets; 0: s + 1, two sets)
-#endif
-#ifndef TEM_TR_SHARE
-#define TEM_TR_SHARE 0   // one-term modes (round 6 experiment): row groups (tz, ty = 0) and (tz, ty = 2) of one wave share their x windows -- 24 % fewer
-                         // LDS reads, bit-identical results, -1.5 .. 3 % in the harness on dense operands and +-0.5 % in the amp step
-                         // (profiles/r06_wgrad_tr_ablations.txt): off, the PF2 loop stays the product path
-#endif
-#ifndef TEM_TR_RTZ
-#define TEM_TR_RTZ 0    // experiment: hi term of x^ by v_cvt_pkrtz_f16_f32 (one instruction per pair; the split stays exact, lo grows to 1 ulp)
-#endif
-#ifndef TEM_TR_DBCOND
-#define TEM_TR_DBCOND 0   // experiment: bias-gradient adds only in the workgroups that store them (cit == 0)
-#endif
-#ifndef TEM_TR_PRIO
-#define TEM_TR_PRIO 0   // s_setprio of the multiplying team (its MFMAs and fragment reads against the staging wave of the same SIMD)
-#endif
-#ifndef TEM_TR_ABL
-#define TEM_TR_ABL 0   // harness-only ablations (wrong results): 1 staging team idle, 2 multiplying team idle, 4 fragments read once
-#endif                 // per plane (no LDS reads in the MFMA stream), 8 staging without global loads
-#ifdef TEM_TR_TRACE   // developer build (scripts/wg_harness.sh ... -DTEM_TR_TRACE): shader-clock stamps of one workgroup's plane loop
-#ifndef TEM_TR_TRACE_BLOCK
-#define TEM_TR_TRACE_BLOCK 100
-#endif
-__device__ unsigned long long tem_tr_trace_buf[8][64][4];
-#define TR_STAMP(it, i)                                                                               \
-    do {                                                                                              \
-        if (blockIdx.x == TEM_TR_TRACE_BLOCK && lane == 0 && (it) >= 0 && (it) < 64)                  \
-            tem_tr_trace_buf[wv][it][i] = __builtin_amdgcn_s_memtime();                               \
-    } while (0)
-void tem_tr_trace_read(unsigned long long* dst) {
-    (void)hipMemcpyFromSymbol(dst, HIP_SYMBOL(tem_tr_trace_buf), sizeof(unsigned long long) * 8 * 64 * 4);
-}
-#else
-#define TR_STAMP(it, i)
-#endif
 
 // TS (round 5): element type of x and g in HBM.  A 16-bit TS is the one-term mode of the same type (ARITH 1: fp16, 2: bf16) and
 // changes only the staging team: a voxel record in HBM is what LDS holds (64 bytes), FOUR lanes move it with one 16-byte load
@@ -219,7 +219,6 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
 
     if (mteam) {
         // ---------------- multiplying team ----------------
-        if (TEM_TR_PRIO) __builtin_amdgcn_s_setprio(TEM_TR_PRIO);
         floatx16 acc[NA];
 #pragma unroll
         for (int j = 0; j < NA; ++j)
@@ -234,7 +233,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
         // taps of this wave (as k_conv_wgrad_zt): accumulators 0..2 = row group (tz, ty) = wv with tx = 0, 1, 2; 3..5 = row group
         // wv + 4; accumulator 6 = (row group 8, tx = wv) -- wave 3 has no seventh tap: it repeats tx = 0 there and never stores it.
         // A row group reads ONE 12-voxel window of its x row (three transposing reads: elements k0 .. k11 of the lane's
-        // channel); the tx = 0 fragment is registers 0..3 of it, tx = 2 registers 1..4, tx = 1 four v_alignbyte.
+        // channel); the tx = 0 fragment is registers 0..3 of it, tx = 2 registers 1..4, tx = 1 two more transposing reads.
         int rgtz[3], rgoff[3];
 #pragma unroll
         for (int a = 0; a < 3; ++a) {
@@ -265,40 +264,19 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                     const unsigned char* p = xb[a] + term * TR_XT + sl * 2 * TR_XROW;
                     const uint2 w0 = tr_read(p), w1 = tr_read(p + 4 * TR_REC), w2 = tr_read(p + 8 * TR_REC);
                     f[3 * a + 0] = make_uint4(w0.x, w0.y, w1.x, w1.y);
-                    if (TEM_TR_TX1_DIRECT)
-                        f[3 * a + 1] = tr_frag(p + TR_REC16);
-                    else
-                        f[3 * a + 1] = make_uint4(__builtin_amdgcn_alignbyte(w0.y, w0.x, 2), __builtin_amdgcn_alignbyte(w1.x, w0.y, 2),
-                                                  __builtin_amdgcn_alignbyte(w1.y, w1.x, 2), __builtin_amdgcn_alignbyte(w2.x, w1.y, 2));
+                    f[3 * a + 1] = tr_frag(p + TR_REC16);
                     f[3 * a + 2] = make_uint4(w0.y, w1.x, w1.y, w2.x);
                 }
                 f[6] = tr_frag(xb[2] + term * TR_XT + sl * 2 * TR_XROW);
             };
-            auto interleave = [&]() {   // the 7 MFMAs of the phase just written and the reads / shifts for the next one:
-                // reads behind the first three MFMAs, the v_alignbyte of the tx = 1 fragments behind the last three (their
-                // reads have returned by then: an LDS wait inside the MFMA stream would stall the matrix pipe)
-                if (TEM_TR_TX1_DIRECT) {   // 12 (+ 2) reads, no shifts: three reads behind each of the first five MFMAs
+            auto interleave = [&]() {   // the 7 MFMAs of the phase just written and the 12 (+ 2) reads for the next one: three reads
+                // behind each of the first five MFMAs (an LDS wait inside the MFMA stream would stall the matrix pipe)
 #pragma unroll
-                    for (int i = 0; i < 5; ++i) {
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-                    }
-                    __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                    __builtin_amdgcn_sched_barrier(0);
-                    return;
+                for (int i = 0; i < 5; ++i) {
+                    __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
+                    __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
                 }
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x100, 4, 0);
                 __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 3, 0);
-                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                __builtin_amdgcn_sched_group_barrier(0x002, 2, 0);
                 __builtin_amdgcn_sched_barrier(0);
             };
             auto bases = [&](int t, const unsigned char** xb) -> const unsigned char* {   // fragment bases of plane t
@@ -310,188 +288,22 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
             // the load of eight waves takes longer than that to return -- with one slab of lead every slab still waited
             // (counters of the amp step: matrix pipe 0.44 busy at 2.2 GHz, not power-limited).  Four register sets named by the
             // slab index (four slabs per plane: static names), 170 -> ~235 VGPRs of the 256 this kernel may use.
-            // ---- one-term modes, round 6: SHARED WINDOWS ------------------------------------------------------------------
-            // The one-term kernel is bound by LDS bandwidth: 14 transposing reads per slab and wave x 4 waves x 512 B = 28 KB per
-            // 224 cycles of MFMAs = the 128 B / clock the LDS delivers.  The fragment of tap (tz, ty = 2) at slab s -- halo rows
-            // 2 s + 2, 2 s + 3 -- IS the fragment of tap (tz, ty = 0) at slab s + 1, so a wave that owns both row groups of one tz
-            // reads FIVE 12-voxel windows per plane instead of eight.  Ownership: waves 0..2 = (tz = wave, ty = 0), (tz = wave,
-            // ty = 2) and one tap of (tz = 2, ty = 1); wave 3 = (0, 1) and (1, 1), no shared rows.  Reads per plane and CU
-            // 224 -> 171.  Window k of a plane lives in register set k & 3; a set is refilled as soon as the last MFMA group that
-            // reads it has been issued, two slabs before its next use; the B group (ty = 2) of a slab is issued before the A
-            // group, so that window 0 of the NEXT plane can follow window 4 into set 0 inside slab 3.
-            constexpr bool SH = NX == 1 && !FP32 && TEM_TR_SHARE;
-            if constexpr (SH) {
-                auto wbase = [&](int t, int tz, int ro) -> const unsigned char* {
-                    return X0 + lane_x + TR_XSLOT(t + tz - 1) + ro * TR_XROW;
-                };
-                auto rd_win = [&](uint4* f, const unsigned char* p) {   // taps tx = 0, 1, 2 of one row pair: 3 + 2 transposing reads
-                    const uint2 w0 = tr_read(p), w1 = tr_read(p + 4 * TR_REC), w2 = tr_read(p + 8 * TR_REC);
-                    f[0] = make_uint4(w0.x, w0.y, w1.x, w1.y);
-                    f[1] = tr_frag(p + TR_REC16);
-                    f[2] = make_uint4(w0.y, w1.x, w1.y, w2.x);
-                };
-                uint4 Bw[4][3], gq[4], eq[4];
-                if (wv < 3) {
-                    {
-                        const unsigned char* wb = wbase(za, wv, 0);
-                        rd_win(Bw[0], wb);
-                        rd_win(Bw[1], wb + 2 * TR_XROW);
-                        rd_win(Bw[2], wb + 4 * TR_XROW);
-                        const unsigned char* eb = wbase(za, 2, 1) + wv * TR_REC;
-                        eq[0] = tr_frag(eb);
-                        eq[1] = tr_frag(eb + 2 * TR_XROW);
-                        const unsigned char* gb = G0 + lane_g + TR_GSLOT(za);
-                        gq[0] = tr_frag(gb);
-                        gq[1] = tr_frag(gb + 16 * TR_REC);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-#pragma unroll 1
-                    for (int t = za; t < zb; ++t) {
-                        const unsigned char *wb = wbase(t, wv, 0), *wbn = wbase(t + 1, wv, 0);
-                        const unsigned char *eb = wbase(t, 2, 1) + wv * TR_REC, *ebn = wbase(t + 1, 2, 1) + wv * TR_REC;
-                        const unsigned char *gb = G0 + lane_g + TR_GSLOT(t), *gbn = G0 + lane_g + TR_GSLOT(t + 1);
-                        TR_STAMP(t - za, 0);
-                        if (TEM_TR_ABL & 2) {
-                            __syncthreads();
-                            continue;
-                        }
-                        TR_STAMP(t - za, 1);
-                        auto group = [&](int a0, const uint4* f, const uint4& gg) {
-#pragma unroll
-                            for (int j = 0; j < 3; ++j) acc[a0 + j] = mfma16<F16>(f[j], gg, acc[a0 + j]);
-                        };
-                        auto pat9 = [&]() {   // 7 MFMAs, 9 reads
-#pragma unroll
-                            for (int i = 0; i < 4; ++i) {
-                                __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                                __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                            }
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                            __builtin_amdgcn_sched_barrier(0);
-                        };
-                        // slab 0: windows 0 (set 0), 1 (set 1); window 3 -> set 3
-                        rd_win(Bw[3], wb + 6 * TR_XROW);
-                        gq[2] = tr_frag(gb + 2 * 16 * TR_REC);
-                        eq[2] = tr_frag(eb + 4 * TR_XROW);
-                        group(3, Bw[1], gq[0]);
-                        group(0, Bw[0], gq[0]);
-                        acc[6] = mfma16<F16>(eq[0], gq[0], acc[6]);
-                        pat9();
-                        // slab 1: windows 1, 2; window 4 -> set 0
-                        rd_win(Bw[0], wb + 8 * TR_XROW);
-                        gq[3] = tr_frag(gb + 3 * 16 * TR_REC);
-                        eq[3] = tr_frag(eb + 6 * TR_XROW);
-                        group(3, Bw[2], gq[1]);
-                        group(0, Bw[1], gq[1]);
-                        acc[6] = mfma16<F16>(eq[1], gq[1], acc[6]);
-                        pat9();
-                        // slab 2: windows 2, 3; window 1 of the NEXT plane -> set 1
-                        rd_win(Bw[1], wbn + 2 * TR_XROW);
-                        gq[0] = tr_frag(gbn);
-                        eq[0] = tr_frag(ebn);
-                        group(3, Bw[3], gq[2]);
-                        group(0, Bw[2], gq[2]);
-                        acc[6] = mfma16<F16>(eq[2], gq[2], acc[6]);
-                        pat9();
-                        // slab 3: windows 3 (set 3), 4 (set 0); windows 2 and -- behind the MFMAs that read set 0 -- 0 of the next plane
-                        rd_win(Bw[2], wbn + 4 * TR_XROW);
-                        gq[1] = tr_frag(gbn + 16 * TR_REC);
-                        eq[1] = tr_frag(ebn + 2 * TR_XROW);
-                        group(3, Bw[0], gq[3]);
-                        rd_win(Bw[0], wbn);
-                        group(0, Bw[3], gq[3]);
-                        acc[6] = mfma16<F16>(eq[3], gq[3], acc[6]);
-#pragma unroll
-                        for (int i = 0; i < 3; ++i) {
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-                        }
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x100, 1, 0);
-                        __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                        __builtin_amdgcn_sched_barrier(0);
-                        TR_STAMP(t - za, 2);
-                        tr_barrier_mult();
-                        TR_STAMP(t - za, 3);
-                    }
-                } else {
-                    // wave 3: row groups (tz = 0, ty = 1) [A, accumulators 0..2] and (tz = 1, ty = 1) [B, 3..5]: different halo planes,
-                    // nothing to share.  Slab s uses sets 2 (s & 1) and 2 (s & 1) + 1; each is refilled for slab s + 2 right behind
-                    // the three MFMAs that read it (two slabs of lead, as the shared windows have).
-                    {
-                        const unsigned char *ab = wbase(za, 0, 1), *bb = wbase(za, 1, 1);
-                        rd_win(Bw[0], ab);
-                        rd_win(Bw[1], bb);
-                        rd_win(Bw[2], ab + 2 * TR_XROW);
-                        rd_win(Bw[3], bb + 2 * TR_XROW);
-                        const unsigned char* gb = G0 + lane_g + TR_GSLOT(za);
-                        gq[0] = tr_frag(gb);
-                        gq[1] = tr_frag(gb + 16 * TR_REC);
-                        __builtin_amdgcn_sched_barrier(0);
-                    }
-#pragma unroll 1
-                    for (int t = za; t < zb; ++t) {
-                        const unsigned char *ab = wbase(t, 0, 1), *bb = wbase(t, 1, 1);
-                        const unsigned char *abn = wbase(t + 1, 0, 1), *bbn = wbase(t + 1, 1, 1);
-                        const unsigned char *gb = G0 + lane_g + TR_GSLOT(t), *gbn = G0 + lane_g + TR_GSLOT(t + 1);
-                        TR_STAMP(t - za, 0);
-                        if (TEM_TR_ABL & 2) {
-                            __syncthreads();
-                            continue;
-                        }
-                        TR_STAMP(t - za, 1);
-#pragma unroll
-                        for (int sl = 0; sl < 4; ++sl) {
-                            const int nsl = (sl + 2) & 3;
-                            uint4* const pa = Bw[2 * (sl & 1)];
-                            uint4* const pb = Bw[2 * (sl & 1) + 1];
-                            gq[nsl] = tr_frag((sl < 2 ? gb : gbn) + nsl * 16 * TR_REC);
-#pragma unroll
-                            for (int j = 0; j < 3; ++j) acc[3 + j] = mfma16<F16>(pb[j], gq[sl], acc[3 + j]);
-                            rd_win(pb, (sl < 2 ? bb : bbn) + nsl * 2 * TR_XROW);
-#pragma unroll
-                            for (int j = 0; j < 3; ++j) acc[j] = mfma16<F16>(pa[j], gq[sl], acc[j]);
-                            rd_win(pa, (sl < 2 ? ab : abn) + nsl * 2 * TR_XROW);
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 3, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x008, 1, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 2, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x008, 2, 0);
-                            __builtin_amdgcn_sched_group_barrier(0x100, 5, 0);
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
-                        TR_STAMP(t - za, 2);
-                        tr_barrier_mult();
-                        TR_STAMP(t - za, 3);
-                    }
-                }
-                for (int e = zb - za + 6; e % (T16 ? TR_UNROLL : TR_UNROLL32); ++e) __syncthreads();
-                continue;
-            }
-            constexpr bool PF2 = NX == 1 && !FP32 && TEM_TR_PF2 && !SH;
+            constexpr bool PF2 = NX == 1 && !FP32;
             uint4 xq[PF2 ? 4 : 1][NA], gq[PF2 ? 4 : 1];
             if constexpr (PF2) {
                 const unsigned char* xb0[3];
                 const unsigned char* gb0 = bases(za, xb0);
 #pragma unroll
                 for (int sl = 0; sl < 2; ++sl) {
-                    gq[PF2 ? sl : 0] = tr_frag(gb0 + sl * 16 * TR_REC);
-                    load_x(xq[PF2 ? sl : 0], xb0, 0, sl);
+                    gq[sl] = tr_frag(gb0 + sl * 16 * TR_REC);
+                    load_x(xq[sl], xb0, 0, sl);
                 }
                 __builtin_amdgcn_sched_barrier(0);
-            } else if constexpr (!FP32) {   // first fragments of the segment's first plane
+            } else if constexpr (NX == 2) {   // two-term x: first fragments of the segment's first plane
                 const unsigned char* xb0[3];
                 const unsigned char* gb0 = bases(za, xb0);
                 load_g(gb0, 0);
-                load_x(NX == 2 ? xl : xh, xb0, NX == 2 ? 1 : 0, 0);
+                load_x(xl, xb0, 1, 0);
                 __builtin_amdgcn_sched_barrier(0);
             }
             if constexpr (FP32) {
@@ -543,10 +355,10 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
 #pragma unroll
                     for (int sl = 0; sl < 4; ++sl) {
                         const int nsl = (sl + 2) & 3;
-                        gq[PF2 ? nsl : 0] = tr_frag((sl < 2 ? gb : gbn) + nsl * 16 * TR_REC);
-                        load_x(xq[PF2 ? nsl : 0], sl < 2 ? xb : xbn, 0, nsl);
+                        gq[nsl] = tr_frag((sl < 2 ? gb : gbn) + nsl * 16 * TR_REC);
+                        load_x(xq[nsl], sl < 2 ? xb : xbn, 0, nsl);
 #pragma unroll
-                        for (int j = 0; j < NA; ++j) acc[j] = mfma16<F16>(xq[PF2 ? sl : 0][j], gq[PF2 ? sl : 0], acc[j]);
+                        for (int j = 0; j < NA; ++j) acc[j] = mfma16<F16>(xq[sl][j], gq[sl], acc[j]);
                         interleave();
                     }
                     TR_STAMP(t - za, 2);
@@ -573,20 +385,6 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                     const uint4 ghc = gh;
                     load_g(sl < 3 ? gb : gbn, (sl + 1) & 3);
                     if (NX == 2) load_x(xl, sl < 3 ? xb : xbn, 1, (sl + 1) & 3);
-                    if constexpr (NX == 1) {
-                        // one-term x (the mixed modes): the lo register set is free, so it is the SECOND fragment buffer -- the
-                        // reads of slab sl + 1 fly during the 7 MFMAs of slab sl (even slabs multiply xh and fill xl, odd ones the
-                        // reverse; four slabs per plane keep the parity).  Round 4 read the next fragments into the SAME registers
-                        // behind the MFMAs that used them: every slab then waited a full LDS round trip (trace of round 5, amp mode:
-                        // 2200 cycles per plane for 28 MFMAs = 0.4 of the matrix pipe, unchanged by 16-bit staging).
-                        uint4* const cur = (sl & 1) ? xl : xh;
-                        uint4* const nxt = (sl & 1) ? xh : xl;
-                        load_x(nxt, sl < 3 ? xb : xbn, 0, (sl + 1) & 3);
-#pragma unroll
-                        for (int j = 0; j < NA; ++j) acc[j] = mfma16<F16>(cur[j], ghc, acc[j]);
-                        interleave();
-                        continue;
-                    }
 #pragma unroll
                     for (int j = 0; j < NA; ++j) acc[j] = mfma16<F16>(xh[j], ghc, acc[j]);
                     interleave();
@@ -598,19 +396,13 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
             // the staging team walks a segment in trips of TR_UNROLL (16-bit tensors) / TR_UNROLL32 iterations
             for (int e = zb - za + 6; e % (T16 ? TR_UNROLL : TR_UNROLL32); ++e) __syncthreads();
         }
-        if (TEM_TR_PRIO) __builtin_amdgcn_s_setprio(0);
         // ---- partial slabs: D[row = ci][col = co] ----
         if (cog * 32 < Cout) {
             const int kh = lane >> 5, r = lane & 31;
 #pragma unroll
             for (int j = 0; j < NA; ++j) {
                 if (j == 6 && wv >= 3) break;
-                // shared windows (one-term modes): waves 0..2 hold row groups (wave, 0), (wave, 2) and tap tx = wave of row group (2, 1),
-                // wave 3 row groups (0, 1) and (1, 1); else row groups wave, wave + 4 and tap tx = wave of row group 8
-                constexpr bool SHT = NX == 1 && !FP32 && TEM_TR_SHARE;
-                const int tap = SHT ? (wv < 3 ? (j < 3 ? (wv * 3) * 3 + j : j < 6 ? (wv * 3 + 2) * 3 + (j - 3) : 7 * 3 + wv)
-                                              : (j < 3 ? 1 * 3 + j : 4 * 3 + (j - 3)))
-                                    : (j < 6) ? (wv + 4 * (j / 3)) * 3 + (j % 3) : 8 * 3 + wv;
+                const int tap = (j < 6) ? (wv + 4 * (j / 3)) * 3 + (j % 3) : 8 * 3 + wv;   // row groups wave, wave + 4; tap tx = wave of row group 8
                 float* dst = part + (((int64_t)sp * NT + tap) * Cin + cit * 32) * Cout + cog * 32 + r;
 #pragma unroll
                 for (int reg = 0; reg < 16; ++reg) {
@@ -688,7 +480,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                     {   // (no branch in here: the pre-norm always runs -- scale 1, shift 0 without a norm reproduces the value bit for
                         // bit --, threads without a second halo voxel write a scratch record, the priming iterations write planes
                         // that are rewritten before anything reads them)
-                        unsigned char* const xs = X0 + TR_XSLOT(t + 3) + oct * 16;
+                        unsigned char* const xs = X0 + TR_XSLOT(t + TR_SX_AHEAD) + oct * 16;
 #pragma unroll
                         for (int q = 0; q < 2; ++q) {
                             const int hv = (tl + 256 * q) >> 2;
@@ -704,7 +496,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                         }
                     }
                     {
-                        unsigned char* const gs = G0 + TR_GSLOT(t + 2) + oct * 16;
+                        unsigned char* const gs = G0 + TR_GSLOT(t + TR_SG_AHEAD) + oct * 16;
                         const uint4 v = gs_;   // zeros where out of range (load offset beyond the buffer)
                         *reinterpret_cast<uint4*>(gs + (tl >> 2) * TR_REC) = v;
                         db8[0] += act_lo<TS>(v.x); db8[1] += act_hi<TS>(v.x); db8[2] += act_lo<TS>(v.y); db8[3] += act_hi<TS>(v.y);
@@ -713,14 +505,14 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                     TR_STAMP(t - za, 1);
                     {
                         // (plain scalar arithmetic, no short-circuit operators: a branch around a load would be back)
-                        const int zx = t + 5;
+                        const int zx = t + TR_SX_AHEAD + TR_LD_AHEAD;
                         const int ldx = (int)(zx >= za - 1) & (int)(zx <= zb) & (int)(zx >= 0) & (int)(zx < D) & (int)!(TEM_TR_ABL & 8);   // wave-uniform
                         zin_ = ldx != 0;
                         const tr_rsrc_t rsx = tr_rsrc(xn + (int64_t)(zx * ldx) * xplane);
                         const unsigned mx = ldx ? 0u : OOB;   // OR-ed into the offsets (< 2^31): beyond the buffer -> zeros
 #pragma unroll
                         for (int q = 0; q < 2; ++q) xs_[q] = tr_load4u(rsx, offx[q] | mx);
-                        const int zg = t + 4;
+                        const int zg = t + TR_SG_AHEAD + TR_LD_AHEAD;
                         const int ldg = (int)(zg >= za) & (int)(zg < zb) & (int)!(TEM_TR_ABL & 8);
                         const tr_rsrc_t rsg = tr_rsrc(gn + (int64_t)(zg * ldg) * gplane);
                         gs_ = tr_load4u(rsg, offg | (ldg ? 0u : OOB));
@@ -823,7 +615,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                     return;
                 }
                 {
-                    unsigned char* const xs = X0 + TR_XSLOT(t + 3) + quad * TR_QB;
+                    unsigned char* const xs = X0 + TR_XSLOT(t + TR_SX_AHEAD) + quad * TR_QB;
                     if (zin_) {
 #pragma unroll
                         for (int q = 0; q < 4; ++q) {
@@ -837,11 +629,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                             }
                             uint2 hi, lo;
                             if (H21) {
-                                if (TEM_TR_RTZ)
-                                    hi = make_uint2(__builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(e0, e1)),
-                                                    __builtin_bit_cast(unsigned, __builtin_amdgcn_cvt_pkrtz(e2, e3)));
-                                else
-                                    hi = make_uint2(pk16<true>(e0, e1), pk16<true>(e2, e3));
+                                hi = make_uint2(pk16<true>(e0, e1), pk16<true>(e2, e3));
                                 lo = make_uint2(tr_mix_lo(hi.x, e0, e1), tr_mix_lo(hi.y, e2, e3));
                             } else if (ARITH == 0) {
                                 split2(e0, e1, hi.x, lo.x);
@@ -868,7 +656,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                 }
                 {   // g plane t + 2 (zeros outside the segment: the load was sent beyond the buffer; such a plane lands in a slot
                     // that is rewritten before anything multiplies with it)
-                    unsigned char* const gs = G0 + TR_GSLOT(t + 2) + quad * TR_QB;
+                    unsigned char* const gs = G0 + TR_GSLOT(t + TR_SG_AHEAD) + quad * TR_QB;
 #pragma unroll
                     for (int q = 0; q < 2; ++q) {
                         const int gv = (tl + 256 * q) >> 3;
@@ -887,12 +675,10 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                         }
                         if (!FP32) *reinterpret_cast<uint2*>(gs + gv * TR_REC) = hi;
                         if (NG == 2) *reinterpret_cast<uint2*>(gs + TR_GT + gv * TR_REC) = lo;
-                        if (!TEM_TR_DBCOND || do_db) {
-                            dbacc[0] += v.x;
-                            dbacc[1] += v.y;
-                            dbacc[2] += v.z;
-                            dbacc[3] += v.w;
-                        }
+                        dbacc[0] += v.x;
+                        dbacc[1] += v.y;
+                        dbacc[2] += v.z;
+                        dbacc[3] += v.w;
                         if (gmax)   // grid-uniform
                             gmx = __builtin_fmaxf(gmx, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(v.x), __builtin_fabsf(v.y)),
                                                                        __builtin_fmaxf(__builtin_fabsf(v.z), __builtin_fabsf(v.w))));
@@ -901,7 +687,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                 TR_STAMP(t - za, 1);
                 {
                     // (plain scalar arithmetic, no short-circuit operators: a branch around a load would be back)
-                    const int zx = t + 5;
+                    const int zx = t + TR_SX_AHEAD + TR_LD_AHEAD;
                     const int ldx = (int)(zx >= za - 1) & (int)(zx <= zb) & (int)(zx >= 0) & (int)(zx < D) & (int)!(TEM_TR_ABL & 8);   // wave-uniform
                     zin_ = ldx != 0;
                     // (TEM_TR_ABL & 16, timing only: every plane is read from z = 0 -- the loads stay, the HBM traffic goes)
@@ -909,7 +695,7 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
                     const unsigned mx = ldx ? 0u : OOB;   // OR-ed into the offsets (< 2^31): beyond the buffer -> zeros
 #pragma unroll
                     for (int q = 0; q < 4; ++q) xs_[q] = tr_load4(rsx, offx[q] | mx);
-                    const int zg = t + 4;
+                    const int zg = t + TR_SG_AHEAD + TR_LD_AHEAD;
                     const int ldg = (int)(zg >= za) & (int)(zg < zb) & (int)!(TEM_TR_ABL & 8);
                     const tr_rsrc_t rsg = tr_rsrc(gn + (int64_t)((TEM_TR_ABL & 16) ? 0 : zg * ldg) * gplane);
                     const unsigned mg = ldg ? 0u : OOB;

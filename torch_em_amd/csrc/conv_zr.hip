@@ -33,11 +33,9 @@
 #include "tem_act.h"
 #include <type_traits>
 
+// ---- tunables (numbers; variant builds override them with -D) ----
 #ifndef TEM_ZR_PRIO
 #define TEM_ZR_PRIO 1    // s_setprio of the team in its MFMA phase
-#endif
-#ifndef TEM_ZR_STAGE_PRIO
-#define TEM_ZR_STAGE_PRIO 0   // s_setprio of the team in its staging phase (experiment)
 #endif
 #ifndef TEM_ZR_R0
 #define TEM_ZR_R0 2      // halo planes (of 6; three 16-byte loads each) requested BEFORE the epilogue of the previous unit
@@ -58,20 +56,34 @@
 #ifndef TEM_ZR_ST_AUX_KS
 #define TEM_ZR_ST_AUX_KS 2  // ... of split-K partial sums (read back at once by tem_splitk_epilogue)
 #endif
-#ifndef TEM_ZR_X32_SCHED
-#define TEM_ZR_X32_SCHED 1   // exact-fp32 tap loop: 1 = (column, channel octet) steps, MFMAs round-robin over the four accumulators; 0 = plane by plane
-#endif
 #ifndef TEM_ZR_X32_R0_M0
 #define TEM_ZR_X32_R0_M0 6   // exact fp32: halo planes requested at the start of a staging phase, per epilogue mode (plain / statistics / ReLU mask /
 #define TEM_ZR_X32_R0_M1 4   // mask + norm backward): the largest counts without register spills.  (With the epilogue inside the staging phase,
 #define TEM_ZR_X32_R0_M2 6   // as in the split modes, they were 6 / 2 / 5 / 3: the 18 registers of a plane overlapped the epilogue's temporaries.)
 #define TEM_ZR_X32_R0_M3 5
 #endif
-#ifndef TEM_ZR_X32_GAP
-#define TEM_ZR_X32_GAP 0     // exact-fp32 tap loop: units of 4 cycles of s_nop behind every MFMA (experiment, see zr_x32_gap: does not help)
+#ifndef TEM_ZR_KS_FILL
+#define TEM_ZR_KS_FILL 4   // tenths of the tiled volume that must be real voxels for a split-K launch (measured: 8 -> 5: cfg 5 -0.2 ms, cfg 2 -0.04 ms, the 8^3 level is half padding; 5 -> 4: cfg 5 25.37 -> 25.04 ms, its 6 x 12 x 12 level is 42 % real; 3: 25.16)
 #endif
+// ---- harness instruments (default off; wrong results when set) ----
 #ifndef TEM_ZR_ABL
-#define TEM_ZR_ABL 0     // harness-only ablations: 1 no halo loads, 2 no stores, 4 no weight loads, 8 no LDS writes, 16 no MFMAs
+#define TEM_ZR_ABL 0     // ablations: 1 no halo loads, 2 no stores, 4 no weight loads, 8 no LDS writes, 16 no MFMAs
+#endif
+#ifdef TEM_ZR_TRACE   // developer build (scripts/zr_harness_fast.sh, pp_harness.cpp): shader-clock stamps of the phases of one workgroup
+#ifndef TEM_ZR_TRACE_BLOCK
+#define TEM_ZR_TRACE_BLOCK 0
+#endif
+__device__ unsigned long long tem_zr_trace_buf[2][64][12];
+#define ZR_STAMP(i)                                                                           \
+    do {                                                                                      \
+        if (blockIdx.x == TEM_ZR_TRACE_BLOCK && tw == 0 && lane == 0 && s < 64)               \
+            tem_zr_trace_buf[team][s][i] = __builtin_amdgcn_s_memtime();                      \
+    } while (0)
+void tem_zr_trace_read(unsigned long long* dst) {
+    (void)hipMemcpyFromSymbol(dst, HIP_SYMBOL(tem_zr_trace_buf), sizeof(unsigned long long) * 2 * 64 * 12);
+}
+#else
+#define ZR_STAMP(i) asm volatile("; ZRMARK " #i)
 #endif
 
 typedef float floatx4z __attribute__((ext_vector_type(4)));
@@ -171,42 +183,13 @@ __device__ __forceinline__ unsigned zr_mix_lo(unsigned h, float g0, float g1) {
     return q;
 }
 
-#ifdef TEM_ZR_TRACE   // developer build (scripts/zr_harness.cpp): shader-clock stamps of the phases of one workgroup
-#ifndef TEM_ZR_TRACE_BLOCK
-#define TEM_ZR_TRACE_BLOCK 0
-#endif
-__device__ unsigned long long tem_zr_trace_buf[2][64][12];
-#define ZR_STAMP(i)                                                                           \
-    do {                                                                                      \
-        if (blockIdx.x == TEM_ZR_TRACE_BLOCK && tw == 0 && lane == 0 && s < 64)               \
-            tem_zr_trace_buf[team][s][i] = __builtin_amdgcn_s_memtime();                      \
-    } while (0)
-void tem_zr_trace_read(unsigned long long* dst) {
-    (void)hipMemcpyFromSymbol(dst, HIP_SYMBOL(tem_zr_trace_buf), sizeof(unsigned long long) * 2 * 64 * 12);
-}
-#else
-#define ZR_STAMP(i) asm volatile("; ZRMARK " #i)
-#endif
-
 // Measured (scripts/proto/issue_bench.hip -DPARTNER_F32, profiles/r06_issue_bench_f32.txt): beside a wave that streams
 // v_mfma_f32_32x32x2_f32 back to back, the other wave of the SIMD issues NO vector-ALU instruction at all -- 512 v_fma_f32 took
 // 68 288 ticks next to a 65 896-tick MFMA loop (LDS and memory instructions are not affected; beside the 8-pass fp16 MFMAs
 // a VALU instruction goes through every ~6 cycles).  The next MFMA of a dense stream waits at the vector-ALU port for the
 // 64 cycles its predecessor occupies the matrix pipe, and the port is the staging team's, too: the first trace of the exact-fp32
 // kernel showed the partner's staging phase starting only AFTER the tap phase (step = 55.6 k cycles of MFMAs + 10 k of staging,
-// 0.84 of the pipe).  So the multiplying wave stays away from the port while its MFMA runs: s_nop for most of the 64 cycles,
-// the next MFMA arrives shortly before the pipe is free, and the staging wave has the port in between.
-__device__ __forceinline__ void zr_x32_gap() {
-    if constexpr (TEM_ZR_X32_GAP > 0) {
-        __builtin_amdgcn_sched_barrier(0);
-        constexpr int FULL16 = TEM_ZR_X32_GAP / 16, REST = TEM_ZR_X32_GAP % 16;
-#pragma unroll
-        for (int i = 0; i < FULL16; ++i) asm volatile("s_nop 15");
-        if constexpr (REST > 0) asm volatile("s_nop %0" ::"n"(REST - 1));
-        __builtin_amdgcn_sched_barrier(0);
-    }
-}
-
+// 0.84 of the pipe).  Hence the exact-fp32 staging below keeps off the vector ALU wherever it can (scalar selects, pvo).
 // a < b ? t : f on the scalar ALU, spelled out (see the exact-fp32 staging phase)
 __device__ __forceinline__ unsigned zr_ssel_ltu(unsigned a, unsigned b, unsigned t, unsigned f) {
     unsigned r;
@@ -351,7 +334,7 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
         else
             lwj[j] = (unsigned)(q * 32) + (unsigned)(((((c4 >> 1) & 1) ^ (hy & 1)) << 4) | ((c4 & 1) << 3)) + (unsigned)((c4 >> 2) * PLB);
     }
-    // Exact fp32: the vector ALU of a SIMD is the matrix pipe of v_mfma_f32_32x32x2_f32 (zr_x32_gap above: beside the partner's
+    // Exact fp32: the vector ALU of a SIMD is the matrix pipe of v_mfma_f32_32x32x2_f32 (measurement above zr_ssel_ltu: beside the partner's
     // MFMA stream this wave issues no VALU instruction), so a staging phase must get its halo loads out WITHOUT one: the per-slot
     // offsets with the in-plane validity of the unit folded in (out-of-range slots read the always-valid plane voxel (1, 1) and
     // are zeroed later) are prepared where the unit is chosen -- behind this team's own tap phase, when the ALU is free -- and the
@@ -444,7 +427,7 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
     };
     // =====================================================================================================================
     // XS (round 6): exact fp32 with ONE team per workgroup.  Beside a stream of v_mfma_f32_32x32x2_f32 the partner wave of a SIMD
-    // issues no vector-ALU instruction (zr_x32_gap above), so a second team cannot stage "behind" the MFMAs: whatever it does on
+    // issues no vector-ALU instruction (measurement above zr_ssel_ltu), so a second team cannot stage "behind" the MFMAs: whatever it does on
     // the vector ALU waits until they are over and then runs exposed, once per phase, with two workgroup barriers around it.  Here
     // the four waves that multiply also stage: the tile of the NEXT chunk (the other half of the same LDS) is filled from inside
     // the tap loop -- one halo slot per step of 48 MFMAs: a buffer_load four steps ahead, four fused multiply-adds, one
@@ -614,7 +597,6 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
         {
             // ================= staging phase (the partner team runs its tap loop) =================
             ZR_STAMP(0);
-            if (TEM_ZR_STAGE_PRIO) __builtin_amdgcn_s_setprio(TEM_ZR_STAGE_PRIO);
             // keep hipcc from hoisting the 18 LDS / 18 global addresses of a phase out of the unit loop (it spills them)
 #pragma unroll
             for (int j = 0; j < SPP; ++j) asm volatile("" : "+v"(lwj[j]), "+v"(poff[j]));
@@ -829,7 +811,6 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
                         wq[0][tz][p] = zr_load4u(rw, woff_lane, wsoff + (unsigned)((tz * 9) * tapstride + p * 64) * 16u);
             }
             ZR_STAMP(2);
-            if (TEM_ZR_STAGE_PRIO) __builtin_amdgcn_s_setprio(0);
         }
         __syncthreads();
         {
@@ -859,7 +840,7 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
                     for (int p = 0; p < NS; ++p)
                         af[st % (AD + 1)][p] = *reinterpret_cast<const uint4*>(lds + a0 + hz * ZSTEP + p * PLB);
                 };
-                if constexpr (X32 && TEM_ZR_X32_SCHED == 1) {
+                if constexpr (X32) {
                     // Exact fp32.  A step = (column g, channel octet p): the six halo planes of the column are read once (one
                     // ds_read_b128 each: channels 8 p + 4 k + (0..3) of this lane's voxel) and each of the four k-steps multiplies
                     // its twelve (plane, z tap) pairs ROUND-ROBIN over the four accumulators -- a v_mfma_f32_32x32x2_f32 cannot start
@@ -900,71 +881,8 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
                                         continue;
                                     }
                                     acc[z] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(wq[g & 1][tz][p], c), comp(xr[u & 1][z + tz], c), acc[z], 0, 0, 0);
-                                    zr_x32_gap();
                                 }
                         __builtin_amdgcn_sched_barrier(0);
-                    }
-                } else if constexpr (X32) {
-                    // (first schedule, TEM_ZR_X32_SCHED 0: kept for the A/B.)  Fragment order inside a column: halo planes 0, 5, 1, 2, 3, 4.  Planes 0 and 5 feed ONE accumulator
-                    // each (output planes 0 / 3): their MFMAs alternate, so that no v_mfma_f32_32x32x2_f32 directly follows the one
-                    // that writes its accumulator (a dependent one cannot start before its predecessor has written back, and this
-                    // SIMD has no second multiplying wave to fill the gap); planes 1..4 feed two or three accumulators in turn.
-                    // A ring of four fragments (2 x 16 bytes each), two ahead of the MFMAs; 96 MFMAs of 16 passes per column.
-                    constexpr int NF = 9 * HZ, RING = 4, PF = 2;
-                    uint4 xf[RING][2];
-                    auto x_read = [&](int f) {   // fragment f = g * 6 + i, i-th plane of the order above (compile-time after unrolling)
-                        const int i = f % HZ;
-                        const int hz = i == 0 ? 0 : (i == 1 ? HZ - 1 : i - 1);
-                        if (i == 0) col_addr(f / HZ);
-#pragma unroll
-                        for (int p = 0; p < 2; ++p) xf[f % RING][p] = *reinterpret_cast<const uint4*>(lds + a0 + hz * ZSTEP + p * PLB);
-                    };
-                    auto comp = [](const uint4& q, int c) {
-                        return __builtin_bit_cast(float, c == 0 ? q.x : (c == 1 ? q.y : (c == 2 ? q.z : q.w)));
-                    };
-#pragma unroll
-                    for (int f = 0; f < 2 + PF; ++f) x_read(f);
-#pragma unroll
-                    for (int g = 0; g < 9; ++g) {
-#pragma unroll
-                        for (int sub = 0; sub < 5; ++sub) {
-                            const int flast = g * HZ + (sub == 0 ? 1 : sub + 1);   // last fragment this substep multiplies
-                            if (sub == 0 && g != 0 && flast + PF - 1 < NF) x_read(flast + PF - 1);   // two fragments are consumed here
-                            if (!(g == 0 && sub == 0) && flast + PF < NF) x_read(flast + PF);
-                            // weight fragments of the next column, one tz per substep
-                            if (sub < 3 && g + 1 < 9 && !(TEM_ZR_ABL & 4)) {
-                                const int gn = g + 1, tz = sub;
-                                const int tap = tz * 9 + gn;
-#pragma unroll
-                                for (int p = 0; p < 2; ++p)
-                                    wq[gn & 1][tz][p] = zr_load4u(rw, woff_lane, wsoff + (unsigned)(tap * ts + p * 64) * 16u);
-                            }
-                            if (sub == 0) {
-                                const uint4* a_lo = xf[(g * HZ) % RING];
-                                const uint4* a_hi = xf[(g * HZ + 1) % RING];
-#pragma unroll
-                                for (int p = 0; p < 2; ++p)
-#pragma unroll
-                                    for (int c = 0; c < 4; ++c) {
-                                        acc[0] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(wq[g & 1][0][p], c), comp(a_lo[p], c), acc[0], 0, 0, 0);
-                                        acc[TZ - 1] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(wq[g & 1][2][p], c), comp(a_hi[p], c), acc[TZ - 1], 0, 0, 0);
-                                    }
-                            } else {
-                                const int hz = sub;   // halo planes 1 .. 4
-                                const uint4* a = xf[(g * HZ + sub + 1) % RING];
-#pragma unroll
-                                for (int p = 0; p < 2; ++p)
-#pragma unroll
-                                    for (int c = 0; c < 4; ++c)
-#pragma unroll
-                                        for (int tz = 0; tz < 3; ++tz) {
-                                            const int z = hz - tz;
-                                            if (z < 0 || z >= TZ) continue;
-                                            acc[z] = __builtin_amdgcn_mfma_f32_32x32x2f32(comp(wq[g & 1][tz][p], c), comp(a[p], c), acc[z], 0, 0, 0);
-                                        }
-                            }
-                            __builtin_amdgcn_sched_barrier(0);
-                        }
                     }
                 } else {
                 col_addr(0);
@@ -1153,9 +1071,6 @@ static void zr_variant(const TemConvCall& c, int mode, bool wide, F&& f) {
 // Split-K launch for shapes zr_geometry() declines only because they have too few (tile, column tile) units: the input
 // channels are cut into ks slices so that ks x units >= two per CU, the partial sums go to the workspace and the common
 // split-K epilogue (conv_mfma.hip) applies bias / activation / ReLU mask.  -> 1 launched, 0 not taken.
-#ifndef TEM_ZR_KS_FILL
-#define TEM_ZR_KS_FILL 4   // tenths of the tiled volume that must be real voxels for a split-K launch (measured: 8 -> 5: cfg 5 -0.2 ms, cfg 2 -0.04 ms, the 8^3 level is half padding; 5 -> 4: cfg 5 25.37 -> 25.04 ms, its 6 x 12 x 12 level is 42 % real; 3: 25.16)
-#endif
 // ks of the split-K launch for this shape (0: not taken): only shapes that zr_geometry() / pp_geometry() decline for
 // their unit count, tiles that are not mostly padding, at least two 16-channel chunks per slice
 int tem_conv_zr_splitk_ks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode) {

@@ -16,9 +16,6 @@ struct VecT<1> {
     typedef float type;
 };
 
-#ifndef TEM_POOL_NT
-#define TEM_POOL_NT 0
-#endif
 template <int VEC, typename T>
 __device__ __forceinline__ void ld_vec(const T* p, float (&v)[VEC]) {
     if constexpr (VEC == 8) {   // 16-bit tensors: 8 channels = one 16-byte access, as 4 fp32 channels are
@@ -35,11 +32,7 @@ __device__ __forceinline__ void st_vec(T* p, const float (&v)[VEC]) {
     if constexpr (VEC == 8) {
         act_st8(p, v);
     } else if constexpr (VEC == 4) {
-#if TEM_POOL_NT
-        act_st4_nt(p, make_float4(v[0], v[1], v[2], v[3]));
-#else
         act_st4(p, make_float4(v[0], v[1], v[2], v[3]));
-#endif
     } else {
         act_st1(p, v[0]);
     }

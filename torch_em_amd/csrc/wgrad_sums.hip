@@ -223,9 +223,6 @@ __global__ __launch_bounds__(512) void k_reduce_slabs_wsum(const float* __restri
 //   with z[u + (t - 1)] and T[tap] sums g[u] over the u with u + (t - 1) inside the volume.
 // Every reduction runs 4 lanes wide (slots) resp. 8 lanes wide (tap x co) with shuffles: no serial 100-step loops.
 // ---------------------------------------------------------------------------
-#ifndef TEM_NS_ABL
-#define TEM_NS_ABL 0   // profiling ablations: 1 no class totals, 2 no bias-gradient total, 4 no weight loop
-#endif
 #define NS_WPRE 32     // weights per thread loaded before the first phase (all of them for Cout <= 32)
 // The norm backward's second stage rides along (NormCoef.coef != nullptr): coef[n][c] = {a, m1, m2r, mean} exactly as
 // k_norm_bwd_finalize derives them from the (A, B) rows -- the same doubles in the same order -- when the channels of a
@@ -253,7 +250,7 @@ __global__ __launch_bounds__(1024) void k_norm_sums_from_wgrad(const float* __re
     const int64_t n_out = (int64_t)27 * Cin * Cout;
     const int cg = Cout >> 5;
     const int ci = blockIdx.x * 32 + (threadIdx.x >> 5), l8 = threadIdx.x & 31;  // last phase: 32 lanes per input channel
-    // Measured (TEM_NS_ABL builds, 32 -> 32 at 2 x 128^3, round 3): 39 us on 2-8 workgroups -- 14 for the class totals, 4 for
+    // Measured (ablation builds, 32 -> 32 at 2 x 128^3, round 3): 39 us on 2-8 workgroups -- 14 for the class totals, 4 for
     // the bias-gradient total, 15 for the weight loop at the end, 5 for everything else -- each phase a chain of 2-4
     // dependent round trips to data another XCD just wrote.  The loads of the LAST phase depend on nothing computed here:
     // they are issued first (weights of this thread's (channel, tap) for the first NS_WPRE output channels, its P entries)
@@ -263,7 +260,7 @@ __global__ __launch_bounds__(1024) void k_norm_sums_from_wgrad(const float* __re
     // and the value is dropped afterwards.
     float wpre[NS_WPRE];
     float ppre[2];
-    const bool wlane = ci < Cin && l8 < 27 && !(TEM_NS_ABL & 4);
+    const bool wlane = ci < Cin && l8 < 27;
     const unsigned wbase = wlane ? (unsigned)ci * 27u + (unsigned)l8 : 0u;
 #pragma unroll
     for (int k = 0; k < NS_WPRE; ++k) wpre[k] = w[(unsigned)k * (unsigned)Cin * 27u + wbase];   // Cout >= 32 = NS_WPRE
@@ -278,7 +275,7 @@ __global__ __launch_bounds__(1024) void k_norm_sums_from_wgrad(const float* __re
     float tot = 0.f;
     {
         const int co = e4 < Cout ? e4 : Cout - 1;
-        for (int sp = l4; sp < ((TEM_NS_ABL & 2) ? 0 : Ss); sp += 128) {
+        for (int sp = l4; sp < Ss; sp += 128) {
             float v[32];
 #pragma unroll
             for (int k = 0; k < 32; ++k) {
@@ -296,7 +293,7 @@ __global__ __launch_bounds__(1024) void k_norm_sums_from_wgrad(const float* __re
     }
     // class totals: one thread per entry (z class, y/x class, co), consecutive lanes on consecutive floats of a slot row, 32
     // slots in flight
-    for (int t = threadIdx.x; t < ((TEM_NS_ABL & 1) ? 0 : 27 * Cout); t += 1024) {
+    for (int t = threadIdx.x; t < 27 * Cout; t += 1024) {
         const int cz = t / (9 * Cout), rem = t % (9 * Cout);
         const int s0 = cz == 1 ? 0 : (cz == 0 ? D - 2 : D - 2 + H), s1 = cz == 1 ? D - 2 : s0 + H;
         float a = 0.f;
@@ -315,8 +312,6 @@ __global__ __launch_bounds__(1024) void k_norm_sums_from_wgrad(const float* __re
         }
         cls[t] = a;
     }
-    if (TEM_NS_ABL & 1)
-        for (int t = threadIdx.x; t < 27 * Cout; t += 1024) cls[t] = 0.f;
     __syncthreads();
     // the interior class (1,1,1) = total - everything else
     if (l4 == 0 && e4 < Cout) {
