@@ -79,22 +79,24 @@ int main(int argc, char** argv) {
     // the layout of a mode is the mode (tem_hip.h: TEM_WL_* are defined as TEM_ARITH_*)
     if (tem_conv_pack_weights(w, wp, Cout, Cin, 3, 3, 3, 0, mode, s)) { printf("pack failed: %s\n", tem_last_error()); return 1; }
     void* ws = nullptr;
-    const int64_t wsb = tem_conv_fwd_mfma_ws(N, D, H, W, Cin, Cout, 3, 3, 3);
+    const TemConvShape sh = {N, D, H, W, Cin, Cout, 3, 3, 3};
+    const TemPatchTiling pt = tem_fwd_patch_tiling(sh);   // the patch kernel's launch: split-K where its grid asks for it
+    const int64_t wsb = pt.ks > 1 ? pt.ks * sh.NV() * Cout * 4 : 0;
     if (wsb) CK(hipMalloc(&ws, wsb));
     auto run = [&]() {
         TemConvCall c;
         c.stx = c.sty = st;
         float* stp = use_norm && !use_ref ? stat : nullptr;
         // variants >= 1: straight into THIS executable's copy of conv_pp.hip (calls inside libtem_hip.so bind locally)
-        if (variant == 2 && tem_conv_fwd_zr(c, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, N, D,
-                                            H, W, Cin, Cout, 3, 3, 3, TEM_ACT_RELU, mode, stp, s) > 0)
-            return;
-        if (variant == 1 && tem_conv_fwd_pp(c, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, N, D,
-                                            H, W, Cin, Cout, 3, 3, 3, TEM_ACT_RELU, mode, stp, s))
-            return;
-        int rc = tem_conv_fwd_bf16x3(c, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, ws, wsb, N,
-                                     D, H, W, Cin, Cout, 3, 3, 3, TEM_ACT_RELU, mode, stp, s);
-        if (rc) { printf("launch failed: %s\n", tem_last_error()); exit(1); }
+        const ZrGeom zr = tem_zr_geometry(c, sh, mode);
+        const PpGeom pp = tem_pp_geometry(c, sh, mode);
+        if (variant == 2 && zr.ok)
+            tem_conv_fwd_zr(c, zr, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, sh, TEM_ACT_RELU, mode, stp, s);
+        else if (variant == 1 && pp.variant)
+            tem_conv_fwd_pp(pp, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, sh, TEM_ACT_RELU, mode, stp, s);
+        else
+            tem_conv_fwd_bf16x3(c, pt, pt.ks, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, ws, sh,
+                                TEM_ACT_RELU, mode, pt.ks > 1 ? nullptr : stp, s);
     };
     for (int i = 0; i < 3; ++i) run();
     CK(hipDeviceSynchronize());
@@ -103,9 +105,8 @@ int main(int argc, char** argv) {
         CK(hipMemcpy(ya.data(), y, ya.size() * 4, hipMemcpyDeviceToHost));
         CK(hipMemset(y, 0xff, V * Cout * 4));
         tem_set_option("conv_fwd_variant", 0);
-        int rc = tem_conv_fwd_bf16x3(TemConvCall{}, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, ws,
-                                     wsb, N, D, H, W, Cin, Cout, 3, 3, 3, TEM_ACT_RELU, mode, nullptr, s);
-        if (rc) { printf("reference launch failed: %s\n", tem_last_error()); exit(1); }
+        tem_conv_fwd_bf16x3(TemConvCall{}, pt, pt.ks, x, Cin, use_norm ? sc : nullptr, use_norm ? sf : nullptr, wp, b, y, Cout, ref, Cout, ws, sh,
+                            TEM_ACT_RELU, mode, nullptr, s);
         CK(hipDeviceSynchronize());
         tem_set_option("conv_fwd_variant", variant);
         CK(hipMemcpy(yb.data(), y, yb.size() * 4, hipMemcpyDeviceToHost));

@@ -80,6 +80,14 @@ extern "C" int tem_device_cus(void) {
     if (hipGetDeviceProperties(&prop, dev) != hipSuccess) return TEM_ELAUNCH;
     return prop.multiProcessorCount;
 }
+int tem_ncu() {
+    static int ncu = 0;
+    if (!ncu) {
+        ncu = tem_device_cus();
+        if (ncu <= 0) ncu = 256;
+    }
+    return ncu;
+}
 
 // ---------------------------------------------------------------------------
 // NCDHW <-> NDHWC.  Tiled through LDS so that both sides are coalesced:

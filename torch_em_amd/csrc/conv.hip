@@ -3,6 +3,7 @@
 // weight (un)packing, and the VALU kernels used where the MFMA path does not apply:
 // Cin==1 first layer (HBM-bound, 13 flop/B), the 32->Cout<=16 output projection
 // (HBM-bound, 0.9 flop/B) and the small test networks.
+#include <stdarg.h>
 #include "tem_common.h"
 #include "conv_internal.h"
 #include "conv_arith.h"
@@ -247,22 +248,190 @@ static void launch_fwd_generic(const TemConvCall& c, const float* x, int64_t x_l
         }                                                             \
     } while (0)
 
+// ---------------------------------------------------------------------------
+// The forward / data-gradient dispatch (DESIGN.md "Forward dispatch: one plan"): fwd_plan() decides ONCE which kernel a call
+// takes, with which geometry, and which statistics rows it writes.  conv3d_fwd_impl executes the plan; the dispatch queries
+// (tem_conv3d_fwd_kernel[_ld], tem_conv3d_fwd_stat_blocks[_ld]) and the argument checks of the _stats / _gscaled / _refnorm
+// calls print it for synthetic facts.  Order of preference: z-reuse, ping-pong, z-reuse split-K, 1x1 stream, patch; exact fp32
+// has no ping-pong and no stream instantiation (conv_arith.h), the VALU mode has the kernels of this file and conv_small.hip.
+// ---------------------------------------------------------------------------
+enum FwdKernel { FK_VALU, FK_ZR, FK_ZR_SPLITK, FK_PP, FK_STREAM1X1, FK_PATCH, FK_PATCH_FP32, FK_REFUSED };
+
+// what the decision depends on besides the call, the shape and the mode
+struct FwdFacts {
+    int64_t x_ld, y_ld, ref_ld;   // ref_ld 0: no ref
+    // operand groups on 16-byte boundaries (an absent operand counts as aligned)
+    bool xw16;      // x, packed weights, scale and shift
+    bool yref16;    // y and ref
+    bool yref_v4;   // y and ref on boundaries of 4 ELEMENTS (16-bit tensors: 8 bytes; the 1x1 stream and the cin1 kernel ask no more)
+    bool bias16;
+    bool scale;     // a pre-norm is applied to x
+    bool sigmoid;
+    bool stat;      // statistics rows are requested
+    int64_t ws_bytes;
+};
+
+struct FwdPlan {
+    FwdKernel kernel;
+    int ks;                  // FK_ZR_SPLITK / FK_PATCH / FK_PATCH_FP32: slices of the input channels (1: no split-K)
+    ZrGeom zr;               // FK_ZR, FK_ZR_SPLITK
+    PpGeom pp;               // FK_PP
+    TemPatchTiling patch;    // FK_PATCH, FK_PATCH_FP32
+    // rows [N][stat_blocks][Cout][2] the launch writes when it is asked for statistics, 0: none (such a request is refused).
+    // FK_STREAM1X1 answers for the patch kernel, which takes the launch when statistics are requested.
+    int64_t stat_blocks;
+    char error[320];         // FK_REFUSED: the message of the TEM_EINVAL the launch returns
+    // tem_conv3d_fwd_kernel(): 3 z-reuse, 4 its split-K launch, 1 / 2 ping-pong with that many column tiles per team, 0 the rest
+    int family() const { return kernel == FK_ZR ? 3 : kernel == FK_ZR_SPLITK ? 4 : kernel == FK_PP ? pp.CT : 0; }
+};
+
+static void plan_refuse(FwdPlan& p, const char* fmt, ...) __attribute__((format(printf, 2, 3)));
+static void plan_refuse(FwdPlan& p, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(p.error, sizeof(p.error), fmt, ap);
+    va_end(ap);
+    p.kernel = FK_REFUSED;
+    p.stat_blocks = 0;
+}
+
+static const char kSplitXLayout[] =
+    "tem_conv3d_fwd(split-bf16): x / packed weights must be 16-byte aligned with ld%%4==0 (16-bit storage: ld%%8==0)";
+
+// split-K factor of the z-reuse kernel for a shape neither team kernel takes directly (0: none)
+static int fwd_zr_splitk_ks(const TemConvCall& c, const ZrGeom& zr, const PpGeom& pp, const TemConvShape& sh, int mode) {
+    return pp.variant ? 0 : tem_zr_splitk_ks(c, zr, sh, mode);
+}
+
+static FwdPlan fwd_plan(const TemConvCall& c, const TemConvShape& sh, int mode, const FwdFacts& f) {
+    FwdPlan p = {};
+    p.kernel = FK_VALU;
+    p.ks = 1;
+    const bool ref = f.ref_ld != 0;
+    const bool ld4 = f.y_ld % 4 == 0 && f.ref_ld % 4 == 0;   // y / ref rows of whole 4-element vectors
+    if (mode == TEM_ARITH_VALU) {   // VALU kernels: only the small-Cin first-layer kernel (conv_small.hip) provides statistics
+        if (ld4 && f.yref_v4 && f.bias16 && !ref && sh.Cout % 4 == 0)
+            p.stat_blocks = tem_conv_fwd_cin1_stat_blocks(sh.D, sh.H, sh.W, sh.Cin, sh.Cout, sh.kd, sh.kh, sh.kw);
+        return p;
+    }
+    const bool split = tem_arith_split_fwd(mode);   // (any other MFMA mode runs the exact-fp32 kernels)
+    const char* const who = split ? "split-bf16" : "mfma";
+    if (sh.Cin % 16 || sh.Cout % 32) {
+        plan_refuse(p, "tem_conv3d_fwd(%s): needs Cin%%16==0 and Cout%%32==0 (got %d,%d)", who, sh.Cin, sh.Cout);
+        return p;
+    }
+    if (split && f.x_ld % (c.stx ? 8 : 4)) {
+        plan_refuse(p, kSplitXLayout);
+        return p;
+    }
+    const int64_t part_bytes = sh.NV() * sh.Cout * 4;   // one split-K slice of partial sums
+    // a team kernel (or the split-K launch) is meant for the shape but declines the layout: the patch kernel runs it, without
+    // statistics -- their rows would have another shape than the caller's buffer
+    bool no_rows = false;
+    // exact fp32 stays on the patch kernel when it cannot load x / weights / scale as 16-byte vectors (the split modes raise)
+    if (split || (mode == TEM_ARITH_FP32 && f.x_ld % 4 == 0 && f.xw16)) {
+        int64_t max_ld = f.x_ld > f.y_ld ? f.x_ld : f.y_ld;
+        if (f.ref_ld > max_ld) max_ld = f.ref_ld;
+        const bool plane = tem_plane32_ok(sh, max_ld);
+        // the team kernels' 16-byte epilogue; statistics of a masked output are never asked for
+        const bool epi = ld4 && f.yref16 && !f.sigmoid && !(f.stat && ref);
+        p.zr = tem_zr_geometry(c, sh, mode);
+        p.pp = tem_pp_geometry(c, sh, mode);
+        if (p.zr.ok && plane) {
+            if (epi && f.bias16) {
+                p.kernel = FK_ZR;
+                p.stat_blocks = ref ? 0 : (int64_t)p.zr.nZ * p.zr.nY * p.zr.nX * 4;
+                return p;
+            }
+            if (f.stat) {
+                plan_refuse(p, "tem_conv3d_fwd_stats / _ex: statistics were sized for the z-reuse kernel but this launch "
+                               "cannot take it (y / ref / bias need 16-byte alignment and ld %% 4 == 0, no ref, no sigmoid)");
+                return p;
+            }
+            no_rows = true;
+        }
+        if (p.pp.variant && plane) {   // (reads bias with scalar loads)
+            if (epi) {
+                p.kernel = FK_PP;
+                p.stat_blocks = ref || no_rows ? 0 : (int64_t)p.pp.nZ * p.pp.nY * p.pp.nX * p.pp.WM;
+                return p;
+            }
+            if (f.stat) {
+                plan_refuse(p, "tem_conv3d_fwd_stats: statistics were sized for the ping-pong kernel but this launch cannot take it "
+                               "(y / ref need 16-byte alignment and ld %% 4 == 0, no ref, no sigmoid)");
+                return p;
+            }
+            no_rows = true;
+        }
+        const int ks = fwd_zr_splitk_ks(c, p.zr, p.pp, sh, mode);
+        if (ks) {
+            const int64_t skb = tem_splitk_stat_blocks(sh.V(), sh.Cout);   // rows of the summing epilogue (0: it has none for this Cout)
+            // 32-bit offsets over x and the Cout-wide workspace; the epilogue handles ref, sigmoid and bias vectors
+            if (!(f.stat && !skb) && tem_plane32_ok(sh, f.x_ld > sh.Cout ? f.x_ld : sh.Cout) && ld4 && f.yref16 && f.bias16 &&
+                f.ws_bytes >= ks * part_bytes) {
+                p.kernel = FK_ZR_SPLITK;
+                p.ks = ks;
+                p.stat_blocks = skb;
+                return p;
+            }
+            if (f.stat && skb) {
+                plan_refuse(p, "tem_conv3d_fwd_stats: the split-K launch that writes the statistics needs its workspace "
+                               "(tem_conv3d_fwd_ws) and 16-byte aligned y / ref / bias");
+                return p;
+            }
+            no_rows = true;
+        }
+    }
+    const int key = sh.key();
+    if (key != 7 && key != 3 && key != 0) {
+        plan_refuse(p, "tem_conv3d_fwd(%s): kernel (%d,%d,%d) has no MFMA instantiation", who, sh.kd, sh.kh, sh.kw);
+        return p;
+    }
+    // patch kernels: split-K where the grid asks for it and the launch has the workspace and a 16-byte epilogue
+    p.patch = tem_fwd_patch_tiling(sh);
+    p.ks = p.patch.ks;
+    if (p.ks > 1 && !(ld4 && f.yref16 && f.bias16 && f.ws_bytes >= p.ks * part_bytes)) p.ks = 1;
+    if (!split) {
+        p.kernel = FK_PATCH_FP32;
+        if (f.stat)
+            plan_refuse(p, "tem_conv3d_fwd_stats: the exact-fp32 patch kernel writes no statistics (tem_conv3d_fwd_stat_blocks() == 0)");
+        return p;
+    }
+    p.stat_blocks = no_rows || p.patch.ks > 1 ? 0 : p.patch.per;
+    if (f.stat && !p.stat_blocks) {
+        plan_refuse(p, p.patch.ks > 1 ? "tem_conv3d_fwd_stats: this shape runs split-K (tem_conv3d_fwd_stat_blocks() == 0)"
+                                      : "tem_conv3d_fwd_stats: this launch cannot write statistics (tem_conv3d_fwd_stat_blocks_ld() == 0)");
+        return p;
+    }
+    // 1x1x1 as a streaming GEMM: no pre-norm, statistics or sigmoid; enough 32-voxel tiles to hide the k-loop's load latency
+    const bool stream = key == 0 && tem_option(TEM_OPT_CONV1X1_STREAM) && tem_stream1x1_takes(mode) && !f.scale && !f.stat &&
+                        !f.sigmoid && sh.NV() >= 16384 && ld4 && f.yref_v4 && f.bias16;
+    p.kernel = stream ? FK_STREAM1X1 : FK_PATCH;
+    return p;
+}
+
+static int64_t fwd_ws(const TemConvCall& c, const TemConvShape& sh, int mode) {
+    if (!mode || sh.Cin % 16 || sh.Cout % 32) return 0;
+    const TemPatchTiling t = tem_fwd_patch_tiling(sh);
+    int ks = t.ks > 1 ? t.ks : 0;
+    if (tem_arith_mfma_fwd(mode)) {   // the z-reuse kernel's split-K launch may want more slices than the patch kernel's
+        const int zk = fwd_zr_splitk_ks(c, tem_zr_geometry(c, sh, mode), tem_pp_geometry(c, sh, mode), sh, mode);
+        if (zk > ks) ks = zk;
+    }
+    return ks * sh.NV() * sh.Cout * 4;
+}
+
 extern "C" int64_t tem_conv3d_fwd_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                                      int use_mfma) {
     const TemConvCall c = conv_call(use_mfma);
-    if (!use_mfma || Cin % 16 || Cout % 32) return 0;
-    int64_t ws = tem_conv_fwd_mfma_ws(N, D, H, W, Cin, Cout, kd, kh, kw);
-    if (tem_arith_mfma_fwd(use_mfma)) {   // the z-reuse kernel's split-K launch may want more slices than the patch kernel's
-        const int64_t zk = (int64_t)tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma) * N * D * H * W * Cout * 4;
-        if (zk > ws) ws = zk;
-    }
-    return ws;
+    return fwd_ws(c, TemConvShape{N, D, H, W, Cin, Cout, kd, kh, kw}, use_mfma);
 }
 
 static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift,
                            const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref,
-                           int64_t ref_ld, void* ws, int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout,
-                           int kd, int kh, int kw, int act, int use_mfma, float* stat, tem_stream_t stream) {
+                           int64_t ref_ld, void* ws, int64_t ws_bytes, const TemConvShape& sh, int act, int use_mfma, float* stat,
+                           tem_stream_t stream) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout, kd = sh.kd, kh = sh.kh, kw = sh.kw;
     TEM_REQUIRE(x && w_packed && y, "tem_conv3d_fwd: null pointer");
     TEM_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && x_ld >= (c.x_cs ? 32 : Cin) &&
                     y_ld >= (c.y_cs ? 32 : Cout),
@@ -278,39 +447,56 @@ static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, c
     TEM_REQUIRE(!(stx || sty) || use_mfma != TEM_ARITH_FP32, "tem_conv3d_fwd: the exact-fp32 MFMA kernels take fp32 tensors only");
     hipStream_t s = (hipStream_t)stream;
     TEM_REQUIRE(!(c.x_cs || c.y_cs) || tem_arith_one_term(use_mfma), "tem_conv3d_fwd_ex: chunk strides need use_mfma 5 / 7");
-    if (tem_arith_split_fwd(use_mfma)) {
-        int rc = tem_conv_fwd_bf16x3(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H,
-                                     W, Cin, Cout, kd, kh, kw, act, use_mfma, stat, s);
-        if (rc != TEM_OK) return rc;
-        TEM_CHECK_LAUNCH("tem_conv3d_fwd(bf16x3)");
+    auto al16 = [](const void* ptr) { return (uintptr_t)ptr % 16 == 0; };
+    if (tem_arith_split_fwd(use_mfma)) {   // every split-precision kernel loads x / weights / scale as 16-byte vectors
+        TEM_REQUIRE(stx == sty, "tem_conv3d_fwd(split-bf16): x and y must have the same storage type");
+        TEM_REQUIRE(tem_storage_ok(use_mfma, stx),
+                    "tem_conv3d_fwd(split-bf16): 16-bit storage goes with the one-term mode of the same type (fp16: use_mfma 5, "
+                    "bf16: use_mfma 7), got storage %d with use_mfma %d", stx, use_mfma);
+        TEM_REQUIRE(al16(x) && al16(w_packed), kSplitXLayout);
+        TEM_REQUIRE(al16(scale) && al16(shift), "tem_conv3d_fwd(split-bf16): scale/shift must be 16-byte aligned");
+    }
+
+    const uintptr_t v4 = tem_st_align4(sty);
+    const FwdFacts facts = {x_ld, y_ld, ref ? ref_ld : 0,
+                            al16(x) && al16(w_packed) && al16(scale) && al16(shift), al16(y) && al16(ref),
+                            (uintptr_t)y % v4 == 0 && (uintptr_t)ref % v4 == 0, al16(bias),
+                            scale != nullptr, act == TEM_ACT_SIGMOID, stat != nullptr, ws ? ws_bytes : 0};
+    const FwdPlan p = fwd_plan(c, sh, use_mfma, facts);
+    if (p.kernel == FK_REFUSED) {
+        tem_set_error("%s", p.error);
+        return TEM_EINVAL;
+    }
+    // what only the z-reuse kernel honours
+    TEM_REQUIRE(!(c.x_cs || c.y_cs) || (p.kernel == FK_ZR && stx && !ref && !(c.x_cs && Cin % 32) && c.x_cs % 8 == 0 && c.y_cs % 8 == 0),
+                "tem_conv3d_fwd_ex: chunk strides (x_cs / y_cs) need 16-bit tensors on the z-reuse kernel (tem_conv3d_fwd_kernel() "
+                "== 3), no ref, strides %% 8 == 0");
+    TEM_REQUIRE(!c.in_amax || p.kernel == FK_ZR, "tem_conv3d_fwd_gscaled: the launch did not take the z-reuse kernel (alignment of y / ref?)");
+    TEM_REQUIRE(!c.ref_coef || p.kernel == FK_ZR, "tem_conv3d_fwd_refnorm: the launch did not take the z-reuse kernel (alignment of y / ref?)");
+    TEM_REQUIRE(!c.ref_coef || (ref && !stat && al16(c.ref_coef)), "tem_conv3d_fwd_refnorm: needs ref, no statistics, 16-byte aligned coefficients");
+    TEM_REQUIRE(!c.in_amax || (use_mfma == TEM_ARITH_F16X3 && !bias && !scale && !stat),
+                "tem_conv3d_fwd_gscaled: fp16 two-term layout, no bias / norm / statistics");
+
+    if (p.kernel != FK_VALU) {
+        static const char* const what[] = {"", "tem_conv3d_fwd(z-reuse)", "tem_conv3d_fwd(z-reuse split-K)", "tem_conv3d_fwd(ping-pong)",
+                                           "tem_conv3d_fwd(1x1 stream)", "tem_conv3d_fwd(bf16x3)", "tem_conv3d_fwd(mfma)"};
+        if (p.kernel == FK_ZR)
+            tem_conv_fwd_zr(c, p.zr, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, sh, act, use_mfma, stat, s);
+        else if (p.kernel == FK_ZR_SPLITK)
+            tem_conv_fwd_zr_splitk(c, p.zr, p.ks, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, sh, act, use_mfma, stat, s);
+        else if (p.kernel == FK_PP)
+            tem_conv_fwd_pp(p.pp, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, sh, act, use_mfma, stat, s);
+        else if (p.kernel == FK_STREAM1X1)
+            tem_conv1x1_stream(c, x, x_ld, w_packed, bias, y, y_ld, ref, ref_ld, sh, act, use_mfma, s);
+        else if (p.kernel == FK_PATCH)
+            tem_conv_fwd_bf16x3(c, p.patch, p.ks, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, sh, act, use_mfma, stat, s);
+        else
+            TEM_TRY(tem_conv_fwd_mfma(p.patch, p.ks, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, sh, act, s));
+        TEM_CHECK_LAUNCH(what[p.kernel]);
         return TEM_OK;
     }
-    if (use_mfma == TEM_ARITH_FP32 && Cin % 16 == 0 && Cout % 32 == 0 && x_ld % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)w_packed % 16 == 0) &&
-        (!scale || (((uintptr_t)scale % 16 == 0) && ((uintptr_t)shift % 16 == 0)))) {
-        // exact fp32 on the z-reuse team kernel (k_conv_zr<..., X32>, round 6): the levels with enough units directly, the
-        // 16^3 / 8^3 levels with split input channels; other shapes stay with k_conv_fwd_mfma[_p] below
-        const int zr = tem_conv_fwd_zr(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw,
-                                       act, TEM_ARITH_FP32, stat, s);
-        if (zr < 0) return TEM_EINVAL;
-        if (!zr && tem_conv_fwd_zr_splitk(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
-                                          Cout, kd, kh, kw, act, TEM_ARITH_FP32, stat, s)) {
-            TEM_CHECK_LAUNCH("tem_conv3d_fwd(fp32, z-reuse split-K)");
-            return TEM_OK;
-        }
-        if (zr) {
-            TEM_CHECK_LAUNCH("tem_conv3d_fwd(fp32, z-reuse)");
-            return TEM_OK;
-        }
-    }
-    TEM_REQUIRE(!stat || !use_mfma, "tem_conv3d_fwd_stats: the exact-fp32 patch kernel writes no statistics (tem_conv3d_fwd_stat_blocks() == 0)");
-    if (use_mfma) {
-        int rc = tem_conv_fwd_mfma(x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H,
-                                   W, Cin, Cout, kd, kh, kw, act, s);
-        if (rc != TEM_OK) return rc;
-        TEM_CHECK_LAUNCH("tem_conv3d_fwd(mfma)");
-        return TEM_OK;
-    }
-    const int64_t NV = (int64_t)N * D * H * W;
+    // VALU kernels: the first that takes the shape
+    const int64_t NV = sh.NV();
     if (tem_conv_fwd_cin1(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, N, D, H, W, Cin, Cout, kd, kh, kw, act,
                           stat, s)) {
         TEM_CHECK_LAUNCH("tem_conv3d_fwd(cin1)");
@@ -361,65 +547,18 @@ extern "C" int tem_conv3d_fwd(const float* x, int64_t x_ld, const float* scale, 
                               int64_t ref_ld, void* ws, int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout,
                               int kd, int kh, int kw, int act, int use_mfma, tem_stream_t stream) {
     const TemConvCall c = conv_call(use_mfma);
-    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
-                           Cout, kd, kh, kw, act, use_mfma, nullptr, stream);
+    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes,
+                           TemConvShape{N, D, H, W, Cin, Cout, kd, kh, kw}, act, use_mfma, nullptr, stream);
 }
 
-static inline bool ref_free_cin1_ok(int Cout) { return Cout % 4 == 0; }
-
-// What a tem_conv3d_fwd launch of this shape AND layout does: the kernel family it takes (tem_conv3d_fwd_kernel) and the
-// statistics rows it writes (tem_conv3d_fwd_stat_blocks) -- the launch conditions of conv3d_fwd_impl, tem_conv_fwd_zr,
-// tem_conv_fwd_pp and tem_conv_fwd_zr_splitk as one function.  ref_ld 0: no ref.  misaligned: a pointer of the launch
-// (x, y, ref, bias, scale, shift, packed weights) is off a 16-byte boundary.  Assumes the tem_conv3d_fwd_ws() workspace and
-// no sigmoid.  Shapes whose team kernel declines the layout get no statistics (the team launches raise when asked for
-// rows they cannot write; the caller runs tem_norm_stats).
-struct FwdPlan {
-    int family;
-    int64_t stat_blocks;
-};
-static FwdPlan fwd_plan(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, int64_t x_ld,
-                        int64_t y_ld, int64_t ref_ld, int misaligned) {
-    FwdPlan p = {0, 0};
-    int64_t max_ld = x_ld > y_ld ? x_ld : y_ld;
-    if (ref_ld > max_ld) max_ld = ref_ld;
-    // the team kernels' 16-byte epilogue (and the cin1 kernel's): y / ref with ld % 4 == 0, aligned pointers
-    const bool vec = y_ld % 4 == 0 && ref_ld % 4 == 0 && !misaligned;
-    if (use_mfma == TEM_ARITH_VALU) {   // VALU kernels: only the small-Cin first-layer kernel (conv_small.hip) provides statistics
-        if (vec && !ref_ld && ref_free_cin1_ok(Cout)) p.stat_blocks = tem_conv_fwd_cin1_stat_blocks(D, H, W, Cin, Cout, kd, kh, kw);
-        return p;
-    }
-    if (!tem_arith_mfma_fwd(use_mfma) || Cin % 16 || Cout % 32) return p;
-    // split-K launch of the z-reuse kernel: 32-bit offsets over x and its Cout-wide workspace
-    const bool sk_ok = vec && (int64_t)H * W * 8 * 4 * (x_ld > Cout ? x_ld : Cout) < (1ll << 31);
-    if (use_mfma == TEM_ARITH_FP32) {   // exact fp32: only the z-reuse kernel (direct or split-K) writes statistics
-        if (x_ld % 4 || misaligned) return p;   // -> the exact-fp32 patch kernel
-        const int64_t zrb = tem_conv_zr_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld);
-        if (zrb >= 0) {
-            if (vec) p = FwdPlan{3, ref_ld ? 0 : zrb};
-        } else if (tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma) && sk_ok) {
-            const int64_t skb = tem_conv_zr_splitk_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma);
-            p = FwdPlan{4, skb > 0 ? skb : 0};
-        }
-        return p;
-    }
-    if (x_ld % (c.stx ? 8 : 4)) return p;   // a precondition of the split-precision launches: they raise
-    const int64_t zrb = tem_conv_zr_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld);
-    const int64_t ppb = zrb >= 0 ? -1 : tem_conv_pp_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld);
-    if (zrb >= 0 || ppb >= 0) {
-        if (vec)
-            p = FwdPlan{zrb >= 0 ? 3 : tem_conv_pp_tiles(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, max_ld),
-                        ref_ld ? 0 : (zrb >= 0 ? zrb : ppb)};
-        return p;
-    }
-    if (tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)) {
-        if (sk_ok) {
-            const int64_t skb = tem_conv_zr_splitk_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma);
-            p = FwdPlan{4, skb > 0 ? skb : 0};
-        }
-        return p;   // (declined: the patch kernel runs it, without statistics)
-    }
-    p.stat_blocks = tem_conv_fwd_patch_stat_blocks(N, D, H, W, Cin, Cout, kd, kh, kw);
-    return p;
+// The plan of a launch of this shape and layout as the queries see it.  ref_ld 0: no ref.  misaligned: a pointer of the launch
+// (x, y, ref, bias, scale, shift, packed weights) is off a 16-byte boundary -- every operand group then counts as misaligned.
+// Assumes the tem_conv3d_fwd_ws() workspace, no pre-norm, no sigmoid.
+static FwdPlan fwd_query(const TemConvCall& c, const TemConvShape& sh, int mode, int64_t x_ld, int64_t y_ld, int64_t ref_ld,
+                         int misaligned) {
+    const bool al = !misaligned;
+    const FwdFacts f = {x_ld, y_ld, ref_ld, al, al, al, al, false, false, false, fwd_ws(c, sh, mode)};
+    return fwd_plan(c, sh, mode, f);
 }
 
 static int fwd_misaligned(const void* x, const void* scale, const void* shift, const void* w, const void* bias, const void* y,
@@ -431,13 +570,13 @@ static int fwd_misaligned(const void* x, const void* scale, const void* shift, c
 extern "C" int64_t tem_conv3d_fwd_stat_blocks_ld(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                                                  int use_mfma, int64_t x_ld, int64_t y_ld, int64_t ref_ld, int misaligned) {
     const TemConvCall c = conv_call(use_mfma);
-    return fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld, misaligned).stat_blocks;
+    return fwd_query(c, TemConvShape{N, D, H, W, Cin, Cout, kd, kh, kw}, use_mfma, x_ld, y_ld, ref_ld, misaligned).stat_blocks;
 }
 
 extern "C" int tem_conv3d_fwd_kernel_ld(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,
                                         int64_t x_ld, int64_t y_ld, int64_t ref_ld, int misaligned) {
     const TemConvCall c = conv_call(use_mfma);
-    return fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld, misaligned).family;
+    return fwd_query(c, TemConvShape{N, D, H, W, Cin, Cout, kd, kh, kw}, use_mfma, x_ld, y_ld, ref_ld, misaligned).family();
 }
 
 // the shape-only queries: dense, aligned x and y, no ref
@@ -453,11 +592,10 @@ extern "C" int tem_conv3d_fwd_kernel(int N, int D, int H, int W, int Cin, int Co
 // the argument checks of tem_conv3d_fwd_stats (also a tem_conv3d_fwd_ex with stat_part)
 static int fwd_stats_check(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift,
                            const float* w_packed, const float* bias, const float* y, int64_t y_ld, const float* ref, int64_t ref_ld,
-                           int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma,
-                           const float* stat_part, int64_t stat_blocks) {
+                           const TemConvShape& sh, int use_mfma, const float* stat_part, int64_t stat_blocks) {
     TEM_REQUIRE(stat_part, "tem_conv3d_fwd_stats: null statistics buffer");
-    const int64_t nblk = fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref ? ref_ld : 0,
-                                  fwd_misaligned(x, scale, shift, w_packed, bias, y, ref)).stat_blocks;
+    const int64_t nblk = fwd_query(c, sh, use_mfma, x_ld, y_ld, ref ? ref_ld : 0,
+                                   fwd_misaligned(x, scale, shift, w_packed, bias, y, ref)).stat_blocks;
     TEM_REQUIRE(stat_blocks > 0 && stat_blocks == nblk,
                 "tem_conv3d_fwd_stats: stat_blocks must be tem_conv3d_fwd_stat_blocks_ld() of this launch's layout (and > 0): "
                 "got %lld, the launch writes %lld", (long long)stat_blocks, (long long)nblk);
@@ -470,10 +608,10 @@ extern "C" int tem_conv3d_fwd_stats(const float* x, int64_t x_ld, const float* s
                                     int Cout, int kd, int kh, int kw, int act, int use_mfma, float* stat_part,
                                     int64_t stat_blocks, tem_stream_t stream) {
     const TemConvCall c = conv_call(use_mfma);
-    TEM_TRY(fwd_stats_check(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma,
-                            stat_part, stat_blocks));
-    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin,
-                           Cout, kd, kh, kw, act, use_mfma, stat_part, stream);
+    const TemConvShape sh = {N, D, H, W, Cin, Cout, kd, kh, kw};
+    TEM_TRY(fwd_stats_check(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, sh, use_mfma, stat_part, stat_blocks));
+    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, sh, act, use_mfma, stat_part,
+                           stream);
 }
 
 // ---------------------------------------------------------------------------
@@ -888,21 +1026,21 @@ extern "C" int tem_conv3d_wgrad_gscaled(const float* x, int64_t x_ld, const floa
 }
 
 // the argument checks of tem_conv3d_fwd_gscaled / _refnorm (also tem_conv3d_fwd_ex with in_amax / ref_coef).  Whether the launch
-// then really takes the z-reuse kernel is tem_conv_fwd_zr's answer: it fails a call that carries one and that it cannot run.
+// then really takes the z-reuse kernel is the plan of its real arguments: conv3d_fwd_impl fails a call that carries one otherwise.
 static int fwd_gscaled_check(const TemConvCall& c, const float* x, int64_t x_ld, const float* w_packed, const float* y, int64_t y_ld,
-                             const float* ref, int64_t ref_ld, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
+                             const float* ref, int64_t ref_ld, const TemConvShape& sh) {
     TEM_REQUIRE(c.in_amax, "tem_conv3d_fwd_gscaled: null in_amax");
-    TEM_REQUIRE(fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, TEM_ARITH_F16X3, x_ld, y_ld, ref ? ref_ld : 0,
-                         fwd_misaligned(x, nullptr, nullptr, w_packed, nullptr, y, ref)).family == 3,
+    TEM_REQUIRE(fwd_query(c, sh, TEM_ARITH_F16X3, x_ld, y_ld, ref ? ref_ld : 0,
+                          fwd_misaligned(x, nullptr, nullptr, w_packed, nullptr, y, ref)).family() == 3,
                 "tem_conv3d_fwd_gscaled: only launches that tem_conv3d_fwd_kernel_ld() reports as 3 (z-reuse kernel) take a "
                 "device-side prescale");
     return TEM_OK;
 }
 static int fwd_refnorm_check(const TemConvCall& c, const float* x, int64_t x_ld, const float* w_packed, const float* y, int64_t y_ld,
-                             const float* ref, int64_t ref_ld, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
+                             const float* ref, int64_t ref_ld, const TemConvShape& sh, int use_mfma) {
     TEM_REQUIRE(ref && c.ref_coef, "tem_conv3d_fwd_refnorm: null ref / coef");
-    TEM_REQUIRE(fwd_plan(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, x_ld, y_ld, ref_ld,
-                         fwd_misaligned(x, nullptr, nullptr, w_packed, c.ref_coef, y, ref)).family == 3,
+    TEM_REQUIRE(fwd_query(c, sh, use_mfma, x_ld, y_ld, ref_ld,
+                          fwd_misaligned(x, nullptr, nullptr, w_packed, c.ref_coef, y, ref)).family() == 3,
                 "tem_conv3d_fwd_refnorm: only launches that tem_conv3d_fwd_kernel_ld() reports as 3 (z-reuse kernel) apply a "
                 "norm backward in their epilogue");
     return TEM_OK;
@@ -914,9 +1052,10 @@ extern "C" int tem_conv3d_fwd_gscaled(const float* x, int64_t x_ld, const float*
                                       int kw, tem_stream_t stream) {
     TemConvCall c;
     c.in_amax = in_amax;
-    TEM_TRY(fwd_gscaled_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw));
-    return conv3d_fwd_impl(c, x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout,
-                           kd, kh, kw, TEM_ACT_NONE, TEM_ARITH_F16X3, nullptr, stream);
+    const TemConvShape sh = {N, D, H, W, Cin, Cout, kd, kh, kw};
+    TEM_TRY(fwd_gscaled_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, sh));
+    return conv3d_fwd_impl(c, x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, sh, TEM_ACT_NONE,
+                           TEM_ARITH_F16X3, nullptr, stream);
 }
 
 // Data gradient that lands behind a ReLU + norm: y = ref > 0 ? a*(conv) - m1 - (ref - mean)*m2r : 0 with coef[N][Cout][4] =
@@ -928,9 +1067,10 @@ extern "C" int tem_conv3d_fwd_refnorm(const float* x, int64_t x_ld, const float*
                                       tem_stream_t stream) {
     TemConvCall c = conv_call(use_mfma);
     c.ref_coef = coef;
-    TEM_TRY(fwd_refnorm_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma));
-    return conv3d_fwd_impl(c, x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout,
-                           kd, kh, kw, TEM_ACT_NONE, use_mfma, nullptr, stream);
+    const TemConvShape sh = {N, D, H, W, Cin, Cout, kd, kh, kw};
+    TEM_TRY(fwd_refnorm_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, sh, use_mfma));
+    return conv3d_fwd_impl(c, x, x_ld, nullptr, nullptr, w_packed, nullptr, y, y_ld, ref, ref_ld, ws, ws_bytes, sh, TEM_ACT_NONE,
+                           use_mfma, nullptr, stream);
 }
 
 extern "C" int tem_conv3d_wgrad_sums_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
@@ -957,6 +1097,7 @@ extern "C" int tem_conv3d_fwd_ex(const float* x, int64_t x_ld, const float* scal
                                  int use_mfma, const unsigned* in_amax, const float* ref_coef, float* stat_part,
                                  int64_t stat_blocks, int64_t x_cs, int64_t y_cs, TemByproducts* bp, tem_stream_t stream) {
     TemConvCall c = conv_call(use_mfma);
+    const TemConvShape sh = {N, D, H, W, Cin, Cout, kd, kh, kw};
     TEM_REQUIRE(!stat_part || (!in_amax && !ref_coef && !bp), "tem_conv3d_fwd_ex: stat_part excludes in_amax / ref_coef / by-products");
     TEM_REQUIRE(!(in_amax && ref_coef), "tem_conv3d_fwd_ex: in_amax and ref_coef exclude each other");
     TEM_REQUIRE(x_cs >= 0 && y_cs >= 0 && (!(x_cs || y_cs) || (!in_amax && !ref_coef && tem_arith_one_term(use_mfma))),
@@ -973,17 +1114,16 @@ extern "C" int tem_conv3d_fwd_ex(const float* x, int64_t x_ld, const float* scal
                     "tem_conv3d_fwd_ex: in_amax (the fp16 two-term data gradient) takes use_mfma 4 and no scale / shift / bias / act");
         c.stx = c.sty = TEM_ST_F32;   // as tem_conv3d_fwd_gscaled: an fp32-tensor mode
         c.in_amax = in_amax;
-        TEM_TRY(fwd_gscaled_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw));
+        TEM_TRY(fwd_gscaled_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, sh));
     } else if (ref_coef) {
         TEM_REQUIRE(!scale && !shift && !bias && act == TEM_ACT_NONE, "tem_conv3d_fwd_ex: ref_coef takes no scale / shift / bias / act");
         c.ref_coef = ref_coef;
-        TEM_TRY(fwd_refnorm_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma));
+        TEM_TRY(fwd_refnorm_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, sh, use_mfma));
     } else if (stat_part) {
-        TEM_TRY(fwd_stats_check(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma,
-                                stat_part, stat_blocks));
+        TEM_TRY(fwd_stats_check(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, sh, use_mfma, stat_part, stat_blocks));
     }
-    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
-                           kw, act, use_mfma, stat_part, stream);
+    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, sh, act, use_mfma, stat_part,
+                           stream);
 }
 
 extern "C" int tem_conv3d_wgrad_ex(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,

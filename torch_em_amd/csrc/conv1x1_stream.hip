@@ -138,21 +138,13 @@ static void stream_launch(const TemConvCall& c, const T* x, int64_t x_ld, const 
                            ref, ref_ld, NV, Cin, Cout, act, nmt, amax);
 }
 
-// false: not taken (a mode without an instantiation here: tem_stream1x1_takes; pre-norm, statistics, sigmoid -- the patch kernel
-// handles those).  Storage types (c.stx / c.sty): fp32, or the 16-bit type that IS the operand type of the mode (tem_storage_ok).
-bool tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* wp, const float* bias, float* y,
-                        int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act, int mode,
-                        const float* stat, hipStream_t s) {
-    const int st = c.stx;
-    if (c.sty != st) return false;
-    if (!tem_stream1x1_takes(mode) || !tem_storage_ok(mode, st)) return false;
-    const uintptr_t a8 = st ? 15 : 15, a4 = tem_st_align4(st) - 1;   // x: 16-byte loads either way; y / ref: vectors of 4 elements
-    if (scale || stat || act == TEM_ACT_SIGMOID) return false;
-    if (NV < 16384) return false;   // too few 32-voxel tiles to hide the k-loop's load latency: the split-K patch kernel wins
-    if (Cin % 16 || Cout % 32 || (x_ld & (st ? 7 : 3)) || (reinterpret_cast<uintptr_t>(x) & a8)) return false;
-    if ((y_ld & 3) || (reinterpret_cast<uintptr_t>(y) & a4) || (bias && (reinterpret_cast<uintptr_t>(bias) & 15)) ||
-        (ref && ((ref_ld & 3) || (reinterpret_cast<uintptr_t>(ref) & a4))))
-        return false;
+// Storage types (c.stx == c.sty): fp32, or the 16-bit type that IS the operand type of the mode (tem_storage_ok).  x: 16-byte
+// loads; y / ref: vectors of 4 elements.  At least 16384 voxels (fewer 32-voxel tiles do not hide the k-loop's load latency: the
+// split-K patch kernel wins) -- the plan (conv.hip) sends only such launches here.
+void tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, const float* wp, const float* bias, float* y, int64_t y_ld,
+                        const float* ref, int64_t ref_ld, const TemConvShape& sh, int act, int mode, hipStream_t s) {
+    const int st = c.stx, Cin = sh.Cin, Cout = sh.Cout;
+    const int64_t NV = sh.NV();
     auto go = [&](auto ns, auto f16, auto t) {
         using T = decltype(t);
         stream_launch<ns(), f16(), T>(c, (const T*)x, x_ld, wp, bias, (T*)y, y_ld, (const T*)ref, ref_ld, NV, Cin, Cout, act, s);
@@ -163,5 +155,4 @@ bool tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, cons
     else if (a.planes == 3) go(TemInt<3>{}, TemBool<false>{}, float{});
     else if (a.planes == 2) go(TemInt<2>{}, TemBool<false>{}, float{});
     else tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) { go(TemInt<1>{}, f16, float{}); });
-    return true;
 }

@@ -620,54 +620,17 @@ static void fwd_variant(int mode, int st, F&& f) {
     else f(FwdVariant<2, false>{});
 }
 
-int tem_conv_fwd_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
-                        const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
-                        int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
-                        int mode, float* stat, hipStream_t s) {
-    TEM_REQUIRE(Cin % 16 == 0 && Cout % 32 == 0, "tem_conv3d_fwd(split-bf16): needs Cin%%16==0 and Cout%%32==0 (got %d,%d)",
-                Cin, Cout);
-    const int st = c.stx;
-    TEM_REQUIRE(st == c.sty, "tem_conv3d_fwd(split-bf16): x and y must have the same storage type");
-    TEM_REQUIRE(tem_storage_ok(mode, st),
-                "tem_conv3d_fwd(split-bf16): 16-bit storage goes with the one-term mode of the same type (fp16: use_mfma 5, "
-                "bf16: use_mfma 7), got storage %d with use_mfma %d", st, mode);
-    TEM_REQUIRE(x_ld % (st ? 8 : 4) == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)wp % 16 == 0),
-                "tem_conv3d_fwd(split-bf16): x / packed weights must be 16-byte aligned with ld%%4==0 (16-bit storage: ld%%8==0)");
-    TEM_REQUIRE(!scale || (((uintptr_t)scale % 16 == 0) && ((uintptr_t)shift % 16 == 0)),
-                "tem_conv3d_fwd(split-bf16): scale/shift must be 16-byte aligned");
-    const int zr = tem_conv_fwd_zr(c, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, act,
-                                   mode, stat, s);
-    if (zr < 0) return TEM_EINVAL;
-    if (zr) return TEM_OK;
-    const int pp = tem_conv_fwd_pp(c, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, kd, kh, kw, act,
-                                   mode, stat, s);
-    if (pp < 0) return TEM_EINVAL;
-    if (pp) return TEM_OK;
-    if (tem_conv_fwd_zr_splitk(c, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh,
-                               kw, act, mode, stat, s))
-        return TEM_OK;
-    TEM_REQUIRE(!stat || tem_conv_zr_splitk_stat_blocks(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode) < 0,
-                "tem_conv3d_fwd_stats: the split-K launch that writes the statistics needs its workspace "
-                "(tem_conv3d_fwd_ws) and 16-byte aligned y / ref / bias");
-    if (kd == 1 && kh == 1 && kw == 1 && tem_option(TEM_OPT_CONV1X1_STREAM) &&
-        tem_conv1x1_stream(c, x, x_ld, scale, wp, bias, y, y_ld, ref, ref_ld, (int64_t)N * D * H * W, Cin, Cout, act, mode, stat, s))
-        return TEM_OK;
-    const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
-    const bool flat = (D == 1 && kd == 1);
-    const int TZ = flat ? 1 : 4, TY = flat ? 16 : 8, TX = flat ? 16 : 8;
-    const bool nr2 = (Cout % 64 == 0);
-    const int64_t nblk0 = (int64_t)N * ((D + TZ - 1) / TZ) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX) * (Cout / (nr2 ? 64 : 32));
-    int ks = tem_fwd_ksplit(nblk0, Cin / BCK);
-    const bool vec_ok = (y_ld % 4 == 0) && ((uintptr_t)y % 16 == 0) &&
-                        (!ref || (ref_ld % 4 == 0 && (uintptr_t)ref % 16 == 0)) && (!bias || (uintptr_t)bias % 16 == 0);
-    if (ks > 1 && (!ws || !vec_ok || ws_bytes < (int64_t)ks * N * D * H * W * Cout * 4)) ks = 1;
-    TEM_REQUIRE(!stat || ks == 1, "tem_conv3d_fwd_stats: this shape runs split-K (tem_conv3d_fwd_stat_blocks() == 0)");
+void tem_conv_fwd_bf16x3(const TemConvCall& c, const TemPatchTiling& t, int ks, const float* x, int64_t x_ld, const float* scale,
+                         const float* shift, const float* wp, const float* bias, float* y, int64_t y_ld, const float* ref,
+                         int64_t ref_ld, void* ws, const TemConvShape& sh, int act, int mode, float* stat, hipStream_t s) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout, key = sh.key(), st = c.stx;
+    const bool flat = t.flat;
     float* part = (float*)ws;
     // one argument list for every instantiation: the mode's variant x column tiles per workgroup x (kernel, patch) shape
     auto go = [&](auto KD, auto KH, auto KW, auto TZ, auto TY, auto TX) {
         fwd_variant(mode, st, [&](auto v) {
             using V = decltype(v);
-            tem_select_bool(nr2, [&](auto two) {
+            tem_select_bool(t.NR == 2, [&](auto two) {
                 launch_b<KD(), KH(), KW(), TZ(), TY(), TX(), two() ? 2 : 1, V::NS, V::F16, V::PS, typename V::T>(
                     x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, ks, part, stat, s);
             });
@@ -686,28 +649,7 @@ int tem_conv_fwd_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, cons
             go(I1{}, I1{}, I1{}, I1{}, I16{}, I16{});
         else
             go(I1{}, I1{}, I1{}, I4{}, I8{}, I8{});
-    } else {
-        tem_set_error("tem_conv3d_fwd(split-bf16): kernel (%d,%d,%d) has no MFMA instantiation", kd, kh, kw);
-        return TEM_EINVAL;
     }
-    return TEM_OK;
-}
-
-// ---------------------------------------------------------------------------
-
-// number of per-sample statistic blocks (= patches) the fused-statistics patch kernel writes, 0 when this shape cannot
-// produce them (split-K over the input channels, or no MFMA instantiation).  The team kernels answer for their own
-// launches first (tem_conv3d_fwd_stat_blocks_ld, conv.hip).
-int64_t tem_conv_fwd_patch_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
-    if (Cin % 16 || Cout % 32) return 0;
-    const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
-    if (key != 7 && key != 3 && key != 0) return 0;
-    const bool flat = (D == 1 && kd == 1);
-    const int TZ = flat ? 1 : 4, TY = flat ? 16 : 8, TX = flat ? 16 : 8;
-    const bool nr2 = (Cout % 64 == 0);
-    const int64_t per = (int64_t)((D + TZ - 1) / TZ) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX);
-    if (tem_fwd_ksplit((int64_t)N * per * (Cout / (nr2 ? 64 : 32)), Cin / BCK) > 1) return 0;
-    return per;
 }
 
 // ---------------------------------------------------------------------------

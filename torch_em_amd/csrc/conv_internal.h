@@ -4,6 +4,7 @@
 #include <hip/hip_runtime.h>
 #include <stdint.h>
 #include "../../include/tem_hip.h"
+#include "tem_common.h"
 
 // Everything a convolution launch needs beyond its tensors and its shape.  The extern "C" entry point (conv.hip) decodes its
 // arguments into one of these; every launcher and dispatch query takes the call it answers for as its first argument.
@@ -33,11 +34,51 @@ struct TemConvCall {
     }
 };
 
-int64_t tem_conv_fwd_mfma_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
-int tem_conv_fwd_mfma(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w_packed,
-                      const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
-                      int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
-                      hipStream_t s);
+// The shape of a convolution call: what the forward host functions pass around instead of nine ints
+struct TemConvShape {
+    int N, D, H, W, Cin, Cout, kd, kh, kw;
+    int64_t V() const { return (int64_t)D * H * W; }
+    int64_t NV() const { return (int64_t)N * D * H * W; }
+    int key() const { return (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3); }   // 7: 3x3x3, 3: 1x3x3, 0: 1x1x1
+};
+
+// ---- the forward / data-gradient dispatch: geometry helpers of the kernel files, called by the ONE plan function (conv.hip:
+// fwd_plan), and the launchers that execute what it planned.  A launcher decides nothing: its caller holds a plan that names it.
+// The team kernels (and the z-reuse split-K launch) address one halo / one patch with 32-bit byte offsets
+inline bool tem_plane32_ok(const TemConvShape& sh, int64_t ld) { return (int64_t)sh.H * sh.W * 8 * 4 * ld < (1ll << 31); }
+// units a launch needs for a team kernel: two per CU; option team_min_units replaces that, conv_fwd_variant == `forced` lifts it
+inline long long tem_team_min_units(int forced) {
+    const long long minu = tem_option(TEM_OPT_TEAM_MIN_UNITS);
+    return tem_option(TEM_OPT_CONV_FWD_VARIANT) == forced ? 1 : (minu > 0 ? minu : 2ll * tem_ncu());
+}
+// patch kernels (split-precision: conv_bf16x3.hip, exact fp32: conv_mfma.hip): patch extent, 32-column tiles per workgroup,
+// patches per sample, workgroups, and the split-K factor the grid asks for (1: none; 16 input channels per staged chunk)
+struct TemPatchTiling {
+    bool flat;
+    int TZ, TY, TX, NR;
+    int64_t per, nblk;
+    int ks;
+};
+TemPatchTiling tem_fwd_patch_tiling(const TemConvShape& sh);
+// conv_zr.hip: 4 x 16 x 8 tiles.  shape_ok: options, mode and shape admit the kernel; ok: ... with enough units for a direct launch
+struct ZrGeom {
+    int shape_ok, ok;
+    int nZ, nY, nX;
+    int64_t nunits;
+};
+// conv_pp.hip
+struct PpGeom {
+    int variant;  // 0: not handled here; 1: ping-pong teams, 4 x 8 x 8 voxel patch per team
+    int TZ, TY, TX, CT, WM;
+    int nZ, nY, nX;
+    int64_t nunits;
+};
+
+// conv_mfma.hip: the exact-fp32 patch kernel with ks slices of the input channels (> 1: partial sums in ws).  Raises on x /
+// weights / scale it cannot load as 16-byte vectors
+int tem_conv_fwd_mfma(const TemPatchTiling& t, int ks, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                      const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
+                      const TemConvShape& sh, int act, hipStream_t s);
 
 int64_t tem_conv_wgrad_mfma_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
 int tem_conv_wgrad_mfma(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
@@ -78,33 +119,30 @@ void tem_reduce_slabs(const float* part, int nchunks, int64_t n, int64_t chunk_s
 // planes, kind: TemArith::planes / ::pack of the layout
 int tem_pack_weights_bf16x3(const float* w, float* dst, int Cout, int Cin, int kd, int kh, int kw, int transpose,
                             int planes, int kind, hipStream_t s);
-int tem_conv_fwd_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
-                        const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
-                        int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
-                        int mode, float* stat, hipStream_t s);
-// statistics rows of the patch kernel (the launches the team kernels leave to it), 0 when it runs split-K
-int64_t tem_conv_fwd_patch_stat_blocks(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
-// conv_pp.hip: ping-pong team kernel for the levels with many patches (1 launched, 0 shape not taken, -1 error set)
-int tem_conv_fwd_pp(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
-                     const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H,
-                     int W, int Cin, int Cout, int kd, int kh, int kw, int act, int mode, float* stat, hipStream_t s);
-// max_ld: the largest leading dimension of x / y / ref (1: the shape alone)
-int64_t tem_conv_pp_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld);
-int tem_conv_pp_tiles(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld);
-// conv_zr.hip: z-reuse ping-pong kernel, 3x3x3 only (same return convention as tem_conv_fwd_pp)
-int tem_conv_fwd_zr(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp, const float* bias,
-                    float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H, int W, int Cin, int Cout,
-                    int kd, int kh, int kw, int act, int mode, float* stat, hipStream_t s);
-int tem_conv_fwd_zr_splitk(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
-                           const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
-                           int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
-                           int mode, float* stat, hipStream_t s);
-int tem_conv_zr_splitk_ks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode);
-int64_t tem_conv_zr_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld);
-// conv1x1_stream.hip: 1x1x1 convolution / data gradient as a streaming GEMM (false: not taken)
-bool tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* wp, const float* bias, float* y,
-                        int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act, int mode,
-                        const float* stat, hipStream_t s);
+// the split-precision patch kernel, ks as tem_conv_fwd_mfma; stat (ks == 1 only): [N][t.per][Cout][2]
+void tem_conv_fwd_bf16x3(const TemConvCall& c, const TemPatchTiling& t, int ks, const float* x, int64_t x_ld, const float* scale,
+                         const float* shift, const float* wp, const float* bias, float* y, int64_t y_ld, const float* ref,
+                         int64_t ref_ld, void* ws, const TemConvShape& sh, int act, int mode, float* stat, hipStream_t s);
+// conv_pp.hip: ping-pong team kernel for the levels with many patches; stat: [N][nZ * nY * nX * WM][Cout][2]
+PpGeom tem_pp_geometry(const TemConvCall& c, const TemConvShape& sh, int mode);
+void tem_conv_fwd_pp(const PpGeom& g, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
+                     const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, const TemConvShape& sh, int act,
+                     int mode, float* stat, hipStream_t s);
+// conv_zr.hip: z-reuse ping-pong kernel, 3x3x3 only; stat: [N][nZ * nY * nX * 4][Cout][2].  Honours c.in_amax, c.ref_coef, c.x_cs / y_cs
+ZrGeom tem_zr_geometry(const TemConvCall& c, const TemConvShape& sh, int mode);
+void tem_conv_fwd_zr(const TemConvCall& c, const ZrGeom& g, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                     const float* wp, const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld,
+                     const TemConvShape& sh, int act, int mode, float* stat, hipStream_t s);
+// ... with the input channels cut into ks slices, for a shape whose geometry g has too few units for a direct launch and that
+// the ping-pong kernel does not take either (0: no split-K launch for this shape).  ws: ks * NV * Cout floats;
+// stat: [N][tem_splitk_stat_blocks()][Cout][2], written by the summing epilogue
+int tem_zr_splitk_ks(const TemConvCall& c, const ZrGeom& g, const TemConvShape& sh, int mode);
+void tem_conv_fwd_zr_splitk(const TemConvCall& c, const ZrGeom& g, int ks, const float* x, int64_t x_ld, const float* scale,
+                            const float* shift, const float* wp, const float* bias, float* y, int64_t y_ld, const float* ref,
+                            int64_t ref_ld, void* ws, const TemConvShape& sh, int act, int mode, float* stat, hipStream_t s);
+// conv1x1_stream.hip: 1x1x1 convolution / data gradient as a streaming GEMM: no pre-norm, no statistics, no sigmoid
+void tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, const float* wp, const float* bias, float* y, int64_t y_ld,
+                        const float* ref, int64_t ref_ld, const TemConvShape& sh, int act, int mode, hipStream_t s);
 // shared with conv_mfma.hip
 int tem_fwd_ksplit(int64_t nblk, int nchunks);
 void tem_splitk_epilogue(int sty, const float* part, int ksplit, int64_t NV, int Cout, const float* bias, int act,
@@ -123,7 +161,6 @@ void tem_splitk_epilogue_bwd_sums(int sty, const float* part, int ksplit, int N,
                                   const float* ref, int64_t ref_ld, float* y, int64_t y_ld, const TemDgradSumsReq& rq,
                                   hipStream_t s);
 int64_t tem_splitk_stat_blocks(int64_t V, int Cout);
-int64_t tem_conv_zr_splitk_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode);
 void tem_splitk_epilogue_stats(int sty, const float* part, int ksplit, int N, int64_t V, int Cout, const float* bias, int act,
                                const float* ref, int64_t ref_ld, float* y, int64_t y_ld, float* stat, hipStream_t s);
 int64_t tem_conv_wgrad_bf16x3_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);

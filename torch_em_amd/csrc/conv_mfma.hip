@@ -736,25 +736,20 @@ void tem_splitk_epilogue(int sty, const float* part, int ksplit, int64_t NV, int
                                      Cout, bias, act, (const T*)ref, ref_ld, (T*)y, y_ld));
 }
 
-static void fwd_geometry(int N, int D, int H, int W, int Cout, int kd, bool& flat, int& TZ, int& TY, int& TX, int& NR,
-                         int64_t& nblk) {
-    flat = (D == 1 && kd == 1);
-    TZ = flat ? 1 : 4;
-    TY = flat ? 16 : 8;
-    TX = flat ? 16 : 8;
-    NR = (Cout % 64 == 0) ? 2 : 1;
-    nblk = (int64_t)N * ((D + TZ - 1) / TZ) * ((H + TY - 1) / TY) * ((W + TX - 1) / TX) * (Cout / (32 * NR));
-}
-
-int64_t tem_conv_fwd_mfma_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
-    (void)kh;
-    (void)kw;
-    bool flat;
-    int TZ, TY, TX, NR;
-    int64_t nblk;
-    fwd_geometry(N, D, H, W, Cout, kd, flat, TZ, TY, TX, NR, nblk);
-    int ks = tem_fwd_ksplit(nblk, Cin / CK);
-    return ks > 1 ? (int64_t)ks * N * D * H * W * Cout * 4 : 0;
+// the patch kernels' tiling (this file's and conv_bf16x3.hip's): 4 x 8 x 8 patches, 16 x 16 for flat (2-D) data; two 32-column
+// tiles per workgroup when Cout allows it
+TemPatchTiling tem_fwd_patch_tiling(const TemConvShape& sh) {
+    static_assert(CK == 16, "one chunk size for both patch kernels");
+    TemPatchTiling t;
+    t.flat = (sh.D == 1 && sh.kd == 1);
+    t.TZ = t.flat ? 1 : 4;
+    t.TY = t.flat ? 16 : 8;
+    t.TX = t.flat ? 16 : 8;
+    t.NR = (sh.Cout % 64 == 0) ? 2 : 1;
+    t.per = (int64_t)((sh.D + t.TZ - 1) / t.TZ) * ((sh.H + t.TY - 1) / t.TY) * ((sh.W + t.TX - 1) / t.TX);
+    t.nblk = sh.N * t.per * (sh.Cout / (32 * t.NR));
+    t.ks = tem_fwd_ksplit(t.nblk, sh.Cin / CK);
+    return t;
 }
 
 template <int KD, int KH, int KW, int TZ, int TY, int TX, int NR, int NW = 4>
@@ -771,11 +766,7 @@ static void launch_fwd(const float* x, int64_t x_ld, const float* scale, const f
     const bool halo32 = (int64_t)(TZ + KD - 1) * H * W * x_ld * 4 < (1ll << 31);
     const bool persistent = NW == 4 && halo32 && (pmode < 0 ? NR == 2 : pmode != 0);
     if constexpr (NW == 4) if (persistent) {
-        static int ncu = 0;
-        if (!ncu) {
-            ncu = tem_device_cus();
-            if (ncu <= 0) ncu = 256;
-        }
+        const int ncu = tem_ncu();
         const int bpc = NR == 1 ? 3 : TEM_MF_OCC2;
         const int64_t grid = nblk < (int64_t)ncu * bpc ? nblk : (int64_t)ncu * bpc;
         hipLaunchKernelGGL((k_conv_fwd_mfma_p<KD, KH, KW, TZ, TY, TX, NR>), dim3((unsigned)grid), dim3(256), ldsb, s, x,
@@ -794,12 +785,10 @@ static void launch_fwd(const float* x, int64_t x_ld, const float* scale, const f
     }
 }
 
-int tem_conv_fwd_mfma(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
-                      const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
-                      int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
-                      hipStream_t s) {
-    TEM_REQUIRE(Cin % 16 == 0 && Cout % 32 == 0, "tem_conv3d_fwd(mfma): needs Cin%%16==0 and Cout%%32==0 (got %d,%d)",
-                Cin, Cout);
+int tem_conv_fwd_mfma(const TemPatchTiling& t, int ks, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                      const float* wp, const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
+                      const TemConvShape& sh, int act, hipStream_t s) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout;
     TEM_REQUIRE(x_ld % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)wp % 16 == 0),
                 "tem_conv3d_fwd(mfma): x / packed weights must be 16-byte aligned with ld%%4==0");
     TEM_REQUIRE(!scale || (((uintptr_t)scale % 16 == 0) && ((uintptr_t)shift % 16 == 0)),
@@ -810,19 +799,11 @@ int tem_conv_fwd_mfma(const float* x, int64_t x_ld, const float* scale, const fl
         TEM_REQUIRE((int64_t)H * W * mld * 4 < (1ll << 31),
                     "tem_conv3d_fwd(mfma): one z-plane of y / ref must stay below 2 GiB (32-bit offsets inside a plane)");
     }
-    const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
-    bool flat;
-    int TZ, TY, TX, NR;
-    int64_t nblk0;
-    fwd_geometry(N, D, H, W, Cout, kd, flat, TZ, TY, TX, NR, nblk0);
-    const bool nr2 = NR == 2;
-    int ks = tem_fwd_ksplit(nblk0, Cin / CK);
-    const bool vec_ok = (y_ld % 4 == 0) && ((uintptr_t)y % 16 == 0) && (!ref || (ref_ld % 4 == 0 && (uintptr_t)ref % 16 == 0)) &&
-                        (!bias || (uintptr_t)bias % 16 == 0);
-    if (ks > 1 && (!ws || !vec_ok || ws_bytes < (int64_t)ks * N * D * H * W * Cout * 4)) ks = 1;
+    const int key = sh.key();
+    const bool flat = t.flat;
     float* part = (float*)ws;
     auto go = [&](auto KD, auto KH, auto KW, auto TZ, auto TY, auto TX) {
-        tem_select_bool(nr2, [&](auto two) {
+        tem_select_bool(t.NR == 2, [&](auto two) {
             launch_fwd<KD(), KH(), KW(), TZ(), TY(), TX(), two() ? 2 : 1>(x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N, D, H, W,
                                                                           Cin, Cout, act, ks, part, s);
         });
@@ -840,9 +821,6 @@ int tem_conv_fwd_mfma(const float* x, int64_t x_ld, const float* scale, const fl
             go(I1{}, I1{}, I1{}, I1{}, I16{}, I16{});
         else
             go(I1{}, I1{}, I1{}, I4{}, I8{}, I8{});
-    } else {
-        tem_set_error("tem_conv3d_fwd(mfma): kernel (%d,%d,%d) has no MFMA instantiation", kd, kh, kw);
-        return TEM_EINVAL;
     }
     return TEM_OK;
 }

@@ -515,52 +515,25 @@ __global__ __launch_bounds__(512, 2) void k_conv_pp(
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct PpGeom {
-    int variant;  // 0: not handled here; 1: ping-pong teams, 4 x 8 x 8 voxel patch per team
-    int TZ, TY, TX, CT, WM;
-    int nZ, nY, nX;
-    int64_t nunits;
-};
-
 // Which shapes run on the ping-pong kernel: 3x3x3 (and 1x3x3 with depth) kernels, two 16-bit planes per operand, and
 // enough (patch, column group) units to give every team of every CU at least one.
-static PpGeom pp_geometry(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld) {
+PpGeom tem_pp_geometry(const TemConvCall& c, const TemConvShape& sh, int mode) {
     PpGeom g = {};
-    const long long opt = tem_option(TEM_OPT_CONV_FWD_VARIANT);
-    if (opt == 0) return g;   // (2 = z-reuse kernel forced: shapes it does not take still come here)
+    if (tem_option(TEM_OPT_CONV_FWD_VARIANT) == 0) return g;   // (2 = z-reuse kernel forced: shapes it does not take still come here)
     if (!tem_pp_takes(mode, c)) return g;   // bf16x3, fp16x3 (scaled lo), one fp16 / bf16 term (mixed modes); fp32 tensors
-    if (!(kh == 3 && kw == 3 && (kd == 3 || kd == 1))) return g;
-    if (D < 4 || Cin % 16 || Cout % 32) return g;
-    if ((int64_t)H * W * 8 * 4 * max_ld >= (1ll << 31)) return g;  // 32-bit byte offsets inside one halo / one patch
-    static int ncu = 0;
-    if (!ncu) {
-        ncu = tem_device_cus();
-        if (ncu <= 0) ncu = 256;
-    }
-    g.CT = (Cout % 64 == 0) ? 2 : 1;
+    if (!(sh.kh == 3 && sh.kw == 3 && (sh.kd == 3 || sh.kd == 1))) return g;
+    if (sh.D < 4 || sh.Cin % 16 || sh.Cout % 32) return g;
+    g.CT = (sh.Cout % 64 == 0) ? 2 : 1;
     g.TZ = 4;
     g.TY = g.TX = 8;
     g.WM = (g.CT == 2) ? 2 : 4;
-    g.nZ = (D + g.TZ - 1) / g.TZ;
-    g.nY = (H + 7) / 8;
-    g.nX = (W + 7) / 8;
-    g.nunits = (int64_t)N * g.nZ * g.nY * g.nX * (Cout / (32 * g.CT));
-    const long long minu = tem_option(TEM_OPT_TEAM_MIN_UNITS);
-    if (g.nunits < (opt == 1 ? 1 : (minu > 0 ? minu : 2ll * ncu))) return g;
+    g.nZ = (sh.D + g.TZ - 1) / g.TZ;
+    g.nY = (sh.H + 7) / 8;
+    g.nX = (sh.W + 7) / 8;
+    g.nunits = (int64_t)sh.N * g.nZ * g.nY * g.nX * (sh.Cout / (32 * g.CT));
+    if (g.nunits < tem_team_min_units(1)) return g;
     g.variant = 1;
     return g;
-}
-
-int64_t tem_conv_pp_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld) {
-    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, max_ld);
-    if (!g.variant) return -1;
-    return (int64_t)g.nZ * g.nY * g.nX * g.WM;
-}
-
-// 32-column tiles per team of the instantiation this shape selects (1 or 2), 0 when the shape is not handled here
-int tem_conv_pp_tiles(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld) {
-    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, max_ld);
-    return g.variant ? g.CT : 0;
 }
 
 template <int KD, int KH, int KW, int TZ, int CT, bool F16, int NS = 2>
@@ -577,48 +550,25 @@ static void pp_launch(const PpGeom& g, const float* x, int64_t x_ld, const float
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
         attr = true;
     }
-    static int ncu = 0;
-    if (!ncu) {
-        ncu = tem_device_cus();
-        if (ncu <= 0) ncu = 256;
-    }
     int64_t grid = (g.nunits + 1) / 2;
-    if (grid > ncu) grid = ncu;
+    if (grid > tem_ncu()) grid = tem_ncu();
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(512), ldsb, s, x, x_ld, scale, shift,
                        reinterpret_cast<const uint4*>(wp), bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, g.nZ,
                        g.nY, g.nX, stat, (int)g.nunits);
 }
 
-// -> 1 when the launch was taken, 0 when the shape belongs to another kernel, -1 when the caller sized a statistics
-// buffer for this kernel (tem_conv_pp_stat_blocks) but an alignment condition of the launch fails: falling through to the
-// patch kernel would write a differently shaped partials buffer (tem_last_error is set)
-int tem_conv_fwd_pp(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
-                     const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H,
-                     int W, int Cin, int Cout, int kd, int kh, int kw, int act, int mode, float* stat, hipStream_t s) {
-    int64_t max_ld = x_ld > y_ld ? x_ld : y_ld;
-    if (ref && ref_ld > max_ld) max_ld = ref_ld;
-    const PpGeom g = pp_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, max_ld);
-    if (!g.variant) return 0;
-    // 16-byte epilogue accesses; statistics of a masked output are the patch kernel's business (never asked for together)
-    if ((y_ld % 4) || ((uintptr_t)y % 16) || (ref && ((ref_ld % 4) || ((uintptr_t)ref % 16))) || (stat && ref) ||
-        act == TEM_ACT_SIGMOID) {
-        if (stat) {
-            tem_set_error("tem_conv3d_fwd_stats: statistics were sized for the ping-pong kernel but this launch cannot take it "
-                          "(y / ref need 16-byte alignment and ld %% 4 == 0, no ref, no sigmoid)");
-            return -1;
-        }
-        return 0;
-    }
+void tem_conv_fwd_pp(const PpGeom& g, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
+                     const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, const TemConvShape& sh, int act,
+                     int mode, float* stat, hipStream_t s) {
     const TemArith& a = tem_arith(mode);
-    tem_select_bool(kd == 3, [&](auto k3) {
+    tem_select_bool(sh.kd == 3, [&](auto k3) {
         tem_select_bool(g.CT == 2, [&](auto ct2) {
             tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) {
                 tem_select_bool(a.planes == 1, [&](auto one) {
                     pp_launch<k3() ? 3 : 1, 3, 3, 4, ct2() ? 2 : 1, f16(), one() ? 1 : 2>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld,
-                                                                                    N, D, H, W, Cin, Cout, act, stat, s);
+                                                                                    sh.N, sh.D, sh.H, sh.W, sh.Cin, sh.Cout, act, stat, s);
                 });
             });
         });
     });
-    return 1;
 }

@@ -974,42 +974,21 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
 // ---------------------------------------------------------------------------
 // host side
 // ---------------------------------------------------------------------------
-struct ZrGeom {
-    int ok;
-    int nZ, nY, nX;
-    int64_t nunits;
-};
-
-// 3x3x3 kernels with two-plane (or the one-term mixed) layouts, 16-byte-vector friendly channel counts and at least one
-// unit per team of every CU (smaller launches stay with k_conv_pp / the split-K patch kernel).
-static ZrGeom zr_geometry(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld) {
+// 3x3x3 kernels with two-plane (or the one-term mixed) layouts, 16-byte-vector friendly channel counts (shape_ok) and at least
+// one unit per team of every CU (ok; smaller launches run with split input channels, or stay with k_conv_pp / the patch kernel).
+ZrGeom tem_zr_geometry(const TemConvCall& c, const TemConvShape& sh, int mode) {
     ZrGeom g = {};
     const long long opt = tem_option(TEM_OPT_CONV_FWD_VARIANT);
     if (opt == 0 || opt == 1) return g;
-    if (!tem_zr_takes(mode, c, Cin)) return g;
-    if (!(kd == 3 && kh == 3 && kw == 3)) return g;
-    if (D < 4 || Cin % 16 || Cout % 32) return g;
-    if ((int64_t)H * W * 8 * 4 * max_ld >= (1ll << 31)) return g;   // 32-bit byte offsets inside one halo / one patch
-    static int ncu = 0;
-    if (!ncu) {
-        ncu = tem_device_cus();
-        if (ncu <= 0) ncu = 256;
-    }
-    g.nZ = (D + 3) / 4;
-    g.nY = (H + 15) / 16;
-    g.nX = (W + 7) / 8;
-    g.nunits = (int64_t)N * g.nZ * g.nY * g.nX * (Cout / 32);
-    if (g.nunits >= (1ll << 31)) return g;
-    const long long minu = tem_option(TEM_OPT_TEAM_MIN_UNITS);
-    if (g.nunits < (opt == 2 ? 1 : (minu > 0 ? minu : 2ll * ncu))) return g;
-    g.ok = 1;
+    if (!tem_zr_takes(mode, c, sh.Cin)) return g;
+    if (sh.key() != 7 || sh.D < 4 || sh.Cin % 16 || sh.Cout % 32) return g;
+    g.shape_ok = 1;
+    g.nZ = (sh.D + 3) / 4;
+    g.nY = (sh.H + 15) / 16;
+    g.nX = (sh.W + 7) / 8;
+    g.nunits = (int64_t)sh.N * g.nZ * g.nY * g.nX * (sh.Cout / 32);
+    g.ok = g.nunits < (1ll << 31) && g.nunits >= tem_team_min_units(2);
     return g;
-}
-
-int64_t tem_conv_zr_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode, int64_t max_ld) {
-    const ZrGeom g = zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, max_ld);
-    if (!g.ok) return -1;
-    return (int64_t)g.nZ * g.nY * g.nX * 4;
 }
 
 // tile-order blocks (see decode() in the kernel): up to 4 x 4 x 4 tiles, each extent a divisor of the tile count
@@ -1021,8 +1000,8 @@ static int zr_tile_blocks(const ZrGeom& g) {
 
 template <int NS, bool F16, int MODE, bool KSPLIT = false, bool WIDE = false, typename T = float, bool X32 = false, bool XS = false>
 static void zr_launch(const TemConvCall& c, const ZrGeom& g, const float* x_, int64_t x_ld, const float* scale, const float* shift, const float* wp,
-                      const float* bias, float* y_, int64_t y_ld, const float* ref_, int64_t ref_ld, int N, int D, int H, int W,
-                      int Cin, int Cout, int act, float* stat, const unsigned* in_amax, hipStream_t s, int ks = 1) {
+                      const float* bias, float* y_, int64_t y_ld, const float* ref_, int64_t ref_ld, const TemConvShape& sh,
+                      int act, float* stat, const unsigned* in_amax, hipStream_t s, int ks = 1) {
     constexpr size_t ldsb = (size_t)2 * NS * 1080 * 32 + 4 * 32 * 144;   // two tiles + the epilogue's transpose scratch
     static_assert(ldsb <= 160 * 1024, "LDS budget");
     const T* x = reinterpret_cast<const T*>(x_);
@@ -1034,16 +1013,12 @@ static void zr_launch(const TemConvCall& c, const ZrGeom& g, const float* x_, in
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
         attr = true;
     }
-    static int ncu = 0;
-    if (!ncu) {
-        ncu = tem_device_cus();
-        if (ncu <= 0) ncu = 256;
-    }
-    int64_t grid = XS ? g.nunits : (g.nunits + 1) / 2;   // (XS: one team per workgroup)
-    if (grid > ncu) grid = ncu;
+    const int64_t nunits = g.nunits * ks;
+    int64_t grid = XS ? nunits : (nunits + 1) / 2;   // (XS: one team per workgroup)
+    if (grid > tem_ncu()) grid = tem_ncu();
     unsigned* const out_amax = (MODE == 2 || MODE == 3) ? c.take_output_amax() : nullptr;
     hipLaunchKernelGGL(kern, dim3((unsigned)grid), dim3(XS ? 256 : 512), ldsb, s, x, x_ld, scale, shift, reinterpret_cast<const uint4*>(wp),
-                       bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, g.nZ, g.nY, g.nX, stat, (int)g.nunits, in_amax, ks,
+                       bias, y, y_ld, ref, ref_ld, sh.N, sh.D, sh.H, sh.W, sh.Cin, sh.Cout, act, g.nZ, g.nY, g.nX, stat, (int)nunits, in_amax, ks,
                        zr_tile_blocks(g), out_amax, (int64_t)(sizeof(T) == 2 ? c.x_cs : 0), (int64_t)(sizeof(T) == 2 && !KSPLIT ? c.y_cs : 0));
 }
 
@@ -1068,59 +1043,32 @@ static void zr_variant(const TemConvCall& c, int mode, bool wide, F&& f) {
     else tem_select_bool(a.pack == TEM_PK_F16_LO12, [&](auto f16) { f(ZrVariant<2, f16()>{}); });
 }
 
-// Split-K launch for shapes zr_geometry() declines only because they have too few (tile, column tile) units: the input
+// Split-K launch for shapes tem_zr_geometry() declines only because they have too few (tile, column tile) units: the input
 // channels are cut into ks slices so that ks x units >= two per CU, the partial sums go to the workspace and the common
-// split-K epilogue (conv_mfma.hip) applies bias / activation / ReLU mask.  -> 1 launched, 0 not taken.
-// ks of the split-K launch for this shape (0: not taken): only shapes that zr_geometry() / pp_geometry() decline for
-// their unit count, tiles that are not mostly padding, at least two 16-channel chunks per slice
-int tem_conv_zr_splitk_ks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode) {
-    const long long opt = tem_option(TEM_OPT_CONV_FWD_VARIANT);
-    if (opt == 0 || opt == 1 || !tem_option(TEM_OPT_ZR_SPLITK)) return 0;
-    if (!tem_zr_takes(mode, c, Cin)) return 0;
-    if (!(kd == 3 && kh == 3 && kw == 3) || D < 4 || Cin % 16 || Cout % 32) return 0;
+// split-K epilogue (conv_mfma.hip) applies bias / activation / ReLU mask.
+// ks for this shape (0: no such launch): tiles that are not mostly padding, at least two 16-channel chunks per slice
+int tem_zr_splitk_ks(const TemConvCall& c, const ZrGeom& g, const TemConvShape& sh, int mode) {
+    if (!g.shape_ok || g.ok || !tem_option(TEM_OPT_ZR_SPLITK)) return 0;
     const bool t16 = c.stx != 0;   // 16-bit storage: slices of whole 32-channel chunks
-    if (zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, 1).ok) return 0;
-    if (tem_conv_pp_tiles(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, 1)) return 0;
-    static int ncu = 0;
-    if (!ncu) {
-        ncu = tem_device_cus();
-        if (ncu <= 0) ncu = 256;
-    }
-    const int nZ = (D + 3) / 4, nY = (H + 15) / 16, nX = (W + 7) / 8;
     // tiles of 4 x 16 x 8 voxels: at most 60 % of the tiled volume may be padding (an 8^3 level has 50 %, 6 x 12 x 12 has 58 %)
-    if ((int64_t)D * H * W * 10 < (int64_t)nZ * 4 * nY * 16 * nX * 8 * TEM_ZR_KS_FILL) return 0;
-    const int64_t units = (int64_t)N * nZ * nY * nX * (Cout / 32);
-    const int nch = Cin / 16;
+    if (sh.V() * 10 < (int64_t)g.nZ * 4 * g.nY * 16 * g.nX * 8 * TEM_ZR_KS_FILL) return 0;
+    const int nch = sh.Cin / 16;
     for (int d = 2; d <= nch / 2; ++d)
-        if (nch % d == 0 && units * d >= 2ll * ncu && !(t16 && (nch / d) % 2)) return d;
+        if (nch % d == 0 && g.nunits * d >= 2ll * tem_ncu() && !(t16 && (nch / d) % 2)) return d;
     return 0;
 }
 
-int tem_conv_fwd_zr_splitk(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
-                           const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
-                           int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
-                           int mode, float* stat, hipStream_t s) {
-    // stat: [N][tem_conv_zr_splitk_stat_blocks()][Cout][2] -- the epilogue also writes the statistics partials of y
-    const int ks = ws ? tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode) : 0;
-    if (!ks) return 0;
-    if (stat && !tem_splitk_stat_blocks((int64_t)D * H * W, Cout)) return 0;
-    if ((int64_t)H * W * 8 * 4 * (x_ld > Cout ? x_ld : Cout) >= (1ll << 31)) return 0;
-    if ((y_ld % 4) || ((uintptr_t)y % 16) || (ref && ((ref_ld % 4) || ((uintptr_t)ref % 16))) || (bias && ((uintptr_t)bias % 16)))
-        return 0;
-    const int64_t NV = (int64_t)N * D * H * W;
-    if (ws_bytes < (int64_t)ks * NV * Cout * 4) return 0;
-    ZrGeom g = {};
-    g.nZ = (D + 3) / 4;
-    g.nY = (H + 15) / 16;
-    g.nX = (W + 7) / 8;
-    g.nunits = (int64_t)N * g.nZ * g.nY * g.nX * (Cout / 32) * ks;
-    g.ok = 1;
+void tem_conv_fwd_zr_splitk(const TemConvCall& c, const ZrGeom& g, int ks, const float* x, int64_t x_ld, const float* scale,
+                            const float* shift, const float* wp, const float* bias, float* y, int64_t y_ld, const float* ref,
+                            int64_t ref_ld, void* ws, const TemConvShape& sh, int act, int mode, float* stat, hipStream_t s) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout;
+    const int64_t NV = sh.NV();
     float* part = (float*)ws;
     const bool wide = tem_arith_one_term(mode) && (Cin / 16 / ks) % 2 == 0 && (tem_option(TEM_OPT_ZR_WIDE) || c.stx);   // slices of whole 32-channel chunks
     zr_variant(c, mode, wide, [&](auto v) {
         using V = decltype(v);
-        zr_launch<V::NS, V::F16, 0, true, V::WIDE, typename V::T, V::X32, V::XS>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, N, D,
-                                                                             H, W, Cin, Cout, TEM_ACT_NONE, nullptr, nullptr, s, ks);
+        zr_launch<V::NS, V::F16, 0, true, V::WIDE, typename V::T, V::X32, V::XS>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, sh,
+                                                                             TEM_ACT_NONE, nullptr, nullptr, s, ks);
     });
     TemDgradSumsReq rq = {nullptr, 0, nullptr, nullptr, 0, nullptr, 0};
     if (!stat && c.wants(TEM_BP_NORM_SUMS)) {
@@ -1135,74 +1083,28 @@ int tem_conv_fwd_zr_splitk(const TemConvCall& c, const float* x, int64_t x_ld, c
         tem_splitk_epilogue_bwd_sums(c.sty, part, ks, N, (int64_t)D * H * W, Cout, bias, act, ref, ref_ld, y, y_ld, rq, s);
     } else
         tem_splitk_epilogue(c.sty, part, ks, NV, Cout, bias, act, ref, ref_ld, y, y_ld, s);
-    return 1;
-}
-
-// statistics partial rows per sample when tem_conv_fwd_zr_splitk takes the launch with stat != NULL (-1: it does not)
-int64_t tem_conv_zr_splitk_stat_blocks(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int mode) {
-    if (!tem_conv_zr_splitk_ks(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode)) return -1;
-    const int64_t nb = tem_splitk_stat_blocks((int64_t)D * H * W, Cout);
-    return nb > 0 ? nb : -1;
 }
 
 // c.in_amax (tem_conv3d_fwd_gscaled): device word with max |input|, the launch prescales its input by a power of two derived from
 // it.  c.ref_coef (tem_conv3d_fwd_refnorm): coef[N][Cout][4], the launch applies the ReLU mask of `ref` AND the backward of the
-// norm behind it in its epilogue (MODE 3).  Only this launcher honours them: a caller that passes one must see 1 come back.
-// -> 1 launched, 0 shape not taken, -1 error (statistics sized for this kernel but the launch cannot take it)
-static int zr_not_taken(const TemConvCall& c) {
-    if (c.in_amax) tem_set_error("tem_conv3d_fwd_gscaled: the launch did not take the z-reuse kernel (alignment of y / ref?)");
-    if (c.ref_coef) tem_set_error("tem_conv3d_fwd_refnorm: the launch did not take the z-reuse kernel (alignment of y / ref?)");
-    return c.in_amax || c.ref_coef ? -1 : 0;
-}
-int tem_conv_fwd_zr(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp, const float* bias,
-                    float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H, int W, int Cin, int Cout,
-                    int kd, int kh, int kw, int act, int mode, float* stat, hipStream_t s) {
-    int64_t max_ld = x_ld > y_ld ? x_ld : y_ld;
-    if (ref && ref_ld > max_ld) max_ld = ref_ld;
-    const ZrGeom g = zr_geometry(c, N, D, H, W, Cin, Cout, kd, kh, kw, mode, max_ld);
-    const bool strided = c.x_cs != 0 || c.y_cs != 0;
-    if (strided && (!g.ok || !c.stx || ref || (c.x_cs && Cin % 32) || (c.x_cs % 8) || (c.y_cs % 8))) {
-        tem_set_error("tem_conv3d_fwd_ex: chunk strides (x_cs / y_cs) need 16-bit tensors on the z-reuse kernel (tem_conv3d_fwd_kernel() "
-                      "== 3), no ref, strides %% 8 == 0");
-        return -1;
-    }
-    if (!g.ok) return zr_not_taken(c);
-    if ((y_ld % 4) || ((uintptr_t)y % 16) || (ref && ((ref_ld % 4) || ((uintptr_t)ref % 16))) || (stat && ref) ||
-        (bias && ((uintptr_t)bias % 16)) || act == TEM_ACT_SIGMOID) {
-        if (stat || strided) {
-            tem_set_error("tem_conv3d_fwd_stats / _ex: statistics (or chunk strides) were sized for the z-reuse kernel but this launch "
-                          "cannot take it (y / ref / bias need 16-byte alignment and ld %% 4 == 0, no ref, no sigmoid)");
-            return -1;
-        }
-        return zr_not_taken(c);
-    }
+// norm behind it in its epilogue (MODE 3).  Only this launcher honours them.
+void tem_conv_fwd_zr(const TemConvCall& c, const ZrGeom& g, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                     const float* wp, const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld,
+                     const TemConvShape& sh, int act, int mode, float* stat, hipStream_t s) {
     const float* rcoef = c.ref_coef;
-    if (rcoef) {
-        if (!ref || stat || ((uintptr_t)rcoef % 16)) {
-            tem_set_error("tem_conv3d_fwd_refnorm: needs ref, no statistics, 16-byte aligned coefficients");
-            return -1;
-        }
-    }
     const unsigned* in_amax = c.in_amax;
-    if (in_amax) {
-        if (mode != TEM_ARITH_F16X3 || bias || scale || stat) {
-            tem_set_error("tem_conv3d_fwd_gscaled: fp16 two-term layout, no bias / norm / statistics");
-            return -1;
-        }
-    }
     // one-term modes: 32 channels per phase whenever the channel count allows it (whole 128-byte lines per staging phase)
-    const bool wide = tem_arith_one_term(mode) && Cin % 32 == 0 && tem_option(TEM_OPT_ZR_WIDE);
+    const bool wide = tem_arith_one_term(mode) && sh.Cin % 32 == 0 && tem_option(TEM_OPT_ZR_WIDE);
     zr_variant(c, mode, wide, [&](auto v) {
         using V = decltype(v);
         // epilogue MODE: 1 statistics, 3 ReLU mask of ref + norm backward from rcoef (in the `stat` slot), 2 ReLU mask of ref, 0 plain
         auto go = [&](auto m, float* st) {
-            zr_launch<V::NS, V::F16, m(), false, V::WIDE, typename V::T, V::X32, V::XS>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, N,
-                                                                                D, H, W, Cin, Cout, act, st, in_amax, s);
+            zr_launch<V::NS, V::F16, m(), false, V::WIDE, typename V::T, V::X32, V::XS>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, sh,
+                                                                                act, st, in_amax, s);
         };
         if (stat) go(TemInt<1>{}, stat);
         else if (ref && rcoef) go(TemInt<3>{}, const_cast<float*>(rcoef));
         else if (ref) go(TemInt<2>{}, stat);
         else go(TemInt<0>{}, stat);
     });
-    return 1;
 }

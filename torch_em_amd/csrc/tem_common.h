@@ -30,6 +30,8 @@ enum {
     TEM_OPT_COUNT
 };
 long long tem_option(int id);
+// compute units of the current device, read once (tem_device_cus(); 256, the MI355X's, where there is no device to ask)
+int tem_ncu();
 
 #define TEM_REQUIRE(cond, ...)                 \
     do {                                       \
