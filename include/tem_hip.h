@@ -656,6 +656,16 @@ int tem_boundary_target(const int64_t* labels, float* out, int D, int H, int W,
  * "subpixel" changes the output shape to 2n-1 and cannot be a training target: not provided. */
 int tem_boundary_target_mode(const int64_t* labels, float* out, int D, int H, int W,
                              int add_binary_target, int mode, tem_stream_t stream);
+/* NoToBackgroundBoundaryTransform (transform/label.py:133-188; kind 0, key_label = bg_label) and
+ * BoundaryTransformWithIgnoreLabel (:192-244; kind 1, key_label = mask_label = ignore_label): the boundaries of the
+ * labels (mode as above) with the boundaries of the binary image (labels != key_label) resp. (labels == key_label)
+ * overwritten by mask_label, both from one read of the neighbourhood.  labels int64 [N][D][H][W];
+ * out int8 [N][C][D][H][W], channels [binary?][boundaries]; the binary channel is (labels != key_label) resp.
+ * (labels != 0) with voxels equal to mask_label overwritten by it.  mask_label must fit int8. */
+int tem_boundary_target_masked(const int64_t* labels, int8_t* out, int N, int D, int H, int W, int mode, int kind,
+                               int64_t key_label, int64_t mask_label, int add_binary_target, tem_stream_t stream);
+/* OneHotTransform (transform/label.py:330-353): out float32 [N][C][V] = (labels[n][v] == ids[c]); ids: HOST int64 [C]. */
+int tem_onehot_target(const int64_t* labels, const int64_t* ids, int C, float* out, int N, int64_t V, tem_stream_t stream);
 /* offsets: HOST array [n_off][3] (z,y,x); 2-D data: D==1 and z offset 0.
  * out channels: [binary?] + n_off affinities (1 = different/invalid) [+ (binary mask?) + n_off mask].
  * has_ignore==0: no ignore label (mask = in-bounds only). */
@@ -693,6 +703,25 @@ int tem_pod_size_apply(int* ids, const int* keep, const int* newid, int N, int64
 int64_t tem_pod_ws(int N, int64_t V, int ndim, int flags);
 int tem_pod_targets(const int* ids, float* out, int N, int D, int H, int W, int ndim, const float* sampling, int flags,
                     float fill, void* ws, int64_t ws_bytes, tem_stream_t stream);
+/* Vector (feature-transform) EDT, the kernel behind DistanceTransform (transform/label.py:356-451, where
+ * bioimage_cpp's vector_difference_transform stands).  labels int64 [N][D][H][W] (2-D: D == 1); T = voxels equal to
+ * foreground_id.  vec int32 [N][3][V]: the offset (z, y, x) = t - x from every voxel x to a nearest voxel t of T;
+ * d2 int32 [N][V]: its exact squared length (0 on T); empty int32 [N]: 1 where the sample has no voxel of T -- there vec
+ * is 0 and d2 is TEM_VDT_NONE.  Unit sampling, integer arithmetic only.  Among equally near targets the separable
+ * passes (x, then y, then z) each keep the candidate with the smallest index along their axis; no atomics: two runs are
+ * bit-identical.  Limits as tem_pod_targets: extents up to 4096, N*D*H*W < 2^31 (TEM_EINVAL before any launch). */
+#define TEM_VDT_NONE 0x3fffffff
+int tem_vector_edt(const int64_t* labels, int64_t foreground_id, int* vec, int* d2, int* empty, int N, int D, int H, int W,
+                   tem_stream_t stream);
+/* DistanceTransform's targets from tem_vector_edt's outputs, following _compute_distances (:390-400),
+ * _compute_directed_distances (:402-411) and the empty case (:413-417) step by step, in double, stored as float32:
+ * out [N][C][V], channels [distances?][directed x ndim?].  flags: 1 distances, 2 directed_distances, 4 normalize,
+ * 8 invert, 16 clip to max_distance.  The directed channels are normalised / inverted with maxima over the reference's
+ * axes (1, 2) of [ndim, *spatial]: one per channel for 2-D labels, one per (channel, x column) for 3-D labels.  All maxima
+ * and the empty-sample decision stay on the device.  ws: tem_distance_targets_ws bytes. */
+int64_t tem_distance_targets_ws(int N, int W);
+int tem_distance_targets(const int* vec, const int* d2, const int* empty, float* out, int N, int D, int H, int W, int ndim,
+                         int flags, double max_distance, void* ws, int64_t ws_bytes, tem_stream_t stream);
 /* DistanceLoss / DiceBasedDistanceLoss (loss/distance_based.py:7-68) on p, t: float [N][3][V] with strides
  * (sn, sc, sv).  Channel 0: Dice (eps_fg); channels 1, 2: Dice (eps_dist) or, mse != 0, MSELoss(reduction="mean"),
  * of p*m and t*m with m = t[:, 0] if mask_bg else 1.  sums: device double[12] (per channel: sum pm*tm, sum pm^2,

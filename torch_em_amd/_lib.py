@@ -128,6 +128,12 @@ SIGNATURES = {
     "tem_pod_ws": (c_i64, [c_int, c_i64, c_int, c_int]),
     "tem_pod_targets": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, ctypes.POINTER(c_float), c_int, c_float,
                                 c_vp, c_i64, c_vp]),
+    "tem_vector_edt": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp]),
+    "tem_distance_targets_ws": (c_i64, [c_int, c_int]),
+    "tem_distance_targets": (c_int, [c_vp, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_double, c_vp, c_i64,
+                                     c_vp]),
+    "tem_boundary_target_masked": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_i64, c_i64, c_int, c_vp]),
+    "tem_onehot_target": (c_int, [c_vp, ctypes.POINTER(c_i64), c_int, c_vp, c_int, c_i64, c_vp]),
     "tem_dist_loss_ws": (c_i64, []),
     "tem_dist_loss_fwd": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_int, c_i64, c_int, c_int,
                                   c_double, c_double, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp]),

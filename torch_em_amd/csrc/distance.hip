@@ -1,5 +1,7 @@
 // distance.hip -- distance-based instance segmentation on device:
 //   * PerObjectDistanceTransform targets (reference transform/label.py:454-633), batched [N][D][H][W] (2-D: D == 1);
+//   * the vector EDT and the DistanceTransform targets (reference transform/label.py:356-451; tem_vector_edt,
+//     tem_distance_targets, further down);
 //   * the DistanceLoss / DiceBasedDistanceLoss sums and gradient (reference loss/distance_based.py).
 //
 // Transform passes (tem_pod_*; the Python side adds torch.sort / torch.cumsum for the id compaction):
@@ -542,6 +544,286 @@ extern "C" int tem_pod_targets(const int* ids, float* out, int N, int D, int H, 
     hipLaunchKernelGGL(k_pod_chmax, dim3(grid), dim3(256), 0, st, ids, f, ob, G);
     hipLaunchKernelGGL(k_pod_write, dim3(grid), dim3(256), 0, st, ids, f, ob, G, fill, out);
     TEM_CHECK_LAUNCH("tem_pod_targets");
+    return TEM_OK;
+}
+
+// ---------------------------------------------------------------------------------------------------------------
+// Vector (feature-transform) EDT and the DistanceTransform targets (reference transform/label.py:356-451).
+//
+// tem_vector_edt: T = voxels equal to foreground_id; per voxel x the integer offset v(x) = t - x to a nearest t in T and
+// |v|^2, all in int32: exact by construction.  The same separable lower envelope as k_pod_edt, one pass per axis (x, y,
+// then z), a workgroup per line, the line staged in LDS; each pass carries the offsets found by the passes before it
+// along with the value.  After the x pass d2(i) = vx(i)^2 with vx the offset to the nearest target of the row; a later
+// pass along axis a picks j minimising d2(j) + (i - j)^2, sets v_a(i) = j - i and copies the earlier components from j,
+// so v(i) always points at a target voxel at squared distance d2(i), and the minimum over j is the minimum over T.
+// Tie rule: candidates j are scanned in ascending index along the axis being processed and replace the best so far
+// only when strictly smaller (`<`): among equally near candidates the smallest j wins, in every pass.  No atomics.
+// A line (or sample) without any target keeps d2 = VDT_NONE and offset 0; empty[n] = (d2 of the sample's first voxel
+// == VDT_NONE), read after the last pass: a sample has a target iff every voxel found one.
+// Brute force over the line like k_pod_edt: O(L^2) per line, priced in profiles/label_targets_bench.txt.
+// ---------------------------------------------------------------------------------------------------------------
+#define VDT_NONE TEM_VDT_NONE   // 0x3fffffff: above every squared distance (3 * 4095^2), and VDT_NONE + 4095^2 still fits an int
+
+// vec [N][3][V] (z, y, x), d2 [N][V].  axis 2 reads the labels; axes 1 and 0 update vec / d2 in place (a line is read
+// into LDS whole before any of it is written, and lines are disjoint).
+__global__ __launch_bounds__(256) void k_vdt_pass(const int64_t* __restrict__ lab, int64_t fg, int* __restrict__ vec,
+                                                  int* __restrict__ d2, int N, int D, int H, int W, int axis) {
+    __shared__ int lf[POD_MAX_LINE];   // value
+    __shared__ int la[POD_MAX_LINE];   // carried x offset (axes 1, 0)
+    __shared__ int lb[POD_MAX_LINE];   // carried y offset (axis 0)
+    const int64_t HW = (int64_t)H * W, V = HW * D;
+    int L;
+    int64_t stride, nl;
+    if (axis == 2) {
+        L = W;
+        stride = 1;
+        nl = (int64_t)N * D * H;
+    } else if (axis == 1) {
+        L = H;
+        stride = W;
+        nl = (int64_t)N * D * W;
+    } else {
+        L = D;
+        stride = HW;
+        nl = (int64_t)N * HW;
+    }
+    for (int64_t l = blockIdx.x; l < nl; l += gridDim.x) {
+        int64_t n, off;   // sample and offset of the line's first voxel inside it
+        if (axis == 2) {
+            n = l / ((int64_t)D * H);
+            off = (l % ((int64_t)D * H)) * W;
+        } else if (axis == 1) {
+            n = l / ((int64_t)D * W);
+            const int64_t r = l % ((int64_t)D * W);
+            off = (r / W) * HW + r % W;
+        } else {
+            n = l / HW;
+            off = l % HW;
+        }
+        int* vz = vec + n * 3 * V + off;
+        int* vy = vz + V;
+        int* vx = vy + V;
+        int* dd = d2 + n * V + off;
+        __syncthreads();   // the previous line's readers are done with the LDS
+        for (int i = threadIdx.x; i < L; i += 256) {
+            if (axis == 2) {
+                lf[i] = lab[n * V + off + i] == fg ? 0 : VDT_NONE;
+            } else {
+                lf[i] = dd[i * stride];
+                la[i] = vx[i * stride];
+                if (axis == 0) lb[i] = vy[i * stride];
+            }
+        }
+        __syncthreads();
+        for (int i = threadIdx.x; i < L; i += 256) {
+            int best = VDT_NONE, bj = -1;
+            for (int j = 0; j < L; ++j) {
+                const int t = i - j, c = lf[j] + t * t;
+                if (c < best) {
+                    best = c;
+                    bj = j;
+                }
+            }
+            dd[i * stride] = best;
+            if (axis == 2) {
+                vz[i] = 0;
+                vy[i] = 0;
+                vx[i] = bj < 0 ? 0 : bj - i;
+            } else if (axis == 1) {
+                vy[i * stride] = bj < 0 ? 0 : bj - i;
+                vx[i * stride] = bj < 0 ? 0 : la[bj];
+            } else {
+                vz[i * stride] = bj < 0 ? 0 : bj - i;
+                vy[i * stride] = bj < 0 ? 0 : lb[bj];
+                vx[i * stride] = bj < 0 ? 0 : la[bj];
+            }
+        }
+    }
+}
+
+__global__ void k_vdt_empty(const int* __restrict__ d2, int* __restrict__ empty, int N, int64_t V) {
+    const int n = blockIdx.x * blockDim.x + threadIdx.x;
+    if (n < N) empty[n] = d2[n * V] == VDT_NONE ? 1 : 0;
+}
+
+static bool vdt_shape_ok(const char* who, int N, int D, int H, int W) {
+    if (!pod_shape_ok(N, D, H, W)) {
+        tem_set_error("%s: bad shape (N*D*H*W must be positive and below 2^31)", who);
+        return false;
+    }
+    if (D > POD_MAX_LINE || H > POD_MAX_LINE || W > POD_MAX_LINE) {
+        tem_set_error("%s: spatial extents up to %d supported", who, POD_MAX_LINE);
+        return false;
+    }
+    return true;
+}
+
+extern "C" int tem_vector_edt(const int64_t* labels, int64_t foreground_id, int* vec, int* d2, int* empty, int N, int D,
+                              int H, int W, tem_stream_t stream) {
+    TEM_REQUIRE(labels && vec && d2 && empty, "tem_vector_edt: null pointer");
+    if (!vdt_shape_ok("tem_vector_edt", N, D, H, W)) return TEM_EINVAL;
+    hipStream_t st = (hipStream_t)stream;
+    hipLaunchKernelGGL(k_vdt_pass, dim3(POD_BLOCKS), dim3(256), 0, st, labels, foreground_id, vec, d2, N, D, H, W, 2);
+    hipLaunchKernelGGL(k_vdt_pass, dim3(POD_BLOCKS), dim3(256), 0, st, labels, foreground_id, vec, d2, N, D, H, W, 1);
+    if (D > 1) hipLaunchKernelGGL(k_vdt_pass, dim3(POD_BLOCKS), dim3(256), 0, st, labels, foreground_id, vec, d2, N, D, H, W, 0);
+    hipLaunchKernelGGL(k_vdt_empty, dim3((unsigned)tem_cdiv(N, 64)), dim3(64), 0, st, d2, empty, N, (int64_t)D * H * W);
+    TEM_CHECK_LAUNCH("tem_vector_edt");
+    return TEM_OK;
+}
+
+// ---- DistanceTransform finishing pass -------------------------------------------------------------------------------
+// The maxima the normalisation needs, as integers (the offsets and d2 are integers; clipping and the division by a
+// positive constant are monotone, so max and clip / divide commute): per sample max d2, and per group max |v_c| and
+// max v_c.  A group is what the reference's `max(axis=(1, 2), keepdims=True)` on [ndim, *spatial] leaves: 2-D labels
+// one per channel; 3-D labels one per (channel, x column) -- the axes (1, 2) are z and y there, a quirk of the
+// reference that is mirrored, not repaired.  Slots per sample: [0] max d2, [1 + c * W + x] max |v_c|,
+// [1 + (3 + c) * W + x] max v_c (2-D labels use x = 0 only).  Integer atomicMax: order-independent.
+enum { DT_DIST = 1, DT_DIRECTED = 2, DT_NORMALIZE = 4, DT_INVERT = 8, DT_CLIP = 16 };
+
+__device__ __forceinline__ int64_t dt_slots(int W) { return 1 + 6 * (int64_t)W; }
+
+__global__ __launch_bounds__(256) void k_dt_init(int* __restrict__ mx, int N, int W) {
+    const int64_t S = dt_slots(W), NS = S * N;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < NS; g += (int64_t)gridDim.x * 256)
+        mx[g] = g % S <= 3 * (int64_t)W ? 0 : INT_MIN;
+}
+
+// grid (column chunks of 256, row chunks, N): a thread owns one x column and walks rows (z, y) of its chunk
+__global__ __launch_bounds__(256) void k_dt_max(const int* __restrict__ vec, const int* __restrict__ d2,
+                                                int* __restrict__ mx, int D, int H, int W, int ndim) {
+    const int64_t rows = (int64_t)D * H, V = rows * W;
+    const int n = blockIdx.z, x = blockIdx.x * 256 + threadIdx.x;
+    int md = 0, ma[3] = {0, 0, 0}, ms[3] = {INT_MIN, INT_MIN, INT_MIN};
+    if (x < W) {
+        const int* v = vec + (int64_t)n * 3 * V;
+        const int* d = d2 + (int64_t)n * V;
+        for (int64_t r = blockIdx.y; r < rows; r += gridDim.y) {
+            const int64_t g = r * W + x;
+            md = max(md, d[g]);
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                const int q = v[c * V + g];
+                ma[c] = max(ma[c], abs(q));
+                ms[c] = max(ms[c], q);
+            }
+        }
+    }
+    int* m = mx + n * dt_slots(W);
+    if (ndim == 3 && x < W) {
+#pragma unroll
+        for (int c = 0; c < 3; ++c) {
+            atomicMax(&m[1 + c * (int64_t)W + x], ma[c]);
+            atomicMax(&m[1 + (3 + c) * (int64_t)W + x], ms[c]);
+        }
+    }
+    // whole-sample maxima: wave reduction, one atomic per wave (all lanes take part; idle lanes hold the identities)
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {
+        md = max(md, __shfl_xor(md, o, 64));
+        if (ndim == 2) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                ma[c] = max(ma[c], __shfl_xor(ma[c], o, 64));
+                ms[c] = max(ms[c], __shfl_xor(ms[c], o, 64));
+            }
+        }
+    }
+    if (lane_id() == 0) {
+        atomicMax(&m[0], md);
+        if (ndim == 2) {
+#pragma unroll
+            for (int c = 0; c < 3; ++c) {
+                atomicMax(&m[1 + c * (int64_t)W], ma[c]);
+                atomicMax(&m[1 + (3 + c) * (int64_t)W], ms[c]);
+            }
+        }
+    }
+}
+
+// out [N][C][V], channels [distances?][directed x ndim?], following _compute_distances / _compute_directed_distances
+// step by step in double, rounded once to float32.  An empty sample (no target voxel) takes the reference's fill vector
+// (`fill` in every component) through the same steps.
+__global__ __launch_bounds__(256) void k_dt_write(const int* __restrict__ vec, const int* __restrict__ d2,
+                                                  const int* __restrict__ empty, const int* __restrict__ mx,
+                                                  float* __restrict__ out, int N, int D, int H, int W, int ndim, int flags,
+                                                  double maxd, double fill) {
+    const int64_t V = (int64_t)D * H * W, NV = V * N;
+    const int nc = ((flags & DT_DIST) ? 1 : 0) + ((flags & DT_DIRECTED) ? ndim : 0);
+    const double eps = 1e-7;
+    for (int64_t g = (int64_t)blockIdx.x * 256 + threadIdx.x; g < NV; g += (int64_t)gridDim.x * 256) {
+        const int64_t n = g / V, v = g % V;
+        const int x = ndim == 3 ? (int)(v % W) : 0;
+        const bool e = empty[n] != 0;
+        const int* m = mx + n * dt_slots(W);
+        float* o = out + n * nc * V + v;
+        int k = 0;
+        if (flags & DT_DIST) {
+            const double dfill = sqrt(fill * fill * ndim);   // |(fill, ..., fill)|
+            double d = e ? dfill : sqrt((double)d2[g]), top = e ? dfill : sqrt((double)m[0]);
+            if (flags & DT_CLIP) {
+                d = fmin(fmax(d, 0.0), maxd);
+                top = fmin(fmax(top, 0.0), maxd);
+            }
+            if (flags & DT_NORMALIZE) {
+                const double den = top + eps;
+                d /= den;
+                top /= den;
+            }
+            if (flags & DT_INVERT) d = top - d;
+            o[V * k++] = (float)d;
+        }
+        if (flags & DT_DIRECTED) {
+            for (int c = 3 - ndim; c < 3; ++c) {
+                double q = e ? fill : (double)vec[(n * 3 + c) * V + v];
+                double ma = e ? fill : (double)m[1 + c * (int64_t)W + x];
+                double ms = e ? fill : (double)m[1 + (3 + c) * (int64_t)W + x];
+                if (flags & DT_CLIP) {
+                    q = fmin(fmax(q, -maxd), maxd);
+                    ma = fmin(ma, fabs(maxd));   // max |clip(v)| = clip(max |v|) for the symmetric interval
+                    ms = fmin(fmax(ms, -maxd), maxd);
+                }
+                if (flags & DT_NORMALIZE) {
+                    const double den = ma + eps;
+                    q /= den;
+                    ms /= den;
+                }
+                if (flags & DT_INVERT) q = ms - q;
+                o[V * k++] = (float)q;
+            }
+        }
+    }
+}
+
+extern "C" int64_t tem_distance_targets_ws(int N, int W) { return (int64_t)N * (1 + 6 * (int64_t)W) * sizeof(int); }
+
+extern "C" int tem_distance_targets(const int* vec, const int* d2, const int* empty, float* out, int N, int D, int H, int W,
+                                    int ndim, int flags, double max_distance, void* ws, int64_t ws_bytes,
+                                    tem_stream_t stream) {
+    TEM_REQUIRE(vec && d2 && empty && out && ws, "tem_distance_targets: null pointer");
+    if (!vdt_shape_ok("tem_distance_targets", N, D, H, W)) return TEM_EINVAL;
+    TEM_REQUIRE(ndim == 3 || (ndim == 2 && D == 1), "tem_distance_targets: bad shape (2-D labels need D == 1)");
+    TEM_REQUIRE((flags & ~31) == 0 && (flags & (DT_DIST | DT_DIRECTED)),
+                "tem_distance_targets: at least one of distances and directed distances required");
+    TEM_REQUIRE(N <= 65535, "tem_distance_targets: at most 65535 samples per call");
+    if (ws_bytes < tem_distance_targets_ws(N, W)) {
+        tem_set_error("tem_distance_targets: workspace too small");
+        return TEM_EWS;
+    }
+    // reference :413-417: 0 if invert else sqrt(|shape|^2 / 2)
+    const double sumsq = (ndim == 3 ? (double)D * D : 0.0) + (double)H * H + (double)W * W;
+    const double fill = (flags & DT_INVERT) ? 0.0 : sqrt(sumsq / 2);
+    hipStream_t st = (hipStream_t)stream;
+    int* mx = (int*)ws;
+    const int64_t rows = (int64_t)D * H, NV = rows * W * N;
+    const int gx = (int)tem_cdiv(W, 256);
+    int64_t gy = tem_cdiv(2048, (int64_t)gx * N);
+    if (gy > rows) gy = rows;
+    if (gy < 1) gy = 1;
+    hipLaunchKernelGGL(k_dt_init, dim3(tem_grid_1d((int64_t)N * (1 + 6 * (int64_t)W), 256)), dim3(256), 0, st, mx, N, W);
+    hipLaunchKernelGGL(k_dt_max, dim3(gx, (unsigned)gy, N), dim3(256), 0, st, vec, d2, mx, D, H, W, ndim);
+    hipLaunchKernelGGL(k_dt_write, dim3(tem_grid_1d(NV, 256)), dim3(256), 0, st, vec, d2, empty, mx, out, N, D, H, W, ndim,
+                       flags, max_distance, fill);
+    TEM_CHECK_LAUNCH("tem_distance_targets");
     return TEM_OK;
 }
 

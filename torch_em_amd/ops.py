@@ -1431,14 +1431,26 @@ def pod_ids(labels: torch.Tensor, apply_label: bool, min_size: int) -> torch.Ten
         rank = _flat_cumsum(flag)
         _lib.check(lib.tem_pod_seq_assign(_p(srt), _p(order), _p(rank), _p(ids), N, V, _stream(labels)),
                    "tem_pod_seq_assign")
+    ids = ids.view(N, D, H, W)
     if min_size > 0:
-        cnt = torch.empty((N * (V + 1),), dtype=torch.int32, device=labels.device)
-        keep = torch.empty_like(cnt)
-        _lib.check(lib.tem_pod_size_keep(_p(ids), _p(cnt), _p(keep), N, V, int(min_size), _stream(labels)),
-                   "tem_pod_size_keep")
-        newid = _flat_cumsum(keep)
-        _lib.check(lib.tem_pod_size_apply(_p(ids), _p(keep), _p(newid), N, V, _stream(labels)), "tem_pod_size_apply")
-    return ids.view(N, D, H, W)
+        size_filter_(ids, min_size)
+    return ids
+
+
+def size_filter_(ids: torch.Tensor, min_size: int) -> torch.Tensor:
+    """in place on contiguous int32 ids [N, D, H, W]: positive ids with fewer than min_size voxels become 0, the surviving
+    ones are renumbered 1..n in ascending order, per sample (tem_pod_size_keep / tem_pod_size_apply); id 0 stays 0."""
+    _req_cuda(ids)
+    assert ids.dtype == torch.int32 and ids.is_contiguous()
+    N = ids.shape[0]
+    V = ids.numel() // N
+    lib = _lib.load()
+    cnt = torch.empty((N * (V + 1),), dtype=torch.int32, device=ids.device)
+    keep = torch.empty_like(cnt)
+    _lib.check(lib.tem_pod_size_keep(_p(ids), _p(cnt), _p(keep), N, V, int(min_size), _stream(ids)), "tem_pod_size_keep")
+    newid = _flat_cumsum(keep)
+    _lib.check(lib.tem_pod_size_apply(_p(ids), _p(keep), _p(newid), N, V, _stream(ids)), "tem_pod_size_apply")
+    return ids
 
 
 def pod_targets(ids: torch.Tensor, ndim: int, sampling, flags: int, fill: float) -> torch.Tensor:
@@ -1455,6 +1467,74 @@ def pod_targets(ids: torch.Tensor, ndim: int, sampling, flags: int, fill: float)
     samp = (ctypes.c_float * 3)(*[float(s) for s in sampling])
     _lib.check(lib.tem_pod_targets(_p(ids), _p(out), N, D, H, W, ndim, samp, int(flags), float(fill), _p(ws), nws,
                                    _stream(ids)), "tem_pod_targets")
+    return out
+
+
+VDT_NONE = 0x3fffffff   # include/tem_hip.h: TEM_VDT_NONE, the squared distance of a sample without target voxels
+DT_DIST, DT_DIRECTED, DT_NORMALIZE, DT_INVERT, DT_CLIP = 1, 2, 4, 8, 16
+
+
+def vector_edt(labels: torch.Tensor, foreground_id: int):
+    """int64 labels [N, D, H, W] (2-D: D == 1) -> (offsets int32 [N, 3, D, H, W] in (z, y, x) order, pointing from each
+    voxel to a nearest voxel equal to foreground_id; their exact squared length int32 [N, D, H, W]; empty int32 [N], 1
+    where a sample has no such voxel -- its offsets are 0 and its squared distances VDT_NONE).  tem_vector_edt."""
+    _req_cuda(labels)
+    labels = labels.to(torch.int64).contiguous()
+    N, D, H, W = labels.shape
+    dev = labels.device
+    vec = torch.empty((N, 3, D, H, W), dtype=torch.int32, device=dev)
+    d2 = torch.empty((N, D, H, W), dtype=torch.int32, device=dev)
+    empty = torch.empty((N,), dtype=torch.int32, device=dev)
+    _lib.check(_lib.load().tem_vector_edt(_p(labels), int(foreground_id), _p(vec), _p(d2), _p(empty), N, D, H, W,
+                                          _stream(labels)), "tem_vector_edt")
+    return vec, d2, empty
+
+
+def distance_targets(labels: torch.Tensor, ndim: int, foreground_id: int = 1, distances: bool = True,
+                     directed_distances: bool = False, normalize: bool = True, max_distance: Optional[float] = None,
+                     invert: bool = False) -> torch.Tensor:
+    """int64 labels [N, D, H, W] -> float32 [N, C, D, H, W], channels [distances?][directed x ndim?] of the reference's
+    DistanceTransform before `func` (tem_vector_edt, tem_distance_targets); no host synchronisation."""
+    vec, d2, empty = vector_edt(labels, foreground_id)
+    N, D, H, W = d2.shape
+    flags = ((DT_DIST if distances else 0) | (DT_DIRECTED if directed_distances else 0) | (DT_NORMALIZE if normalize else 0)
+             | (DT_INVERT if invert else 0) | (DT_CLIP if max_distance is not None else 0))
+    nc = (1 if distances else 0) + (ndim if directed_distances else 0)
+    out = torch.empty((N, nc, D, H, W), dtype=torch.float32, device=d2.device)
+    lib = _lib.load()
+    nws = lib.tem_distance_targets_ws(N, W)
+    ws = torch.empty((nws,), dtype=torch.uint8, device=d2.device)
+    _lib.check(lib.tem_distance_targets(_p(vec), _p(d2), _p(empty), _p(out), N, D, H, W, ndim, flags,
+                                        float(max_distance or 0.0), _p(ws), nws, _stream(d2)), "tem_distance_targets")
+    return out
+
+
+def onehot_target(labels: torch.Tensor, class_ids) -> torch.Tensor:
+    """int64 labels [N, *spatial] and a list of ids -> float32 [N, C, *spatial] (tem_onehot_target)."""
+    _req_cuda(labels)
+    labels = labels.to(torch.int64).contiguous()
+    ids = (ctypes.c_int64 * len(class_ids))(*[int(c) for c in class_ids])
+    N, C = labels.shape[0], len(class_ids)
+    V = labels.numel() // N
+    out = torch.empty((N, C) + tuple(labels.shape[1:]), dtype=torch.float32, device=labels.device)
+    _lib.check(_lib.load().tem_onehot_target(_p(labels), ids, C, _p(out), N, V, _stream(labels)), "tem_onehot_target")
+    return out
+
+
+def boundary_target_masked(labels: torch.Tensor, mode: str, kind: int, key_label: int, mask_label: int,
+                           add_binary_target: bool) -> torch.Tensor:
+    """int64 labels [N, D, H, W] -> int8 [N, 1(+1), D, H, W]: boundaries with the boundaries of (labels != key_label)
+    (kind 0) or (labels == key_label) (kind 1) set to mask_label (tem_boundary_target_masked)."""
+    _req_cuda(labels)
+    if mode not in BOUNDARY_MODES:
+        raise NotImplementedError(f"find_boundaries mode '{mode}': the MI355X kernel has {sorted(BOUNDARY_MODES)} "
+                                  "('subpixel' returns a 2n-1 grid, which cannot be a training target)")
+    labels = labels.to(torch.int64).contiguous()
+    N, D, H, W = labels.shape
+    out = torch.empty((N, 2 if add_binary_target else 1, D, H, W), dtype=torch.int8, device=labels.device)
+    _lib.check(_lib.load().tem_boundary_target_masked(_p(labels), _p(out), N, D, H, W, BOUNDARY_MODES[mode], int(kind),
+                                                      int(key_label), int(mask_label), int(add_binary_target),
+                                                      _stream(labels)), "tem_boundary_target_masked")
     return out
 
 

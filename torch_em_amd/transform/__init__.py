@@ -1,5 +1,7 @@
 """Transforms of the MI355X path that belong to the hot path (reference torch_em/transform/)."""
-from .label import AffinityTransform, BoundaryTransform, PerObjectDistanceTransform, labels_to_binary
+from .label import (AffinityTransform, BoundaryTransform, BoundaryTransformWithIgnoreLabel, DistanceTransform,
+                    MinSizeLabelTransform, NoToBackgroundBoundaryTransform, OneHotTransform, PerObjectDistanceTransform,
+                    connected_components, label_consecutive, labels_to_binary)
 from .raw import (RandomContrast, RandomPercentileNormalization, RawTransform, get_raw_transform, normalize, normalize_percentile,
                   standardize)
 from .augmentation import (KorniaAugmentationPipeline, RandomAffine, RandomAffine3D, RandomElasticDeformation, RandomRotation,
