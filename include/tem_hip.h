@@ -917,6 +917,31 @@ int tem_rawnorm_apply(const float* x, float* y, int N, int64_t L, const float* s
 int tem_rawnorm_contrast(const float* x, float* y, int N, int64_t L, const float* alpha, float mean, int clip, float lo,
                          float hi, tem_stream_t stream);
 
+/* ---- noise and blur raw augmentations (transform/raw.py: AdditiveGaussianNoise :337-363, AdditivePoissonNoise :366-391,
+ * PoissonNoise :394-425, GaussianBlur :428-454; csrc/rawaug.hip) -----------------------------------------------------
+ * Rows as above (N <= 65535, any L >= 1, any 4-byte aligned base).  The random stream is Philox4x32-10 with key = (seed lo,
+ * seed hi) and counter = (i lo, i hi, row, round): element i of data row n draws from stream row `row0 + n`, so a sample
+ * depends on (seed, row, i) alone -- not on the grid, the alignment or how many rows a call carries (DESIGN.md has the
+ * specification of the stream and of both samplers).  Per-row scalars are device arrays [N]; `seed` travels by value.
+ * Nothing is read back, allocated or synchronised; no atomics.  clip: y = min(max(y, lo), hi).  NaN input is undefined, and
+ * so is a Poisson mean that is negative, NaN or >= 2^24 (the sampler loops are bounded and still end). */
+/* out[4*t + 0..3] (device uint32) = the words w0..w3 of element i0 + t, t < n: the stream itself, for tests */
+int tem_rawaug_philox_words(uint32_t* out, uint64_t seed, uint32_t row, uint64_t i0, uint32_t round, int64_t n,
+                            tem_stream_t stream);
+/* y = fl32(x + fl32(std[n] * z)), z = sqrtf(-2 logf(u1)) * cospif(2 u2) from w0, w1 of round 0; std[n] == 0: y = x */
+int tem_rawaug_gauss_noise(const float* x, float* y, int N, int64_t L, const float* std, uint64_t seed, uint32_t row0, int clip,
+                           float lo, float hi, tem_stream_t stream);
+/* y = fl32(x + fl32(k / lam[n])), k ~ Poisson(lam[n]) (lam[n] == 0 divides by zero, as the reference does) */
+int tem_rawaug_poisson_add(const float* x, float* y, int N, int64_t L, const float* lam, uint64_t seed, uint32_t row0, int clip,
+                           float lo, float hi, tem_stream_t stream);
+/* y = fl32(fl32(k / mult[n]) + offset[n]), k ~ Poisson(fl32(fl32(x - offset[n]) * mult[n])) */
+int tem_rawaug_poisson_scaled(const float* x, float* y, int N, int64_t L, const float* offset, const float* mult, uint64_t seed,
+                              uint32_t row0, int clip, float lo, float hi, tem_stream_t stream);
+/* y = the P planes of H x W of x, each convolved with wy (ky taps, along H) and wx (kx taps, along W), reflect border
+ * (index -j -> j, H-1+j -> H-1-j).  wy, wx: device arrays; tap counts odd, 1..63, k/2 < the axis' size; y must not be x. */
+int tem_rawaug_blur2d(const float* x, float* y, int64_t P, int H, int W, const float* wy, const float* wx, int ky, int kx,
+                      tem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

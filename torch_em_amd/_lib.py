@@ -20,6 +20,8 @@ c_int = ctypes.c_int
 c_float = ctypes.c_float
 c_double = ctypes.c_double
 c_vp = ctypes.c_void_p
+c_u32 = ctypes.c_uint32
+c_u64 = ctypes.c_uint64
 
 # name -> (restype, argtypes); must list every symbol of include/tem_hip.h
 SIGNATURES = {
@@ -201,6 +203,12 @@ SIGNATURES = {
     "tem_rawnorm_percentile_coef": (c_int, [c_vp, ctypes.POINTER(c_float), c_int, c_float, c_vp, c_vp, c_vp, c_vp]),
     "tem_rawnorm_apply": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_int, c_float, c_float, c_vp]),
     "tem_rawnorm_contrast": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_float, c_int, c_float, c_float, c_vp]),
+    # noise and blur raw augmentations (csrc/rawaug.hip): (..., seed, stream row of the first data row, clip, lo, hi, stream)
+    "tem_rawaug_philox_words": (c_int, [c_vp, c_u64, c_u32, c_u64, c_u32, c_i64, c_vp]),
+    "tem_rawaug_gauss_noise": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_u64, c_u32, c_int, c_float, c_float, c_vp]),
+    "tem_rawaug_poisson_add": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_u64, c_u32, c_int, c_float, c_float, c_vp]),
+    "tem_rawaug_poisson_scaled": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_u64, c_u32, c_int, c_float, c_float, c_vp]),
+    "tem_rawaug_blur2d": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp]),
 }
 
 _lib = None

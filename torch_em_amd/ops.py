@@ -1398,6 +1398,86 @@ def contrast(x: torch.Tensor, alpha, mean: float, clip=None) -> torch.Tensor:
     return y
 
 
+# ---- noise and blur raw augmentations (csrc/rawaug.hip; the stream: transform/_philox.py) ----
+def _seed(seed) -> int:
+    seed = int(seed)
+    if not 0 <= seed < 2 ** 64:
+        raise ValueError(f"seed must be within [0, 2^64), got {seed}")
+    return seed
+
+
+def philox_words(seed: int, row: int, i0: int, rnd: int, n: int, device="cuda") -> torch.Tensor:
+    """The words w0..w3 of elements i0 .. i0+n-1 of stream row `row` at redraw `rnd`, [n, 4] on the device (int32 storage of
+    the uint32 bit patterns): the stream itself, for tests (tem_rawaug_philox_words)."""
+    if n <= 0 or not (0 <= row < 2 ** 32 and 0 <= rnd < 2 ** 32 and 0 <= i0 and i0 + n <= 2 ** 64):
+        raise ValueError("philox_words: n > 0, row and round within [0, 2^32), elements within [0, 2^64)")
+    out = torch.empty((n, 4), dtype=torch.int32, device=device)
+    _req_cuda(out)
+    _lib.check(_lib.load().tem_rawaug_philox_words(_p(out), _seed(seed), row, i0, rnd, n, _stream(out)), "tem_rawaug_philox_words")
+    return out
+
+
+def gauss_noise(x: torch.Tensor, std, seed: int, clip=None, row0: int = 0) -> torch.Tensor:
+    """fl32(x + fl32(std[n] * z)) per entry of the first axis, z standard normal from the stream (seed, row0 + n, i), then
+    the clip (`AdditiveGaussianNoise`, transform/raw.py:337-363); std: a number or one per row (HOST values)."""
+    x, N, L = _rows(x)
+    s = _fill(std, N, x.device, "std")
+    y = torch.empty_like(x)
+    flag, lo, hi = _clip(clip)
+    _lib.check(_lib.load().tem_rawaug_gauss_noise(_p(x), _p(y), N, L, _p(s), _seed(seed), int(row0), flag, lo, hi, _stream(x)),
+               "tem_rawaug_gauss_noise")
+    return y
+
+
+def poisson_add(x: torch.Tensor, lam, seed: int, clip=None, row0: int = 0) -> torch.Tensor:
+    """fl32(x + fl32(k / lam[n])) with k ~ Poisson(lam[n]) from the stream, then the clip (`AdditivePoissonNoise`,
+    transform/raw.py:366-391); lam: a positive number or one per row (HOST values; below 2^24)."""
+    x, N, L = _rows(x)
+    lm = _fill(lam, N, x.device, "lam")
+    y = torch.empty_like(x)
+    flag, lo, hi = _clip(clip)
+    _lib.check(_lib.load().tem_rawaug_poisson_add(_p(x), _p(y), N, L, _p(lm), _seed(seed), int(row0), flag, lo, hi, _stream(x)),
+               "tem_rawaug_poisson_add")
+    return y
+
+
+def poisson_scaled(x: torch.Tensor, mult, seed: int, clip=None, row0: int = 0, offset=None) -> torch.Tensor:
+    """fl32(fl32(k / mult[n]) + offset[n]) with k ~ Poisson(fl32(fl32(x - offset[n]) * mult[n])), then the clip
+    (`PoissonNoise`, transform/raw.py:394-425).  offset: None -> the row minimum (tem_row_minmax, composed here), or a
+    device float32 [N]; mult: a number or one per row (HOST values)."""
+    x, N, L = _rows(x)
+    if offset is None:
+        offset, _ = row_minmax(x)
+    elif not (torch.is_tensor(offset) and offset.is_cuda and offset.dtype == torch.float32 and offset.numel() == N):
+        raise ValueError(f"poisson_scaled: offset must be a device float32 tensor of {N} entries (one per row) or None")
+    offset = offset.contiguous()
+    m = _fill(mult, N, x.device, "mult")
+    y = torch.empty_like(x)
+    flag, lo, hi = _clip(clip)
+    _lib.check(_lib.load().tem_rawaug_poisson_scaled(_p(x), _p(y), N, L, _p(offset), _p(m), _seed(seed), int(row0), flag, lo, hi,
+                                                     _stream(x)), "tem_rawaug_poisson_scaled")
+    return y
+
+
+def blur2d(x: torch.Tensor, wy, wx=None) -> torch.Tensor:
+    """The last two axes of x convolved with the 1-D weights wy (along H) and wx (along W; None: wy), reflect border without
+    edge repeat; all other axes are independent planes (`GaussianBlur`, transform/raw.py:428-454).  Weights: HOST sequences
+    of odd length <= 63 with len // 2 < the axis' size."""
+    _req_cuda(x)
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"blur2d: expected a non-empty tensor of at least two axes, got shape {tuple(x.shape)}")
+    x = x.float().contiguous()
+    H, W = int(x.shape[-2]), int(x.shape[-1])
+    wy = [float(v) for v in wy]
+    wx = wy if wx is None else [float(v) for v in wx]
+    dy = _fill(wy, len(wy), x.device, "wy")
+    dx = dy if wx is wy else _fill(wx, len(wx), x.device, "wx")
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().tem_rawaug_blur2d(_p(x), _p(y), x.numel() // (H * W), H, W, _p(dy), _p(dx), len(wy), len(wx), _stream(x)),
+               "tem_rawaug_blur2d")
+    return y
+
+
 # ---- distance-based instance segmentation (csrc/distance.hip) ----
 POD_DIST, POD_BOUNDARY, POD_DIRECTED, POD_FOREGROUND, POD_INSTANCES = 1, 2, 4, 8, 16
 

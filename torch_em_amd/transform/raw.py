@@ -1,15 +1,21 @@
 """Raw-data transforms on the hot path (reference torch_em/transform/raw.py).
 
-Built: `standardize`, `normalize`, `normalize_percentile`, `RandomPercentileNormalization`, `RandomContrast`, `RawTransform`,
-`get_raw_transform`.  Each dispatches on its input: a CUDA tensor runs through the HIP kernels of csrc/rawnorm.hip (nothing
-is read back, so they run inside the input pipeline's side stream and as `predict_with_halo(preprocess=...)`); numpy input
-takes the reference's numpy expression, which is also the CPU oracle of the device path -- the two agree bit for bit on
-float32 data.  A CPU torch tensor counts as numpy input and comes back as a numpy array (the reference returns a tensor
-there): on this path tensors live on the device.
+Built: `standardize`, `normalize`, `normalize_percentile`, `RandomPercentileNormalization`, `RandomContrast`,
+`AdditiveGaussianNoise`, `AdditivePoissonNoise`, `PoissonNoise`, `GaussianBlur`, `RawTransform`, `get_raw_transform`,
+`get_default_mean_teacher_augmentations`: everything the reference's module offers.  Each dispatches on its input: a CUDA
+tensor runs through the HIP kernels of csrc/rawnorm.hip and csrc/rawaug.hip (nothing is read back, so they run inside the
+input pipeline's side stream and as `predict_with_halo(preprocess=...)`); numpy input takes the reference's numpy
+expression.  For the deterministic transforms that is also the CPU oracle of the device path -- the two agree bit for bit
+on float32 data.  A CPU torch tensor counts as numpy input and comes back as a numpy array (the reference returns a tensor
+there; `GaussianBlur` returns a tensor on every path, as the reference's does): on this path tensors live on the device.
 
-Out of scope: the noise transforms (`AdditiveGaussianNoise`, `AdditivePoissonNoise`, `PoissonNoise`: their random streams
-have no device counterpart that could be pinned to the reference's), `GaussianBlur` (defined by torchvision, which this
-package does not depend on) and `get_default_mean_teacher_augmentations` (needs both).
+The noise transforms draw their scalar (std, lam, multiplier) with `np.random.uniform` on every path.  The noise FIELD of
+the numpy branch is the reference's `np.random` draw; on the device it comes from a stream of the package's own, because
+numpy's cannot be reproduced there: Philox4x32-10 keyed by one 64-bit seed per call (drawn from `np.random`, so
+`np.random.seed` pins a device call), counter = (element, row, redraw).  DESIGN.md specifies the stream and both samplers;
+`_philox.py` implements them in numpy, and the tests compare the device with it word for word and sample for sample.  The
+two branches therefore agree in distribution, not value by value.  `GaussianBlur` is defined by torchvision in the
+reference; here its arithmetic is written out (see the class), so the package needs no torchvision.
 """
 from typing import Callable, Dict, Optional, Tuple
 
@@ -266,6 +272,201 @@ class RandomContrast:
         return np.clip(res, **self.clip_kwargs) if self.clip_kwargs else res
 
 
+def _device_clip(clip_kwargs, who: str):
+    """clip_kwargs -> (a_min, a_max) or None, by RandomContrast's rule for the device"""
+    if not clip_kwargs:
+        return None
+    unknown = set(clip_kwargs) - {"a_min", "a_max"}
+    if unknown:
+        raise ValueError(f"{who} on the device: clip_kwargs takes a_min and a_max only, got {sorted(unknown)}")
+    return (clip_kwargs.get("a_min"), clip_kwargs.get("a_max"))
+
+
+def _field_seed() -> int:
+    """the 64-bit seed of one device noise field, from numpy's global state (so np.random.seed pins a device call)"""
+    return int(np.random.randint(0, 2 ** 63, dtype=np.int64))
+
+
+class AdditiveGaussianNoise:
+    """img + N(0, std) with std drawn uniformly from `scale` by `np.random.uniform` (reference `:337-363`).  As in the
+    reference a truthy `clip_kwargs` clips to [0, 1] whatever it holds.
+    numpy input: the reference's expression and `np.random.normal` draw.  A CUDA tensor: std is drawn the same way, then one
+    64-bit seed by `np.random.randint(0, 2**63, dtype=np.int64)`, and the Gauss kernel adds std * z with z from the package's
+    counter-based stream (`_philox.py`; not numpy's stream, which has no device counterpart) -- `np.random.seed` makes the
+    call reproducible.  `per_sample=True` (not in the reference): one std per entry of the first axis, drawn in order, and
+    still one seed (each sample is its own row of the stream); on numpy input it is the reference sample by sample.  On the
+    device `clip_kwargs` may hold `a_min` and `a_max` only; any other np.clip keyword raises."""
+
+    def __init__(self, scale: Tuple[float, float] = (0.0, 0.3), clip_kwargs: Optional[Dict] = {"a_min": 0, "a_max": 1},
+                 per_sample: bool = False):
+        self.scale = scale
+        self.clip_kwargs = clip_kwargs
+        self.per_sample = bool(per_sample)
+
+    def _numpy(self, img):
+        std = np.random.uniform(self.scale[0], self.scale[1])
+        gaussian_noise = np.random.normal(0, std, size=img.shape)
+        if self.clip_kwargs:
+            return np.clip(img + gaussian_noise, 0, 1)
+        return img + gaussian_noise
+
+    def __call__(self, img):
+        if _on_device(img):
+            n = len(img) if self.per_sample else 1
+            std = [np.random.uniform(self.scale[0], self.scale[1]) for _ in range(n)]
+            seed = _field_seed()
+            clip = (0.0, 1.0) if _device_clip(self.clip_kwargs, "AdditiveGaussianNoise") else None
+            return ops.gauss_noise(img.reshape(n, -1), std, seed, clip).reshape(img.shape)
+        img = np.asarray(img)
+        return np.stack([self._numpy(s) for s in img]) if self.per_sample else self._numpy(img)
+
+
+class AdditivePoissonNoise:
+    """img + Poisson(lam) / lam with lam drawn uniformly from `lam` by `np.random.uniform` (reference `:366-391`); a truthy
+    `clip_kwargs` clips to [0, 1] whatever it holds.  Dispatch, seed, `per_sample` and the device's `clip_kwargs` rule as in
+    `AdditiveGaussianNoise`; the device counts come from the package's stream (inversion below lam = 10, transformed
+    rejection from there).  A drawn lam == 0 raises ValueError on the device path (the reference divides by zero there)."""
+
+    def __init__(self, lam: Tuple[float, float] = (0.0, 0.1), clip_kwargs: Optional[Dict] = {"a_min": 0, "a_max": 1},
+                 per_sample: bool = False):
+        self.lam = lam
+        self.clip_kwargs = clip_kwargs
+        self.per_sample = bool(per_sample)
+
+    def _numpy(self, img):
+        lam = np.random.uniform(self.lam[0], self.lam[1])
+        poisson_noise = np.random.poisson(lam, size=img.shape) / lam
+        if self.clip_kwargs:
+            return np.clip(img + poisson_noise, 0, 1)
+        return img + poisson_noise
+
+    def __call__(self, img):
+        if _on_device(img):
+            n = len(img) if self.per_sample else 1
+            lam = [np.random.uniform(self.lam[0], self.lam[1]) for _ in range(n)]
+            seed = _field_seed()
+            if any(np.float32(v) == 0 for v in lam):
+                raise ValueError("AdditivePoissonNoise: the drawn lam is 0, and the noise is Poisson(lam) / lam")
+            clip = (0.0, 1.0) if _device_clip(self.clip_kwargs, "AdditivePoissonNoise") else None
+            return ops.poisson_add(img.reshape(n, -1), lam, seed, clip).reshape(img.shape)
+        img = np.asarray(img)
+        return np.stack([self._numpy(s) for s in img]) if self.per_sample else self._numpy(img)
+
+
+class PoissonNoise:
+    """Poisson((img - min) * multiplier) / multiplier + min, the multiplier drawn uniformly from `multiplier` by
+    `np.random.uniform`, then np.clip with `clip_kwargs` (reference `:394-425`).  Dispatch, seed and the device's
+    `clip_kwargs` rule as in `AdditiveGaussianNoise`; on the device the minimum comes from the row min / max kernel and the
+    means (img - min) * multiplier must stay below 2^24.  `per_sample=True` (not in the reference): one multiplier and one
+    minimum per entry of the first axis.  NaN input is undefined on the device."""
+
+    def __init__(self, multiplier: Tuple[float, float] = (5.0, 10.0), clip_kwargs: Optional[Dict] = {"a_min": 0, "a_max": 1},
+                 per_sample: bool = False):
+        self.multiplier = multiplier
+        self.clip_kwargs = clip_kwargs
+        self.per_sample = bool(per_sample)
+
+    def _numpy(self, img):
+        multiplier = np.random.uniform(self.multiplier[0], self.multiplier[1])
+        offset = img.min()
+        poisson_noise = np.random.poisson((img - offset) * multiplier)
+        poisson_noise = poisson_noise / multiplier + offset
+        if self.clip_kwargs:
+            return np.clip(poisson_noise, **self.clip_kwargs)
+        return poisson_noise
+
+    def __call__(self, img):
+        if _on_device(img):
+            n = len(img) if self.per_sample else 1
+            mult = [np.random.uniform(self.multiplier[0], self.multiplier[1]) for _ in range(n)]
+            seed = _field_seed()
+            clip = _device_clip(self.clip_kwargs, "PoissonNoise")
+            return ops.poisson_scaled(img.reshape(n, -1), mult, seed, clip).reshape(img.shape)
+        img = np.asarray(img)
+        return np.stack([self._numpy(s) for s in img]) if self.per_sample else self._numpy(img)
+
+
+def gaussian_weights(sigma: float) -> torch.Tensor:
+    """The normalised 1-D Gaussian of `GaussianBlur`, float32 on the CPU: kernel_size = int(2 * ceil(3 sigma) + 1) taps at
+    x = linspace(-(k-1)/2, (k-1)/2, k), pdf = exp(-0.5 (x / sigma)^2), w = pdf / pdf.sum() -- torch float32 operations."""
+    if not sigma > 0:
+        raise ValueError(f"GaussianBlur: sigma must be positive, got {sigma}")
+    k = int(2 * np.ceil(3 * sigma) + 1)
+    half = (k - 1) * 0.5
+    x = torch.linspace(-half, half, steps=k, dtype=torch.float32)
+    pdf = torch.exp(-0.5 * (x / sigma).pow(2))
+    return pdf / pdf.sum()
+
+
+class GaussianBlur:
+    """Gaussian blur of the last two axes with sigma drawn by `np.random.uniform(sigma[1], sigma[0])` -- the bounds swapped,
+    as in the reference (`:428-454`), which hands the image to torchvision's `GaussianBlur(kernel_size, sigma)`.
+    torchvision is not a dependency of this package and is not installed where its golden files are made, so the
+    definition is pinned by this text and not by a golden file: the weights of `gaussian_weights` (one vector for both
+    axes), their outer product, reflect padding (index -j -> j, no edge repeat) and a depth-wise 2-D convolution.  All axes
+    but the last two are independent planes (a [C, D, H, W] volume is blurred in-plane only, which is what the reference
+    does); the input has at least two axes and kernel_size // 2 must be smaller than both of the last two.
+    numpy input or a CPU tensor: `F.pad(mode="reflect")` + `F.conv2d(groups=planes)` on the CPU; returns a torch tensor, as
+    the reference does (integer input comes back as float32).  A CUDA tensor: the blur kernel (kernel_size <= 63), which
+    forms the two 1-D sums one after the other and agrees with the CPU branch to rounding.  Both branches call
+    `torch.empty(1).uniform_(sigma, sigma)` once, as torchvision's transform does, which keeps torch's generator in step."""
+
+    def __init__(self, sigma: Tuple[float, float] = (0.0, 3.0)):
+        self.sigma = sigma
+
+    def __call__(self, img):
+        sigma = np.random.uniform(self.sigma[1], self.sigma[0])
+        w = gaussian_weights(sigma)
+        torch.empty(1).uniform_(sigma, sigma)
+        if _on_device(img):
+            if img.dim() < 2:
+                raise ValueError("GaussianBlur: the input needs at least two axes")
+            return ops.blur2d(img, w.tolist()).reshape(img.shape)
+        if not torch.is_tensor(img):
+            img = torch.from_numpy(np.ascontiguousarray(img))
+        if img.dim() < 2:
+            raise ValueError("GaussianBlur: the input needs at least two axes")
+        x = img if img.is_floating_point() else img.float()
+        H, W = x.shape[-2:]
+        pad = len(w) // 2
+        if pad >= H or pad >= W:
+            raise ValueError(f"GaussianBlur: the reflect border needs kernel_size // 2 < size on each axis "
+                             f"({len(w)} taps on a {H} x {W} plane)")
+        planes = x.reshape(1, -1, H, W)
+        w = w.to(x.dtype)
+        kernel = torch.mm(w[:, None], w[None, :]).expand(planes.shape[1], 1, len(w), len(w))
+        out = torch.nn.functional.conv2d(torch.nn.functional.pad(planes, [pad, pad, pad, pad], mode="reflect"), kernel,
+                                         groups=planes.shape[1])
+        return out.reshape(x.shape)
+
+
+class _Compose:
+    """call the transforms in order (torchvision.transforms.Compose)"""
+
+    def __init__(self, transforms):
+        self.transforms = transforms
+
+    def __call__(self, img):
+        for t in self.transforms:
+            img = t(img)
+        return img
+
+
+class _RandomApply:
+    """apply the transforms with probability p: skipped when p < torch.rand(1) (torchvision.transforms.RandomApply)"""
+
+    def __init__(self, transforms, p: float = 0.5):
+        self.transforms = transforms
+        self.p = p
+
+    def __call__(self, img):
+        if self.p < torch.rand(1):
+            return img
+        for t in self.transforms:
+            img = t(img)
+        return img
+
+
 class RawTransform:
     """The raw transform of training: `augmentation1`, then `normalizer`, then `augmentation2` (reference `:461-492`)."""
 
@@ -285,3 +486,21 @@ def get_raw_transform(normalizer: Callable = standardize, augmentation1: Optiona
                       augmentation2: Optional[Callable] = None) -> Callable:
     """`RawTransform(normalizer, augmentation1, augmentation2)` (reference `:495-510`)."""
     return RawTransform(normalizer, augmentation1=augmentation1, augmentation2=augmentation2)
+
+
+def get_default_mean_teacher_augmentations(p: float = 0.3, norm: Optional[Callable] = None, blur_kwargs: Optional[Dict] = None,
+                                           poisson_kwargs: Optional[Dict] = None, gaussian_kwargs: Optional[Dict] = None) -> Callable:
+    """The default augmentations of mean-teacher training (reference `:513-546`), designed for values in [0, 1]: `norm`
+    (default `normalize`), then blur with probability p, Poisson noise and additive Gaussian noise with p / 2 each; then
+    `norm` again as the normaliser, then contrast with probability p.  The coin flips are `torch.rand(1)` as in
+    torchvision's `RandomApply`, so `torch.manual_seed` and `np.random.seed` together pin a call."""
+    if norm is None:
+        norm = normalize
+    aug1 = _Compose([
+        norm,
+        _RandomApply([GaussianBlur(**({} if blur_kwargs is None else blur_kwargs))], p=p),
+        _RandomApply([PoissonNoise(**({} if poisson_kwargs is None else poisson_kwargs))], p=p / 2),
+        _RandomApply([AdditiveGaussianNoise(**({} if gaussian_kwargs is None else gaussian_kwargs))], p=p / 2),
+    ])
+    aug2 = _RandomApply([RandomContrast(clip_kwargs={"a_min": 0, "a_max": 1})], p=p)
+    return get_raw_transform(normalizer=norm, augmentation1=aug1, augmentation2=aug2)
