@@ -97,6 +97,9 @@ int tem_device_cus(void);
  *                        one-team-per-workgroup variant, staging from inside the tap loop: measured 1-4 % slower, same results)
  *                        (k_conv_zr<..., X32>: fused statistics, ReLU mask, norm backward, split-K as in the split modes;
  *                        0: the one-patch-per-workgroup kernels of rounds 1-5, which deliver none of those)
+ *   "zr_pair"             1 | 0   z-reuse launches of the two-term split modes (2, 4) on fp32 tensors with Cout % 64 == 0: the two
+ *                        teams of a workgroup hold sibling output-channel tiles and stage each halo chunk once between them
+ *                        (direct and split-K launches; 0: every team stages its own copy -- the same bits, A/B)
  * Unknown names return TEM_EINVAL. */
 int tem_set_option(const char* name, int64_t value);
 int tem_get_option(const char* name, int64_t* value);

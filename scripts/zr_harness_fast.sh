@@ -1,5 +1,7 @@
 #!/bin/bash
 # usage: scripts/zr_harness_fast.sh <tag> <extra -D flags for conv_zr.hip>   -> build/zr_harness_<tag>
+# run it with ZR_PAIR=0 / ZR_PAIR=1 in the environment to time the unpaired / the paired kernel (option zr_pair) from one build;
+# -DTEM_ZR_ABL=128 builds the half-staging ceiling of the pairing (run with ZR_PAIR=0)
 # pp_harness.cpp + conv_pp.hip are compiled once (build/zrh_*.o); a variant costs one compile of conv_zr.hip (~40 s)
 set -e
 cd "$(dirname "$0")/.."

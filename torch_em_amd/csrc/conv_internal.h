@@ -61,10 +61,13 @@ struct TemPatchTiling {
 };
 TemPatchTiling tem_fwd_patch_tiling(const TemConvShape& sh);
 // conv_zr.hip: 4 x 16 x 8 tiles.  shape_ok: options, mode and shape admit the kernel; ok: ... with enough units for a direct launch
+// pair: the two teams of a workgroup share one staged halo per chunk (sibling output-channel tiles: Cout % 64 == 0, a two-term
+// split mode on fp32 tensors, option zr_pair) -- the direct launch and the split-K launch of this geometry both run k_conv_zr<.., PAIR>
 struct ZrGeom {
     int shape_ok, ok;
     int nZ, nY, nX;
     int64_t nunits;
+    int pair;
 };
 // conv_pp.hip
 struct PpGeom {

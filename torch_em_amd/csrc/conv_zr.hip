@@ -40,6 +40,10 @@
 #ifndef TEM_ZR_R0
 #define TEM_ZR_R0 2      // halo planes (of 6; three 16-byte loads each) requested BEFORE the epilogue of the previous unit
 #endif
+#ifndef TEM_ZR_R0_PAIR
+#define TEM_ZR_R0_PAIR 1 // ... of the three planes a team of the paired kernel stages (a ring of 9 slots instead of 18): more planes in one
+                         // burst measured slower on the largest launch (profiles/zr_pair_ab.txt, section 2)
+#endif
 #ifndef TEM_ZR_R0_16
 #define TEM_ZR_R0_16 2   // ... with 16-bit tensors (three 16-byte loads per plane: all six planes fit the register ring), plain / ReLU-mask epilogues
 #endif
@@ -67,7 +71,8 @@
 #endif
 // ---- harness instruments (default off; wrong results when set) ----
 #ifndef TEM_ZR_ABL
-#define TEM_ZR_ABL 0     // ablations: 1 no halo loads, 2 no stores, 4 no weight loads, 8 no LDS writes, 16 no MFMAs
+#define TEM_ZR_ABL 0     // ablations: 1 no halo loads, 2 no stores, 4 no weight loads, 8 no LDS writes, 16 no MFMAs,
+                         // 128 half staging (team 0 stages halo planes 0-2 only, team 1 planes 3-5: the paired kernel's ceiling)
 #endif
 #ifdef TEM_ZR_TRACE   // developer build (scripts/zr_harness_fast.sh, pp_harness.cpp): shader-clock stamps of the phases of one workgroup
 #ifndef TEM_ZR_TRACE_BLOCK
@@ -231,7 +236,24 @@ struct ZrUnit {
 // chunk, like the two terms of the split layouts).  Eight 16-pass MFMAs per (tap, chunk, z-plane) instead of three 8-pass ones:
 // the tap phase is 5.3x as long as the fp16x3 one while staging and epilogue shrink, so the matrix pipe only idles in the
 // barrier hand-overs -- this is the mode that is NOT power-limited (profiles/r06_mfma_busy_fp32.txt), where that converts.
-template <int NS, bool F16, int MODE, bool KSPLIT = false, bool WIDE = false, typename T = float, bool X32 = false, bool XS = false>
+// PAIR (launch plan: ZrGeom::pair; Cout % 64 == 0, two-term split modes on fp32 tensors): with the output-channel tile fastest in
+// decode() and an even tile count, the two teams of a workgroup always hold SIBLING units -- (tile, cot) and (tile, cot + 1): the same
+// halo, the same samples, the same input-channel chunks.  Unpaired, each team loads, normalises, splits and writes that halo into its
+// own LDS tile: the two tiles hold the same bytes.  Paired, the two tiles are a double buffer of CHUNKS shared by both teams -- chunk k
+// of the pair's common sequence lives in tile k & 1 -- and a team stages HALF of each chunk: team 0 halo planes 0-2, team 1 planes 3-5.
+// Barrier intervals (in iteration s of the slot loop team 1 stages and taps chunk s, team 0 stages chunk s and taps chunk s - 1; both
+// teams enter the loop together and stage their halves of chunk 0 side by side in interval 0):
+//     interval 2s-1 (s >= 1)   team 0 stages planes 0-2 of chunk s       team 1 taps chunk s - 1
+//     interval 2s   (s >= 1)   team 0 taps chunk s - 1                   team 1 stages planes 3-5 of chunk s
+// No race: tile s & 1 last held chunk s - 2, whose taps ran in intervals 2s - 3 (team 1) and 2s - 2 (team 0), both a barrier before the
+// first write of interval 2s - 1; chunk s is complete after interval 2s, a barrier before team 1 taps it (2s + 1); team 0 taps it in
+// 2s + 2 and the tile is next written in 2s + 3.  The epilogues stay in the staging phases -- team 0's in odd, team 1's in even
+// intervals (none is pending in interval 0): the transposing scratch is never used by both.  Team 0 therefore stages one chunk AHEAD of
+// its taps (stage cursor su / sci, tap cursor cu / ci) and its last epilogue needs one more iteration.  Barriers: the loop bound is
+// launch-uniform and every iteration has two __syncthreads() outside any data-dependent condition, except that team 0 (whose iteration 0
+// has no tap phase) executes one in iteration 0 and one behind the loop: team 0 1 + 2 (P + 1) + 1, team 1 2 (P + 2) -- the same count.
+// Tap loop, accumulators, epilogue and every operand are those of the unpaired kernel, in the same order: results are bit-identical.
+template <int NS, bool F16, int MODE, bool KSPLIT = false, bool WIDE = false, typename T = float, bool X32 = false, bool XS = false, bool PAIR = false>
 __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
     const T* __restrict__ x, int64_t x_ld, const float* __restrict__ scale, const float* __restrict__ shift,
     const uint4* __restrict__ wp, const float* __restrict__ bias, std::conditional_t<KSPLIT, float, T>* __restrict__ y, int64_t y_ld,
@@ -244,6 +266,7 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
     static_assert(!WIDE || NS == 2, "the wide one-term kernel uses the two LDS planes of the two-term layout");
     static_assert(!X32 || (NS == 2 && !F16 && !WIDE && sizeof(T) == 4), "exact fp32: two LDS planes of eight fp32 channels, fp32 tensors");
     static_assert(!XS || X32, "the one-team workgroup exists for the exact-fp32 arithmetic only");
+    static_assert(!PAIR || (NS == 2 && !WIDE && !X32 && sizeof(T) == 4), "sibling pairing: the two-term split modes on fp32 tensors");
     constexpr bool T16 = sizeof(T) == 2;         // 16-bit activations in HBM
     using TOut = std::conditional_t<KSPLIT, float, T>;
     constexpr bool Y16 = sizeof(TOut) == 2;
@@ -254,7 +277,9 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
     constexpr int HZ = TZ + 2, HY = TY + 2, HX = TX + 2;
     constexpr int HV = HZ * HY * HX;             // 1080 halo voxels
     constexpr int PLB = HV * 32;                 // bytes per plane of a team's tile (16 channels x 2 B per voxel)
-    constexpr int NIT = HZ * 3;                  // float4 slots per thread: a ring of RP halo planes
+    constexpr bool HALF = PAIR || ((TEM_ZR_ABL & 128) && !X32 && !WIDE && !T16);   // a team stages three of the six halo planes: 3 team .. 3 team + 2
+    constexpr int HZS = HALF ? HZ / 2 : HZ;      // halo planes a team stages per chunk
+    constexpr int NIT = HZS * 3;                 // float4 slots per thread: a ring of RP halo planes
     constexpr int LPV = (WIDE && !T16) ? 8 : 4;  // lanes per halo voxel: one 16-byte load each (WIDE: a whole 128-byte line; 16-bit: the 64-byte record)
     constexpr int SPP = (WIDE && !T16) ? 6 : 3;  // load slots per thread and halo plane (the last one only for part of the team)
     constexpr int CPL = T16 ? 8 : 4;             // channels per load slot
@@ -262,7 +287,9 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
     constexpr int R0 = X32 ? (MODE == 0 ? TEM_ZR_X32_R0_M0 : MODE == 1 ? TEM_ZR_X32_R0_M1 : MODE == 2 ? TEM_ZR_X32_R0_M2 : TEM_ZR_X32_R0_M3)   // exact fp32: as much of the halo as the epilogue's registers allow, by instructions that need no vector ALU (see pvo below)
                        : (WIDE && !T16) ? ((MODE == 1 || MODE == 3) ? 1 : 2)   // (a ring of three planes: at most two ahead; the statistics / norm-backward epilogues have no room for 12 loads)
                        : T16 ? ((MODE == 1 || MODE == 3) ? TEM_ZR_R0_16S : TEM_ZR_R0_16)
+                       : HALF ? TEM_ZR_R0_PAIR
                              : (TEM_ZR_R0 < HZ ? TEM_ZR_R0 : HZ);   // halo planes loaded before the epilogue
+    static_assert(R0 >= 1 && R0 <= HZS, "planes requested ahead: at least one, at most what the team stages");
     constexpr int FR = NS * 64;                  // uint4s per (tap, 16-channel chunk) fragment group
     constexpr bool SC = F16 && NS == 2 && !WIDE;
     constexpr int ZSTEP = HY * HX * 32;          // bytes between halo z-planes: 5760 = 45 * 128 (bank-neutral)
@@ -283,7 +310,7 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
     // lane order + the former bit-2 swizzle took 16 (SQ_LDS_BANK_CONFLICT was 67 % of SQ_LDS_IDX_ACTIVE).
     const int vu = (int)((0x73261540u >> (4 * (v >> 2))) & 7u) * 4 + (v & 3);
     const int py = vu >> 3, px = vu & 7;
-    unsigned char* lds = zr_lds + team * (NS * PLB);
+    const int hzb = HALF ? (HZ / 2) * team : 0;   // first halo plane this team stages (wave-uniform)
 
     const int G = (XS ? 1 : 2) * gridDim.x;   // (XS: 256 threads = one team per workgroup, team == 0)
     const int slot = XS ? tem_xcd_remap(blockIdx.x, gridDim.x) : tem_xcd_remap(blockIdx.x, gridDim.x) * 2 + team;
@@ -297,8 +324,9 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
         int u = slot + ui * G;
         ZrUnit t;
         t.ksl = 0;
-        if (KSPLIT) { t.ksl = u % ks; u /= ks; }   // the slices of a tile are neighbours: they share its halo in L2
+        if (KSPLIT && !PAIR) { t.ksl = u % ks; u /= ks; }   // the slices of a tile are neighbours: they share its halo in L2
         t.cot = u % ncot; u /= ncot;
+        if (KSPLIT && PAIR) { t.ksl = u % ks; u /= ks; }    // paired: column tile fastest, the team pair is (tile, slice, cot) / (tile, slice, cot + 1)
         // Tiles in blocks of 2^lx x 2^ly x 2^lz (x fastest inside a block, blocks x fastest): the 64 units that the teams of
         // one XCD work on at a time (tem_xcd_remap) then form a compact 3-D block whose halos overlap inside that XCD's L2
         // -- in plain x, y, z order they are a 4-voxel-thin slab whose z halo (a third of all halo lines) belongs to
@@ -385,6 +413,10 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
 
     int ui = 0, ci = 0;
     ZrUnit cu = decode(0), eu = cu;
+    // paired: the stage cursor (unit, chunk) of this team; team 0 stages one chunk ahead of its taps (lag), team 1 in step with them
+    ZrUnit su = cu;
+    int sui = 0, sci = 0;
+    const int lag = (PAIR && team == 0) ? 1 : 0;
     unit_offsets(cu);
     bool epi_pending = false;
     // bias: lane l keeps channel (l & 31) of the unit being computed.  It is added in the epilogue: accumulators that START
@@ -589,9 +621,15 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
         if (AMAX && out_amax) tem_amax_commit(out_amax, amx);
         return;
     }
-    if (team) __syncthreads();
-    for (int s = 0; s <= P; ++s) {
-        const bool do_stage = ui < my_units;
+    if (team && !PAIR) __syncthreads();   // (paired: both teams stage their halves of chunk 0 side by side; team 0 drops a barrier of iteration 0 instead)
+    for (int s = 0; s <= P + (PAIR ? 1 : 0); ++s) {   // (paired: team 0's last tap is in iteration P, its epilogue in P + 1)
+        const bool do_tap = s >= lag && ui < my_units;          // this iteration has a tap phase: chunk (cu, ci)
+        const bool do_stage = PAIR ? sui < my_units : do_tap;   // ... a staging phase: chunk (stu, stc); unpaired: the same chunk
+        const ZrUnit& stu = PAIR ? su : cu;
+        const int stc = PAIR ? sci : ci;
+        // unpaired: a tile per team; paired: chunk s is staged into tile s & 1, the chunk tapped (s - lag) comes out of its own
+        unsigned char* const slds = zr_lds + (PAIR ? (s & 1) : team) * (NS * PLB) + hzb * ZSTEP;
+        const unsigned char* const lds = zr_lds + (PAIR ? ((s - lag) & 1) : team) * (NS * PLB);
         uint4 wq[2][3][NS];   // weight fragments of the (ty, tx) column in use and of the next one (declared per step: a
                               // function-scope array is loop-carried for hipcc and gets spilled across the staging phase)
         {
@@ -610,11 +648,11 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
             __amdgpu_buffer_rsrc_t rx = zr_rsrc(x);
             auto load_norm = [&]() {
                 if (scale) {
-                    sc4 = *reinterpret_cast<const float4*>(scale + (int64_t)cu.n * Cin + (cu.ksl * nch + ci) * CK + c4 * CPL);
-                    sf4 = *reinterpret_cast<const float4*>(shift + (int64_t)cu.n * Cin + (cu.ksl * nch + ci) * CK + c4 * CPL);
+                    sc4 = *reinterpret_cast<const float4*>(scale + (int64_t)stu.n * Cin + (stu.ksl * nch + stc) * CK + c4 * CPL);
+                    sf4 = *reinterpret_cast<const float4*>(shift + (int64_t)stu.n * Cin + (stu.ksl * nch + stc) * CK + c4 * CPL);
                     if (T16) {
-                        sc5 = *reinterpret_cast<const float4*>(scale + (int64_t)cu.n * Cin + (cu.ksl * nch + ci) * CK + c4 * CPL + 4);
-                        sf5 = *reinterpret_cast<const float4*>(shift + (int64_t)cu.n * Cin + (cu.ksl * nch + ci) * CK + c4 * CPL + 4);
+                        sc5 = *reinterpret_cast<const float4*>(scale + (int64_t)stu.n * Cin + (stu.ksl * nch + stc) * CK + c4 * CPL + 4);
+                        sf5 = *reinterpret_cast<const float4*>(shift + (int64_t)stu.n * Cin + (stu.ksl * nch + stc) * CK + c4 * CPL + 4);
                     }
                 } else if (in_amax) {
                     sc4 = make_float4(psc, psc, psc, psc);
@@ -624,11 +662,11 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
                 if constexpr (!X32) load_norm();   // (exact fp32: behind the halo loads -- its address arithmetic is vector-ALU work)
                 // the halo origin may lie outside the tensor for border patches (only in-range voxels are dereferenced)
                 // (16-bit storage: a chunk stride x_cs != 0 puts chunk k at x + k * x_cs -- planar concat halves, tem_act.h)
-                const int64_t xch = (T16 && x_cs) ? (int64_t)(cu.ksl * nch + ci) * x_cs : (int64_t)((cu.ksl * nch + ci) * CK);
-                const T* xb = x + ((((int64_t)cu.n * D + (cu.z0 - 1)) * H + (cu.y0 - 1)) * W + (cu.x0 - 1)) * x_ld + xch;
+                const int64_t xch = (T16 && x_cs) ? (int64_t)(stu.ksl * nch + stc) * x_cs : (int64_t)((stu.ksl * nch + stc) * CK);
+                const T* xb = x + ((((int64_t)stu.n * D + (stu.z0 - 1)) * H + (stu.y0 - 1)) * W + (stu.x0 - 1)) * x_ld + xch;
                 rx = zr_rsrc((TEM_ZR_ABL & 64) ? x + xch : xb);   // timing experiment: every unit reads the halo at the origin (L2 hits)
-                interior = (cu.z0 >= 1) & (cu.z0 + HZ - 1 <= D) & (cu.y0 >= 1) & (cu.y0 + HY - 1 <= H) & (cu.x0 >= 1) &
-                           (cu.x0 + HX - 1 <= W);
+                interior = (stu.z0 >= 1) & (stu.z0 + HZ - 1 <= D) & (stu.y0 >= 1) & (stu.y0 + HY - 1 <= H) & (stu.x0 >= 1) &
+                           (stu.x0 + HX - 1 <= W);
                 if (TEM_ZR_ABL & 32) interior = true;   // timing experiment: border code paths compiled out (wrong at the faces)
                 if constexpr (X32) {
                     // the whole halo: 18 buffer loads whose offsets exist already (pvo; the plane offset with the z validity is a
@@ -670,12 +708,12 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
 #pragma unroll
                 for (int j = 0; j < SPP; ++j) {
                     const int q = min((tl_ + 256 * j) / LPV, HY * HX - 1);
-                    const unsigned gy = (unsigned)(cu.y0 - 1 + q / HX), gx = (unsigned)(cu.x0 - 1 + q % HX);
+                    const unsigned gy = (unsigned)(stu.y0 - 1 + q / HX), gx = (unsigned)(stu.x0 - 1 + q % HX);
                     yx |= ((gy < (unsigned)H) & (gx < (unsigned)W)) ? (1u << j) : 0u;
                 }
             }
-            // the SPP loads of halo plane hz live in slot hz % RP of the register ring
-            auto issue_loads = [&](auto interior_tag, auto lo_tag, auto hi_tag) {   // halo planes LO .. HI-1
+            // the SPP loads of halo plane hzb + hz (hz counts the planes THIS team stages) live in slot hz % RP of the register ring
+            auto issue_loads = [&](auto interior_tag, auto lo_tag, auto hi_tag) {   // staged planes LO .. HI-1
                 constexpr bool INTERIOR = decltype(interior_tag)::value;
                 constexpr int LO = decltype(lo_tag)::value, HI = decltype(hi_tag)::value;
                 if (INTERIOR) {
@@ -684,18 +722,18 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
 #pragma unroll
                         for (int j = 0; j < SPP; ++j) {
                             if (TEM_ZR_ABL & 1) tmp[(hz % RP) * SPP + j] = make_float4(0.5f + hz, 0.25f, -1.f, 2.f);
-                            else tmp[(hz % RP) * SPP + j] = zr_load4(rx, poff[j], (unsigned)hz * plane_b);
+                            else tmp[(hz % RP) * SPP + j] = zr_load4(rx, poff[j], (unsigned)(hzb + hz) * plane_b);
                         }
                 } else {
                     if (LO == 0) inb[0] = inb[1] = 0;
 #pragma unroll
                     for (int hz = LO; hz < HI; ++hz) {
-                        const bool zok = (unsigned)(cu.z0 - 1 + hz) < (unsigned)D;   // wave-uniform
+                        const bool zok = (unsigned)(stu.z0 - 1 + hzb + hz) < (unsigned)D;   // wave-uniform
 #pragma unroll
                         for (int j = 0; j < SPP; ++j) {
                             const bool ok = zok & ((yx >> j) & 1u);
                             inb[hz / 3] |= ok ? (1u << ((hz % 3) * SPP + j)) : 0u;
-                            tmp[(hz % RP) * SPP + j] = zr_load4(rx, (ok ? poff[j] : ctr_off) + (ok ? (unsigned)hz * plane_b : plane_b), 0);
+                            tmp[(hz % RP) * SPP + j] = zr_load4(rx, (ok ? poff[j] : ctr_off) + (ok ? (unsigned)(hzb + hz) * plane_b : plane_b), 0);
                         }
                     }
                 }
@@ -740,7 +778,7 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
                                     raw.x = ok ? raw.x : 0u; raw.y = ok ? raw.y : 0u; raw.z = ok ? raw.z : 0u; raw.w = ok ? raw.w : 0u;
                                 }
                                 if (!(TEM_ZR_ABL & 8) || raw.x == 0x12345678u)
-                                    *reinterpret_cast<uint4*>(lds + lwj[j] + hz * ZSTEP) = make_uint4(raw.x, raw.y, raw.z, raw.w);
+                                    *reinterpret_cast<uint4*>(slds + lwj[j] + hz * ZSTEP) = make_uint4(raw.x, raw.y, raw.z, raw.w);
                             }
                         } else
                         if (j < SPP - 1 || slot2) {
@@ -752,7 +790,7 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
 #pragma unroll
                                 for (int c = 0; c < 4; ++c) e[c] *= m;
                             }
-                            unsigned char* dstp = lds + lwj[j] + hz * ZSTEP;   // HY is even: the row parity does not depend on the plane
+                            unsigned char* dstp = slds + lwj[j] + hz * ZSTEP;   // HY is even: the row parity does not depend on the plane
                             if constexpr (X32) {
                                 if (!(TEM_ZR_ABL & 8) || e[0] == 12345.678f) *reinterpret_cast<float4*>(dstp) = make_float4(e[0], e[1], e[2], e[3]);
                             } else
@@ -792,17 +830,20 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
                 auto stage_planes = [&](auto interior_tag) {
 #define ZR_PLANE(HZI)                                                                                              \
     do {                                                                                                           \
-        if ((HZI) + R0 < HZ)                                                                                       \
-            issue_loads(interior_tag, std::integral_constant<int, ((HZI) + R0 < HZ ? (HZI) + R0 : 0)>{},           \
-                        std::integral_constant<int, ((HZI) + R0 < HZ ? (HZI) + R0 + 1 : 0)>{});                    \
+        if ((HZI) + R0 < HZS)                                                                                      \
+            issue_loads(interior_tag, std::integral_constant<int, ((HZI) + R0 < HZS ? (HZI) + R0 : 0)>{},          \
+                        std::integral_constant<int, ((HZI) + R0 < HZS ? (HZI) + R0 + 1 : 0)>{});                   \
         convert(interior_tag, std::integral_constant<int, (HZI)>{});                                               \
     } while (0)
-                    ZR_PLANE(0); ZR_PLANE(1); ZR_PLANE(2); ZR_PLANE(3); ZR_PLANE(4); ZR_PLANE(5);
+                    ZR_PLANE(0); ZR_PLANE(1); ZR_PLANE(2);
+                    if constexpr (HZS == HZ) { ZR_PLANE(3); ZR_PLANE(4); ZR_PLANE(5); }   // (half staging: planes hzb .. hzb + 2 are this team's)
 #undef ZR_PLANE
                 };
                 if (interior) stage_planes(std::true_type{});
                 else stage_planes(std::false_type{});
                 ZR_STAMP(7);
+            }
+            if (do_tap) {   // the chunk this team multiplies next (paired team 0: not the one it has just staged)
                 wsoff = (unsigned)((cu.cot * 27 * nch_all + cu.ksl * nch + ci) * FR) * 16u;   // (column tile, tap 0, chunk) of the packed weights
 #pragma unroll
                 for (int tz = 0; tz < 3; ++tz)
@@ -815,8 +856,8 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
         __syncthreads();
         {
             ZR_STAMP(3);
-            // ================= MFMA phase: 27 taps of one 16-channel chunk out of this team's tile =================
-            if (do_stage) {
+            // ================= MFMA phase: 27 taps of one 16-channel chunk out of this team's tile (paired: the chunk's tile) =================
+            if (do_tap) {
                 int ts = tapstride;
                 asm volatile("" : "+s"(ts));
                 if (TEM_ZR_PRIO) __builtin_amdgcn_s_setprio(TEM_ZR_PRIO);
@@ -941,7 +982,13 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
             }
             ZR_STAMP(4);
         }
-        if (do_stage) {
+        if (PAIR && do_stage) {   // the stage cursor moves on
+            if (++sci == nch) {
+                sci = 0;
+                if (++sui < my_units) su = decode(sui);
+            }
+        }
+        if (do_tap) {
             if (++ci == nch) {
                 ci = 0;
                 eu = cu;
@@ -964,7 +1011,9 @@ __global__ __launch_bounds__(XS ? 256 : 512, XS ? 1 : 2) void k_conv_zr(
                 }
             }
         }
-        __syncthreads();
+        // paired: team 0 has no tap phase in iteration 0 and goes straight on to stage chunk 1 beside team 1's first taps
+        // (wave-uniform condition; team 0's missing barrier is the one behind the loop that team 1 never executes)
+        if (!(PAIR && lag && s == 0)) __syncthreads();
         ZR_STAMP(5);
     }
     if (!team) __syncthreads();
@@ -988,6 +1037,9 @@ ZrGeom tem_zr_geometry(const TemConvCall& c, const TemConvShape& sh, int mode) {
     g.nX = (sh.W + 7) / 8;
     g.nunits = (int64_t)sh.N * g.nZ * g.nY * g.nX * (sh.Cout / 32);
     g.ok = g.nunits < (1ll << 31) && g.nunits >= tem_team_min_units(2);
+    // sibling pairing (k_conv_zr<.., PAIR>): an even number of column tiles, so that the teams of a workgroup hold (tile, cot) and
+    // (tile, cot + 1); instantiated for the two-term split modes on fp32 tensors (zr_variant: ZrVariant<2, f16>)
+    g.pair = tem_option(TEM_OPT_ZR_PAIR) && sh.Cout % 64 == 0 && c.stx == TEM_ST_F32 && mode != TEM_ARITH_FP32 && tem_arith(mode).planes == 2;
     return g;
 }
 
@@ -998,7 +1050,7 @@ static int zr_tile_blocks(const ZrGeom& g) {
     return lg(g.nX) | (lg(g.nY) << 4) | (lg(g.nZ) << 8);
 }
 
-template <int NS, bool F16, int MODE, bool KSPLIT = false, bool WIDE = false, typename T = float, bool X32 = false, bool XS = false>
+template <int NS, bool F16, int MODE, bool KSPLIT = false, bool WIDE = false, typename T = float, bool X32 = false, bool XS = false, bool PAIR = false>
 static void zr_launch(const TemConvCall& c, const ZrGeom& g, const float* x_, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                       const float* bias, float* y_, int64_t y_ld, const float* ref_, int64_t ref_ld, const TemConvShape& sh,
                       int act, float* stat, const unsigned* in_amax, hipStream_t s, int ks = 1) {
@@ -1007,7 +1059,10 @@ static void zr_launch(const TemConvCall& c, const ZrGeom& g, const float* x_, in
     const T* x = reinterpret_cast<const T*>(x_);
     const T* ref = reinterpret_cast<const T*>(ref_);
     auto* y = reinterpret_cast<std::conditional_t<KSPLIT, float, T>*>(y_);
-    auto kern = &k_conv_zr<NS, F16, MODE, KSPLIT, WIDE, T, X32, XS>;
+    if constexpr (!PAIR && NS == 2 && !WIDE && !X32 && sizeof(T) == 4) {   // the plan's pairing bit: the same launch on the paired kernel
+        if (g.pair) return zr_launch<NS, F16, MODE, KSPLIT, WIDE, T, X32, XS, true>(c, g, x_, x_ld, scale, shift, wp, bias, y_, y_ld, ref_, ref_ld, sh, act, stat, in_amax, s, ks);
+    }
+    auto kern = &k_conv_zr<NS, F16, MODE, KSPLIT, WIDE, T, X32, XS, PAIR>;
     static bool attr = false;
     if (!attr) {
         (void)hipFuncSetAttribute(reinterpret_cast<const void*>(kern), hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsb);
