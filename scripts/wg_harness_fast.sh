@@ -7,7 +7,7 @@ cd "$(dirname "$0")/.."
 tag=$1; shift
 mkdir -p build
 HIPCC="/opt/rocm/bin/hipcc --offload-arch=gfx950 -O3 -std=c++17 -Wno-unused-result -fno-slp-vectorize"
-REN="-Dk_conv_wgrad_zs=k_conv_wgrad_zs_hx -Dtem_conv_wgrad_bf16x3=tem_conv_wgrad_bf16x3_hx -Dtem_tr_trace_buf=tem_tr_trace_buf_hx -Dk_conv_wgrad_tr=k_conv_wgrad_tr_hx -Dtem_conv_wgrad_tr_launch=tem_conv_wgrad_tr_launch_hx"
+REN="-Dk_conv_wgrad_zs=k_conv_wgrad_zs_hx -Dtem_conv_wgrad_zs=tem_conv_wgrad_zs_hx -Dtem_tr_trace_buf=tem_tr_trace_buf_hx -Dk_conv_wgrad_tr=k_conv_wgrad_tr_hx -Dtem_conv_wgrad_tr_launch=tem_conv_wgrad_tr_launch_hx"
 if [ ! -f build/wgh_bf16x3.o ] || [ torch_em_amd/csrc/conv_bf16x3.hip -nt build/wgh_bf16x3.o ]; then
   $HIPCC $REN -c torch_em_amd/csrc/conv_bf16x3.hip -o build/wgh_bf16x3.o
 fi

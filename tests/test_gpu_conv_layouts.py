@@ -293,6 +293,60 @@ def test_conv_dgrad_refnorm_wgrad_layouts(shape, lay, mode, dt, variant):
         assert rel_err(dw.cpu().view(w.shape), dwe) < 1e-4
 
 
+def test_wgrad_refusals_write_nothing():
+    """Five weight-gradient calls that the launch plan (csrc/conv.hip: wgrad_plan) refuses for an argument, through the C entry
+    points: each returns TEM_EINVAL with dw, db, the sums, the amax word and the workspace still at their sentinel -- a refusal
+    comes before anything is enqueued.  (1, 8, 8, 8, 32 -> 32), 3x3x3 is the smallest shape of the z-sliding plan."""
+    from torch_em_amd import _lib
+    lib = _lib.load()
+    EINVAL = -1
+    stream = ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+    P = lambda t: ctypes.c_void_p(t.data_ptr())   # noqa: E731
+    N, D, H, W, C = 1, 8, 8, 8, 32
+    NV, K = N * D * H * W, (3, 3, 3)
+    gen = torch.Generator().manual_seed(5)
+    rnd = lambda *s, dt=torch.float32: torch.randn(*s, generator=gen).to(DEV, dt)   # noqa: E731
+    F16 = 5 | (1 << 8) | (1 << 12)   # use_mfma 5 with fp16 storage of x and g
+    assert lib.tem_conv3d_wgrad_sums_ok(N, D, H, W, C, C, *K, 1) == 1   # (wgrad_sums_min_mb is 0 under tests/conftest.py)
+    assert lib.tem_conv3d_wgrad_gmax_ok(N, D, H, W, C, C, *K, 5) == 0 and lib.tem_conv3d_wgrad_cs_ok(N, D, H, W, C, C, *K, 0, 64) == 0
+
+    def refused(call, shape=(N, D, H, W, C, C), mode=1):
+        """call(dw, db, sums, amax, ws, ws_bytes) -> return code; the outputs it was handed must come back untouched"""
+        nws = lib.tem_conv3d_wgrad_ws(*shape, *K, mode)
+        outs = [torch.full((n,), SENT, device=DEV) for n in (27 * shape[4] * shape[5], shape[5], 4096, nws // 4 + 1)]
+        amax = torch.full((1,), 0x07070707, dtype=torch.int32, device=DEV)
+        lib.tem_last_error()
+        rc = call(outs[0], outs[1], outs[2], amax, outs[3], nws)
+        torch.cuda.synchronize()
+        assert rc == EINVAL, (rc, lib.tem_last_error())
+        assert all(bool((t == SENT).all()) for t in outs) and int(amax) == 0x07070707, "a refused weight gradient wrote to its outputs"
+
+    x, g, w = rnd(NV, C), rnd(NV, C), rnd(C, C, 3, 3, 3)
+    x35 = torch.zeros(NV, 35, device=DEV)
+    # exact fp32 with the norm sums, x in rows of 35 floats: the transposing kernel that delivers the sums cannot load them
+    refused(lambda dw, db, sums, amax, ws, n: lib.tem_conv3d_wgrad_sums(P(x35), 35, None, None, P(g), C, P(w), None, None, P(dw), P(db), P(sums),
+                                                                         P(ws), n, N, D, H, W, C, C, *K, 1, stream))
+    # a chunk stride on fp32 tensors
+    refused(lambda dw, db, sums, amax, ws, n: lib.tem_conv3d_wgrad_ex(P(x), C, None, None, P(g), C, None, None, None, P(dw), P(db), None, None, None,
+                                                                       P(ws), n, N, D, H, W, C, C, *K, 5, 64, None, stream), mode=5)
+    # fp16 tensors on a z-sliding kernel other than the transposing one
+    x16, g16 = x.half(), g.half()
+    old = _lib.get_option("wgrad_zs")
+    _lib.set_option("wgrad_zs", 2)
+    try:
+        refused(lambda dw, db, sums, amax, ws, n: lib.tem_conv3d_wgrad_ex(P(x16), C, None, None, P(g16), C, None, None, None, P(dw), P(db), None, None,
+                                                                           None, P(ws), n, N, D, H, W, C, C, *K, F16, 0, None, stream), mode=F16)
+    finally:
+        _lib.set_option("wgrad_zs", old)
+    # the first-layer weight gradient behind a norm, y in rows of 9 floats
+    x1, g8, y9, coef = rnd(NV, 1), rnd(NV, 8), torch.zeros(NV, 9, device=DEV), rnd(N, 8, 4)
+    refused(lambda dw, db, sums, amax, ws, n: lib.tem_conv3d_wgrad_gnorm(P(x1), 1, None, None, P(g8), 8, P(y9), 9, P(coef), P(dw), P(db), P(ws), n,
+                                                                          N, D, H, W, 1, 8, *K, 1, stream), shape=(N, D, H, W, 1, 8), mode=0)
+    # max |g| from a one-term mode
+    refused(lambda dw, db, sums, amax, ws, n: lib.tem_conv3d_wgrad_ex(P(x), C, None, None, P(g), C, None, None, None, P(dw), P(db), None, None, P(amax),
+                                                                       P(ws), n, N, D, H, W, C, C, *K, 5, 0, None, stream), mode=5)
+
+
 # ---------------------------------------------------------------------------------------------------------------------
 # L3: the 32-bit plane edge of the team kernels, H * W * 32 * ld = 2^31 (refused) and ld = 1016 (taken), one wide operand
 # at a time.  2 x 4 x 256^2 voxels: 2 GiB per wide fp32 buffer.

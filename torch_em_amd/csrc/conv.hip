@@ -745,34 +745,6 @@ static WgradGenericPlan wgrad_generic_plan(int64_t NV, int Cin, int Cout, int nt
     return p;
 }
 
-extern "C" int64_t tem_conv3d_wgrad_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
-                                       int use_mfma) {
-    use_mfma &= 0xff;   // (the storage types do not change the workspace)
-    int64_t NV = (int64_t)N * D * H * W;
-    int ntaps = kd * kh * kw;
-    WgradGenericPlan p = wgrad_generic_plan(NV, Cin, Cout, ntaps);
-    int64_t bytes = tem_align_up(p.db_floats, 64) * 4;
-    // an MFMA mode asked about channel counts its launch refuses: the plans below divide by Cin / 32 -- answer for the VALU path
-    if (Cin % 32 || Cout % 32) use_mfma = TEM_ARITH_VALU;
-    if (tem_arith_split_wgrad(use_mfma)) {
-        bytes += tem_conv_wgrad_bf16x3_ws(N, D, H, W, Cin, Cout, kd, kh, kw);
-    } else if (use_mfma) {
-        int64_t b = tem_conv_wgrad_mfma_ws(N, D, H, W, Cin, Cout, kd, kh, kw);
-        if (tem_conv_wgrad_tr_fp32_ok(N, D, H, W, Cin, Cout, kd, kh, kw)) {
-            const int64_t b2 = tem_conv_wgrad_bf16x3_ws(N, D, H, W, Cin, Cout, kd, kh, kw);
-            if (b2 > b) b = b2;
-        }
-        bytes += b;
-    } else {
-        int64_t b = p.part_floats * 4;
-        int64_t c1 = tem_conv_wgrad_cin1_ws(Cout, ntaps), pj = tem_conv1x1_proj_wgrad_ws(Cin, Cout);
-        if (Cin <= 4 && c1 > b) b = c1;
-        if (ntaps == 1 && pj > b) b = pj;
-        bytes += b;
-    }
-    return bytes + 256;
-}
-
 template <int KD, int KH, int KW>
 static void launch_wgrad_generic(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
                                  int64_t g_ld, int N, int D, int H, int W, int Cin, int Cout,
@@ -782,6 +754,189 @@ static void launch_wgrad_generic(const TemConvCall& c, const float* x, int64_t x
     TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, (void)0,
                    hipLaunchKernelGGL((k_conv_wgrad_generic<KD, KH, KW, TX, TG>), dim3(p.nchunks, p.npb), dim3(256), lds, s, (const TX*)x,
                                       x_ld, scale, shift, (const TG*)g, g_ld, N, D, H, W, Cin, Cout, p.npairs_blk, p.rows, p.vper, part));
+}
+
+// ---------------------------------------------------------------------------
+// The weight-gradient dispatch (DESIGN.md "Weight-gradient dispatch: one plan"): wgrad_plan() decides ONCE which kernel a call
+// takes, with which geometry and workspace regions, and which by-products that kernel delivers.  conv3d_wgrad_impl executes the
+// plan; the queries (tem_conv3d_wgrad_ws, _sums_ok, _gmax_ok, _gscaled_ok, _cs_ok, _gnorm_ok) print it for synthetic facts.
+// Split modes: z-sliding, else the split-precision patch kernel.  Every other MFMA mode runs exact fp32: the transposing
+// z-sliding kernel where the layout allows its 16-byte loads, else the fp32 patch kernel.  VALU: first layer, projection, generic.
+// ---------------------------------------------------------------------------
+enum WgradKernel { WK_GENERIC, WK_CIN1, WK_PROJ, WK_ZS, WK_PATCH, WK_PATCH_FP32, WK_REFUSED };
+
+// what the decision depends on besides the call, the shape and the mode
+struct WgradFacts {
+    int64_t x_ld, g_ld, gnx_ld;
+    // operand groups on 16-byte boundaries (an absent operand counts as aligned)
+    bool x16, g16;
+    bool ss16;   // scale and shift
+    bool gn16;   // gnx and gcoef
+    bool scale, db, norm_sums, w, gcoef, sd_layout;   // which optional operands the call carries (w: the weights the sums read)
+    int64_t ws_bytes;
+};
+
+struct WgradPlan {
+    WgradKernel kernel;
+    int rc;                  // WK_REFUSED: TEM_EINVAL or TEM_EWS
+    TemWgradKind kind;       // the arithmetic of the MFMA families
+    ZsPlan zs;               // WK_ZS (k_conv_wgrad_zs<zs.nco> / _zt if zs.teams / _tr if zs.tr)
+    WbPlan wb;               // WK_PATCH
+    WgradFp32Plan fp32;      // WK_PATCH_FP32
+    WgradGenericPlan gen;    // WK_GENERIC; its bias partials lie at the start of the workspace in every plan
+    int64_t ws_bytes;        // the workspace the launch needs (also of a plan refused for its layout)
+    int64_t part, dbpart, extra;   // regions of the planned kernel, in floats from the start of the workspace: partial slabs, bias
+                                   // partials, WK_ZS: what the sums merge needs behind them
+    // what the planned kernel delivers when a call asks for it (a call that asks for more is refused)
+    bool sums;    // the norm-backward sums
+    bool gmax;    // max |g| (g_amax_out)
+    bool f16x2;   // the fp16 2x1 arithmetic from a prescale (g_amax_in)
+    bool cs;      // this call's chunk stride of x
+    char error[320];         // WK_REFUSED: the message of the error the launch returns
+};
+
+static WgradPlan& wgrad_refuse(WgradPlan& p, int rc, const char* fmt, ...) __attribute__((format(printf, 3, 4)));
+static WgradPlan& wgrad_refuse(WgradPlan& p, int rc, const char* fmt, ...) {
+    va_list ap;
+    va_start(ap, fmt);
+    vsnprintf(p.error, sizeof(p.error), fmt, ap);
+    va_end(ap);
+    p.kernel = WK_REFUSED;
+    p.rc = rc;
+    return p;
+}
+
+static WgradPlan wgrad_plan(const TemConvCall& c, const TemConvShape& sh, int mode, const WgradFacts& f) {
+    WgradPlan p = {};
+    const int Cin = sh.Cin, Cout = sh.Cout, ntaps = sh.kd * sh.kh * sh.kw, st = c.stx;
+    const bool split = tem_arith_split_wgrad(mode);   // (any other MFMA mode runs exact fp32)
+    p.kind = split ? tem_arith(mode).wgrad : mode != TEM_ARITH_VALU ? TEM_WG_FP32 : TEM_WG_NONE;
+    // the MFMA geometries divide by Cin / 32: an MFMA mode on other channel counts is sized as the VALU family and refused below
+    const bool chan32 = Cin % 32 == 0 && Cout % 32 == 0;
+    p.kernel = WK_GENERIC;
+    p.gen = wgrad_generic_plan(sh.NV(), Cin, Cout, ntaps);
+    p.part = tem_align_up(p.gen.db_floats, 64);
+    int64_t bytes;   // of the regions behind p.part
+    bool sums_shape = false;
+    if (mode != TEM_ARITH_VALU && chan32) {
+        p.zs = tem_zs_plan(sh);
+        sums_shape = p.zs.use && tem_wgrad_sums_takes(sh);
+        const int64_t zs_bytes =
+            (p.zs.part_floats(sh) + p.zs.db_floats(sh) + (sums_shape ? tem_wgrad_sums_ws_floats(sh.N, sh.D, sh.H, Cin, Cout) : 0)) * 4 + 256;
+        if (split && p.zs.use) {
+            p.kernel = WK_ZS;
+            bytes = zs_bytes;
+        } else if (split) {
+            p.kernel = WK_PATCH;
+            p.wb = tem_wb_plan(sh);
+            p.dbpart = p.part + tem_align_up((int64_t)p.wb.S * p.wb.ks2 * ntaps * Cin * Cout, 64);
+            bytes = (p.dbpart - p.part) * 4 + (int64_t)p.wb.S * Cout * 4 + 256;
+        } else {
+            const bool tr = p.zs.use && p.zs.tr;
+            p.kernel = tr && !c.stx && !c.sty && f.x_ld % 4 == 0 && f.g_ld % 4 == 0 && f.x16 && f.g16 ? WK_ZS : WK_PATCH_FP32;
+            p.fp32 = tem_wgrad_fp32_plan(sh);
+            p.dbpart = p.part + tem_align_up((int64_t)p.fp32.S * ntaps * Cin * Cout, 64);
+            bytes = ((int64_t)p.fp32.S * ntaps * Cin * Cout + (int64_t)p.fp32.S * Cout) * 4 + 256;
+            // alignment moves an exact-fp32 call between the transposing kernel and the patch kernel at launch time, which the
+            // workspace query cannot know: sized for both
+            if (tr && zs_bytes > bytes) bytes = zs_bytes;
+        }
+        if (p.kernel == WK_ZS) {
+            p.dbpart = p.part + p.zs.part_floats(sh);
+            p.extra = p.dbpart + p.zs.db_floats(sh);
+        }
+    } else {
+        bytes = p.gen.part_floats * 4;
+        if (Cin <= 4 && tem_conv_wgrad_cin1_ws(Cout, ntaps) > bytes) bytes = tem_conv_wgrad_cin1_ws(Cout, ntaps);
+        if (ntaps == 1 && tem_conv1x1_proj_wgrad_ws(Cin, Cout) > bytes) bytes = tem_conv1x1_proj_wgrad_ws(Cin, Cout);
+        if (mode == TEM_ARITH_VALU) {   // g (and the gnorm operands) in 16-byte rows / x without a pre-norm in 16-byte rows
+            if (tem_conv_wgrad_cin1_takes(sh) && f.g_ld % 4 == 0 && f.g16 && !(f.gcoef && (f.gnx_ld % 4 || !f.gn16))) p.kernel = WK_CIN1;
+            else if (ntaps == 1 && tem_conv1x1_proj_wgrad_takes(Cin, Cout) && !f.scale && f.x_ld % 4 == 0 && f.x16) p.kernel = WK_PROJ;
+        }
+    }
+    p.ws_bytes = p.part * 4 + bytes + 256;
+    const bool zs = p.kernel == WK_ZS;
+    p.gmax = zs && p.kind == TEM_WG_BF16X3;
+    p.f16x2 = zs && p.kind == TEM_WG_F16X2 && (!p.zs.teams || p.zs.tr);   // (k_conv_wgrad_zt has no fp16 2x1 variant)
+    p.cs = zs && p.zs.tr && st != 0 && c.x_cs % 8 == 0;
+    // exact fp32 delivers the sums where the data gradient that consumes them runs on the z-reuse kernel (option fp32_zr); an
+    // fp32 call that alignment moves off the transposing kernel is refused below
+    p.sums = sums_shape && (split || (mode == TEM_ARITH_FP32 && tem_option(TEM_OPT_FP32_ZR) && !c.stx && !c.sty && p.zs.tr));
+
+    // by-products the planned kernel does not deliver
+    if (c.g_amax_out && !p.gmax)
+        return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad_gmax: tem_conv3d_wgrad_gmax_ok() == 0 for this layer");
+    if (c.g_amax_in && !p.f16x2)
+        return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad_gscaled: tem_conv3d_wgrad_gscaled_ok() == 0 for this layer");
+    if (f.norm_sums && !(f.w && f.db && f.sd_layout && p.sums))
+        return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad_sums: norm_sums needs weights, a bias gradient and tem_conv3d_wgrad_sums_ok() != 0");
+    if (f.gcoef && p.kernel != WK_CIN1)
+        return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad_gnorm: only the small-Cin first-layer kernel applies a norm backward to g "
+                                           "(tem_conv3d_wgrad_gnorm_ok() != 0; g / y / coefficients 16-byte aligned with ld %% 4 == 0)");
+    if (f.ws_bytes < p.ws_bytes) return wgrad_refuse(p, TEM_EWS, "tem_conv3d_wgrad: workspace too small");
+    if (c.x_cs && !p.cs)
+        return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad_ex: a chunk stride (x_cs) needs 16-bit tensors on the transposing z-sliding "
+                                           "kernel (use_mfma 5 / 7, tem_conv3d_wgrad_cs_ok() != 0), x_cs %% 8 == 0");
+    if (mode == TEM_ARITH_VALU) return p;
+    const char* const who = split ? "bf16x3" : "mfma";
+    if (!chan32) return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad(%s): needs Cin%%32==0 and Cout%%32==0 (got %d,%d)", who, Cin, Cout);
+    if (st != c.sty) return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad(%s): x and g must have the same storage type", who);
+    if (!tem_wgrad_storage_ok(p.kind, st))
+        return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad(%s): 16-bit storage goes with the one-term mode of the same type (fp16: "
+                                           "use_mfma 5, bf16: use_mfma 7), got storage %d", who, st);
+    if (f.x_ld % (st ? 8 : 4) || f.g_ld % (st ? 8 : 4) || !f.x16 || !f.g16)
+        return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad(%s): x / g must be 16-byte aligned with ld%%4==0 (16-bit storage: ld%%8==0)", who);
+    if (!f.ss16) return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad(%s): scale/shift must be 16-byte aligned", who);
+    if (p.kind == TEM_WG_F16X2 && !c.g_amax_in)
+        return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad_gscaled: the fp16 2x1 arithmetic (use_mfma 8) needs g_amax");
+    if (f.norm_sums && !zs)
+        return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad_sums: only the z-sliding kernels deliver the norm sums (x / g need 16-byte rows)");
+    if (zs) {
+        if ((int64_t)sh.H * sh.W * (f.x_ld > f.g_ld ? f.x_ld : f.g_ld) * 4 >= (1ll << 31))
+            return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad(%s): one z-plane of x / g must stay below 2 GiB (32-bit offsets inside a plane)", who);
+        if (st && !p.zs.tr)
+            return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad: 16-bit storage needs the transposing z-sliding kernel (option wgrad_zs = 3)");
+    } else if (sh.key() != 7 && sh.key() != 3 && sh.key() != 0) {
+        return wgrad_refuse(p, TEM_EINVAL, "tem_conv3d_wgrad(%s): kernel (%d,%d,%d) has no MFMA instantiation", who, sh.kd, sh.kh, sh.kw);
+    }
+    return p;
+}
+
+// The plan of a dense, 16-byte aligned launch of this shape with all the workspace it asks for, as the queries see it
+static WgradPlan wgrad_query(const TemConvCall& c, const TemConvShape& sh, int mode) {
+    const WgradFacts f = {sh.Cin, sh.Cout, sh.Cout, true, true, true, true, false, true, false, false, false, true, INT64_MAX};
+    return wgrad_plan(c, sh, mode, f);
+}
+
+extern "C" int64_t tem_conv3d_wgrad_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
+    // (the storage types do not change the workspace)
+    return wgrad_query(TemConvCall{}, TemConvShape{N, D, H, W, Cin, Cout, kd, kh, kw}, use_mfma & 0xff).ws_bytes;
+}
+
+extern "C" int tem_conv3d_wgrad_sums_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
+    const TemConvCall c = conv_call(use_mfma);
+    return wgrad_query(c, TemConvShape{N, D, H, W, Cin, Cout, kd, kh, kw}, use_mfma).sums;
+}
+
+extern "C" int tem_conv3d_wgrad_gmax_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
+    return wgrad_query(TemConvCall{}, TemConvShape{N, D, H, W, Cin, Cout, kd, kh, kw}, use_mfma & 0xff).gmax;
+}
+
+extern "C" int tem_conv3d_wgrad_gscaled_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
+    return wgrad_query(TemConvCall{}, TemConvShape{N, D, H, W, Cin, Cout, kd, kh, kw}, TEM_ARITH_F16X2).f16x2;
+}
+
+// x of storage type st with chunk stride x_cs, in the one-term mode of that type
+extern "C" int tem_conv3d_wgrad_cs_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int st, int64_t x_cs) {
+    TemConvCall c = {st, st};
+    c.x_cs = x_cs;
+    return wgrad_query(c, TemConvShape{N, D, H, W, Cin, Cout, kd, kh, kw}, st == TEM_ST_BF16 ? TEM_ARITH_BF16 : TEM_ARITH_F16).cs;
+}
+
+// tem_conv3d_wgrad_gnorm: the layers of the small-Cin first-layer kernel (whatever their extent)
+extern "C" int tem_conv3d_wgrad_gnorm_ok(int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
+    if (Cin <= 0 || Cout <= 0) return 0;
+    return wgrad_query(TemConvCall{}, TemConvShape{1, 1, 1, 1, Cin, Cout, kd, kh, kw}, use_mfma & 0xff).kernel == WK_CIN1;
 }
 
 static int conv3d_wgrad_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
@@ -800,74 +955,50 @@ static int conv3d_wgrad_impl(const TemConvCall& c, const float* x, int64_t x_ld,
                 "tem_conv3d_wgrad: unsupported storage types (x %d, g %d)", stx, sty);
     TEM_REQUIRE(!(stx || sty) || tem_arith(use_mfma).wgrad != TEM_WG_FP32,
                 "tem_conv3d_wgrad: the exact-fp32 MFMA kernels take fp32 tensors only");
-    if (ws_bytes < tem_conv3d_wgrad_ws(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)) {
-        tem_set_error("tem_conv3d_wgrad: workspace too small");
-        return TEM_EWS;
+    const TemConvShape sh = {N, D, H, W, Cin, Cout, kd, kh, kw};
+    auto al16 = [](const void* ptr) { return (uintptr_t)ptr % 16 == 0; };
+    const WgradFacts facts = {x_ld, g_ld, gnx_ld, al16(x), al16(g), al16(scale) && al16(shift), al16(gnx) && al16(gcoef),
+                              scale != nullptr, db != nullptr, norm_sums != nullptr, w_sd != nullptr, gcoef != nullptr, sd_layout != 0,
+                              ws_bytes};
+    const WgradPlan p = wgrad_plan(c, sh, use_mfma, facts);
+    if (p.kernel == WK_REFUSED) {
+        tem_set_error("%s", p.error);
+        return p.rc;
     }
     hipStream_t s = (hipStream_t)stream;
-    const int64_t NV = (int64_t)N * D * H * W;
-    const int ntaps = kd * kh * kw;
-    WgradGenericPlan p = wgrad_generic_plan(NV, Cin, Cout, ntaps);
-    float* dbpart = (float*)ws;
-    float* rest = dbpart + tem_align_up(p.db_floats, 64);
-    TEM_REQUIRE(!gcoef || !use_mfma, "tem_conv3d_wgrad_gnorm: use_mfma must be 0");
-    TEM_REQUIRE(!c.x_cs || tem_arith_one_term(use_mfma), "tem_conv3d_wgrad_ex: a chunk stride needs use_mfma 5 / 7");
-    if (tem_arith_split_wgrad(use_mfma)) {
-        // F16 / BF16: single product in the z-sliding kernel (autocast-equivalent); the other shapes keep bf16x3
-        // F16X2: fp16 2x1 (tem_conv3d_wgrad_gscaled; z-sliding kernel only)
-        int rc = tem_conv_wgrad_bf16x3(c, x, x_ld, scale, shift, g, g_ld, dw, db, rest,
-                                       ws_bytes - (int64_t)((char*)rest - (char*)ws), N, D, H, W, Cin, Cout, kd, kh, kw,
-                                       sd_layout, tem_arith(use_mfma).wgrad, w_sd, gamma,
-                                       beta, norm_sums, s);
-        if (rc != TEM_OK) return rc;
-        TEM_CHECK_LAUNCH("tem_conv3d_wgrad(bf16x3)");
-        return TEM_OK;
-    }
-    if (use_mfma && !(stx || sty) && tem_conv_wgrad_tr_fp32_ok(N, D, H, W, Cin, Cout, kd, kh, kw) && x_ld % 4 == 0 && g_ld % 4 == 0 &&
-        ((uintptr_t)x % 16 == 0) && ((uintptr_t)g % 16 == 0)) {
-        // exact fp32 on the z-sliding staging-team kernel (round 4): fp32 records in LDS, v_mfma_f32_32x32x2_f32; the slab
-        // merge delivers the norm sums as in the split modes (round 6: the merge does not care which arithmetic filled the slabs)
-        int rc = tem_conv_wgrad_bf16x3(c, x, x_ld, scale, shift, g, g_ld, dw, db, rest,
-                                       ws_bytes - (int64_t)((char*)rest - (char*)ws), N, D, H, W, Cin, Cout, kd, kh, kw,
-                                       sd_layout, TEM_WG_FP32, w_sd, gamma, beta, norm_sums, s);
-        if (rc != TEM_OK) return rc;
-        TEM_CHECK_LAUNCH("tem_conv3d_wgrad(fp32, z-sliding)");
-        return TEM_OK;
-    }
-    TEM_REQUIRE(!norm_sums, "tem_conv3d_wgrad_sums: only the z-sliding kernels deliver the norm sums (tem_conv3d_wgrad_sums_ok() == 0)");
-    if (use_mfma) {
-        int rc = tem_conv_wgrad_mfma(x, x_ld, scale, shift, g, g_ld, dw, db, rest,
-                                     ws_bytes - (int64_t)((char*)rest - (char*)ws), N, D, H, W, Cin, Cout, kd, kh, kw,
-                                     sd_layout, s);
-        if (rc != TEM_OK) return rc;
-        TEM_CHECK_LAUNCH("tem_conv3d_wgrad(mfma)");
-        return TEM_OK;
-    }
-    if (tem_conv_wgrad_cin1(c, x, x_ld, scale, shift, g, g_ld, dw, db, rest, N, D, H, W, Cin, Cout, kd, kh, kw, sd_layout,
-                            gnx, gnx_ld, gcoef, s)) {
-        TEM_CHECK_LAUNCH("tem_conv3d_wgrad(cin1)");
-        return TEM_OK;
-    }
-    TEM_REQUIRE(!gcoef, "tem_conv3d_wgrad_gnorm: only the small-Cin first-layer kernel applies a norm backward to g");
-    if (ntaps == 1 && tem_conv1x1_proj_wgrad(c, x, x_ld, scale, g, g_ld, dw, db, rest, NV, Cin, Cout, sd_layout, s)) {
-        TEM_CHECK_LAUNCH("tem_conv3d_wgrad(proj)");
-        return TEM_OK;
-    }
-    if (db) {
-        int Cb = Cout < 256 ? Cout : 256;
-        int rows = 256 / Cb;
-        int64_t vper = tem_cdiv(NV, p.db_chunks);
-        TEM_ST_SWITCH(c.sty, TG,
-                      hipLaunchKernelGGL(k_colsum_partial<TG>, dim3(p.db_chunks), dim3(256), (size_t)rows * Cb * sizeof(float), s,
-                                         (const TG*)g, g_ld, NV, Cout, rows, vper, dbpart));
-        tem_reduce_slabs(dbpart, p.db_chunks, (int64_t)Cout, (int64_t)Cout, db, s);
-    }
-#define CALL(A, B, C) launch_wgrad_generic<A, B, C>(c, x, x_ld, scale, shift, g, g_ld, N, D, H, W, Cin, Cout, p, rest, s)
-    DISPATCH_K(kd, kh, kw, CALL);
+    float* const part = (float*)ws + p.part;
+    float* const dbpart = db ? (float*)ws + p.dbpart : nullptr;
+    static const char* const what[] = {"tem_conv3d_wgrad(generic)", "tem_conv3d_wgrad(cin1)", "tem_conv3d_wgrad(proj)",
+                                       "tem_conv3d_wgrad(z-sliding)", "tem_conv3d_wgrad(bf16x3)", "tem_conv3d_wgrad(mfma)"};
+    if (p.kernel == WK_ZS) {
+        tem_conv_wgrad_zs(c, p.zs, p.kind, x, x_ld, scale, shift, g, g_ld, dw, db, part, dbpart, (float*)ws + p.extra, sh, sd_layout, w_sd,
+                          gamma, beta, norm_sums, s);
+    } else if (p.kernel == WK_PATCH) {
+        tem_conv_wgrad_patch(c, p.wb, x, x_ld, scale, shift, g, g_ld, dw, db, part, dbpart, sh, sd_layout, s);
+    } else if (p.kernel == WK_PATCH_FP32) {
+        tem_conv_wgrad_mfma(p.fp32, x, x_ld, scale, shift, g, g_ld, dw, db, part, dbpart, sh, sd_layout, s);
+    } else if (p.kernel == WK_CIN1) {
+        tem_conv_wgrad_cin1(c, x, x_ld, scale, shift, g, g_ld, dw, db, part, sh, sd_layout, gnx, gnx_ld, gcoef, s);
+    } else if (p.kernel == WK_PROJ) {
+        tem_conv1x1_proj_wgrad(c, x, x_ld, g, g_ld, dw, db, part, sh.NV(), Cin, Cout, sd_layout, s);
+    } else {
+        const int64_t NV = sh.NV();
+        const int ntaps = kd * kh * kw;
+        if (db) {   // bias partials at the start of the workspace
+            int Cb = Cout < 256 ? Cout : 256;
+            int rows = 256 / Cb;
+            int64_t vper = tem_cdiv(NV, p.gen.db_chunks);
+            TEM_ST_SWITCH(c.sty, TG,
+                          hipLaunchKernelGGL(k_colsum_partial<TG>, dim3(p.gen.db_chunks), dim3(256), (size_t)rows * Cb * sizeof(float), s,
+                                             (const TG*)g, g_ld, NV, Cout, rows, vper, (float*)ws));
+            tem_reduce_slabs((const float*)ws, p.gen.db_chunks, (int64_t)Cout, (int64_t)Cout, db, s);
+        }
+#define CALL(A, B, C) launch_wgrad_generic<A, B, C>(c, x, x_ld, scale, shift, g, g_ld, N, D, H, W, Cin, Cout, p.gen, part, s)
+        DISPATCH_K(kd, kh, kw, CALL);
 #undef CALL
-    int64_t n = (int64_t)ntaps * Cin * Cout;
-    tem_reduce_slabs_w(rest, p.nchunks, ntaps, Cin, Cout, n, dw, sd_layout, s);
-    TEM_CHECK_LAUNCH("tem_conv3d_wgrad(generic)");
+        tem_reduce_slabs_w(part, p.gen.nchunks, ntaps, Cin, Cout, (int64_t)ntaps * Cin * Cout, dw, sd_layout, s);
+    }
+    TEM_CHECK_LAUNCH(what[p.kernel]);
     return TEM_OK;
 }
 
@@ -883,9 +1014,7 @@ extern "C" int tem_conv3d_wgrad(const float* x, int64_t x_ld, const float* scale
 // Backward of the network's output projection (out_conv: nn.Conv3d(features, out_channels, 1), reference model/unet.py:638)
 // in ONE pass over its input x (a ReLU output): dw, db as tem_conv3d_wgrad AND the masked data gradient
 // gx = (x > 0) * (g . w) as tem_conv3d_fwd(transposed pack, ref = x) -- two kernels that each read the 512 MB tensor before.
-extern "C" int tem_conv1x1_out_bwd_ok(int Cin, int Cout) {
-    return Cin % 32 == 0 && Cin <= 64 && Cout >= 1 && Cout <= 4 && (Cin / 32) * Cout <= 8;
-}
+extern "C" int tem_conv1x1_out_bwd_ok(int Cin, int Cout) { return tem_conv1x1_out_bwd_takes(Cin, Cout); }
 static int conv1x1_out_bwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* g, int64_t g_ld, const float* w,
                                 float* gx, int64_t gx_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int64_t NV, int Cin,
                                 int Cout, tem_stream_t stream) {
@@ -893,10 +1022,9 @@ static int conv1x1_out_bwd_impl(const TemConvCall& c, const float* x, int64_t x_
                 "tem_conv1x1_out_bwd: bad arguments");
     TEM_REQUIRE(tem_conv1x1_out_bwd_ok(Cin, Cout), "tem_conv1x1_out_bwd: tem_conv1x1_out_bwd_ok() == 0 for %d -> %d", Cin, Cout);
     TEM_REQUIRE(ws_bytes >= tem_conv1x1_proj_wgrad_ws(Cin, Cout), "tem_conv1x1_out_bwd: workspace too small");
-    if (!tem_conv1x1_out_bwd(c, x, x_ld, g, g_ld, w, gx, gx_ld, dw, db, ws, NV, Cin, Cout, 1, (hipStream_t)stream)) {
-        tem_set_error("tem_conv1x1_out_bwd: x / gx / w need 16-byte alignment and ld %% 4 == 0");
-        return TEM_EINVAL;
-    }
+    TEM_REQUIRE(tem_st2_ok(c.stx, c.sty) && x_ld % 4 == 0 && gx_ld % 4 == 0 && ((uintptr_t)x | (uintptr_t)gx | (uintptr_t)w) % 16 == 0,
+                "tem_conv1x1_out_bwd: x / gx / w need 16-byte alignment and ld %% 4 == 0");
+    tem_conv1x1_out_bwd(c, x, x_ld, g, g_ld, w, gx, gx_ld, dw, db, (float*)ws, NV, Cin, Cout, 1, (hipStream_t)stream);
     TEM_CHECK_LAUNCH("tem_conv1x1_out_bwd");
     return TEM_OK;
 }
@@ -920,53 +1048,14 @@ extern "C" int tem_conv1x1_out_bwd_st(const void* x, int64_t x_ld, const void* g
                                 Cout, stream);
 }
 
-extern "C" int tem_conv3d_wgrad_gmax_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
-                                        int use_mfma) {
-    return (use_mfma & 0xff) == TEM_ARITH_BF16X3 && tem_conv_wgrad_gmax_ok(N, D, H, W, Cin, Cout, kd, kh, kw);
-}
-
-// tem_conv3d_wgrad_sums_ok for a decoded call
-static int wgrad_sums_ok(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
-    if (use_mfma == TEM_ARITH_FP32)   // exact fp32: the layers k_conv_wgrad_tr<TEM_WG_FP32> takes (option fp32_zr: the data gradient that consumes the sums)
-        return tem_option(TEM_OPT_FP32_ZR) && !c.stx && !c.sty && tem_conv_wgrad_tr_fp32_ok(N, D, H, W, Cin, Cout, kd, kh, kw) &&
-               tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, c.x_cs);
-    if (!tem_arith_split_wgrad(use_mfma)) return 0;
-    return tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, c.x_cs);
-}
-
-// the argument checks of tem_conv3d_wgrad_gmax / _gscaled / _sums (also tem_conv3d_wgrad_ex with g_amax_out / g_amax_in / norm_sums)
-static int wgrad_gmax_check(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, const float* w, const float* db,
-                            const float* norm_sums) {
-    TEM_REQUIRE(c.g_amax_out, "tem_conv3d_wgrad_gmax: null g_amax");
-    TEM_REQUIRE(use_mfma == TEM_ARITH_BF16X3 && tem_conv_wgrad_gmax_ok(N, D, H, W, Cin, Cout, kd, kh, kw),
-                "tem_conv3d_wgrad_gmax: tem_conv3d_wgrad_gmax_ok() == 0 for this layer");
-    TEM_REQUIRE(!norm_sums || (w && db && wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma)),
-                "tem_conv3d_wgrad_gmax: norm_sums needs weights, a bias gradient and tem_conv3d_wgrad_sums_ok() != 0");
-    return TEM_OK;
-}
-static int wgrad_gscaled_check(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, const float* w, const float* db, const float* norm_sums) {
-    TEM_REQUIRE(c.g_amax_in, "tem_conv3d_wgrad_gscaled: null g_amax");
-    TEM_REQUIRE(tem_conv_wgrad_gscaled_ok(N, D, H, W, Cin, Cout, kd, kh, kw),
-                "tem_conv3d_wgrad_gscaled: tem_conv3d_wgrad_gscaled_ok() == 0 for this layer");
-    TEM_REQUIRE(!norm_sums || (w && db && wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, TEM_ARITH_F16X2)),
-                "tem_conv3d_wgrad_gscaled: norm_sums needs weights, a bias gradient and tem_conv3d_wgrad_sums_ok() != 0");
-    return TEM_OK;
-}
-static int wgrad_sums_check(const TemConvCall& c, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, const float* w, const float* db,
-                            const float* norm_sums) {
-    TEM_REQUIRE(w && norm_sums && db, "tem_conv3d_wgrad_sums: null pointer (weights, sums and bias gradient are required)");
-    TEM_REQUIRE(wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma), "tem_conv3d_wgrad_sums: tem_conv3d_wgrad_sums_ok() == 0 for this layer");
-    return TEM_OK;
-}
-
 extern "C" int tem_conv3d_wgrad_gmax(const float* x, int64_t x_ld, const float* scale, const float* shift,
                                      const float* g, int64_t g_ld, const float* w, const float* gamma,
                                      const float* beta, float* dw, float* db, float* norm_sums, unsigned* g_amax,
                                      void* ws, int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd,
                                      int kh, int kw, int use_mfma, tem_stream_t stream) {
     TemConvCall c = conv_call(use_mfma);
+    TEM_REQUIRE(g_amax, "tem_conv3d_wgrad_gmax: null g_amax");
     c.g_amax_out = g_amax;
-    TEM_TRY(wgrad_gmax_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, w, db, norm_sums));
     return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, 1,
                              norm_sums ? w : nullptr, gamma, beta, norm_sums, nullptr, 0, nullptr, stream);
 }
@@ -1005,22 +1094,14 @@ extern "C" int tem_absmax(const float* x, int64_t ld, int C, int64_t nvox, unsig
     return TEM_OK;
 }
 
-extern "C" int tem_conv3d_wgrad_gscaled_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
-    return tem_conv_wgrad_gscaled_ok(N, D, H, W, Cin, Cout, kd, kh, kw);
-}
-
-extern "C" int tem_conv3d_wgrad_cs_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int st, int64_t x_cs) {
-    return tem_conv_wgrad_cs_ok(N, D, H, W, Cin, Cout, kd, kh, kw, st, x_cs);
-}
-
 extern "C" int tem_conv3d_wgrad_gscaled(const float* x, int64_t x_ld, const float* scale, const float* shift,
                                         const float* g, int64_t g_ld, const float* w, const float* gamma,
                                         const float* beta, float* dw, float* db, float* norm_sums,
                                         const unsigned* g_amax, void* ws, int64_t ws_bytes, int N, int D, int H, int W,
                                         int Cin, int Cout, int kd, int kh, int kw, tem_stream_t stream) {
     TemConvCall c;
+    TEM_REQUIRE(g_amax, "tem_conv3d_wgrad_gscaled: null g_amax");
     c.g_amax_in = g_amax;
-    TEM_TRY(wgrad_gscaled_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, w, db, norm_sums));
     return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, TEM_ARITH_F16X2, 1,
                              norm_sums ? w : nullptr, gamma, beta, norm_sums, nullptr, 0, nullptr, stream);
 }
@@ -1073,19 +1154,13 @@ extern "C" int tem_conv3d_fwd_refnorm(const float* x, int64_t x_ld, const float*
                            use_mfma, nullptr, stream);
 }
 
-extern "C" int tem_conv3d_wgrad_sums_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
-                                        int use_mfma) {
-    const TemConvCall c = conv_call(use_mfma);
-    return wgrad_sums_ok(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma);
-}
-
 extern "C" int tem_conv3d_wgrad_sums(const float* x, int64_t x_ld, const float* scale, const float* shift,
                                      const float* g, int64_t g_ld, const float* w, const float* gamma,
                                      const float* beta, float* dw, float* db, float* norm_sums, void* ws,
                                      int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh,
                                      int kw, int use_mfma, tem_stream_t stream) {
     const TemConvCall c = conv_call(use_mfma);
-    TEM_TRY(wgrad_sums_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, w, db, norm_sums));
+    TEM_REQUIRE(w && norm_sums && db, "tem_conv3d_wgrad_sums: null pointer (weights, sums and bias gradient are required)");
     return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, 1,
                              w, gamma, beta, norm_sums, nullptr, 0, nullptr, stream);
 }
@@ -1144,13 +1219,8 @@ extern "C" int tem_conv3d_wgrad_ex(const float* x, int64_t x_ld, const float* sc
         TEM_REQUIRE(use_mfma == TEM_ARITH_F16X2, "tem_conv3d_wgrad_ex: g_amax_in (the fp16 2x1 arithmetic) takes use_mfma 8");
         c.stx = c.sty = TEM_ST_F32;   // as tem_conv3d_wgrad_gscaled: an fp32-tensor mode
         c.g_amax_in = g_amax_in;
-        TEM_TRY(wgrad_gscaled_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, w, db, norm_sums));
-    } else if (g_amax_out) {
-        c.g_amax_out = g_amax_out;
-        TEM_TRY(wgrad_gmax_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, w, db, norm_sums));
-    } else if (norm_sums) {
-        TEM_TRY(wgrad_sums_check(c, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, w, db, norm_sums));
     }
+    c.g_amax_out = g_amax_out;
     return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, 1,
                              norm_sums ? w : nullptr, gamma, beta, norm_sums, nullptr, 0, nullptr, stream);   // (w, gamma, beta: read for the sums only)
 }
@@ -1158,18 +1228,11 @@ extern "C" int tem_conv3d_wgrad_ex(const float* x, int64_t x_ld, const float* sc
 // tem_conv3d_wgrad of a FIRST layer (small Cin, VALU kernel) whose output gradient g is still the raw data gradient
 // behind the norm that follows this conv's ReLU: the norm backward (coefficients from tem_norm_bwd_coef) and the ReLU
 // mask are applied while g is loaded -- y (this conv's output, the norm's input) is read instead of a rewritten g.
-extern "C" int tem_conv3d_wgrad_gnorm_ok(int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
-    use_mfma &= 0xff;
-    const int cq = Cout / 4, key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
-    return use_mfma == TEM_ARITH_VALU && Cin >= 1 && Cin <= 4 && Cout % 4 == 0 && cq <= 16 && (cq & (cq - 1)) == 0 && (key == 7 || key == 3);
-}
-
 static int wgrad_gnorm_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
                             int64_t g_ld, const float* y, int64_t y_ld, const float* gcoef, float* dw, float* db, void* ws,
                             int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int sd_layout,
                             tem_stream_t stream) {
     TEM_REQUIRE(y && gcoef && y_ld >= Cout, "tem_conv3d_wgrad_gnorm: null pointer");
-    TEM_REQUIRE(tem_conv3d_wgrad_gnorm_ok(Cin, Cout, kd, kh, kw, TEM_ARITH_VALU), "tem_conv3d_wgrad_gnorm: tem_conv3d_wgrad_gnorm_ok() == 0");
     return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, TEM_ARITH_VALU,
                              sd_layout, nullptr, nullptr, nullptr, nullptr, y, y_ld, gcoef, stream);
 }

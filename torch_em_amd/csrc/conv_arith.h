@@ -20,7 +20,7 @@ enum TemWgradKind : int {
     TEM_WG_F16 = 1,      // one fp16 term
     TEM_WG_BF16 = 2,     // one bf16 term
     TEM_WG_F16X2 = 3,    // fp16 2x1: x^ two fp16 terms, g one fp16 term prescaled from TemConvCall::g_amax_in
-    TEM_WG_FP32 = 4,     // exact fp32 on k_conv_wgrad_tr where tem_conv_wgrad_tr_fp32_ok(), else on tem_conv_wgrad_mfma
+    TEM_WG_FP32 = 4,     // exact fp32 on k_conv_wgrad_tr where the plan (conv.hip: wgrad_plan) admits it, else on tem_conv_wgrad_mfma
     TEM_WG_NONE = -1,    // VALU kernels
 };
 constexpr int TEM_ST_NONE = -1;
@@ -59,7 +59,7 @@ constexpr bool tem_arith_mfma_fwd(int mode) { return tem_arith(mode).planes != 0
 constexpr bool tem_arith_split_fwd(int mode) { return tem_arith_mfma_fwd(mode) && tem_arith(mode).elem != TEM_EL_F32; }
 // the one-term mixed-precision modes, whose tensors may be stored in the operand type
 constexpr bool tem_arith_one_term(int mode) { return tem_arith(mode).st16 != TEM_ST_NONE; }
-// weight gradient on the split-precision launcher (tem_conv_wgrad_bf16x3) in the mode's own arithmetic
+// weight gradient on the split-precision launchers (tem_conv_wgrad_zs / _patch) in the mode's own arithmetic
 constexpr bool tem_arith_split_wgrad(int mode) { return tem_arith(mode).wgrad >= TEM_WG_BF16X3 && tem_arith(mode).wgrad <= TEM_WG_F16X2; }
 // (layout -> mode is the identity: tem_hip.h defines TEM_WL_* as the modes)
 constexpr bool tem_layout_is_split(int layout) { return tem_arith_split_fwd(layout); }

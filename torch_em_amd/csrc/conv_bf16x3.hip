@@ -1633,16 +1633,11 @@ __global__ __launch_bounds__(512, 2) void k_conv_wgrad_zt(const float* __restric
     }
 }
 
-struct ZsPlan {
-    bool use;
-    bool teams;   // k_conv_wgrad_zt (staging team) instead of k_conv_wgrad_zs
-    bool tr;      // k_conv_wgrad_tr (conv_wgrad_tr.hip: staging team + transposing LDS reads); same plan as `teams`
-    int nco, ks2, T, nY, nX, zsegs, S, Ss, ncz;
-};
-static ZsPlan zs_plan(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
+ZsPlan tem_zs_plan(const TemConvShape& sh) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout;
     ZsPlan p;
     const int enable = (int)tem_option(TEM_OPT_WGRAD_ZS);
-    p.use = enable && kd == 3 && kh == 3 && kw == 3 && D >= TEM_ZS_MIN_D;
+    p.use = enable && sh.key() == 7 && D >= TEM_ZS_MIN_D;
     const int ncot = Cout / 32;
     p.teams = enable >= 2;
     p.tr = enable >= 3;
@@ -1669,11 +1664,8 @@ static ZsPlan zs_plan(int N, int D, int H, int W, int Cin, int Cout, int kd, int
     return p;
 }
 
-struct WbPlan {
-    int nco, ks2, T, S, P, nZ, nY, nX, ptz;
-};
-
-static WbPlan wb_plan(int N, int D, int H, int W, int Cin, int Cout, int ntaps) {
+WbPlan tem_wb_plan(const TemConvShape& sh) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout, ntaps = sh.kd * sh.kh * sh.kw;
     WbPlan p;
     const int ncot = Cout / 32;
     p.nco = (ntaps == 1) ? (ncot >= 4 ? 4 : (ncot >= 2 ? 2 : 1)) : (ncot >= 2 ? 2 : 1);
@@ -1700,31 +1692,6 @@ static WbPlan wb_plan(int N, int D, int H, int W, int Cin, int Cout, int ntaps) 
     return p;
 }
 
-// Can this weight gradient also deliver the norm-backward sums (wgrad_sums.hip)?  z-sliding kernel, a few samples,
-// widths whose [27][Cout] tables fit a block's LDS
-int tem_conv_wgrad_sums_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int64_t x_cs) {
-    const int enable = (int)tem_option(TEM_OPT_WGRAD_SUMS);
-    if (!enable || Cin % 32 || Cout % 32) return 0;
-    const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
-    TEM_REQUIRE(!x_cs || z.use, "tem_conv3d_wgrad_ex: a chunk stride (x_cs) needs the z-sliding kernel (3x3x3, D >= 8)");
-    const int cq = Cout / 4;
-    // four small launches replace one pass over gz and x: only worth it where that pass is long (>= 128 MB tensors by default)
-    const int64_t min_bytes = (int64_t)tem_option(TEM_OPT_WGRAD_SUMS_MIN_MB) << 20;
-    const int64_t bytes = (int64_t)N * D * H * W * Cin * 4;
-    return z.use && N <= 4 && Cout <= 128 && Cin <= 256 && (cq & (cq - 1)) == 0 && H >= 3 && W >= 3 && D >= 3 &&
-           bytes >= min_bytes;
-}
-
-int64_t tem_conv_wgrad_bf16x3_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
-    const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
-    if (z.use)
-        return tem_align_up((int64_t)z.S * z.ks2 * 27 * Cin * Cout, 64) * 4 + tem_align_up((int64_t)z.S * Cout, 64) * 4 +
-               (tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, 0) ? tem_wgrad_sums_ws_floats(N, D, H, Cin, Cout) * 4 : 0) +
-               256;
-    WbPlan p = wb_plan(N, D, H, W, Cin, Cout, kd * kh * kw);
-    return tem_align_up((int64_t)p.S * p.ks2 * kd * kh * kw * Cin * Cout, 64) * 4 + (int64_t)p.S * Cout * 4 + 256;
-}
-
 template <int KD, int KH, int KW, int NCO, int KS2, int PTZ, typename T>
 static void launch_wb_tt(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g, int64_t g_ld,
                          float* part, float* dbpart, int N, int D, int H, int W, int Cin, int Cout, const WbPlan& p,
@@ -1732,12 +1699,7 @@ static void launch_wb_tt(const float* x, int64_t x_ld, const float* scale, const
     constexpr int ROWS = (PTZ + KD - 1) * (16 / PTZ + KH - 1);
     constexpr size_t ldsbytes = 2 * (size_t)32 * (ROWS * 32 + 16) + 2 * (size_t)32 * NCO * WB_GS;
     static_assert(ldsbytes <= 160 * 1024, "LDS budget");
-    static bool attr_done = false;
-    if (!attr_done) {
-        (void)hipFuncSetAttribute(reinterpret_cast<const void*>(&k_conv_wgrad_bf16x3<KD, KH, KW, NCO, KS2, PTZ, T>),
-                            hipFuncAttributeMaxDynamicSharedMemorySize, (int)ldsbytes);
-        attr_done = true;
-    }
+    tem_raise_dynamic_lds(&k_conv_wgrad_bf16x3<KD, KH, KW, NCO, KS2, PTZ, T>, ldsbytes);
     hipLaunchKernelGGL((k_conv_wgrad_bf16x3<KD, KH, KW, NCO, KS2, PTZ, T>), dim3((unsigned)(p.T * p.S)), dim3(256), ldsbytes, s,
                        reinterpret_cast<const T*>(x), x_ld, scale, shift, reinterpret_cast<const T*>(g), g_ld, part, dbpart, N, D, H, W,
                        Cin, Cout, p.T, p.S, p.P, p.nZ, p.nY, p.nX);
@@ -1762,137 +1724,58 @@ static void launch_wb(const TemConvCall& c, const float* x, int64_t x_ld, const 
     launch_wb_t<KD, KH, KW, NCO, KS2, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
 }
 
-int tem_conv_wgrad_gscaled_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
-    if (Cin % 32 || Cout % 32) return 0;   // (before the plan: it divides by Cin / 32)
-    const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
-    return z.use && (!z.teams || z.tr);
-}
-// exact-fp32 weight gradient on k_conv_wgrad_tr<4> (TEM_PRECISION=fp32): the layers the z-sliding plan takes, option wgrad_zs >= 3
-int tem_conv_wgrad_tr_fp32_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
-    if (Cin % 32 || Cout % 32) return 0;
-    const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
-    return z.use && z.tr;
-}
-// the chunk-stride conditions of the launch below (x_cs != 0), as a query
-int tem_conv_wgrad_cs_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int st, int64_t x_cs) {
-    if (Cin % 32 || Cout % 32) return 0;
-    const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
-    return z.use && z.tr && st != 0 && x_cs % 8 == 0;
-}
-int tem_conv_wgrad_gmax_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
-    return Cin % 32 == 0 && Cout % 32 == 0 && zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw).use;
+void tem_conv_wgrad_zs(const TemConvCall& c, const ZsPlan& z, int wg_kind, const float* x, int64_t x_ld, const float* scale,
+                       const float* shift, const float* g, int64_t g_ld, float* dw, float* db, float* zpart, float* zdb, float* extra,
+                       const TemConvShape& sh, int sd_layout, const float* w_sd, const float* gamma, const float* beta, float* norm_sums,
+                       hipStream_t s) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout;
+    const TemWgradKind kind = (TemWgradKind)wg_kind;
+    auto launch = [&](auto kern, size_t lb) {
+        tem_raise_dynamic_lds(kern, lb);
+        hipLaunchKernelGGL(kern, dim3((unsigned)((int64_t)z.T * z.S)), dim3(512), lb, s, x, x_ld, scale, shift, g, g_ld, zpart, zdb, N, D, H,
+                           W, Cin, Cout, z.T, z.nY, z.nX, z.zsegs, z.Ss, z.ncz, c.g_amax_out, c.g_amax_in);
+    };
+    // the kernel of this call's arithmetic out of a family's four (k_conv_wgrad_zt has no fp16 2x1 variant: the plan keeps that
+    // kind off it)
+    auto go = [&](auto bf16x3, auto f16, auto bf16, auto f16x2, size_t lb) {
+        if (kind == TEM_WG_F16) launch(f16, lb);
+        else if (kind == TEM_WG_BF16) launch(bf16, lb);
+        else if (kind == TEM_WG_F16X2) launch(f16x2, lb);
+        else launch(bf16x3, lb);
+    };
+    if (z.tr)
+        tem_conv_wgrad_tr_launch(c, kind, z, x, x_ld, scale, shift, g, g_ld, zpart, zdb, sh, s);
+    else if (z.teams)
+        go(&k_conv_wgrad_zt<TEM_WG_BF16X3>, &k_conv_wgrad_zt<TEM_WG_F16>, &k_conv_wgrad_zt<TEM_WG_BF16>, &k_conv_wgrad_zt<TEM_WG_BF16X3>,
+           2 * (size_t)32 * ZS_CIS + 4 * (size_t)32 * ZS_GS);
+    else if (z.nco == 2)
+        go(&k_conv_wgrad_zs<2, TEM_WG_BF16X3>, &k_conv_wgrad_zs<2, TEM_WG_F16>, &k_conv_wgrad_zs<2, TEM_WG_BF16>, &k_conv_wgrad_zs<2, TEM_WG_F16X2>,
+           2 * (size_t)32 * ZS_CIS + 4 * (size_t)64 * ZS_GS);
+    else
+        go(&k_conv_wgrad_zs<1, TEM_WG_BF16X3>, &k_conv_wgrad_zs<1, TEM_WG_F16>, &k_conv_wgrad_zs<1, TEM_WG_BF16>, &k_conv_wgrad_zs<1, TEM_WG_F16X2>,
+           2 * (size_t)32 * ZS_CIS + 4 * (size_t)32 * ZS_GS);
+    if (norm_sums)
+        tem_wgrad_sums_launch(c, zpart, z.Ss, z.ks2, zdb, g, g_ld, w_sd, gamma, beta, dw, extra, N, D, H, W, Cin, Cout, norm_sums, z.S, db, s);
+    else
+        tem_reduce_slabs_w_db(zpart, z.S * z.ks2, 27, Cin, Cout, (int64_t)27 * Cin * Cout, dw, sd_layout, zdb, z.S, db, s);
 }
 
-int tem_conv_wgrad_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
-                          int64_t g_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H, int W,
-                          int Cin, int Cout, int kd, int kh, int kw, int sd_layout, int wg_kind, const float* w_sd,
-                          const float* gamma, const float* beta, float* norm_sums, hipStream_t s) {
-    TEM_REQUIRE(Cin % 32 == 0 && Cout % 32 == 0, "tem_conv3d_wgrad(bf16x3): needs Cin%%32==0 and Cout%%32==0 (got %d,%d)",
-                Cin, Cout);
-    const int st = c.stx;
-    TEM_REQUIRE(st == c.sty, "tem_conv3d_wgrad(split-bf16): x and g must have the same storage type");
-    const TemWgradKind kind = (TemWgradKind)wg_kind;
-    TEM_REQUIRE(tem_wgrad_storage_ok(kind, st),
-                "tem_conv3d_wgrad(split-bf16): 16-bit storage goes with the one-term mode of the same type (fp16: use_mfma 5, "
-                "bf16: use_mfma 7), got storage %d", st);
-    TEM_REQUIRE(x_ld % (st ? 8 : 4) == 0 && g_ld % (st ? 8 : 4) == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)g % 16 == 0),
-                "tem_conv3d_wgrad(bf16x3): x / g must be 16-byte aligned with ld%%4==0 (16-bit storage: ld%%8==0)");
-    TEM_REQUIRE(!scale || (((uintptr_t)scale % 16 == 0) && ((uintptr_t)shift % 16 == 0)),
-                "tem_conv3d_wgrad(bf16x3): scale/shift must be 16-byte aligned");
-    const int ntaps = kd * kh * kw;
-    WbPlan p = wb_plan(N, D, H, W, Cin, Cout, ntaps);
-    if (ws_bytes < tem_conv_wgrad_bf16x3_ws(N, D, H, W, Cin, Cout, kd, kh, kw)) {
-        tem_set_error("tem_conv3d_wgrad(bf16x3): workspace too small");
-        return TEM_EWS;
-    }
-    const ZsPlan z = zs_plan(N, D, H, W, Cin, Cout, kd, kh, kw);
-    unsigned* const gmax = c.g_amax_out;   // tem_conv3d_wgrad_gmax
-    TEM_REQUIRE(!gmax || (z.use && kind == TEM_WG_BF16X3), "tem_conv3d_wgrad_gmax: tem_conv3d_wgrad_gmax_ok() == 0 for this layer");
-    const unsigned* const g_amax = c.g_amax_in;   // tem_conv3d_wgrad_gscaled (TEM_WG_F16X2 reads it)
-    TEM_REQUIRE(kind != TEM_WG_FP32 || (z.use && z.tr), "tem_conv3d_wgrad(fp32 on k_conv_wgrad_tr): tem_conv_wgrad_tr_fp32_ok() == 0 for this layer");
-    TEM_REQUIRE(kind != TEM_WG_F16X2 || (g_amax && z.use && (!z.teams || z.tr)),
-                "tem_conv3d_wgrad_gscaled: tem_conv3d_wgrad_gscaled_ok() == 0 for this layer (or no g_amax)");
-    if (z.use) {
-        TEM_REQUIRE((int64_t)H * W * (x_ld > g_ld ? x_ld : g_ld) * 4 < (1ll << 31),
-                    "tem_conv3d_wgrad(bf16x3): one z-plane of x / g must stay below 2 GiB (32-bit offsets inside a plane)");
-        float* zpart = (float*)ws;
-        float* zdb = db ? zpart + tem_align_up((int64_t)z.S * z.ks2 * 27 * Cin * Cout, 64) : nullptr;
-        TEM_REQUIRE(!norm_sums || (db && w_sd && sd_layout && tem_conv_wgrad_sums_ok(N, D, H, W, Cin, Cout, kd, kh, kw, c.x_cs)),
-                    "tem_conv3d_wgrad_sums: this layer cannot deliver the norm sums (tem_conv3d_wgrad_sums_ok() == 0)");
-        const unsigned nblk = (unsigned)((int64_t)z.T * z.S);
-        auto launch = [&](auto kern, size_t lb) {
-            static std::set<const void*> sized;   // kernels whose dynamic-LDS limit was raised already
-            const void* key = reinterpret_cast<const void*>(kern);
-            if (!sized.count(key)) {
-                (void)hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-                sized.insert(key);
-            }
-            hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lb, s, x, x_ld, scale, shift, g, g_ld, zpart, zdb, N, D, H, W, Cin,
-                               Cout, z.T, z.nY, z.nX, z.zsegs, z.Ss, z.ncz, gmax, g_amax);
-        };
-        // the kernel of this call's arithmetic out of a family's four (k_conv_wgrad_zt has no fp16 2x1 variant: the requirement above
-        // keeps that kind off it)
-        auto go = [&](auto bf16x3, auto f16, auto bf16, auto f16x2, size_t lb) {
-            if (kind == TEM_WG_F16) launch(f16, lb);
-            else if (kind == TEM_WG_BF16) launch(bf16, lb);
-            else if (kind == TEM_WG_F16X2) launch(f16x2, lb);
-            else launch(bf16x3, lb);
-        };
-        TEM_REQUIRE(!st || z.tr, "tem_conv3d_wgrad: 16-bit storage needs the transposing z-sliding kernel (option wgrad_zs = 3)");
-        TEM_REQUIRE(!c.x_cs || (st && z.tr && c.x_cs % 8 == 0),
-                    "tem_conv3d_wgrad_ex: a chunk stride (x_cs) needs 16-bit tensors on the transposing z-sliding kernel, x_cs %% 8 == 0");
-        if (z.tr)
-            tem_conv_wgrad_tr_launch(c, kind, nblk, x, x_ld, scale, shift, g, g_ld, zpart, zdb, N, D, H, W, Cin, Cout, z.T, z.nY, z.nX,
-                                     z.zsegs, z.Ss, z.ncz, s);
-        else if (z.teams)
-            go(&k_conv_wgrad_zt<TEM_WG_BF16X3>, &k_conv_wgrad_zt<TEM_WG_F16>, &k_conv_wgrad_zt<TEM_WG_BF16>, &k_conv_wgrad_zt<TEM_WG_BF16X3>,
-               2 * (size_t)32 * ZS_CIS + 4 * (size_t)32 * ZS_GS);
-        else if (z.nco == 2)
-            go(&k_conv_wgrad_zs<2, TEM_WG_BF16X3>, &k_conv_wgrad_zs<2, TEM_WG_F16>, &k_conv_wgrad_zs<2, TEM_WG_BF16>, &k_conv_wgrad_zs<2, TEM_WG_F16X2>,
-               2 * (size_t)32 * ZS_CIS + 4 * (size_t)64 * ZS_GS);
-        else
-            go(&k_conv_wgrad_zs<1, TEM_WG_BF16X3>, &k_conv_wgrad_zs<1, TEM_WG_F16>, &k_conv_wgrad_zs<1, TEM_WG_BF16>, &k_conv_wgrad_zs<1, TEM_WG_F16X2>,
-               2 * (size_t)32 * ZS_CIS + 4 * (size_t)32 * ZS_GS);
-        if (norm_sums) {
-            float* extra = zdb + tem_align_up((int64_t)z.S * Cout, 64);
-            tem_wgrad_sums_launch(c, zpart, z.Ss, z.ks2, zdb, g, g_ld, w_sd, gamma, beta, dw, extra, N, D, H, W, Cin, Cout,
-                                  norm_sums, z.S, db, s);
-        } else {
-            tem_reduce_slabs_w_db(zpart, z.S * z.ks2, 27, Cin, Cout, (int64_t)27 * Cin * Cout, dw, sd_layout, zdb, z.S, db, s);
-        }
-        return TEM_OK;
-    }
-    TEM_REQUIRE(!norm_sums, "tem_conv3d_wgrad_sums: this layer cannot deliver the norm sums (tem_conv3d_wgrad_sums_ok() == 0)");
-    float* part = (float*)ws;
-    float* dbpart = db ? part + tem_align_up((int64_t)p.S * p.ks2 * ntaps * Cin * Cout, 64) : nullptr;
-    const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
-#define WGO(KD, KH, KW)                                                                                              \
-    do {                                                                                                             \
-        if (p.nco == 4)                                                                                              \
-            launch_wb<KD, KH, KW, 4>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);     \
-        else if (p.nco == 2)                                                                                         \
-            launch_wb<KD, KH, KW, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);     \
-        else                                                                                                         \
-            launch_wb<KD, KH, KW, 1>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);     \
-    } while (0)
-    if (key == 7) {
-        if (p.nco == 2)
-            launch_wb<3, 3, 3, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
-        else
-            launch_wb<3, 3, 3, 1, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
-    } else if (key == 3) {
-        if (p.nco == 2)
-            launch_wb<1, 3, 3, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
-        else
-            launch_wb<1, 3, 3, 1, 2>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
-    } else if (key == 0) {
-        WGO(1, 1, 1);
-    } else {
-        tem_set_error("tem_conv3d_wgrad(bf16x3): kernel (%d,%d,%d) has no MFMA instantiation", kd, kh, kw);
-        return TEM_EINVAL;
+void tem_conv_wgrad_patch(const TemConvCall& c, const WbPlan& p, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                          const float* g, int64_t g_ld, float* dw, float* db, float* part, float* dbpart, const TemConvShape& sh,
+                          int sd_layout, hipStream_t s) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout, ntaps = sh.kd * sh.kh * sh.kw;
+#define WGO(KD, KH, KW, NCO, ...) launch_wb<KD, KH, KW, NCO, ##__VA_ARGS__>(c, x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s)
+    if (sh.key() == 7) {
+        if (p.nco == 2) WGO(3, 3, 3, 2);
+        else WGO(3, 3, 3, 1, 2);
+    } else if (sh.key() == 3) {
+        if (p.nco == 2) WGO(1, 3, 3, 2);
+        else WGO(1, 3, 3, 1, 2);
+    } else {   // 1x1x1
+        if (p.nco == 4) WGO(1, 1, 1, 4);
+        else if (p.nco == 2) WGO(1, 1, 1, 2);
+        else WGO(1, 1, 1, 1);
     }
 #undef WGO
-    const int64_t n = (int64_t)ntaps * Cin * Cout;
-    tem_reduce_slabs_w_db(part, p.S * p.ks2, ntaps, Cin, Cout, n, dw, sd_layout, dbpart, p.S, db, s);
-    return TEM_OK;
+    tem_reduce_slabs_w_db(part, p.S * p.ks2, ntaps, Cin, Cout, (int64_t)ntaps * Cin * Cout, dw, sd_layout, dbpart, p.S, db, s);
 }

@@ -1,8 +1,11 @@
 // conv_internal.h -- C++-internal interface between conv.hip (entry points, VALU kernels)
-// and conv_mfma.hip (v_mfma_f32_32x32x2_f32 implicit-GEMM kernels).
+// and the kernel files (conv_mfma.hip, conv_bf16x3.hip, conv_zr.hip, conv_pp.hip, conv_wgrad_tr.hip, conv_small.hip, ...).
+// Both dispatches are built the same way: ONE plan function in conv.hip (fwd_plan, wgrad_plan) decides which kernel a call takes,
+// with which geometry and workspace regions; the kernel files export geometry helpers the plan calls and launchers that execute it.
 #pragma once
 #include <hip/hip_runtime.h>
 #include <stdint.h>
+#include <set>
 #include "../../include/tem_hip.h"
 #include "tem_common.h"
 
@@ -83,31 +86,16 @@ int tem_conv_fwd_mfma(const TemPatchTiling& t, int ks, const float* x, int64_t x
                       const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
                       const TemConvShape& sh, int act, hipStream_t s);
 
-int64_t tem_conv_wgrad_mfma_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
-int tem_conv_wgrad_mfma(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
-                        int64_t g_ld, float* dw_tap_ci_co, float* db, void* ws, int64_t ws_bytes, int N, int D, int H,
-                        int W, int Cin, int Cout, int kd, int kh, int kw, int sd_layout, hipStream_t s);
-
 // conv_small.hip: HBM-bound special cases (return false when the shape is not covered)
 bool tem_conv_fwd_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
                        const float* bias, float* y, int64_t y_ld, const float* ref, int N, int D, int H, int W,
                        int Cin, int Cout, int kd, int kh, int kw, int act, float* stat, hipStream_t s);
 int64_t tem_conv_fwd_cin1_stat_blocks(int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
-int64_t tem_conv_wgrad_cin1_ws(int Cout, int ntaps);
-bool tem_conv_wgrad_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
-                         int64_t g_ld, float* dw, float* db, void* ws, int N, int D, int H, int W, int Cin, int Cout,
-                         int kd, int kh, int kw, int sd_layout, const float* gnx, int64_t gnx_ld, const float* gcoef,
-                         hipStream_t s);
 bool tem_conv_fwd_cout1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
                         const float* bias, float* y, int64_t y_ld, const float* ref, int N, int D, int H, int W,
                         int Cin, int Cout, int kd, int kh, int kw, int act, hipStream_t s);
 bool tem_conv1x1_proj(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* w, const float* bias, float* y,
                       int64_t y_ld, const float* ref, int64_t NV, int Cin, int Cout, int act, hipStream_t s);
-int64_t tem_conv1x1_proj_wgrad_ws(int Cin, int Cout);
-bool tem_conv1x1_proj_wgrad(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* g, int64_t g_ld, float* dw,
-                            float* db, void* ws, int64_t NV, int Cin, int Cout, int sd_layout, hipStream_t s);
-bool tem_conv1x1_out_bwd(const TemConvCall& c, const float* x, int64_t x_ld, const float* g, int64_t g_ld, const float* w, float* gx, int64_t gx_ld,
-                         float* dw, float* db, void* ws, int64_t NV, int Cin, int Cout, int sd_layout, hipStream_t s);
 bool tem_conv1x1_expand(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* w, const float* bias, float* y,
                         int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act,
                         hipStream_t s);
@@ -166,21 +154,76 @@ void tem_splitk_epilogue_bwd_sums(int sty, const float* part, int ksplit, int N,
 int64_t tem_splitk_stat_blocks(int64_t V, int Cout);
 void tem_splitk_epilogue_stats(int sty, const float* part, int ksplit, int N, int64_t V, int Cout, const float* bias, int act,
                                const float* ref, int64_t ref_ld, float* y, int64_t y_ld, float* stat, hipStream_t s);
-int64_t tem_conv_wgrad_bf16x3_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
-int tem_conv_wgrad_bf16x3(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
-                          int64_t g_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H, int W,
-                          int Cin, int Cout, int kd, int kh, int kw, int sd_layout, int wg_kind /* TemWgradKind */, const float* w_sd,
-                          const float* gamma, const float* beta, float* norm_sums, hipStream_t s);
-// largest |g| as a by-product of the z-sliding weight gradient (tem_conv3d_wgrad_gmax: TemConvCall::g_amax_out)
-int tem_conv_wgrad_gmax_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
-// wg_kind TEM_WG_F16X2 of tem_conv_wgrad_bf16x3 ("fp16 2x1": x^ two fp16 terms, g one fp16 term prescaled from TemConvCall::g_amax_in)
-int tem_conv_wgrad_gscaled_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
-int tem_conv_wgrad_cs_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int st, int64_t x_cs);
-int tem_conv_wgrad_tr_fp32_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);   // TEM_WG_FP32
-// conv_wgrad_tr.hip: z-sliding weight gradient with a staging team and transposing LDS reads (option wgrad_zs = 3)
-void tem_conv_wgrad_tr_launch(const TemConvCall& c, int wg_kind, unsigned nblk, const float* x, int64_t x_ld, const float* scale, const float* shift,
-                              const float* g, int64_t g_ld, float* zpart, float* zdb, int N, int D, int H, int W, int Cin,
-                              int Cout, int T, int nY, int nX, int zsegs, int Ss, int ncz, hipStream_t s);
+
+// ---- the weight-gradient dispatch: geometry helpers and shape predicates of the kernel files, plain functions of the shape that
+// the ONE plan function (conv.hip: wgrad_plan) calls, and the launchers that execute what it planned.  As in the forward, a
+// launcher decides and re-checks nothing: its caller holds a plan that names it, with the geometry and the workspace regions.
+// z-sliding kernels (conv_bf16x3.hip: k_conv_wgrad_zs<1|2>, k_conv_wgrad_zt; conv_wgrad_tr.hip: k_conv_wgrad_tr), 3x3x3 only.
+// Cin % 32 == 0 and Cout % 32 == 0 (this and the two patch plans divide by Cin / 32)
+struct ZsPlan {
+    bool use;     // option wgrad_zs, 3x3x3, D >= TEM_ZS_MIN_D
+    bool teams;   // k_conv_wgrad_zt (staging team) instead of k_conv_wgrad_zs
+    bool tr;      // k_conv_wgrad_tr (staging team + transposing LDS reads); same geometry as `teams`
+    int nco, ks2, T, nY, nX, zsegs, S, Ss, ncz;
+    int64_t part_floats(const TemConvShape& sh) const { return tem_align_up((int64_t)S * ks2 * 27 * sh.Cin * sh.Cout, 64); }   // slabs
+    int64_t db_floats(const TemConvShape& sh) const { return tem_align_up((int64_t)S * sh.Cout, 64); }   // bias partials behind them
+};
+ZsPlan tem_zs_plan(const TemConvShape& sh);
+// split-precision patch kernel (conv_bf16x3.hip: k_conv_wgrad_bf16x3), 3x3x3 / 1x3x3 / 1x1x1
+struct WbPlan {
+    int nco, ks2, T, S, P, nZ, nY, nX, ptz;
+};
+WbPlan tem_wb_plan(const TemConvShape& sh);
+// exact-fp32 patch kernel (conv_mfma.hip: k_conv_wgrad_mfma), the same kernel sizes
+struct WgradFp32Plan {
+    int nco, T, S, P, nZ, nY, nX;
+};
+WgradFp32Plan tem_wgrad_fp32_plan(const TemConvShape& sh);
+// conv_small.hip: the shapes its kernels take, and the bytes of their partial slabs
+bool tem_conv_wgrad_cin1_takes(const TemConvShape& sh);   // small-Cin first layer, 3x3x3 / 1x3x3
+int64_t tem_conv_wgrad_cin1_ws(int Cout, int ntaps);
+bool tem_conv1x1_proj_wgrad_takes(int Cin, int Cout);     // 1x1x1 projection to a few channels
+int64_t tem_conv1x1_proj_wgrad_ws(int Cin, int Cout);
+bool tem_conv1x1_out_bwd_takes(int Cin, int Cout);        // ... fused with its masked data gradient (same slabs)
+// wgrad_sums.hip: the z-sliding layers whose slab merge can also deliver the norm-backward sums (option wgrad_sums), and the
+// floats of its region behind the bias partials
+bool tem_wgrad_sums_takes(const TemConvShape& sh);
+int64_t tem_wgrad_sums_ws_floats(int N, int D, int H, int Cin, int Cout);
+
+// raise a kernel's dynamic-LDS limit to `bytes`, once per kernel
+template <typename K>
+inline void tem_raise_dynamic_lds(K kern, size_t bytes) {
+    static std::set<const void*> sized;
+    const void* key = reinterpret_cast<const void*>(kern);
+    if (sized.insert(key).second) (void)hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)bytes);
+}
+
+// The launchers.  part / dbpart (null: no bias gradient) / extra: the plan's workspace regions; each enqueues its kernel and the
+// merge of the partial slabs into dw / db.
+// z-sliding.  wg_kind: TemWgradKind (TEM_WG_F16X2 reads c.g_amax_in; c.g_amax_out, c.x_cs as the plan admitted them).
+// norm_sums (optional): the merge also delivers the norm-backward sums from w_sd / gamma / beta, through `extra`
+void tem_conv_wgrad_zs(const TemConvCall& c, const ZsPlan& z, int wg_kind, const float* x, int64_t x_ld, const float* scale,
+                       const float* shift, const float* g, int64_t g_ld, float* dw, float* db, float* part, float* dbpart, float* extra,
+                       const TemConvShape& sh, int sd_layout, const float* w_sd, const float* gamma, const float* beta, float* norm_sums,
+                       hipStream_t s);
+void tem_conv_wgrad_patch(const TemConvCall& c, const WbPlan& p, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                          const float* g, int64_t g_ld, float* dw, float* db, float* part, float* dbpart, const TemConvShape& sh,
+                          int sd_layout, hipStream_t s);
+void tem_conv_wgrad_mfma(const WgradFp32Plan& p, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
+                         int64_t g_ld, float* dw, float* db, float* part, float* dbpart, const TemConvShape& sh, int sd_layout,
+                         hipStream_t s);
+// conv_wgrad_tr.hip: the main kernel of tem_conv_wgrad_zs for z.tr
+void tem_conv_wgrad_tr_launch(const TemConvCall& c, int wg_kind, const ZsPlan& z, const float* x, int64_t x_ld, const float* scale,
+                              const float* shift, const float* g, int64_t g_ld, float* zpart, float* zdb, const TemConvShape& sh,
+                              hipStream_t s);
+// gnx / gcoef (optional): the norm backward and ReLU mask applied to g while it is loaded (tem_conv3d_wgrad_gnorm)
+void tem_conv_wgrad_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
+                         int64_t g_ld, float* dw, float* db, float* part, const TemConvShape& sh, int sd_layout, const float* gnx,
+                         int64_t gnx_ld, const float* gcoef, hipStream_t s);
+void tem_conv1x1_proj_wgrad(const TemConvCall& c, const float* x, int64_t x_ld, const float* g, int64_t g_ld, float* dw, float* db,
+                            float* part, int64_t NV, int Cin, int Cout, int sd_layout, hipStream_t s);
+void tem_conv1x1_out_bwd(const TemConvCall& c, const float* x, int64_t x_ld, const float* g, int64_t g_ld, const float* w, float* gx,
+                         int64_t gx_ld, float* dw, float* db, float* part, int64_t NV, int Cin, int Cout, int sd_layout, hipStream_t s);
 // TEM_BP_NORM_COEF of a call, as tem_wgrad_sums_launch reads it (delivered when the layer's group layout allows it)
 struct TemWgradCoefReq {
     int G;
@@ -188,9 +231,7 @@ struct TemWgradCoefReq {
     const float* rstd;
     float* coef;
 };
-// wgrad_sums.hip: norm-backward sums from the weight gradient
-int tem_conv_wgrad_sums_ok(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int64_t x_cs);   // x_cs: the call's chunk stride of x
-int64_t tem_wgrad_sums_ws_floats(int N, int D, int H, int Cin, int Cout);
+// wgrad_sums.hip: the z-sliding slab merge that also delivers the norm-backward sums
 void tem_wgrad_sums_launch(const TemConvCall& c, const float* zpart, int Ss, int ks2, const float* zdb, const float* g, int64_t g_ld,
                            const float* w, const float* gamma, const float* beta, float* dw, float* extra, int N, int D,
                            int H, int W, int Cin, int Cout, float* sums, int db_chunks, float* db, hipStream_t s);

@@ -1016,24 +1016,22 @@ __global__ __launch_bounds__(256, 2) void k_conv_wgrad_mfma(const float* __restr
     }
 }
 
-struct WgradPlan {
-    int nco, T, S, P, nZ, nY, nX;
-};
 
-static WgradPlan wgrad_plan(int N, int D, int H, int W, int Cin, int Cout, int ntaps) {
-    WgradPlan p;
+WgradFp32Plan tem_wgrad_fp32_plan(const TemConvShape& sh) {
+    const int ntaps = sh.kd * sh.kh * sh.kw;
+    WgradFp32Plan p;
     p.nco = ntaps == 27 ? 1 : (ntaps == 9 ? 3 : 4);
-    int ncot = Cout / 32;
+    int ncot = sh.Cout / 32;
     int ngroups = (ncot + p.nco - 1) / p.nco;
-    p.T = (Cin / 32) * ngroups;
-    p.nZ = (D + WG_TZ - 1) / WG_TZ;
-    p.nY = (H + WG_TY - 1) / WG_TY;
-    p.nX = (W + WG_TX - 1) / WG_TX;
-    int64_t P = (int64_t)N * p.nZ * p.nY * p.nX;
+    p.T = (sh.Cin / 32) * ngroups;
+    p.nZ = (sh.D + WG_TZ - 1) / WG_TZ;
+    p.nY = (sh.H + WG_TY - 1) / WG_TY;
+    p.nX = (sh.W + WG_TX - 1) / WG_TX;
+    int64_t P = (int64_t)sh.N * p.nZ * p.nY * p.nX;
     p.P = (int)P;
     int64_t S = (1024 + p.T - 1) / p.T;
     // keep the partial slab below 256 MiB
-    int64_t slab = (int64_t)ntaps * Cin * Cout * 4;
+    int64_t slab = (int64_t)ntaps * sh.Cin * sh.Cout * 4;
     int64_t cap = (256ll << 20) / slab;
     if (cap < 1) cap = 1;
     if (S > cap) S = cap;
@@ -1043,52 +1041,26 @@ static WgradPlan wgrad_plan(int N, int D, int H, int W, int Cin, int Cout, int n
     return p;
 }
 
-int64_t tem_conv_wgrad_mfma_ws(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw) {
-    WgradPlan p = wgrad_plan(N, D, H, W, Cin, Cout, kd * kh * kw);
-    return (int64_t)p.S * kd * kh * kw * Cin * Cout * 4 + (int64_t)p.S * Cout * 4 + 256;
-}
-
 template <int KD, int KH, int KW, int NCO>
 static void launch_wgrad(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
-                         int64_t g_ld, float* part, float* dbpart, int N, int D, int H, int W, int Cin, int Cout,
-                         const WgradPlan& p, hipStream_t s) {
+                         int64_t g_ld, float* part, float* dbpart, const TemConvShape& sh, const WgradFp32Plan& p, hipStream_t s) {
     constexpr int HV = (WG_TZ + KD - 1) * (WG_TY + KH - 1) * (WG_TX + KW - 1);
     constexpr int PV = WG_TZ * WG_TY * WG_TX;
     size_t ldsb = ((size_t)HV * 32 + (size_t)PV * 32 * NCO) * sizeof(float);
     hipLaunchKernelGGL((k_conv_wgrad_mfma<KD, KH, KW, NCO>), dim3((unsigned)(p.T * p.S)), dim3(256), ldsb, s, x, x_ld,
-                       scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p.T, p.S, p.P, p.nZ, p.nY, p.nX);
+                       scale, shift, g, g_ld, part, dbpart, sh.N, sh.D, sh.H, sh.W, sh.Cin, sh.Cout, p.T, p.S, p.P, p.nZ, p.nY, p.nX);
 }
 
-int tem_conv_wgrad_mfma(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
-                        int64_t g_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H, int W,
-                        int Cin, int Cout, int kd, int kh, int kw, int sd_layout, hipStream_t s) {
-    TEM_REQUIRE(Cin % 32 == 0 && Cout % 32 == 0, "tem_conv3d_wgrad(mfma): needs Cin%%32==0 and Cout%%32==0 (got %d,%d)",
-                Cin, Cout);
-    TEM_REQUIRE(x_ld % 4 == 0 && g_ld % 4 == 0 && ((uintptr_t)x % 16 == 0) && ((uintptr_t)g % 16 == 0),
-                "tem_conv3d_wgrad(mfma): x / g must be 16-byte aligned with ld%%4==0");
-    TEM_REQUIRE(!scale || (((uintptr_t)scale % 16 == 0) && ((uintptr_t)shift % 16 == 0)),
-                "tem_conv3d_wgrad(mfma): scale/shift must be 16-byte aligned");
-    const int ntaps = kd * kh * kw;
-    WgradPlan p = wgrad_plan(N, D, H, W, Cin, Cout, ntaps);
-    if (ws_bytes < tem_conv_wgrad_mfma_ws(N, D, H, W, Cin, Cout, kd, kh, kw)) {
-        tem_set_error("tem_conv3d_wgrad(mfma): workspace too small");
-        return TEM_EWS;
-    }
-    float* part = (float*)ws;
-    float* dbpart = db ? part + tem_align_up((int64_t)p.S * ntaps * Cin * Cout, 64) : nullptr;
-    const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
-    if (key == 7)
-        launch_wgrad<3, 3, 3, 1>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
-    else if (key == 3)
-        launch_wgrad<1, 3, 3, 3>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
-    else if (key == 0)
-        launch_wgrad<1, 1, 1, 4>(x, x_ld, scale, shift, g, g_ld, part, dbpart, N, D, H, W, Cin, Cout, p, s);
-    else {
-        tem_set_error("tem_conv3d_wgrad(mfma): kernel (%d,%d,%d) has no MFMA instantiation", kd, kh, kw);
-        return TEM_EINVAL;
-    }
-    const int64_t n = (int64_t)ntaps * Cin * Cout;
-    tem_reduce_slabs_w(part, p.S, ntaps, Cin, Cout, n, dw, sd_layout, s);
-    if (db) tem_reduce_slabs(dbpart, p.S, Cout, Cout, db, s);
-    return TEM_OK;
+void tem_conv_wgrad_mfma(const WgradFp32Plan& p, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
+                         int64_t g_ld, float* dw, float* db, float* part, float* dbpart, const TemConvShape& sh, int sd_layout,
+                         hipStream_t s) {
+    const int ntaps = sh.kd * sh.kh * sh.kw;
+    if (sh.key() == 7)
+        launch_wgrad<3, 3, 3, 1>(x, x_ld, scale, shift, g, g_ld, part, dbpart, sh, p, s);
+    else if (sh.key() == 3)
+        launch_wgrad<1, 3, 3, 3>(x, x_ld, scale, shift, g, g_ld, part, dbpart, sh, p, s);
+    else   // 1x1x1
+        launch_wgrad<1, 1, 1, 4>(x, x_ld, scale, shift, g, g_ld, part, dbpart, sh, p, s);
+    tem_reduce_slabs_w(part, p.S, ntaps, sh.Cin, sh.Cout, (int64_t)ntaps * sh.Cin * sh.Cout, dw, sd_layout, s);
+    if (db) tem_reduce_slabs(dbpart, p.S, sh.Cout, sh.Cout, db, s);
 }

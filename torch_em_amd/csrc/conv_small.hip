@@ -839,26 +839,25 @@ void tem_reduce_slabs_w(const float* part, int nchunks, int ntaps, int Cin, int 
 
 int64_t tem_conv_wgrad_cin1_ws(int Cout, int ntaps) { return (int64_t)CIN1_GRID * (ntaps + 1) * Cout * 4; }
 
-bool tem_conv_wgrad_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
-                         int64_t g_ld, float* dw, float* db, void* ws, int N, int D, int H, int W, int Cin, int Cout,
-                         int kd, int kh, int kw, int sd_layout, const float* gnx, int64_t gnx_ld, const float* gcoef,
-                         hipStream_t s) {
-    const int cq = Cout / 4;
-    if (gcoef && (gnx_ld % 4 || ((uintptr_t)gnx % 16) || ((uintptr_t)gcoef % 16))) return false;
-    // Cin 2..4: one pass per input channel (g is re-read Cin times: still ~6x faster than the generic kernel)
-    if (Cin > 4 || Cout % 4 || cq > 16 || (cq & (cq - 1)) || g_ld % 4 || ((uintptr_t)g % 16)) return false;
-    const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
-    if (key != 7 && key != 3) return false;
+// Cin 2..4: one pass per input channel (g is re-read Cin times: still ~6x faster than the generic kernel)
+bool tem_conv_wgrad_cin1_takes(const TemConvShape& sh) {
+    const int cq = sh.Cout / 4;
+    return sh.Cin >= 1 && sh.Cin <= 4 && sh.Cout % 4 == 0 && cq <= 16 && (cq & (cq - 1)) == 0 && (sh.key() == 7 || sh.key() == 3);
+}
+
+void tem_conv_wgrad_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
+                         int64_t g_ld, float* dw, float* db, float* part, const TemConvShape& sh, int sd_layout, const float* gnx,
+                         int64_t gnx_ld, const float* gcoef, hipStream_t s) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout, key = sh.key();
     const int nZ = (D + 3) / 4, nY = (H + 7) / 8, nX = (W + 7) / 8;
     const int64_t P64 = (int64_t)N * nZ * nY * nX;
     const int P = (int)P64;
     const int grid = P < CIN1_GRID ? P : CIN1_GRID;
-    const int NT = kd * kh * kw;
-    float* part = (float*)ws;
+    const int NT = sh.kd * sh.kh * sh.kw;
     for (int ci = 0; ci < Cin; ++ci) {
         const float* sc = scale ? scale + ci : nullptr;
         const float* sf = scale ? shift + ci : nullptr;
-        TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, return false, {
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, return, {
             if (key == 7) {
                 size_t ldsf = 6 * 10 * 12 > 4 * (NT + 1) * Cout ? 6 * 10 * 12 : 4 * (NT + 1) * Cout;
                 hipLaunchKernelGGL((k_conv_wgrad_cin1<3, 3, 3, TX, TG>), dim3(grid), dim3(256), ldsf * sizeof(float), s, (const TX*)x + ci,
@@ -880,7 +879,6 @@ bool tem_conv_wgrad_cin1(const TemConvCall& c, const float* x, int64_t x_ld, con
         }
         if (db && ci == 0 && Cin != 1) tem_reduce_slabs(part + (int64_t)NT * Cout, grid, Cout, (int64_t)(NT + 1) * Cout, db, s);
     }
-    return true;
 }
 
 // ---------------------------------------------------------------------------
@@ -1143,17 +1141,21 @@ __global__ __launch_bounds__(256) void k_conv1x1_proj_wgrad(const EX* __restrict
 #define PROJ_GRID 1024
 int64_t tem_conv1x1_proj_wgrad_ws(int Cin, int Cout) { return (int64_t)PROJ_GRID * (Cin + 1) * Cout * 4; }
 
-bool tem_conv1x1_proj_wgrad(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* g, int64_t g_ld, float* dw,
-                            float* db, void* ws, int64_t NV, int Cin, int Cout, int sd_layout, hipStream_t s) {
-    if (scale || Cin % 32 || Cin > 128 || x_ld % 4 || ((uintptr_t)x % 16)) return false;
+// (x without a pre-norm, in 16-byte rows: the plan's part)
+bool tem_conv1x1_proj_wgrad_takes(int Cin, int Cout) {
     const int njr = Cin / 32;
-    if (njr == 3 || njr * Cout > 32) return false;  // accumulators: NJ * 4 * COUT registers per lane
+    if (Cin % 32 || Cin > 128 || njr == 3 || njr * Cout > 32) return false;  // accumulators: NJ * 4 * COUT registers per lane
+    return (Cout >= 1 && Cout <= 4) || Cout == 6 || Cout == 8 || Cout == 12 || Cout == 16 || Cout == 24 || Cout == 32;   // the instantiations
+}
+
+void tem_conv1x1_proj_wgrad(const TemConvCall& c, const float* x, int64_t x_ld, const float* g, int64_t g_ld, float* dw, float* db,
+                            float* part, int64_t NV, int Cin, int Cout, int sd_layout, hipStream_t s) {
+    const int njr = Cin / 32;
     int64_t nb = tem_cdiv(NV, 32);
     const int grid = (int)(nb < PROJ_GRID ? nb : PROJ_GRID);
-    float* part = (float*)ws;
     size_t ldsb = (size_t)4 * (Cin + 1) * Cout * sizeof(float);
 #define PWJ(CO, J)                                                                                                \
-    TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, return false,                                            \
+    TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, return,                                                  \
                    hipLaunchKernelGGL((k_conv1x1_proj_wgrad<CO, J, false, TX, TG>), dim3(grid), dim3(256), ldsb, s, (const TX*)x, x_ld, \
                                       (const TG*)g, g_ld, part, NV, Cin))
 #define PW(CO)                                                                                                    \
@@ -1171,7 +1173,6 @@ bool tem_conv1x1_proj_wgrad(const TemConvCall& c, const float* x, int64_t x_ld, 
     case CO: PWJ(CO, 1); break;
     switch (Cout) {
         PW(1) PW(2) PW(3) PW(4) PW(6) PW(8) PW2(12) PW2(16) PW1(24) PW1(32)
-        default: return false;
     }
 #undef PW
 #undef PW2
@@ -1179,24 +1180,22 @@ bool tem_conv1x1_proj_wgrad(const TemConvCall& c, const float* x, int64_t x_ld, 
 #undef PWJ
     const int64_t slab = (int64_t)(Cin + 1) * Cout;
     tem_reduce_slabs_w_db(part, grid, 1, Cin, Cout, slab, dw, sd_layout, part + (int64_t)Cin * Cout, grid, db, s, slab);  // [tap=0][ci][co], db behind it
-    return true;
 }
 
 // out_conv backward in ONE pass over x: weight / bias gradient of the projection AND its masked data gradient
-// (w: state_dict layout [Cout][Cin]).  false: shape not covered (the caller runs the two separate kernels).
-bool tem_conv1x1_out_bwd(const TemConvCall& c, const float* x, int64_t x_ld, const float* g, int64_t g_ld, const float* w, float* gx, int64_t gx_ld,
-                         float* dw, float* db, void* ws, int64_t NV, int Cin, int Cout, int sd_layout, hipStream_t s) {
-    if (Cin % 32 || Cin > 64 || x_ld % 4 || ((uintptr_t)x % 16) || gx_ld % 4 || ((uintptr_t)gx % 16) || ((uintptr_t)w % 16)) return false;
+// (w: state_dict layout [Cout][Cin]).  The caller checked the shape (below), the storage pair and the 16-byte rows of x / gx / w.
+bool tem_conv1x1_out_bwd_takes(int Cin, int Cout) {   // wq registers: NJ * COUT * 4 per lane beside the accumulators
+    return Cin % 32 == 0 && Cin <= 64 && Cout >= 1 && Cout <= 4 && (Cin / 32) * Cout <= 8;
+}
+void tem_conv1x1_out_bwd(const TemConvCall& c, const float* x, int64_t x_ld, const float* g, int64_t g_ld, const float* w, float* gx,
+                         int64_t gx_ld, float* dw, float* db, float* part, int64_t NV, int Cin, int Cout, int sd_layout, hipStream_t s) {
     const int njr = Cin / 32;
-    if (Cout > 4 || njr * Cout > 8) return false;   // wq registers: NJ * COUT * 4 per lane beside the accumulators
     int64_t nb = tem_cdiv(NV, 32);
     const int grid = (int)(nb < PROJ_GRID ? nb : PROJ_GRID);
-    float* part = (float*)ws;
     size_t ldsb = (size_t)4 * (Cin + 1) * Cout * sizeof(float);
-    if (!tem_st2_ok(c.stx, c.sty)) return false;
     unsigned* const amax = c.take_output_amax();
 #define OBJ(CO, J)                                                                                                     \
-    TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, return false,                                                 \
+    TEM_ST2_SWITCH(c.stx, c.sty, TX, TG, return,                                                       \
                    hipLaunchKernelGGL((k_conv1x1_proj_wgrad<CO, J, true, TX, TG>), dim3(grid), dim3(256), ldsb, s, (const TX*)x, x_ld, \
                                       (const TG*)g, g_ld, part, NV, Cin, w, (TX*)gx, gx_ld, amax))
 #define OB(CO)                \
@@ -1206,13 +1205,11 @@ bool tem_conv1x1_out_bwd(const TemConvCall& c, const float* x, int64_t x_ld, con
         break;
     switch (Cout) {
         OB(1) OB(2) OB(3) OB(4)
-        default: return false;
     }
 #undef OB
 #undef OBJ
     const int64_t slab = (int64_t)(Cin + 1) * Cout;
     tem_reduce_slabs_w_db(part, grid, 1, Cin, Cout, slab, dw, sd_layout, part + (int64_t)Cin * Cout, grid, db, s, slab);
-    return true;
 }
 
 // ---------------------------------------------------------------------------

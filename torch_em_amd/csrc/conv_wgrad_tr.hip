@@ -742,33 +742,22 @@ __global__ __launch_bounds__(512, 1) void k_conv_wgrad_tr(const TS* __restrict__
 
 // wg_kind: TemWgradKind (TEM_WG_F16X2 needs c.g_amax_in).  Same arguments, partial-slab format and
 // plan (teams: one (Cin tile, Cout tile) pair per workgroup, KS2 = 1) as k_conv_wgrad_zt.
-void tem_conv_wgrad_tr_launch(const TemConvCall& c, int wg_kind, unsigned nblk, const float* x, int64_t x_ld, const float* scale, const float* shift,
-                              const float* g, int64_t g_ld, float* zpart, float* zdb, int N, int D, int H, int W, int Cin,
-                              int Cout, int T, int nY, int nX, int zsegs, int Ss, int ncz, hipStream_t s) {
-    unsigned* const gmax = c.g_amax_out;
-    const unsigned* const g_amax = c.g_amax_in;
+void tem_conv_wgrad_tr_launch(const TemConvCall& c, int wg_kind, const ZsPlan& z, const float* x, int64_t x_ld, const float* scale,
+                              const float* shift, const float* g, int64_t g_ld, float* zpart, float* zdb, const TemConvShape& sh,
+                              hipStream_t s) {
+    const dim3 grid((unsigned)((int64_t)z.T * z.S));
     auto launch = [&](auto kern, size_t lb) {
-        static std::set<const void*> sized;   // kernels whose dynamic-LDS limit was raised already
-        const void* key = reinterpret_cast<const void*>(kern);
-        if (!sized.count(key)) {
-            (void)hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-            sized.insert(key);
-        }
-        hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lb, s, x, x_ld, scale, shift, g, g_ld, zpart, zdb, N, D, H, W, Cin, Cout,
-                           T, nY, nX, zsegs, Ss, ncz, gmax, g_amax, (int64_t)0);
+        tem_raise_dynamic_lds(kern, lb);
+        hipLaunchKernelGGL(kern, grid, dim3(512), lb, s, x, x_ld, scale, shift, g, g_ld, zpart, zdb, sh.N, sh.D, sh.H, sh.W, sh.Cin, sh.Cout,
+                           z.T, z.nY, z.nX, z.zsegs, z.Ss, z.ncz, c.g_amax_out, c.g_amax_in, (int64_t)0);
     };
     constexpr size_t XT = TR_XT_OF(TR_REC16), GT = TR_GT_OF(TR_REC16);
-    auto launch16 = [&](auto kern, size_t lb, auto tag) {   // 16-bit x and g (the caller checked that the mode matches the type)
+    auto launch16 = [&](auto kern, size_t lb, auto tag) {   // 16-bit x and g (the plan checked that the mode matches the type)
         using TS = decltype(tag);
-        static std::set<const void*> sized;
-        const void* key = reinterpret_cast<const void*>(kern);
-        if (!sized.count(key)) {
-            (void)hipFuncSetAttribute(key, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lb);
-            sized.insert(key);
-        }
-        hipLaunchKernelGGL(kern, dim3(nblk), dim3(512), lb, s, reinterpret_cast<const TS*>(x), x_ld, scale, shift,
-                           reinterpret_cast<const TS*>(g), g_ld, zpart, zdb, N, D, H, W, Cin, Cout, T, nY, nX, zsegs, Ss, ncz, gmax, g_amax,
-                           c.x_cs);
+        tem_raise_dynamic_lds(kern, lb);
+        hipLaunchKernelGGL(kern, grid, dim3(512), lb, s, reinterpret_cast<const TS*>(x), x_ld, scale, shift,
+                           reinterpret_cast<const TS*>(g), g_ld, zpart, zdb, sh.N, sh.D, sh.H, sh.W, sh.Cin, sh.Cout, z.T, z.nY, z.nX, z.zsegs,
+                           z.Ss, z.ncz, c.g_amax_out, c.g_amax_in, c.x_cs);
     };
     if (c.stx == TEM_ST_F16) launch16(&k_conv_wgrad_tr<TEM_WG_F16, tem_f16>, XT + GT + 4096, tem_f16{});
     else if (c.stx == TEM_ST_BF16) launch16(&k_conv_wgrad_tr<TEM_WG_BF16, tem_bf16>, XT + GT + 4096, tem_bf16{});

@@ -401,6 +401,16 @@ __global__ __launch_bounds__(1024) void k_norm_sums_from_wgrad(const float* __re
     }
 }
 
+// Can a z-sliding weight gradient of this shape also deliver the norm-backward sums?  A few samples, widths whose [27][Cout]
+// tables fit a block's LDS
+bool tem_wgrad_sums_takes(const TemConvShape& sh) {
+    const int cq = sh.Cout / 4;
+    // four small launches replace one pass over gz and x: only worth it where that pass is long (>= 128 MB tensors by default)
+    const int64_t min_bytes = (int64_t)tem_option(TEM_OPT_WGRAD_SUMS_MIN_MB) << 20;
+    return tem_option(TEM_OPT_WGRAD_SUMS) && sh.N <= 4 && sh.Cout <= 128 && sh.Cin <= 256 && (cq & (cq - 1)) == 0 && sh.H >= 3 &&
+           sh.W >= 3 && sh.D >= 3 && sh.NV() * sh.Cin * 4 >= min_bytes;
+}
+
 // workspace (floats) behind the slab workspace: P [N][27*Cin*Cout/32] + planepart [N][D-2+2H][9][Cout]
 int64_t tem_wgrad_sums_ws_floats(int N, int D, int H, int Cin, int Cout) {
     return tem_align_up((int64_t)N * 27 * Cin * Cout / 32, 64) + (int64_t)N * (D - 2 + 2 * H) * 9 * Cout;
