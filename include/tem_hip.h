@@ -563,6 +563,16 @@ int tem_upsample_bwd_st(const void* gy, int64_t gy_ld, void* gx, int64_t gx_ld, 
                         tem_stream_t stream);
 int tem_upsample_stats_st(const void* u, int64_t u_ld, int N, int D, int H, int W, int C, int fz, int fy, int fx,
                           float* part, int st, tem_stream_t stream);
+/* Dispatch queries: the kernel tem_upsample_fwd_st / tem_upsample_bwd_st launch for exactly these pointers, leading
+ * dimensions, sizes and storage type, under the current options "upsample_generic" and "upsample2_ch8" (has_part: a
+ * statistics buffer is passed; u = NULL: without the fused norm backward).  They launch nothing and change no state.
+ *   0 the any-factor gather kernel, one channel per item     2 the factor-2 kernel, 4 channels per thread
+ *   1 the gather kernel, 4 channels per item                 3 the factor-2 kernel, 8 channels per thread (16-bit tensors)
+ *  -1 the launch refuses these arguments */
+int tem_upsample_fwd_path(const void* x, int64_t x_ld, const void* y, int64_t y_ld, int N, int D, int H, int W, int C,
+                          int fz, int fy, int fx, int has_part, int st);
+int tem_upsample_bwd_path(const void* gy, int64_t gy_ld, const void* gx, int64_t gx_ld, int N, int D, int H, int W, int C,
+                          int fz, int fy, int fx, const void* u, int64_t u_ld, int st);
 
 /* ---- Dice ------------------------------------------------------------------
  * dice_score / DiceLoss (loss/dice.py:34-133) and the masked variant

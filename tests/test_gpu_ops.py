@@ -1179,7 +1179,9 @@ def test_maxpool(C, f, shape):
                                         (12, (2, 2, 2), (1, 2, 1, 3)), (32, (1, 2, 2), (2, 3, 9, 6))])
 def test_upsample(C, f, shape, generic):
     """F.interpolate(trilinear) forward / adjoint (reference Upsampler3d, model/unet.py:455-458): the factor-2 kernels
-    (2x2x2 outputs per thread, separable) and, with option upsample_generic = 1, the any-factor gather kernels."""
+    (2x2x2 outputs per thread, separable) and, with option upsample_generic = 1, the any-factor gather kernels.
+    In the backward direction these shapes (at most 960 coarse pairs) reach only the gather kernel; k_upsample2_bwd and every
+    other dispatch path are held to float64 element by element in tests/test_gpu_upsample.py."""
     ops = _ops()
     from torch_em_amd import _lib
     _lib.set_option("upsample_generic", generic)

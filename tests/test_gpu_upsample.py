@@ -1,0 +1,326 @@
+"""GPU: every upsample kernel of csrc/pool_upsample.hip on every dispatch path, op by op through ops.upsample_fwd /
+ops.upsample_bwd / ops.upsample_stats (the `_st` entries), against the float64 references of oracle/upsample_ref.py (which
+tests/test_upsample_cpu.py pins to torch float64 interpolate and its autograd, and whose judge it tests on deliberately
+wrong outputs).
+
+Rule (that of tests/test_gpu_dice.py and tests/test_gpu_optim.py).  Errors are counted in units of 2^-23 times a per-element
+scale -- forward U|x|, adjoint U^T|g|, fused norm backward |a| U^T|g| + |m1| S + |m2r| (U^T U|u| + |mean| S), sum y: sum |y|,
+sum y^2: its own float64 value.  On the same inputs the test takes the worst figure e32 of the numpy float32 restatement
+(one rounding per operation, float32 weights as ATen computes them -- a reference, not the code under test; at factor 3,
+where 1 / f and the source index are rounded, the worse of its separately rounded and its fused evaluation of the source
+index: the compiler contracts lin_src's `scale * (o + 0.5) - 0.5` into one fma, which moves the weights' last-bit errors to
+other positions, oracle/upsample_ref.py: _src32; at factors 1 and 2 the weights are exact either way); EVERY element
+of a fp32 output must stay within MARGIN * max(e32, 1) units, MARGIN = 4 (oracle/dice_ref.py).  A 16-bit kernel computes in
+fp32 and rounds once on store: every stored element must lie in the closed interval [round16(ref - band), round16(ref + band)]
+of the same band (rounding is monotone, so this is exact).  The row statistics of a 16-bit launch describe the tensor as
+stored and are judged against the float64 sums of the stored values.
+
+Every case asserts and prints the kernel the library's own dispatch query (tem_upsample_fwd_path / _bwd_path) names for
+exactly the pointers, leading dimensions and options of the launch, so a case that drifts to another kernel fails even when
+a threshold moves.  Backward cases are the smallest shapes that reach each kernel (oracle/upsample_cases.py; the pair
+counts are asserted on the CPU), with odd coarse sizes: every axis has a pair without a second element.
+
+tem_upsample_stats sums per COARSE row of u (sum_x S u, sum_x u (U^T U u)): another partition of the totals than the
+per-fine-row-group sums of tem_upsample_fwd_stats.  Its rows are judged against that definition (u_row_stats_f64), and its
+totals over the rows against the totals of row_stats_f64(U u), at that quantity's scales.
+
+The 16-bit launches of b4 and b6 (the 8-channel instantiation) are also compared, bit for bit, with the rounded result of
+the fp32 launch (the 4-channel instantiation) on the same values: the contract tests/test_gpu_storage16.py states.
+
+No test provokes a device fault: the test lays every tensor out itself and asserts its extent against its buffer before a
+launch, unused channels of wide buffers hold NaN on input and keep their fill on output, every tensor sits between
+sentinels that must survive, and every launch is repeated and must return the same bits (there are no atomics).
+
+Observed on the MI355X (profiles/upsample_op_errors.txt): worst kernel error / max(e32, 1) = 2.49 (OBSERVED_WORST_RATIO
+below: the adjoint of the gather kernel, whose 64 taps form one fma chain; the factor-2 kernels stay at 1.00 and below), no
+16-bit element outside its interval, and the 16-bit launches of b4 and b6 equal the rounded fp32 launches in every bit.
+"""
+import ctypes
+
+import numpy as np
+import pytest
+import torch
+
+from conftest import rel_err
+from oracle import upsample_cases as K
+from oracle import upsample_ref as R
+
+pytestmark = pytest.mark.gpu
+DEV = "cuda:0"
+MARGIN = R.MARGIN
+OBSERVED_WORST_RATIO = 2.49       # informational (profiles/upsample_op_errors.txt); the assertions use MARGIN
+SENT = 12288.0                    # the sentinel around every tensor: a value fp16 and bf16 hold exactly
+PAD = 64                          # sentinel elements before and after (keeps the 16-byte alignment of the first element)
+TORCH = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
+ST = {"f32": 0, "f16": 1, "bf16": 2}
+BITS = {torch.float32: torch.int32, torch.float16: torch.int16, torch.bfloat16: torch.int16}
+
+
+def _lib():
+    from torch_em_amd import _lib
+    return _lib
+
+
+def _ops():
+    from torch_em_amd import ops
+    return ops
+
+
+@pytest.fixture
+def upsample_option():
+    """set dispatch options ("upsample2_ch8", "upsample_generic") for one test"""
+    lib, old = _lib(), {}
+
+    def set_option(name, value):
+        old.setdefault(name, lib.get_option(name))
+        lib.set_option(name, value)
+    yield set_option
+    for name, value in old.items():
+        lib.set_option(name, value)
+
+
+# ------------------------------------------------------------------------------------------ worst figures, for the record
+WORST = {}
+
+
+def _note(path, quantity, ek, e32):
+    ratio = ek / max(e32, 1.0)
+    cur = WORST.get((path, quantity))
+    if cur is None or ratio > cur[2]:
+        WORST[(path, quantity)] = (ek, e32, ratio)
+
+
+@pytest.fixture(scope="module", autouse=True)
+def _print_worst():
+    yield
+    print("\nUPSAMPLE_ERR_SUMMARY path / quantity: kernel, f32, ratio")
+    for (path, q), (ek, e32, ratio) in sorted(WORST.items()):
+        print(f"UPSAMPLE_ERR_SUMMARY {path:<26} {q:<16} {ek:7.2f} {e32:7.2f} {ratio:6.2f}")
+    if WORST:
+        print(f"UPSAMPLE_ERR_SUMMARY worst ratio {max(v[2] for v in WORST.values()):.2f}")
+
+
+# ------------------------------------------------------------------------------------------ tensors the test lays out itself
+class Laid:
+    """A logical channels-last [N, D, H, W, C] tensor as channels [lo, lo + C) of a Wd-channel buffer the test owns, PAD
+    sentinels before and after.  The other channels hold `other` (NaN for an input, the sentinel for an output); the
+    elements hold `data` (float32 values the storage type holds exactly) or NaN (an output: an element never written shows)."""
+
+    def __init__(self, shape, dtype, data=None, Wd=None, lo=0, other=float("nan")):
+        N, D, H, W, C = shape
+        Wd = Wd or C
+        self.shape, self.Wd, self.lo, self.other, self.C = tuple(shape), Wd, lo, other, C
+        self.vox = N * D * H * W
+        self.buf = torch.full((2 * PAD + self.vox * Wd,), SENT, dtype=dtype, device=DEV)
+        last = PAD + lo + (self.vox - 1) * Wd + C - 1
+        assert 0 <= lo and lo + C <= Wd and last < PAD + self.vox * Wd == self.buf.numel() - PAD, "the tensor leaves its buffer"
+        if Wd != C:
+            self._body().fill_(other)
+        if data is None:
+            self.view.fill_(float("nan"))
+        else:
+            assert tuple(data.shape) == self.shape and data.dtype == np.float32
+            src = torch.from_numpy(data).to(DEV)
+            self.view.copy_(src)
+            assert torch.equal(self.view.float(), src), "the storage type holds the inputs exactly"
+
+    def _body(self):
+        return self.buf[PAD:PAD + self.vox * self.Wd].view(self.vox, self.Wd)
+
+    @property
+    def view(self):
+        N, D, H, W, C = self.shape
+        Wd = self.Wd
+        return torch.as_strided(self.buf, self.shape, (D * H * W * Wd, H * W * Wd, W * Wd, Wd, 1), PAD + self.lo)
+
+    def ptr(self):
+        return ctypes.c_void_p(self.view.data_ptr())
+
+    def host(self):
+        return self.view.to(torch.float64).cpu().numpy()
+
+    def bits(self):
+        return self.view.contiguous().view(BITS[self.buf.dtype]).clone()
+
+    def intact(self):
+        """the sentinels before and after, and the channels that are not the tensor's, hold what they held"""
+        ok = bool((self.buf[:PAD] == SENT).all()) and bool((self.buf[-PAD:] == SENT).all())
+        if self.Wd != self.C:
+            b = self._body()
+            rest = torch.cat([b[:, :self.lo], b[:, self.lo + self.C:]], dim=1)
+            ok = ok and bool(torch.isnan(rest).all() if self.other != self.other else (rest == self.other).all())
+        return ok
+
+
+def _lay(shape, dtype, spec, data=None, output=False):
+    Wd, lo = spec if spec else (None, 0)
+    return Laid(shape, dtype, data, Wd, lo, other=SENT if output else float("nan"))
+
+
+def _judge(tag, path, quantity, dt, got, ref, scale, e32):
+    """every element: fp32 within MARGIN * max(e32, 1) units; 16-bit inside the rounded band's closed interval"""
+    assert np.isfinite(got).all(), f"{tag}: {int((~np.isfinite(got)).sum())} elements of {quantity} were never written or are not finite"
+    if dt == "f32":
+        ek = R.units(got, ref, scale)
+        print(f"UPSAMPLE_ERR {tag} -> {path} {quantity}: kernel {ek:.2f} f32 {e32:.2f}")
+        _note(path, quantity, ek, e32)
+        assert R.within(ek, e32), f"{tag}: {quantity} is {ek:.2f} units from float64, plain fp32 arithmetic {e32:.2f}"
+    else:
+        ek = R.excess16(got, ref, scale, dt)
+        bad = R.outside16(got, ref, scale, e32, dt)
+        print(f"UPSAMPLE_ERR {tag} -> {path} {quantity}: {bad} of {got.size} stored elements outside their interval; beyond the "
+              f"ideal rounding: kernel {ek:.2f} f32 {e32:.2f}")
+        _note(path, quantity, ek, e32)
+        assert bad == 0, f"{tag}: {bad} stored elements of {quantity} outside [round16(ref - band), round16(ref + band)]"
+
+
+# ------------------------------------------------------------------------------------------ backward
+def _bwd_cases():
+    out = []
+    for name, (f, shape, dtypes, want, layout, opts) in K.BWD.items():
+        for dt in dtypes:
+            for norm in (False, True):
+                out.append((name, dt, norm))
+    # cases of one (shape, factor, value grid) share their float64 reference: keep them together
+    out.sort(key=lambda c: (K.BWD[c[0]][1], K.BWD[c[0]][0], K.grid_of(c[1])))
+    return out
+
+
+BWD_CASES = _bwd_cases()
+
+
+def _bwd_layout(layout, which):
+    if layout and layout[0] in (which, "both"):
+        return layout[1], layout[2]
+    return None
+
+
+def _launch_bwd(name, dtype, shape, f, layout, d, norm):
+    """-> (path the query names, GX host float64, bits of GX); launches twice"""
+    lib, ops = _lib().load(), _ops()
+    N, D, H, W, C = shape
+    GY = _lay(K.fine(shape, f), dtype, _bwd_layout(layout, "gy"), d["g"])
+    GX = _lay(shape, dtype, _bwd_layout(layout, "gx"), None, output=True)
+    UU = _lay(shape, dtype, None, d["u"]) if norm else None
+    coef = torch.from_numpy(d["coef"]).to(DEV) if norm else None
+    assert GY.view.shape == K.fine(GX.view.shape, f)
+    path = lib.tem_upsample_bwd_path(GY.ptr(), GY.Wd, GX.ptr(), GX.Wd, N, D, H, W, C, f[0], f[1], f[2],
+                                     UU.ptr() if norm else None, UU.Wd if norm else 0, ST[_name(dtype)])
+    ops.upsample_bwd(GY.view, GX.view, f, norm=(UU.view, coef) if norm else None)
+    torch.cuda.synchronize()
+    first = GX.bits()
+    GX.view.fill_(float("nan"))
+    ops.upsample_bwd(GY.view, GX.view, f, norm=(UU.view, coef) if norm else None)
+    torch.cuda.synchronize()
+    assert torch.equal(first, GX.bits()), f"{name}: a repeated launch is bit-identical"
+    assert GX.intact(), f"{name}: wrote outside the elements of gx"
+    assert GY.intact() and torch.equal(GY.view.float(), torch.from_numpy(d["g"]).to(DEV)), f"{name}: gy is an input"
+    assert not norm or (UU.intact() and torch.equal(UU.view.float(), torch.from_numpy(d["u"]).to(DEV))), f"{name}: u is an input"
+    return path, GX.host(), first
+
+
+def _name(dtype):
+    return {v: k for k, v in TORCH.items()}[dtype]
+
+
+@pytest.mark.parametrize("name,dt,norm", BWD_CASES, ids=[f"{n}-{t}-{'norm' if m else 'plain'}" for n, t, m in BWD_CASES])
+def test_backward_against_float64(name, dt, norm, upsample_option):
+    f, shape, dtypes, want, layout, opts = K.BWD[name]
+    for key, value in opts.items():
+        upsample_option(key, value)
+    d = K.bwd_data(shape, f, K.grid_of(dt))
+    path, got, bits = _launch_bwd(name, TORCH[dt], shape, f, layout, d, norm)
+    tag = f"bwd {name} f={f} {shape} {dt} {'norm' if norm else 'plain'} pairs={K.pairs(shape, f)}"
+    print(f"UPSAMPLE_PATH {tag}: query {path} ({K.PATH_NAME.get(path)}), intended {want}")
+    assert path == want, f"{tag}: meant for {K.PATH_NAME[want]}, the query names {K.PATH_NAME.get(path, path)}"
+    q = "nrm" if norm else "adj"
+    _judge(tag, f"bwd {K.PATH_NAME[path]} {'f32' if dt == 'f32' else '16'}", "bwd_norm" if norm else "adjoint", dt, got,
+           d[q], d[q + "_scale"], d[q + "_e32"])
+    if name in ("b4", "b6"):
+        # the contract of tests/test_gpu_storage16.py between the 8-channel 16-bit instantiation and the fp32 4-channel one
+        p32, got32, _ = _launch_bwd(name + "/fp32", torch.float32, shape, f, layout, d, norm)
+        assert p32 == K.FACTOR2_CH4
+        rounded = torch.from_numpy(got32).to(TORCH[dt]).contiguous().view(torch.int16)
+        diff = int((rounded != bits.cpu()).sum())
+        print(f"UPSAMPLE_BITS {tag}: {diff} of {rounded.numel()} elements differ from the rounded fp32 launch")
+        assert diff == 0, f"{tag}: the 16-bit launch is not the rounded fp32 launch on the same values ({diff} elements)"
+
+
+# ------------------------------------------------------------------------------------------ forward and statistics
+FWD_CASES = [(name, dt) for name, c in K.FWD.items() for dt in c[2]]
+
+
+def _stats64(rows, V, eps=1e-5):
+    """mean and rstd per (sample, channel) from float64 row sums [N, R, C, 2]"""
+    s = rows.sum(axis=1)
+    mean = s[..., 0] / V
+    var = s[..., 1] / V - mean * mean
+    return mean, 1.0 / np.sqrt(var + eps)
+
+
+def _check_finalize(tag, part, rows64, V, C):
+    """both kinds of partials through tem_norm_finalize_partials, per channel, at the tolerance of tests/test_gpu_ops.py"""
+    ops = _ops()
+    N = part.shape[0]
+    mean, rstd, _, _ = ops.norm_stats_from_partials(part, N, V, C, C, None, None, 1e-5)
+    m64, r64 = _stats64(rows64, V)
+    em, er = rel_err(mean.cpu().numpy().reshape(N, C), m64), rel_err(rstd.cpu().numpy().reshape(N, C), r64)
+    print(f"UPSAMPLE_ERR {tag} finalize: mean rel_err {em:.2e} rstd rel_err {er:.2e}")
+    assert em < 2e-6 and er < 2e-6, (tag, em, er)
+
+
+@pytest.mark.parametrize("name,dt", FWD_CASES, ids=[f"{n}-{t}" for n, t in FWD_CASES])
+def test_forward_and_statistics_against_float64(name, dt):
+    lib, ops = _lib().load(), _ops()
+    f, shape, dtypes, want, want_stats, ylay = K.FWD[name]
+    N, D, H, W, C = shape
+    d = K.fwd_data(shape, f, K.grid_of(dt))
+    X = _lay(shape, TORCH[dt], None, d["x"])
+    Y = _lay(K.fine(shape, f), TORCH[dt], ylay, None, output=True)
+    stats_ok = bool(lib.tem_upsample_fwd_stats_ok(C, *f)) and ops._rows_vec4(X.view, X.Wd, Y.view, Y.Wd)
+    assert stats_ok == want_stats, f"{name}: the case table says stats={want_stats}"
+    path = lib.tem_upsample_fwd_path(X.ptr(), X.Wd, Y.ptr(), Y.Wd, N, D, H, W, C, f[0], f[1], f[2], int(stats_ok), ST[dt])
+    tag = f"fwd {name} f={f} {shape} {dt}"
+    print(f"UPSAMPLE_PATH {tag}: query {path} ({K.PATH_NAME.get(path)}), intended {want}")
+    assert path == want, f"{tag}: meant for {K.PATH_NAME[want]}, the query names {K.PATH_NAME.get(path, path)}"
+    part = ops.upsample_fwd(X.view, Y.view, f, stats=True)
+    torch.cuda.synchronize()
+    assert (part is not None) == want_stats
+    first, part1 = Y.bits(), None if part is None else part.clone()
+    Y.view.fill_(float("nan"))
+    again = ops.upsample_fwd(X.view, Y.view, f, stats=True)
+    torch.cuda.synchronize()
+    assert torch.equal(first, Y.bits()), f"{tag}: a repeated launch is bit-identical"
+    assert part is None or torch.equal(part1.view(torch.int32), again.view(torch.int32)), f"{tag}: ... and so are its row sums"
+    assert Y.intact(), f"{tag}: wrote outside the elements of y"
+    assert X.intact() and torch.equal(X.view.float(), torch.from_numpy(d["x"]).to(DEV)), f"{tag}: x is an input"
+    kernel = f"fwd {K.PATH_NAME[path]} {'f32' if dt == 'f32' else '16'}"
+    got = Y.host()
+    _judge(tag, kernel, "forward", dt, got, d["y"], d["y_scale"], d["y_e32"])
+    V = D * f[0] * H * f[1] * W * f[2]
+    if part is not None:
+        assert tuple(part.shape) == (N, D * H, C, 2)
+        pk = part.double().cpu().numpy()
+        if dt == "f32":
+            rows, scale, e32 = d["rows"], d["rows_scale"], d["rows_e32"]
+        else:                                               # the sums describe the tensor as stored
+            rows, scale = R.row_stats_f64(got, f), R.row_stats_scale(got, f)
+            r32 = R.row_stats_f32(got, f)
+            e32 = [R.units(r32[..., k], rows[..., k], scale[..., k]) for k in (0, 1)]
+        for k, q in enumerate(("sum y", "sum y^2")):
+            _judge(tag, kernel, q, "f32", pk[..., k], rows[..., k], scale[..., k], e32[k])
+    if name in K.U_STATS:
+        assert part is not None
+        _check_finalize(tag + " fwd partials", part, rows, V, C)
+        upart = ops.upsample_stats(X.view, f)
+        torch.cuda.synchronize()
+        assert torch.equal(upart.view(torch.int32), ops.upsample_stats(X.view, f).view(torch.int32)), "bit-identical when repeated"
+        uk = upart.double().cpu().numpy()
+        ukernel = f"stats {'f32' if dt == 'f32' else '16'}"
+        for k, q in enumerate(("sum y", "sum y^2")):        # per coarse row of u: the definition of tem_upsample_stats
+            _judge(tag, ukernel, "u " + q, "f32", uk[..., k], d["urows"][..., k], d["urows_scale"][..., k], d["urows_e32"][k])
+        tot, tot_scale = d["rows"].sum(axis=1), d["rows_scale"].sum(axis=1)
+        for k, q in enumerate(("sum y", "sum y^2")):        # the totals: those of the unrounded y = U u
+            e32 = R.units(d["urows_f32"].astype(np.float64).sum(axis=1)[..., k], tot[..., k], tot_scale[..., k])
+            _judge(tag, ukernel, "u total " + q, "f32", uk.sum(axis=1)[..., k], tot[..., k], tot_scale[..., k], e32)
+        _check_finalize(tag + " u partials", upart, d["rows"], V, C)

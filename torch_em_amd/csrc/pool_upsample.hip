@@ -1206,6 +1206,28 @@ extern "C" int tem_upsample_fwd_stats_ok(int C, int fz, int fy, int fx) {
     return upsample2_ok(C, fz, fy, fx) && cq <= 64 && (cq & (cq - 1)) == 0;
 }
 
+// The kernel a launch takes (what tem_upsample_fwd_path / tem_upsample_bwd_path return)
+enum { UPS_GATHER1 = 0, UPS_GATHER4 = 1, UPS_FACTOR2_CH4 = 2, UPS_FACTOR2_CH8 = 3 };
+
+static int upsample_fwd_select(const void* x, int64_t x_ld, const void* y, int64_t y_ld, int C, int fz, int fy, int fx, int st) {
+    // 16-bit tensors: 8 channels per thread (16-byte accesses) where the row partials keep their layout (C / 8 a power of two)
+    // (factor (1, 2, 2) only: with three coarse z-planes in registers the 8-channel variant needs 300 VGPRs)
+    if (fz == 1 && upsample2_ok(C, fz, fy, fx) && vec8_ok(C, {x, y}, {x_ld, y_ld}, st) && ((C / 8) & (C / 8 - 1)) == 0 && C / 8 <= 64)
+        return UPS_FACTOR2_CH8;
+    const bool v4 = vec4_ok(C, {x, y}, {x_ld, y_ld}, st);
+    if (upsample2_ok(C, fz, fy, fx) && v4) return UPS_FACTOR2_CH4;
+    return v4 ? UPS_GATHER4 : UPS_GATHER1;
+}
+
+// The query of upsample_fwd_impl: the kernel it launches for this layout (UPS_*), or -1 where it refuses the arguments.
+extern "C" int tem_upsample_fwd_path(const void* x, int64_t x_ld, const void* y, int64_t y_ld, int N, int D, int H, int W, int C,
+                                     int fz, int fy, int fx, int has_part, int st) {
+    if (!(x && y && N > 0 && C > 0 && x_ld >= C && y_ld >= C && D > 0 && H > 0 && W > 0 && fz > 0 && fy > 0 && fx > 0)) return -1;
+    if (st < 0 || st > 2 || (int64_t)N * D * fz * H * fy >= (1ll << 31)) return -1;
+    if (has_part && !(tem_upsample_fwd_stats_ok(C, fz, fy, fx) && vec4_ok(C, {x, y}, {x_ld, y_ld}, st))) return -1;
+    return upsample_fwd_select(x, x_ld, y, y_ld, C, fz, fy, fx, st);
+}
+
 static int upsample_fwd_impl(const void* x, int64_t x_ld, void* y, int64_t y_ld, int N, int D, int H, int W, int C, int fz,
                              int fy, int fx, float* part, int st, tem_stream_t stream) {
     TEM_REQUIRE(x && y && N > 0 && C > 0 && x_ld >= C && y_ld >= C && D > 0 && H > 0 && W > 0,
@@ -1218,9 +1240,8 @@ static int upsample_fwd_impl(const void* x, int64_t x_ld, void* y, int64_t y_ld,
     int64_t rows = (int64_t)N * D * fz * H * fy;
     TEM_REQUIRE(rows < (1ll << 31), "tem_upsample_fwd: too many rows");
     const size_t ldsb = part ? (size_t)4 * C * 2 * sizeof(float) : 0;
-    // 16-bit tensors: 8 channels per thread (16-byte accesses) where the row partials keep their layout (C / 8 a power of two)
-    // (factor (1, 2, 2) only: with three coarse z-planes in registers the 8-channel variant needs 300 VGPRs)
-    if (fz == 1 && upsample2_ok(C, fz, fy, fx) && vec8_ok(C, {x, y}, {x_ld, y_ld}, st) && ((C / 8) & (C / 8 - 1)) == 0 && C / 8 <= 64) {
+    const int path = upsample_fwd_select(x, x_ld, y, y_ld, C, fz, fy, fx, st);
+    if (path == UPS_FACTOR2_CH8) {
         const int64_t crow = (int64_t)N * D * H;
         TEM_ST16_SWITCH(st, T, {
             hipLaunchKernelGGL((k_upsample2_fwd<1, T, 8>), dim3((unsigned)crow), dim3(256), ldsb, (hipStream_t)stream, (const T*)x,
@@ -1232,7 +1253,7 @@ static int upsample_fwd_impl(const void* x, int64_t x_ld, void* y, int64_t y_ld,
     TEM_ST_SWITCH(st, T, {
         const T* xs = (const T*)x;
         T* ys = (T*)y;
-        if (upsample2_ok(C, fz, fy, fx) && v4) {
+        if (path == UPS_FACTOR2_CH4) {
             const int64_t crow = (int64_t)N * D * H;
             if (fz == 2)
                 hipLaunchKernelGGL((k_upsample2_fwd<2, T>), dim3((unsigned)crow), dim3(256), ldsb, (hipStream_t)stream, xs, x_ld, ys,
@@ -1240,7 +1261,7 @@ static int upsample_fwd_impl(const void* x, int64_t x_ld, void* y, int64_t y_ld,
             else
                 hipLaunchKernelGGL((k_upsample2_fwd<1, T>), dim3((unsigned)crow), dim3(256), ldsb, (hipStream_t)stream, xs, x_ld, ys,
                                    y_ld, D, H, W, C, part);
-        } else if (v4)
+        } else if (path == UPS_GATHER4)
             hipLaunchKernelGGL((k_upsample_fwd<4, T>), dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, xs, x_ld, ys,
                                y_ld, D, H, W, C, fz, fy, fx);
         else
@@ -1268,6 +1289,25 @@ extern "C" int tem_upsample_fwd_st(const void* x, int64_t x_ld, void* y, int64_t
     return upsample_fwd_impl(x, x_ld, y, y_ld, N, D, H, W, C, fz, fy, fx, part, st, stream);
 }
 
+static int upsample_bwd_select(const void* gy, int64_t gy_ld, const void* gx, int64_t gx_ld, int N, int D, int H, int W, int C,
+                               int fz, int fy, int fx, const void* u, int64_t u_ld, int st) {
+    // the 2x2x2-per-thread kernel has 1/8 of the gather kernel's threads: it needs a volume that still fills the chip
+    const int64_t pairs = (int64_t)N * ((D + fz - 1) / fz) * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
+    if (upsample2_ok(C, fz, fy, fx) && pairs >= 2 * 65536 && vec8_ok(C, {gy, gx, u}, {gy_ld, gx_ld, u ? u_ld : 0}, st) && tem_option(TEM_OPT_UPSAMPLE2_CH8))
+        return UPS_FACTOR2_CH8;
+    if (upsample2_ok(C, fz, fy, fx) && pairs >= 65536 && vec4_ok(C, {gy, gx, u}, {gy_ld, gx_ld, u_ld}, st)) return UPS_FACTOR2_CH4;
+    return vec4_ok(C, {gy, gx, u}, {gy_ld, gx_ld, u ? u_ld : 0}, st) ? UPS_GATHER4 : UPS_GATHER1;
+}
+
+// The query of upsample_bwd_impl (u = NULL: without the fused norm backward): UPS_*, or -1 where it refuses the arguments.
+extern "C" int tem_upsample_bwd_path(const void* gy, int64_t gy_ld, const void* gx, int64_t gx_ld, int N, int D, int H, int W, int C,
+                                     int fz, int fy, int fx, const void* u, int64_t u_ld, int st) {
+    if (!(gy && gx && N > 0 && C > 0 && gy_ld >= C && gx_ld >= C && D > 0 && H > 0 && W > 0 && fz > 0 && fy > 0 && fx > 0)) return -1;
+    if (st < 0 || st > 2 || (int64_t)N * D * H >= (1ll << 31)) return -1;
+    if (u && !(u_ld >= C && (C % 4 || (u_ld % 4 == 0 && (uintptr_t)u % tem_st_align4(st) == 0)))) return -1;
+    return upsample_bwd_select(gy, gy_ld, gx, gx_ld, N, D, H, W, C, fz, fy, fx, u, u_ld, st);
+}
+
 static int upsample_bwd_impl(const void* gy, int64_t gy_ld, void* gx, int64_t gx_ld, int N, int D, int H, int W,
                              int C, int fz, int fy, int fx, const void* u, int64_t u_ld, const float* ncoef,
                              int64_t ncoef_ld, int st, tem_stream_t stream) {
@@ -1277,9 +1317,8 @@ static int upsample_bwd_impl(const void* gy, int64_t gy_ld, void* gx, int64_t gx
     TEM_REQUIRE(fz > 0 && fy > 0 && fx > 0, "tem_upsample_bwd: bad factors");
     int64_t rows = (int64_t)N * D * H;
     TEM_REQUIRE(rows < (1ll << 31), "tem_upsample_bwd: too many rows");
-    // the 2x2x2-per-thread kernel has 1/8 of the gather kernel's threads: it needs a volume that still fills the chip
-    const int64_t pairs = (int64_t)N * ((D + fz - 1) / fz) * ((H + 1) / 2) * ((W + 1) / 2) * (C / 4);
-    if (upsample2_ok(C, fz, fy, fx) && pairs >= 2 * 65536 && vec8_ok(C, {gy, gx, u}, {gy_ld, gx_ld, u ? u_ld : 0}, st) && tem_option(TEM_OPT_UPSAMPLE2_CH8)) {
+    const int path = upsample_bwd_select(gy, gy_ld, gx, gx_ld, N, D, H, W, C, fz, fy, fx, u, u_ld, st);
+    if (path == UPS_FACTOR2_CH8) {
         TEM_ST16_SWITCH(st, T, {
             if (fz == 2) {
                 const int64_t prow = (int64_t)N * ((D + 1) / 2) * ((H + 1) / 2);
@@ -1298,7 +1337,7 @@ static int upsample_bwd_impl(const void* gy, int64_t gy_ld, void* gx, int64_t gx
         const T* gys = (const T*)gy;
         const T* us = (const T*)u;
         T* gxs = (T*)gx;
-        if (upsample2_ok(C, fz, fy, fx) && pairs >= 65536 && vec4_ok(C, {gy, gx, u}, {gy_ld, gx_ld, u_ld}, st)) {
+        if (path == UPS_FACTOR2_CH4) {
             if (fz == 2) {
                 const int64_t prow = (int64_t)N * ((D + 1) / 2) * ((H + 1) / 2);
                 hipLaunchKernelGGL((k_upsample2_bwd<2, T>), dim3((unsigned)prow), dim3(256), 0, (hipStream_t)stream, gys, gy_ld, gxs,
@@ -1308,7 +1347,7 @@ static int upsample_bwd_impl(const void* gy, int64_t gy_ld, void* gx, int64_t gx
                 hipLaunchKernelGGL((k_upsample2_bwd<1, T>), dim3((unsigned)prow), dim3(256), 0, (hipStream_t)stream, gys, gy_ld, gxs,
                                    gx_ld, D, H, W, C, us, u_ld, ncoef, ncoef_ld);
             }
-        } else if (vec4_ok(C, {gy, gx, u}, {gy_ld, gx_ld, u ? u_ld : 0}, st))
+        } else if (path == UPS_GATHER4)
             hipLaunchKernelGGL((k_upsample_bwd<4, T>), dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, gys, gy_ld, gxs,
                                gx_ld, D, H, W, C, fz, fy, fx, us, u_ld, ncoef, ncoef_ld);
         else
