@@ -487,6 +487,16 @@ int tem_norm_bwd_st(const void* gy, int64_t gy_ld, const void* x, int64_t x_ld, 
                     const float* gamma, const float* mean, const float* rstd, int relu_mask, void* gx, int64_t gx_ld,
                     float* dgamma, float* dbeta, const float* part, int64_t part_nblk, float* coef_out,
                     unsigned* out_amax, void* ws, int64_t ws_bytes, int st, tem_stream_t stream);
+/* Dispatch queries of the two passes over the tensors; they launch nothing, change no state, and return -1 where the launch
+ * would refuse the arguments (else 0).  The launches call the selector functions these print.
+ *   tem_norm_reduce_geom : the reduction pass of tem_norm_stats_st (gy = NULL) or tem_norm_bwd_st (gy given):
+ *                          out[5] = {vec (4 | 1 elements per thread), rows (voxels a block reads at once), threads,
+ *                          nblk (blocks = partial rows per sample, at most 512), vper (voxels per block)}
+ *   tem_norm_apply_geom  : the elementwise pass of tem_norm_bwd_st: out[4] = {vec, threads, grid_x (blocks per sample; the
+ *                          kernel grid-strides), fast (1 = a thread keeps its four channels: grid stride % (C / 4) == 0)} */
+int tem_norm_reduce_geom(const void* x, int64_t x_ld, const void* gy, int64_t gy_ld, int64_t V, int C, int st, int64_t* out);
+int tem_norm_apply_geom(const void* gy, int64_t gy_ld, const void* x, int64_t x_ld, const void* gx, int64_t gx_ld, int N,
+                        int64_t V, int C, int has_amax, int st, int64_t* out);
 
 
 /* ---- pooling / upsampling ------------------------------------------------

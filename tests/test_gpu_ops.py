@@ -1120,6 +1120,9 @@ def test_conv_relu_mask_ref_and_channel_slices():
                                                (32, 32, False, (2, 8, 8, 8)), (64, 32, True, (2, 4, 8, 8)),
                                                (6, 3, True, (1, 3, 5, 7)), (512, 512, False, (1, 2, 2, 2))])
 def test_norm_stats_and_backward(C, G, affine, shape):
+    """A whole-tensor comparison with torch float32 on six small shapes (one reduction block, one trip of the apply).  The
+    kernels' dispatch paths -- the multi-block partition, the grid-stride apply, out_amax, the finalize stages on many rows --
+    are judged element by element against float64 in tests/test_gpu_norm.py."""
     ops = _ops()
     N, D, H, W = shape
     g = torch.Generator().manual_seed(C + G)

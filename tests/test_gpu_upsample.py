@@ -35,8 +35,6 @@ Observed on the MI355X (profiles/upsample_op_errors.txt): worst kernel error / m
 below: the adjoint of the gather kernel, whose 64 taps form one fma chain; the factor-2 kernels stay at 1.00 and below), no
 16-bit element outside its interval, and the 16-bit launches of b4 and b6 equal the rounded fp32 launches in every bit.
 """
-import ctypes
-
 import numpy as np
 import pytest
 import torch
@@ -44,16 +42,11 @@ import torch
 from conftest import rel_err
 from oracle import upsample_cases as K
 from oracle import upsample_ref as R
+from oracle.gpu_layout import BITS, DEV, PAD, SENT, ST, TORCH, Laid  # noqa: F401  (shared with tests/test_gpu_norm.py)
 
 pytestmark = pytest.mark.gpu
-DEV = "cuda:0"
 MARGIN = R.MARGIN
 OBSERVED_WORST_RATIO = 2.49       # informational (profiles/upsample_op_errors.txt); the assertions use MARGIN
-SENT = 12288.0                    # the sentinel around every tensor: a value fp16 and bf16 hold exactly
-PAD = 64                          # sentinel elements before and after (keeps the 16-byte alignment of the first element)
-TORCH = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
-ST = {"f32": 0, "f16": 1, "bf16": 2}
-BITS = {torch.float32: torch.int32, torch.float16: torch.int16, torch.bfloat16: torch.int16}
 
 
 def _lib():
@@ -98,58 +91,6 @@ def _print_worst():
         print(f"UPSAMPLE_ERR_SUMMARY {path:<26} {q:<16} {ek:7.2f} {e32:7.2f} {ratio:6.2f}")
     if WORST:
         print(f"UPSAMPLE_ERR_SUMMARY worst ratio {max(v[2] for v in WORST.values()):.2f}")
-
-
-# ------------------------------------------------------------------------------------------ tensors the test lays out itself
-class Laid:
-    """A logical channels-last [N, D, H, W, C] tensor as channels [lo, lo + C) of a Wd-channel buffer the test owns, PAD
-    sentinels before and after.  The other channels hold `other` (NaN for an input, the sentinel for an output); the
-    elements hold `data` (float32 values the storage type holds exactly) or NaN (an output: an element never written shows)."""
-
-    def __init__(self, shape, dtype, data=None, Wd=None, lo=0, other=float("nan")):
-        N, D, H, W, C = shape
-        Wd = Wd or C
-        self.shape, self.Wd, self.lo, self.other, self.C = tuple(shape), Wd, lo, other, C
-        self.vox = N * D * H * W
-        self.buf = torch.full((2 * PAD + self.vox * Wd,), SENT, dtype=dtype, device=DEV)
-        last = PAD + lo + (self.vox - 1) * Wd + C - 1
-        assert 0 <= lo and lo + C <= Wd and last < PAD + self.vox * Wd == self.buf.numel() - PAD, "the tensor leaves its buffer"
-        if Wd != C:
-            self._body().fill_(other)
-        if data is None:
-            self.view.fill_(float("nan"))
-        else:
-            assert tuple(data.shape) == self.shape and data.dtype == np.float32
-            src = torch.from_numpy(data).to(DEV)
-            self.view.copy_(src)
-            assert torch.equal(self.view.float(), src), "the storage type holds the inputs exactly"
-
-    def _body(self):
-        return self.buf[PAD:PAD + self.vox * self.Wd].view(self.vox, self.Wd)
-
-    @property
-    def view(self):
-        N, D, H, W, C = self.shape
-        Wd = self.Wd
-        return torch.as_strided(self.buf, self.shape, (D * H * W * Wd, H * W * Wd, W * Wd, Wd, 1), PAD + self.lo)
-
-    def ptr(self):
-        return ctypes.c_void_p(self.view.data_ptr())
-
-    def host(self):
-        return self.view.to(torch.float64).cpu().numpy()
-
-    def bits(self):
-        return self.view.contiguous().view(BITS[self.buf.dtype]).clone()
-
-    def intact(self):
-        """the sentinels before and after, and the channels that are not the tensor's, hold what they held"""
-        ok = bool((self.buf[:PAD] == SENT).all()) and bool((self.buf[-PAD:] == SENT).all())
-        if self.Wd != self.C:
-            b = self._body()
-            rest = torch.cat([b[:, :self.lo], b[:, self.lo + self.C:]], dim=1)
-            ok = ok and bool(torch.isnan(rest).all() if self.other != self.other else (rest == self.other).all())
-        return ok
 
 
 def _lay(shape, dtype, spec, data=None, output=False):

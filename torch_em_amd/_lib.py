@@ -193,6 +193,9 @@ SIGNATURES = {
                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "tem_norm_bwd_st": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_i64,
                                 c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
+    # dispatch queries (launch nothing): out int64[5] = vec, rows, threads, nblk, vper / int64[4] = vec, threads, grid_x, fast; -1 refused
+    "tem_norm_reduce_geom": (c_int, [c_vp, c_i64, c_vp, c_i64, c_i64, c_int, c_int, ctypes.POINTER(c_i64)]),
+    "tem_norm_apply_geom": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_int, ctypes.POINTER(c_i64)]),
     "tem_conv3d_wgrad_gnorm_st": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_i64]
                                   + [c_int] * 12 + [c_vp]),
     "tem_conv1x1_out_bwd_st": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_i64, c_int, c_int,

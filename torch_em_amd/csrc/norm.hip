@@ -36,6 +36,58 @@ static NormGeom norm_geom(const void* p0, const void* p1, int64_t ld0, int64_t l
     return g;
 }
 
+// The geometry of the elementwise backward pass (k_norm_bwd_apply): what norm_bwd_impl launches and tem_norm_apply_geom prints
+struct NormApplyGeom {
+    int vec;      // 4 or 1 elements per thread item
+    int threads;  // 1024 with out_amax (one atomic per block), else 256
+    int grid_x;   // blocks per sample; the kernel grid-strides the rest
+    int fast;     // 1 = the grid stride is a multiple of C / 4: the kernel's `dq == 0` branch (vec 4 only)
+};
+
+static NormApplyGeom norm_apply_geom(const void* gy, int64_t gy_ld, const void* x, int64_t x_ld, const void* gx, int64_t gx_ld,
+                                     int N, int64_t V, int C, bool has_amax, int st) {
+    NormApplyGeom a;
+    const uintptr_t a4 = tem_st_align4(st);
+    const bool v4 = (C % 4 == 0) && gy_ld % 4 == 0 && x_ld % 4 == 0 && gx_ld % 4 == 0 && (uintptr_t)gy % a4 == 0 &&
+                    (uintptr_t)x % a4 == 0 && (uintptr_t)gx % a4 == 0;
+    a.vec = v4 ? 4 : 1;
+    const int64_t items = V * (C / a.vec);
+    // gx is what a weight gradient reads next: max |gx| as a by-product when asked for (one atomic per 1024-thread block, see the kernel)
+    a.threads = has_amax ? 1024 : 256;
+    a.grid_x = has_amax ? tem_grid_1d(items, 1024, N > 0 ? (256 + N - 1) / N : 256) : tem_grid_1d(items, 256, 2048);
+    a.fast = (v4 && ((int64_t)a.grid_x * a.threads) % (C / 4) == 0) ? 1 : 0;
+    return a;
+}
+
+// what both entry points below and the launchers require of a tensor argument
+static bool norm_shape_ok(int64_t V, int C, int st) { return st >= 0 && st <= 2 && V > 0 && C > 0 && C <= NORM_MAX_C; }
+
+// The query of the reduction pass (k_norm_partial) of norm_stats_impl (gy = NULL) and norm_bwd_impl (gy given): out[5] =
+// {vec, rows, threads, nblk, vper} -- norm_geom as the launch calls it.  Launches nothing; -1 where the launch refuses the arguments.
+extern "C" int tem_norm_reduce_geom(const void* x, int64_t x_ld, const void* gy, int64_t gy_ld, int64_t V, int C, int st,
+                                    int64_t* out) {
+    if (!(x && out && norm_shape_ok(V, C, st) && x_ld >= C && (!gy || gy_ld >= C))) return -1;
+    const NormGeom g = norm_geom(x, gy, x_ld, gy ? gy_ld : 0, V, C, st);
+    out[0] = g.vec;
+    out[1] = g.rows;
+    out[2] = g.threads;
+    out[3] = g.nblk;
+    out[4] = g.vper;
+    return 0;
+}
+
+// The query of the elementwise pass (k_norm_bwd_apply) of norm_bwd_impl: out[4] = {vec, threads, grid_x, fast}
+extern "C" int tem_norm_apply_geom(const void* gy, int64_t gy_ld, const void* x, int64_t x_ld, const void* gx, int64_t gx_ld,
+                                   int N, int64_t V, int C, int has_amax, int st, int64_t* out) {
+    if (!(gy && x && gx && out && N > 0 && norm_shape_ok(V, C, st) && x_ld >= C && gy_ld >= C && gx_ld >= C)) return -1;
+    const NormApplyGeom a = norm_apply_geom(gy, gy_ld, x, x_ld, gx, gx_ld, N, V, C, has_amax != 0, st);
+    out[0] = a.vec;
+    out[1] = a.threads;
+    out[2] = a.grid_x;
+    out[3] = a.fast;
+    return 0;
+}
+
 extern "C" int64_t tem_norm_ws(int N, int64_t V, int C) {
     (void)V;
     // partials [N][NORM_MAX_BLOCKS][C][2] floats + coefficients [N][C][4] floats
@@ -528,14 +580,10 @@ static int norm_bwd_impl(const void* gy, int64_t gy_ld, const void* x, int64_t x
         TEM_CHECK_LAUNCH("tem_norm_bwd_coef");
         return TEM_OK;
     }
-    const uintptr_t a4 = tem_st_align4(st);
-    bool v4 = (C % 4 == 0) && gy_ld % 4 == 0 && x_ld % 4 == 0 && gx_ld % 4 == 0 && (uintptr_t)gy % a4 == 0 &&
-              (uintptr_t)x % a4 == 0 && (uintptr_t)gx % a4 == 0;
-    int64_t items = V * (v4 ? C / 4 : C);
-    dim3 agrid(tem_grid_1d(items, 256, 2048), N);
-    // gx is what a weight gradient reads next: max |gx| as a by-product when asked for (one atomic per 1024-thread block, see the kernel)
-    const int threads = amax ? 1024 : 256;
-    if (amax) agrid = dim3(tem_grid_1d(items, 1024, N > 0 ? (256 + N - 1) / N : 256), N);
+    const NormApplyGeom a = norm_apply_geom(gy, gy_ld, x, x_ld, gx, gx_ld, N, V, C, amax != nullptr, st);
+    const bool v4 = a.vec == 4;
+    const dim3 agrid(a.grid_x, N);
+    const int threads = a.threads;
     TEM_ST_SWITCH(st, T, {
         if (v4)
             hipLaunchKernelGGL((k_norm_bwd_apply<4, T>), agrid, dim3(threads), 0, (hipStream_t)stream, (const T*)gy, gy_ld,
