@@ -628,6 +628,28 @@ int tem_dice_grad2(const float* p, int64_t p_sn, int64_t p_sc, int64_t p_sv, con
                    int64_t t_sv, const float* ca, const float* cb, const float* gout, int gout_per_channel, float* gp,
                    int64_t g_sn, int64_t g_sc, int64_t g_sv, int N, int C, int64_t V, int flags, float w_dice,
                    float w_bce, tem_stream_t stream);
+/* Masked AND unmasked sums from one pass over p, t and mask (mask non-NULL, target strides): sums = double[2][C][3], the
+ * first half what tem_dice_sums gives with the mask, the second what it gives without -- bit for bit, the partial sums run
+ * in the same order.  Each half goes through tem_dice_finalize.  ws: 2 * tem_dice_ws(N, V, C) bytes.  Loss (masked) and
+ * metric (unmasked) of a self-training validation step (reference self_training/loss.py:52-85) from one read of the prediction. */
+int tem_dice_sums_pair(const float* p, int64_t p_sn, int64_t p_sc, int64_t p_sv, const float* t, int64_t t_sn, int64_t t_sc,
+                       int64_t t_sv, const float* mask, int N, int C, int64_t V, double* sums /*[2][C][3]*/, void* ws,
+                       int64_t ws_bytes, tem_stream_t stream);
+
+/* ---- self-training: pseudo labels and confidence mask from the teacher's output (csrc/selftrain.hip) ----------------
+ * What DefaultPseudoLabeler.__call__ does after the teacher's forward pass (reference self_training/pseudo_labeling.py:39-72),
+ * in one streaming launch.  x: N samples of S elements each, dense (any permutation of a dense tensor: the storage is
+ * processed flat), storage type st; labels and mask have x's layout.
+ *   act:       TEM_ACT_NONE -- the labels are x itself, `labels` must be NULL and nothing is written for them;
+ *              TEM_ACT_SIGMOID -- labels = sigmoid(x), computed in fp32 and rounded once to the storage type.
+ *   mask_mode: 0 none (mask NULL); 1 both sides, (l >= t_hi) | (l <= t_lo) as float32 0 / 1; 2 one side, l >= t_hi as bool
+ *              (one byte, 0 / 1).  The compare runs on the STORED label in the storage type; t_hi and t_lo are the
+ *              thresholds already rounded to that type (t_lo = 1 - t formed in double first), as the reference compares on
+ *              the CPU.
+ *   mask_sample: -1, or k in [0, N): every sample gets sample k's mask, in all channels -- the reference's `mask_channel`
+ *              slices the BATCH axis (:65-71), reproduced as it is.  Then a sample's S elements must be one dense block. */
+int tem_pseudo_label_st(const void* x, void* labels, void* mask, int N, int64_t S, int act, int mask_mode, int mask_sample,
+                        float t_hi, float t_lo, int st, tem_stream_t stream);
 
 /* ---- optimizer -------------------------------------------------------------
  * torch.optim.AdamW step as configured by default_segmentation_trainer

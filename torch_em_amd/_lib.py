@@ -108,6 +108,10 @@ SIGNATURES = {
     "tem_dice_finalize2": (c_int, [c_vp, c_int, c_int, c_double, c_int, c_int, c_int, c_vp, c_vp, c_vp, c_vp]),
     "tem_dice_grad2": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_vp, c_vp, c_int,
                                c_vp, c_i64, c_i64, c_i64, c_int, c_int, c_i64, c_int, c_float, c_float, c_vp]),
+    "tem_dice_sums_pair": (c_int, [c_vp, c_i64, c_i64, c_i64, c_vp, c_i64, c_i64, c_i64, c_vp, c_int, c_int, c_i64,
+                                   c_vp, c_vp, c_i64, c_vp]),
+    # (x, labels, mask, N, S, act, mask_mode, mask_sample, t_hi, t_lo, st, stream)
+    "tem_pseudo_label_st": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_float, c_float, c_int, c_vp]),
     "tem_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_float, c_float, c_float, c_i64,
                                c_float, c_vp]),
     "tem_adamw_hyper": (c_int, [c_vp, c_float, c_float, c_float, c_float, c_float, c_i64, c_float]),

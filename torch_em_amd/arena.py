@@ -21,6 +21,40 @@ def arena_layout(params: List[torch.Tensor]) -> Tuple[Dict[int, Tuple[int, int]]
     return offsets, total
 
 
+def _student_flat(trainer, params):
+    """The student's flat parameter buffer WITHOUT re-homing its parameters a second time: FusedAdamW already keeps
+    them in one arena (optim.py); building another ParamArena over the same tensors would invalidate that one, and
+    the two would rebuild each other (and every packed weight) on every step."""
+    ar = getattr(trainer.optimizer, "_arena", None)
+    if ar is not None and ar.is_current() and len(ar.params) == len(params) and \
+            all(a is b for a, b in zip(ar.params, params)):
+        return ar.flat
+    if hasattr(trainer.optimizer, "_ensure_arena"):
+        return None  # a FusedAdamW over a different parameter list: leave its arena alone
+    if trainer._arena1 is None or not trainer._arena1.is_current():
+        trainer._arena1 = ParamArena(trainer.model)
+    return trainer._arena1.flat
+
+
+def ema_teacher_update(trainer, teacher: torch.nn.Module, momentum: float):
+    """teacher <- m * teacher + (1 - m) * trainer.model as ONE launch over the flat arenas of both models (tem_ema_update):
+    the momentum update of SPOCOTrainer and MeanTeacherTrainer.  The trainer keeps `_arena1` (the student's arena when the
+    optimizer has none) and `_arena2` (the teacher's), both None at first."""
+    from . import ops
+    p1 = [p for p in trainer.model.parameters()]
+    if not p1 or not p1[0].is_cuda:
+        raise RuntimeError(f"{type(trainer).__name__}._momentum_update runs on MI355X only (parameters are on the CPU)")
+    if trainer._arena2 is None or not trainer._arena2.is_current():
+        trainer._arena2 = ParamArena(teacher)
+    src = _student_flat(trainer, p1)
+    if src is not None:
+        ops.ema_update(trainer._arena2.flat, src, float(momentum))
+    else:  # no shared flat buffer (foreign optimizer layout): one launch per tensor, nothing is re-homed
+        for q, p in zip(trainer._arena2.params, p1):
+            ops.ema_update(q.data.view(-1), p.data.contiguous().view(-1), float(momentum))
+    ops.bump_versions(trainer._arena2.params)
+
+
 class ParamArena:
     """Re-homes the parameters of a module into one flat buffer (p.data becomes a view)."""
 

@@ -21,12 +21,14 @@ __device__ __forceinline__ float dice_sigmoid(float x) { return 1.f / (1.f + exp
 
 // thread -> (channel c, voxel sub-row r); CFAST: consecutive threads walk channels (NDHWC
 // prediction), else consecutive threads walk voxels (NCDHW prediction).  NS sums per channel: 3, or 4 with the BCE term.
-template <bool CFAST>
+// PAIR (tem_dice_sums_pair; mask non-null, flags 0): the UNMASKED sums of the same elements go to `part2` -- same order of
+// operations as a launch without a mask, so either half equals what tem_dice_sums gives for it bit for bit.
+template <bool CFAST, bool PAIR = false>
 __global__ void k_dice_partial(const float* __restrict__ p, int64_t p_sn, int64_t p_sc, int64_t p_sv,
                                const float* __restrict__ t, int64_t t_sn, int64_t t_sc, int64_t t_sv,
                                const float* __restrict__ mask, int N, int C, int64_t V, int rows, int64_t vper,
-                               int nblk_per_n, float* __restrict__ part, int flags) {
-    extern __shared__ float sh[];  // [rows][C][NS]
+                               int nblk_per_n, float* __restrict__ part, int flags, float* __restrict__ part2 = nullptr) {
+    extern __shared__ float sh[];  // [rows][C][NS] (PAIR: twice, the unmasked sums behind the masked)
     const int NS = (flags & TEM_DICE_BCE) ? 4 : 3;
     const int n = blockIdx.x / nblk_per_n, b = blockIdx.x % nblk_per_n;
     int c, r;
@@ -43,8 +45,14 @@ __global__ void k_dice_partial(const float* __restrict__ p, int64_t p_sn, int64_
     const float* tp = t + (int64_t)n * t_sn + (int64_t)c * t_sc;
     const float* mp = mask ? mask + (int64_t)n * t_sn + (int64_t)c * t_sc : nullptr;
     float s0 = 0.f, s1 = 0.f, s2 = 0.f, s3 = 0.f;
+    float u0 = 0.f, u1 = 0.f, u2 = 0.f;
     for (int64_t v = v0 + r; v < v1; v += rows) {
         float pv = pp[v * p_sv], tv = tp[v * t_sv];
+        if constexpr (PAIR) {
+            u0 = fmaf(pv, tv, u0);
+            u1 = fmaf(pv, pv, u1);
+            u2 = fmaf(tv, tv, u2);
+        }
         if (flags) {   // launch-uniform
             const float xv = pv;
             if (flags & TEM_DICE_LOGITS) pv = dice_sigmoid(xv);
@@ -69,6 +77,12 @@ __global__ void k_dice_partial(const float* __restrict__ p, int64_t p_sn, int64_
     my[1] = s1;
     my[2] = s2;
     if (NS == 4) my[3] = s3;
+    if constexpr (PAIR) {
+        float* mu = my + (int64_t)rows * C * NS;
+        mu[0] = u0;
+        mu[1] = u1;
+        mu[2] = u2;
+    }
     __syncthreads();
     if (r == 0) {
         float a0 = 0.f, a1 = 0.f, a2 = 0.f, a3 = 0.f;
@@ -84,6 +98,19 @@ __global__ void k_dice_partial(const float* __restrict__ p, int64_t p_sn, int64_
         o[1] = a1;
         o[2] = a2;
         if (NS == 4) o[3] = a3;
+        if constexpr (PAIR) {
+            float b0 = 0.f, b1 = 0.f, b2 = 0.f;
+            for (int rr = 0; rr < rows; ++rr) {
+                const float* q = sh + ((int64_t)(rows + rr) * C + c) * NS;
+                b0 += q[0];
+                b1 += q[1];
+                b2 += q[2];
+            }
+            float* q = part2 + ((int64_t)blockIdx.x * C + c) * NS;
+            q[0] = b0;
+            q[1] = b1;
+            q[2] = b2;
+        }
     }
 }
 
@@ -93,12 +120,18 @@ __global__ void k_dice_partial(const float* __restrict__ p, int64_t p_sn, int64_
 // affinity channels of cfg 3, 1.5 TB/s.  Here both are coalesced: a lane reads its voxel's C contiguous prediction values
 // (16-byte loads when C % 4 == 0) and, per channel, the wave reads 64 consecutive target values.
 #define DICE_VOX_C 16
-template <int VECP>   // prediction loads: 4 = float4 (p_sc == 1, C % 4 == 0, aligned), 2 = float2 (C == 2), 1 = scalar / any strides
+template <int VECP, bool PAIR = false>   // prediction loads: 4 = float4 (p_sc == 1, C % 4 == 0, aligned), 2 = float2 (C == 2), 1 = scalar / any strides
 __global__ __launch_bounds__(256) void k_dice_partial_vox(const float* __restrict__ p, int64_t p_sn, int64_t p_sc, int64_t p_sv,
                                                           const float* __restrict__ t, int64_t t_sn, int64_t t_sc, int64_t t_sv,
                                                           const float* __restrict__ mask, int N, int C, int64_t V, int64_t vper,
-                                                          int nblk_per_n, float* __restrict__ part, int flags) {
+                                                          int nblk_per_n, float* __restrict__ part, int flags,
+                                                          float* __restrict__ part2 = nullptr) {
     __shared__ float shv[4][DICE_VOX_C][4];
+    __shared__ float shu[PAIR ? 4 : 1][PAIR ? DICE_VOX_C : 1][4];   // PAIR: the unmasked sums (see k_dice_partial)
+    constexpr int NU = PAIR ? DICE_VOX_C : 1;
+    float u0[NU], u1[NU], u2[NU];
+#pragma unroll
+    for (int c = 0; c < NU; ++c) u0[c] = u1[c] = u2[c] = 0.f;
     const int NS = (flags & TEM_DICE_BCE) ? 4 : 3;
     const int n = blockIdx.x / nblk_per_n, b = blockIdx.x % nblk_per_n;
     (void)vper;
@@ -139,6 +172,11 @@ __global__ __launch_bounds__(256) void k_dice_partial_vox(const float* __restric
         for (int c = 0; c < DICE_VOX_C; ++c)
             if (c < C) {
                 float pv = pq[c], tv = tq[c];
+                if constexpr (PAIR) {
+                    u0[c] = fmaf(pv, tv, u0[c]);
+                    u1[c] = fmaf(pv, pv, u1[c]);
+                    u2[c] = fmaf(tv, tv, u2[c]);
+                }
                 if (flags) {   // launch-uniform
                     const float xv = pv;
                     if (flags & TEM_DICE_LOGITS) pv = dice_sigmoid(xv);
@@ -171,10 +209,23 @@ __global__ __launch_bounds__(256) void k_dice_partial_vox(const float* __restric
                 shv[wv][c][3] = a3;
             }
         }
+    if constexpr (PAIR) {
+#pragma unroll
+        for (int c = 0; c < DICE_VOX_C; ++c)
+            if (c < C) {
+                const float b0 = tem_wave_sum(u0[c]), b1 = tem_wave_sum(u1[c]), b2 = tem_wave_sum(u2[c]);
+                if (lane == 0) {
+                    shu[wv][c][0] = b0;
+                    shu[wv][c][1] = b1;
+                    shu[wv][c][2] = b2;
+                }
+            }
+    }
     __syncthreads();
     for (int i = threadIdx.x; i < C * NS; i += 256) {
         const int c = i / NS, k = i % NS;
         part[((int64_t)blockIdx.x * C + c) * NS + k] = shv[0][c][k] + shv[1][c][k] + shv[2][c][k] + shv[3][c][k];
+        if constexpr (PAIR) part2[((int64_t)blockIdx.x * C + c) * NS + k] = shu[0][c][k] + shu[1][c][k] + shu[2][c][k] + shu[3][c][k];
     }
 }
 
@@ -199,15 +250,18 @@ __global__ __launch_bounds__(256) void k_dice_reduce(const float* __restrict__ p
     if (threadIdx.x < NS) sums[c * NS + threadIdx.x] = sh[threadIdx.x][0] + sh[threadIdx.x][1] + sh[threadIdx.x][2] + sh[threadIdx.x][3];
 }
 
+// PAIR: sums is double[2][C][3] (masked, unmasked) and ws holds two partial tables (2 * tem_dice_ws bytes)
+template <bool PAIR = false>
 static int dice_sums_impl(const float* p, int64_t p_sn, int64_t p_sc, int64_t p_sv, const float* t, int64_t t_sn,
                           int64_t t_sc, int64_t t_sv, const float* mask, int N, int C, int64_t V, double* sums,
                           void* ws, int64_t ws_bytes, int flags, tem_stream_t stream) {
     TEM_REQUIRE(p && t && sums && ws, "tem_dice_sums: null pointer");
+    TEM_REQUIRE(!PAIR || (mask && !flags), "tem_dice_sums_pair: needs a mask and no flags");
     TEM_REQUIRE((flags & ~(TEM_DICE_LOGITS | TEM_DICE_BCE)) == 0 && (!(flags & TEM_DICE_BCE) || !mask),
                 "tem_dice_sums2: unknown flags, or the BCE term together with a mask");
     const int NS = (flags & TEM_DICE_BCE) ? 4 : 3;
     TEM_REQUIRE(N > 0 && C > 0 && C <= 1024 && V > 0, "tem_dice_sums: bad shape (C=%d)", C);
-    if (ws_bytes < tem_dice_ws(N, V, C)) {
+    if (ws_bytes < (PAIR ? 2 : 1) * tem_dice_ws(N, V, C)) {
         tem_set_error("tem_dice_sums: workspace too small");
         return TEM_EWS;
     }
@@ -224,27 +278,29 @@ static int dice_sums_impl(const float* p, int64_t p_sn, int64_t p_sc, int64_t p_
     if (nb > maxb) nb = maxb;
     int64_t vper = tem_cdiv(V, nb);
     int nblk = (int)nb * N;
-    size_t lds = (size_t)rows * C * NS * sizeof(float);
+    size_t lds = (size_t)rows * C * NS * sizeof(float) * (PAIR ? 2 : 1);
     float* part = (float*)ws;
+    float* part2 = PAIR ? part + (int64_t)DICE_MAX_BLOCKS * C * 4 : nullptr;
     bool cfast = (p_sc == 1);
     if (C <= DICE_VOX_C && tem_option(TEM_OPT_DICE_VOX)) {
         const bool al = cfast && p_sn % 4 == 0 && p_sv % 4 == 0 && ((uintptr_t)p % 16 == 0);
         if (al && C % 4 == 0)
-            hipLaunchKernelGGL((k_dice_partial_vox<4>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, p, p_sn, p_sc, p_sv, t, t_sn,
-                               t_sc, t_sv, mask, N, C, V, vper, (int)nb, part, flags);
+            hipLaunchKernelGGL((k_dice_partial_vox<4, PAIR>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, p, p_sn, p_sc, p_sv, t, t_sn,
+                               t_sc, t_sv, mask, N, C, V, vper, (int)nb, part, flags, part2);
         else if (cfast && C == 2 && p_sn % 2 == 0 && p_sv == 2 && ((uintptr_t)p % 8 == 0))
-            hipLaunchKernelGGL((k_dice_partial_vox<2>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, p, p_sn, p_sc, p_sv, t, t_sn,
-                               t_sc, t_sv, mask, N, C, V, vper, (int)nb, part, flags);
+            hipLaunchKernelGGL((k_dice_partial_vox<2, PAIR>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, p, p_sn, p_sc, p_sv, t, t_sn,
+                               t_sc, t_sv, mask, N, C, V, vper, (int)nb, part, flags, part2);
         else
-            hipLaunchKernelGGL((k_dice_partial_vox<1>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, p, p_sn, p_sc, p_sv, t, t_sn,
-                               t_sc, t_sv, mask, N, C, V, vper, (int)nb, part, flags);
+            hipLaunchKernelGGL((k_dice_partial_vox<1, PAIR>), dim3(nblk), dim3(256), 0, (hipStream_t)stream, p, p_sn, p_sc, p_sv, t, t_sn,
+                               t_sc, t_sv, mask, N, C, V, vper, (int)nb, part, flags, part2);
     } else if (cfast)
-        hipLaunchKernelGGL((k_dice_partial<true>), dim3(nblk), dim3(threads), lds, (hipStream_t)stream, p, p_sn, p_sc,
-                           p_sv, t, t_sn, t_sc, t_sv, mask, N, C, V, rows, vper, (int)nb, part, flags);
+        hipLaunchKernelGGL((k_dice_partial<true, PAIR>), dim3(nblk), dim3(threads), lds, (hipStream_t)stream, p, p_sn, p_sc,
+                           p_sv, t, t_sn, t_sc, t_sv, mask, N, C, V, rows, vper, (int)nb, part, flags, part2);
     else
-        hipLaunchKernelGGL((k_dice_partial<false>), dim3(nblk), dim3(threads), lds, (hipStream_t)stream, p, p_sn, p_sc,
-                           p_sv, t, t_sn, t_sc, t_sv, mask, N, C, V, rows, vper, (int)nb, part, flags);
+        hipLaunchKernelGGL((k_dice_partial<false, PAIR>), dim3(nblk), dim3(threads), lds, (hipStream_t)stream, p, p_sn, p_sc,
+                           p_sv, t, t_sn, t_sc, t_sv, mask, N, C, V, rows, vper, (int)nb, part, flags, part2);
     hipLaunchKernelGGL(k_dice_reduce, dim3(C), dim3(256), 0, (hipStream_t)stream, part, nblk, C, sums, NS);
+    if (PAIR) hipLaunchKernelGGL(k_dice_reduce, dim3(C), dim3(256), 0, (hipStream_t)stream, part2, nblk, C, sums + (int64_t)C * 3, NS);
     TEM_CHECK_LAUNCH("tem_dice_sums");
     return TEM_OK;
 }
@@ -253,6 +309,14 @@ extern "C" int tem_dice_sums(const float* p, int64_t p_sn, int64_t p_sc, int64_t
                              int64_t t_sc, int64_t t_sv, const float* mask, int N, int C, int64_t V, double* sums,
                              void* ws, int64_t ws_bytes, tem_stream_t stream) {
     return dice_sums_impl(p, p_sn, p_sc, p_sv, t, t_sn, t_sc, t_sv, mask, N, C, V, sums, ws, ws_bytes, 0, stream);
+}
+
+// sums[2][C][3]: the masked sums of tem_dice_sums and, from the same pass over p, t and mask, the unmasked ones -- loss and
+// metric of a self-training validation step (self_training/loss.py: DefaultSelfTrainingLossAndMetric) from one read
+extern "C" int tem_dice_sums_pair(const float* p, int64_t p_sn, int64_t p_sc, int64_t p_sv, const float* t, int64_t t_sn,
+                                  int64_t t_sc, int64_t t_sv, const float* mask, int N, int C, int64_t V, double* sums,
+                                  void* ws, int64_t ws_bytes, tem_stream_t stream) {
+    return dice_sums_impl<true>(p, p_sn, p_sc, p_sv, t, t_sn, t_sc, t_sv, mask, N, C, V, sums, ws, ws_bytes, 0, stream);
 }
 
 // sums[C][3] as tem_dice_sums, or [C][4] with TEM_DICE_BCE (4th column: the sum of the per-element cross entropy)

@@ -70,6 +70,21 @@ def dice_score(input_: torch.Tensor, target: torch.Tensor, invert: bool = False,
     return _DiceFunction.apply(input_, target, mask, invert, channelwise, reduce_channel, eps)
 
 
+def dice_loss_pair(input_: torch.Tensor, target: torch.Tensor, mask: torch.Tensor, channelwise: bool = True,
+                   reduce_channel: Optional[str] = "sum", eps: float = 1e-7):
+    """(DiceLoss with `mask`, DiceLoss without it) from ONE pass over prediction, target and mask (tem_dice_sums_pair): loss
+    and metric of a self-training validation step.  No gradient is recorded: for passes under `torch.no_grad()`."""
+    _check_inputs(input_, target)
+    if channelwise and reduce_channel not in ("sum", "mean", "max", "min", None):
+        raise ValueError(f"Unsupported channel reduction {reduce_channel}")
+    if not input_.is_cuda:
+        raise RuntimeError("torch_em_amd.loss runs on MI355X only (got CPU tensors); there is no CPU fallback")
+    sums, _, _ = ops.dice_sums_pair(input_.detach().to(torch.float32), target.to(torch.float32), mask.to(torch.float32))
+    per_channel = channelwise and reduce_channel is None
+    outs = [ops.dice_finalize(sums[i], eps, channelwise, True, reduce_channel)[0] for i in range(2)]
+    return tuple(o if per_channel else o.reshape(()) for o in outs)
+
+
 class DiceLoss(nn.Module):
     """Dice error 1 - 2<x,t>/(|x|^2+|t|^2) per channel, reduced over channels (reference loss/dice.py:96-133)."""
 

@@ -919,6 +919,94 @@ def dice_grad(p, t, mask, ca, cb, gout, gout_per_channel, channels_last: bool):
     return gp
 
 
+def dice_sums_pair(p, t, mask):
+    """-> (double[2, C, 3], p, t): `dice_sums(p, t, mask)[0]` and `dice_sums(p, t)[0]` from ONE pass over prediction, target
+    and mask (tem_dice_sums_pair) -- bit for bit what the two calls give.  For passes that need no gradient."""
+    _req_cuda(p, t, mask)
+    ps = _ncv_strides(p)
+    if ps is None:
+        p = p.contiguous()
+        ps = _ncv_strides(p)
+    ts = _ncv_strides(t)
+    if ts is None:
+        t = t.contiguous()
+        ts = _ncv_strides(t)
+    ms = _ncv_strides(mask)
+    if ms is None or ms[:3] != ts[:3]:
+        raise ValueError("dice: mask must share the target's strides")
+    N, C, V = ps[3:]
+    sums = torch.empty((2, C, 3), dtype=torch.float64, device=p.device)
+    lib = _lib.load()
+    nws = 2 * lib.tem_dice_ws(N, V, C)
+    ws = _workspace(nws, p.device)
+    _lib.check(lib.tem_dice_sums_pair(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], _p(mask), N, C, V,
+                                      _p(sums), _p(ws), nws, _stream(p)), "tem_dice_sums_pair")
+    return sums, p, t
+
+
+# ---------------------------------------------------------- self-training ----
+PL_MASK_NONE, PL_MASK_BOTH, PL_MASK_ONE = 0, 1, 2   # mask_mode of tem_pseudo_label_st (include/tem_hip.h)
+
+
+def _is_dense(t: torch.Tensor) -> bool:
+    """the elements of t fill one block of storage without gaps or overlap, in whatever order of the axes"""
+    expect = 1
+    for stride, size in sorted((st, sz) for st, sz in zip(t.stride(), t.shape) if sz != 1):
+        if stride != expect:
+            return False
+        expect *= size
+    return True
+
+
+def round_to(value: float, dtype: torch.dtype) -> float:
+    """`value` (a Python float: a double) rounded to `dtype` the way a torch compare rounds its scalar operand"""
+    return float(torch.tensor(float(value), dtype=torch.float64).to(dtype).item())
+
+
+def pseudo_label(x: torch.Tensor, activation: Optional[str] = None, confidence_threshold: Optional[float] = None,
+                 threshold_from_both_sides: bool = True, mask_sample: Optional[int] = None, out=None):
+    """Pseudo labels and confidence mask from a teacher prediction x [N, C, *spatial] (float32 / float16 / bfloat16), one
+    streaming launch (tem_pseudo_label_st; reference self_training/pseudo_labeling.py:59-72 after the forward pass).
+    -> (labels, mask): labels = x itself (activation None) or sigmoid(x) in x's dtype; mask = None (no threshold),
+    float32 0 / 1 for both sides, bool for one side.  Both come out in x's memory layout, so the masked Dice kernels take them
+    as they are.  `mask_sample=k`: every sample gets sample k's mask (the reference's `mask_channel` slices the batch axis).
+    `out=(labels, mask)` is a TEST HOOK (no library caller uses it): write into these tensors (x's shape and strides; an entry
+    that is not produced is None), so a test can lay the outputs out between guard zones and poison them first."""
+    _req_cuda(x)
+    if x.dtype not in _ST:
+        raise ValueError(f"pseudo_label: expected float32, float16 or bfloat16, got {x.dtype}")
+    if activation not in (None, "sigmoid"):
+        raise ValueError(f"pseudo_label: Invalid activation: {activation}")
+    if x.dim() < 2 or x.numel() == 0:
+        raise ValueError(f"pseudo_label: expected a non-empty [N, C, ...] tensor, got shape {tuple(x.shape)}")
+    if confidence_threshold is None:
+        mask_sample = None
+        if activation is None:
+            return x, None
+    N = x.shape[0]
+    if mask_sample is not None and not 0 <= mask_sample < N:
+        # the reference slices past the end of the batch axis and fails in expand()
+        raise ValueError(f"pseudo_label: mask_channel {mask_sample} is out of range for a batch of {N}")
+    if not _is_dense(x) or (mask_sample is not None and N > 1 and x.stride(0) != x.numel() // N):
+        x = x.contiguous()
+    mdtype = torch.float32 if threshold_from_both_sides else torch.bool
+    if out is not None:
+        for t, dtype, needed in ((out[0], x.dtype, activation is not None), (out[1], mdtype, confidence_threshold is not None)):
+            if (t is not None) != needed or (needed and (t.dtype != dtype or t.shape != x.shape or t.stride() != x.stride()
+                                                         or t.device != x.device)):
+                raise ValueError("pseudo_label: `out` must hold exactly the tensors this call writes, laid out like x")
+    labels = (out[0] if out is not None else torch.empty_like(x)) if activation is not None else None
+    mode, mask, t_hi, t_lo = PL_MASK_NONE, None, 0.0, 0.0
+    if confidence_threshold is not None:
+        mode = PL_MASK_BOTH if threshold_from_both_sides else PL_MASK_ONE
+        mask = out[1] if out is not None else torch.empty_like(x, dtype=mdtype)
+        t_hi, t_lo = round_to(confidence_threshold, x.dtype), round_to(1.0 - confidence_threshold, x.dtype)
+    _lib.check(_lib.load().tem_pseudo_label_st(_p(x), _p(labels), _p(mask), N, x.numel() // N, ACT[activation], mode,
+                                               -1 if mask_sample is None else int(mask_sample), t_hi, t_lo, _st(x), _stream(x)),
+               "tem_pseudo_label_st")
+    return (x if labels is None else labels), mask
+
+
 # ---------------------------------------------------------------- clDice ----
 # modes of tem_cldice_step (include/tem_hip.h)
 CLD_ROUND0, CLD_ROUND, CLD_ERODE, CLD_OPEN, CLD_DILATE, CLD_BWD_POINT0, CLD_BWD_POINT = range(7)

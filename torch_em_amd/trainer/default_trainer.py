@@ -280,19 +280,17 @@ class DefaultTrainer:
 
     @classmethod
     def from_checkpoint(cls, checkpoint_folder, name="best", device=None, train_loader=None, val_loader=None,
-                        raw_transform=_FROM_CHECKPOINT, target_transform=_FROM_CHECKPOINT, augmentation=_FROM_CHECKPOINT):
+                        raw_transform=_FROM_CHECKPOINT, target_transform=_FROM_CHECKPOINT, augmentation=_FROM_CHECKPOINT,
+                        save_dict=None):
         """Rebuild a trainer from `<checkpoint_folder>/<name>.pt` (reference :288-330).  Loaders are rebuilt
         from the pickled datasets unless given.  The on-device `raw_transform` / `target_transform` / `augmentation` of
         the saved trainer come back from the checkpoint; one that could not be pickled must be passed again (RuntimeError
-        otherwise: training on un-standardised inputs or raw label ids must not happen silently)."""
-        save_dict = torch.load(os.path.join(checkpoint_folder, f"{name}.pt"), weights_only=False)
+        otherwise: training on un-standardised inputs or raw label ids must not happen silently).  `save_dict`: the
+        checkpoint file's content when the caller has loaded it already (util.get_trainer)."""
+        if save_dict is None:
+            save_dict = torch.load(os.path.join(checkpoint_folder, f"{name}.pt"), weights_only=False)
         init = save_dict["init"]
-        given = {"raw_transform": raw_transform, "target_transform": target_transform, "augmentation": augmentation}
-        missing = [k for k in init.get("unpicklable_transforms", []) if given[k] is _FROM_CHECKPOINT]
-        if missing:
-            raise RuntimeError(f"from_checkpoint: the saved trainer used {missing}, which could not be stored in the "
-                               "checkpoint; pass them to from_checkpoint()")
-        transforms = {k: (init.get(k) if v is _FROM_CHECKPOINT else v) for k, v in given.items()}
+        transforms = cls._device_transforms_from(init, raw_transform, target_transform, augmentation)
         model = _import_class(init["model_class"])(**init["model_kwargs"])
         loss = _import_class(init["loss_class"])(**init["loss_kwargs"])
         metric = _import_class(init["metric_class"])(**init["metric_kwargs"])
@@ -315,6 +313,17 @@ class DefaultTrainer:
         trainer._initialize(0, save_dict)
         trainer._is_initialized = True
         return trainer
+
+    @staticmethod
+    def _device_transforms_from(init, raw_transform, target_transform, augmentation):
+        """The on-device pre-pass of a saved trainer: from its `init` record unless given; RuntimeError when one could not
+        be pickled and is not given."""
+        given = {"raw_transform": raw_transform, "target_transform": target_transform, "augmentation": augmentation}
+        missing = [k for k in init.get("unpicklable_transforms", []) if given[k] is _FROM_CHECKPOINT]
+        if missing:
+            raise RuntimeError(f"from_checkpoint: the saved trainer used {missing}, which could not be stored in the "
+                               "checkpoint; pass them to from_checkpoint()")
+        return {k: (init.get(k) if v is _FROM_CHECKPOINT else v) for k, v in given.items()}
 
     def _verify_if_training_completed(self, checkpoint="latest"):
         path = os.path.join(self.checkpoint_folder, f"{checkpoint}.pt")

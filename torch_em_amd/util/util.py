@@ -89,11 +89,16 @@ def get_constructor_arguments(obj) -> dict:
 
 
 def get_trainer(checkpoint, name: str = "best", device=None):
-    """Trainer from a checkpoint FOLDER (or the trainer itself, passed through)."""
+    """Trainer from a checkpoint FOLDER (or the trainer itself, passed through).  A checkpoint that names its trainer class
+    (`init.trainer_class`: MeanTeacherTrainer) is rebuilt by that class, any other by DefaultTrainer."""
     from ..trainer import DefaultTrainer
     if isinstance(checkpoint, str):
         assert os.path.exists(checkpoint), checkpoint
-        checkpoint = DefaultTrainer.from_checkpoint(checkpoint, name=name, device=device)
+        from ..trainer.default_trainer import _import_class
+        save_dict = torch.load(os.path.join(checkpoint, f"{name}.pt"), weights_only=False)   # loaded once, handed on
+        trainer_class = save_dict["init"].get("trainer_class")
+        cls = DefaultTrainer if trainer_class is None else _import_class(trainer_class)
+        checkpoint = cls.from_checkpoint(checkpoint, name=name, device=device, save_dict=save_dict)
     assert isinstance(checkpoint, DefaultTrainer)
     return checkpoint
 
