@@ -583,6 +583,19 @@ int tem_upsample_fwd_path(const void* x, int64_t x_ld, const void* y, int64_t y_
                           int fz, int fy, int fx, int has_part, int st);
 int tem_upsample_bwd_path(const void* gy, int64_t gy_ld, const void* gx, int64_t gx_ld, int N, int D, int H, int W, int C,
                           int fz, int fy, int fx, const void* u, int64_t u_ld, int st);
+/* ... and the kernel tem_maxpool3d_fwd_st / tem_maxpool3d_bwd_st launch, under the current option "pool_vec8" (has_stat:
+ * stat_part is passed, with stat_blocks = tem_maxpool3d_fwd_stat_blocks(); has_gcoef / has_ycoef: coefficient tables that
+ * pass the launch's own checks are passed).  Windows of at most 8 voxels take the unrolled form of the kernel named, larger
+ * ones its loop form.
+ *   0 one channel per item          3 the packed-word 16-bit backward, windows of 1 x 2 x 2 voxels
+ *   1 4 channels per item           4 the packed-word 16-bit backward, windows of 2 x 2 x 2 voxels
+ *   2 8 channels per item (16-bit tensors)
+ *  -1 the launch refuses these arguments */
+int tem_maxpool3d_fwd_path(const void* x, int64_t x_ld, const void* y, int64_t y_ld, int N, int D, int H, int W, int C,
+                           int fz, int fy, int fx, int has_stat, int st);
+int tem_maxpool3d_bwd_path(const void* gy, int64_t gy_ld, const void* x, int64_t x_ld, const void* gskip, int64_t gskip_ld,
+                           const void* gx, int64_t gx_ld, int N, int D, int H, int W, int C, int fz, int fy, int fx,
+                           int has_gcoef, int has_ycoef, int st);
 
 /* ---- Dice ------------------------------------------------------------------
  * dice_score / DiceLoss (loss/dice.py:34-133) and the masked variant

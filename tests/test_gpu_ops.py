@@ -1155,6 +1155,9 @@ def test_norm_stats_and_backward(C, G, affine, shape):
 @pytest.mark.parametrize("C,f,shape", [(4, (2, 2, 2), (2, 4, 6, 8)), (32, (1, 2, 2), (1, 3, 8, 8)),
                                         (3, (2, 2, 2), (1, 2, 2, 2)), (64, (1, 2, 2), (2, 1, 16, 16))])
 def test_maxpool(C, f, shape):
+    """nn.MaxPool3d forward and backward against ATen on dense fp32 tensors of one trip per row.  Every dispatch path of both
+    directions, the fused norm backwards, the 16-bit kernels, sliced layouts and the row partials are held to float64 element by
+    element in tests/test_gpu_maxpool.py."""
     ops = _ops()
     N, D, H, W = shape
     g = torch.Generator().manual_seed(C)

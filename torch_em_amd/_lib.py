@@ -193,6 +193,9 @@ SIGNATURES = {
     # dispatch queries: 0 gather<1>, 1 gather<4>, 2 factor-2 <.., 4>, 3 factor-2 <.., 8>, -1 refused
     "tem_upsample_fwd_path": (c_int, [c_vp, c_i64, c_vp, c_i64] + [c_int] * 8 + [c_int, c_int]),
     "tem_upsample_bwd_path": (c_int, [c_vp, c_i64, c_vp, c_i64] + [c_int] * 8 + [c_vp, c_i64, c_int]),
+    # 0 <1>, 1 <4>, 2 <8>, 3 packed 16-bit fz = 1, 4 packed 16-bit fz = 2, -1 refused
+    "tem_maxpool3d_fwd_path": (c_int, [c_vp, c_i64, c_vp, c_i64] + [c_int] * 8 + [c_int, c_int]),
+    "tem_maxpool3d_bwd_path": (c_int, [c_vp, c_i64, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64] + [c_int] * 8 + [c_int, c_int, c_int]),
     "tem_norm_stats_st": (c_int, [c_vp, c_i64, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_float,
                                   c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_int, c_vp]),
     "tem_norm_bwd_st": (c_int, [c_vp, c_i64, c_vp, c_i64, c_int, c_i64, c_int, c_int, c_vp, c_vp, c_vp, c_int, c_vp, c_i64,

@@ -301,6 +301,15 @@ __global__ __launch_bounds__(256) void k_maxpool_bwd(const T* __restrict__ gy, i
     if (amax) tem_amax_commit(amax, amx);
 }
 
+// The kernel a launch takes (what tem_maxpool3d_fwd_path / tem_maxpool3d_bwd_path return)
+enum { MP_VEC1 = 0, MP_VEC4 = 1, MP_VEC8 = 2, MP_PACKED16_FZ1 = 3, MP_PACKED16_FZ2 = 4 };
+
+static int maxpool_fwd_select(const void* x, int64_t x_ld, const void* y, int64_t y_ld, int C, int st) {
+    // 16-bit tensors: 8 channels per thread (16-byte accesses) where a thread keeps its channels over its trips (the row partials)
+    if (vec8_ok(C, {x, y}, {x_ld, y_ld}, st) && 256 % (C / 8) == 0 && tem_option(TEM_OPT_POOL_VEC8)) return MP_VEC8;
+    return vec4_ok(C, {x, y}, {x_ld, y_ld}, st) ? MP_VEC4 : MP_VEC1;
+}
+
 static int maxpool3d_fwd_impl(const void* x, int64_t x_ld, void* y, int64_t y_ld, int N, int D, int H, int W, int C, int fz,
                               int fy, int fx, float* stat, int st, tem_stream_t stream) {
     TEM_REQUIRE(x && y && N > 0 && C > 0 && x_ld >= C && y_ld >= C, "tem_maxpool3d_fwd: bad arguments");
@@ -309,19 +318,18 @@ static int maxpool3d_fwd_impl(const void* x, int64_t x_ld, void* y, int64_t y_ld
                 "tem_maxpool3d_fwd: shape (%d,%d,%d) not divisible by factors (%d,%d,%d)", D, H, W, fz, fy, fx);
     int64_t rows = (int64_t)N * (D / fz) * (H / fy);
     TEM_REQUIRE(rows < (1ll << 31), "tem_maxpool3d_fwd: too many rows");
-    const bool v4 = vec4_ok(C, {x, y}, {x_ld, y_ld}, st);
-    const bool v8 = vec8_ok(C, {x, y}, {x_ld, y_ld}, st) && 256 % (C / 8) == 0 && tem_option(TEM_OPT_POOL_VEC8);
-    const int cq = v8 ? C / 8 : v4 ? C / 4 : C;
+    const int path = maxpool_fwd_select(x, x_ld, y, y_ld, C, st);
+    const int cq = path == MP_VEC8 ? C / 8 : path == MP_VEC4 ? C / 4 : C;
     TEM_REQUIRE(!stat || (cq <= 256 && 256 % cq == 0), "tem_maxpool3d_fwd_stats: tem_maxpool3d_fwd_stat_blocks() == 0 for C = %d", C);
     const size_t lds = stat ? (size_t)(256 / cq) * C * 2 * sizeof(float) : 0;
-    if (v8) {
+    if (path == MP_VEC8) {
         TEM_ST16_SWITCH(st, T, hipLaunchKernelGGL((k_maxpool_fwd<8, T>), dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream,
                                                   (const T*)x, x_ld, (T*)y, y_ld, D, H, W, C, fz, fy, fx, stat));
         TEM_CHECK_LAUNCH("tem_maxpool3d_fwd");
         return TEM_OK;
     }
     TEM_ST_SWITCH(st, T, {
-        if (v4)
+        if (path == MP_VEC4)
             hipLaunchKernelGGL((k_maxpool_fwd<4, T>), dim3((unsigned)rows), dim3(256), lds, (hipStream_t)stream, (const T*)x, x_ld,
                                (T*)y, y_ld, D, H, W, C, fz, fy, fx, stat);
         else
@@ -362,6 +370,21 @@ extern "C" int tem_maxpool3d_fwd_st(const void* x, int64_t x_ld, void* y, int64_
                     "tem_maxpool3d_fwd_stats: x / y must be aligned to 4 elements with ld %% 4 == 0");
     }
     return maxpool3d_fwd_impl(x, x_ld, y, y_ld, N, D, H, W, C, fz, fy, fx, stat_part, st, stream);
+}
+
+// Dispatch query: the kernel tem_maxpool3d_fwd_st takes for these arguments (has_stat: with stat_part and its own
+// tem_maxpool3d_fwd_stat_blocks()), or -1 where the launch refuses them.  Launches nothing.
+extern "C" int tem_maxpool3d_fwd_path(const void* x, int64_t x_ld, const void* y, int64_t y_ld, int N, int D, int H, int W, int C,
+                                      int fz, int fy, int fx, int has_stat, int st) {
+    if (!(x && y && N > 0 && C > 0 && x_ld >= C && y_ld >= C && D > 0 && H > 0 && W > 0 && fz > 0 && fy > 0 && fx > 0)) return -1;
+    if (st < 0 || st > 2 || D % fz || H % fy || W % fx || (int64_t)N * (D / fz) * (H / fy) >= (1ll << 31)) return -1;
+    const int path = maxpool_fwd_select(x, x_ld, y, y_ld, C, st);
+    if (has_stat) {
+        const int cq = path == MP_VEC8 ? C / 8 : path == MP_VEC4 ? C / 4 : C;
+        if (tem_maxpool3d_fwd_stat_blocks(D, H, C, fz, fy) <= 0 || (C % 4 == 0) != vec4_ok(C, {x, y}, {x_ld, y_ld}, st)) return -1;
+        if (cq > 256 || 256 % cq) return -1;
+    }
+    return path;
 }
 
 // k_maxpool_bwd<8, T> for 16-bit tensors and windows of FZ x 2 x 2 voxels, written for REGISTERS: the generic kernel
@@ -458,6 +481,17 @@ __global__ __launch_bounds__(256, 3) void k_maxpool_bwd16(const T* __restrict__ 
     if (amax) tem_amax_commit(amax, amx);
 }
 
+static int maxpool_bwd_select(const void* gy, int64_t gy_ld, const void* x, int64_t x_ld, const void* gskip, int64_t gskip_ld,
+                              const void* gx, int64_t gx_ld, int C, int fz, int fy, int fx, int st) {
+    if (vec8_ok(C, {gy, x, gskip, gx}, {gy_ld, x_ld, gskip ? gskip_ld : 0, gx_ld}, st) && tem_option(TEM_OPT_POOL_VEC8)) {
+        // the packed-word kernel: windows of fz x 2 x 2 voxels, both coefficient tables (2 x C float4) within 64 KB of LDS
+        if (fy == 2 && fx == 2 && (fz == 1 || fz == 2) && C <= 2048 && tem_option(TEM_OPT_POOL_VEC8) >= 2)
+            return fz == 2 ? MP_PACKED16_FZ2 : MP_PACKED16_FZ1;
+        return MP_VEC8;
+    }
+    return vec4_ok(C, {gy, x, gskip, gx}, {gy_ld, x_ld, gskip ? gskip_ld : 0, gx_ld}, st) ? MP_VEC4 : MP_VEC1;
+}
+
 static int maxpool3d_bwd_impl(const void* gy, int64_t gy_ld, const void* x, int64_t x_ld, const void* gskip,
                               int64_t gskip_ld, int relu_mask, void* gx, int64_t gx_ld, int N, int D, int H, int W,
                               int C, int fz, int fy, int fx, const float* gcoef, int64_t gcoef_ld, const float* ycoef,
@@ -469,23 +503,23 @@ static int maxpool3d_bwd_impl(const void* gy, int64_t gy_ld, const void* x, int6
                 "tem_maxpool3d_bwd: shape (%d,%d,%d) not divisible by factors (%d,%d,%d)", D, H, W, fz, fy, fx);
     int64_t rows = (int64_t)N * (D / fz) * (H / fy);
     TEM_REQUIRE(rows < (1ll << 31), "tem_maxpool3d_bwd: too many rows");
-    const bool v4 = vec4_ok(C, {gy, x, gskip, gx}, {gy_ld, x_ld, gskip ? gskip_ld : 0, gx_ld}, st);
-    if (vec8_ok(C, {gy, x, gskip, gx}, {gy_ld, x_ld, gskip ? gskip_ld : 0, gx_ld}, st) && tem_option(TEM_OPT_POOL_VEC8)) {
-        if (fy == 2 && fx == 2 && (fz == 1 || fz == 2) && C <= 2048 && tem_option(TEM_OPT_POOL_VEC8) >= 2) {
-            const size_t ldsb = (gcoef || ycoef) ? (size_t)2 * C * sizeof(float4) : 0;
-            TEM_ST16_SWITCH(st, T, {
-                if (fz == 2)
-                    hipLaunchKernelGGL((k_maxpool_bwd16<2, T>), dim3((unsigned)rows), dim3(256), ldsb, (hipStream_t)stream, (const T*)gy,
-                                       gy_ld, (const T*)x, x_ld, (const T*)gskip, gskip_ld, relu_mask, (T*)gx, gx_ld, D, H, W, C, gcoef,
-                                       gcoef_ld, ycoef, amax);
-                else
-                    hipLaunchKernelGGL((k_maxpool_bwd16<1, T>), dim3((unsigned)rows), dim3(256), ldsb, (hipStream_t)stream, (const T*)gy,
-                                       gy_ld, (const T*)x, x_ld, (const T*)gskip, gskip_ld, relu_mask, (T*)gx, gx_ld, D, H, W, C, gcoef,
-                                       gcoef_ld, ycoef, amax);
-            });
-            TEM_CHECK_LAUNCH("tem_maxpool3d_bwd");
-            return TEM_OK;
-        }
+    const int path = maxpool_bwd_select(gy, gy_ld, x, x_ld, gskip, gskip_ld, gx, gx_ld, C, fz, fy, fx, st);
+    if (path == MP_PACKED16_FZ1 || path == MP_PACKED16_FZ2) {
+        const size_t ldsb = (gcoef || ycoef) ? (size_t)2 * C * sizeof(float4) : 0;
+        TEM_ST16_SWITCH(st, T, {
+            if (path == MP_PACKED16_FZ2)
+                hipLaunchKernelGGL((k_maxpool_bwd16<2, T>), dim3((unsigned)rows), dim3(256), ldsb, (hipStream_t)stream, (const T*)gy,
+                                   gy_ld, (const T*)x, x_ld, (const T*)gskip, gskip_ld, relu_mask, (T*)gx, gx_ld, D, H, W, C, gcoef,
+                                   gcoef_ld, ycoef, amax);
+            else
+                hipLaunchKernelGGL((k_maxpool_bwd16<1, T>), dim3((unsigned)rows), dim3(256), ldsb, (hipStream_t)stream, (const T*)gy,
+                                   gy_ld, (const T*)x, x_ld, (const T*)gskip, gskip_ld, relu_mask, (T*)gx, gx_ld, D, H, W, C, gcoef,
+                                   gcoef_ld, ycoef, amax);
+        });
+        TEM_CHECK_LAUNCH("tem_maxpool3d_bwd");
+        return TEM_OK;
+    }
+    if (path == MP_VEC8) {
         TEM_ST16_SWITCH(st, T, hipLaunchKernelGGL((k_maxpool_bwd<8, T>), dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream,
                                                   (const T*)gy, gy_ld, (const T*)x, x_ld, (const T*)gskip, gskip_ld, relu_mask, (T*)gx,
                                                   gx_ld, D, H, W, C, fz, fy, fx, gcoef, gcoef_ld, ycoef, amax));
@@ -493,7 +527,7 @@ static int maxpool3d_bwd_impl(const void* gy, int64_t gy_ld, const void* x, int6
         return TEM_OK;
     }
     TEM_ST_SWITCH(st, T, {
-        if (v4)
+        if (path == MP_VEC4)
             hipLaunchKernelGGL((k_maxpool_bwd<4, T>), dim3((unsigned)rows), dim3(256), 0, (hipStream_t)stream, (const T*)gy, gy_ld,
                                (const T*)x, x_ld, (const T*)gskip, gskip_ld, relu_mask, (T*)gx, gx_ld, D, H, W, C, fz, fy, fx, gcoef,
                                gcoef_ld, ycoef, amax);
@@ -538,6 +572,18 @@ extern "C" int tem_maxpool3d_bwd_st(const void* gy, int64_t gy_ld, const void* x
     TEM_REQUIRE(!ycoef || ((uintptr_t)ycoef % 16 == 0), "tem_maxpool3d_bwd_norm: ycoef must be 16-byte aligned");
     return maxpool3d_bwd_impl(gy, gy_ld, x, x_ld, gskip, gskip_ld, relu_mask, gx, gx_ld, N, D, H, W, C, fz, fy, fx, gcoef,
                               gcoef_ld, ycoef, out_amax, st, stream);
+}
+
+// Dispatch query: the kernel tem_maxpool3d_bwd_st takes for these arguments (has_gcoef / has_ycoef: with coefficient tables
+// that pass its checks), or -1 where the launch refuses them.  Launches nothing.
+extern "C" int tem_maxpool3d_bwd_path(const void* gy, int64_t gy_ld, const void* x, int64_t x_ld, const void* gskip, int64_t gskip_ld,
+                                      const void* gx, int64_t gx_ld, int N, int D, int H, int W, int C, int fz, int fy, int fx,
+                                      int has_gcoef, int has_ycoef, int st) {
+    (void)has_ycoef;   // no path depends on it, and dense [N][C][4] rows are always accepted
+    if (!(gy && x && gx && N > 0 && C > 0 && x_ld >= C && gy_ld >= C && gx_ld >= C && D > 0 && H > 0 && W > 0)) return -1;
+    if (!(fz > 0 && fy > 0 && fx > 0) || st < 0 || st > 2 || D % fz || H % fy || W % fx) return -1;
+    if ((int64_t)N * (D / fz) * (H / fy) >= (1ll << 31) || (has_gcoef && !gskip)) return -1;
+    return maxpool_bwd_select(gy, gy_ld, x, x_ld, gskip, gskip_ld, gx, gx_ld, C, fz, fy, fx, st);
 }
 
 // ---------------------------------------------------------------------------
