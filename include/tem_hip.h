@@ -664,6 +664,28 @@ int tem_dice_sums_pair(const float* p, int64_t p_sn, int64_t p_sc, int64_t p_sv,
 int tem_pseudo_label_st(const void* x, void* labels, void* mask, int N, int64_t S, int act, int mask_mode, int mask_sample,
                         float t_hi, float t_lo, int st, tem_stream_t stream);
 
+/* ---- self-training: FixMatch's distribution alignment (csrc/selftrain.hip) -------------------------------------------
+ * What FixMatchTrainer.get_distribution_alignment does on every training step (reference self_training/fix_match.py:164-181):
+ * binarise the labels at the threshold, count the two classes (torch.unique(..., return_counts=True): a sort and a
+ * device-to-host synchronisation), scale every label by source_k / (count_k / n) of its own class, clip to [0, 1].  Two
+ * launches, no atomics, no memset, nothing crosses the host.  labels: n elements, dense, storage type st, processed flat.
+ *
+ * tem_label_count_st (reference :171-172): partials[b] = how many labels of block b's share are >= threshold, as 64-bit
+ *   integers; EVERY block writes its partial, so the buffer needs no clearing.  `parts` must equal
+ *   tem_label_count_parts(n, st) (at most 2048; 0 for arguments the launch refuses).  The compare runs on the STORED value
+ *   against `threshold`, which the caller has rounded to the storage type; NaN counts as below.
+ * tem_distribution_align_st (reference :173-179): every block sums the partials to c1, c0 = n - c1, forms
+ *   r_k = source_k / ((float)c_k / (float)n) in fp32 in the reference's order, and writes
+ *   out = clip(label * (label < threshold ? r0 : r1), 0, 1): the product in fp32, rounded ONCE to the storage type (the
+ *   reference multiplies a 16-bit tensor by the fp32 ratio in fp32 too; tests/golden/g18_fixmatch.npz pins it).  NaN passes the
+ *   clip, as through torch.clip.  A class with c_k = 0 is never selected by a number; its ratio is 0, not inf.  With one
+ *   class present the reference's ratio collapses to source / 1, which this formula gives as well.  out must not overlap
+ *   labels; source0, source1 finite and > 0. */
+int tem_label_count_parts(int64_t n, int st);
+int tem_label_count_st(const void* labels, int64_t n, float threshold, void* partials, int parts, int st, tem_stream_t stream);
+int tem_distribution_align_st(const void* labels, void* out, int64_t n, float threshold, float source0, float source1,
+                              const void* partials, int parts, int st, tem_stream_t stream);
+
 /* ---- optimizer -------------------------------------------------------------
  * torch.optim.AdamW step as configured by default_segmentation_trainer
  * (segmentation.py:543): decoupled weight decay, bias correction, eps outside

@@ -112,6 +112,10 @@ SIGNATURES = {
                                    c_vp, c_vp, c_i64, c_vp]),
     # (x, labels, mask, N, S, act, mask_mode, mask_sample, t_hi, t_lo, st, stream)
     "tem_pseudo_label_st": (c_int, [c_vp, c_vp, c_vp, c_int, c_i64, c_int, c_int, c_int, c_float, c_float, c_int, c_vp]),
+    "tem_label_count_parts": (c_int, [c_i64, c_int]),
+    # (labels, n, threshold, partials, parts, st, stream) / (labels, out, n, threshold, source0, source1, partials, parts, st, stream)
+    "tem_label_count_st": (c_int, [c_vp, c_i64, c_float, c_vp, c_int, c_int, c_vp]),
+    "tem_distribution_align_st": (c_int, [c_vp, c_vp, c_i64, c_float, c_float, c_float, c_vp, c_int, c_int, c_vp]),
     "tem_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_float, c_float, c_float, c_i64,
                                c_float, c_vp]),
     "tem_adamw_hyper": (c_int, [c_vp, c_float, c_float, c_float, c_float, c_float, c_i64, c_float]),

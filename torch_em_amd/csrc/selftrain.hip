@@ -9,6 +9,8 @@
 // Compare semantics (pinned by tests/golden/g17_selftrain.npz against the reference on the CPU): the compare runs on the STORED
 // label -- the sigmoid is computed in fp32 and rounded once to the storage type first -- against the threshold rounded to that
 // type; the caller passes both thresholds already rounded (1 - t formed in double before the rounding).
+//
+// Below it: the distribution alignment of FixMatch (class count and scale-and-clip pass), in the same style.
 #include "tem_common.h"
 #include "tem_act.h"
 
@@ -132,5 +134,120 @@ extern "C" int tem_pseudo_label_st(const void* x, void* labels, void* mask, int 
         }
     });
     TEM_CHECK_LAUNCH("tem_pseudo_label_st");
+    return TEM_OK;
+}
+
+// ---- distribution alignment of FixMatch (reference self_training/fix_match.py:164-181: get_distribution_alignment) ----------
+// The reference binarises the labels at the threshold, counts the two classes with torch.unique (a sort and a device-to-host
+// synchronisation for the output size), scales each label by source_k / (count_k / n) of ITS class and clips to [0, 1].  Here:
+// one integer count (k_label_count: every block writes its 64-bit partial, no atomics, no memset) and one scale-and-clip pass
+// (k_distribution_align: every block sums the partials itself, so nothing crosses the host).  Compare semantics as above: on
+// the stored value against the threshold rounded to the storage type; NaN is "below" for the count (l >= t is false) and takes
+// the upper class's ratio in the pass (l < t is false), as in the reference -- it stays NaN either way.
+#define DA_MAX_PARTS 2048   // the grid cap of the count; k_distribution_align sums at most this many partials
+#define DA_MAX_N ((int64_t)1 << 40)   // per-thread and per-wave counts stay in 32 bits far beyond this
+
+static int da_parts(int64_t n, int st) { return tem_grid_1d(tem_cdiv(n, 16 / tem_st_size(st)), 256, DA_MAX_PARTS); }
+
+// the block's sum of one 64-bit value per thread (256 threads), in every thread: over the wave, then over the four waves
+// (each kernel calls it once: sh is written once per block)
+__device__ __forceinline__ unsigned long long da_block_sum(unsigned long long v, unsigned long long* sh /*[4]*/) {
+#pragma unroll
+    for (int o = 32; o > 0; o >>= 1) {   // a 64-bit value travels as two 32-bit shuffles
+        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
+        v += ((unsigned long long)hi << 32) | lo;
+    }
+    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
+    __syncthreads();
+    return sh[0] + sh[1] + sh[2] + sh[3];
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_label_count(const T* __restrict__ x, int64_t n, int64_t nvec, float thr,
+                                                     unsigned long long* __restrict__ partials) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    __shared__ unsigned long long sh[4];
+    const int64_t step = (int64_t)gridDim.x * 256, first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    unsigned cnt = 0;
+    for (int64_t q = first; q < nvec; q += step) {
+        float l[VEC];
+        pl_load<T, VEC>(x + q * VEC, l);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) cnt += l[k] >= thr ? 1u : 0u;
+    }
+    for (int64_t i = nvec * VEC + first; i < n; i += step) cnt += act_ld1(x + i) >= thr ? 1u : 0u;
+    const unsigned long long total = da_block_sum(cnt, sh);
+    if (threadIdx.x == 0) partials[blockIdx.x] = total;   // every block, zero included: the buffer is never cleared
+}
+
+template <typename T> __device__ __forceinline__ float da_one(float l, float thr, float r0, float r1) {
+    const float v = l * (l < thr ? r0 : r1);
+    // torch.clip lets NaN through (fminf / fmaxf would not): both compares are false for NaN
+    return v < 0.f ? 0.f : (v > 1.f ? 1.f : v);
+}
+
+template <typename T>
+__global__ __launch_bounds__(256) void k_distribution_align(const T* __restrict__ x, T* __restrict__ out, int64_t n, int64_t nvec,
+                                                            const unsigned long long* __restrict__ partials, int parts, float thr,
+                                                            float s0, float s1) {
+    constexpr int VEC = 16 / (int)sizeof(T);
+    __shared__ unsigned long long sh[4];
+    unsigned long long mine = 0;
+    for (int i = threadIdx.x; i < parts; i += 256) mine += partials[i];
+    const unsigned long long c1 = da_block_sum(mine, sh), c0 = (unsigned long long)n - c1;
+    // the reference's order: counts / counts.sum() in fp32, then source / that.  An empty class is never selected -- with a
+    // NaN label it can be (NaN is not < thr); the label is NaN then whatever the ratio -- so its ratio is a plain 0, not inf
+    const float fn = (float)n;
+    const float r0 = c0 ? s0 / ((float)c0 / fn) : 0.f, r1 = c1 ? s1 / ((float)c1 / fn) : 0.f;
+    const int64_t step = (int64_t)gridDim.x * 256, first = (int64_t)blockIdx.x * 256 + threadIdx.x;
+    for (int64_t q = first; q < nvec; q += step) {
+        float l[VEC];
+        pl_load<T, VEC>(x + q * VEC, l);
+#pragma unroll
+        for (int k = 0; k < VEC; ++k) l[k] = da_one<T>(l[k], thr, r0, r1);
+        pl_store<T, VEC>(out + q * VEC, l);
+    }
+    for (int64_t i = nvec * VEC + first; i < n; i += step) act_st1(out + i, da_one<T>(act_ld1(x + i), thr, r0, r1));
+}
+
+extern "C" int tem_label_count_parts(int64_t n, int st) {
+    if (n <= 0 || n > DA_MAX_N || st < TEM_ST_F32 || st > TEM_ST_BF16) return 0;
+    return da_parts(n, st);
+}
+
+extern "C" int tem_label_count_st(const void* labels, int64_t n, float threshold, void* partials, int parts, int st,
+                                  tem_stream_t stream) {
+    TEM_REQUIRE(labels && partials && n > 0 && n <= DA_MAX_N, "tem_label_count_st: bad arguments (n=%lld)", (long long)n);
+    TEM_REQUIRE(st >= TEM_ST_F32 && st <= TEM_ST_BF16, "tem_label_count_st: unknown storage type %d", st);
+    TEM_REQUIRE(parts == da_parts(n, st), "tem_label_count_st: %d partials, tem_label_count_parts() says %d", parts, da_parts(n, st));
+    TEM_REQUIRE((uintptr_t)partials % 8 == 0, "tem_label_count_st: partials must be 8-byte aligned");
+    TEM_ST_SWITCH(st, T, {
+        constexpr int VEC = 16 / (int)sizeof(T);
+        const int64_t nvec = (uintptr_t)labels % 16 == 0 ? n / VEC : 0;
+        hipLaunchKernelGGL((k_label_count<T>), dim3(parts), dim3(256), 0, (hipStream_t)stream, (const T*)labels, n, nvec, threshold,
+                           (unsigned long long*)partials);
+    });
+    TEM_CHECK_LAUNCH("tem_label_count_st");
+    return TEM_OK;
+}
+
+extern "C" int tem_distribution_align_st(const void* labels, void* out, int64_t n, float threshold, float source0, float source1,
+                                         const void* partials, int parts, int st, tem_stream_t stream) {
+    TEM_REQUIRE(labels && out && partials && n > 0 && n <= DA_MAX_N, "tem_distribution_align_st: bad arguments (n=%lld)", (long long)n);
+    TEM_REQUIRE(st >= TEM_ST_F32 && st <= TEM_ST_BF16, "tem_distribution_align_st: unknown storage type %d", st);
+    TEM_REQUIRE(parts == da_parts(n, st), "tem_distribution_align_st: %d partials, tem_label_count_parts() says %d", parts, da_parts(n, st));
+    TEM_REQUIRE((uintptr_t)partials % 8 == 0, "tem_distribution_align_st: partials must be 8-byte aligned");
+    TEM_REQUIRE(source0 > 0.f && source1 > 0.f && source0 <= 3.0e38f && source1 <= 3.0e38f,
+                "tem_distribution_align_st: the source distribution must be finite and positive");
+    const int64_t bytes = n * tem_st_size(st);
+    TEM_REQUIRE((const char*)out + bytes <= (const char*)labels || (const char*)labels + bytes <= (const char*)out,
+                "tem_distribution_align_st: out must not overlap the labels");
+    TEM_ST_SWITCH(st, T, {
+        constexpr int VEC = 16 / (int)sizeof(T);
+        const int64_t nvec = ((uintptr_t)labels % 16 == 0 && (uintptr_t)out % 16 == 0) ? n / VEC : 0;
+        hipLaunchKernelGGL((k_distribution_align<T>), dim3(da_parts(n, st)), dim3(256), 0, (hipStream_t)stream, (const T*)labels, (T*)out, n,
+                           nvec, (const unsigned long long*)partials, parts, threshold, source0, source1);
+    });
+    TEM_CHECK_LAUNCH("tem_distribution_align_st");
     return TEM_OK;
 }

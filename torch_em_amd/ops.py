@@ -7,6 +7,7 @@ dimension `ld`) may exceed C so that a tensor can be a channel slice of a concat
 There is no CPU fallback: CPU tensors raise.
 """
 import ctypes
+import math
 from typing import Optional, Sequence, Tuple
 
 import torch
@@ -1005,6 +1006,80 @@ def pseudo_label(x: torch.Tensor, activation: Optional[str] = None, confidence_t
                                                -1 if mask_sample is None else int(mask_sample), t_hi, t_lo, _st(x), _stream(x)),
                "tem_pseudo_label_st")
     return (x if labels is None else labels), mask
+
+
+def _da_check(name: str, labels, threshold):
+    """argument checks shared by label_count_partials / distribution_align: all of them before the library is touched"""
+    if not isinstance(labels, torch.Tensor) or not labels.is_cuda:
+        raise ValueError(f"{name}: expected a tensor on the GPU (there is no CPU path)")
+    if labels.dtype not in _ST:
+        raise ValueError(f"{name}: expected float32, float16 or bfloat16, got {labels.dtype}")
+    if labels.numel() == 0:
+        raise ValueError(f"{name}: expected a non-empty tensor, got shape {tuple(labels.shape)}")
+    if not _is_dense(labels):
+        raise ValueError(f"{name}: the labels must be dense (any permutation of a contiguous tensor), got strides {labels.stride()}")
+    if not math.isfinite(float(threshold)):
+        raise ValueError(f"{name}: the label threshold must be finite, got {threshold}")
+
+
+def source_shares(source_distribution) -> Tuple[float, float]:
+    """the two class shares of a `source_distribution` (a sequence or a tensor) as Python floats; ValueError unless there are
+    exactly two finite positive ones (the reference indexes [0] and [1] of the ratio).  Touches no device library."""
+    src = source_distribution
+    if isinstance(src, torch.Tensor):
+        src = src.detach().cpu().tolist()
+    try:
+        src = [float(v) for v in src]
+    except TypeError:
+        raise ValueError(f"distribution_align: source_distribution must hold two numbers, got {source_distribution!r}") from None
+    if len(src) != 2 or not all(math.isfinite(v) and v > 0 for v in src):
+        raise ValueError(f"distribution_align: source_distribution must hold exactly two finite positive entries, got {src}")
+    return src[0], src[1]
+
+
+def _label_count(lib, labels, threshold):
+    """`threshold`: already rounded to the labels' dtype"""
+    n = labels.numel()
+    parts = lib.tem_label_count_parts(n, _st(labels))
+    if parts <= 0:
+        raise ValueError(f"label_count: {n} elements are out of range")
+    partials = torch.empty((parts,), dtype=torch.int64, device=labels.device)
+    _lib.check(lib.tem_label_count_st(_p(labels), n, threshold, _p(partials), parts, _st(labels), _stream(labels)),
+               "tem_label_count_st")
+    return partials
+
+
+def label_count_partials(labels: torch.Tensor, threshold: float = 0.5) -> torch.Tensor:
+    """int64 [tem_label_count_parts(n)] on the device: per-block counts of `labels >= threshold` (tem_label_count_st; the
+    compare runs in the labels' dtype against the rounded threshold, NaN counts as below).  Their sum is the size of the
+    upper class; `distribution_align` hands them to its second launch without reading them."""
+    _da_check("label_count_partials", labels, threshold)
+    return _label_count(_lib.load(), labels, round_to(threshold, labels.dtype))
+
+
+def distribution_align(labels: torch.Tensor, source_distribution, label_threshold: float = 0.5, out=None) -> torch.Tensor:
+    """FixMatch's distribution alignment (reference self_training/fix_match.py:164-181) in two launches and without a host
+    round trip: clip(labels * source_k / (count_k / n), 0, 1) with k the side of `label_threshold` the label is on.  -> a new
+    tensor in the dtype and memory layout of `labels` (float32 / float16 / bfloat16, dense); `labels` is not written.
+    `source_distribution`: two finite positive numbers (a sequence or a tensor; a device tensor is read once -- pass floats
+    inside a captured region).  `out=` is a TEST HOOK (no library caller uses it): write into this tensor (the shape, strides,
+    dtype and device of `labels`, other storage), so a test can lay the output out between guard zones."""
+    _da_check("distribution_align", labels, label_threshold)
+    s0, s1 = source_shares(source_distribution)
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != labels.dtype or out.shape != labels.shape
+                or out.stride() != labels.stride() or out.device != labels.device):
+            raise ValueError("distribution_align: `out` must be laid out like the labels")
+        nbytes = labels.numel() * labels.element_size()
+        if out.data_ptr() < labels.data_ptr() + nbytes and labels.data_ptr() < out.data_ptr() + nbytes:
+            raise ValueError("distribution_align: `out` must not overlap the labels")
+    lib = _lib.load()
+    threshold = round_to(label_threshold, labels.dtype)
+    partials = _label_count(lib, labels, threshold)
+    res = torch.empty_like(labels) if out is None else out
+    _lib.check(lib.tem_distribution_align_st(_p(labels), _p(res), labels.numel(), threshold, s0, s1, _p(partials),
+                                             partials.numel(), _st(labels), _stream(labels)), "tem_distribution_align_st")
+    return res
 
 
 # ---------------------------------------------------------------- clDice ----

@@ -20,6 +20,8 @@ What runs differently:
 The semi-supervised step runs the student twice with gradients before one `backward()`: two `UNetFunction` nodes, each with
 its own gradient arena, which autograd adds.  `FusedAdamW` then takes its per-tensor path for that step; the unsupervised
 step has one node and stays on the one-launch path.
+
+`SelfTrainingTrainer` holds what this trainer shares with `FixMatchTrainer` (fix_match.py).
 """
 import os
 import pickle
@@ -47,25 +49,22 @@ def _to(batch, device):
     return batch.to(device, non_blocking=True)
 
 
-class MeanTeacherTrainer(DefaultTrainer):
-    """See the module docstring.  Loaders: `unsupervised_train_loader` (two views of the same input per batch, or one raw
-    batch with `view_transforms`), optional `supervised_train_loader` (input, labels), and at least one of
-    `unsupervised_val_loader` / `supervised_val_loader`.  Callables: `pseudo_labeler(teacher, input) -> (labels, filter)`,
-    `unsupervised_loss(model, input, labels, filter)`, `supervised_loss(model, input, labels)`, and at least one of the
-    `*_loss_and_metric` variants returning (loss, metric).  `reinit_teacher=None`: reinitialise iff there is supervised data.
-    `sampler(pseudo_labels, filter) -> bool` may reject a batch."""
+class SelfTrainingTrainer(DefaultTrainer):
+    """What `MeanTeacherTrainer` and `FixMatchTrainer` share: loader and loss selection, the checkpoint record and
+    `from_checkpoint`, the batches (`_raw`, `_views`), the logger calls, the training loops around `_unsupervised_step` /
+    `_semisupervised_step` and the validation loops.  A subclass provides the two steps and says through the hooks below which
+    model labels, what follows a step and what its record holds."""
+    _PARTS = _PARTS                  # callables of the constructor that go into the checkpoint record
+    _VAL_LOADER_FROM_TRAIN = False   # `val_loader` when there is an unsupervised validation loader: that loader, or the TRAIN loader
+    _STEP_DESCRIPTION = ""           # what the step runs, for the refusal of hip_graph=True
 
-    def __init__(self, model: torch.nn.Module, unsupervised_train_loader, unsupervised_loss: Callable,
-                 pseudo_labeler: Callable, supervised_train_loader=None, unsupervised_val_loader=None,
-                 supervised_val_loader=None, supervised_loss: Optional[Callable] = None,
-                 unsupervised_loss_and_metric: Optional[Callable] = None,
-                 supervised_loss_and_metric: Optional[Callable] = None, logger=None, momentum: float = 0.999,
-                 reinit_teacher: Optional[bool] = None, sampler: Optional[Callable] = None, view_transforms=None, **kwargs):
+    def _select(self, unsupervised_train_loader, supervised_train_loader, unsupervised_val_loader, supervised_val_loader,
+                supervised_loss, unsupervised_loss_and_metric, supervised_loss_and_metric, kwargs):
+        """The constructor logic of both references -> (train_loader, val_loader).  `kwargs` loses what a deserialised
+        `init` may carry."""
         if kwargs.get("hip_graph"):
-            raise NotImplementedError("MeanTeacherTrainer: hip_graph=True is not supported -- the captured training step "
-                                      "(torch_em_amd/graph.py) knows one model and one loss; this step runs a teacher, a "
-                                      "pseudo labeler and up to two student passes")
-        self.sampler = sampler
+            raise NotImplementedError(f"{type(self).__name__}: hip_graph=True is not supported -- the captured training step "
+                                      f"(torch_em_amd/graph.py) knows one model and one loss; {self._STEP_DESCRIPTION}")
         if supervised_train_loader is None:
             train_loader = unsupervised_train_loader
             self._train_epoch_impl = self._train_epoch_unsupervised
@@ -78,48 +77,53 @@ class MeanTeacherTrainer(DefaultTrainer):
         self.unsupervised_train_loader, self.supervised_train_loader = unsupervised_train_loader, supervised_train_loader
         assert supervised_val_loader is not None or unsupervised_val_loader is not None
         self.supervised_val_loader, self.unsupervised_val_loader = supervised_val_loader, unsupervised_val_loader
-        # as the reference (`:117-120`): with an unsupervised validation loader, `val_loader` is the unsupervised TRAIN loader
-        val_loader = supervised_val_loader if unsupervised_val_loader is None else unsupervised_train_loader
+        if unsupervised_val_loader is None:
+            val_loader = supervised_val_loader
+        else:
+            val_loader = unsupervised_train_loader if self._VAL_LOADER_FROM_TRAIN else unsupervised_val_loader
         assert supervised_loss_and_metric is not None or unsupervised_loss_and_metric is not None
         self.supervised_loss_and_metric = supervised_loss_and_metric
         self.unsupervised_loss_and_metric = unsupervised_loss_and_metric
         for key in ("train_loader", "val_loader", "metric", "loss"):   # may come back from a deserialised `init`
             kwargs.pop(key, None)
         kwargs["hip_graph"] = False
-        super().__init__(model=model, train_loader=train_loader, val_loader=val_loader, loss=Dummy(), metric=Dummy(),
-                         logger=logger, **kwargs)
-        self.unsupervised_loss, self.supervised_loss = unsupervised_loss, supervised_loss
-        self.pseudo_labeler, self.momentum = pseudo_labeler, momentum
+        return train_loader, val_loader
+
+    def _set_view_transforms(self, view_transforms):
         if view_transforms is not None and len(view_transforms) != 2:
             raise ValueError("view_transforms: expected (teacher_augmentation, student_augmentation)")
         self.view_transforms = view_transforms
-        self.reinit_teacher = (supervised_train_loader is not None) if reinit_teacher is None else reinit_teacher
-        with torch.no_grad():
-            self.teacher = deepcopy(self.model)
-            if self.reinit_teacher:
-                for layer in self.teacher.children():   # direct children only (for the U-Nets: out_conv), as the reference
-                    if hasattr(layer, "reset_parameters"):
-                        layer.reset_parameters()
-            for param in self.teacher.parameters():
-                param.requires_grad = False
-        self._arena1 = self._arena2 = None
 
-    # ---- EMA teacher ------------------------------------------------------------------------
-    def _current_momentum(self) -> float:
-        """A reinitialised teacher follows the student quickly at first: min(1 - 1 / (iteration + 1), momentum)."""
-        if self.reinit_teacher:
-            return min(1 - 1 / (self._iteration + 1), self.momentum)
-        return self.momentum
+    # ---- hooks ----------------------------------------------------------------------------------
+    def _labeling_model(self):
+        """the model the pseudo labeler runs"""
+        raise NotImplementedError
 
-    def _momentum_update(self):
-        ema_teacher_update(self, self.teacher, float(self._current_momentum()))
+    def _after_step(self):
+        """between a training step (and its logger calls) and the iteration counter"""
+
+    def _after_unsupervised_validation(self, metric_val):
+        pass
+
+    def _record_extra(self) -> dict:
+        """the subclass's own constructor arguments, for the checkpoint's `self_training` record"""
+        return {}
+
+    @classmethod
+    def _ctor_extra(cls, record) -> dict:
+        """... and back: record -> constructor keywords"""
+        return {}
+
+    def _extra_state(self) -> dict:
+        """top-level checkpoint entries next to `init`"""
+        return {}
 
     # ---- checkpoints --------------------------------------------------------------------------
     def _self_training_record(self):
         """What `from_checkpoint` needs beyond DefaultTrainer's record: the callables (pickled when they can be) and the
         datasets / batch sizes of the four loaders."""
-        rec, lost = {"momentum": self.momentum, "reinit_teacher": self.reinit_teacher}, []
-        for key in _PARTS:
+        rec, lost = self._record_extra(), []
+        for key in self._PARTS:
             obj = getattr(self, key)
             try:
                 pickle.dumps(obj)
@@ -133,38 +137,23 @@ class MeanTeacherTrainer(DefaultTrainer):
             rec[key + "_kwargs"] = {"batch_size": getattr(loader, "batch_size", None)}
         rec["unpicklable"] = lost
         if lost:
-            warnings.warn(f"MeanTeacherTrainer: {lost} cannot be pickled into the checkpoint; from_checkpoint() will ask for them")
+            warnings.warn(f"{type(self).__name__}: {lost} cannot be pickled into the checkpoint; from_checkpoint() will ask for them")
         return rec
 
     def save_checkpoint(self, name, current_metric, best_metric, **extra_save_dict):
         dummy = f"{Dummy.__module__}.{Dummy.__name__}"
-        extra_state = {
-            "teacher_state": self.teacher.state_dict(),
-            "init": {
-                "train_loader_kwargs": {"batch_size": getattr(self.train_loader, "batch_size", None)},
-                "train_dataset": getattr(self.train_loader, "dataset", None),
-                "val_loader_kwargs": {"batch_size": getattr(self.val_loader, "batch_size", None)},
-                "val_dataset": getattr(self.val_loader, "dataset", None),
-                "loss_class": dummy, "loss_kwargs": {}, "metric_class": dummy, "metric_kwargs": {},
-                "trainer_class": f"{type(self).__module__}.{type(self).__name__}",
-                "self_training": self._self_training_record(),
-            },
+        extra_state = self._extra_state()
+        extra_state["init"] = {
+            "train_loader_kwargs": {"batch_size": getattr(self.train_loader, "batch_size", None)},
+            "train_dataset": getattr(self.train_loader, "dataset", None),
+            "val_loader_kwargs": {"batch_size": getattr(self.val_loader, "batch_size", None)},
+            "val_dataset": getattr(self.val_loader, "dataset", None),
+            "loss_class": dummy, "loss_kwargs": {}, "metric_class": dummy, "metric_kwargs": {},
+            "trainer_class": f"{type(self).__module__}.{type(self).__name__}",
+            "self_training": self._self_training_record(),
         }
         extra_state.update(**extra_save_dict)
         super().save_checkpoint(name, current_metric, best_metric, **extra_state)
-
-    def load_checkpoint(self, checkpoint="best"):
-        save_dict = super().load_checkpoint(checkpoint)
-        if save_dict is not None:
-            self.teacher.load_state_dict(save_dict["teacher_state"])
-            self.teacher.to(self.device)
-            self._arena2 = None
-        return save_dict
-
-    def _initialize(self, iterations, load_from_checkpoint, epochs=None):
-        best_metric = super()._initialize(iterations, load_from_checkpoint, epochs)
-        self.teacher.to(self.device)
-        return best_metric
 
     @classmethod
     def from_checkpoint(cls, checkpoint_folder, name="best", device=None, raw_transform=_FROM_CHECKPOINT,
@@ -188,7 +177,7 @@ class MeanTeacherTrainer(DefaultTrainer):
         sched = None
         if init.get("lr_scheduler_class"):
             sched = _import_class(init["lr_scheduler_class"])(optimizer, **init["lr_scheduler_kwargs"])
-        parts = {k: given.pop(k, st[k]) for k in _PARTS}
+        parts = {k: given.pop(k, st[k]) for k in cls._PARTS}
         for key in _LOADERS:
             loader = given.pop(key, None)
             if loader is None and st[key + "_dataset"] is not None:
@@ -196,13 +185,13 @@ class MeanTeacherTrainer(DefaultTrainer):
             parts[key] = loader
         if given:
             raise TypeError(f"from_checkpoint: unexpected arguments {sorted(given)}")
-        trainer = cls(model=model, momentum=st["momentum"], reinit_teacher=st["reinit_teacher"], name=init["name"],
+        trainer = cls(model=model, name=init["name"],
                       optimizer=optimizer, device=device or init["device"], lr_scheduler=sched,
                       log_image_interval=init["log_image_interval"], mixed_precision=init["mixed_precision"],
                       early_stopping=init["early_stopping"], logger=None, id_=init["id_"], save_root=init["save_root"],
                       rank=init.get("rank"), mixed_precision_dtype=init["mixed_precision_dtype"]
                       if init.get("mixed_precision_explicit", False) else None, prefetch=init.get("prefetch", True),
-                      **transforms, **parts)
+                      **cls._ctor_extra(st), **transforms, **parts)
         trainer._initialize(0, save_dict)
         trainer._is_initialized = True
         return trainer
@@ -222,7 +211,7 @@ class MeanTeacherTrainer(DefaultTrainer):
             return self._raw(xu1), self._raw(xu2)
         if isinstance(batch, (list, tuple)):
             if len(batch) != 1:
-                raise ValueError("MeanTeacherTrainer: with view_transforms the unsupervised loaders yield one raw batch")
+                raise ValueError(f"{type(self).__name__}: with view_transforms the unsupervised loaders yield one raw batch")
             batch = batch[0]
         x = self._raw(batch)
         teacher_aug, student_aug = self.view_transforms
@@ -230,7 +219,7 @@ class MeanTeacherTrainer(DefaultTrainer):
 
     def _pseudo_labels(self, teacher_input):
         with self._precision(), torch.no_grad():
-            return self.pseudo_labeler(self.teacher, teacher_input)
+            return self.pseudo_labeler(self._labeling_model(), teacher_input)
 
     def _log_common(self):
         self.logger.log_lr(self._iteration, [pm["lr"] for pm in self.optimizer.param_groups][0])
@@ -247,31 +236,6 @@ class MeanTeacherTrainer(DefaultTrainer):
     def _train_epoch(self, progress):
         return self._train_epoch_impl(progress)
 
-    def _unsupervised_step(self, xu1, xu2):
-        """teacher forward + labeler, student forward / backward on the pseudo labels, optimizer step (the caller updates the
-        teacher) -> (loss, pseudo_labels, label_filter), or None when the sampler rejects the batch (nothing ran but the teacher)"""
-        pseudo_labels, label_filter = self._pseudo_labels(xu1)
-        if self.sampler is not None and not self.sampler(pseudo_labels, label_filter):
-            return None
-        self.optimizer.zero_grad()
-        with self._precision():
-            loss = self.unsupervised_loss(self.model, xu2, pseudo_labels, label_filter)
-            self._backprop(loss)
-        return loss, pseudo_labels, label_filter
-
-    def _semisupervised_step(self, xs, ys, xu1, xu2):
-        """supervised and unsupervised student passes, ONE backward pass over the mean of the two losses
-        -> (supervised loss, unsupervised loss, combined loss, pseudo_labels, label_filter)"""
-        self.optimizer.zero_grad()
-        with self._precision():
-            supervised_loss = self.supervised_loss(self.model, xs, ys)
-        pseudo_labels, label_filter = self._pseudo_labels(xu1)
-        with self._precision():
-            unsupervised_loss = self.unsupervised_loss(self.model, xu2, pseudo_labels, label_filter)
-            loss = (supervised_loss + unsupervised_loss) / 2
-            self._backprop(loss)
-        return supervised_loss, unsupervised_loss, loss, pseudo_labels, label_filter
-
     def _train_epoch_unsupervised(self, progress):
         self.model.train()
         n_iter, t0 = 0, time.time()
@@ -285,8 +249,7 @@ class MeanTeacherTrainer(DefaultTrainer):
                 self.logger.log_train_unsupervised(self._iteration, loss, xu1, xu2, self._log_pred(xu2), pseudo_labels,
                                                    label_filter)
                 self._log_common()
-            with torch.no_grad():
-                self._momentum_update()
+            self._after_step()
             self._iteration += 1
             n_iter += 1
             if self._iteration >= self.max_iteration:
@@ -309,8 +272,7 @@ class MeanTeacherTrainer(DefaultTrainer):
                                                    label_filter)
                 self.logger.log_combined_loss(self._iteration, loss)
                 self._log_common()
-            with torch.no_grad():
-                self._momentum_update()
+            self._after_step()
             self._iteration += 1
             n_iter += 1
             if self._iteration >= self.max_iteration:
@@ -340,7 +302,7 @@ class MeanTeacherTrainer(DefaultTrainer):
         for batch in self.unsupervised_val_loader:
             x1, x2 = self._views(batch)
             with self._precision():
-                pseudo_labels, label_filter = self.pseudo_labeler(self.teacher, x1)
+                pseudo_labels, label_filter = self.pseudo_labeler(self._labeling_model(), x1)
                 loss, metric = self.unsupervised_loss_and_metric(self.model, x2, pseudo_labels, label_filter)
             loss_val = loss.detach() if loss_val is None else loss_val + loss.detach()
             metric_val = metric.detach() if metric_val is None else metric_val + metric.detach()
@@ -351,7 +313,7 @@ class MeanTeacherTrainer(DefaultTrainer):
                 pred = self.model(x2)
             self.logger.log_validation_unsupervised(self._iteration, metric_val, loss_val, x1, x2, pred, pseudo_labels,
                                                     label_filter)
-        self.pseudo_labeler.step(metric_val, self._epoch)   # the threshold schedule advances with the validation metric
+        self._after_unsupervised_validation(metric_val)
         return metric_val
 
     def _validate(self):
@@ -364,3 +326,111 @@ class MeanTeacherTrainer(DefaultTrainer):
         if sup is None:
             return unsup
         return (sup + unsup) / 2
+
+
+class MeanTeacherTrainer(SelfTrainingTrainer):
+    """See the module docstring.  Loaders: `unsupervised_train_loader` (two views of the same input per batch, or one raw
+    batch with `view_transforms`), optional `supervised_train_loader` (input, labels), and at least one of
+    `unsupervised_val_loader` / `supervised_val_loader`.  Callables: `pseudo_labeler(teacher, input) -> (labels, filter)`,
+    `unsupervised_loss(model, input, labels, filter)`, `supervised_loss(model, input, labels)`, and at least one of the
+    `*_loss_and_metric` variants returning (loss, metric).  `reinit_teacher=None`: reinitialise iff there is supervised data.
+    `sampler(pseudo_labels, filter) -> bool` may reject a batch."""
+    # as the reference (`:117-120`): with an unsupervised validation loader, `val_loader` is the unsupervised TRAIN loader
+    _VAL_LOADER_FROM_TRAIN = True
+    _STEP_DESCRIPTION = "this step runs a teacher, a pseudo labeler and up to two student passes"
+
+    def __init__(self, model: torch.nn.Module, unsupervised_train_loader, unsupervised_loss: Callable,
+                 pseudo_labeler: Callable, supervised_train_loader=None, unsupervised_val_loader=None,
+                 supervised_val_loader=None, supervised_loss: Optional[Callable] = None,
+                 unsupervised_loss_and_metric: Optional[Callable] = None,
+                 supervised_loss_and_metric: Optional[Callable] = None, logger=None, momentum: float = 0.999,
+                 reinit_teacher: Optional[bool] = None, sampler: Optional[Callable] = None, view_transforms=None, **kwargs):
+        self.sampler = sampler
+        train_loader, val_loader = self._select(unsupervised_train_loader, supervised_train_loader, unsupervised_val_loader,
+                                                supervised_val_loader, supervised_loss, unsupervised_loss_and_metric,
+                                                supervised_loss_and_metric, kwargs)
+        super().__init__(model=model, train_loader=train_loader, val_loader=val_loader, loss=Dummy(), metric=Dummy(),
+                         logger=logger, **kwargs)
+        self.unsupervised_loss, self.supervised_loss = unsupervised_loss, supervised_loss
+        self.pseudo_labeler, self.momentum = pseudo_labeler, momentum
+        self._set_view_transforms(view_transforms)
+        self.reinit_teacher = (supervised_train_loader is not None) if reinit_teacher is None else reinit_teacher
+        with torch.no_grad():
+            self.teacher = deepcopy(self.model)
+            if self.reinit_teacher:
+                for layer in self.teacher.children():   # direct children only (for the U-Nets: out_conv), as the reference
+                    if hasattr(layer, "reset_parameters"):
+                        layer.reset_parameters()
+            for param in self.teacher.parameters():
+                param.requires_grad = False
+        self._arena1 = self._arena2 = None
+
+    # ---- EMA teacher ------------------------------------------------------------------------
+    def _current_momentum(self) -> float:
+        """A reinitialised teacher follows the student quickly at first: min(1 - 1 / (iteration + 1), momentum)."""
+        if self.reinit_teacher:
+            return min(1 - 1 / (self._iteration + 1), self.momentum)
+        return self.momentum
+
+    def _momentum_update(self):
+        ema_teacher_update(self, self.teacher, float(self._current_momentum()))
+
+    def _labeling_model(self):
+        return self.teacher
+
+    def _after_step(self):
+        with torch.no_grad():
+            self._momentum_update()
+
+    def _after_unsupervised_validation(self, metric_val):
+        self.pseudo_labeler.step(metric_val, self._epoch)   # the threshold schedule advances with the validation metric
+
+    # ---- checkpoints --------------------------------------------------------------------------
+    def _record_extra(self):
+        return {"momentum": self.momentum, "reinit_teacher": self.reinit_teacher}
+
+    @classmethod
+    def _ctor_extra(cls, record):
+        return {"momentum": record["momentum"], "reinit_teacher": record["reinit_teacher"]}
+
+    def _extra_state(self):
+        return {"teacher_state": self.teacher.state_dict()}
+
+    def load_checkpoint(self, checkpoint="best"):
+        save_dict = super().load_checkpoint(checkpoint)
+        if save_dict is not None:
+            self.teacher.load_state_dict(save_dict["teacher_state"])
+            self.teacher.to(self.device)
+            self._arena2 = None
+        return save_dict
+
+    def _initialize(self, iterations, load_from_checkpoint, epochs=None):
+        best_metric = super()._initialize(iterations, load_from_checkpoint, epochs)
+        self.teacher.to(self.device)
+        return best_metric
+
+    # ---- steps ------------------------------------------------------------------------------------
+    def _unsupervised_step(self, xu1, xu2):
+        """teacher forward + labeler, student forward / backward on the pseudo labels, optimizer step (the caller updates the
+        teacher) -> (loss, pseudo_labels, label_filter), or None when the sampler rejects the batch (nothing ran but the teacher)"""
+        pseudo_labels, label_filter = self._pseudo_labels(xu1)
+        if self.sampler is not None and not self.sampler(pseudo_labels, label_filter):
+            return None
+        self.optimizer.zero_grad()
+        with self._precision():
+            loss = self.unsupervised_loss(self.model, xu2, pseudo_labels, label_filter)
+            self._backprop(loss)
+        return loss, pseudo_labels, label_filter
+
+    def _semisupervised_step(self, xs, ys, xu1, xu2):
+        """supervised and unsupervised student passes, ONE backward pass over the mean of the two losses
+        -> (supervised loss, unsupervised loss, combined loss, pseudo_labels, label_filter)"""
+        self.optimizer.zero_grad()
+        with self._precision():
+            supervised_loss = self.supervised_loss(self.model, xs, ys)
+        pseudo_labels, label_filter = self._pseudo_labels(xu1)
+        with self._precision():
+            unsupervised_loss = self.unsupervised_loss(self.model, xu2, pseudo_labels, label_filter)
+            loss = (supervised_loss + unsupervised_loss) / 2
+            self._backprop(loss)
+        return supervised_loss, unsupervised_loss, loss, pseudo_labels, label_filter
