@@ -241,6 +241,36 @@ int tem_conv3d_fwd_stats(const float* x, int64_t x_ld, const float* scale, const
                          int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                          int act, int use_mfma, float* stat_part, int64_t stat_blocks, tem_stream_t stream);
 
+/* Which kernel of the VALU family (use_mfma 0, with the storage types in its high bits) a tem_conv3d_fwd / _stats / _ex
+ * launch with EXACTLY these arguments takes; launches nothing and reads no memory.  has_stat: the launch carries stat_part.
+ * Returns TEM_VALU_* or -1 for a launch the library refuses (bad arguments -- the launch's own checks run, and a failed one
+ * leaves its message for tem_last_error() --, another arithmetic mode, a statistics request on a launch that writes no rows).  The selector (csrc/conv.hip: fwd_valu_select) takes the first that applies of
+ *   C1ROWS / CIN1   Cin <= 4, Cout % 4 == 0, Cin * Cout <= 128, 3x3x3 or 1x3x3, no ref, y_ld % 4 == 0, y aligned to 4
+ *                   elements, bias 16-byte aligned; C1ROWS (k_conv_fwd_c1rows<KD>) where Cin == 1 and Cout / 2 is a power of
+ *                   two <= 64, CIN1 (k_conv_fwd_cin1<KD, 3, 3, CIN>) otherwise.  Statistics rows: 4 x 8 x (32 | 8) voxel blocks,
+ *                   ceil(D / 4) * ceil(H / 8) * ceil(W / (32 | 8)) per sample, x fastest, where Cout / 4 is a power of two <= 64
+ *   COUT1           Cout == 1, Cin % 16 == 0, 3x3x3 or 1x3x3, no pre-norm, no ref, x 16-byte aligned with x_ld % 4 == 0
+ *   PROJ_R / PROJ   1x1x1, Cin % 32 == 0, Cout in {1, 2, 3, 4, 6, 8, 12, 16}, no pre-norm, no ref, x as for COUT1;
+ *                   PROJ_R (k_conv1x1_proj_r<COUT, NJ>) for NJ = Cin / 32 in {1, 2} and for NJ == 4 with Cout <= 8,
+ *                   PROJ (k_conv1x1_proj<COUT>) otherwise
+ *   EXPAND          1x1x1, Cin <= 16, Cout % 4 == 0, no pre-norm, y (and ref) 16-byte aligned with ld % 4 == 0, weights and
+ *                   bias 16-byte aligned; the only path that delivers TEM_BP_OUT_AMAX
+ *   SMALLCOUT       1x1x1, Cin % 4 == 0, Cout in {1, 2, 3, 4, 8, 12, 16}, x as for COUT1 (k_conv1x1_smallcout<COUT>)
+ *   GENERIC         everything else (k_conv_fwd_generic<KD, KH, KW>)
+ * inst (optional): int[4] = the COUT, NJ, CIN, KD template arguments of the instantiation, 0 where the path has none;
+ * GENERIC reports its <KD, KH, KW> as the decimal digits of inst[3]. */
+#define TEM_VALU_C1ROWS 0
+#define TEM_VALU_CIN1 1
+#define TEM_VALU_COUT1 2
+#define TEM_VALU_PROJ_R 3
+#define TEM_VALU_PROJ 4
+#define TEM_VALU_EXPAND 5
+#define TEM_VALU_SMALLCOUT 6
+#define TEM_VALU_GENERIC 7
+int tem_conv3d_fwd_valu_path(const void* x, int64_t x_ld, const void* scale, const void* shift, const void* w_packed,
+                             const void* bias, const void* y, int64_t y_ld, const void* ref, int64_t ref_ld, int N, int D, int H,
+                             int W, int Cin, int Cout, int kd, int kh, int kw, int act, int use_mfma, int has_stat, int* inst);
+
 /* dw = sum_v xhat[v+tap][ci] * g[v][co]  (xhat = x*scale+shift, zero padded)
  * db[co] = sum_v g[v][co] (optional).  ws: workspace of tem_conv3d_wgrad_ws() bytes.
  * sd_layout != 0: dw is written in the reference's state_dict order [Cout][Cin][kd][kh][kw]
@@ -254,6 +284,24 @@ int tem_conv3d_wgrad(const float* x, int64_t x_ld, const float* scale, const flo
                      void* ws, int64_t ws_bytes,
                      int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw,
                      int use_mfma, int sd_layout, tem_stream_t stream);
+
+/* Which kernel the weight-gradient plan (csrc/conv.hip: wgrad_plan) names for a tem_conv3d_wgrad / tem_conv3d_wgrad_gnorm[_st]
+ * launch with EXACTLY these arguments, in any arithmetic mode (use_mfma with the storage types in its high bits); launches
+ * nothing and reads no memory.  gnx / gcoef: the y and the coefficients of tem_conv3d_wgrad_gnorm (NULL: a plain
+ * tem_conv3d_wgrad); has_db: the launch carries db; ws_bytes: its workspace.  Returns TEM_WGRAD_* or -1 for a launch the
+ * library refuses (the launch's own argument checks run: a failed one leaves its message for tem_last_error()).  VALU mode: CIN1 (k_conv_wgrad_cin1) for Cin <= 4, Cout % 4 == 0 with Cout / 4 a power of two <= 16, 3x3x3 or
+ * 1x3x3, g (and gnx / gcoef) 16-byte aligned with ld % 4 == 0; PROJ (k_conv1x1_proj_wgrad<COUT, NJ>) for 1x1x1, Cin in
+ * {32, 64, 128}, Cout in {1, 2, 3, 4, 6, 8, 12, 16, 24, 32} with (Cin / 32) * Cout <= 32, no pre-norm, x 16-byte aligned with
+ * x_ld % 4 == 0; GENERIC otherwise. */
+#define TEM_WGRAD_GENERIC 0
+#define TEM_WGRAD_CIN1 1
+#define TEM_WGRAD_PROJ 2
+#define TEM_WGRAD_ZS 3
+#define TEM_WGRAD_PATCH 4
+#define TEM_WGRAD_PATCH_FP32 5
+int tem_conv3d_wgrad_path(const void* x, int64_t x_ld, const void* scale, const void* shift, const void* g, int64_t g_ld,
+                          const void* gnx, int64_t gnx_ld, const void* gcoef, int has_db, int64_t ws_bytes, int N, int D, int H,
+                          int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, int sd_layout);
 
 /* Backward of the output projection out_conv = nn.Conv3d(features, out_channels, 1) (/root/reference/torch_em/model/unet.py:638:
  * the wgrad + dgrad halves of its convolution_backward, and the threshold_backward of the ReLU in front of it) in ONE pass over

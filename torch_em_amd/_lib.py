@@ -44,6 +44,10 @@ SIGNATURES = {
     "tem_conv3d_fwd_kernel_ld": (c_int, [c_int] * 10 + [c_i64] * 3 + [c_int]),
     "tem_conv3d_fwd_stats": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_i64]
                              + [c_int] * 11 + [c_vp, c_i64, c_vp]),
+    # dispatch queries of the VALU family for the arguments of an actual launch (launch nothing); inst: host int[4] or None
+    "tem_conv3d_fwd_valu_path": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64] + [c_int] * 12
+                                 + [ctypes.POINTER(c_int)]),
+    "tem_conv3d_wgrad_path": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_i64] + [c_int] * 11),
     "tem_conv3d_wgrad_ws": (c_i64, [c_int] * 10),
     "tem_conv3d_wgrad": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64] + [c_int] * 11 + [c_vp]),
     "tem_conv1x1_out_bwd_ok": (c_int, [c_int] * 2),

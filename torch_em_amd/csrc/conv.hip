@@ -233,6 +233,22 @@ static void launch_fwd_generic(const TemConvCall& c, const float* x, int64_t x_l
                                       Cout, act));
 }
 
+static void launch_fwd_smallcout(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
+                                 const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int64_t V, int64_t NV,
+                                 int Cin, int Cout, int act, hipStream_t s) {
+    dim3 grid(tem_grid_1d(NV, 256, 256 * 16));
+#define SC(CO)                                                                                                   \
+    case CO:                                                                                                     \
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, (void)0,                                            \
+                       hipLaunchKernelGGL((k_conv1x1_smallcout<CO, TX, TY>), grid, dim3(256), 0, s, (const TX*)x, x_ld, scale, shift, \
+                                          w, bias, (TY*)y, y_ld, (const TY*)ref, ref_ld, V, NV, Cin, act)); \
+        break;
+    switch (Cout) {
+        SC(1) SC(2) SC(3) SC(4) SC(8) SC(12) SC(16)
+    }
+#undef SC
+}
+
 #define DISPATCH_K(KD, KH, KW, CALL)                                  \
     do {                                                              \
         int key__ = ((KD) == 3) * 4 + ((KH) == 3) * 2 + ((KW) == 3);  \
@@ -410,6 +426,45 @@ static FwdPlan fwd_plan(const TemConvCall& c, const TemConvShape& sh, int mode, 
     return p;
 }
 
+// The VALU family (fwd_plan: FK_VALU) has eight kernels.  fwd_valu_select() names the ONE a launch takes, with the template
+// arguments of its instantiation, from the launch's real pointers, leading dimensions, storage pair, shape and operands;
+// conv3d_fwd_impl switches on the answer and tem_conv3d_fwd_valu_path() reports it.  Order of preference: first layer (small Cin,
+// 3x3x3 / 1x3x3), its data gradient (Cout 1), then for 1x1x1 the projection, the expansion and the one-thread-per-voxel
+// projection; the generic kernel takes everything.  Only the first-layer kernels write statistics rows.
+struct ValuSel {
+    int path;               // TemValuPath
+    int cout, nj, cin, kd;  // the instantiation: COUT / NJ / CIN / KD template arguments, 0 where the path has none
+};
+
+static bool smallcout_takes(int Cin, int Cout) {
+    return Cin % 4 == 0 && (Cout == 1 || Cout == 2 || Cout == 3 || Cout == 4 || Cout == 8 || Cout == 12 || Cout == 16);
+}
+
+static ValuSel fwd_valu_select(const TemConvCall& c, const TemConvShape& sh, const void* x, int64_t x_ld, bool scale, const void* w,
+                               const void* bias, const void* y, int64_t y_ld, const void* ref, int64_t ref_ld, bool stat) {
+    auto al = [](const void* ptr, uintptr_t a) { return (uintptr_t)ptr % a == 0; };   // (an absent operand counts as aligned)
+    const int Cin = sh.Cin, Cout = sh.Cout;
+    const bool x16 = x_ld % 4 == 0 && al(x, 16);   // x in 16-byte rows
+    const bool one = sh.key() == 0;
+    const int first = tem_conv_fwd_cin1_takes(sh);
+    if (first && !ref && y_ld % 4 == 0 && al(y, tem_st_align4(c.sty)) && al(bias, 16)) {
+        if (stat && !tem_conv_fwd_cin1_stat_blocks(sh.D, sh.H, sh.W, Cin, Cout, sh.kd, sh.kh, sh.kw)) return {TEM_VP_REFUSED, 0, 0, 0, 0};
+        if (first == 2) return {TEM_VP_C1ROWS, 0, 0, 0, sh.kd};
+        return {TEM_VP_CIN1, 0, 0, Cin, sh.kd};
+    }
+    if (stat) return {TEM_VP_REFUSED, 0, 0, 0, 0};
+    if (tem_conv_fwd_cout1_takes(sh) && !scale && !ref && x16) return {TEM_VP_COUT1, 0, 0, 0, sh.kd};
+    if (one && !scale) {
+        const int nj = tem_conv1x1_proj_nj(Cin, Cout);
+        if (nj >= 0 && !ref && x16) return {nj ? TEM_VP_PROJ_R : TEM_VP_PROJ, Cout, nj, 0, 0};
+        if (tem_conv1x1_expand_takes(Cin, Cout) && y_ld % 4 == 0 && al(y, 16) && al(w, 16) && al(bias, 16) &&
+            (!ref || (ref_ld % 4 == 0 && al(ref, 16))))
+            return {TEM_VP_EXPAND, 0, 0, 0, 0};
+    }
+    if (one && smallcout_takes(Cin, Cout) && x16) return {TEM_VP_SMALLCOUT, Cout, 0, 0, 0};
+    return {TEM_VP_GENERIC, 0, 0, 0, sh.kd * 100 + sh.kh * 10 + sh.kw};   // <KD, KH, KW> as decimal digits
+}
+
 static int64_t fwd_ws(const TemConvCall& c, const TemConvShape& sh, int mode) {
     if (!mode || sh.Cin % 16 || sh.Cout % 32) return 0;
     const TemPatchTiling t = tem_fwd_patch_tiling(sh);
@@ -427,10 +482,10 @@ extern "C" int64_t tem_conv3d_fwd_ws(int N, int D, int H, int W, int Cin, int Co
     return fwd_ws(c, TemConvShape{N, D, H, W, Cin, Cout, kd, kh, kw}, use_mfma);
 }
 
-static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift,
-                           const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref,
-                           int64_t ref_ld, void* ws, int64_t ws_bytes, const TemConvShape& sh, int act, int use_mfma, float* stat,
-                           tem_stream_t stream) {
+// the argument checks of every forward / data-gradient launch, shared by conv3d_fwd_impl and the dispatch query of an actual
+// launch (tem_conv3d_fwd_valu_path): a failed check leaves its message for tem_last_error()
+static int fwd_args_check(const TemConvCall& c, const void* x, int64_t x_ld, const void* scale, const void* shift, const void* w_packed,
+                          const void* y, int64_t y_ld, const void* ref, int64_t ref_ld, const TemConvShape& sh, int act, int use_mfma) {
     const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout, kd = sh.kd, kh = sh.kh, kw = sh.kw;
     TEM_REQUIRE(x && w_packed && y, "tem_conv3d_fwd: null pointer");
     TEM_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && x_ld >= (c.x_cs ? 32 : Cin) &&
@@ -445,7 +500,6 @@ static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, c
     TEM_REQUIRE(stx >= 0 && stx <= 2 && sty >= 0 && sty <= 2 && (stx == 0 || sty == 0 || stx == sty),
                 "tem_conv3d_fwd: unsupported storage types (x %d, y %d)", stx, sty);
     TEM_REQUIRE(!(stx || sty) || use_mfma != TEM_ARITH_FP32, "tem_conv3d_fwd: the exact-fp32 MFMA kernels take fp32 tensors only");
-    hipStream_t s = (hipStream_t)stream;
     TEM_REQUIRE(!(c.x_cs || c.y_cs) || tem_arith_one_term(use_mfma), "tem_conv3d_fwd_ex: chunk strides need use_mfma 5 / 7");
     auto al16 = [](const void* ptr) { return (uintptr_t)ptr % 16 == 0; };
     if (tem_arith_split_fwd(use_mfma)) {   // every split-precision kernel loads x / weights / scale as 16-byte vectors
@@ -456,6 +510,18 @@ static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, c
         TEM_REQUIRE(al16(x) && al16(w_packed), kSplitXLayout);
         TEM_REQUIRE(al16(scale) && al16(shift), "tem_conv3d_fwd(split-bf16): scale/shift must be 16-byte aligned");
     }
+    return TEM_OK;
+}
+
+static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                           const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref,
+                           int64_t ref_ld, void* ws, int64_t ws_bytes, const TemConvShape& sh, int act, int use_mfma, float* stat,
+                           tem_stream_t stream) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout, kd = sh.kd, kh = sh.kh, kw = sh.kw;
+    TEM_TRY(fwd_args_check(c, x, x_ld, scale, shift, w_packed, y, y_ld, ref, ref_ld, sh, act, use_mfma));
+    const int stx = c.stx, sty = c.sty;
+    hipStream_t s = (hipStream_t)stream;
+    auto al16 = [](const void* ptr) { return (uintptr_t)ptr % 16 == 0; };
 
     const uintptr_t v4 = tem_st_align4(sty);
     const FwdFacts facts = {x_ld, y_ld, ref ? ref_ld : 0,
@@ -495,51 +561,45 @@ static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, c
         TEM_CHECK_LAUNCH(what[p.kernel]);
         return TEM_OK;
     }
-    // VALU kernels: the first that takes the shape
+    // VALU kernels: the one fwd_valu_select names
     const int64_t NV = sh.NV();
-    if (tem_conv_fwd_cin1(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, N, D, H, W, Cin, Cout, kd, kh, kw, act,
-                          stat, s)) {
-        TEM_CHECK_LAUNCH("tem_conv3d_fwd(cin1)");
-        return TEM_OK;
-    }
-    TEM_REQUIRE(!stat, "tem_conv3d_fwd_stats: this launch cannot write statistics (tem_conv3d_fwd_stat_blocks() == 0)");
-    if (tem_conv_fwd_cout1(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, N, D, H, W, Cin, Cout, kd, kh, kw, act,
-                           s)) {
-        TEM_CHECK_LAUNCH("tem_conv3d_fwd(cout1)");
-        return TEM_OK;
-    }
-    if (kd == 1 && kh == 1 && kw == 1 &&
-        tem_conv1x1_proj(c, x, x_ld, scale, w_packed, bias, y, y_ld, ref, NV, Cin, Cout, act, s)) {
-        TEM_CHECK_LAUNCH("tem_conv3d_fwd(proj)");
-        return TEM_OK;
-    }
-    if (kd == 1 && kh == 1 && kw == 1 &&
-        tem_conv1x1_expand(c, x, x_ld, scale, w_packed, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s)) {
-        TEM_CHECK_LAUNCH("tem_conv3d_fwd(expand)");
-        return TEM_OK;
-    }
-    if (kd == 1 && kh == 1 && kw == 1 && Cin % 4 == 0 && x_ld % 4 == 0 && ((uintptr_t)x % 16 == 0) &&
-        (Cout == 1 || Cout == 2 || Cout == 3 || Cout == 4 || Cout == 8 || Cout == 12 || Cout == 16)) {
-        dim3 grid(tem_grid_1d(NV, 256, 256 * 16));
-#define SC(CO)                                                                                                   \
-    case CO:                                                                                                     \
-        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, (void)0,                                            \
-                       hipLaunchKernelGGL((k_conv1x1_smallcout<CO, TX, TY>), grid, dim3(256), 0, s, (const TX*)x, x_ld, scale, shift, \
-                                          w_packed, bias, (TY*)y, y_ld, (const TY*)ref, ref_ld, (int64_t)D * H * W, NV, Cin, act)); \
-        break;
-        switch (Cout) {
-            SC(1) SC(2) SC(3) SC(4) SC(8) SC(12) SC(16)
-        }
-#undef SC
-        TEM_CHECK_LAUNCH("tem_conv3d_fwd(1x1)");
-        return TEM_OK;
-    }
+    const ValuSel v = fwd_valu_select(c, sh, x, x_ld, scale != nullptr, w_packed, bias, y, y_ld, ref, ref_ld, stat != nullptr);
+    switch (v.path) {
+        case TEM_VP_C1ROWS:
+        case TEM_VP_CIN1:
+            tem_conv_fwd_cin1(c, v.path == TEM_VP_C1ROWS, x, x_ld, scale, shift, w_packed, bias, y, y_ld, N, D, H, W, Cin, Cout, kd, kh, kw,
+                              act, stat, s);
+            TEM_CHECK_LAUNCH("tem_conv3d_fwd(cin1)");
+            return TEM_OK;
+        case TEM_VP_COUT1:
+            tem_conv_fwd_cout1(c, x, x_ld, w_packed, bias, y, y_ld, N, D, H, W, Cin, kd, kh, kw, act, s);
+            TEM_CHECK_LAUNCH("tem_conv3d_fwd(cout1)");
+            return TEM_OK;
+        case TEM_VP_PROJ_R:
+        case TEM_VP_PROJ:
+            tem_conv1x1_proj(c, v.nj, x, x_ld, w_packed, bias, y, y_ld, NV, Cin, Cout, act, s);
+            TEM_CHECK_LAUNCH("tem_conv3d_fwd(proj)");
+            return TEM_OK;
+        case TEM_VP_EXPAND:
+            tem_conv1x1_expand(c, x, x_ld, w_packed, bias, y, y_ld, ref, ref_ld, NV, Cin, Cout, act, s);
+            TEM_CHECK_LAUNCH("tem_conv3d_fwd(expand)");
+            return TEM_OK;
+        case TEM_VP_SMALLCOUT:
+            launch_fwd_smallcout(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, (int64_t)D * H * W, NV, Cin, Cout, act, s);
+            TEM_CHECK_LAUNCH("tem_conv3d_fwd(1x1)");
+            return TEM_OK;
+        case TEM_VP_GENERIC: {
 #define CALL(A, B, C) \
     launch_fwd_generic<A, B, C>(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, N, D, H, W, Cin, Cout, act, s)
-    DISPATCH_K(kd, kh, kw, CALL);
+            DISPATCH_K(kd, kh, kw, CALL);
 #undef CALL
-    TEM_CHECK_LAUNCH("tem_conv3d_fwd(generic)");
-    return TEM_OK;
+            TEM_CHECK_LAUNCH("tem_conv3d_fwd(generic)");
+            return TEM_OK;
+        }
+        default:
+            TEM_REQUIRE(false, "tem_conv3d_fwd_stats: this launch cannot write statistics (tem_conv3d_fwd_stat_blocks() == 0)");
+    }
+    return TEM_EINVAL;
 }
 
 extern "C" int tem_conv3d_fwd(const float* x, int64_t x_ld, const float* scale, const float* shift,
@@ -587,6 +647,30 @@ extern "C" int64_t tem_conv3d_fwd_stat_blocks(int N, int D, int H, int W, int Ci
 
 extern "C" int tem_conv3d_fwd_kernel(int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma) {
     return tem_conv3d_fwd_kernel_ld(N, D, H, W, Cin, Cout, kd, kh, kw, use_mfma, Cin, Cout, 0, 0);
+}
+
+// The kernel of the VALU family a tem_conv3d_fwd / _stats / _ex launch with exactly these arguments takes (tem_hip.h; launches
+// nothing): the argument checks of conv3d_fwd_impl, the plan, the selector.  inst (optional): int[4] = COUT, NJ, CIN, KD
+extern "C" int tem_conv3d_fwd_valu_path(const void* x, int64_t x_ld, const void* scale, const void* shift, const void* w_packed,
+                                        const void* bias, const void* y, int64_t y_ld, const void* ref, int64_t ref_ld, int N, int D,
+                                        int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act, int use_mfma, int has_stat,
+                                        int* inst) {
+    if (inst) inst[0] = inst[1] = inst[2] = inst[3] = 0;
+    const TemConvCall c = conv_call(use_mfma);
+    const TemConvShape sh = {N, D, H, W, Cin, Cout, kd, kh, kw};
+    if (use_mfma != TEM_ARITH_VALU || fwd_args_check(c, x, x_ld, scale, shift, w_packed, y, y_ld, ref, ref_ld, sh, act, use_mfma) != TEM_OK)
+        return TEM_VP_REFUSED;
+    if (has_stat && !fwd_query(c, sh, use_mfma, x_ld, y_ld, ref ? ref_ld : 0, fwd_misaligned(x, scale, shift, w_packed, bias, y, ref))
+                         .stat_blocks)
+        return TEM_VP_REFUSED;   // (fwd_stats_check)
+    const ValuSel v = fwd_valu_select(c, sh, x, x_ld, scale != nullptr, w_packed, bias, y, y_ld, ref, ref_ld, has_stat != 0);
+    if (inst && v.path != TEM_VP_REFUSED) {
+        inst[0] = v.cout;
+        inst[1] = v.nj;
+        inst[2] = v.cin;
+        inst[3] = v.kd;
+    }
+    return v.path;
 }
 
 // the argument checks of tem_conv3d_fwd_stats (also a tem_conv3d_fwd_ex with stat_part)
@@ -939,12 +1023,12 @@ extern "C" int tem_conv3d_wgrad_gnorm_ok(int Cin, int Cout, int kd, int kh, int 
     return wgrad_query(TemConvCall{}, TemConvShape{1, 1, 1, 1, Cin, Cout, kd, kh, kw}, use_mfma & 0xff).kernel == WK_CIN1;
 }
 
-static int conv3d_wgrad_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
-                             int64_t g_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H,
-                             int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, int sd_layout,
-                             const float* w_sd, const float* gamma, const float* beta, float* norm_sums,
-                             const float* gnx, int64_t gnx_ld, const float* gcoef, tem_stream_t stream) {
-    TEM_REQUIRE(x && g && dw && ws, "tem_conv3d_wgrad: null pointer");
+// the argument checks of every weight-gradient launch, shared by conv3d_wgrad_impl and the dispatch query of an actual launch
+// (tem_conv3d_wgrad_path; outputs: the launch has dw and its workspace): a failed check leaves its message for tem_last_error()
+static int wgrad_args_check(const TemConvCall& c, const void* x, int64_t x_ld, const void* scale, const void* shift, const void* g,
+                            int64_t g_ld, bool outputs, const TemConvShape& sh, int use_mfma) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout, kd = sh.kd, kh = sh.kh, kw = sh.kw;
+    TEM_REQUIRE(x && g && outputs, "tem_conv3d_wgrad: null pointer");
     TEM_REQUIRE(N > 0 && D > 0 && H > 0 && W > 0 && Cin > 0 && Cout > 0 && x_ld >= (c.x_cs ? 32 : Cin) && g_ld >= Cout,
                 "tem_conv3d_wgrad: bad shape");
     TEM_REQUIRE((kd == 1 || kd == 3) && (kh == 1 || kh == 3) && (kw == 1 || kw == 3),
@@ -955,7 +1039,21 @@ static int conv3d_wgrad_impl(const TemConvCall& c, const float* x, int64_t x_ld,
                 "tem_conv3d_wgrad: unsupported storage types (x %d, g %d)", stx, sty);
     TEM_REQUIRE(!(stx || sty) || tem_arith(use_mfma).wgrad != TEM_WG_FP32,
                 "tem_conv3d_wgrad: the exact-fp32 MFMA kernels take fp32 tensors only");
+    return TEM_OK;
+}
+// ... and of tem_conv3d_wgrad_gnorm[_st] on top of them
+static int wgrad_gnorm_args_check(const void* y, int64_t y_ld, const void* gcoef, int Cout) {
+    TEM_REQUIRE(y && gcoef && y_ld >= Cout, "tem_conv3d_wgrad_gnorm: null pointer");
+    return TEM_OK;
+}
+
+static int conv3d_wgrad_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,
+                             int64_t g_ld, float* dw, float* db, void* ws, int64_t ws_bytes, int N, int D, int H,
+                             int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, int sd_layout,
+                             const float* w_sd, const float* gamma, const float* beta, float* norm_sums,
+                             const float* gnx, int64_t gnx_ld, const float* gcoef, tem_stream_t stream) {
     const TemConvShape sh = {N, D, H, W, Cin, Cout, kd, kh, kw};
+    TEM_TRY(wgrad_args_check(c, x, x_ld, scale, shift, g, g_ld, dw && ws, sh, use_mfma));
     auto al16 = [](const void* ptr) { return (uintptr_t)ptr % 16 == 0; };
     const WgradFacts facts = {x_ld, g_ld, gnx_ld, al16(x), al16(g), al16(scale) && al16(shift), al16(gnx) && al16(gcoef),
                               scale != nullptr, db != nullptr, norm_sums != nullptr, w_sd != nullptr, gcoef != nullptr, sd_layout != 0,
@@ -1009,6 +1107,23 @@ extern "C" int tem_conv3d_wgrad(const float* x, int64_t x_ld, const float* scale
     const TemConvCall c = conv_call(use_mfma);
     return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw,
                              use_mfma, sd_layout, nullptr, nullptr, nullptr, nullptr, nullptr, 0, nullptr, stream);
+}
+
+// The kernel wgrad_plan() names for a tem_conv3d_wgrad / _gnorm[_st] launch with exactly these arguments (tem_hip.h: TEM_WGRAD_*;
+// launches nothing): the argument checks of conv3d_wgrad_impl, then the plan of the launch's real facts.  gnx / gcoef: the y and
+// the coefficients of tem_conv3d_wgrad_gnorm (null: a plain tem_conv3d_wgrad)
+extern "C" int tem_conv3d_wgrad_path(const void* x, int64_t x_ld, const void* scale, const void* shift, const void* g, int64_t g_ld,
+                                     const void* gnx, int64_t gnx_ld, const void* gcoef, int has_db, int64_t ws_bytes, int N, int D,
+                                     int H, int W, int Cin, int Cout, int kd, int kh, int kw, int use_mfma, int sd_layout) {
+    const TemConvCall c = conv_call(use_mfma);
+    const TemConvShape sh = {N, D, H, W, Cin, Cout, kd, kh, kw};
+    if (wgrad_args_check(c, x, x_ld, scale, shift, g, g_ld, true, sh, use_mfma) != TEM_OK) return -1;
+    if ((gnx || gcoef) && (use_mfma != TEM_ARITH_VALU || wgrad_gnorm_args_check(gnx, gnx_ld, gcoef, Cout) != TEM_OK)) return -1;
+    auto al16 = [](const void* ptr) { return (uintptr_t)ptr % 16 == 0; };
+    const WgradFacts facts = {x_ld, g_ld, gnx_ld, al16(x), al16(g), al16(scale) && al16(shift), al16(gnx) && al16(gcoef),
+                              scale != nullptr, has_db != 0, false, false, gcoef != nullptr, sd_layout != 0, ws_bytes};
+    const WgradPlan p = wgrad_plan(c, sh, use_mfma, facts);
+    return p.kernel == WK_REFUSED ? -1 : (int)p.kernel;
 }
 
 // Backward of the network's output projection (out_conv: nn.Conv3d(features, out_channels, 1), reference model/unet.py:638)
@@ -1232,7 +1347,7 @@ static int wgrad_gnorm_impl(const TemConvCall& c, const float* x, int64_t x_ld, 
                             int64_t g_ld, const float* y, int64_t y_ld, const float* gcoef, float* dw, float* db, void* ws,
                             int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int sd_layout,
                             tem_stream_t stream) {
-    TEM_REQUIRE(y && gcoef && y_ld >= Cout, "tem_conv3d_wgrad_gnorm: null pointer");
+    TEM_TRY(wgrad_gnorm_args_check(y, y_ld, gcoef, Cout));
     return conv3d_wgrad_impl(c, x, x_ld, scale, shift, g, g_ld, dw, db, ws, ws_bytes, N, D, H, W, Cin, Cout, kd, kh, kw, TEM_ARITH_VALU,
                              sd_layout, nullptr, nullptr, nullptr, nullptr, y, y_ld, gcoef, stream);
 }

@@ -86,17 +86,27 @@ int tem_conv_fwd_mfma(const TemPatchTiling& t, int ks, const float* x, int64_t x
                       const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
                       const TemConvShape& sh, int act, hipStream_t s);
 
-// conv_small.hip: HBM-bound special cases (return false when the shape is not covered)
-bool tem_conv_fwd_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
-                       const float* bias, float* y, int64_t y_ld, const float* ref, int N, int D, int H, int W,
+// conv_small.hip: the HBM-bound special cases of the VALU family (use_mfma 0).  As everywhere in this file: shape predicates
+// that the ONE selector (conv.hip: fwd_valu_select) calls, and launchers that execute what it selected and decide nothing.
+// The paths, as tem_conv3d_fwd_valu_path() reports them (tem_hip.h: TEM_VALU_*)
+enum TemValuPath {
+    TEM_VP_REFUSED = -1, TEM_VP_C1ROWS = 0, TEM_VP_CIN1, TEM_VP_COUT1, TEM_VP_PROJ_R, TEM_VP_PROJ, TEM_VP_EXPAND, TEM_VP_SMALLCOUT,
+    TEM_VP_GENERIC
+};
+int tem_conv_fwd_cin1_takes(const TemConvShape& sh);      // 0: neither, 1: k_conv_fwd_cin1, 2: k_conv_fwd_c1rows
+void tem_conv_fwd_cin1(const TemConvCall& c, bool rows, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
+                       const float* bias, float* y, int64_t y_ld, int N, int D, int H, int W,
                        int Cin, int Cout, int kd, int kh, int kw, int act, float* stat, hipStream_t s);
 int64_t tem_conv_fwd_cin1_stat_blocks(int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw);
-bool tem_conv_fwd_cout1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
-                        const float* bias, float* y, int64_t y_ld, const float* ref, int N, int D, int H, int W,
-                        int Cin, int Cout, int kd, int kh, int kw, int act, hipStream_t s);
-bool tem_conv1x1_proj(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* w, const float* bias, float* y,
-                      int64_t y_ld, const float* ref, int64_t NV, int Cin, int Cout, int act, hipStream_t s);
-bool tem_conv1x1_expand(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* w, const float* bias, float* y,
+bool tem_conv_fwd_cout1_takes(const TemConvShape& sh);
+void tem_conv_fwd_cout1(const TemConvCall& c, const float* x, int64_t x_ld, const float* w,
+                        const float* bias, float* y, int64_t y_ld, int N, int D, int H, int W,
+                        int Cin, int kd, int kh, int kw, int act, hipStream_t s);
+int tem_conv1x1_proj_nj(int Cin, int Cout);               // NJ of k_conv1x1_proj_r, 0: k_conv1x1_proj, -1: none
+void tem_conv1x1_proj(const TemConvCall& c, int nj, const float* x, int64_t x_ld, const float* w, const float* bias, float* y,
+                      int64_t y_ld, int64_t NV, int Cin, int Cout, int act, hipStream_t s);
+bool tem_conv1x1_expand_takes(int Cin, int Cout);
+void tem_conv1x1_expand(const TemConvCall& c, const float* x, int64_t x_ld, const float* w, const float* bias, float* y,
                         int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act,
                         hipStream_t s);
 void tem_reduce_slabs_w(const float* part, int nchunks, int ntaps, int Cin, int Cout, int64_t chunk_stride, float* dw,

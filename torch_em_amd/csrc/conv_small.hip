@@ -274,21 +274,24 @@ int64_t tem_conv_fwd_cin1_stat_blocks(int D, int H, int W, int Cin, int Cout, in
     return (int64_t)((D + 3) / 4) * ((H + 7) / 8) * ((W + tx - 1) / tx);
 }
 
-bool tem_conv_fwd_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
-                       const float* bias, float* y, int64_t y_ld, const float* ref, int N, int D, int H, int W,
+// the shapes of the two first-layer kernels: 0 neither, 1 k_conv_fwd_cin1, 2 k_conv_fwd_c1rows.  Cin 2..4 (RGB / multi-channel raw
+// data) share the kernel; weights stay in LDS, so Cin * Cout is bounded.  (y in rows of whole 4-element vectors, a 16-byte
+// aligned bias and no ref: fwd_valu_select's part)
+int tem_conv_fwd_cin1_takes(const TemConvShape& sh) {
+    if (sh.Cin > 4 || sh.Cout % 4 || sh.Cin * sh.Cout > 128 || (sh.key() != 7 && sh.key() != 3)) return 0;
+    return c1rows_ok(sh.Cin, sh.Cout, sh.kh, sh.kw) ? 2 : 1;
+}
+
+void tem_conv_fwd_cin1(const TemConvCall& c, bool rows, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
+                       const float* bias, float* y, int64_t y_ld, int N, int D, int H, int W,
                        int Cin, int Cout, int kd, int kh, int kw, int act, float* stat, hipStream_t s) {
-    // Cin 2..4 (RGB / multi-channel raw data) share the kernel; weights stay in LDS, so Cin * Cout is bounded
-    if (Cin > 4 || Cout % 4 || Cin * Cout > 128 || ref || y_ld % 4 || ((uintptr_t)y % tem_st_align4(c.sty)) ||
-        (bias && ((uintptr_t)bias % 16)))
-        return false;
     const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
-    if (key != 7 && key != 3) return false;
-    if (c1rows_ok(Cin, Cout, kh, kw) && y_ld % 2 == 0) {
+    if (rows) {
         const int nZ = (D + 3) / 4, nY = (H + 7) / 8, nX = (W + C1R_TXW - 1) / C1R_TXW;
         const int64_t nblk = (int64_t)N * nZ * nY * nX;
         const int kdv = key == 7 ? 3 : 1;
         const size_t ldsb = (size_t)((kdv + 3) * 10 * (C1R_TXW + 4) + kdv * 9 * Cout) * sizeof(float);
-        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false, {
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return, {
             if (key == 7)
                 hipLaunchKernelGGL((k_conv_fwd_c1rows<3, TX, TY>), dim3((unsigned)nblk), dim3(256), ldsb, s, (const TX*)x, x_ld, scale,
                                    shift, w, bias, (TY*)y, y_ld, N, D, H, W, Cout, act, nZ, nY, nX, stat);
@@ -296,14 +299,14 @@ bool tem_conv_fwd_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const
                 hipLaunchKernelGGL((k_conv_fwd_c1rows<1, TX, TY>), dim3((unsigned)nblk), dim3(256), ldsb, s, (const TX*)x, x_ld, scale,
                                    shift, w, bias, (TY*)y, y_ld, N, D, H, W, Cout, act, nZ, nY, nX, stat);
         });
-        return true;
+        return;
     }
     const int nZ = (D + 3) / 4, nY = (H + 7) / 8, nX = (W + 7) / 8;
     const int64_t nblk = (int64_t)N * nZ * nY * nX;
 #define C1(KD_, CI)                                                                                                   \
     case CI: {                                                                                                        \
         size_t ldsb = (size_t)(CI * ((KD_ + 3) * 10 * 12) + KD_ * 9 * CI * Cout) * sizeof(float);                    \
-        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false,                                            \
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return,                                            \
                        hipLaunchKernelGGL((k_conv_fwd_cin1<KD_, 3, 3, CI, TX, TY>), dim3((unsigned)nblk), dim3(256), ldsb, s, \
                                           (const TX*)x, x_ld, scale, shift, w, bias, (TY*)y, y_ld, N, D, H, W, Cout, act, nZ, nY, nX, stat)); \
     } break;
@@ -313,7 +316,6 @@ bool tem_conv_fwd_cin1(const TemConvCall& c, const float* x, int64_t x_ld, const
         switch (Cin) { C1(1, 1) C1(1, 2) C1(1, 3) C1(1, 4) }
     }
 #undef C1
-    return true;
 }
 
 // ---------------------------------------------------------------------------
@@ -383,16 +385,16 @@ __global__ __launch_bounds__(256) void k_conv_fwd_cout1(const EX* __restrict__ x
     }
 }
 
-bool tem_conv_fwd_cout1(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w,
-                        const float* bias, float* y, int64_t y_ld, const float* ref, int N, int D, int H, int W,
-                        int Cin, int Cout, int kd, int kh, int kw, int act, hipStream_t s) {
-    (void)shift;
-    if (Cout != 1 || Cin % 16 || scale || ref || x_ld % 4 || ((uintptr_t)x % 16)) return false;
+// (x without a pre-norm, in 16-byte rows, no ref: fwd_valu_select's part)
+bool tem_conv_fwd_cout1_takes(const TemConvShape& sh) { return sh.Cout == 1 && sh.Cin % 16 == 0 && (sh.key() == 7 || sh.key() == 3); }
+
+void tem_conv_fwd_cout1(const TemConvCall& c, const float* x, int64_t x_ld, const float* w,
+                        const float* bias, float* y, int64_t y_ld, int N, int D, int H, int W,
+                        int Cin, int kd, int kh, int kw, int act, hipStream_t s) {
     const int key = (kd == 3) * 4 + (kh == 3) * 2 + (kw == 3);
-    if (key != 7 && key != 3) return false;
     const int nZ = (D + 3) / 4, nY = (H + 7) / 8, nX = (W + 7) / 8;
     const int64_t nblk = (int64_t)N * nZ * nY * nX;
-    TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false, {
+    TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return, {
         if (key == 7)
             hipLaunchKernelGGL((k_conv_fwd_cout1<3, 3, 3, TX, TY>), dim3((unsigned)nblk), dim3(256), 0, s, (const TX*)x, x_ld, w, bias,
                                (TY*)y, y_ld, N, D, H, W, Cin, act, nZ, nY, nX);
@@ -400,7 +402,6 @@ bool tem_conv_fwd_cout1(const TemConvCall& c, const float* x, int64_t x_ld, cons
             hipLaunchKernelGGL((k_conv_fwd_cout1<1, 3, 3, TX, TY>), dim3((unsigned)nblk), dim3(256), 0, s, (const TX*)x, x_ld, w, bias,
                                (TY*)y, y_ld, N, D, H, W, Cin, act, nZ, nY, nX);
     });
-    return true;
 }
 
 // ---------------------------------------------------------------------------
@@ -995,17 +996,24 @@ __global__ __launch_bounds__(256) void k_conv1x1_proj_r(const EX* __restrict__ x
     }
 }
 
-bool tem_conv1x1_proj(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* w, const float* bias, float* y,
-                      int64_t y_ld, const float* ref, int64_t NV, int Cin, int Cout, int act, hipStream_t s) {
-    if (scale || ref || Cin % 32 || x_ld % 4 || ((uintptr_t)x % 16)) return false;
+// the instantiation for Cin -> Cout: NJ of k_conv1x1_proj_r<COUT, NJ> (weights in registers where they fit: NJ * COUT <= 32
+// values per 16-byte piece and lane), 0: k_conv1x1_proj<COUT>, -1: none.  (x without a pre-norm, in 16-byte rows, no ref:
+// fwd_valu_select's part)
+int tem_conv1x1_proj_nj(int Cin, int Cout) {
+    if (Cin % 32 || !((Cout >= 1 && Cout <= 4) || Cout == 6 || Cout == 8 || Cout == 12 || Cout == 16)) return -1;
+    const int nj = Cin / 32;
+    return nj == 1 || nj == 2 || (nj == 4 && Cout <= 8) ? nj : 0;
+}
+
+void tem_conv1x1_proj(const TemConvCall& c, int nj, const float* x, int64_t x_ld, const float* w, const float* bias, float* y,
+                      int64_t y_ld, int64_t NV, int Cin, int Cout, int act, hipStream_t s) {
     dim3 grid(tem_grid_1d(NV, 32, 256 * 16));
-    // weights in registers where they fit (NJ * COUT <= 32 values per 16-byte piece and lane)
 #define PJR(CO, NJ_)                                                                                                 \
-    if (Cout == CO && Cin == 32 * NJ_) {                                                                             \
-        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false,                                           \
+    if (Cout == CO && nj == NJ_) {                                                                                   \
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return,                                                 \
                        hipLaunchKernelGGL((k_conv1x1_proj_r<CO, NJ_, TX, TY>), grid, dim3(256), 0, s, (const TX*)x, x_ld, w, bias, \
                                           (TY*)y, y_ld, NV, act));                                                   \
-        return true;                                                                                                 \
+        return;                                                                                                      \
     }
     PJR(1, 1) PJR(2, 1) PJR(3, 1) PJR(4, 1) PJR(6, 1) PJR(8, 1) PJR(12, 1) PJR(16, 1)
     PJR(1, 2) PJR(2, 2) PJR(3, 2) PJR(4, 2) PJR(6, 2) PJR(8, 2) PJR(12, 2) PJR(16, 2)
@@ -1013,13 +1021,12 @@ bool tem_conv1x1_proj(const TemConvCall& c, const float* x, int64_t x_ld, const 
 #undef PJR
 #define PJ(CO)                                                                                                     \
     case CO:                                                                                                       \
-        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false,                                         \
+        TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return,                                               \
                        hipLaunchKernelGGL((k_conv1x1_proj<CO, TX, TY>), grid, dim3(256), 0, s, (const TX*)x, x_ld, w, bias, (TY*)y, \
                                           y_ld, NV, Cin, act));                                                    \
-        return true;
+        return;
     switch (Cout) {
         PJ(1) PJ(2) PJ(3) PJ(4) PJ(6) PJ(8) PJ(12) PJ(16)
-        default: return false;
     }
 #undef PJ
 }
@@ -1263,15 +1270,14 @@ __global__ __launch_bounds__(256) void k_conv1x1_expand(const EX* __restrict__ x
     if (amax) tem_amax_commit(amax, amx);
 }
 
-bool tem_conv1x1_expand(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* w, const float* bias, float* y,
+// (no pre-norm; y / ref in 16-byte rows, 16-byte aligned weights and bias: fwd_valu_select's part)
+bool tem_conv1x1_expand_takes(int Cin, int Cout) { return Cin <= 16 && Cout % 4 == 0; }
+
+void tem_conv1x1_expand(const TemConvCall& c, const float* x, int64_t x_ld, const float* w, const float* bias, float* y,
                         int64_t y_ld, const float* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act,
                         hipStream_t s) {
-    if (scale || Cin > 16 || Cout % 4 || y_ld % 4 || ((uintptr_t)y % 16) || ((uintptr_t)w % 16) ||
-        (bias && (uintptr_t)bias % 16) || (ref && (ref_ld % 4 || (uintptr_t)ref % 16)) || !tem_st2_ok(c.stx, c.sty))
-        return false;
     unsigned* const amax = c.take_output_amax();
-    TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return false,
+    TEM_ST2_SWITCH(c.stx, c.sty, TX, TY, return,
                    hipLaunchKernelGGL((k_conv1x1_expand<TX, TY>), dim3(tem_grid_1d(NV * (Cout / 4), 256, 256 * 16)), dim3(256), 0, s,
                                       (const TX*)x, x_ld, w, bias, (TY*)y, y_ld, (const TY*)ref, ref_ld, NV, Cin, Cout, act, amax));
-    return true;
 }
