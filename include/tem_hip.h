@@ -734,6 +734,23 @@ int tem_label_count_st(const void* labels, int64_t n, float threshold, void* par
 int tem_distribution_align_st(const void* labels, void* out, int64_t n, float threshold, float source0, float source1,
                               const void* partials, int parts, int st, tem_stream_t stream);
 
+/* ---- self-training: invertible augmentations, per-sample dihedral transform (csrc/invaug.hip) ------------------------
+ * The geometric part of the reference's transform/invertible_augmentations.py (horizontal / vertical flips and rotations by
+ * multiples of 90 degrees, drawn per sample, and their inverses) as ONE permutation pass.  src, dst: dense
+ * [N][planes][H][W], planes = C or C * D; codes_dev: int32[N] on the device.  Code c of a sample: bit 0 transposes, bit 1
+ * reverses the source row, bit 2 reverses the source column --
+ *   dst[n,p,i,j] = src[n,p,r,s],  (r, s) = (j, i) if c & 1 else (i, j);  r = H-1-r if c & 2;  s = W-1-s if c & 4
+ * so a sample with an odd code is written as [planes][W][H].  Inverses: 3 <-> 5, every other code is its own.
+ * A bit copy of elements of elem_bytes = 1, 2 or 4; src and dst must not overlap.  Mixed codes in one call are the normal
+ * case (a workgroup serves one sample and reads its code once); the bits above the third of a code are ignored.
+ * tem_dihedral2d_path launches nothing: the path a sample with the HOST value `code` takes in such a call -- 0 vector stream
+ * (even code, W * elem_bytes and both bases multiples of 16 bytes), 1 scalar stream (even code otherwise), 2 LDS tile of
+ * 32 x 32 elements, one per LDS dword (odd code), 3 packed LDS tile (odd code, elem_bytes < 4, H, W and both bases multiples
+ * of 4 bytes: 64 x 64 or 128 x 128 elements, dword accesses on both global sides); -1 for arguments the launch refuses. */
+int tem_dihedral2d(const void* src, void* dst, const int* codes_dev, int N, int planes, int H, int W, int elem_bytes,
+                   tem_stream_t stream);
+int tem_dihedral2d_path(const void* src, const void* dst, int code, int N, int planes, int H, int W, int elem_bytes);
+
 /* ---- optimizer -------------------------------------------------------------
  * torch.optim.AdamW step as configured by default_segmentation_trainer
  * (segmentation.py:543): decoupled weight decay, bias correction, eps outside

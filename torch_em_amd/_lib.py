@@ -120,6 +120,10 @@ SIGNATURES = {
     # (labels, n, threshold, partials, parts, st, stream) / (labels, out, n, threshold, source0, source1, partials, parts, st, stream)
     "tem_label_count_st": (c_int, [c_vp, c_i64, c_float, c_vp, c_int, c_int, c_vp]),
     "tem_distribution_align_st": (c_int, [c_vp, c_vp, c_i64, c_float, c_float, c_float, c_vp, c_int, c_int, c_vp]),
+    # (src, dst, codes_dev, N, planes, H, W, elem_bytes, stream) / (src, dst, code, N, planes, H, W, elem_bytes) -> 0 vector
+    # stream, 1 scalar stream, 2 tile, 3 packed tile, -1 refused
+    "tem_dihedral2d": (c_int, [c_vp, c_vp, c_vp] + [c_int] * 5 + [c_vp]),
+    "tem_dihedral2d_path": (c_int, [c_vp, c_vp] + [c_int] * 6),
     "tem_adamw_step": (c_int, [c_vp, c_vp, c_vp, c_vp, c_i64, c_float, c_float, c_float, c_float, c_float, c_i64,
                                c_float, c_vp]),
     "tem_adamw_hyper": (c_int, [c_vp, c_float, c_float, c_float, c_float, c_float, c_i64, c_float]),

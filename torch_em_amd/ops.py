@@ -1082,6 +1082,138 @@ def distribution_align(labels: torch.Tensor, source_distribution, label_threshol
     return res
 
 
+# ---- invertible augmentations: per-sample dihedral transform of the last two axes (csrc/invaug.hip) ----
+# code: bit 0 transposes, bit 1 reverses the source row, bit 2 reverses the source column (include/tem_hip.h)
+DH_PATH_VEC, DH_PATH_SCALAR, DH_PATH_TILE, DH_PATH_TILE_PACKED = 0, 1, 2, 3
+_DH_ROT = (0, 5, 6, 3)   # torch.rot90(x, k, (-2, -1)) for k % 4 = 0, 1, 2, 3
+_DH_INVERSE = (0, 1, 2, 5, 4, 3, 6, 7)
+
+
+def dihedral_compose(first: int, then: int) -> int:
+    """the code of applying `first` and then `then` (host table arithmetic; no device is touched)"""
+    t_a, fr_a, fc_a = first & 1, (first >> 1) & 1, (first >> 2) & 1
+    t_b, fr_b, fc_b = then & 1, (then >> 1) & 1, (then >> 2) & 1
+    fr, fc = (fr_a ^ fc_b, fc_a ^ fr_b) if t_a else (fr_a ^ fr_b, fc_a ^ fc_b)
+    return (t_a ^ t_b) | (fr << 1) | (fc << 2)
+
+
+def _host_ints(values, what: str):
+    if isinstance(values, torch.Tensor):
+        if values.is_cuda:
+            raise ValueError(f"{what}: expected host values (a sequence or a CPU tensor), got a device tensor")
+        values = values.reshape(-1).tolist()
+    elif isinstance(values, (bool, int)):
+        values = [values]
+    out = []
+    for v in values:
+        if int(v) != v:
+            raise ValueError(f"{what}: expected integers, got {v!r}")
+        out.append(int(v))
+    return out
+
+
+def dihedral_codes(h, v, k):
+    """One code per sample for `x.flip(-1)` where h, then `.flip(-2)` where v, then `torch.rot90(., k, (-2, -1))`: h, v, k are
+    host values, one per sample (numbers, sequences or CPU tensors of equal length) -> list of ints in 0..7."""
+    h, v, k = _host_ints(h, "dihedral_codes: h"), _host_ints(v, "dihedral_codes: v"), _host_ints(k, "dihedral_codes: k")
+    if not len(h) == len(v) == len(k):
+        raise ValueError(f"dihedral_codes: h, v and k must have one entry per sample, got {len(h)}, {len(v)}, {len(k)}")
+    return [dihedral_compose(dihedral_compose(4 if a else 0, 2 if b else 0), _DH_ROT[c % 4]) for a, b, c in zip(h, v, k)]
+
+
+def _dh_codes(codes, what: str):
+    codes = _host_ints(codes, what)
+    bad = [c for c in codes if not 0 <= c <= 7]
+    if bad:
+        raise ValueError(f"{what}: codes must be within 0..7, got {bad[0]}")
+    return codes
+
+
+def dihedral_inverse(codes):
+    """the codes that undo `codes`: 3 <-> 5, every other element of D4 is its own inverse"""
+    return [_DH_INVERSE[c] for c in _dh_codes(codes, "dihedral_inverse")]
+
+
+_DH_ELEM = {torch.float32, torch.float16, torch.bfloat16, torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32}
+
+
+def _dh_plan(x: torch.Tensor, codes, inverse: bool):
+    """every check of `dihedral` that needs no device -> (codes to launch, output shape)"""
+    if not isinstance(x, torch.Tensor) or x.dim() not in (4, 5):
+        raise ValueError("dihedral: expected a 4d [N,C,H,W] or 5d [N,C,D,H,W] tensor, got "
+                         f"{tuple(x.shape) if isinstance(x, torch.Tensor) else type(x).__name__}")
+    if x.dtype not in _DH_ELEM:
+        raise ValueError(f"dihedral: elements of 1, 2 or 4 bytes are moved (float32, float16, bfloat16, bool, ...), got {x.dtype}")
+    if x.numel() == 0:
+        raise ValueError(f"dihedral: expected a non-empty tensor, got shape {tuple(x.shape)}")
+    codes = _dh_codes(codes, "dihedral")
+    N, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    if len(codes) != N:
+        raise ValueError(f"dihedral: expected one code per sample ({N}), got {len(codes)}")
+    if inverse:
+        codes = [_DH_INVERSE[c] for c in codes]
+    odd = sum(c & 1 for c in codes)
+    if H != W and 0 < odd < N:
+        raise ValueError(f"dihedral: codes {codes} mix transposing and non-transposing elements, which needs H == W (got {H} x {W}: "
+                         "the samples of one output tensor must share a shape)")
+    shape = tuple(x.shape[:-2]) + ((W, H) if odd else (H, W))
+    return codes, shape
+
+
+def _dh_launch(x: torch.Tensor, codes, shape, out=None) -> torch.Tensor:
+    _req_cuda(x)
+    x = x.contiguous()
+    dev = torch.tensor(codes, dtype=torch.int32).pin_memory().to(x.device, non_blocking=True)
+    y = torch.empty(shape, dtype=x.dtype, device=x.device) if out is None else out
+    N, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    _lib.check(_lib.load().tem_dihedral2d(_p(x), _p(y), _p(dev), N, x.numel() // (N * H * W), H, W, x.element_size(), _stream(x)),
+               "tem_dihedral2d")
+    return y
+
+
+class _Dihedral(torch.autograd.Function):
+    """y = P x with P a permutation: the gradient is the inverse permutation of the incoming one, the same launch"""
+
+    @staticmethod
+    def forward(ctx, x, codes, shape):
+        ctx.codes, ctx.shape = codes, tuple(x.shape)
+        return _dh_launch(x, codes, shape)
+
+    @staticmethod
+    def backward(ctx, grad):
+        return _dh_launch(grad, [_DH_INVERSE[c] for c in ctx.codes], ctx.shape), None, None
+
+
+def dihedral(x: torch.Tensor, codes, inverse: bool = False, out=None) -> torch.Tensor:
+    """Per-sample element of the dihedral group D4 on the last two axes of x [N,C,H,W] / [N,C,D,H,W], one launch at copy
+    speed, exact to the bit (tem_dihedral2d).  `codes`: HOST values, one per sample (a sequence or a CPU tensor; see
+    `dihedral_codes`), uploaded asynchronously; `inverse=True` applies the inverse elements instead.  -> a new tensor,
+    [..., W, H] when the codes transpose.  Differentiable: the backward pass is the same launch with the inverse codes.
+    ValueError for a code outside 0..7, a wrong number of codes, or transposing and non-transposing codes in one call
+    when H != W.  `out=` is a TEST HOOK (no library caller uses it): write into this contiguous tensor of the output's shape
+    and dtype, so a test can lay the output out between guard zones."""
+    codes, shape = _dh_plan(x, codes, inverse)
+    if out is not None:
+        if (not isinstance(out, torch.Tensor) or out.dtype != x.dtype or tuple(out.shape) != shape or not out.is_contiguous()
+                or out.device != x.device):
+            raise ValueError("dihedral: `out` must be a contiguous tensor of the output's shape, dtype and device")
+        return _dh_launch(x, codes, shape, out)
+    if torch.is_grad_enabled() and x.requires_grad:
+        return _Dihedral.apply(x, codes, shape)
+    return _dh_launch(x, codes, shape)
+
+
+def dihedral_path(x: torch.Tensor, code: int, out=None) -> int:
+    """the path a sample with `code` takes when `dihedral(x, ..., out=out)` runs (tem_dihedral2d_path; launches nothing):
+    DH_PATH_VEC, DH_PATH_SCALAR, DH_PATH_TILE or DH_PATH_TILE_PACKED"""
+    N, H, W = x.shape[0], x.shape[-2], x.shape[-1]
+    y = torch.empty_like(x) if out is None else out
+    rc = _lib.load().tem_dihedral2d_path(_p(x), _p(y), int(code), N, x.numel() // (N * H * W), H, W, x.element_size())
+    if rc < 0:
+        _lib.check(-1, "tem_dihedral2d_path")
+    return rc
+
+
 # ---------------------------------------------------------------- clDice ----
 # modes of tem_cldice_step (include/tem_hip.h)
 CLD_ROUND0, CLD_ROUND, CLD_ERODE, CLD_OPEN, CLD_DILATE, CLD_BWD_POINT0, CLD_BWD_POINT = range(7)

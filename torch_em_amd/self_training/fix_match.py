@@ -27,9 +27,9 @@ from typing import Callable, Optional, Sequence
 import torch
 
 from .. import ops
-from .mean_teacher import _PARTS, Dummy, SelfTrainingTrainer
+from .mean_teacher import _PARTS, Dummy, InvertibleAugmentationsMixin, SelfTrainingTrainer
 
-__all__ = ["FixMatchTrainer"]
+__all__ = ["FixMatchTrainer", "FixMatchTrainerWithInvertibleAugmentations"]
 
 
 class FixMatchTrainer(SelfTrainingTrainer):
@@ -114,3 +114,26 @@ class FixMatchTrainer(SelfTrainingTrainer):
             loss = (supervised_loss + unsupervised_loss) / 2
             self._backprop(loss)
         return supervised_loss, unsupervised_loss, loss, pseudo_labels, label_filter
+
+
+class FixMatchTrainerWithInvertibleAugmentations(InvertibleAugmentationsMixin, FixMatchTrainer):
+    """`FixMatchTrainer` whose views come from `augmenter` (a `FixMatchAugmenters`: weak teacher view, strong student view)
+    and whose losses take predictions in the common frame: the loops and their order of operations are
+    `mean_teacher.InvertibleAugmentationsMixin`'s (reference `fix_match.py:371-689`).  Its own: the labels are detached and
+    aligned to `source_distribution` BEFORE they are mapped back (training only), and -- unlike the plain `FixMatchTrainer` --
+    `pseudo_labeler.step` follows every unsupervised validation."""
+    _PARTS = tuple(k for k in FixMatchTrainer._PARTS if k != "view_transforms") + ("augmenter",)
+
+    def __init__(self, model: torch.nn.Module, unsupervised_train_loader, unsupervised_loss: Callable, pseudo_labeler: Callable,
+                 augmenter, **kwargs):
+        if kwargs.get("view_transforms") is not None:
+            raise ValueError(f"{type(self).__name__}: the views come from `augmenter`; view_transforms must be None")
+        self._set_augmenter(augmenter)
+        super().__init__(model=model, unsupervised_train_loader=unsupervised_train_loader, unsupervised_loss=unsupervised_loss,
+                         pseudo_labeler=pseudo_labeler, **kwargs)
+
+    def _prepare_labels(self, pseudo_labels, label_filter):
+        pseudo_labels = pseudo_labels.detach()
+        if label_filter is not None:
+            label_filter = label_filter.detach()
+        return self.get_distribution_alignment(pseudo_labels), label_filter

@@ -22,6 +22,11 @@ its own gradient arena, which autograd adds.  `FusedAdamW` then takes its per-te
 step has one node and stays on the one-launch path.
 
 `SelfTrainingTrainer` holds what this trainer shares with `FixMatchTrainer` (fix_match.py).
+
+At the end of the file: `MeanTeacherTrainerWithInvertibleAugmentations` (reference `:402-723`) and the
+`InvertibleAugmentationsMixin` it shares with `FixMatchTrainerWithInvertibleAugmentations` -- one raw batch from the loader,
+views formed and inverted on the device (transform/invertible_augmentations.py), losses that take predictions.  The places
+where their order of operations differs from the trainers above are listed in the mixin's docstring.
 """
 import os
 import pickle
@@ -434,3 +439,176 @@ class MeanTeacherTrainer(SelfTrainingTrainer):
             loss = (supervised_loss + unsupervised_loss) / 2
             self._backprop(loss)
         return supervised_loss, unsupervised_loss, loss, pseudo_labels, label_filter
+
+
+class InvertibleAugmentationsMixin:
+    """The loops of the reference's `MeanTeacherTrainerWithInvertibleAugmentations` (`mean_teacher.py:402-723`) and
+    `FixMatchTrainerWithInvertibleAugmentations` (`fix_match.py:371-689`), which differ only in what the hooks of
+    `SelfTrainingTrainer` say: the unsupervised loaders yield ONE raw batch, `augmenter.teacher` / `augmenter.student`
+    (transform/invertible_augmentations.py) form the two views on the device, and pseudo labels, label filter and student
+    prediction are mapped back into the common frame (one `ops.dihedral` launch each) before the loss.  The losses take
+    PREDICTIONS: `unsupervised_loss(pred, labels, filter)`, `supervised_loss(pred, labels)` and the `*_loss_and_metric`
+    variants alike (self_training/loss.py: `SelfTrainingLossWithInvertibleAugmentations`, ...).
+
+    Where the order of operations differs from the base trainers, it is the reference's:
+      * `augmenter.reset_all()` at the start of every batch, training and validation;
+      * the views are formed before `zero_grad` and before any model runs, teacher first, then student;
+      * the sampler sees the UN-inverted pseudo labels and filter;
+      * the student runs once per step -- its prediction is inverted and handed to the loss, and the logger gets that same
+        prediction (the base trainers run the model again for the logger);
+      * `pseudo_labeler.step` follows the unsupervised validation in BOTH variants (the plain FixMatchTrainer never steps);
+      * logger calls: `log_train_unsupervised(it, loss, x, x, pred_inv, labels_inv, filter_inv)` with the raw batch twice,
+        then `log_train_augmentations(it, view1, view2, labels, pred)` -- and `log_validation_augmentations` -- when the
+        logger object has them.
+    `raw_transform` is applied to the raw batch before the augmenter; supervised batches take the trainer's usual pre-pass.
+    `hip_graph=True` is refused as by the base class; `augmenter` joins the checkpoint record."""
+    _AUGMENTER_VIEWS = ("teacher", "student")
+
+    def _set_augmenter(self, augmenter):
+        missing = [v for v in self._AUGMENTER_VIEWS + ("reset_all",) if not hasattr(augmenter, v)]
+        if missing:
+            raise ValueError(f"{type(self).__name__}: the augmenter lacks {missing} (see transform/invertible_augmentations.py)")
+        self.augmenter = augmenter
+
+    def _raw_batch(self, batch):
+        if isinstance(batch, (list, tuple)):
+            if len(batch) != 1:
+                raise ValueError(f"{type(self).__name__}: the unsupervised loaders yield one raw batch")
+            batch = batch[0]
+        return self._raw(batch)
+
+    def _two_views(self, batch):
+        """-> (raw batch, teacher view, student view), after `reset_all`"""
+        self.augmenter.reset_all()
+        xu = self._raw_batch(batch)
+        return xu, self.augmenter.teacher.transform(xu), self.augmenter.student.transform(xu)
+
+    def _prepare_labels(self, pseudo_labels, label_filter):
+        """between the labeler and the inversion, in training (FixMatch: detach and align)"""
+        return pseudo_labels, label_filter
+
+    def _inverted_labels(self, teacher_input, train: bool):
+        """-> (labels, filter, labels in the common frame, filter in the common frame)"""
+        with self._precision(), torch.no_grad():
+            pseudo_labels, label_filter = self.pseudo_labeler(self._labeling_model(), teacher_input)
+            if train:
+                pseudo_labels, label_filter = self._prepare_labels(pseudo_labels, label_filter)
+            inverse = self.augmenter.teacher.reverse_transform
+            return pseudo_labels, label_filter, inverse(pseudo_labels), None if label_filter is None else inverse(label_filter)
+
+    def _log_if_present(self, name, *args):
+        log = getattr(self.logger, name, None)
+        if log is not None:
+            log(*args)
+
+    def _shown(self, pred):
+        return pred if self._iteration % self.log_image_interval == 0 else None
+
+    # ---- loops ------------------------------------------------------------------------------------
+    def _train_epoch_unsupervised(self, progress):
+        self.model.train()
+        n_iter, t0 = 0, time.time()
+        for batch in self.unsupervised_train_loader:
+            xu, xu1, xu2 = self._two_views(batch)
+            pseudo_labels, label_filter, labels_inv, filter_inv = self._inverted_labels(xu1, train=True)
+            sampler = getattr(self, "sampler", None)
+            if sampler is not None and not sampler(pseudo_labels, label_filter):
+                continue
+            self.optimizer.zero_grad()
+            with self._precision():
+                pred = self.model(xu2)
+                pred_inv = self.augmenter.student.reverse_transform(pred)
+                loss = self.unsupervised_loss(pred_inv, labels_inv, filter_inv)
+                self._backprop(loss)
+            if self.logger is not None:
+                self.logger.log_train_unsupervised(self._iteration, loss, xu, xu, pred_inv, labels_inv, filter_inv)
+                self._log_if_present("log_train_augmentations", self._iteration, xu1, xu2, pseudo_labels, self._shown(pred))
+                self._log_common()
+            self._after_step()
+            self._iteration += 1
+            n_iter += 1
+            if self._iteration >= self.max_iteration:
+                break
+            progress.update(1)
+        return (time.time() - t0) / max(n_iter, 1)
+
+    def _train_epoch_semisupervised(self, progress):
+        self.model.train()
+        n_iter, t0 = 0, time.time()
+        prepass = self._prepass(train=True)
+        for (xs, ys), batch in zip(self.supervised_train_loader, self.unsupervised_train_loader):
+            xs, ys = prepass(_to(xs, self.device), _to(ys, self.device))
+            xu, xu1, xu2 = self._two_views(batch)
+            self.optimizer.zero_grad()
+            with self._precision():
+                supervised_pred = self.model(xs)
+                supervised_loss = self.supervised_loss(supervised_pred, ys)
+            pseudo_labels, label_filter, labels_inv, filter_inv = self._inverted_labels(xu1, train=True)
+            with self._precision():
+                unsup_pred = self.model(xu2)
+                unsup_pred_inv = self.augmenter.student.reverse_transform(unsup_pred)
+                unsupervised_loss = self.unsupervised_loss(unsup_pred_inv, labels_inv, filter_inv)
+                loss = (supervised_loss + unsupervised_loss) / 2
+                self._backprop(loss)
+            if self.logger is not None:
+                self.logger.log_train_supervised(self._iteration, supervised_loss, xs, ys, self._shown(supervised_pred))
+                self.logger.log_train_unsupervised(self._iteration, unsupervised_loss, xu, xu, unsup_pred_inv, labels_inv, filter_inv)
+                self._log_if_present("log_train_augmentations", self._iteration, xu1, xu2, pseudo_labels, self._shown(unsup_pred))
+                self.logger.log_combined_loss(self._iteration, loss)
+                self._log_common()
+            self._after_step()
+            self._iteration += 1
+            n_iter += 1
+            if self._iteration >= self.max_iteration:
+                break
+            progress.update(1)
+        return (time.time() - t0) / max(n_iter, 1)
+
+    def _validate_supervised(self):
+        metric_val = loss_val = None
+        prepass = self._prepass(train=False)
+        for x, y in self.supervised_val_loader:
+            x, y = prepass(_to(x, self.device), _to(y, self.device))
+            with self._precision():
+                pred = self.model(x)
+                loss, metric = self.supervised_loss_and_metric(pred, y)
+            loss_val = loss.detach() if loss_val is None else loss_val + loss.detach()
+            metric_val = metric.detach() if metric_val is None else metric_val + metric.detach()
+        n = len(self.supervised_val_loader)
+        metric_val, loss_val = float(metric_val) / n, float(loss_val) / n
+        if self.logger is not None:
+            self.logger.log_validation_supervised(self._iteration, metric_val, loss_val, x, y, pred)
+        return metric_val
+
+    def _validate_unsupervised(self):
+        metric_val = loss_val = None
+        for batch in self.unsupervised_val_loader:
+            x, x1, x2 = self._two_views(batch)
+            pseudo_labels, label_filter, labels_inv, filter_inv = self._inverted_labels(x1, train=False)
+            with self._precision():
+                pred = self.model(x2)
+                pred_inv = self.augmenter.student.reverse_transform(pred)
+                loss, metric = self.unsupervised_loss_and_metric(pred_inv, labels_inv, filter_inv)
+            loss_val = loss.detach() if loss_val is None else loss_val + loss.detach()
+            metric_val = metric.detach() if metric_val is None else metric_val + metric.detach()
+        n = len(self.unsupervised_val_loader)
+        metric_val, loss_val = float(metric_val) / n, float(loss_val) / n
+        if self.logger is not None:
+            self.logger.log_validation_unsupervised(self._iteration, metric_val, loss_val, x, x, pred_inv, labels_inv, filter_inv)
+            self._log_if_present("log_validation_augmentations", self._iteration, x1, x2, pseudo_labels, pred)
+        self.pseudo_labeler.step(metric_val, self._epoch)
+        return metric_val
+
+
+class MeanTeacherTrainerWithInvertibleAugmentations(InvertibleAugmentationsMixin, MeanTeacherTrainer):
+    """`MeanTeacherTrainer` whose views come from `augmenter` (a `MeanTeacherAugmenters`) and whose losses take predictions
+    in the common frame: see `InvertibleAugmentationsMixin`.  Constructor as the reference (`mean_teacher.py:466-502`)."""
+    _PARTS = tuple(k for k in _PARTS if k != "view_transforms") + ("augmenter",)
+
+    def __init__(self, model: torch.nn.Module, unsupervised_train_loader, unsupervised_loss: Callable, pseudo_labeler: Callable,
+                 augmenter, **kwargs):
+        if kwargs.get("view_transforms") is not None:
+            raise ValueError(f"{type(self).__name__}: the views come from `augmenter`; view_transforms must be None")
+        self._set_augmenter(augmenter)
+        super().__init__(model=model, unsupervised_train_loader=unsupervised_train_loader, unsupervised_loss=unsupervised_loss,
+                         pseudo_labeler=pseudo_labeler, **kwargs)

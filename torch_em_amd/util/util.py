@@ -90,7 +90,7 @@ def get_constructor_arguments(obj) -> dict:
 
 def get_trainer(checkpoint, name: str = "best", device=None):
     """Trainer from a checkpoint FOLDER (or the trainer itself, passed through).  A checkpoint that names its trainer class
-    (`init.trainer_class`: MeanTeacherTrainer, FixMatchTrainer) is rebuilt by that class, any other by DefaultTrainer."""
+    (`init.trainer_class`: the self-training trainers) is rebuilt by that class, any other by DefaultTrainer."""
     from ..trainer import DefaultTrainer
     if isinstance(checkpoint, str):
         assert os.path.exists(checkpoint), checkpoint
