@@ -1087,6 +1087,42 @@ int tem_rawaug_poisson_scaled(const float* x, float* y, int N, int64_t L, const 
 int tem_rawaug_blur2d(const float* x, float* y, int64_t P, int H, int W, const float* wy, const float* wx, int ky, int kx,
                       tem_stream_t stream);
 
+/* ---- EM defect augmentation (transform/defect.py: EMDefectAugmentation :41-245; csrc/defect.hip) -------------------------
+ * x, y: S contiguous float32 slices of H x W (L = H * W; any 4-byte aligned base).  Two device tables written by the host
+ * describe a call, so the launches do not depend on what the plan says:
+ *   plan[S][4] (int32): code (0 keep, 1 drop, 2 low contrast, 3 paste, 4 deformed), plane of `art` / `alpha` (paste), the
+ *              bits of the float32 contrast scale, 0
+ *   rec[D][8]  (int32), one per deformed slice: slice, mode (0 undirected, 1 compress with one line interval per row,
+ *              2 compress with one per column), offset of the slice's interval table in `tables`, stream row of its first
+ *              noise field (the second: + 1), the bits of the float32 flow of the positive side along columns and along
+ *              rows, the bits of cval, 0
+ *   tables     (int32): per compress slice H (mode 1) or W (mode 2) entries lo | hi << 16: the line covers lo..hi there
+ * The noise is noise(row, i) = 2u - 1, u = (w0 >> 8) * 2^-24 of the Philox stream above at round 0, i = r * W + c.
+ * Nothing reads device memory back, allocates or synchronises; no atomics: all results are bitwise reproducible. */
+/* mean[n] (device) = float32 of the float64 mean of slice n where plan says low contrast, 0 elsewhere */
+int tem_defect_mean(const float* x, int S, int64_t L, const int32_t* plan, float* mean, tem_stream_t stream);
+/* y = x (keep), 0 (drop), fl32(fl32(fl32(x - mean[n]) * scale) + mean[n]) (low contrast), fl32(fl32(x * fl32(1 - alpha)) +
+ * fl32(art * alpha)) with plane plan[n][1] of art / alpha (paste; both may be NULL if no slice pastes); deformed slices are
+ * NOT written (tem_defect_warp writes them).  S <= 65535; y must not be x. */
+int tem_defect_apply(const float* x, float* y, int S, int64_t L, const int32_t* plan, const float* mean, const float* art,
+                     const float* alpha, tem_stream_t stream);
+/* flow[d][f] (D x 2 planes of H x W) = the noise plane of stream row rec[d][3] + f times `strength` (one rounded product),
+ * filtered along W, then along H, with the k weights w (device; k odd, <= 33), edge repeat (the noise of the clamped index);
+ * fused multiply-adds in tap order.  Records of mode != 0 are skipped.  f = 0 displaces columns, f = 1 rows.  H, W >= 4. */
+int tem_defect_flow(float* flow, int D, int H, int W, const int32_t* rec, uint64_t seed, float strength, const float* w, int k,
+                    tem_stream_t stream);
+/* coef[d] = slice rec[d][0] of x filtered along W, then along H, with the k weights w (device; k odd, <= 33), whole-sample
+ * mirror border (period 2(n - 1)).  With w[j] = sqrt(3) z^|j - k/2|, z = sqrt(3) - 2, these are the cubic B-spline
+ * coefficients of scipy.ndimage.spline_filter(order=3, mode="mirror") up to |z|^(k/2 + 1). */
+int tem_defect_prefilter(const float* x, float* coef, int D, int H, int W, const int32_t* rec, const float* w, int k,
+                         tem_stream_t stream);
+/* slice rec[d][0] of y = the cubic B-spline interpolant of coef[d] at (r + flow_r, c + flow_c): cval outside
+ * [0, H-1] x [0, W-1], else the 4 x 4 weighted sum over mirrored indices, in float64, rounded once.  Mode 0: the flow is
+ * flow[d]; compress: fl32(double(side * rec flow) + noise * noise_scale) per axis, side from the interval table, and 0
+ * wherever the L1 distance to a pixel of the line is <= 10. */
+int tem_defect_warp(const float* coef, const float* flow, float* y, int D, int H, int W, const int32_t* rec,
+                    const int32_t* tables, uint64_t seed, double noise_scale, tem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

@@ -234,6 +234,12 @@ SIGNATURES = {
     "tem_rawaug_poisson_add": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_u64, c_u32, c_int, c_float, c_float, c_vp]),
     "tem_rawaug_poisson_scaled": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_u64, c_u32, c_int, c_float, c_float, c_vp]),
     "tem_rawaug_blur2d": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp]),
+    # EM defect augmentation (csrc/defect.hip): plan int32 [S][4], rec int32 [D][8], tables int32 (include/tem_hip.h)
+    "tem_defect_mean": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp]),
+    "tem_defect_apply": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),
+    "tem_defect_flow": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_u64, c_float, c_vp, c_int, c_vp]),
+    "tem_defect_prefilter": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp]),
+    "tem_defect_warp": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_u64, c_double, c_vp]),
 }
 
 _lib = None

@@ -1773,6 +1773,141 @@ def blur2d(x: torch.Tensor, wy, wx=None) -> torch.Tensor:
     return y
 
 
+# ---- EM defect augmentation (csrc/defect.hip; the tables: include/tem_hip.h, host side: transform/defect.py) ----
+DEFECT_KEEP, DEFECT_DROP, DEFECT_LOW, DEFECT_PASTE, DEFECT_DEFORM = range(5)
+DEFECT_KMAX = 33   # taps of the separable filter
+
+
+def _to_device(host, device) -> torch.Tensor:
+    """a small host numpy array -> the device, through pinned memory, on the current stream, without a synchronisation"""
+    return torch.from_numpy(host).pin_memory().to(device, non_blocking=True)
+
+
+def _slices(x: torch.Tensor, what: str):
+    _req_cuda(x)
+    if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
+        raise ValueError(f"{what}: expected a contiguous float32 tensor [S, H, W], got {x.dtype} {tuple(x.shape)}")
+    return int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
+
+
+class DefectTables:
+    """The device tables of one defect call (include/tem_hip.h), checked on the host before they are copied: the kernels
+    index with what they hold.  plan int32 [S, 4], rec int32 [D, 8] (None if D == 0), tables int32."""
+
+    def __init__(self, plan, rec, tables, S, H, W, planes, device):
+        import numpy as np
+        plan = np.ascontiguousarray(plan, dtype=np.int32).reshape(-1, 4)
+        rec = np.ascontiguousarray(rec, dtype=np.int32).reshape(-1, 8)
+        tables = np.ascontiguousarray(tables, dtype=np.int32).reshape(-1)
+        self.S, self.H, self.W, self.D, self.planes = int(S), int(H), int(W), int(rec.shape[0]), int(planes)
+        if self.H < 4 or self.W < 4 or self.H > 65535 or self.W > 65535 or not 0 < self.S <= 65535:
+            raise ValueError(f"defect: slices of 4 x 4 to 65535 x 65535 pixels, at most 65535 of them (got {S} of {H} x {W})")
+        code = plan[:, 0]
+        if plan.shape[0] != self.S or code.min() < DEFECT_KEEP or code.max() > DEFECT_DEFORM:
+            raise ValueError("defect: the plan holds one record with a code of 0..4 per slice")
+        paste = plan[code == DEFECT_PASTE, 1]
+        if paste.size and (paste.min() < 0 or paste.max() >= self.planes):
+            raise ValueError(f"defect: a pasted slice names an artifact plane outside [0, {self.planes})")
+        if sorted(rec[:, 0].tolist()) != np.nonzero(code == DEFECT_DEFORM)[0].tolist():
+            raise ValueError("defect: the records must name exactly the slices the plan marks deformed, each once")
+        for r in rec:
+            mode, off = int(r[1]), int(r[2])
+            if mode not in (0, 1, 2) or not 0 <= int(r[3]) + 1 < 2 ** 31:
+                raise ValueError("defect: a record's mode is 0, 1 or 2 and its stream rows lie within [0, 2^31)")
+            if mode:
+                n, other = (self.H, self.W) if mode == 1 else (self.W, self.H)
+                if off < 0 or off + n > tables.size:
+                    raise ValueError("defect: an interval table does not lie within `tables`")
+                lo, hi = tables[off:off + n] & 0xffff, (tables[off:off + n] >> 16) & 0xffff
+                if (lo > hi).any() or hi.max() >= other:
+                    raise ValueError("defect: an interval of a line leaves the slice")
+        self.plan = _to_device(plan, device)
+        self.rec = _to_device(rec, device) if self.D else None
+        self.tables = _to_device(tables if tables.size else np.zeros(1, np.int32), device)
+
+    def _geom(self, x, what):
+        if _slices(x, what) != (self.S, self.H, self.W) or x.device != self.plan.device:
+            raise ValueError(f"{what}: the tables were made for [{self.S}, {self.H}, {self.W}] on {self.plan.device}")
+
+
+def defect_mean(x: torch.Tensor, tab: DefectTables) -> torch.Tensor:
+    """float32 [S]: the mean of every slice the plan marks low contrast (summed in float64 in a fixed order), 0 elsewhere"""
+    tab._geom(x, "defect_mean")
+    mean = torch.empty((tab.S,), dtype=torch.float32, device=x.device)
+    _lib.check(_lib.load().tem_defect_mean(_p(x), tab.S, tab.H * tab.W, _p(tab.plan), _p(mean), _stream(x)), "tem_defect_mean")
+    return mean
+
+
+def defect_apply(x: torch.Tensor, tab: DefectTables, mean: torch.Tensor, art=None, alpha=None) -> torch.Tensor:
+    """The streaming pass over all slices: keep, drop, low contrast with `mean`, paste of plane plan[n, 1] of `art` / `alpha`
+    (float32 [planes, H, W]).  Deformed slices of the result are left unwritten: `defect_warp` fills them."""
+    tab._geom(x, "defect_apply")
+    if (art is None) != (alpha is None) or (art is None and tab.planes) or mean.dtype != torch.float32 or mean.numel() != tab.S \
+            or mean.device != x.device:
+        raise ValueError("defect_apply: art and alpha come together (the planes the tables were made for), mean is float32 [S]")
+    for t in (art, alpha):
+        if t is not None and (_slices(t, "defect_apply: art / alpha") != (tab.planes, tab.H, tab.W) or t.device != x.device):
+            raise ValueError(f"defect_apply: artifact and alpha planes must be [{tab.planes}, {tab.H}, {tab.W}] on {x.device}")
+    y = torch.empty_like(x)
+    _lib.check(_lib.load().tem_defect_apply(_p(x), _p(y), tab.S, tab.H * tab.W, _p(tab.plan), _p(mean), _p(art), _p(alpha), _stream(x)),
+               "tem_defect_apply")
+    return y
+
+
+def _defect_weights(w, device):
+    w = [float(v) for v in w]
+    if not (1 <= len(w) <= DEFECT_KMAX and len(w) % 2 == 1):
+        raise ValueError(f"defect: the filter takes an odd number of at most {DEFECT_KMAX} weights, got {len(w)}")
+    return _fill(w, len(w), device, "weights"), len(w)
+
+
+def _defect_out(out, shape, device, what):
+    if out is None:
+        return torch.empty(shape, dtype=torch.float32, device=device)
+    if tuple(out.shape) != tuple(shape) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != device:
+        raise ValueError(f"{what}: `out` must be a contiguous float32 tensor {tuple(shape)} on {device}")
+    return out
+
+
+def defect_flow(tab: DefectTables, seed: int, strength: float, weights, out=None) -> torch.Tensor:
+    """float32 [D, 2, H, W]: for every record of mode 0 the two noise planes (stream rows rec[d, 3], + 1) times `strength`,
+    filtered along W then H with the HOST `weights`, edge repeat; plane 0 displaces columns, plane 1 rows.  The planes of
+    compress records are not written."""
+    if not tab.D:
+        raise ValueError("defect_flow: no slice is deformed")
+    flow = _defect_out(out, (tab.D, 2, tab.H, tab.W), tab.plan.device, "defect_flow")
+    w, k = _defect_weights(weights, flow.device)
+    _lib.check(_lib.load().tem_defect_flow(_p(flow), tab.D, tab.H, tab.W, _p(tab.rec), _seed(seed), float(strength), _p(w), k,
+                                           _stream(flow)), "tem_defect_flow")
+    return flow
+
+
+def defect_prefilter(x: torch.Tensor, tab: DefectTables, weights, out=None) -> torch.Tensor:
+    """float32 [D, H, W]: slice rec[d, 0] of x filtered along W then H with the HOST `weights`, whole-sample mirror border
+    (`transform.defect.spline_fir_weights()`: the cubic B-spline coefficients)."""
+    tab._geom(x, "defect_prefilter")
+    if not tab.D:
+        raise ValueError("defect_prefilter: no slice is deformed")
+    coef = _defect_out(out, (tab.D, tab.H, tab.W), x.device, "defect_prefilter")
+    w, k = _defect_weights(weights, x.device)
+    _lib.check(_lib.load().tem_defect_prefilter(_p(x), _p(coef), tab.D, tab.H, tab.W, _p(tab.rec), _p(w), k, _stream(x)),
+               "tem_defect_prefilter")
+    return coef
+
+
+def defect_warp(coef: torch.Tensor, flow: torch.Tensor, y: torch.Tensor, tab: DefectTables, seed: int, noise_scale: float) -> torch.Tensor:
+    """Writes slice rec[d, 0] of y [S, H, W]: the cubic interpolant of coef[d] at the identity plus the flow (flow[d], or the
+    compress flow of the record and its interval table), cval outside the slice, 0 in the band of a compress line."""
+    tab._geom(y, "defect_warp")
+    if not tab.D:
+        raise ValueError("defect_warp: no slice is deformed")
+    _defect_out(coef, (tab.D, tab.H, tab.W), y.device, "defect_warp: coef")
+    _defect_out(flow, (tab.D, 2, tab.H, tab.W), y.device, "defect_warp: flow")
+    _lib.check(_lib.load().tem_defect_warp(_p(coef), _p(flow), _p(y), tab.D, tab.H, tab.W, _p(tab.rec), _p(tab.tables), _seed(seed),
+                                           float(noise_scale), _stream(y)), "tem_defect_warp")
+    return y
+
+
 # ---- distance-based instance segmentation (csrc/distance.hip) ----
 POD_DIST, POD_BOUNDARY, POD_DIRECTED, POD_FOREGROUND, POD_INSTANCES = 1, 2, 4, 8, 16
 

@@ -7,3 +7,4 @@ from .raw import (AdditiveGaussianNoise, AdditivePoissonNoise, GaussianBlur, Poi
                   normalize_percentile, standardize)
 from .augmentation import (KorniaAugmentationPipeline, RandomAffine, RandomAffine3D, RandomElasticDeformation, RandomRotation,
                            RandomElasticDeformationStacked, RandomRotation3D, get_augmentations)
+from .defect import EMDefectAugmentation
