@@ -12,7 +12,7 @@ Two input recipes.
 
 The selector rules the tables are written against (include/tem_hip.h: tem_conv3d_fwd_valu_path, tem_conv3d_wgrad_path) are
 restated in expected_fwd() / expected_wgrad(); every case names the kernel it is meant for, the rules must agree, and the
-library's query must agree with both.  A tensor is channels [lo, lo + C) of a Wd-channel buffer behind oracle/gpu_layout.py's
+library's query must agree with both.  A tensor is channels [lo, lo + C) of a Wd-channel buffer behind oracle/gpu_kit.py's
 PAD sentinels: address() gives the byte address the rules see.
 """
 import numpy as np
@@ -25,7 +25,7 @@ FWD_NAME = {-1: "refused", 0: "c1rows", 1: "cin1", 2: "cout1", 3: "proj_r", 4: "
 WG_GENERIC, WG_CIN1, WG_PROJ = 0, 1, 2                                        # TEM_WGRAD_*
 WG_NAME = {-1: "refused", 0: "wgrad_generic", 1: "wgrad_cin1", 2: "proj_wgrad"}
 ESIZE = {"f32": 4, "f16": 2, "bf16": 2}
-PAD = 64                                  # oracle/gpu_layout.py
+PAD = 64                                  # oracle/gpu_kit.py
 BASE = 1 << 20                            # a 256-byte aligned allocation, as the caching allocator returns them
 K333, K133, K111 = (3, 3, 3), (1, 3, 3), (1, 1, 1)
 KSIZES = [(a, b, c) for a in (1, 3) for b in (1, 3) for c in (1, 3)]

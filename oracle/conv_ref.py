@@ -22,13 +22,12 @@ pack w[tap][ci][co], tap = (tz kh + ty) kw + tx, of the correlation y[v] = sum_t
                               fma: exact product, one rounding) -- the yardstick "plain fp32 arithmetic", a reference and not
                               the code under test; e32 is the worse of the two against float64, in units
   units / within / outside16 / mismatches / amax_ok    the judge: units of 2^-23 x the per-element scale after the absolute
-                              allowance TINY (a sigmoid below 2^-126 is a float32 subnormal), MARGIN of oracle/dice_ref.py;
+                              allowance TINY (a sigmoid below 2^-126 is a float32 subnormal), the rule of oracle/judge.py;
                               equality as values for the lattice inputs (oracle/conv_cases.py)
 """
 import numpy as np
 
-from .dice_ref import MARGIN, TINY, U
-from .upsample_ref import band, excess16, interval16, outside16, round16, within  # noqa: F401  (the judge's pieces, re-exported)
+from . import judge as J
 
 f32 = np.float32
 NONE, RELU, SIGMOID = 0, 1, 2            # TEM_ACT_*
@@ -267,32 +266,17 @@ def out_bwd_f32(x, g, w_sd, fused=False):
 
 
 # ------------------------------------------------------------------------------------------------------- the judge
+# oracle/judge.py under the names the tests use; the absolute allowance TINY: a sigmoid below 2^-126 is a float32 subnormal
+U, TINY, MARGIN = J.U, J.TINY, J.MARGIN
+round16, stored = J.round16, J.stored
+band, within = J.band, J.within
+interval16, outside16, excess16 = J.interval16, J.outside16, J.excess16
+mismatches = J.mismatches                  # a NaN, an element never written, matches nothing
+
+
 def units(got, ref, scale):
-    """worst |got - ref| in units of 2^-23 x scale over EVERY element, after the absolute allowance TINY; a non-finite value,
-    a wrong shape, or an error where the scale is 0 counts as infinite"""
-    got, ref, scale = (np.asarray(v, np.float64) for v in (got, ref, scale))
-    if got.shape != ref.shape:
-        return float("inf")
-    scale = np.broadcast_to(scale, ref.shape)
-    excess = np.maximum(np.abs(got - ref) - TINY, 0.0)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        u = np.where(excess == 0.0, 0.0, excess / (U * scale))
-    u = np.where(np.isfinite(got), u, np.inf)
-    return float(np.nan_to_num(u, nan=np.inf, posinf=np.inf).max()) if u.size else 0.0
-
-
-def mismatches(got, want):
-    """the number of elements that are not the exact value (as values: -0.0 equals 0.0; a NaN, an element never written,
-    matches nothing); a wrong shape: every element"""
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    if got.shape != want.shape:
-        return int(want.size)
-    return int((~(got == want)).sum())
-
-
-def stored(val, dt):
-    """the exact value as the storage type holds it"""
-    return np.asarray(val, np.float64) if dt == "f32" else round16(val, dt)
+    """judge.units after the absolute allowance TINY"""
+    return J.units(got, ref, scale, tiny=TINY)
 
 
 def amax_ok(word, gx, dt):

@@ -12,15 +12,15 @@ All tensors are LOGICAL numpy arrays [N, C, V] (any trailing shape is flattened)
   dice_grad_f64      -> the gradient for the float32-valued ca / cb / gout / weights the kernel receives (one-step error)
   *_f32              the same three in numpy float32 with one rounding per operation: the yardstick "plain fp32
                      arithmetic" of the tests, a reference and not the code under test
-  grad_scale, sums_units, grad_units, finalize_units, within: the judge (units of 2^-23 x a per-quantity scale)
+  grad_scale, sums_units, grad_units, finalize_units, within: the judge (oracle/judge.py: units of 2^-23 x a per-quantity
+                     scale, here after the absolute allowance TINY)
 """
 import numpy as np
 
+from . import judge as J
+
 LOGITS, BCE = 1, 2                      # TEM_DICE_LOGITS, TEM_DICE_BCE
 REDUCE = {None: 0, "none": 0, "sum": 1, "mean": 2, "max": 3, "min": 4}
-U = 2.0 ** -23
-TINY = 2.0 ** -126                      # absolute allowance: sigmoid(-90) is a float32 subnormal
-MARGIN = 4.0                            # the project's margin over plain fp32 arithmetic (tests/test_gpu_optim.py)
 BCE_EPS = float(np.float32(1e-12))      # aten binary_cross_entropy_backward: a float constant
 
 
@@ -218,17 +218,13 @@ def dice_grad_f32(p, t, mask, ca, cb, gout=None, per_channel=False, flags=0, w_d
 
 
 # ------------------------------------------------------------------------------------------------------- the judge
+# oracle/judge.py under the names the tests use; the absolute allowance TINY: sigmoid(-90) is a float32 subnormal
+U, TINY, MARGIN, within = J.U, J.TINY, J.MARGIN, J.within
+
+
 def _units(got, ref, scale):
-    """worst |got - ref| in units of 2^-23 x scale after the absolute allowance TINY; a non-finite or missing value, or an
-    error where the scale is 0, counts as infinite"""
-    got, ref, scale = (np.asarray(v, np.float64) for v in (got, ref, scale))
-    if got.shape != ref.shape:
-        return float("inf")
-    excess = np.maximum(np.abs(got - ref) - TINY, 0.0)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        u = np.where(excess == 0.0, 0.0, excess / (U * scale))
-    u = np.where(np.isfinite(got), u, np.inf)
-    return float(np.nan_to_num(u, nan=np.inf, posinf=np.inf).max()) if u.size else 0.0
+    """judge.units after the absolute allowance TINY"""
+    return J.units(got, ref, scale, tiny=TINY)
 
 
 def sums_units(got, ref):
@@ -246,8 +242,3 @@ def grad_units(got, ref, scale):
 def finalize_units(got, ref):
     """the float32 rounding of the float64 result: units of 2^-23 |value|"""
     return _units(got, ref, np.abs(np.asarray(ref, np.float64)))
-
-
-def within(kernel_units, f32_units):
-    """the rule of tests/test_gpu_optim.py: kernel <= MARGIN * max(e32, 1)"""
-    return kernel_units <= MARGIN * max(f32_units, 1.0)

@@ -21,7 +21,7 @@ from . import upsample_cases as UK
 VEC1, VEC4, VEC8, PACKED16_FZ1, PACKED16_FZ2 = 0, 1, 2, 3, 4
 PATH_NAME = {0: "vec<1>", 1: "vec<4>", 2: "vec<8>", 3: "packed16<fz1>", 4: "packed16<fz2>"}
 VEC_OF = {VEC1: 1, VEC4: 4, VEC8: 8, PACKED16_FZ1: 8, PACKED16_FZ2: 8}
-PAD_BYTES = 128                       # oracle/gpu_layout.py: PAD elements of at least 2 bytes in front of a 256-byte aligned buffer
+PAD_BYTES = 128                       # oracle/gpu_kit.py: PAD elements of at least 2 bytes in front of a 256-byte aligned buffer
 
 
 def nwin(f):

@@ -29,13 +29,13 @@ The judge
   mismatches(got, want)     the number of elements that differ AS VALUES (+0.0 == -0.0, NaN matches NaN, a wrong shape: all)
   add_exact(gy, x, f, gskip, relu_mask, kind)   what a backward without coefficients must store: float32(gskip + gy) at the
                             arg-max, gskip (or 0) elsewhere, 0 under the mask; 16-bit: round16 of that
-  units / within / band / round16 / outside16: oracle/upsample_ref.py (units of 2^-23 x scale, MARGIN of oracle/dice_ref.py)
+  units / within / band / round16 / outside16: oracle/judge.py (units of 2^-23 x scale, no absolute allowance)
   amax_ok(word, stored, kind)   fp32: the word is the bit pattern of max |gx| as stored; 16-bit: round16(word) == max |gx stored|
 """
 import numpy as np
 
+from . import judge as J
 from . import norm_ref as NR
-from .upsample_ref import MARGIN, band, excess16, outside16, round16, round_common16, units, within  # noqa: F401  (the judge is shared)
 
 f32 = np.float32
 
@@ -177,11 +177,15 @@ def row_stats_e32(y, cq, ref, scale):
 
 
 # ------------------------------------------------------------------------------------------------------- the judge
+# oracle/judge.py under the names the tests use; no absolute allowance; an exact quantity may be NaN, and NaN matches NaN
+MARGIN = J.MARGIN
+round16, round_common16 = J.round16, J.round_common16
+units, band, within = J.units, J.band, J.within
+outside16, excess16 = J.outside16, J.excess16
+
+
 def mismatches(got, want):
-    got, want = np.asarray(got, np.float64), np.asarray(want, np.float64)
-    if got.shape != want.shape:
-        return int(want.size)
-    return int((~((got == want) | (np.isnan(got) & np.isnan(want)))).sum())
+    return J.mismatches(got, want, nan_equal=True)
 
 
 def add_exact(gy, x, f, gskip=None, relu_mask=False, kind="f32"):

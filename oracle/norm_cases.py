@@ -4,7 +4,7 @@ Tensors are logical [N, V, C]: seeded randn, channel c scaled by 2^((c % 5) - 2)
 factor of 2 or more), x plus a per-channel offset of about 0.7 (`offset` of the case: r9 / r9x use 16 / 27 and no zeros, so
 |mean| / sigma of a group is 6.8 .. 9.6 / 11.2 .. 15.6 -- a group's sigma is 1.7 .. 2.4 -- and ss / cnt - m^2 cancels
 6 .. 8 bits).  grid "16": rounded to values fp16,
-bf16 and fp32 all hold exactly (upsample_ref.round_common16).  Some x are exactly 0.0 and -0.0 (the ReLU mask `!(x > 0)`);
+bf16 and fp32 all hold exactly (judge.round_common16).  Some x are exactly 0.0 and -0.0 (the ReLU mask `!(x > 0)`);
 the last voxel of every sample has |x| >= the channel's mean |x| (and |g| >= mean |g|), so a dropped last voxel moves a sum by
 at least 2^23 / V units.  gamma = 1 + 0.3 randn, beta = 0.2 randn (tests/test_gpu_ops.py: test_norm_stats_and_backward).
 

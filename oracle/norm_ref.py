@@ -36,8 +36,8 @@ float32, the yardstick e32 "plain fp32 arithmetic" (a reference, not the code un
   apply_f32(g, x, coef, relu, v)      one rounding per operation; v & 1: a g - m1 as one fma, v & 2: u - d m2r as one fma.
                                       The compiler is free to contract: e32 of the apply is the worse of v = 0 and v = 3.
 
-The judge: errors in units of 2^-23 x a per-quantity scale (units / within / band of oracle/upsample_ref.py, MARGIN of
-oracle/dice_ref.py); every element within MARGIN max(e32, 1) units.  Scales:
+The judge: errors in units of 2^-23 x a per-quantity scale (units / within / band / MARGIN of oracle/judge.py, no absolute
+allowance); every element within MARGIN max(e32, 1) units.  Scales:
   sum x: sum |x|      sum x^2: its value      sum g: sum |g|      sum g xn: sum |g xn|
   mean: sum |x| / cnt                          var as computed (ss / cnt - m^2): E[x^2] + 2 |m| E|x|
 Derived quantities get the first-order propagation of the bands dm, dv, dS0, dS1 (ABSOLUTE half-widths, band(e32) x scale)
@@ -57,11 +57,15 @@ of what they are built from, plus one rounding to float32, RND |value| with RND 
 """
 import numpy as np
 
-from .dice_ref import MARGIN
-from .upsample_ref import band, round16, round_common16, units, within  # noqa: F401  (the judge is shared)
+from . import judge as J
 
 f32 = np.float32
 RND = 2.0 ** -24 * (1.0 + 2.0 ** -20)
+# oracle/judge.py under the names the tests use; no absolute allowance
+MARGIN = J.MARGIN
+round16, round_common16 = J.round16, J.round_common16
+units, band, within = J.units, J.band, J.within
+outside_interval, outside16_abs = J.outside_interval, J.outside16_abs
 
 
 def _nvc(a, dtype=np.float64):
@@ -333,20 +337,6 @@ def ratio_band(got, ref, d):
         q = np.where(err == 0.0, 0.0, err / np.broadcast_to(d, ref.shape))
     q = np.where(np.isfinite(got), q, np.inf)
     return MARGIN * float(np.nan_to_num(q, nan=np.inf, posinf=np.inf).max()) if q.size else 0.0
-
-
-def outside_interval(got, lo, hi):
-    """the number of elements outside their closed interval (non-finite ones and a wrong shape included)"""
-    got, lo, hi = (np.asarray(v, np.float64) for v in (got, lo, hi))
-    if got.shape != lo.shape:
-        return int(lo.size)
-    return int((~((got >= lo) & (got <= hi))).sum())
-
-
-def outside16_abs(got, ref, d, kind):
-    """16-bit stores: the number of elements outside [round16(ref - d), round16(ref + d)]"""
-    ref, d = np.asarray(ref, np.float64), np.asarray(d, np.float64)
-    return outside_interval(got, round16(ref - d, kind), round16(ref + d, kind))
 
 
 def judge_stats(got, ref, sums_scale, V, G, gamma=None, beta=None, eps=1e-5, e32=None):

@@ -9,8 +9,8 @@ smallest normal float: an fp32 result cannot be expected to agree below it):
 """
 import numpy as np
 
-U = 2.0 ** -23
-TINY = 2.0 ** -126
+from .judge import TINY, U
+
 DEFAULT = dict(lr=1e-3, b1=0.9, b2=0.999, eps=1e-8, wd=1e-2, grad_scale=1.0)
 
 # (growth, backoff, interval) -> probability of an overflow per step, chosen so that the scale keeps away from both

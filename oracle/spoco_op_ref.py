@@ -24,42 +24,29 @@ scale: the fp32 distance may fall on either side.
                                   allowances `allow` (fixed point, below) and TINY = 2^-126 (an exp that underflows in fp32
                                   is 1e-290 in float64)
   fix_allow(adds)                 adds x 2^-29: each fixed-point add rounds to the nearest 2^-28
-  within(ek, e32)                 ek <= MARGIN * max(e32, 1)
+  within(ek, e32)                 ek <= MARGIN * max(e32, 1)                          (units, within, MARGIN: oracle/judge.py)
 """
 import numpy as np
 
-from .dice_ref import MARGIN, U as EPS23
+from . import judge as J
 
 f64, f32 = np.float64, np.float32
-TINY = 2.0 ** -126
 NEAR = 2.0 ** -20
 ZCH = 1024                      # voxels per chunk of tem_zero_count
 SP_NCH, SP_IT, SP_MAXA, SP_MAXK, SP_MAXB = 8, 8, 64, 32, 1024
 
 
 # ------------------------------------------------------------------------------------------------------- the judge
+# oracle/judge.py under the names the tests use; the absolute allowances: `allow` per element (fixed point) and TINY
+TINY, MARGIN, within, band = J.TINY, J.MARGIN, J.within, J.band
+
+
 def units(got, ref, scale, allow=0.0):
-    got, ref, scale = (np.asarray(v, f64) for v in (got, ref, scale))
-    if got.shape != ref.shape:
-        return float("inf")
-    scale = np.broadcast_to(scale, ref.shape)
-    err = np.maximum(np.abs(got - ref) - np.broadcast_to(np.asarray(allow, f64), ref.shape) - TINY, 0.0)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        u = np.where(err == 0.0, 0.0, err / (EPS23 * scale))
-    u = np.where(np.isfinite(got), u, np.inf)
-    return float(np.nan_to_num(u, nan=np.inf, posinf=np.inf).max()) if u.size else 0.0
+    return J.units(got, ref, scale, allow=allow, tiny=TINY)
 
 
 def fix_allow(adds):
     return np.asarray(adds, f64) * 2.0 ** -29
-
-
-def within(ek, e32):
-    return ek <= MARGIN * max(float(e32), 1.0)
-
-
-def band(e32):
-    return MARGIN * max(float(e32), 1.0) * EPS23
 
 
 def exact(got, ref):

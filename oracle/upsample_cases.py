@@ -1,7 +1,7 @@
 """Inputs and the case tables shared by tests/test_upsample_cpu.py and tests/test_gpu_upsample.py (TEST INFRASTRUCTURE).
 
 Tensors: seeded randn, channel c scaled by 2^((c % 5) - 2) (a channel mix-up moves an element by a factor of 2 or more).
-grid "f32": the float32 values; grid "16": rounded to values fp16, bf16 and fp32 all hold exactly (upsample_ref.round_common16),
+grid "f32": the float32 values; grid "16": rounded to values fp16, bf16 and fp32 all hold exactly (judge.round_common16),
 so the two 16-bit types of a case share one float64 reference and a fp32 launch can run on the very same values.
 Coefficients (a, m1, m2r, mean) per (sample, channel), float32: a in [0.5, 2.5], m1 about 0.1, m2r about 0.05, mean about 1.
 

@@ -19,11 +19,12 @@ All tensors are channels-last numpy arrays [N, D, H, W, C]; f = (fz, fy, fx) are
   *_f32                     the same formulas in numpy float32 with one rounding per operation and float32 weights computed
                             as ATen computes them: the yardstick "plain fp32 arithmetic", a reference and not the code under test
                             (fused=True: the source index with one rounding, see _src32)
-  units, within, band, interval16, outside16, round16: the judge (units of 2^-23 x a per-element scale; MARGIN of oracle/dice_ref.py)
+  units, within, band, interval16, outside16, excess16, round16, round_common16, FMT, MARGIN: the judge of oracle/judge.py
+                            (units of 2^-23 x a per-element scale), here without an absolute allowance
 """
 import numpy as np
 
-from .dice_ref import MARGIN, U as EPS23
+from . import judge as J
 
 f32 = np.float32
 
@@ -276,68 +277,9 @@ def u_row_stats_f32(u, f, fused=False):
     return out.reshape(N, D * H, C, 2)
 
 
-# ------------------------------------------------------------------------------------------------------- 16-bit rounding
-FMT = {"f16": (11, -14), "bf16": (8, -126)}          # significant bits, exponent of the smallest normal number
-
-
-def round16(x, kind):
-    """float64 -> the nearest value of the 16-bit type (ties to even, gradual underflow), as float64; monotone.  No
-    overflow handling: the tests stay far below 65504."""
-    p, emin = FMT[kind]
-    x = np.asarray(x, np.float64)
-    _, e = np.frexp(x)                                 # |x| in [2^(e-1), 2^e)
-    q = np.ldexp(1.0, np.maximum(e - 1, emin) - (p - 1))
-    return np.rint(x / q) * q
-
-
-def round_common16(x):
-    """values every storage type holds exactly: rounded to fp16, then to bf16 (an fp16 number's bf16 rounding is an fp16
-    number again: fewer significant bits on the same exponent, subnormals included)"""
-    return round16(round16(x, "f16"), "bf16")
-
-
 # ------------------------------------------------------------------------------------------------------- the judge
-def units(got, ref, scale):
-    """worst |got - ref| in units of 2^-23 x scale over EVERY element; a non-finite value, a wrong shape, or an error where
-    the scale is 0 counts as infinite"""
-    got, ref, scale = (np.asarray(v, np.float64) for v in (got, ref, scale))
-    if got.shape != ref.shape:
-        return float("inf")
-    scale = np.broadcast_to(scale, ref.shape)
-    err = np.abs(got - ref)
-    with np.errstate(divide="ignore", invalid="ignore"):
-        u = np.where(err == 0.0, 0.0, err / (EPS23 * scale))
-    u = np.where(np.isfinite(got), u, np.inf)
-    return float(np.nan_to_num(u, nan=np.inf, posinf=np.inf).max()) if u.size else 0.0
-
-
-def band(e32):
-    """the allowed error per unit of scale: MARGIN * max(e32, 1) * 2^-23"""
-    return MARGIN * max(float(e32), 1.0) * EPS23
-
-
-def within(kernel_units, e32):
-    return kernel_units <= MARGIN * max(float(e32), 1.0)
-
-
-def interval16(ref, scale, e32, kind):
-    """the closed interval of 16-bit values a kernel that computes in fp32 within the band and rounds once may store"""
-    ref, scale = np.asarray(ref, np.float64), np.asarray(scale, np.float64)
-    b = band(e32) * scale
-    return round16(ref - b, kind), round16(ref + b, kind)
-
-
-def outside16(got, ref, scale, e32, kind):
-    """the number of stored elements outside their interval (non-finite ones included); a wrong shape: every element"""
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    if got.shape != ref.shape:
-        return int(ref.size)
-    lo, hi = interval16(ref, np.broadcast_to(scale, ref.shape), e32, kind)
-    return int((~((got >= lo) & (got <= hi))).sum())
-
-
-def excess16(got, ref, scale, kind):
-    """for the record: the worst error beyond the ideal rounding of the float64 value, in units of 2^-23 x scale"""
-    got, ref = np.asarray(got, np.float64), np.asarray(ref, np.float64)
-    extra = np.maximum(np.abs(got - ref) - np.abs(round16(ref, kind) - ref), 0.0)
-    return units(ref + extra, ref, scale)
+# oracle/judge.py under the names the tests use; this module takes no absolute allowance
+FMT, MARGIN = J.FMT, J.MARGIN
+round16, round_common16 = J.round16, J.round_common16
+units, band, within = J.units, J.band, J.within
+interval16, outside16, excess16 = J.interval16, J.outside16, J.excess16

@@ -12,7 +12,7 @@ Rules, none of them measured.
                      s (1 - s) (sum |terms| + 1) + s after the absolute allowance 2^-126; dw: sum_v |xhat g|); on the same inputs
                      e32 is the worst figure of the numpy float32 restatement (bias first, then (tap, ci) in order; products
                      rounded separately, and contracted) -- a reference, not the code under test.  EVERY fp32 element within
-                     MARGIN * max(e32, 1) units, MARGIN = 4 (oracle/dice_ref.py); every stored 16-bit element in
+                     MARGIN * max(e32, 1) units, MARGIN of oracle/judge.py: 4; every stored 16-bit element in
                      [round16(ref - band), round16(ref + band)].
   statistics rows    the units rule per (block, channel, quantity) against the float64 sums of the tensor AS STORED (just judged),
                      scales sum |y| and sum y^2, blocks as tem_conv3d_fwd_valu_path documents them.
@@ -23,7 +23,7 @@ Rules, none of them measured.
 Every case asserts and prints the kernel and instantiation the library's own dispatch query (tem_conv3d_fwd_valu_path /
 tem_conv3d_wgrad_path) names for exactly the pointers, leading dimensions and operands of the launch.
 
-No test provokes a device fault: the test lays every tensor out itself (oracle/gpu_layout.py: extent asserted against its
+No test provokes a device fault: the test lays every tensor out itself (oracle/gpu_kit.py: extent asserted against its
 buffer, NaN in the unused channels of wide inputs, sentinel fill in those of wide outputs, outputs start as NaN, sentinels
 before and after), every launch is one the library accepts or refuses with an error code, and every accepted launch is
 repeated into outputs reset to NaN and must return the same bits.
@@ -41,123 +41,35 @@ import torch
 
 from oracle import conv_cases as K
 from oracle import conv_ref as R
-from oracle.gpu_layout import DEV, PAD, SENT, ST, TORCH, Laid
+from oracle import gpu_kit as kit
+from oracle.gpu_kit import ST, Flat, holds_bits as _holds, lay as _lay, lib as _lib, stream as _stream
 
 pytestmark = pytest.mark.gpu
 BIG = 0x7F000000                  # the bit pattern of 2^127: more than any |y| here
 NAN = float("nan")
+LEDGER = kit.Ledger("CONV_VALU_ERR")
 
 
-def _lib():
-    from torch_em_amd import _lib
-    return _lib
+def _lattice_totals():
+    e = LEDGER.exact
+    print(f"CONV_VALU_ERR_SUMMARY lattice: {e['mismatches']} of {e['elements']} elements differ from float64 "
+          f"in {e['cases']} judged quantities")
 
 
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
+_print_worst = LEDGER.summary_fixture(after=_lattice_totals)
 
 
 def _mode(pair):
     return (ST[pair[0]] << 8) | (ST[pair[1]] << 12)
 
 
-# ------------------------------------------------------------------------------------------ worst figures, for the record
-WORST, EXACT = {}, {"elements": 0, "mismatches": 0, "cases": 0}
-
-
-def _note(path, quantity, ek, e32):
-    ratio = ek / max(e32, 1.0)
-    cur = WORST.get((path, quantity))
-    if cur is None or ratio > cur[2]:
-        WORST[(path, quantity)] = (ek, e32, ratio, 1 + (cur[3] if cur else 0))
-    else:
-        WORST[(path, quantity)] = cur[:3] + (cur[3] + 1,)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _print_worst():
-    yield
-    print("\nCONV_VALU_ERR_SUMMARY path / quantity: kernel, f32, ratio, cases")
-    for (path, q), (ek, e32, ratio, n) in sorted(WORST.items()):
-        print(f"CONV_VALU_ERR_SUMMARY {path:<22} {q:<22} {ek:7.2f} {e32:7.2f} {ratio:6.2f} {n:4d}")
-    if WORST:
-        print(f"CONV_VALU_ERR_SUMMARY worst ratio {max(v[2] for v in WORST.values()):.2f}")
-    print(f"CONV_VALU_ERR_SUMMARY lattice: {EXACT['mismatches']} of {EXACT['elements']} elements differ from float64 "
-          f"in {EXACT['cases']} judged quantities")
-
-
-class Flat:
-    """a float32 array between sentinels: an output the library writes (NaN until written) or a small input (weights, bias,
-    coefficients); off: elements the first one is moved off its 16-byte boundary"""
-
-    def __init__(self, n, fill=NAN, data=None, off=0):
-        n = int(np.asarray(data).size) if data is not None else int(n)
-        self.buf = torch.full((2 * PAD + n + off,), SENT, dtype=torch.float32, device=DEV)
-        self.body = self.buf[PAD + off:PAD + off + n]
-        self.off = off
-        if data is not None:
-            self.data = torch.from_numpy(np.ascontiguousarray(data, np.float32).reshape(-1)).to(DEV)
-            self.body.copy_(self.data)
-        else:
-            self.data = None
-            self.body.fill_(fill)
-
-    def ptr(self):
-        return ctypes.c_void_p(self.body.data_ptr())
-
-    def intact(self):
-        """the sentinels, and for an input the values"""
-        ok = bool((self.buf[:PAD + self.off] == SENT).all()) and bool((self.buf[PAD + self.off + self.body.numel():] == SENT).all())
-        return ok and (self.data is None or torch.equal(self.body.view(torch.int32), self.data.view(torch.int32)))
-
-    def bits(self):
-        return self.body.view(torch.int32).clone()
-
-    def host(self):
-        return self.body.double().cpu().numpy()
-
-    def unwritten(self):
-        return bool(torch.isnan(self.body).all())
-
-
 def _optr(t):
     return t.ptr() if t is not None else None
 
 
-def _lay(shape, dt, spec, data=None, output=False):
-    Wd, lo = spec if spec else (None, 0)
-    return Laid(shape, TORCH[dt], data, Wd, lo, other=SENT if output else NAN)
-
-
-def _holds(L, data):
-    """the tensor still holds `data`, bit for bit (-0.0 included)"""
-    want = torch.from_numpy(data).to(DEV).to(L.buf.dtype)
-    return L.intact() and torch.equal(L.bits(), want.contiguous().view(L.bits().dtype))
-
-
 def _judge(tag, label, quantity, dt, got, ref, scale, e32, exact):
     """exact: every element equals the float64 value as the storage type holds it; else the units rule"""
-    assert np.isfinite(got).all(), f"{tag}: {int((~np.isfinite(got)).sum())} elements of {quantity} were never written or are not finite"
-    if exact:
-        want = R.stored(ref, dt)
-        bad = R.mismatches(got, want)
-        EXACT["elements"] += want.size
-        EXACT["mismatches"] += bad
-        EXACT["cases"] += 1
-        print(f"CONV_VALU_ERR {tag} -> {label} {quantity}: {bad} of {want.size} elements differ from the exact value")
-        _note(label + ("" if dt == "f32" else " 16"), quantity + " (exact)", 0.0 if bad == 0 else float("inf"), 0.0)
-        assert bad == 0, f"{tag}: {bad} elements of {quantity} are not the exact value (first at {np.argwhere(~(got == want))[:3].tolist()})"
-    elif dt == "f32":
-        ek = R.units(got, ref, scale)
-        print(f"CONV_VALU_ERR {tag} -> {label} {quantity}: kernel {ek:.2f} f32 {e32:.2f}")
-        _note(label, quantity, ek, e32)
-        assert R.within(ek, e32), f"{tag}: {quantity} is {ek:.2f} units from float64, plain fp32 arithmetic {e32:.2f}"
-    else:
-        bad, ek = R.outside16(got, ref, scale, e32, dt), R.excess16(got, ref, scale, dt)
-        print(f"CONV_VALU_ERR {tag} -> {label} {quantity}: {bad} of {got.size} stored elements outside their interval; beyond the "
-              f"ideal rounding: kernel {ek:.2f} f32 {e32:.2f}")
-        _note(label + " 16", quantity, ek, e32)
-        assert bad == 0, f"{tag}: {bad} stored elements of {quantity} outside [round16(ref - band), round16(ref + band)]"
+    kit.judge(LEDGER, R, tag, label, quantity, dt, got, R.stored(ref, dt) if exact else ref, scale, e32, exact, suffix=True)
 
 
 _REF = {}

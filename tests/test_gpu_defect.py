@@ -29,6 +29,9 @@ import pytest
 import torch
 
 import defect_ref as R
+from oracle import gpu_kit as kit
+from oracle.gpu_kit import ops as _ops
+from oracle.judge import MARGIN
 from torch_em_amd.transform import EMDefectAugmentation, get_raw_transform
 from torch_em_amd.transform import defect as D
 
@@ -38,32 +41,9 @@ DEV = "cuda:0"
 # 1e-3 of a range end (one pixel would be 4 % of such a slice, against the 0.5 % that may be left out); the largest share
 # left out in any slice is 0.1 %.
 SEED = 0x1234_5678_9ABC_DEF1
-MARGIN = 4.0
-
-WORST = {}
-
-
-def _note(op, quantity, ek, e32):
-    ratio = ek / max(e32, 1.0)
-    cur = WORST.get((op, quantity))
-    n = 1 + (cur[3] if cur else 0)
-    WORST[(op, quantity)] = (ek, e32, ratio, n) if cur is None or ratio > cur[2] else cur[:3] + (n,)
-    return ratio
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _print_worst():
-    yield
-    print("\nDEFECT_ERR_SUMMARY op / quantity: kernel, f32, ratio, cases")
-    for (op, q), (ek, e32, ratio, n) in sorted(WORST.items()):
-        print(f"DEFECT_ERR_SUMMARY {op:<12} {q:<22} {ek:7.2f} {e32:7.2f} {ratio:6.2f} {n:4d}")
-    if WORST:
-        print(f"DEFECT_ERR_SUMMARY worst ratio {max(v[2] for v in WORST.values()):.2f}")
-
-
-def _ops():
-    from torch_em_amd import ops
-    return ops
+LEDGER = kit.Ledger("DEFECT_ERR")
+_note = LEDGER.note
+_print_worst = LEDGER.summary_fixture()
 
 
 # ---------------------------------------------------------------------------------------------------------------- cases

@@ -2,12 +2,12 @@
 oracle/dice_ref.py (which tests/test_dice_cpu.py pins to torch float64 autograd and to the reference-made fixtures, and
 whose judge it tests on deliberately wrong outputs).
 
-Rule (that of tests/test_gpu_optim.py).  Errors are counted in units of 2^-23 times a per-quantity scale: a sum column
+Rule (oracle/judge.py).  Errors are counted in units of 2^-23 times a per-quantity scale: a sum column
 against the column's own float64 value (every term is non-negative), a gradient element against
 |gout| (w_dice (|ca t| + |cb p|) s + |w_bce| b) [m] (oracle/dice_ref.py: grad_scale), after an absolute allowance of 2^-126
 (sigmoid(-90) is a float32 subnormal).  On the same inputs the test evaluates the numpy float32 restatement (one rounding
 per operation -- a reference, not the code under test) and takes its worst figure e32; the kernel must stay within
-MARGIN * max(e32, 1), MARGIN = 4.  EVERY sum column and EVERY gradient element is judged.  The restatement stays at <= 1.9
+MARGIN * max(e32, 1), the MARGIN of 4 of oracle/judge.py.  EVERY sum column and EVERY gradient element is judged.  The restatement stays at <= 1.9
 units for the sums and <= 2.8 for the gradients on the small shapes (asserted on the CPU; 2.9 over the 5e5 elements of the
 grid-cap cases, and up to 7.2 for its pairwise float32 sums of the 5 million terms of the clamped case), so the bound has
 room for the reference.  No allowance for the kernels' fp32 chains was needed: a thread sums at most 11 terms before the wave reduction
@@ -39,8 +39,10 @@ import torch
 
 from conftest import rel_err
 from oracle import dice_ref as R
+from oracle import gpu_kit as kit
 from oracle import loss_ref
 from oracle.dice_cases import FLAG_SETS, coefficients, flag_name, gout_variant, make_inputs
+from oracle.gpu_kit import lib as _lib, ops as _ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -50,44 +52,11 @@ SENT = 12345.0                   # the sentinel around every output
 f32 = np.float32
 
 
-def _lib():
-    from torch_em_amd import _lib
-    return _lib
-
-
-def _ops():
-    from torch_em_amd import ops
-    return ops
-
-
-@pytest.fixture
-def dice_vox_option():
-    """select the one-voxel-per-thread kernels (1, the default) or the (channel, voxel) kernels (0) for one test"""
-    lib = _lib()
-    old = lib.get_option("dice_vox")
-    yield lambda v: lib.set_option("dice_vox", v)
-    lib.set_option("dice_vox", old)
-
-
-# ------------------------------------------------------------------------------------------ worst figures, for the record
-WORST = {}
-
-
-def _note(path, quantity, ek, e32):
-    ratio = ek / max(e32, 1.0)
-    cur = WORST.get((path, quantity))
-    if cur is None or ratio > cur[2]:
-        WORST[(path, quantity)] = (ek, e32, ratio)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _print_worst():
-    yield
-    print("\nDICE_ERR_SUMMARY kernel path / quantity: kernel f32 ratio")
-    for (path, q), (ek, e32, ratio) in sorted(WORST.items()):
-        print(f"DICE_ERR_SUMMARY {path:<22} {q:<8} {ek:7.2f} {e32:7.2f} {ratio:6.2f}")
-    if WORST:
-        print(f"DICE_ERR_SUMMARY worst ratio {max(v[2] for v in WORST.values()):.2f}")
+LEDGER = kit.Ledger("DICE_ERR")
+_note = LEDGER.note
+_print_worst = LEDGER.summary_fixture()
+# select the one-voxel-per-thread kernels (1, the default) or the (channel, voxel) kernels (0) for one test
+dice_vox_option = kit.option_fixture("dice_vox")
 
 
 # ------------------------------------------------------------------------------------------ tensors the test lays out itself

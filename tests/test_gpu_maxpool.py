@@ -10,7 +10,7 @@ Rules, none of them measured.
   backward with gcoef / ycoef     errors in units of 2^-23 x scale (scale: norm_ref.apply_scale of the skip term, at the
                      arg-max plus that of the pooled term); on the same inputs e32 is the worst figure of the numpy float32
                      restatement (one rounding per operation, each fused apply uncontracted and contracted -- a reference, not
-                     the code under test).  EVERY fp32 element within MARGIN * max(e32, 1) units, MARGIN = 4 (oracle/dice_ref.py);
+                     the code under test).  EVERY fp32 element within MARGIN * max(e32, 1) units, MARGIN of oracle/judge.py: 4;
                      every stored 16-bit element in [round16(ref - band), round16(ref + band)].
   no element is excluded: arg-max and mask are decided on exact input values (x holds half-integers times powers of two,
                      exact in every storage type), so nothing can flip.
@@ -26,7 +26,7 @@ exactly the pointers, leading dimensions and options of the launch, next to the 
 At the two main shapes the 16-bit outputs of the packed-word kernel (pool_vec8 = 2) and of the generic 8-channel kernel
 (pool_vec8 = 1) must be equal bit for bit, in every variant.
 
-No test provokes a device fault: the test lays every tensor out itself (oracle/gpu_layout.py: extent asserted against its
+No test provokes a device fault: the test lays every tensor out itself (oracle/gpu_kit.py: extent asserted against its
 buffer, NaN in the unused channels of wide inputs, sentinel fill in those of wide outputs, outputs start as NaN, sentinels
 before and after), every launch is one the library accepts or refuses with an error code, and every accepted launch is
 repeated and must return the same bits.  The planted -inf / NaN / signed-zero windows are data values.
@@ -42,89 +42,18 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import gpu_kit as kit
 from oracle import maxpool_cases as K
 from oracle import maxpool_ref as R
-from oracle.gpu_layout import DEV, PAD, SENT, ST, TORCH, Laid
+from oracle.gpu_kit import DEV, ST, Flat, holds_values as _holds, lay as _lay, lib as _lib, stream as _stream
 
 pytestmark = pytest.mark.gpu
 MARGIN = R.MARGIN
 OBSERVED_WORST_RATIO = 1.00       # informational (profiles/maxpool_op_errors.txt); the assertions use MARGIN
 BIG = 0x7F000000                  # the bit pattern of 2^127: more than any |gx| here
-
-
-def _lib():
-    from torch_em_amd import _lib
-    return _lib
-
-
-def _stream():
-    return ctypes.c_void_p(torch.cuda.current_stream().cuda_stream)
-
-
-@pytest.fixture
-def pool_option():
-    """set a dispatch option ("pool_vec8") for one test"""
-    lib, old = _lib(), {}
-
-    def set_option(name, value):
-        old.setdefault(name, lib.get_option(name))
-        lib.set_option(name, value)
-    yield set_option
-    for name, value in old.items():
-        lib.set_option(name, value)
-
-
-# ------------------------------------------------------------------------------------------ worst figures, for the record
-WORST = {}
-
-
-def _note(path, quantity, ek, e32):
-    ratio = ek / max(e32, 1.0)
-    cur = WORST.get((path, quantity))
-    if cur is None or ratio > cur[2]:
-        WORST[(path, quantity)] = (ek, e32, ratio, 1 + (cur[3] if cur else 0))
-    else:
-        WORST[(path, quantity)] = cur[:3] + (cur[3] + 1,)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _print_worst():
-    yield
-    print("\nMAXPOOL_ERR_SUMMARY path / quantity: kernel, f32, ratio, cases")
-    for (path, q), (ek, e32, ratio, n) in sorted(WORST.items()):
-        print(f"MAXPOOL_ERR_SUMMARY {path:<36} {q:<18} {ek:7.2f} {e32:7.2f} {ratio:6.2f} {n:4d}")
-    if WORST:
-        print(f"MAXPOOL_ERR_SUMMARY worst ratio {max(v[2] for v in WORST.values()):.2f}")
-
-
-class Flat:
-    """a float32 array the library writes (row partials, the amax word) between sentinels, NaN until written"""
-
-    def __init__(self, n, fill=float("nan")):
-        self.buf = torch.full((2 * PAD + n,), SENT, dtype=torch.float32, device=DEV)
-        self.body = self.buf[PAD:PAD + n]
-        self.body.fill_(fill)
-
-    def ptr(self):
-        return ctypes.c_void_p(self.body.data_ptr())
-
-    def intact(self):
-        return bool((self.buf[:PAD] == SENT).all()) and bool((self.buf[-PAD:] == SENT).all())
-
-    def bits(self):
-        return self.body.view(torch.int32).clone()
-
-
-def _lay(shape, dt, spec, data=None, output=False):
-    Wd, lo = spec if spec else (None, 0)
-    return Laid(shape, TORCH[dt], data, Wd, lo, other=SENT if output else float("nan"))
-
-
-def _holds(L, data):
-    """the tensor still holds `data` as values (NaN matches NaN)"""
-    want = torch.from_numpy(data).to(DEV)
-    got = L.view.float()
-    return L.intact() and bool(((got == want) | (torch.isnan(got) & torch.isnan(want))).all())
+LEDGER = kit.Ledger("MAXPOOL_ERR")
+_print_worst = LEDGER.summary_fixture()
+pool_option = kit.option_fixture()            # a dispatch option ("pool_vec8") for one test
 
 
 def _plant(L, data):
@@ -139,26 +68,12 @@ def _label(direction, path, dt, f):
 
 def _judge(tag, label, quantity, dt, got, ref, scale, e32):
     """every element: fp32 within MARGIN * max(e32, 1) units; 16-bit inside the rounded band's closed interval"""
-    assert np.isfinite(got).all(), f"{tag}: {int((~np.isfinite(got)).sum())} elements of {quantity} were never written or are not finite"
-    if dt == "f32":
-        ek = R.units(got, ref, scale)
-        print(f"MAXPOOL_ERR {tag} -> {label} {quantity}: kernel {ek:.2f} f32 {e32:.2f}")
-        _note(label, quantity, ek, e32)
-        assert R.within(ek, e32), f"{tag}: {quantity} is {ek:.2f} units from float64, plain fp32 arithmetic {e32:.2f}"
-    else:
-        ek = R.excess16(got, ref, scale, dt)
-        bad = R.outside16(got, ref, scale, e32, dt)
-        print(f"MAXPOOL_ERR {tag} -> {label} {quantity}: {bad} of {got.size} stored elements outside their interval; beyond the "
-              f"ideal rounding: kernel {ek:.2f} f32 {e32:.2f}")
-        _note(label, quantity, ek, e32)
-        assert bad == 0, f"{tag}: {bad} stored elements of {quantity} outside [round16(ref - band), round16(ref + band)]"
+    kit.judge(LEDGER, R, tag, label, quantity, dt, got, ref, scale, e32)
 
 
 def _judge_exact(tag, label, quantity, got, want):
-    bad = R.mismatches(got, want)
-    print(f"MAXPOOL_ERR {tag} -> {label} {quantity}: {bad} of {want.size} elements differ from the exact value")
-    _note(label, quantity, 0.0 if bad == 0 else float("inf"), 0.0)
-    assert bad == 0, f"{tag}: {bad} elements of {quantity} are not the exact value"
+    """every element equals the exact value, NaN where it has NaN (R.mismatches)"""
+    kit.judge(LEDGER, R, tag, label, quantity, None, got, want, exact=True, finite=False)
 
 
 # ------------------------------------------------------------------------------------------ forward

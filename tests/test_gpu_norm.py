@@ -3,13 +3,13 @@ norm_stats_from_partials2 / norm_bwd_coef / norm_bwd (the `_st` entries), agains
 oracle/norm_ref.py (which tests/test_norm_cpu.py pins to torch float64 group_norm / batch_norm and their autograd, and whose
 judge it tests on deliberately wrong results).
 
-Rule (that of tests/test_gpu_dice.py, test_gpu_optim.py, test_gpu_upsample.py).  Errors are counted in units of 2^-23 times a
+Rule (oracle/judge.py).  Errors are counted in units of 2^-23 times a
 per-quantity scale -- sum x: sum |x|, sum x^2: its value, sum g: sum |g|, sum g xn: sum |g xn|, mean: sum |x| / cnt.  On the
 same inputs the test takes the worst figure e32 of the numpy float32 restatement (a reference, not the code under test): for
 the reductions the partition the header of norm.hip documents, fp32 chains -> fp32 per-block rows -> fp64 merge, with the
 chain lengths (`rows`, `vper`, `nblk`) the dispatch query names for the launch; for the apply one rounding per operation, the
 worse of the products rounded on their own and contracted into fmas.  EVERY element must stay within MARGIN * max(e32, 1)
-units, MARGIN = 4 (oracle/dice_ref.py).  The partial rows are read from the workspace the launch wrote.  Quantities derived
+units, MARGIN of oracle/judge.py: 4.  The partial rows are read from the workspace the launch wrote.  Quantities derived
 from those (rstd, scale, shift, the coef entries, dgamma, dbeta, gx end to end) get the propagated bands stated in the
 docstring of oracle/norm_ref.py: rstd the closed float32 interval of the var band (scale E[x^2] + 2 |m| E|x|: what
 ss / cnt - m^2 can lose), the others first order plus one rounding.  gx is judged twice: the apply alone against the float64
@@ -23,7 +23,7 @@ tem_norm_apply_geom) name for exactly the pointers and leading dimensions of the
 same table without a device.  Cases are the smallest shapes that reach each path (oracle/norm_cases.py).
 
 No test provokes a device fault: the test lays every tensor out itself and asserts its extent against its buffer before a
-launch (oracle/gpu_layout.py), unused channels of wide buffers hold NaN on input and keep their fill on output, every tensor
+launch (oracle/gpu_kit.py), unused channels of wide buffers hold NaN on input and keep their fill on output, every tensor
 sits between sentinels that must survive, and every launch is repeated and must return the same bits (the reductions have no
 atomics; the one atomic of out_amax is a max).
 
@@ -37,29 +37,23 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import gpu_kit as kit
 from oracle import norm_cases as K
 from oracle import norm_ref as R
-from oracle.gpu_layout import DEV, SENT, TORCH, Laid
+from oracle.gpu_kit import DEV, TORCH, lib as _lib, ops as _ops
 
 pytestmark = pytest.mark.gpu
 MARGIN = R.MARGIN
 OBSERVED_WORST_RATIO = 1.27       # informational (profiles/norm_op_errors.txt); the assertions use MARGIN
 f32 = np.float32
-
-
-def _lib():
-    from torch_em_amd import _lib
-    return _lib
-
-
-def _ops():
-    from torch_em_amd import ops
-    return ops
-
-
-# ------------------------------------------------------------------------------------------ worst figures, for the record
-WORST = {}
 EXACT = ("a", "cmean")            # quantities whose band is one rounding or none: not part of the worst ratio
+LEDGER = kit.Ledger("NORM_ERR")
+_print_worst = LEDGER.summary_fixture(
+    legend=" (kernel, f32: units of 2^-23 x scale, ratio = kernel / max(f32, 1); band quantities: ratio = MARGIN x error / band; "
+           "at most MARGIN passes)",
+    left_out=lambda q: q in EXACT,
+    footnote=f" (without a and cmean: a is one correctly rounded product, whose band is half a float32 step, so up to {MARGIN:.0f} "
+             f"by construction; cmean is 0 or infinite)")
 
 
 def _note(path, ratios, e32):
@@ -67,23 +61,7 @@ def _note(path, ratios, e32):
     are MARGIN x error / band"""
     for q, v in ratios.items():
         e = e32.get(q)
-        row = (v, None if e is None else v * max(e, 1.0), e)
-        if (path, q) not in WORST or v > WORST[(path, q)][0]:
-            WORST[(path, q)] = row
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _print_worst():
-    yield
-    print("\nNORM_ERR_SUMMARY path / quantity: kernel, f32 (units of 2^-23 x scale), ratio = kernel / max(f32, 1); band quantities: "
-          "ratio = MARGIN x error / band; at most MARGIN passes")
-    for (path, q), (v, ek, e) in sorted(WORST.items()):
-        cols = f"{ek:7.2f} {e:7.2f}" if e is not None else "      -       -"
-        print(f"NORM_ERR_SUMMARY {path:<30} {q:<10} {cols} {v:6.2f}")
-    rest = [v[0] for (path, q), v in WORST.items() if q not in EXACT]
-    if rest:
-        print(f"NORM_ERR_SUMMARY worst ratio {max(rest):.2f} (without a and cmean: a is one correctly rounded product, whose band is "
-              f"half a float32 step, so up to {MARGIN:.0f} by construction; cmean is 0 or infinite)")
+        LEDGER.note(path, q, None if e is None else v * max(e, 1.0), e, ratio=v)
 
 
 def _check(tag, path, ratios, e32=None):
@@ -97,9 +75,8 @@ def _check(tag, path, ratios, e32=None):
 
 # ------------------------------------------------------------------------------------------ helpers
 def _lay(N, V, C, dt, layout, data=None, output=False):
-    Wd, lo = layout if layout else (None, 0)
     data = None if data is None else np.ascontiguousarray(data.reshape(N, 1, 1, V, C))
-    return Laid((N, 1, 1, V, C), TORCH[dt], data, Wd, lo, other=SENT if output else float("nan"))
+    return kit.lay((N, 1, 1, V, C), dt, layout, data, output)
 
 
 def _dev(a):

@@ -2,11 +2,11 @@
 oracle/spoco_op_ref.py (which tests/test_spoco_cpu.py pins to torch float64 autograd and to the goldens, and whose judge it
 tests on deliberately wrong outputs).  Inputs and the census that proves the path: oracle/spoco_cases.py.
 
-Rule (that of tests/test_gpu_optim.py / test_gpu_dice.py).  Errors are counted in units of 2^-23 times a per-element scale
+Rule (oracle/judge.py).  Errors are counted in units of 2^-23 times a per-element scale
 (oracle/spoco_op_ref.py: the sum of the absolute values of an element's terms, a difference a - b formed in fp32 counting as
 |a| + |b|, a term through exp(x) as exp(x) (1 + |x|)).  On the same inputs the test evaluates the numpy float32 restatement
 (one rounding per operation -- a reference, not the code under test) and takes its worst figure e32; the kernel must stay
-within MARGIN * max(e32, 1), MARGIN = 4.  EVERY element of EVERY output is judged.  Exact quantities (label range, counts,
+within MARGIN * max(e32, 1), the MARGIN of 4 of oracle/judge.py.  EVERY element of EVERY output is judged.  Exact quantities (label range, counts,
 chunk counts, indices, every gradient element an op must not touch, the stride padding, the sentinels) are compared exactly.
 
 Derived allowance, not fitted to an observed error: means, S and dpush are 64-bit fixed-point sums with 2^-28 resolution;
@@ -42,8 +42,10 @@ import numpy as np
 import pytest
 import torch
 
+from oracle import gpu_kit as kit
 from oracle import spoco_cases as K
 from oracle import spoco_op_ref as R
+from oracle.gpu_kit import lib as _lib, ops as _ops
 
 pytestmark = pytest.mark.gpu
 DEV = "cuda:0"
@@ -54,36 +56,9 @@ G = 64                           # guard floats around every buffer (keeps 256-b
 f32, f64 = np.float32, np.float64
 
 
-def _lib():
-    from torch_em_amd import _lib
-    return _lib
-
-
-def _ops():
-    from torch_em_amd import ops
-    return ops
-
-
-# ------------------------------------------------------------------------------------------ worst figures, for the record
-WORST = {}
-
-
-def _note(entry, quantity, ek, e32):
-    ratio = ek / max(e32, 1.0)
-    cur = WORST.get((entry, quantity))
-    if cur is None or ratio > cur[2]:
-        WORST[(entry, quantity)] = (ek, e32, ratio)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _print_worst():
-    yield
-    print("\nSPOCO_ERR_SUMMARY entry point / quantity: kernel f32 ratio")
-    for (entry, q), (ek, e32, ratio) in sorted(WORST.items()):
-        print(f"SPOCO_ERR_SUMMARY {entry:<26} {q:<14} {ek:7.2f} {e32:7.2f} {ratio:6.2f}")
-    judged = [v[2] for (_, q), v in WORST.items() if not q.endswith("no allow.")]      # those rows are for the record
-    if judged:
-        print(f"SPOCO_ERR_SUMMARY worst ratio {max(judged):.2f}")
+LEDGER = kit.Ledger("SPOCO_ERR")
+_note = LEDGER.note
+_print_worst = LEDGER.summary_fixture(left_out=lambda q: q.endswith("no allow."))      # those rows are for the record
 
 
 def _raw(entry, key, got, ref, scale):

@@ -3,14 +3,14 @@ ops.upsample_bwd / ops.upsample_stats (the `_st` entries), against the float64 r
 tests/test_upsample_cpu.py pins to torch float64 interpolate and its autograd, and whose judge it tests on deliberately
 wrong outputs).
 
-Rule (that of tests/test_gpu_dice.py and tests/test_gpu_optim.py).  Errors are counted in units of 2^-23 times a per-element
+Rule (oracle/judge.py).  Errors are counted in units of 2^-23 times a per-element
 scale -- forward U|x|, adjoint U^T|g|, fused norm backward |a| U^T|g| + |m1| S + |m2r| (U^T U|u| + |mean| S), sum y: sum |y|,
 sum y^2: its own float64 value.  On the same inputs the test takes the worst figure e32 of the numpy float32 restatement
 (one rounding per operation, float32 weights as ATen computes them -- a reference, not the code under test; at factor 3,
 where 1 / f and the source index are rounded, the worse of its separately rounded and its fused evaluation of the source
 index: the compiler contracts lin_src's `scale * (o + 0.5) - 0.5` into one fma, which moves the weights' last-bit errors to
 other positions, oracle/upsample_ref.py: _src32; at factors 1 and 2 the weights are exact either way); EVERY element
-of a fp32 output must stay within MARGIN * max(e32, 1) units, MARGIN = 4 (oracle/dice_ref.py).  A 16-bit kernel computes in
+of a fp32 output must stay within MARGIN * max(e32, 1) units, MARGIN of oracle/judge.py: 4.  A 16-bit kernel computes in
 fp32 and rounds once on store: every stored element must lie in the closed interval [round16(ref - band), round16(ref + band)]
 of the same band (rounding is monotone, so this is exact).  The row statistics of a 16-bit launch describe the tensor as
 stored and are judged against the float64 sums of the stored values.
@@ -40,79 +40,22 @@ import pytest
 import torch
 
 from conftest import rel_err
+from oracle import gpu_kit as kit
 from oracle import upsample_cases as K
 from oracle import upsample_ref as R
-from oracle.gpu_layout import BITS, DEV, PAD, SENT, ST, TORCH, Laid  # noqa: F401  (shared with tests/test_gpu_norm.py)
+from oracle.gpu_kit import DEV, ST, TORCH, lay as _lay, lib as _lib, ops as _ops
 
 pytestmark = pytest.mark.gpu
 MARGIN = R.MARGIN
 OBSERVED_WORST_RATIO = 2.49       # informational (profiles/upsample_op_errors.txt); the assertions use MARGIN
-
-
-def _lib():
-    from torch_em_amd import _lib
-    return _lib
-
-
-def _ops():
-    from torch_em_amd import ops
-    return ops
-
-
-@pytest.fixture
-def upsample_option():
-    """set dispatch options ("upsample2_ch8", "upsample_generic") for one test"""
-    lib, old = _lib(), {}
-
-    def set_option(name, value):
-        old.setdefault(name, lib.get_option(name))
-        lib.set_option(name, value)
-    yield set_option
-    for name, value in old.items():
-        lib.set_option(name, value)
-
-
-# ------------------------------------------------------------------------------------------ worst figures, for the record
-WORST = {}
-
-
-def _note(path, quantity, ek, e32):
-    ratio = ek / max(e32, 1.0)
-    cur = WORST.get((path, quantity))
-    if cur is None or ratio > cur[2]:
-        WORST[(path, quantity)] = (ek, e32, ratio)
-
-
-@pytest.fixture(scope="module", autouse=True)
-def _print_worst():
-    yield
-    print("\nUPSAMPLE_ERR_SUMMARY path / quantity: kernel, f32, ratio")
-    for (path, q), (ek, e32, ratio) in sorted(WORST.items()):
-        print(f"UPSAMPLE_ERR_SUMMARY {path:<26} {q:<16} {ek:7.2f} {e32:7.2f} {ratio:6.2f}")
-    if WORST:
-        print(f"UPSAMPLE_ERR_SUMMARY worst ratio {max(v[2] for v in WORST.values()):.2f}")
-
-
-def _lay(shape, dtype, spec, data=None, output=False):
-    Wd, lo = spec if spec else (None, 0)
-    return Laid(shape, dtype, data, Wd, lo, other=SENT if output else float("nan"))
+LEDGER = kit.Ledger("UPSAMPLE_ERR")
+_print_worst = LEDGER.summary_fixture()
+upsample_option = kit.option_fixture()        # dispatch options ("upsample2_ch8", "upsample_generic") for one test
 
 
 def _judge(tag, path, quantity, dt, got, ref, scale, e32):
     """every element: fp32 within MARGIN * max(e32, 1) units; 16-bit inside the rounded band's closed interval"""
-    assert np.isfinite(got).all(), f"{tag}: {int((~np.isfinite(got)).sum())} elements of {quantity} were never written or are not finite"
-    if dt == "f32":
-        ek = R.units(got, ref, scale)
-        print(f"UPSAMPLE_ERR {tag} -> {path} {quantity}: kernel {ek:.2f} f32 {e32:.2f}")
-        _note(path, quantity, ek, e32)
-        assert R.within(ek, e32), f"{tag}: {quantity} is {ek:.2f} units from float64, plain fp32 arithmetic {e32:.2f}"
-    else:
-        ek = R.excess16(got, ref, scale, dt)
-        bad = R.outside16(got, ref, scale, e32, dt)
-        print(f"UPSAMPLE_ERR {tag} -> {path} {quantity}: {bad} of {got.size} stored elements outside their interval; beyond the "
-              f"ideal rounding: kernel {ek:.2f} f32 {e32:.2f}")
-        _note(path, quantity, ek, e32)
-        assert bad == 0, f"{tag}: {bad} stored elements of {quantity} outside [round16(ref - band), round16(ref + band)]"
+    kit.judge(LEDGER, R, tag, path, quantity, dt, got, ref, scale, e32)
 
 
 # ------------------------------------------------------------------------------------------ backward
@@ -136,17 +79,17 @@ def _bwd_layout(layout, which):
     return None
 
 
-def _launch_bwd(name, dtype, shape, f, layout, d, norm):
+def _launch_bwd(name, dt, shape, f, layout, d, norm):
     """-> (path the query names, GX host float64, bits of GX); launches twice"""
     lib, ops = _lib().load(), _ops()
     N, D, H, W, C = shape
-    GY = _lay(K.fine(shape, f), dtype, _bwd_layout(layout, "gy"), d["g"])
-    GX = _lay(shape, dtype, _bwd_layout(layout, "gx"), None, output=True)
-    UU = _lay(shape, dtype, None, d["u"]) if norm else None
+    GY = _lay(K.fine(shape, f), dt, _bwd_layout(layout, "gy"), d["g"])
+    GX = _lay(shape, dt, _bwd_layout(layout, "gx"), None, output=True)
+    UU = _lay(shape, dt, None, d["u"]) if norm else None
     coef = torch.from_numpy(d["coef"]).to(DEV) if norm else None
     assert GY.view.shape == K.fine(GX.view.shape, f)
     path = lib.tem_upsample_bwd_path(GY.ptr(), GY.Wd, GX.ptr(), GX.Wd, N, D, H, W, C, f[0], f[1], f[2],
-                                     UU.ptr() if norm else None, UU.Wd if norm else 0, ST[_name(dtype)])
+                                     UU.ptr() if norm else None, UU.Wd if norm else 0, ST[dt])
     ops.upsample_bwd(GY.view, GX.view, f, norm=(UU.view, coef) if norm else None)
     torch.cuda.synchronize()
     first = GX.bits()
@@ -160,17 +103,13 @@ def _launch_bwd(name, dtype, shape, f, layout, d, norm):
     return path, GX.host(), first
 
 
-def _name(dtype):
-    return {v: k for k, v in TORCH.items()}[dtype]
-
-
 @pytest.mark.parametrize("name,dt,norm", BWD_CASES, ids=[f"{n}-{t}-{'norm' if m else 'plain'}" for n, t, m in BWD_CASES])
 def test_backward_against_float64(name, dt, norm, upsample_option):
     f, shape, dtypes, want, layout, opts = K.BWD[name]
     for key, value in opts.items():
         upsample_option(key, value)
     d = K.bwd_data(shape, f, K.grid_of(dt))
-    path, got, bits = _launch_bwd(name, TORCH[dt], shape, f, layout, d, norm)
+    path, got, bits = _launch_bwd(name, dt, shape, f, layout, d, norm)
     tag = f"bwd {name} f={f} {shape} {dt} {'norm' if norm else 'plain'} pairs={K.pairs(shape, f)}"
     print(f"UPSAMPLE_PATH {tag}: query {path} ({K.PATH_NAME.get(path)}), intended {want}")
     assert path == want, f"{tag}: meant for {K.PATH_NAME[want]}, the query names {K.PATH_NAME.get(path, path)}"
@@ -179,7 +118,7 @@ def test_backward_against_float64(name, dt, norm, upsample_option):
            d[q], d[q + "_scale"], d[q + "_e32"])
     if name in ("b4", "b6"):
         # the contract of tests/test_gpu_storage16.py between the 8-channel 16-bit instantiation and the fp32 4-channel one
-        p32, got32, _ = _launch_bwd(name + "/fp32", torch.float32, shape, f, layout, d, norm)
+        p32, got32, _ = _launch_bwd(name + "/fp32", "f32", shape, f, layout, d, norm)
         assert p32 == K.FACTOR2_CH4
         rounded = torch.from_numpy(got32).to(TORCH[dt]).contiguous().view(torch.int16)
         diff = int((rounded != bits.cpu()).sum())
@@ -216,8 +155,8 @@ def test_forward_and_statistics_against_float64(name, dt):
     f, shape, dtypes, want, want_stats, ylay = K.FWD[name]
     N, D, H, W, C = shape
     d = K.fwd_data(shape, f, K.grid_of(dt))
-    X = _lay(shape, TORCH[dt], None, d["x"])
-    Y = _lay(K.fine(shape, f), TORCH[dt], ylay, None, output=True)
+    X = _lay(shape, dt, None, d["x"])
+    Y = _lay(K.fine(shape, f), dt, ylay, None, output=True)
     stats_ok = bool(lib.tem_upsample_fwd_stats_ok(C, *f)) and ops._rows_vec4(X.view, X.Wd, Y.view, Y.Wd)
     assert stats_ok == want_stats, f"{name}: the case table says stats={want_stats}"
     path = lib.tem_upsample_fwd_path(X.ptr(), X.Wd, Y.ptr(), Y.Wd, N, D, H, W, C, f[0], f[1], f[2], int(stats_ok), ST[dt])
