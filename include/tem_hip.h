@@ -1123,6 +1123,42 @@ int tem_defect_prefilter(const float* x, float* coef, int D, int H, int W, const
 int tem_defect_warp(const float* coef, const float* flow, float* y, int D, int H, int W, const int32_t* rec,
                     const int32_t* tables, uint64_t seed, double noise_scale, tem_stream_t stream);
 
+/* ---- patch supply from device-resident volumes (data/device_dataset.py; reference data/segmentation_dataset.py :155-216,
+ * data/sampler.py; csrc/patch.hip) ---------------------------------------------------------------------------------------
+ * Two device tables written by the host describe a call:
+ *   vols[V][6]  (int64): base pointer, dtype code, C, D, H, W of a contiguous volume [C][D][H][W] (2-D data: D = 1)
+ *   boxes[M][8] (int32): volume, z0, y0, x0, dz, dy, dx, 0; the box is [z0, z0 + dz) x [y0, y0 + dy) x [x0, x0 + dx) of every
+ *               channel, dz, dy, dx >= 1 and ALREADY CLIPPED to the volume
+ * The kernels index with what the tables hold and check nothing; the caller validates every box against its descriptor
+ * before the launch (ops.PatchVolumes does).  Every volume a call touches has the dtype passed as `dtype` / `in_dtype`.
+ * Offsets are 64-bit; a box holds at most max_vox < 2^31 voxels (max_vox: the largest dz * dy * dx of the call, sizes the
+ * grid), counts are int32.  At most 65535 boxes (gather: B * C planes) per call.  Nothing reads device memory back, allocates
+ * or synchronises; outputs are cleared inside the call; sums are integer adds: all results are bitwise reproducible. */
+#define TEM_PT_U8 0
+#define TEM_PT_U16 1
+#define TEM_PT_I16 2
+#define TEM_PT_I32 3
+#define TEM_PT_I64 4
+#define TEM_PT_F32 5
+/* out[m][0] = voxels of box m (channel 0 of a label volume: uint8, uint16, int32 or int64) != value, out[m][1] = voxels != the
+ * box's first voxel (z0, y0, x0).  A value the element type cannot hold differs from every voxel. */
+int tem_patch_count(const void* vols, const int32_t* boxes, int M, int dtype, int64_t max_vox, int64_t value, int32_t* out,
+                    tem_stream_t stream);
+/* hist[m][id] = voxels of box m with that id; the volumes hold DENSE int32 ids (TEM_PT_I32), ids outside [0, n_ids) are not
+ * counted.  tem_patch_hist_path: 0 = per-workgroup LDS table flushed once, 1 = run-aggregated global adds, -1 refused. */
+int tem_patch_hist(const void* vols, const int32_t* boxes, int M, int64_t max_vox, int n_ids, int32_t* hist, tem_stream_t stream);
+int tem_patch_hist_path(int n_ids);
+/* mode 0: out[m] = number of ids with hist[m][id] >= max(min_size, 1) and sel[id] == 0 (sel: int32 [n_ids], non-zero = excluded);
+ * mode 1: out[m][k] = hist[m][sel[k]], k < K (sel: int32 [K] dense ids; an entry outside [0, n_ids) gives 0) */
+int tem_patch_hist_reduce(const int32_t* hist, int M, int n_ids, int mode, const int32_t* sel, int K, int min_size, int32_t* out,
+                          tem_stream_t stream);
+/* out[b][c][z][y][x] (dense, B x C x pd x ph x pw, out_dtype TEM_PT_F32 / _I32 / _I64) = voxel (c, z0 + z, y0 + y, x0 + x) of box
+ * b's volume converted by a C cast (exact for uint8 / uint16 / int16 / float32 -> float32 and for integers that fit), 0 where
+ * z >= dz, y >= dy or x >= dx (constant padding to the patch).  Every volume of the call has C channels.  float32 volumes
+ * gather to float32 only. */
+int tem_patch_gather(const void* vols, const int32_t* boxes, int B, int C, int in_dtype, int pd, int ph, int pw, void* out,
+                     int out_dtype, tem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

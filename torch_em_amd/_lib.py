@@ -240,6 +240,12 @@ SIGNATURES = {
     "tem_defect_flow": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_u64, c_float, c_vp, c_int, c_vp]),
     "tem_defect_prefilter": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_int, c_vp]),
     "tem_defect_warp": (c_int, [c_vp, c_vp, c_vp, c_int, c_int, c_int, c_vp, c_vp, c_u64, c_double, c_vp]),
+    # patch supply from device-resident volumes (csrc/patch.hip): vols int64 [V][6], boxes int32 [M][8] (include/tem_hip.h)
+    "tem_patch_count": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_i64, c_vp, c_vp]),
+    "tem_patch_hist": (c_int, [c_vp, c_vp, c_int, c_i64, c_int, c_vp, c_vp]),
+    "tem_patch_hist_path": (c_int, [c_int]),
+    "tem_patch_hist_reduce": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
+    "tem_patch_gather": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp]),
 }
 
 _lib = None

@@ -3,6 +3,7 @@ reference segmentation.py:143-148, data/tensor_dataset.py, sample pipeline
 data/image_collection_dataset.py:241-264): per sample
     random crop to patch_shape -> raw_transform -> label_transform -> transform(raw, labels)
     -> label_transform2 -> float tensors with a channel axis.
+`sampler(raw_crop, label_crop) -> bool` (data/sampler.py) rejects crops: the crop is redrawn until it accepts.
 File-backed datasets (HDF5/zarr/tif readers, ~250 download wrappers) are data plumbing outside
 the hot path and are not re-implemented; feed arrays.
 """
@@ -13,6 +14,8 @@ import torch
 
 
 class TensorDataset(torch.utils.data.Dataset):
+    max_sampling_attempts = 500  # re-draws of one sample before `sampler` is given up on (the reference's limit)
+
     def __init__(self, images: List[Union[np.ndarray, torch.Tensor]], labels: List[Union[np.ndarray, torch.Tensor]],
                  patch_shape: Tuple[int, ...], raw_transform: Optional[Callable] = None,
                  label_transform: Optional[Callable] = None, label_transform2: Optional[Callable] = None,
@@ -47,8 +50,20 @@ class TensorDataset(torch.utils.data.Dataset):
         shape = labels.shape
         start = [np.random.randint(0, sh - psh) if sh - psh > 0 else 0 for sh, psh in zip(shape, self.patch_shape)]
         bb = tuple(slice(s, s + p) for s, p in zip(start, self.patch_shape))
-        raw = raw[(slice(None),) + bb] if self.with_channels else raw[bb]
-        labels = labels[bb]
+        return (raw[(slice(None),) + bb] if self.with_channels else raw[bb]), labels[bb]
+
+    def _sample(self, raw, labels):
+        """A random crop the sampler accepts, looped as the reference's datasets loop (data/segmentation_dataset.py:191-199):
+        the sampler sees the crop before padding, a rejected crop is drawn again from the same image."""
+        image, label_image = raw, labels
+        raw, labels = self._crop(image, label_image)
+        if self.sampler is not None:
+            attempts = 0
+            while not self.sampler(raw, labels):
+                raw, labels = self._crop(image, label_image)
+                attempts += 1
+                if attempts > self.max_sampling_attempts:
+                    raise RuntimeError(f"Could not sample a valid batch in {self.max_sampling_attempts} attempts")
         if self.with_padding and tuple(labels.shape) != self.patch_shape:
             pad = [(0, p - s) for p, s in zip(self.patch_shape, labels.shape)]
             labels = np.pad(labels, pad, mode="reflect")
@@ -61,7 +76,7 @@ class TensorDataset(torch.utils.data.Dataset):
         raw, labels = self.raw_images[index], self.label_images[index]
         raw = raw.numpy() if torch.is_tensor(raw) else np.asarray(raw)
         labels = labels.numpy() if torch.is_tensor(labels) else np.asarray(labels)
-        raw, labels = self._crop(raw, labels)
+        raw, labels = self._sample(raw, labels)
         if self.raw_transform is not None:
             raw = self.raw_transform(raw)
         if self.label_transform is not None:

@@ -2087,3 +2087,135 @@ def dist_loss_grad(p, t, coef, gout, mask_bg: bool) -> torch.Tensor:
     _lib.check(_lib.load().tem_dist_loss_grad(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], _p(coef), _p(gout),
                                               _p(gp), N, V, int(mask_bg), _stream(p)), "tem_dist_loss_grad")
     return gp
+
+
+# ---- patch supply from device-resident volumes (csrc/patch.hip; the tables: include/tem_hip.h; data/device_dataset.py) ----
+PT_DTYPE = {torch.uint8: 0, torch.uint16: 1, torch.int16: 2, torch.int32: 3, torch.int64: 4, torch.float32: 5}
+_PT_LABELS = (torch.uint8, torch.uint16, torch.int32, torch.int64)
+
+
+class PatchBoxes:
+    """Boxes checked against their volumes and copied to the device: int32 [M, 8] (volume, z0, y0, x0, dz, dy, dx, 0)."""
+    __slots__ = ("dev", "host", "M", "max_vox")
+
+    def __init__(self, dev, host):
+        self.dev, self.host, self.M = dev, host, int(host.shape[0])
+        self.max_vox = int((host[:, 4].astype("int64") * host[:, 5] * host[:, 6]).max())
+
+
+class PatchVolumes:
+    """Volumes [C, D, H, W] of one dtype that stay on the device, and their descriptor table (int64 [V, 6]: pointer, dtype code,
+    C, D, H, W).  The kernels index with what the tables hold, so `boxes()` checks every box on the host before it is copied."""
+
+    def __init__(self, volumes):
+        volumes = list(volumes)
+        _req_cuda(*volumes)
+        if not volumes or any(v.dim() != 4 or v.numel() == 0 or not v.is_contiguous() for v in volumes):
+            raise ValueError("PatchVolumes: expected non-empty contiguous tensors [C, D, H, W]")
+        if len({v.dtype for v in volumes}) != 1 or volumes[0].dtype not in PT_DTYPE or len({v.device for v in volumes}) != 1:
+            raise ValueError(f"PatchVolumes: one device and one dtype of {sorted(str(d) for d in PT_DTYPE)} for all volumes")
+        self.volumes, self.dtype, self.device = volumes, volumes[0].dtype, volumes[0].device
+        self.shapes = [tuple(int(s) for s in v.shape) for v in volumes]
+        import numpy as np
+        self.table = _to_device(np.array([[v.data_ptr(), PT_DTYPE[v.dtype], *v.shape] for v in volumes], dtype=np.int64), self.device)
+
+    def boxes(self, boxes) -> PatchBoxes:
+        """host integers [M, 7] (volume, z0, y0, x0, dz, dy, dx) -> PatchBoxes; raises for a box that leaves its volume"""
+        if isinstance(boxes, PatchBoxes):
+            return boxes
+        import numpy as np
+        b = np.asarray(boxes, dtype=np.int64).reshape(-1, 7)
+        if not 0 < b.shape[0] <= 65535:
+            raise ValueError(f"patch: 1..65535 boxes per call, got {b.shape[0]}")
+        if b[:, 0].min() < 0 or b[:, 0].max() >= len(self.volumes):
+            raise ValueError(f"patch: a box names a volume outside [0, {len(self.volumes)})")
+        dims = np.array([s[1:] for s in self.shapes], dtype=np.int64)[b[:, 0]]
+        if (b[:, 1:4] < 0).any() or (b[:, 4:7] < 1).any() or (b[:, 1:4] + b[:, 4:7] > dims).any():
+            bad = int(np.nonzero((b[:, 1:4] < 0).any(1) | (b[:, 4:7] < 1).any(1) | (b[:, 1:4] + b[:, 4:7] > dims).any(1))[0][0])
+            raise ValueError(f"patch: box {bad} {b[bad, 1:].tolist()} is empty or leaves its volume {self.shapes[int(b[bad, 0])][1:]}")
+        if (b[:, 4] * b[:, 5] * b[:, 6]).max() >= 2 ** 31:
+            raise ValueError("patch: a box holds 2^31 voxels or more")
+        host = np.zeros((b.shape[0], 8), dtype=np.int32)
+        host[:, :7] = b
+        return PatchBoxes(_to_device(host, self.device), host)
+
+
+def patch_count(vols: PatchVolumes, boxes, value: int) -> torch.Tensor:
+    """int32 [M, 2] on the device: per box of channel 0 of a label volume (uint8 / uint16 / int32 / int64) the voxels != value
+    and the voxels != the box's first voxel (tem_patch_count; one streaming pass, bitwise reproducible)"""
+    if vols.dtype not in _PT_LABELS:
+        raise ValueError(f"patch_count: label volumes are uint8, uint16, int32 or int64, got {vols.dtype}")
+    bx = vols.boxes(boxes)
+    out = torch.empty((bx.M, 2), dtype=torch.int32, device=vols.device)
+    _lib.check(_lib.load().tem_patch_count(_p(vols.table), _p(bx.dev), bx.M, PT_DTYPE[vols.dtype], bx.max_vox, int(value), _p(out),
+                                           _stream(out)), "tem_patch_count")
+    return out
+
+
+def patch_hist_path(n_ids: int) -> int:
+    """which kernel `patch_hist` runs for this many ids: 0 the workgroup's LDS table, 1 global adds (-1: refused)"""
+    return int(_lib.load().tem_patch_hist_path(int(n_ids)))
+
+
+def patch_hist(vols: PatchVolumes, boxes, n_ids: int) -> torch.Tensor:
+    """int32 [M, n_ids] on the device: voxels per dense id (int32 volumes, channel 0; `pod_ids` makes them) in every box
+    (tem_patch_hist; runs of equal ids along x are added once)"""
+    if vols.dtype != torch.int32:
+        raise ValueError(f"patch_hist: the volumes hold dense int32 ids, got {vols.dtype}")
+    if patch_hist_path(n_ids) < 0:
+        raise ValueError(f"patch_hist: n_ids >= 1, got {n_ids}")
+    bx = vols.boxes(boxes)
+    hist = torch.empty((bx.M, int(n_ids)), dtype=torch.int32, device=vols.device)
+    _lib.check(_lib.load().tem_patch_hist(_p(vols.table), _p(bx.dev), bx.M, bx.max_vox, int(n_ids), _p(hist), _stream(hist)),
+               "tem_patch_hist")
+    return hist
+
+
+def _pt_sel(sel, n, hist, what):
+    if sel.dtype != torch.int32 or sel.dim() != 1 or (n is not None and sel.numel() != n) or sel.numel() == 0 or sel.device != hist.device \
+            or not sel.is_contiguous():
+        raise ValueError(f"{what}: expected a contiguous int32 vector{'' if n is None else f' of {n} entries'} on {hist.device}")
+
+
+def patch_hist_instances(hist: torch.Tensor, excluded: torch.Tensor, min_size: int = 1) -> torch.Tensor:
+    """int32 [M]: ids with at least max(min_size, 1) voxels in the box whose entry of `excluded` (int32 [n_ids]) is 0"""
+    _req_cuda(hist, excluded)
+    if hist.dim() != 2 or hist.dtype != torch.int32 or not hist.is_contiguous():
+        raise ValueError("patch_hist_instances: expected the contiguous int32 [M, n_ids] of patch_hist")
+    _pt_sel(excluded, hist.shape[1], hist, "patch_hist_instances: excluded")
+    out = torch.empty((hist.shape[0],), dtype=torch.int32, device=hist.device)
+    _lib.check(_lib.load().tem_patch_hist_reduce(_p(hist), hist.shape[0], hist.shape[1], 0, _p(excluded), 0, int(min_size), _p(out),
+                                                 _stream(out)), "tem_patch_hist_reduce")
+    return out
+
+
+def patch_hist_listed(hist: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
+    """int32 [M, K]: the box's voxels of every dense id in `ids` (int32 [K]; an id outside the histogram counts 0)"""
+    _req_cuda(hist, ids)
+    if hist.dim() != 2 or hist.dtype != torch.int32 or not hist.is_contiguous():
+        raise ValueError("patch_hist_listed: expected the contiguous int32 [M, n_ids] of patch_hist")
+    _pt_sel(ids, None, hist, "patch_hist_listed: ids")
+    out = torch.empty((hist.shape[0], ids.numel()), dtype=torch.int32, device=hist.device)
+    _lib.check(_lib.load().tem_patch_hist_reduce(_p(hist), hist.shape[0], hist.shape[1], 1, _p(ids), ids.numel(), 1, _p(out),
+                                                 _stream(out)), "tem_patch_hist_reduce")
+    return out
+
+
+def patch_gather(vols: PatchVolumes, boxes, patch_shape, dtype: torch.dtype = torch.float32) -> torch.Tensor:
+    """[B, C, pd, ph, pw] of `dtype` (float32 / int32 / int64) on the device: every box cast to dtype, with ZEROS where the box
+    is smaller than the patch -- `np.pad(mode="constant")`, what the reference's `ensure_patch_shape` does for its
+    SegmentationDataset; NOT the reflect padding of `TensorDataset`.  One launch (tem_patch_gather)."""
+    if dtype not in (torch.float32, torch.int32, torch.int64) or (vols.dtype == torch.float32 and dtype != torch.float32):
+        raise ValueError(f"patch_gather: {vols.dtype} volumes do not gather to {dtype} (float32, int32, int64; float32 stays float32)")
+    bx = vols.boxes(boxes)
+    pd, ph, pw = (int(p) for p in patch_shape)
+    C = {s[0] for s in (vols.shapes[int(i)] for i in set(bx.host[:, 0].tolist()))}
+    if len(C) != 1:
+        raise ValueError("patch_gather: the volumes of one call have the same number of channels")
+    C = C.pop()
+    if min(pd, ph, pw) < 1 or (bx.host[:, 4:7] > (pd, ph, pw)).any() or bx.M * C > 65535 or pd * ph * pw >= 2 ** 31:
+        raise ValueError(f"patch_gather: boxes must fit the patch {(pd, ph, pw)}; at most 65535 planes of < 2^31 voxels")
+    out = torch.empty((bx.M, C, pd, ph, pw), dtype=dtype, device=vols.device)
+    _lib.check(_lib.load().tem_patch_gather(_p(vols.table), _p(bx.dev), bx.M, C, PT_DTYPE[vols.dtype], pd, ph, pw, _p(out),
+                                            PT_DTYPE[dtype], _stream(out)), "tem_patch_gather")
+    return out

@@ -11,7 +11,7 @@ from typing import Any, Callable, Dict, Optional, Union
 import numpy as np
 import torch
 
-from .data import TensorDataset
+from .data import DevicePatchLoader, DeviceSegmentationDataset, TensorDataset
 from .loss import DiceLoss
 from .optim import FusedAdamW
 from .trainer import DefaultTrainer
@@ -28,7 +28,10 @@ def standardize_raw(raw, eps: float = 1e-7):
 def default_segmentation_dataset(raw_paths, raw_key, label_paths, label_key, patch_shape, label_transform=None,
                                  label_transform2=None, raw_transform=None, transform=None, dtype=torch.float32,
                                  label_dtype=torch.float32, n_samples=None, sampler=None, with_channels=False,
-                                 with_padding=True, **unused):
+                                 with_padding=True, resident_device=None, roi=None, **unused):
+    """`resident_device` (e.g. "cuda"): the arrays move to that device once and a `DeviceSegmentationDataset` is returned, whose
+    crops and sampler run there (data/device_dataset.py); the dataset then takes no transforms -- pass them to the trainer
+    (`raw_transform`, `target_transform`, `augmentation`), which applies them to the device batch."""
     if not (isinstance(raw_paths, (list, tuple)) and len(raw_paths) and
             isinstance(raw_paths[0], (np.ndarray, torch.Tensor))):
         raise NotImplementedError(
@@ -36,6 +39,13 @@ def default_segmentation_dataset(raw_paths, raw_key, label_paths, label_key, pat
             "file-backed datasets are outside the MI355X hot path -- load the arrays and pass them in"
         )
     assert raw_key is None and label_key is None
+    if resident_device is not None:
+        if any(t is not None for t in (raw_transform, label_transform, label_transform2, transform)):
+            raise NotImplementedError("a device-resident dataset applies no transforms: give them to the trainer "
+                                      "(raw_transform, target_transform, augmentation), or use the host TensorDataset")
+        return DeviceSegmentationDataset(list(raw_paths), list(label_paths), patch_shape, sampler=sampler, n_samples=n_samples,
+                                         roi=roi, with_channels=with_channels, with_padding=with_padding, dtype=dtype,
+                                         label_dtype=label_dtype, device=resident_device)
     return TensorDataset(list(raw_paths), list(label_paths), patch_shape=patch_shape,
                          raw_transform=standardize_raw if raw_transform is None else raw_transform,
                          label_transform=label_transform, label_transform2=label_transform2, transform=transform,
@@ -44,11 +54,14 @@ def default_segmentation_dataset(raw_paths, raw_key, label_paths, label_key, pat
 
 
 def default_segmentation_loader(raw_paths, raw_key, label_paths, label_key, batch_size, patch_shape,
-                                **kwargs) -> torch.utils.data.DataLoader:
+                                **kwargs):
     """Dataset + DataLoader (reference :222-330); loader kwargs are split off like the reference does."""
     loader_keys = ("shuffle", "num_workers", "pin_memory", "drop_last", "sampler", "collate_fn", "persistent_workers")
     loader_kwargs = {k: kwargs.pop(k) for k in list(kwargs) if k in loader_keys and k != "sampler"}
+    seed = kwargs.pop("seed", None)   # of the device loader's sample streams; drawn from np.random if not given
     ds = default_segmentation_dataset(raw_paths, raw_key, label_paths, label_key, patch_shape, **kwargs)
+    if isinstance(ds, DeviceSegmentationDataset):   # resident_device: batches are drawn and gathered on the device
+        return DevicePatchLoader(ds, batch_size, seed=int(np.random.randint(0, 2 ** 31)) if seed is None else seed)
     loader = torch.utils.data.DataLoader(ds, batch_size=batch_size, **loader_kwargs)
     loader.shuffle = loader_kwargs.get("shuffle", False)
     return loader
