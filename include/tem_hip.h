@@ -1086,6 +1086,23 @@ int tem_rawaug_poisson_scaled(const float* x, float* y, int N, int64_t L, const 
  * (index -j -> j, H-1+j -> H-1-j).  wy, wx: device arrays; tap counts odd, 1..63, k/2 < the axis' size; y must not be x. */
 int tem_rawaug_blur2d(const float* x, float* y, int64_t P, int H, int W, const float* wy, const float* wx, int ky, int kx,
                       tem_stream_t stream);
+/* the z pass of a separable 3-D blur: y = the P volumes of D planes of HW elements of x, convolved along z with wz (kz taps,
+ * device array; odd, 1..63, kz/2 < D), the same reflect border; y must not be x.  Any 4-byte aligned base. */
+int tem_rawaug_blur_z(const float* x, float* y, int64_t P, int D, int64_t HW, const float* wz, int kz, tem_stream_t stream);
+
+/* ---- seeded watershed (csrc/watershed.hip; the definition: DESIGN.md "Seeded watershed") -----------------------------
+ * The minimum spanning forest rooted in the markers, on a batch [N][D][H][W] (2-D: D == 1), V = D*H*W < 2^31 - 1.
+ * rank, order: int32 [N][V], the voxels of each sample ranked by (height, linear index): rank[v] unique in [0, V),
+ * order[rank[v]] = v (a stable ascending sort, by the caller).  markers: int32 (marker_bytes 4) or int64 (8) [N][V]; a
+ * value that is negative or above 2^31 - 1 counts as no marker.  mask: uint8 [N][V], non-zero = inside; NULL = everything.
+ * out: int32 [N][V], the marker value of each masked voxel's tree, 0 for a masked voxel without a path to a marker and
+ * outside the mask.  rounds_out: NULL or a device int32 that receives the number of rounds that did work (at most
+ * tem_watershed_rounds(V) = ceil(log2(V)) + 1, the number enqueued).  ws: tem_watershed_ws(N, V) bytes (20 per voxel and a
+ * few flags), 16-byte aligned.  One call enqueues everything; nothing is read back by the host. */
+int tem_watershed_rounds(int64_t V);
+int64_t tem_watershed_ws(int N, int64_t V);
+int tem_watershed(const int* rank, const int* order, const void* markers, int marker_bytes, const uint8_t* mask, int* out,
+                  int* rounds_out, int N, int D, int H, int W, void* ws, int64_t ws_bytes, tem_stream_t stream);
 
 /* ---- EM defect augmentation (transform/defect.py: EMDefectAugmentation :41-245; csrc/defect.hip) -------------------------
  * x, y: S contiguous float32 slices of H x W (L = H * W; any 4-byte aligned base).  Two device tables written by the host

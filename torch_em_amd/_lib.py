@@ -234,6 +234,11 @@ SIGNATURES = {
     "tem_rawaug_poisson_add": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_u64, c_u32, c_int, c_float, c_float, c_vp]),
     "tem_rawaug_poisson_scaled": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_u64, c_u32, c_int, c_float, c_float, c_vp]),
     "tem_rawaug_blur2d": (c_int, [c_vp, c_vp, c_i64, c_int, c_int, c_vp, c_vp, c_int, c_int, c_vp]),
+    "tem_rawaug_blur_z": (c_int, [c_vp, c_vp, c_i64, c_int, c_i64, c_vp, c_int, c_vp]),
+    # seeded watershed (csrc/watershed.hip): (rank, order, markers, marker_bytes, mask, out, rounds_out, N, D, H, W, ws, ws_bytes, stream)
+    "tem_watershed_rounds": (c_int, [c_i64]),
+    "tem_watershed_ws": (c_i64, [c_int, c_i64]),
+    "tem_watershed": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
     # EM defect augmentation (csrc/defect.hip): plan int32 [S][4], rec int32 [D][8], tables int32 (include/tem_hip.h)
     "tem_defect_mean": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp]),
     "tem_defect_apply": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),

@@ -300,3 +300,57 @@ extern "C" int tem_rawaug_blur2d(const float* x, float* y, int64_t P, int H, int
     TEM_CHECK_LAUNCH("tem_rawaug_blur2d");
     return TEM_OK;
 }
+
+// ---------------------------------------------------------------------------
+// the third pass of a separable blur: taps along z, streaming along the H*W plane
+// ---------------------------------------------------------------------------
+// grid-stride over groups of VEC consecutive elements of a plane (VEC = 4: planes of a multiple of 4 elements at 16-byte
+// aligned bases); one accumulation chain per output, taps in ascending order
+template <int VEC>
+__global__ __launch_bounds__(256) void k_ra_blur_z(const float* __restrict__ x, float* __restrict__ y, int64_t P, int D, int64_t HW,
+                                                   const float* __restrict__ wz, int kz) {
+    const int rz = kz >> 1;
+    const int64_t per = HW / VEC, total = P * D * per;
+    for (int64_t e = (int64_t)blockIdx.x * 256 + threadIdx.x; e < total; e += (int64_t)gridDim.x * 256) {
+        const int64_t i = (e % per) * VEC, pz = e / per;
+        const int z = (int)(pz % D);
+        const float* src = x + (pz - z) * HW + i;
+        float acc[VEC];
+#pragma unroll
+        for (int c = 0; c < VEC; ++c) acc[c] = 0.f;
+        for (int j = 0; j < kz; ++j) {
+            const float* s = src + (int64_t)ra_reflect(z - rz + j, D) * HW;
+            const float w = wz[j];
+            if (VEC == 4) {
+                const float4 v = *(const float4*)s;
+                acc[0] = __builtin_fmaf(w, v.x, acc[0]);
+                acc[1] = __builtin_fmaf(w, v.y, acc[1]);
+                acc[2] = __builtin_fmaf(w, v.z, acc[2]);
+                acc[3] = __builtin_fmaf(w, v.w, acc[3]);
+            } else {
+                acc[0] = __builtin_fmaf(w, s[0], acc[0]);
+            }
+        }
+        float* o = y + pz * HW + i;
+        if (VEC == 4)
+            *(float4*)o = make_float4(acc[0], acc[1], acc[2], acc[3]);
+        else
+            o[0] = acc[0];
+    }
+}
+
+extern "C" int tem_rawaug_blur_z(const float* x, float* y, int64_t P, int D, int64_t HW, const float* wz, int kz,
+                                 tem_stream_t stream) {
+    TEM_REQUIRE(x && y && wz && x != y && P > 0 && D > 0 && HW > 0, "tem_rawaug_blur_z: bad arguments (x and y must differ)");
+    TEM_REQUIRE(kz >= 1 && kz <= RA_KMAX && (kz & 1), "tem_rawaug_blur_z: the tap count must be odd and within 1..%d (got %d)",
+                RA_KMAX, kz);
+    TEM_REQUIRE(kz / 2 < D, "tem_rawaug_blur_z: the reflect border needs k/2 < size (%d taps on %d planes)", kz, D);
+    const bool vec = HW % 4 == 0 && ((((uintptr_t)x) | ((uintptr_t)y)) & 15u) == 0;
+    const int64_t groups = P * D * (vec ? HW / 4 : HW);
+    if (vec)
+        hipLaunchKernelGGL(k_ra_blur_z<4>, dim3(tem_grid_1d(groups, 256)), dim3(256), 0, (hipStream_t)stream, x, y, P, D, HW, wz, kz);
+    else
+        hipLaunchKernelGGL(k_ra_blur_z<1>, dim3(tem_grid_1d(groups, 256)), dim3(256), 0, (hipStream_t)stream, x, y, P, D, HW, wz, kz);
+    TEM_CHECK_LAUNCH("tem_rawaug_blur_z");
+    return TEM_OK;
+}

@@ -1773,6 +1773,31 @@ def blur2d(x: torch.Tensor, wy, wx=None) -> torch.Tensor:
     return y
 
 
+def blur3d(x: torch.Tensor, wz, wy, wx) -> torch.Tensor:
+    """The last three axes of x convolved with the 1-D weights wz (along D), wy (along H) and wx (along W): `blur2d` of
+    every plane, then a pass that streams along the plane and takes its taps along z (tem_rawaug_blur_z), the same reflect
+    border without edge repeat on all three axes.  Weights: HOST sequences of odd length <= 63 with len // 2 < the axis'
+    size; the one tap [1.0] along z (all a volume of D = 1 admits) leaves `blur2d`."""
+    _req_cuda(x)
+    if x.dim() < 3 or x.numel() == 0:
+        raise ValueError(f"blur3d: expected a non-empty tensor of at least three axes, got shape {tuple(x.shape)}")
+    wz = [float(v) for v in wz]
+    D = int(x.shape[-3])
+    if len(wz) % 2 == 0 or len(wz) > 63:
+        raise ValueError(f"blur3d: the tap count along z must be odd and within 1..63 (got {len(wz)})")
+    if len(wz) // 2 >= D:
+        raise ValueError(f"blur3d: the reflect border needs k/2 < size ({len(wz)} taps along z on {D} planes)")
+    y = blur2d(x, wy, wx)
+    if wz == [1.0]:
+        return y
+    HW = int(x.shape[-2]) * int(x.shape[-1])
+    dz = _fill(wz, len(wz), x.device, "wz")
+    out = torch.empty_like(y)
+    _lib.check(_lib.load().tem_rawaug_blur_z(_p(y), _p(out), y.numel() // (D * HW), D, HW, _p(dz), len(wz), _stream(y)),
+               "tem_rawaug_blur_z")
+    return out
+
+
 # ---- EM defect augmentation (csrc/defect.hip; the tables: include/tem_hip.h, host side: transform/defect.py) ----
 DEFECT_KEEP, DEFECT_DROP, DEFECT_LOW, DEFECT_PASTE, DEFECT_DEFORM = range(5)
 DEFECT_KMAX = 33   # taps of the separable filter
@@ -1961,6 +1986,86 @@ def size_filter_(ids: torch.Tensor, min_size: int) -> torch.Tensor:
     newid = _flat_cumsum(keep)
     _lib.check(lib.tem_pod_size_apply(_p(ids), _p(keep), _p(newid), N, V, _stream(ids)), "tem_pod_size_apply")
     return ids
+
+
+# ---- seeded watershed (csrc/watershed.hip) ----
+_WS_MARKERS = (torch.bool, torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+def watershed_rounds(V: int) -> int:
+    """ceil(log2(V)) + 1: the Boruvka rounds `seeded_watershed` enqueues for samples of V voxels, the bound of `rounds_out`"""
+    return max(int(V) - 1, 0).bit_length() + 1
+
+
+def voxel_ranks(height: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
+    """float32 heights [N, ...] -> (rank, order), int32 [N, V]: the voxels of each sample ranked by (height, linear index),
+    by a stable ascending sort (`np.argsort(kind="stable")` of the flattened sample): order[n, rank[n, v]] = v.  -0.0 and
+    0.0 tie.  The heights are not read back: NaNs are not rejected and where they are ranked is not promised."""
+    if height.dtype != torch.float32 or height.dim() < 2 or height.numel() == 0:
+        raise ValueError(f"voxel_ranks: expected non-empty float32 heights [N, ...], got {height.dtype} {tuple(height.shape)}")
+    _req_cuda(height)
+    N = int(height.shape[0])
+    V = height.numel() // N
+    if V >= 2 ** 31 - 1:
+        raise ValueError(f"voxel_ranks: {V} voxels per sample, at most 2^31 - 2 supported")
+    # x + 0.0 turns -0.0 into 0.0 and nothing else: a sort that compares bit patterns ties the two as well
+    order = torch.sort(height.reshape(N, V) + 0.0, dim=1, stable=True).indices
+    rank = torch.empty((N, V), dtype=torch.int32, device=height.device)
+    rank.scatter_(1, order, torch.arange(V, dtype=torch.int32, device=height.device).expand(N, V))
+    return rank, order.to(torch.int32)
+
+
+def _ws_args(height, markers, mask, rounds_out):
+    """the host-side checks of `seeded_watershed` (dtypes, shapes; the values of tensors that are still on the host)"""
+    if height.dim() != 4 or height.dtype != torch.float32 or height.numel() == 0:
+        raise ValueError(f"seeded_watershed: expected non-empty float32 heights [N, D, H, W], got {height.dtype} {tuple(height.shape)}")
+    if markers.dtype not in _WS_MARKERS:
+        raise ValueError(f"seeded_watershed: markers must be of an integer type, got {markers.dtype}")
+    if markers.shape != height.shape:
+        raise ValueError(f"seeded_watershed: markers {tuple(markers.shape)} do not match the heights {tuple(height.shape)}")
+    if mask is not None and (mask.dtype != torch.bool or mask.shape != height.shape):
+        raise ValueError(f"seeded_watershed: expected a bool mask {tuple(height.shape)}, got {mask.dtype} {tuple(mask.shape)}")
+    if rounds_out is not None and (rounds_out.dtype != torch.int32 or rounds_out.numel() != 1):
+        raise ValueError(f"seeded_watershed: rounds_out is one int32, got {rounds_out.dtype} {tuple(rounds_out.shape)}")
+    V = height.numel() // int(height.shape[0])
+    if V >= 2 ** 31 - 1:
+        raise ValueError(f"seeded_watershed: {V} voxels per sample, at most 2^31 - 2 supported")
+    if not markers.is_cuda and markers.dtype != torch.bool and int(markers.min()) < 0:
+        raise ValueError("seeded_watershed: markers must be >= 0")
+    if not height.is_cuda and not bool(torch.isfinite(height).all()):
+        raise ValueError("seeded_watershed: heights must be finite")
+
+
+def seeded_watershed(height: torch.Tensor, markers: torch.Tensor, mask: Optional[torch.Tensor] = None,
+                     rounds_out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """Seeded watershed of float32 heights [N, D, H, W] (2-D: D = 1) from integer markers >= 0 inside a bool mask (None:
+    everything) -> int32 [N, D, H, W]: the minimum spanning forest rooted in the markers (tem_watershed; the definition:
+    DESIGN.md "Seeded watershed").  Voxels are ranked by (height, linear index) (`voxel_ranks`), an edge between masked
+    face neighbours is as high as its higher end, ties go to the lower other end; every masked voxel takes the marker of
+    its tree, a masked voxel without a path to a marker and every voxel outside the mask get 0; markers outside the mask
+    are ignored, marker voxels keep their value.  On heights without ties this is a priority flood's segmentation up to the
+    voxels on a pass; a PLATEAU goes to the marker that reaches it first in raster order, it is not split half-way.
+    Deterministic, stream-ordered, nothing is read back: the values of device tensors are not checked -- a negative marker
+    (or one above 2^31 - 1) counts as no marker, and heights must be finite (tensors still on the host are checked and then
+    refused like any host tensor).  rounds_out: a device int32 that receives the rounds that did work, at most
+    `watershed_rounds(D * H * W)`."""
+    _ws_args(height, markers, mask, rounds_out)
+    _req_cuda(height, markers, mask, rounds_out)
+    N, D, H, W = (int(s) for s in height.shape)
+    V = D * H * W
+    height = height.contiguous()
+    if markers.dtype not in (torch.int32, torch.int64):
+        markers = markers.to(torch.int32)
+    markers = markers.contiguous()
+    mask = None if mask is None else mask.contiguous()
+    rank, order = voxel_ranks(height)
+    lib = _lib.load()
+    nbytes = int(lib.tem_watershed_ws(N, V))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=height.device)
+    out = torch.empty((N, D, H, W), dtype=torch.int32, device=height.device)
+    _lib.check(lib.tem_watershed(_p(rank), _p(order), _p(markers), markers.element_size(), _p(mask), _p(out), _p(rounds_out),
+                                 N, D, H, W, _p(ws), nbytes, _stream(height)), "tem_watershed")
+    return out
 
 
 def pod_targets(ids: torch.Tensor, ndim: int, sampling, flags: int, fill: float) -> torch.Tensor:
