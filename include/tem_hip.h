@@ -1104,6 +1104,39 @@ int64_t tem_watershed_ws(int N, int64_t V);
 int tem_watershed(const int* rank, const int* order, const void* markers, int marker_bytes, const uint8_t* mask, int* out,
                   int* rounds_out, int N, int D, int H, int W, void* ws, int64_t ws_bytes, tem_stream_t stream);
 
+/* ---- label overlaps and instance-segmentation scores (csrc/overlap.hip; the definitions: DESIGN.md "Instance
+ * segmentation scores") ------------------------------------------------------------------------------------------------
+ * The contingency table of two label batches [N][V], V < 2^31 - 1 and N * V < 2^31 - 1, N <= 65535, whose ids a (first
+ * volume) and b (second) are dense per sample: 0..V.  The caller forms the keys a * (V + 1) + b (int64 [N][V]), sorts them
+ * per sample, has the run ends flagged (flag: int32 [N][V]) and hands in the flat inclusive prefix sum of the flags (rank:
+ * int32 [N * V]; the table kernel subtracts the previous sample's total).
+ *   the table: pa, pb, n_ab int32 [N][V] -- the distinct pairs in ascending (a, b) order with their voxel counts, valid below
+ *   npairs[n] (int32 [N]); the marginals n_a, n_b int32 [N][V + 1], indexed by id.  An id outside 0..V is clamped.
+ *   the scores: one TemOverlapRecord per sample; best_a, best_b (double [N][V + 1]): per object of either side the maximum
+ *   over the objects of the other side of 2 n_ab / (n_a + n_b) (label 0 ignored on both sides, 0 without a partner).
+ *   threshold in [0.5, 1]: below 0.5 the match graph is no longer a set of isolated pairs (and stars of two at exactly
+ *   0.5) and the count of tp would need an assignment solver -- refused.
+ * ws: tem_overlap_ws(N, V) bytes (about 12 per voxel), 16-byte aligned, shared by both calls (nothing is carried over in
+ * it).  Integer fields are exact; every floating-point sum is reduced in a fixed order, so a record is bit-identical from
+ * run to run.  Nothing is read back by the host. */
+typedef struct TemOverlapRecord {
+    uint64_t sum_ab, sum_a, sum_b; /* sum n_ab^2 over the pairs, sum n_a^2, sum n_b^2 over the ids (label 0 included) */
+    double s_ab, s_a, s_b;         /* sum n log2 n over the same */
+    double dice_pred, dice_true;   /* the mean of best_a over the objects of the first volume, of best_b over the second's; 0
+                                      for a side without objects */
+    int32_t n_pred, n_true;        /* the distinct non-zero ids of the first and of the second volume */
+    int32_t tp;                    /* pairs with a, b != 0 and n_ab >= threshold * (n_a + n_b - n_ab), minus the objects of
+                                      either side that have two of them */
+    int32_t npairs;
+} TemOverlapRecord;
+int64_t tem_overlap_ws(int N, int64_t V);
+int tem_overlap_flag(const int64_t* sorted, int* flag, int N, int64_t V, tem_stream_t stream);
+int tem_overlap_table(const int64_t* sorted, const int* rank, int* pa, int* pb, int* n_ab, int* npairs, int* n_a, int* n_b, int N,
+                      int64_t V, void* ws, int64_t ws_bytes, tem_stream_t stream);
+int tem_overlap_scores(const int* pa, const int* pb, const int* n_ab, const int* npairs, const int* n_a, const int* n_b,
+                       double threshold, TemOverlapRecord* rec, double* best_a, double* best_b, int N, int64_t V, void* ws,
+                       int64_t ws_bytes, tem_stream_t stream);
+
 /* ---- EM defect augmentation (transform/defect.py: EMDefectAugmentation :41-245; csrc/defect.hip) -------------------------
  * x, y: S contiguous float32 slices of H x W (L = H * W; any 4-byte aligned base).  Two device tables written by the host
  * describe a call, so the launches do not depend on what the plan says:

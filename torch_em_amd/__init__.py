@@ -13,7 +13,7 @@ def __getattr__(name):
     if name in ("default_segmentation_trainer", "default_segmentation_loader", "default_segmentation_dataset"):
         from . import segmentation
         return getattr(segmentation, name)
-    if name in ("model", "loss", "transform", "trainer", "multi_gpu_training", "segmentation", "ops", "data"):
+    if name in ("model", "loss", "transform", "trainer", "multi_gpu_training", "segmentation", "ops", "data", "metric"):
         import importlib
         return importlib.import_module(f"{__name__}.{name}")
     raise AttributeError(name)

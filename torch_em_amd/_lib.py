@@ -239,6 +239,13 @@ SIGNATURES = {
     "tem_watershed_rounds": (c_int, [c_i64]),
     "tem_watershed_ws": (c_i64, [c_int, c_i64]),
     "tem_watershed": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
+    # label overlaps and instance-segmentation scores (csrc/overlap.hip): (sorted, flag, N, V, stream) /
+    # (sorted, rank, pa, pb, n_ab, npairs, n_a, n_b, N, V, ws, ws_bytes, stream) /
+    # (pa, pb, n_ab, npairs, n_a, n_b, threshold, rec, best_a, best_b, N, V, ws, ws_bytes, stream)
+    "tem_overlap_ws": (c_i64, [c_int, c_i64]),
+    "tem_overlap_flag": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp]),
+    "tem_overlap_table": (c_int, [c_vp] * 8 + [c_int, c_i64, c_vp, c_i64, c_vp]),
+    "tem_overlap_scores": (c_int, [c_vp] * 6 + [c_double, c_vp, c_vp, c_vp, c_int, c_i64, c_vp, c_i64, c_vp]),
     # EM defect augmentation (csrc/defect.hip): plan int32 [S][4], rec int32 [D][8], tables int32 (include/tem_hip.h)
     "tem_defect_mean": (c_int, [c_vp, c_int, c_i64, c_vp, c_vp, c_vp]),
     "tem_defect_apply": (c_int, [c_vp, c_vp, c_int, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp]),

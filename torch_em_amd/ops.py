@@ -8,7 +8,7 @@ There is no CPU fallback: CPU tensors raise.
 """
 import ctypes
 import math
-from typing import Optional, Sequence, Tuple
+from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
 
@@ -2066,6 +2066,117 @@ def seeded_watershed(height: torch.Tensor, markers: torch.Tensor, mask: Optional
     _lib.check(lib.tem_watershed(_p(rank), _p(order), _p(markers), markers.element_size(), _p(mask), _p(out), _p(rounds_out),
                                  N, D, H, W, _p(ws), nbytes, _stream(height)), "tem_watershed")
     return out
+
+
+# ---- label overlaps and instance-segmentation scores (csrc/overlap.hip) ----
+_OV_LABELS = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+
+
+class LabelOverlaps(NamedTuple):
+    """The contingency table of two label batches of V voxels per sample, all on the device (`label_overlaps`): the
+    distinct (seg id, target id) pairs in ascending order with their voxel counts -- rows below `npairs[n]` are valid,
+    the rest is unspecified -- and both marginals, indexed by the DENSE ids (0 stays 0, the other values 1..n in
+    ascending order, per sample)."""
+    pa: torch.Tensor       # int32 [N, V]
+    pb: torch.Tensor       # int32 [N, V]
+    n_ab: torch.Tensor     # int32 [N, V]
+    npairs: torch.Tensor   # int32 [N]
+    n_a: torch.Tensor      # int32 [N, V + 1]
+    n_b: torch.Tensor      # int32 [N, V + 1]
+    ws: torch.Tensor       # uint8 [tem_overlap_ws(N, V)], scratch of both calls
+
+
+class OverlapScores(NamedTuple):
+    """Per-sample sums over a contingency table (`overlap_scores`; include/tem_hip.h: TemOverlapRecord), on the device"""
+    sum_ab: torch.Tensor      # int64 [N]    sum n_ab^2 (exact; below 2^62)
+    sum_a: torch.Tensor       # int64 [N]    sum n_a^2
+    sum_b: torch.Tensor       # int64 [N]    sum n_b^2
+    s_ab: torch.Tensor        # float64 [N]  sum n_ab log2 n_ab
+    s_a: torch.Tensor         # float64 [N]
+    s_b: torch.Tensor         # float64 [N]
+    dice_pred: torch.Tensor   # float64 [N]  mean best Dice of the seg objects against the target's
+    dice_true: torch.Tensor   # float64 [N]  mean best Dice of the target objects against the seg's
+    n_pred: torch.Tensor      # int32 [N]    distinct non-zero ids of seg
+    n_true: torch.Tensor      # int32 [N]    distinct non-zero ids of target
+    tp: torch.Tensor          # int32 [N]    matches at the threshold
+    best_pred: torch.Tensor   # float64 [N, V + 1]  best Dice per dense seg id (0 for id 0 and absent ids)
+    best_true: torch.Tensor   # float64 [N, V + 1]
+    n: int                    # voxels per sample
+
+
+def _ov_args(seg, target):
+    """the host-side checks of `label_overlaps` (dtypes and shapes; values are not looked at)"""
+    for name, t in (("seg", seg), ("target", target)):
+        if not torch.is_tensor(t) or t.dtype not in _OV_LABELS:
+            raise ValueError(f"label_overlaps: {name} must be a tensor of an integer type, got {getattr(t, 'dtype', type(t))}")
+    if seg.shape != target.shape:
+        raise ValueError(f"label_overlaps: seg {tuple(seg.shape)} and target {tuple(target.shape)} must have one shape")
+    if seg.dim() != 4 or seg.numel() == 0:
+        raise ValueError(f"label_overlaps: expected non-empty labels [N, D, H, W], got {tuple(seg.shape)}")
+    N = int(seg.shape[0])
+    V = seg.numel() // N
+    if V >= 2 ** 31 - 1 or N * V >= 2 ** 31 - 1 or N > 65535:
+        raise ValueError(f"label_overlaps: {N} samples of {V} voxels; at most 2^31 - 2 voxels in all and 65535 samples supported")
+    return N, V
+
+
+def label_overlaps(seg: torch.Tensor, target: torch.Tensor) -> LabelOverlaps:
+    """The contingency table of two integer label batches [N, D, H, W] (2-D: D = 1) of one shape, any integer dtype, values
+    >= 0, built per sample on the device (tem_overlap_flag / tem_overlap_table; DESIGN.md "Instance segmentation scores").
+    Both sides are made dense first (`pod_ids(x, False, 0)`: 0 stays 0, the other values become 1..n ascending), so pa,
+    pb and the marginals speak of dense ids.  Deterministic, stream-ordered, nothing is read back: the values of device
+    tensors are not inspected -- a negative id is not refused, it is numbered like any other non-zero value; host tensors
+    are refused like any host tensor."""
+    N, V = _ov_args(seg, target)
+    _req_cuda(seg, target)
+    a = pod_ids(seg, False, 0).view(N, V)
+    b = pod_ids(target, False, 0).view(N, V)
+    key = a.to(torch.int64).mul_(V + 1).add_(b)
+    srt = torch.sort(key, dim=1).values
+    dev = seg.device
+    lib = _lib.load()
+    flag = torch.empty((N * V,), dtype=torch.int32, device=dev)
+    _lib.check(lib.tem_overlap_flag(_p(srt), _p(flag), N, V, _stream(seg)), "tem_overlap_flag")
+    rank = _flat_cumsum(flag)
+    nbytes = int(lib.tem_overlap_ws(N, V))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    pa, pb, n_ab = (torch.empty((N, V), dtype=torch.int32, device=dev) for _ in range(3))
+    n_a, n_b = (torch.empty((N, V + 1), dtype=torch.int32, device=dev) for _ in range(2))
+    npairs = torch.empty((N,), dtype=torch.int32, device=dev)
+    _lib.check(lib.tem_overlap_table(_p(srt), _p(rank), _p(pa), _p(pb), _p(n_ab), _p(npairs), _p(n_a), _p(n_b), N, V, _p(ws),
+                                     nbytes, _stream(seg)), "tem_overlap_table")
+    return LabelOverlaps(pa, pb, n_ab, npairs, n_a, n_b, ws)
+
+
+def _ov_threshold(threshold) -> float:
+    threshold = float(threshold)
+    if not 0.5 <= threshold <= 1.0:
+        raise ValueError(f"overlap_scores: threshold {threshold}: a threshold below 0.5 needs an assignment solver and is not "
+                         "provided (0.5 <= threshold <= 1)")
+    return threshold
+
+
+def overlap_scores(ov: LabelOverlaps, threshold: float = 0.5) -> OverlapScores:
+    """The sums every instance score is a fixed expression of, per sample, from a contingency table (tem_overlap_scores;
+    the fields: `OverlapScores`).  Label 0 counts in the sums of squares and of n log2 n; it is ignored in n_pred, n_true,
+    tp and the best Dice.  tp counts the pairs with n_ab >= threshold * (n_a + n_b - n_ab) minus the objects of either
+    side with two of them: the size of the maximum matching for 0.5 <= threshold <= 1; a threshold below
+    0.5 is refused.  Integer fields are exact, the float64 sums are reduced in a fixed order: bit-identical from run to
+    run.  Nothing is read back."""
+    threshold = _ov_threshold(threshold)
+    _req_cuda(*ov[:7])
+    N, V = (int(s) for s in ov.pa.shape)
+    dev = ov.pa.device
+    lib = _lib.load()
+    rec = torch.empty((N, 10), dtype=torch.int64, device=dev)
+    best = torch.empty((2, N, V + 1), dtype=torch.float64, device=dev)
+    _lib.check(lib.tem_overlap_scores(_p(ov.pa), _p(ov.pb), _p(ov.n_ab), _p(ov.npairs), _p(ov.n_a), _p(ov.n_b), threshold,
+                                      _p(rec), _p(best[0]), _p(best[1]), N, V, _p(ov.ws), ov.ws.numel(), _stream(ov.pa)),
+               "tem_overlap_scores")
+    real = rec[:, 3:8].view(torch.float64)
+    ints = rec[:, 8:10].view(torch.int32)
+    return OverlapScores(rec[:, 0], rec[:, 1], rec[:, 2], real[:, 0], real[:, 1], real[:, 2], real[:, 3], real[:, 4],
+                         ints[:, 0], ints[:, 1], ints[:, 2], best[0], best[1], V)
 
 
 def pod_targets(ids: torch.Tensor, ndim: int, sampling, flags: int, fill: float) -> torch.Tensor:
