@@ -1104,6 +1104,31 @@ int64_t tem_watershed_ws(int N, int64_t V);
 int tem_watershed(const int* rank, const int* order, const void* markers, int marker_bytes, const uint8_t* mask, int* out,
                   int* rounds_out, int N, int D, int H, int W, void* ws, int64_t ws_bytes, tem_stream_t stream);
 
+/* ---- mutex watershed (csrc/mws.hip; the definition: DESIGN.md "Mutex watershed") ---------------------------------------
+ * Kruskal with mutex constraints over the affinity graph of a batch [N][C][D][H][W] (2-D: D == 1), V = D*H*W < 2^31 - 1,
+ * C <= TEM_MWS_MAX_CHANNELS, C * V < 2^32 - 1, N * V < 2^33 - 1.  offsets: HOST int32 [C][3] (dz, dy, dx); edge (c, v)
+ * joins v and v + offsets[c] when that voxel is inside the sample, both are inside mask (uint8 [N][V], non-zero = inside;
+ * NULL = everything) and edge_valid (uint8 [N][C][V]; NULL = every edge) is non-zero.  The first n_attractive channels
+ * are attractive (priority 1 - aff), the others repulsive (priority aff); aff: float32 [N][C][V].
+ *   tem_mws_init   builds the state in ws (tem_mws_ws bytes, 16-byte aligned) and counts the edges: when it has run the
+ *                  workspace starts with two uint64 -- the existing edges and the existing repulsive edges of the batch.
+ *   tem_mws_run    enqueues `rounds` (1..TEM_MWS_MAX_BATCH) rounds; first != 0 on the call after tem_mws_init.  table:
+ *                  `slots` uint64, a power of two >= tem_mws_table_slots(repulsive edges) (twice their count at least), any
+ *                  content on the first call.  A round returns at once when the one before it did nothing.  When the batch
+ *                  has run, the int32 at byte 16 of ws holds the rounds that did work so far and the int32 at byte 20 is
+ *                  non-zero when the batch's last round did work: then another batch is due.
+ *   tem_mws_labels out: int32 [N][V], 0 outside the mask, else 1 + the smallest voxel index of the voxel's cluster.
+ * One stream throughout; the host reads back only what is named above. */
+#define TEM_MWS_MAX_CHANNELS 32
+#define TEM_MWS_MAX_BATCH 64
+int64_t tem_mws_ws(int N, int C, int D, int H, int W);
+int64_t tem_mws_table_slots(int64_t n_repulsive);
+int tem_mws_init(const uint8_t* mask, const uint8_t* edge_valid, const int* offsets, int n_attractive, int N, int C, int D, int H,
+                 int W, void* ws, int64_t ws_bytes, tem_stream_t stream);
+int tem_mws_run(const float* aff, const int* offsets, int n_attractive, int N, int C, int D, int H, int W, void* ws,
+                int64_t ws_bytes, uint64_t* table, int64_t slots, int first, int rounds, tem_stream_t stream);
+int tem_mws_labels(int* out, int N, int C, int D, int H, int W, void* ws, int64_t ws_bytes, tem_stream_t stream);
+
 /* ---- label overlaps and instance-segmentation scores (csrc/overlap.hip; the definitions: DESIGN.md "Instance
  * segmentation scores") ------------------------------------------------------------------------------------------------
  * The contingency table of two label batches [N][V], V < 2^31 - 1 and N * V < 2^31 - 1, N <= 65535, whose ids a (first

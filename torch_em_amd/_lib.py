@@ -239,6 +239,14 @@ SIGNATURES = {
     "tem_watershed_rounds": (c_int, [c_i64]),
     "tem_watershed_ws": (c_i64, [c_int, c_i64]),
     "tem_watershed": (c_int, [c_vp, c_vp, c_vp, c_int, c_vp, c_vp, c_vp, c_int, c_int, c_int, c_int, c_vp, c_i64, c_vp]),
+    # mutex watershed (csrc/mws.hip): (mask, edge_valid, offsets, n_attractive, N, C, D, H, W, ws, ws_bytes, stream) /
+    # (aff, offsets, n_attractive, N, C, D, H, W, ws, ws_bytes, table, slots, first, rounds, stream) /
+    # (out, N, C, D, H, W, ws, ws_bytes, stream)
+    "tem_mws_ws": (c_i64, [c_int] * 5),
+    "tem_mws_table_slots": (c_i64, [c_i64]),
+    "tem_mws_init": (c_int, [c_vp, c_vp, c_vp, c_int] + [c_int] * 5 + [c_vp, c_i64, c_vp]),
+    "tem_mws_run": (c_int, [c_vp, c_vp, c_int] + [c_int] * 5 + [c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp]),
+    "tem_mws_labels": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_i64, c_vp]),
     # label overlaps and instance-segmentation scores (csrc/overlap.hip): (sorted, flag, N, V, stream) /
     # (sorted, rank, pa, pb, n_ab, npairs, n_a, n_b, N, V, ws, ws_bytes, stream) /
     # (pa, pb, n_ab, npairs, n_a, n_b, threshold, rec, best_a, best_b, N, V, ws, ws_bytes, stream)

@@ -14,7 +14,8 @@ was compared with its output.  IoU thresholds below 0.5 are refused: there the m
 counting them needs an assignment solver.
 
 Not provided: the reference's `MWS*`, `EmbeddingMWS*`, `Multicut*` and `HDBScan*` classes (and their segmenters): the
-mutex watershed is sequential by nature (see util/segmentation.py), and there is no multicut solver and no HDBSCAN here.
+mutex watershed exists as a segmenter (util/mutex_watershed.py: `mutex_watershed_segmentation`) but its metric classes are not
+written, and there is no multicut solver and no HDBSCAN here.
 The prefab classes sit on the two watershed segmenters that exist: `Watershed{IOU,SBD,VOI,Rand}Metric`."""
 import torch
 import torch.nn as nn

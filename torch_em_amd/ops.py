@@ -8,6 +8,7 @@ There is no CPU fallback: CPU tensors raise.
 """
 import ctypes
 import math
+import numbers
 from typing import NamedTuple, Optional, Sequence, Tuple
 
 import torch
@@ -2066,6 +2067,101 @@ def seeded_watershed(height: torch.Tensor, markers: torch.Tensor, mask: Optional
     _lib.check(lib.tem_watershed(_p(rank), _p(order), _p(markers), markers.element_size(), _p(mask), _p(out), _p(rounds_out),
                                  N, D, H, W, _p(ws), nbytes, _stream(height)), "tem_watershed")
     return out
+
+
+# ---- mutex watershed (csrc/mws.hip) ----
+MWS_MAX_CHANNELS = 32          # TEM_MWS_MAX_CHANNELS
+MWS_MAX_BATCH = 64             # TEM_MWS_MAX_BATCH
+MWS_ROUNDS_PER_BATCH = 16      # the default: profiles/mws_bench.txt
+
+
+def mws_table_slots(n_repulsive: int) -> int:
+    """the slots of the mutex set for `n_repulsive` existing repulsive edges: a power of two, at least twice their count"""
+    return int(_lib.load().tem_mws_table_slots(int(n_repulsive)))
+
+
+def _mws_args(aff, offsets, n_attractive, mask, edge_valid, rounds_per_batch):
+    """the host-side checks of `mutex_watershed` (dtypes, shapes, offsets) -> offsets as a list of C (dz, dy, dx)"""
+    if not torch.is_tensor(aff) or aff.dim() != 5 or aff.dtype != torch.float32 or aff.numel() == 0:
+        raise ValueError("mutex_watershed: expected non-empty float32 affinities [N, C, D, H, W], got "
+                         f"{getattr(aff, 'dtype', type(aff))} {tuple(getattr(aff, 'shape', ()))}")
+    N, C, D, H, W = (int(s) for s in aff.shape)
+    V = D * H * W
+    try:
+        offs = [[int(x) for x in o] for o in offsets]
+    except (TypeError, ValueError):
+        raise ValueError("mutex_watershed: offsets must be integer vectors of length 2 or 3") from None
+    if len(offs) != C:
+        raise ValueError(f"mutex_watershed: {len(offs)} offsets do not match the {C} affinity channels")
+    if C > MWS_MAX_CHANNELS:
+        raise ValueError(f"mutex_watershed: {C} channels, at most {MWS_MAX_CHANNELS} supported")
+    if any(len(o) not in (2, 3) or len(o) != len(offs[0]) for o in offs):
+        raise ValueError("mutex_watershed: offsets must be integer vectors of one length, 2 or 3")
+    if len(offs[0]) == 2 and D != 1:
+        raise ValueError(f"mutex_watershed: offsets of length 2 need D = 1, got D = {D}")
+    if any(abs(x) >= 2 ** 30 for o in offs for x in o):
+        raise ValueError("mutex_watershed: offsets must be below 2^30 in magnitude")
+    if isinstance(n_attractive, bool) or not isinstance(n_attractive, numbers.Integral) or not 0 <= n_attractive <= C:
+        raise ValueError(f"mutex_watershed: n_attractive must be an integer within 0..{C}, got {n_attractive}")
+    if mask is not None and (mask.dtype != torch.bool or tuple(mask.shape) != (N, D, H, W)):
+        raise ValueError(f"mutex_watershed: expected a bool mask {(N, D, H, W)}, got {mask.dtype} {tuple(mask.shape)}")
+    if edge_valid is not None and (edge_valid.dtype != torch.bool or edge_valid.shape != aff.shape):
+        raise ValueError(f"mutex_watershed: expected bool edge_valid {tuple(aff.shape)}, got {edge_valid.dtype} {tuple(edge_valid.shape)}")
+    if V >= 2 ** 31 - 1 or C * V >= 2 ** 32 - 1 or N * V >= 2 ** 33 - 1:
+        raise ValueError(f"mutex_watershed: {N} samples of {C} x {V} edges; V below 2^31 - 1, C * V below 2^32 - 1 and "
+                         "N * V below 2^33 - 1 supported")
+    if isinstance(rounds_per_batch, bool) or not isinstance(rounds_per_batch, numbers.Integral) or not 1 <= rounds_per_batch <= MWS_MAX_BATCH:
+        raise ValueError(f"mutex_watershed: rounds_per_batch must be an integer within 1..{MWS_MAX_BATCH}, got {rounds_per_batch}")
+    return [[0] * (3 - len(o)) + o for o in offs]
+
+
+def mutex_watershed(aff: torch.Tensor, offsets, n_attractive: int, mask: Optional[torch.Tensor] = None,
+                    edge_valid: Optional[torch.Tensor] = None, rounds_per_batch: int = MWS_ROUNDS_PER_BATCH,
+                    return_rounds: bool = False):
+    """Mutex watershed of float32 affinities [N, C, D, H, W] (2-D: D = 1) -> int32 ids [N, D, H, W] (tem_mws_*; the
+    definition: DESIGN.md "Mutex watershed").  Edge (c, v) joins voxel v and v + offsets[c] (C integer vectors of length 2
+    or 3) when that voxel is inside the sample, both are inside the bool `mask` [N, D, H, W] (None: everything) and the
+    bool `edge_valid` [N, C, D, H, W] (None: every edge) is set; edges never cross samples.  The `n_attractive` leading
+    channels are attractive with priority 1 - aff, the others repulsive with priority aff (float32; -0.0 ties with 0.0);
+    edges are taken by priority descending, ties by the lower id c * V + v: an attractive edge merges its two clusters
+    unless they are one or mutually exclusive (the union inherits the mutexes), a repulsive edge between two clusters makes
+    them mutually exclusive.  Ids: 0 outside the mask, else 1..n per sample in raster order of each cluster's first voxel;
+    a masked voxel without edges is a segment of its own.  The result is that of the sequential algorithm, bit for bit;
+    where NaN affinities are placed is not promised, and parity with affogato / elf is not pinned (their sort leaves the
+    order of ties open).
+    The number of rounds depends on the data: rounds are enqueued `rounds_per_batch` (1..64) at a time and two ints are
+    read back after each batch, plus the edge counts once at the start (they size the mutex set).  `return_rounds`: also
+    the number of rounds that did work."""
+    offs = _mws_args(aff, offsets, n_attractive, mask, edge_valid, rounds_per_batch)
+    _req_cuda(aff, mask, edge_valid)
+    N, C, D, H, W = (int(s) for s in aff.shape)
+    aff = aff.contiguous()
+    mask = None if mask is None else mask.contiguous()
+    edge_valid = None if edge_valid is None else edge_valid.contiguous()
+    dev = aff.device
+    lib = _lib.load()
+    coffs = (ctypes.c_int * (3 * C))(*[x for o in offs for x in o])
+    geom = (int(n_attractive), N, C, D, H, W)
+    nbytes = int(lib.tem_mws_ws(N, C, D, H, W))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    _lib.check(lib.tem_mws_init(_p(mask), _p(edge_valid), coffs, *geom, _p(ws), nbytes, _stream(aff)), "tem_mws_init")
+    n_edges, n_rep = ws[:16].view(torch.int64).tolist()
+    slots = mws_table_slots(n_rep)
+    table = torch.empty((slots,), dtype=torch.int64, device=dev)
+    first, work = 1, 0
+    while True:
+        _lib.check(lib.tem_mws_run(_p(aff), coffs, *geom, _p(ws), nbytes, _p(table), slots, first, int(rounds_per_batch),
+                                   _stream(aff)), "tem_mws_run")
+        work, alive = ws[16:24].view(torch.int32).tolist()
+        first = 0
+        if work > n_edges + 1:
+            raise RuntimeError(f"mutex_watershed: {work} working rounds for {n_edges} edges: every working round commits an edge")
+        if not alive:
+            break
+    first_voxel = torch.empty((N, D, H, W), dtype=torch.int32, device=dev)
+    _lib.check(lib.tem_mws_labels(_p(first_voxel), N, C, D, H, W, _p(ws), nbytes, _stream(aff)), "tem_mws_labels")
+    ids = pod_ids(first_voxel, False, 0)       # 1 + first voxel, ascending -> 1..n in raster order of the first voxel
+    return (ids, work) if return_rounds else ids
 
 
 # ---- label overlaps and instance-segmentation scores (csrc/overlap.hip) ----

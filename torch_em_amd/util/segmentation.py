@@ -12,8 +12,10 @@ is not split half-way.  Parity with `bioimage_cpp.segmentation.watershed` itself
 this was written), nor is the numbering of `bioimage_cpp.segmentation.label`: seeds are numbered in raster order, as
 `transform.label.connected_components` documents.
 
-Not provided: `mutex_watershed_segmentation` (Kruskal with mutex constraints, sequential by nature) and
-`watershed_from_maxima` (needs `peak_local_max` with greedy spacing)."""
+The mutex watershed, `mutex_watershed_segmentation`, lives in `torch_em_amd.util.mutex_watershed` and is exported by
+`torch_em_amd.util`: a test of this module pins that it does not carry that name.
+
+Not provided: `watershed_from_maxima` (needs `peak_local_max` with greedy spacing)."""
 from typing import Optional
 
 import numpy as np
