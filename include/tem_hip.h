@@ -271,6 +271,48 @@ int tem_conv3d_fwd_valu_path(const void* x, int64_t x_ld, const void* scale, con
                              const void* bias, const void* y, int64_t y_ld, const void* ref, int64_t ref_ld, int N, int D, int H,
                              int W, int Cin, int Cout, int kd, int kh, int kw, int act, int use_mfma, int has_stat, int* inst);
 
+/* Which kernel of the MATRIX-CORE forward / data-gradient family (use_mfma 1 .. 7, with the storage types in its high bits) a
+ * tem_conv3d_fwd / _stats / _gscaled / _refnorm / _ex launch with EXACTLY these arguments takes, and which instantiation of it;
+ * launches nothing and reads no device memory (bp is a host struct and is only read).  has_stat: the launch carries stat_part;
+ * in_amax / ref_coef / x_cs / y_cs / bp as in tem_conv3d_fwd_ex.  Returns TEM_MFMA_* or -1 for a launch the library refuses
+ * (the launch's own argument checks and its plan run: a failed one leaves its message for tem_last_error()) and for use_mfma 0.
+ * The plan (csrc/conv.hip: fwd_plan) prefers: z-reuse team kernel (3x3x3, D >= 4, enough 4 x 16 x 8 tiles x Cout / 32 units for
+ * two per CU, or option conv_fwd_variant 2), ping-pong team kernel (3x3x3 / 1x3x3, D >= 4, 4 x 8 x 8 patches, units likewise or
+ * conv_fwd_variant 1), z-reuse with split input channels (too few units, workspace given), 1x1x1 stream (NV >= 16384, no
+ * pre-norm / statistics / sigmoid), patch kernel; the team kernels need 16-byte aligned y / ref (z-reuse: and bias) with
+ * ld % 4 == 0, no sigmoid; exact fp32 has no ping-pong and no stream instantiation.
+ * inst (optional): int[TEM_MFMA_INST_N], the template arguments the launch instantiates, 0 where the family has none:
+ *   every family   TEM_MI_NS planes per staged operand (exact fp32 patch kernel: 0), TEM_MI_F16 fp16 (1) or bf16 (0) MFMAs,
+ *                  TEM_MI_T storage type of the tensors (TEM_ST_*), TEM_MI_KS slices of the input channels (1: no split-K),
+ *                  TEM_MI_EPILOGUE the summing kernel behind a split-K launch: 0 none, 1 k_splitk_epilogue, 2
+ *                  k_splitk_epilogue_stats<false> (statistics rows), 3 k_splitk_epilogue_stats<true> (TEM_BP_NORM_SUMS)
+ *   ZR, ZR_SPLITK  k_conv_zr<NS, F16, MODE, KSPLIT, WIDE, T, X32, XS, PAIR>: TEM_MI_A MODE (0 plain, 1 statistics, 2 ReLU mask,
+ *                  3 mask + norm backward), TEM_MI_B WIDE, TEM_MI_C X32, TEM_MI_D XS, TEM_MI_E PAIR, TEM_MI_F the tile-block word
+ *                  (log2 of the block extent in x | y << 4 | z << 8); KSPLIT is TEM_MFMA_ZR_SPLITK itself
+ *   PP             k_conv_pp<KD, 3, 3, 4, 8, 8, CT, CT, NS, F16>: TEM_MI_A KD, TEM_MI_B CT
+ *   PATCH          k_conv_fwd_bfsplit<key.., patch.., NR, NS, F16, PS, T>: TEM_MI_A the kernel key (7: 3x3x3, 3: 1x3x3, 0: 1x1x1),
+ *                  TEM_MI_B flat (1 x 16 x 16 patches of 2-D data instead of 4 x 8 x 8), TEM_MI_C NR, TEM_MI_D PS
+ *   PATCH_FP32     k_conv_fwd_mfma[_p]<key.., patch.., NR>: TEM_MI_A key, TEM_MI_B flat, TEM_MI_C NR, TEM_MI_D persistent (_p)
+ *   STREAM         k_conv1x1_stream<NS, F16, CT, T>: TEM_MI_A CT */
+#define TEM_MFMA_ZR 1
+#define TEM_MFMA_ZR_SPLITK 2
+#define TEM_MFMA_PP 3
+#define TEM_MFMA_STREAM 4
+#define TEM_MFMA_PATCH 5
+#define TEM_MFMA_PATCH_FP32 6
+#define TEM_MFMA_INST_N 12
+#define TEM_MI_NS 0
+#define TEM_MI_F16 1
+#define TEM_MI_T 2
+#define TEM_MI_KS 3
+#define TEM_MI_EPILOGUE 4
+#define TEM_MI_A 5
+#define TEM_MI_B 6
+#define TEM_MI_C 7
+#define TEM_MI_D 8
+#define TEM_MI_E 9
+#define TEM_MI_F 10
+
 /* dw = sum_v xhat[v+tap][ci] * g[v][co]  (xhat = x*scale+shift, zero padded)
  * db[co] = sum_v g[v][co] (optional).  ws: workspace of tem_conv3d_wgrad_ws() bytes.
  * sd_layout != 0: dw is written in the reference's state_dict order [Cout][Cin][kd][kh][kw]
@@ -401,6 +443,12 @@ int tem_conv3d_fwd_ex(const float* x, int64_t x_ld, const float* scale, const fl
                       int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act, int use_mfma,
                       const unsigned* in_amax, const float* ref_coef, float* stat_part, int64_t stat_blocks, int64_t x_cs,
                       int64_t y_cs, TemByproducts* bp, tem_stream_t stream);
+/* the dispatch query of such a launch (TEM_MFMA_* above) */
+int tem_conv3d_fwd_mfma_path(const void* x, int64_t x_ld, const void* scale, const void* shift, const void* w_packed,
+                             const void* bias, const void* y, int64_t y_ld, const void* ref, int64_t ref_ld, int64_t ws_bytes,
+                             int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act, int use_mfma,
+                             const void* in_amax, const void* ref_coef, int has_stat, int64_t x_cs, int64_t y_cs,
+                             const TemByproducts* bp, int* inst);
 /* tem_conv3d_wgrad (sd_layout = 1) / _wgrad_sums / _wgrad_gmax / _wgrad_gscaled in one entry point:
  *   norm_sums  != NULL: tem_conv3d_wgrad_sums (w and db required; gamma / beta of the norm or NULL);
  *   g_amax_out != NULL: tem_conv3d_wgrad_gmax;   g_amax_in != NULL: tem_conv3d_wgrad_gscaled (use_mfma must be 8);

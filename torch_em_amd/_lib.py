@@ -47,6 +47,10 @@ SIGNATURES = {
     # dispatch queries of the VALU family for the arguments of an actual launch (launch nothing); inst: host int[4] or None
     "tem_conv3d_fwd_valu_path": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64] + [c_int] * 12
                                  + [ctypes.POINTER(c_int)]),
+    # ... of the matrix-core family: (x, x_ld, scale, shift, w, bias, y, y_ld, ref, ref_ld, ws_bytes, N .. kw, act, use_mfma, in_amax,
+    # ref_coef, has_stat, x_cs, y_cs, TemByproducts* (host, read only), inst: host int[TEM_MFMA_INST_N] or None)
+    "tem_conv3d_fwd_mfma_path": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_i64] + [c_int] * 11
+                                 + [c_vp, c_vp, c_int, c_i64, c_i64, c_vp, ctypes.POINTER(c_int)]),
     "tem_conv3d_wgrad_path": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_i64, c_vp, c_int, c_i64] + [c_int] * 11),
     "tem_conv3d_wgrad_ws": (c_i64, [c_int] * 10),
     "tem_conv3d_wgrad": (c_int, [c_vp, c_i64, c_vp, c_vp, c_vp, c_i64, c_vp, c_vp, c_vp, c_i64] + [c_int] * 11 + [c_vp]),

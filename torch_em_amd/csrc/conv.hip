@@ -272,6 +272,9 @@ static void launch_fwd_smallcout(const TemConvCall& c, const float* x, int64_t x
 // has no ping-pong and no stream instantiation (conv_arith.h), the VALU mode has the kernels of this file and conv_small.hip.
 // ---------------------------------------------------------------------------
 enum FwdKernel { FK_VALU, FK_ZR, FK_ZR_SPLITK, FK_PP, FK_STREAM1X1, FK_PATCH, FK_PATCH_FP32, FK_REFUSED };
+static_assert(FK_ZR == TEM_MFMA_ZR && FK_ZR_SPLITK == TEM_MFMA_ZR_SPLITK && FK_PP == TEM_MFMA_PP && FK_STREAM1X1 == TEM_MFMA_STREAM &&
+                  FK_PATCH == TEM_MFMA_PATCH && FK_PATCH_FP32 == TEM_MFMA_PATCH_FP32,
+              "tem_conv3d_fwd_mfma_path() returns the plan's kernel");
 
 // what the decision depends on besides the call, the shape and the mode
 struct FwdFacts {
@@ -513,28 +516,26 @@ static int fwd_args_check(const TemConvCall& c, const void* x, int64_t x_ld, con
     return TEM_OK;
 }
 
-static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift,
-                           const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref,
-                           int64_t ref_ld, void* ws, int64_t ws_bytes, const TemConvShape& sh, int act, int use_mfma, float* stat,
-                           tem_stream_t stream) {
-    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout, kd = sh.kd, kh = sh.kh, kw = sh.kw;
+// The plan of a launch with exactly these arguments, after every check that stands between the arguments and the launch: the
+// argument checks, the plan's own refusals, and what only the z-reuse kernel honours.  Shared by conv3d_fwd_impl and the
+// dispatch query of an actual launch (tem_conv3d_fwd_mfma_path).  ws_bytes: 0 without a workspace
+static int fwd_launch_plan(const TemConvCall& c, const void* x, int64_t x_ld, const void* scale, const void* shift, const void* w_packed,
+                           const void* bias, const void* y, int64_t y_ld, const void* ref, int64_t ref_ld, int64_t ws_bytes,
+                           const TemConvShape& sh, int act, int use_mfma, bool stat, FwdPlan& p) {
     TEM_TRY(fwd_args_check(c, x, x_ld, scale, shift, w_packed, y, y_ld, ref, ref_ld, sh, act, use_mfma));
-    const int stx = c.stx, sty = c.sty;
-    hipStream_t s = (hipStream_t)stream;
     auto al16 = [](const void* ptr) { return (uintptr_t)ptr % 16 == 0; };
-
-    const uintptr_t v4 = tem_st_align4(sty);
+    const uintptr_t v4 = tem_st_align4(c.sty);
     const FwdFacts facts = {x_ld, y_ld, ref ? ref_ld : 0,
                             al16(x) && al16(w_packed) && al16(scale) && al16(shift), al16(y) && al16(ref),
                             (uintptr_t)y % v4 == 0 && (uintptr_t)ref % v4 == 0, al16(bias),
-                            scale != nullptr, act == TEM_ACT_SIGMOID, stat != nullptr, ws ? ws_bytes : 0};
-    const FwdPlan p = fwd_plan(c, sh, use_mfma, facts);
+                            scale != nullptr, act == TEM_ACT_SIGMOID, stat, ws_bytes};
+    p = fwd_plan(c, sh, use_mfma, facts);
     if (p.kernel == FK_REFUSED) {
         tem_set_error("%s", p.error);
         return TEM_EINVAL;
     }
     // what only the z-reuse kernel honours
-    TEM_REQUIRE(!(c.x_cs || c.y_cs) || (p.kernel == FK_ZR && stx && !ref && !(c.x_cs && Cin % 32) && c.x_cs % 8 == 0 && c.y_cs % 8 == 0),
+    TEM_REQUIRE(!(c.x_cs || c.y_cs) || (p.kernel == FK_ZR && c.stx && !ref && !(c.x_cs && sh.Cin % 32) && c.x_cs % 8 == 0 && c.y_cs % 8 == 0),
                 "tem_conv3d_fwd_ex: chunk strides (x_cs / y_cs) need 16-bit tensors on the z-reuse kernel (tem_conv3d_fwd_kernel() "
                 "== 3), no ref, strides %% 8 == 0");
     TEM_REQUIRE(!c.in_amax || p.kernel == FK_ZR, "tem_conv3d_fwd_gscaled: the launch did not take the z-reuse kernel (alignment of y / ref?)");
@@ -542,6 +543,18 @@ static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, c
     TEM_REQUIRE(!c.ref_coef || (ref && !stat && al16(c.ref_coef)), "tem_conv3d_fwd_refnorm: needs ref, no statistics, 16-byte aligned coefficients");
     TEM_REQUIRE(!c.in_amax || (use_mfma == TEM_ARITH_F16X3 && !bias && !scale && !stat),
                 "tem_conv3d_fwd_gscaled: fp16 two-term layout, no bias / norm / statistics");
+    return TEM_OK;
+}
+
+static int conv3d_fwd_impl(const TemConvCall& c, const float* x, int64_t x_ld, const float* scale, const float* shift,
+                           const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref,
+                           int64_t ref_ld, void* ws, int64_t ws_bytes, const TemConvShape& sh, int act, int use_mfma, float* stat,
+                           tem_stream_t stream) {
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout, kd = sh.kd, kh = sh.kh, kw = sh.kw;
+    FwdPlan p;
+    TEM_TRY(fwd_launch_plan(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws ? ws_bytes : 0, sh, act, use_mfma,
+                            stat != nullptr, p));
+    hipStream_t s = (hipStream_t)stream;
 
     if (p.kernel != FK_VALU) {
         static const char* const what[] = {"", "tem_conv3d_fwd(z-reuse)", "tem_conv3d_fwd(z-reuse split-K)", "tem_conv3d_fwd(ping-pong)",
@@ -1281,6 +1294,10 @@ extern "C" int tem_conv3d_wgrad_sums(const float* x, int64_t x_ld, const float* 
 }
 
 // ---- every variant and by-product of the forward / data-gradient convolution as explicit arguments (tem_hip.h) -----------------
+static int fwd_ex_call(TemConvCall& c, const void* x, int64_t x_ld, const void* scale, const void* shift, const void* w_packed,
+                       const void* bias, const void* y, int64_t y_ld, const void* ref, int64_t ref_ld, const TemConvShape& sh, int act,
+                       int use_mfma, const unsigned* in_amax, const float* ref_coef, bool stat_part, int64_t x_cs, int64_t y_cs,
+                       TemByproducts* bp);
 extern "C" int tem_conv3d_fwd_ex(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* w_packed,
                                  const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
                                  int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
@@ -1288,6 +1305,61 @@ extern "C" int tem_conv3d_fwd_ex(const float* x, int64_t x_ld, const float* scal
                                  int64_t stat_blocks, int64_t x_cs, int64_t y_cs, TemByproducts* bp, tem_stream_t stream) {
     TemConvCall c = conv_call(use_mfma);
     const TemConvShape sh = {N, D, H, W, Cin, Cout, kd, kh, kw};
+    TEM_TRY(fwd_ex_call(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, sh, act, use_mfma, in_amax, ref_coef,
+                        stat_part != nullptr, x_cs, y_cs, bp));
+    if (stat_part)
+        TEM_TRY(fwd_stats_check(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, sh, use_mfma, stat_part, stat_blocks));
+    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, sh, act, use_mfma, stat_part,
+                           stream);
+}
+
+// The kernel of the matrix-core family and the instantiation a tem_conv3d_fwd_ex launch with exactly these arguments takes
+// (tem_hip.h; launches nothing): the checks of tem_conv3d_fwd_ex and of conv3d_fwd_impl, the plan, and the family's own
+// selector of its template arguments (*_describe: conv_internal.h)
+extern "C" int tem_conv3d_fwd_mfma_path(const void* x, int64_t x_ld, const void* scale, const void* shift, const void* w_packed,
+                                        const void* bias, const void* y, int64_t y_ld, const void* ref, int64_t ref_ld,
+                                        int64_t ws_bytes, int N, int D, int H, int W, int Cin, int Cout, int kd, int kh, int kw, int act,
+                                        int use_mfma, const void* in_amax, const void* ref_coef, int has_stat, int64_t x_cs,
+                                        int64_t y_cs, const TemByproducts* bp, int* inst) {
+    TemFwdInst in = {};
+    auto report = [&] { for (int i = 0; inst && i < TEM_MFMA_INST_N; ++i) inst[i] = in.v[i]; };
+    report();
+    TemConvCall c = conv_call(use_mfma);
+    const TemConvShape sh = {N, D, H, W, Cin, Cout, kd, kh, kw};
+    TemByproducts asked = {};   // the request as the launch would see it: nothing delivered yet
+    if (bp) {
+        asked = *bp;
+        asked.delivered = 0;
+    }
+    if (use_mfma == TEM_ARITH_VALU ||
+        fwd_ex_call(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, sh, act, use_mfma, (const unsigned*)in_amax,
+                    (const float*)ref_coef, has_stat != 0, x_cs, y_cs, bp ? &asked : nullptr) != TEM_OK)
+        return -1;
+    FwdPlan p;
+    if (fwd_launch_plan(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws_bytes, sh, act, use_mfma, has_stat != 0, p) != TEM_OK)
+        return -1;
+    if (has_stat && !p.stat_blocks) {   // (fwd_stats_check: the caller's rows must be the launch's)
+        tem_set_error("tem_conv3d_fwd_stats: this launch writes no statistics rows");
+        return -1;
+    }
+    switch (p.kernel) {
+        case FK_ZR: tem_conv_fwd_zr_describe(c, p.zr, 0, sh, use_mfma, ref != nullptr, has_stat != 0, in); break;
+        case FK_ZR_SPLITK: tem_conv_fwd_zr_describe(c, p.zr, p.ks, sh, use_mfma, ref != nullptr, has_stat != 0, in); break;
+        case FK_PP: tem_conv_fwd_pp_describe(p.pp, sh, use_mfma, in); break;
+        case FK_STREAM1X1: tem_conv1x1_stream_describe(c, sh, use_mfma, in); break;
+        case FK_PATCH: tem_conv_fwd_bf16x3_describe(c, p.patch, p.ks, sh, use_mfma, in); break;
+        case FK_PATCH_FP32: tem_fwd_mfma_describe(p.patch, p.ks, sh, x_ld, in); break;
+        default: return -1;
+    }
+    report();
+    return (int)p.kernel;   // FwdKernel IS TEM_MFMA_*
+}
+
+// the checks of tem_conv3d_fwd_ex on its variant arguments; fills the call
+static int fwd_ex_call(TemConvCall& c, const void* x, int64_t x_ld, const void* scale, const void* shift, const void* w_packed,
+                       const void* bias, const void* y, int64_t y_ld, const void* ref, int64_t ref_ld, const TemConvShape& sh, int act,
+                       int use_mfma, const unsigned* in_amax, const float* ref_coef, bool stat_part, int64_t x_cs, int64_t y_cs,
+                       TemByproducts* bp) {
     TEM_REQUIRE(!stat_part || (!in_amax && !ref_coef && !bp), "tem_conv3d_fwd_ex: stat_part excludes in_amax / ref_coef / by-products");
     TEM_REQUIRE(!(in_amax && ref_coef), "tem_conv3d_fwd_ex: in_amax and ref_coef exclude each other");
     TEM_REQUIRE(x_cs >= 0 && y_cs >= 0 && (!(x_cs || y_cs) || (!in_amax && !ref_coef && tem_arith_one_term(use_mfma))),
@@ -1304,16 +1376,14 @@ extern "C" int tem_conv3d_fwd_ex(const float* x, int64_t x_ld, const float* scal
                     "tem_conv3d_fwd_ex: in_amax (the fp16 two-term data gradient) takes use_mfma 4 and no scale / shift / bias / act");
         c.stx = c.sty = TEM_ST_F32;   // as tem_conv3d_fwd_gscaled: an fp32-tensor mode
         c.in_amax = in_amax;
-        TEM_TRY(fwd_gscaled_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, sh));
+        TEM_TRY(fwd_gscaled_check(c, (const float*)x, x_ld, (const float*)w_packed, (const float*)y, y_ld, (const float*)ref, ref_ld, sh));
     } else if (ref_coef) {
         TEM_REQUIRE(!scale && !shift && !bias && act == TEM_ACT_NONE, "tem_conv3d_fwd_ex: ref_coef takes no scale / shift / bias / act");
         c.ref_coef = ref_coef;
-        TEM_TRY(fwd_refnorm_check(c, x, x_ld, w_packed, y, y_ld, ref, ref_ld, sh, use_mfma));
-    } else if (stat_part) {
-        TEM_TRY(fwd_stats_check(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, sh, use_mfma, stat_part, stat_blocks));
+        TEM_TRY(fwd_refnorm_check(c, (const float*)x, x_ld, (const float*)w_packed, (const float*)y, y_ld, (const float*)ref, ref_ld, sh,
+                                  use_mfma));
     }
-    return conv3d_fwd_impl(c, x, x_ld, scale, shift, w_packed, bias, y, y_ld, ref, ref_ld, ws, ws_bytes, sh, act, use_mfma, stat_part,
-                           stream);
+    return TEM_OK;
 }
 
 extern "C" int tem_conv3d_wgrad_ex(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* g,

@@ -119,12 +119,15 @@ __global__ __launch_bounds__(256) void k_conv1x1_stream(const T* __restrict__ x,
     if (amax) tem_amax_commit(amax, amx);
 }
 
+// 32-column tiles per workgroup
+static int stream_ct(int Cout) { return Cout / 32 >= 2 ? 2 : 1; }
+
 template <int NS, bool F16, typename T>
 static void stream_launch(const TemConvCall& c, const T* x, int64_t x_ld, const float* wp, const float* bias, T* y, int64_t y_ld,
                           const T* ref, int64_t ref_ld, int64_t NV, int Cin, int Cout, int act, hipStream_t s) {
     const int64_t nmt = (NV + 31) / 32;
     const int ntile = Cout / 32;
-    const int CT = ntile >= 2 ? 2 : 1;
+    const int CT = stream_ct(Cout);
     const int ngroups = (ntile + CT - 1) / CT;
     int64_t gx = (nmt + 3) / 4;
     if (gx > 8192) gx = 8192;   // grid-stride: 8 workgroups per CU keep the loads in flight
@@ -138,21 +141,37 @@ static void stream_launch(const TemConvCall& c, const T* x, int64_t x_ld, const 
                            ref, ref_ld, NV, Cin, Cout, act, nmt, amax);
 }
 
+// The instantiation a call runs on: f(NS, F16, T) -- weight planes, fp16 or bf16 MFMAs, element type of the tensors.  One
+// selector for the launch and for the dispatch query.
+template <typename F>
+static void stream_variant(int st, int mode, F&& f) {
+    const TemArith& a = tem_arith(mode);
+    if (st == TEM_ST_F16) f(TemInt<1>{}, TemBool<true>{}, tem_f16{});
+    else if (st == TEM_ST_BF16) f(TemInt<1>{}, TemBool<false>{}, tem_bf16{});
+    else if (a.planes == 3) f(TemInt<3>{}, TemBool<false>{}, float{});
+    else if (a.planes == 2) f(TemInt<2>{}, TemBool<false>{}, float{});
+    else tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) { f(TemInt<1>{}, f16, float{}); });
+}
+
 // Storage types (c.stx == c.sty): fp32, or the 16-bit type that IS the operand type of the mode (tem_storage_ok).  x: 16-byte
 // loads; y / ref: vectors of 4 elements.  At least 16384 voxels (fewer 32-voxel tiles do not hide the k-loop's load latency: the
 // split-K patch kernel wins) -- the plan (conv.hip) sends only such launches here.
 void tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, const float* wp, const float* bias, float* y, int64_t y_ld,
                         const float* ref, int64_t ref_ld, const TemConvShape& sh, int act, int mode, hipStream_t s) {
-    const int st = c.stx, Cin = sh.Cin, Cout = sh.Cout;
+    const int Cin = sh.Cin, Cout = sh.Cout;
     const int64_t NV = sh.NV();
-    auto go = [&](auto ns, auto f16, auto t) {
+    stream_variant(c.stx, mode, [&](auto ns, auto f16, auto t) {
         using T = decltype(t);
         stream_launch<ns(), f16(), T>(c, (const T*)x, x_ld, wp, bias, (T*)y, y_ld, (const T*)ref, ref_ld, NV, Cin, Cout, act, s);
-    };
-    const TemArith& a = tem_arith(mode);
-    if (st == TEM_ST_F16) go(TemInt<1>{}, TemBool<true>{}, tem_f16{});
-    else if (st == TEM_ST_BF16) go(TemInt<1>{}, TemBool<false>{}, tem_bf16{});
-    else if (a.planes == 3) go(TemInt<3>{}, TemBool<false>{}, float{});
-    else if (a.planes == 2) go(TemInt<2>{}, TemBool<false>{}, float{});
-    else tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) { go(TemInt<1>{}, f16, float{}); });
+    });
+}
+
+void tem_conv1x1_stream_describe(const TemConvCall& c, const TemConvShape& sh, int mode, TemFwdInst& inst) {
+    stream_variant(c.stx, mode, [&](auto ns, auto f16, auto t) {
+        inst[TEM_MI_NS] = ns();
+        inst[TEM_MI_F16] = f16();
+        inst[TEM_MI_T] = TemSt<decltype(t)>::id;
+    });
+    inst[TEM_MI_KS] = 1;
+    inst[TEM_MI_A] = stream_ct(sh.Cout);
 }

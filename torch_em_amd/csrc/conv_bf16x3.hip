@@ -652,6 +652,21 @@ void tem_conv_fwd_bf16x3(const TemConvCall& c, const TemPatchTiling& t, int ks, 
     }
 }
 
+void tem_conv_fwd_bf16x3_describe(const TemConvCall& c, const TemPatchTiling& t, int ks, const TemConvShape& sh, int mode, TemFwdInst& inst) {
+    fwd_variant(mode, c.stx, [&](auto v) {
+        using V = decltype(v);
+        inst[TEM_MI_NS] = V::NS;
+        inst[TEM_MI_F16] = V::F16;
+        inst[TEM_MI_T] = TemSt<typename V::T>::id;
+        inst[TEM_MI_D] = V::PS;
+    });
+    inst[TEM_MI_KS] = ks;
+    inst[TEM_MI_EPILOGUE] = ks > 1 ? TEM_SKE_PLAIN : TEM_SKE_NONE;
+    inst[TEM_MI_A] = sh.key();
+    inst[TEM_MI_B] = t.flat;
+    inst[TEM_MI_C] = t.NR;
+}
+
 // ---------------------------------------------------------------------------
 // weight gradient on the bf16 matrix cores (split-bf16, fp32 accumulate)
 //   dw[tap][ci][co] = sum_v xhat[v+tap][ci] * g[v][co]

@@ -80,11 +80,23 @@ struct PpGeom {
     int64_t nunits;
 };
 
+// The template arguments of the instantiation a planned launch runs, as tem_conv3d_fwd_mfma_path() reports them (tem_hip.h:
+// TEM_MI_*).  Every family's *_describe() below fills them through the SAME host selector its launcher instantiates from.
+struct TemFwdInst {
+    int v[TEM_MFMA_INST_N];
+    int& operator[](int i) { return v[i]; }
+};
+// the summing kernel behind a launch with split input channels (TEM_MI_EPILOGUE)
+enum TemSplitkEpilogue { TEM_SKE_NONE = 0, TEM_SKE_PLAIN = 1, TEM_SKE_STATS = 2, TEM_SKE_BWD_SUMS = 3 };
+
 // conv_mfma.hip: the exact-fp32 patch kernel with ks slices of the input channels (> 1: partial sums in ws).  Raises on x /
 // weights / scale it cannot load as 16-byte vectors
 int tem_conv_fwd_mfma(const TemPatchTiling& t, int ks, const float* x, int64_t x_ld, const float* scale, const float* shift,
                       const float* w_packed, const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, void* ws,
                       const TemConvShape& sh, int act, hipStream_t s);
+// ... does that launch run the persistent variant (k_conv_fwd_mfma_p)?  Option fwd_persistent, the tile width, 32-bit halo offsets
+bool tem_fwd_mfma_persistent(const TemPatchTiling& t, const TemConvShape& sh, int64_t x_ld);
+void tem_fwd_mfma_describe(const TemPatchTiling& t, int ks, const TemConvShape& sh, int64_t x_ld, TemFwdInst& inst);
 
 // conv_small.hip: the HBM-bound special cases of the VALU family (use_mfma 0).  As everywhere in this file: shape predicates
 // that the ONE selector (conv.hip: fwd_valu_select) calls, and launchers that execute what it selected and decide nothing.
@@ -124,11 +136,13 @@ int tem_pack_weights_bf16x3(const float* w, float* dst, int Cout, int Cin, int k
 void tem_conv_fwd_bf16x3(const TemConvCall& c, const TemPatchTiling& t, int ks, const float* x, int64_t x_ld, const float* scale,
                          const float* shift, const float* wp, const float* bias, float* y, int64_t y_ld, const float* ref,
                          int64_t ref_ld, void* ws, const TemConvShape& sh, int act, int mode, float* stat, hipStream_t s);
+void tem_conv_fwd_bf16x3_describe(const TemConvCall& c, const TemPatchTiling& t, int ks, const TemConvShape& sh, int mode, TemFwdInst& inst);
 // conv_pp.hip: ping-pong team kernel for the levels with many patches; stat: [N][nZ * nY * nX * WM][Cout][2]
 PpGeom tem_pp_geometry(const TemConvCall& c, const TemConvShape& sh, int mode);
 void tem_conv_fwd_pp(const PpGeom& g, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                      const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, const TemConvShape& sh, int act,
                      int mode, float* stat, hipStream_t s);
+void tem_conv_fwd_pp_describe(const PpGeom& g, const TemConvShape& sh, int mode, TemFwdInst& inst);
 // conv_zr.hip: z-reuse ping-pong kernel, 3x3x3 only; stat: [N][nZ * nY * nX * 4][Cout][2].  Honours c.in_amax, c.ref_coef, c.x_cs / y_cs
 ZrGeom tem_zr_geometry(const TemConvCall& c, const TemConvShape& sh, int mode);
 void tem_conv_fwd_zr(const TemConvCall& c, const ZrGeom& g, const float* x, int64_t x_ld, const float* scale, const float* shift,
@@ -141,9 +155,14 @@ int tem_zr_splitk_ks(const TemConvCall& c, const ZrGeom& g, const TemConvShape& 
 void tem_conv_fwd_zr_splitk(const TemConvCall& c, const ZrGeom& g, int ks, const float* x, int64_t x_ld, const float* scale,
                             const float* shift, const float* wp, const float* bias, float* y, int64_t y_ld, const float* ref,
                             int64_t ref_ld, void* ws, const TemConvShape& sh, int act, int mode, float* stat, hipStream_t s);
+// the instantiation of k_conv_zr of the direct launch (ks 0) or the split-K launch with ks slices, and the latter's epilogue;
+// ref / stat: the launch carries them
+void tem_conv_fwd_zr_describe(const TemConvCall& c, const ZrGeom& g, int ks, const TemConvShape& sh, int mode, bool ref, bool stat,
+                              TemFwdInst& inst);
 // conv1x1_stream.hip: 1x1x1 convolution / data gradient as a streaming GEMM: no pre-norm, no statistics, no sigmoid
 void tem_conv1x1_stream(const TemConvCall& c, const float* x, int64_t x_ld, const float* wp, const float* bias, float* y, int64_t y_ld,
                         const float* ref, int64_t ref_ld, const TemConvShape& sh, int act, int mode, hipStream_t s);
+void tem_conv1x1_stream_describe(const TemConvCall& c, const TemConvShape& sh, int mode, TemFwdInst& inst);
 // shared with conv_mfma.hip
 int tem_fwd_ksplit(int64_t nblk, int nchunks);
 void tem_splitk_epilogue(int sty, const float* part, int ksplit, int64_t NV, int Cout, const float* bias, int act,

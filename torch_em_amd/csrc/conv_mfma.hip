@@ -752,6 +752,27 @@ TemPatchTiling tem_fwd_patch_tiling(const TemConvShape& sh) {
     return t;
 }
 
+// The persistent variant (k_conv_fwd_mfma_p) of a launch with NR 32-column tiles per workgroup and halos of halo_z planes:
+// persistent pipelining pays for the 64-column tiles (measured +5%), not for the 32-column ones (option fwd_persistent: -1 that
+// rule, 0 never, else always); the persistent kernel addresses a patch's halo with 32-bit offsets from its origin
+static bool fwd_persistent(int halo_z, int NR, int H, int W, int64_t x_ld) {
+    const int pmode = (int)tem_option(TEM_OPT_FWD_PERSISTENT);
+    const bool halo32 = (int64_t)halo_z * H * W * x_ld * 4 < (1ll << 31);
+    return halo32 && (pmode < 0 ? NR == 2 : pmode != 0);
+}
+bool tem_fwd_mfma_persistent(const TemPatchTiling& t, const TemConvShape& sh, int64_t x_ld) {
+    return fwd_persistent(t.TZ + sh.kd - 1, t.NR, sh.H, sh.W, x_ld);
+}
+void tem_fwd_mfma_describe(const TemPatchTiling& t, int ks, const TemConvShape& sh, int64_t x_ld, TemFwdInst& inst) {
+    inst[TEM_MI_T] = TEM_ST_F32;
+    inst[TEM_MI_KS] = ks;
+    inst[TEM_MI_EPILOGUE] = ks > 1 ? TEM_SKE_PLAIN : TEM_SKE_NONE;
+    inst[TEM_MI_A] = sh.key();
+    inst[TEM_MI_B] = t.flat;
+    inst[TEM_MI_C] = t.NR;
+    inst[TEM_MI_D] = tem_fwd_mfma_persistent(t, sh, x_ld);
+}
+
 template <int KD, int KH, int KW, int TZ, int TY, int TX, int NR, int NW = 4>
 static void launch_fwd(const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                        const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, int N, int D, int H,
@@ -760,11 +781,7 @@ static void launch_fwd(const float* x, int64_t x_ld, const float* scale, const f
     const int nZ = (D + TZ - 1) / TZ, nY = (H + TY - 1) / TY, nX = (W + TX - 1) / TX;
     const int64_t nblk = (int64_t)N * nZ * nY * nX * (Cout / (32 * NR)) * ksplit;
     size_t ldsb = (size_t)HV * LSF * sizeof(float);
-    // persistent pipelining pays for the 64-column tiles (measured +5%), not for the 32-column ones
-    const int pmode = (int)tem_option(TEM_OPT_FWD_PERSISTENT);
-    // (the persistent kernel addresses a patch's halo with 32-bit offsets from its origin)
-    const bool halo32 = (int64_t)(TZ + KD - 1) * H * W * x_ld * 4 < (1ll << 31);
-    const bool persistent = NW == 4 && halo32 && (pmode < 0 ? NR == 2 : pmode != 0);
+    const bool persistent = NW == 4 && fwd_persistent(TZ + KD - 1, NR, H, W, x_ld);
     if constexpr (NW == 4) if (persistent) {
         const int ncu = tem_ncu();
         const int bpc = NR == 1 ? 3 : TEM_MF_OCC2;

@@ -557,18 +557,38 @@ static void pp_launch(const PpGeom& g, const float* x, int64_t x_ld, const float
                        g.nY, g.nX, stat, (int)g.nunits);
 }
 
-void tem_conv_fwd_pp(const PpGeom& g, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
-                     const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, const TemConvShape& sh, int act,
-                     int mode, float* stat, hipStream_t s) {
+// The instantiation of k_conv_pp a launch runs on: f(KD, CT, F16, NS) as compile-time values.  One selector for the launch and
+// for the dispatch query.
+template <typename F>
+static void pp_variant(const PpGeom& g, const TemConvShape& sh, int mode, F&& f) {
     const TemArith& a = tem_arith(mode);
     tem_select_bool(sh.kd == 3, [&](auto k3) {
         tem_select_bool(g.CT == 2, [&](auto ct2) {
             tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) {
                 tem_select_bool(a.planes == 1, [&](auto one) {
-                    pp_launch<k3() ? 3 : 1, 3, 3, 4, ct2() ? 2 : 1, f16(), one() ? 1 : 2>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld,
-                                                                                    sh.N, sh.D, sh.H, sh.W, sh.Cin, sh.Cout, act, stat, s);
+                    f(TemInt<k3() ? 3 : 1>{}, TemInt<ct2() ? 2 : 1>{}, f16, TemInt<one() ? 1 : 2>{});
                 });
             });
         });
     });
+}
+
+void tem_conv_fwd_pp(const PpGeom& g, const float* x, int64_t x_ld, const float* scale, const float* shift, const float* wp,
+                     const float* bias, float* y, int64_t y_ld, const float* ref, int64_t ref_ld, const TemConvShape& sh, int act,
+                     int mode, float* stat, hipStream_t s) {
+    pp_variant(g, sh, mode, [&](auto kd, auto ct, auto f16, auto ns) {
+        pp_launch<kd(), 3, 3, 4, ct(), f16(), ns()>(g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, sh.N, sh.D, sh.H, sh.W, sh.Cin,
+                                                    sh.Cout, act, stat, s);
+    });
+}
+
+void tem_conv_fwd_pp_describe(const PpGeom& g, const TemConvShape& sh, int mode, TemFwdInst& inst) {
+    pp_variant(g, sh, mode, [&](auto kd, auto ct, auto f16, auto ns) {
+        inst[TEM_MI_NS] = ns();
+        inst[TEM_MI_F16] = f16();
+        inst[TEM_MI_A] = kd();
+        inst[TEM_MI_B] = ct();
+    });
+    inst[TEM_MI_T] = TEM_ST_F32;
+    inst[TEM_MI_KS] = 1;
 }

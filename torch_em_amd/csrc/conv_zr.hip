@@ -1050,6 +1050,10 @@ static int zr_tile_blocks(const ZrGeom& g) {
     return lg(g.nX) | (lg(g.nY) << 4) | (lg(g.nZ) << 8);
 }
 
+// the variants that have a paired instantiation (k_conv_zr<.., PAIR>): two planes, 16 channels per phase, fp32 tensors, 16-bit MFMAs
+template <int NS, bool WIDE, typename T, bool X32>
+static constexpr bool zr_pairable() { return NS == 2 && !WIDE && !X32 && sizeof(T) == 4; }
+
 template <int NS, bool F16, int MODE, bool KSPLIT = false, bool WIDE = false, typename T = float, bool X32 = false, bool XS = false, bool PAIR = false>
 static void zr_launch(const TemConvCall& c, const ZrGeom& g, const float* x_, int64_t x_ld, const float* scale, const float* shift, const float* wp,
                       const float* bias, float* y_, int64_t y_ld, const float* ref_, int64_t ref_ld, const TemConvShape& sh,
@@ -1059,7 +1063,7 @@ static void zr_launch(const TemConvCall& c, const ZrGeom& g, const float* x_, in
     const T* x = reinterpret_cast<const T*>(x_);
     const T* ref = reinterpret_cast<const T*>(ref_);
     auto* y = reinterpret_cast<std::conditional_t<KSPLIT, float, T>*>(y_);
-    if constexpr (!PAIR && NS == 2 && !WIDE && !X32 && sizeof(T) == 4) {   // the plan's pairing bit: the same launch on the paired kernel
+    if constexpr (!PAIR && zr_pairable<NS, WIDE, T, X32>()) {   // the plan's pairing bit: the same launch on the paired kernel
         if (g.pair) return zr_launch<NS, F16, MODE, KSPLIT, WIDE, T, X32, XS, true>(c, g, x_, x_ld, scale, shift, wp, bias, y_, y_ld, ref_, ref_ld, sh, act, stat, in_amax, s, ks);
     }
     auto kern = &k_conv_zr<NS, F16, MODE, KSPLIT, WIDE, T, X32, XS, PAIR>;
@@ -1097,6 +1101,31 @@ static void zr_variant(const TemConvCall& c, int mode, bool wide, F&& f) {
     else if (a.planes == 1) tem_select_bool(a.elem == TEM_EL_F16, [&](auto f16) { f(ZrVariant<1, f16()>{}); });
     else tem_select_bool(a.pack == TEM_PK_F16_LO12, [&](auto f16) { f(ZrVariant<2, f16()>{}); });
 }
+// `wide` of a launch.  Direct (ks 0): 32 channels per phase whenever the channel count allows it (whole 128-byte lines per
+// staging phase).  Split-K with ks slices: slices of whole 32-channel chunks; 16-bit tensors stage no other way.
+static bool zr_wide(const TemConvCall& c, const TemConvShape& sh, int mode, int ks) {
+    if (!tem_arith_one_term(mode)) return false;
+    if (!ks) return sh.Cin % 32 == 0 && tem_option(TEM_OPT_ZR_WIDE);
+    return (sh.Cin / 16 / ks) % 2 == 0 && (tem_option(TEM_OPT_ZR_WIDE) || c.stx);
+}
+// epilogue MODE of a direct launch: 1 statistics, 3 ReLU mask of ref + norm backward from c.ref_coef, 2 ReLU mask of ref, 0 plain
+static int zr_epilogue_mode(const TemConvCall& c, bool ref, bool stat) {
+    return stat ? 1 : ref && c.ref_coef ? 3 : ref ? 2 : 0;
+}
+// the summing kernel of a split-K launch: the statistics rows when asked, the first stage of a norm backward when the call asks
+// for TEM_BP_NORM_SUMS with rows of this epilogue's geometry (rq: that request), else the plain one
+static TemSplitkEpilogue zr_splitk_epilogue(const TemConvCall& c, const TemConvShape& sh, bool stat, TemDgradSumsReq& rq) {
+    rq = TemDgradSumsReq{nullptr, 0, nullptr, nullptr, 0, nullptr, 0};
+    if (stat) return TEM_SKE_STATS;
+    if (c.wants(TEM_BP_NORM_SUMS)) {
+        const TemByproducts* bp = c.bp;
+        rq = TemDgradSumsReq{bp->sums_x, bp->sums_x_ld, bp->sums_mean, bp->sums_rstd, bp->sums_G, bp->sums_part, bp->sums_nblk};
+    }
+    if (rq.part && rq.x && rq.mean && rq.rstd && rq.nblk == tem_splitk_stat_blocks(sh.V(), sh.Cout) && rq.G > 0 && sh.Cout % rq.G == 0 &&
+        rq.x_ld % 4 == 0 && ((uintptr_t)rq.x % 16 == 0))
+        return TEM_SKE_BWD_SUMS;
+    return TEM_SKE_PLAIN;
+}
 
 // Split-K launch for shapes tem_zr_geometry() declines only because they have too few (tile, column tile) units: the input
 // channels are cut into ks slices so that ks x units >= two per CU, the partial sums go to the workspace and the common
@@ -1116,24 +1145,19 @@ int tem_zr_splitk_ks(const TemConvCall& c, const ZrGeom& g, const TemConvShape& 
 void tem_conv_fwd_zr_splitk(const TemConvCall& c, const ZrGeom& g, int ks, const float* x, int64_t x_ld, const float* scale,
                             const float* shift, const float* wp, const float* bias, float* y, int64_t y_ld, const float* ref,
                             int64_t ref_ld, void* ws, const TemConvShape& sh, int act, int mode, float* stat, hipStream_t s) {
-    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cin = sh.Cin, Cout = sh.Cout;
+    const int N = sh.N, D = sh.D, H = sh.H, W = sh.W, Cout = sh.Cout;
     const int64_t NV = sh.NV();
     float* part = (float*)ws;
-    const bool wide = tem_arith_one_term(mode) && (Cin / 16 / ks) % 2 == 0 && (tem_option(TEM_OPT_ZR_WIDE) || c.stx);   // slices of whole 32-channel chunks
-    zr_variant(c, mode, wide, [&](auto v) {
+    zr_variant(c, mode, zr_wide(c, sh, mode, ks), [&](auto v) {
         using V = decltype(v);
         zr_launch<V::NS, V::F16, 0, true, V::WIDE, typename V::T, V::X32, V::XS>(c, g, x, x_ld, scale, shift, wp, nullptr, part, Cout, nullptr, 0, sh,
                                                                              TEM_ACT_NONE, nullptr, nullptr, s, ks);
     });
-    TemDgradSumsReq rq = {nullptr, 0, nullptr, nullptr, 0, nullptr, 0};
-    if (!stat && c.wants(TEM_BP_NORM_SUMS)) {
-        const TemByproducts* bp = c.bp;
-        rq = TemDgradSumsReq{bp->sums_x, bp->sums_x_ld, bp->sums_mean, bp->sums_rstd, bp->sums_G, bp->sums_part, bp->sums_nblk};
-    }
-    if (stat)
+    TemDgradSumsReq rq;
+    const TemSplitkEpilogue e = zr_splitk_epilogue(c, sh, stat != nullptr, rq);
+    if (e == TEM_SKE_STATS)
         tem_splitk_epilogue_stats(c.sty, part, ks, N, (int64_t)D * H * W, Cout, bias, act, ref, ref_ld, y, y_ld, stat, s);
-    else if (rq.part && rq.x && rq.mean && rq.rstd && rq.nblk == tem_splitk_stat_blocks((int64_t)D * H * W, Cout) && rq.G > 0 &&
-             Cout % rq.G == 0 && rq.x_ld % 4 == 0 && ((uintptr_t)rq.x % 16 == 0)) {
+    else if (e == TEM_SKE_BWD_SUMS) {
         c.delivered(TEM_BP_NORM_SUMS);
         tem_splitk_epilogue_bwd_sums(c.sty, part, ks, N, (int64_t)D * H * W, Cout, bias, act, ref, ref_ld, y, y_ld, rq, s);
     } else
@@ -1148,18 +1172,36 @@ void tem_conv_fwd_zr(const TemConvCall& c, const ZrGeom& g, const float* x, int6
                      const TemConvShape& sh, int act, int mode, float* stat, hipStream_t s) {
     const float* rcoef = c.ref_coef;
     const unsigned* in_amax = c.in_amax;
-    // one-term modes: 32 channels per phase whenever the channel count allows it (whole 128-byte lines per staging phase)
-    const bool wide = tem_arith_one_term(mode) && sh.Cin % 32 == 0 && tem_option(TEM_OPT_ZR_WIDE);
-    zr_variant(c, mode, wide, [&](auto v) {
+    zr_variant(c, mode, zr_wide(c, sh, mode, 0), [&](auto v) {
         using V = decltype(v);
-        // epilogue MODE: 1 statistics, 3 ReLU mask of ref + norm backward from rcoef (in the `stat` slot), 2 ReLU mask of ref, 0 plain
+        // (MODE 3 takes its coefficients in the `stat` slot)
         auto go = [&](auto m, float* st) {
             zr_launch<V::NS, V::F16, m(), false, V::WIDE, typename V::T, V::X32, V::XS>(c, g, x, x_ld, scale, shift, wp, bias, y, y_ld, ref, ref_ld, sh,
                                                                                 act, st, in_amax, s);
         };
-        if (stat) go(TemInt<1>{}, stat);
-        else if (ref && rcoef) go(TemInt<3>{}, const_cast<float*>(rcoef));
-        else if (ref) go(TemInt<2>{}, stat);
+        const int m = zr_epilogue_mode(c, ref != nullptr, stat != nullptr);
+        if (m == 1) go(TemInt<1>{}, stat);
+        else if (m == 3) go(TemInt<3>{}, const_cast<float*>(rcoef));
+        else if (m == 2) go(TemInt<2>{}, stat);
         else go(TemInt<0>{}, stat);
     });
+}
+
+void tem_conv_fwd_zr_describe(const TemConvCall& c, const ZrGeom& g, int ks, const TemConvShape& sh, int mode, bool ref, bool stat,
+                              TemFwdInst& inst) {
+    zr_variant(c, mode, zr_wide(c, sh, mode, ks), [&](auto v) {
+        using V = decltype(v);
+        inst[TEM_MI_NS] = V::NS;
+        inst[TEM_MI_F16] = V::F16;
+        inst[TEM_MI_T] = TemSt<typename V::T>::id;
+        inst[TEM_MI_B] = V::WIDE;
+        inst[TEM_MI_C] = V::X32;
+        inst[TEM_MI_D] = V::XS;
+        inst[TEM_MI_E] = g.pair && zr_pairable<V::NS, V::WIDE, typename V::T, V::X32>();
+    });
+    inst[TEM_MI_KS] = ks ? ks : 1;
+    TemDgradSumsReq rq;
+    inst[TEM_MI_EPILOGUE] = ks ? zr_splitk_epilogue(c, sh, stat, rq) : TEM_SKE_NONE;
+    inst[TEM_MI_A] = ks ? 0 : zr_epilogue_mode(c, ref, stat);   // (a split-K launch writes plain partial sums)
+    inst[TEM_MI_F] = zr_tile_blocks(g);
 }
