@@ -1177,6 +1177,38 @@ int tem_mws_run(const float* aff, const int* offsets, int n_attractive, int N, i
                 int64_t ws_bytes, uint64_t* table, int64_t slots, int first, int rounds, tem_stream_t stream);
 int tem_mws_labels(int* out, int N, int C, int D, int H, int W, void* ws, int64_t ws_bytes, tem_stream_t stream);
 
+/* ---- peak maxima (csrc/peaks.hip; the definition: DESIGN.md "Peak maxima") ------------------------------------------------
+ * peak_local_max of a float32 batch [N][D][H][W] (2-D: D == 1), V = D*H*W < 2^31 - 1, N <= 65535, min_distance d within
+ * 1..TEM_PEAKS_MAX_DISTANCE.  One stream throughout; ws: tem_peaks_ws bytes, 16-byte aligned, kept from call to call.
+ *   tem_peaks_candidates  per-sample minimum and maximum, the box maximum of half-width d (clamped to the sample) and the
+ *                  peak test: image == its box maximum, the sample not constant, image > threshold (threshold_abs if
+ *                  has_abs, else the sample's minimum; raised to threshold_rel * the maximum if has_rel, a float32 product),
+ *                  at least `border` voxels from both ends of every axis longer than 1.  Writes the state volume into ws.
+ *   tem_peaks_rounds  enqueues `rounds` (1..TEM_PEAKS_MAX_BATCH) rounds of the minimum-spacing pass; first != 0 on the call
+ *                  after tem_peaks_candidates.  A round returns at once when the one before it left nothing undecided.  When
+ *                  the batch has run, ws starts with int32: [0] the rounds that ran so far, [1] non-zero when candidates
+ *                  are still undecided (then another batch is due), [2] the candidates of the batch, [3] unused, [4 + n]
+ *                  the kept peaks of sample n (valid once [1] is 0); counts: int32 [N][tem_peaks_chunks(V)], the kept
+ *                  peaks per chunk of consecutive voxels (written once [1] is 0).
+ *   tem_peaks_compact  base: int64 [N][chunks], the exclusive prefix sum of counts over the flat array.  Writes the kept
+ *                  peaks in raster order, sample after sample: idx (sample-local linear index), height, sample -- arrays of
+ *                  the sum of the kept peaks.
+ *   tem_peaks_seeds  out: int32 [N][V] = 0, then out[sample[i]][idx[i]] = i - start[sample[i]] + 1 for the T peaks of a flat
+ *                  list in output order (start: int64 [N], where each sample begins), of every sample the first `limit`
+ *                  (<= 0: all). */
+#define TEM_PEAKS_MAX_DISTANCE 31
+#define TEM_PEAKS_MAX_BATCH 64
+int64_t tem_peaks_ws(int N, int D, int H, int W);
+int64_t tem_peaks_chunks(int64_t V);
+int tem_peaks_candidates(const float* image, int N, int D, int H, int W, int min_distance, int has_abs, float threshold_abs,
+                         int has_rel, float threshold_rel, int border, void* ws, int64_t ws_bytes, tem_stream_t stream);
+int tem_peaks_rounds(int N, int D, int H, int W, int min_distance, void* ws, int64_t ws_bytes, int* counts, int first, int rounds,
+                     tem_stream_t stream);
+int tem_peaks_compact(const float* image, const int64_t* base, int* idx, float* height, int* sample, int N, int D, int H, int W,
+                      void* ws, int64_t ws_bytes, tem_stream_t stream);
+int tem_peaks_seeds(const int* idx, const int* sample, const int64_t* start, int64_t T, int limit, int* out, int N, int64_t V,
+                    tem_stream_t stream);
+
 /* ---- label overlaps and instance-segmentation scores (csrc/overlap.hip; the definitions: DESIGN.md "Instance
  * segmentation scores") ------------------------------------------------------------------------------------------------
  * The contingency table of two label batches [N][V], V < 2^31 - 1 and N * V < 2^31 - 1, N <= 65535, whose ids a (first

@@ -251,6 +251,15 @@ SIGNATURES = {
     "tem_mws_init": (c_int, [c_vp, c_vp, c_vp, c_int] + [c_int] * 5 + [c_vp, c_i64, c_vp]),
     "tem_mws_run": (c_int, [c_vp, c_vp, c_int] + [c_int] * 5 + [c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp]),
     "tem_mws_labels": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_i64, c_vp]),
+    # peak maxima (csrc/peaks.hip): (image, N, D, H, W, min_distance, has_abs, thr_abs, has_rel, thr_rel, border, ws, ws_bytes,
+    # stream) / (N, D, H, W, min_distance, ws, ws_bytes, counts, first, rounds, stream) /
+    # (image, base, idx, height, sample, N, D, H, W, ws, ws_bytes, stream) / (idx, sample, start, T, limit, out, N, V, stream)
+    "tem_peaks_ws": (c_i64, [c_int] * 4),
+    "tem_peaks_chunks": (c_i64, [c_i64]),
+    "tem_peaks_candidates": (c_int, [c_vp] + [c_int] * 6 + [c_float, c_int, c_float, c_int, c_vp, c_i64, c_vp]),
+    "tem_peaks_rounds": (c_int, [c_int] * 5 + [c_vp, c_i64, c_vp, c_int, c_int, c_vp]),
+    "tem_peaks_compact": (c_int, [c_vp] * 5 + [c_int] * 4 + [c_vp, c_i64, c_vp]),
+    "tem_peaks_seeds": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_i64, c_vp]),
     # label overlaps and instance-segmentation scores (csrc/overlap.hip): (sorted, flag, N, V, stream) /
     # (sorted, rank, pa, pb, n_ab, npairs, n_a, n_b, N, V, ws, ws_bytes, stream) /
     # (pa, pb, n_ab, npairs, n_a, n_b, threshold, rec, best_a, best_b, N, V, ws, ws_bytes, stream)

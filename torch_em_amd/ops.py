@@ -2164,6 +2164,136 @@ def mutex_watershed(aff: torch.Tensor, offsets, n_attractive: int, mask: Optiona
     return (ids, work) if return_rounds else ids
 
 
+# ---- peak maxima (csrc/peaks.hip) ----
+PEAKS_MAX_DISTANCE = 31        # TEM_PEAKS_MAX_DISTANCE
+PEAKS_MAX_BATCH = 64           # TEM_PEAKS_MAX_BATCH
+PEAKS_ROUNDS_PER_BATCH = 8     # the default: profiles/peaks_bench.txt
+
+
+def _int_arg(value, lo, hi, what):
+    if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= value <= hi:
+        raise ValueError(f"peak_local_max: {what} must be an integer within {lo}..{hi}, got {value!r}")
+    return int(value)
+
+
+def _peak_args(image, min_distance, threshold_abs, threshold_rel, exclude_border, num_peaks, rounds_per_batch, extra):
+    """the host-side checks of `peak_local_max` / `peak_markers` -> (d, has_abs, thr_abs, has_rel, thr_rel, border, limit);
+    the thresholds as the float32 the comparison uses"""
+    if extra:
+        raise TypeError(f"peak_local_max: {sorted(extra)} not offered (no footprint, no labels, p_norm is 2)")
+    if not torch.is_tensor(image) or image.dim() != 4 or image.dtype != torch.float32 or image.numel() == 0:
+        raise ValueError("peak_local_max: expected a non-empty float32 image [N, D, H, W], got "
+                         f"{getattr(image, 'dtype', type(image))} {tuple(getattr(image, 'shape', ()))}")
+    N = int(image.shape[0])
+    V = image.numel() // N
+    if V >= 2 ** 31 - 1 or N > 65535:
+        raise ValueError(f"peak_local_max: {N} samples of {V} voxels; V below 2^31 - 1 and N at most 65535 supported")
+    d = _int_arg(min_distance, 1, PEAKS_MAX_DISTANCE, "min_distance")
+    if exclude_border is True or exclude_border is False:
+        border = d if exclude_border else 0
+    else:
+        border = _int_arg(exclude_border, 0, 2 ** 31 - 1, "exclude_border (or a bool)")
+    limit = 0 if num_peaks is None else _int_arg(num_peaks, 1, 2 ** 31 - 1, "num_peaks (or None)")
+    _int_arg(rounds_per_batch, 1, PEAKS_MAX_BATCH, "rounds_per_batch")
+    thr = []
+    for name, v in (("threshold_abs", threshold_abs), ("threshold_rel", threshold_rel)):
+        if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Real) or math.isnan(v)):
+            raise ValueError(f"peak_local_max: {name} must be a number or None, got {v!r}")
+        thr += [int(v is not None), 0.0 if v is None else float(torch.tensor(float(v), dtype=torch.float32))]
+    return (d, *thr, border, limit)
+
+
+def _peaks_kept(image, args, rounds_per_batch):
+    """the filter, the peak test, the spacing rounds and the compaction -> (idx, height, sample: the kept peaks in raster
+    order, sample after sample; counts: the kept peaks per sample, a host list; working rounds)"""
+    d, has_abs, thr_abs, has_rel, thr_rel, border, _ = args
+    _req_cuda(image)
+    image = image.contiguous()
+    N, D, H, W = (int(s) for s in image.shape)
+    V = D * H * W
+    dev = image.device
+    lib = _lib.load()
+    nbytes = int(lib.tem_peaks_ws(N, D, H, W))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
+    counts = torch.empty((N * int(lib.tem_peaks_chunks(V)),), dtype=torch.int32, device=dev)
+    _lib.check(lib.tem_peaks_candidates(_p(image), N, D, H, W, d, has_abs, thr_abs, has_rel, thr_rel, border, _p(ws), nbytes,
+                                        _stream(image)), "tem_peaks_candidates")
+    first = 1
+    while True:
+        _lib.check(lib.tem_peaks_rounds(N, D, H, W, d, _p(ws), nbytes, _p(counts), first, int(rounds_per_batch), _stream(image)),
+                   "tem_peaks_rounds")
+        head = ws[:16 + 4 * N].view(torch.int32).tolist()
+        work, alive, cand = head[:3]
+        first = 0
+        if work > cand + 1:
+            raise RuntimeError(f"peak_local_max: {work} working rounds for {cand} candidates: every working round decides one")
+        if not alive:
+            break
+    kept = head[4:4 + N]
+    T = sum(kept)
+    idx = torch.empty((T,), dtype=torch.int32, device=dev)
+    height = torch.empty((T,), dtype=torch.float32, device=dev)
+    sample = torch.empty((T,), dtype=torch.int32, device=dev)
+    if T:
+        base = torch.cumsum(counts, dim=0, dtype=torch.int64) - counts
+        _lib.check(lib.tem_peaks_compact(_p(image), _p(base), _p(idx), _p(height), _p(sample), N, D, H, W, _p(ws), nbytes,
+                                         _stream(image)), "tem_peaks_compact")
+    return idx, height, sample, kept, work
+
+
+def _peaks_ordered(idx, height, sample):
+    """the flat raster-order list -> by sample, then height descending, then raster order: two stable sorts of a list of
+    peaks.  -h + 0.0 turns -0.0 into 0.0, so that a sort that compares bit patterns ties the two as well."""
+    by_height = torch.sort(-height + 0.0, stable=True).indices
+    order = by_height[torch.sort(sample[by_height], stable=True).indices]
+    return idx[order], sample[order]
+
+
+def peak_local_max(image: torch.Tensor, min_distance: int = 1, threshold_abs=None, threshold_rel=None, exclude_border=True,
+                   num_peaks=None, rounds_per_batch: int = PEAKS_ROUNDS_PER_BATCH, return_rounds: bool = False, **not_offered):
+    """`skimage.feature.peak_local_max` (scikit-image >= 0.19) of a float32 batch [N, D, H, W] (2-D: D = 1) -> a list of N
+    device tensors, int32 [n_i, 3]: the (z, y, x) of the peaks of sample i, highest first, equal heights in raster order
+    (tem_peaks_*; the definition: DESIGN.md "Peak maxima").  A voxel is a candidate when it equals the maximum over the box
+    of half-width `min_distance` (1..31) clamped to the sample, the sample is not constant, it is above the threshold
+    (`threshold_abs`, default the sample's minimum; raised to `threshold_rel` * the sample's maximum when that is given;
+    both compared as float32) and it is at least `exclude_border` (True: min_distance, False: 0, or an int) voxels from
+    both ends of every axis longer than 1.  Candidates are taken in the order above and one is kept unless an earlier
+    kept one lies at dz^2 + dy^2 + dx^2 < min_distance^2; `num_peaks` cuts the result.  The result is the sequential
+    algorithm's, bit for bit.  `footprint`, `labels` and `p_norm` are not offered.  NaNs are not rejected and where they
+    land is not promised.
+    The spacing pass runs rounds whose number depends on the data (plateaus only): they are enqueued `rounds_per_batch`
+    (1..64) at a time and 4 + N ints are read back after each batch -- the round counters and the peaks per sample.
+    `return_rounds`: also the number of rounds that ran."""
+    args = _peak_args(image, min_distance, threshold_abs, threshold_rel, exclude_border, num_peaks, rounds_per_batch, not_offered)
+    idx, height, sample, kept, work = _peaks_kept(image, args, rounds_per_batch)
+    H, W = int(image.shape[2]), int(image.shape[3])
+    idx, _ = _peaks_ordered(idx, height, sample)
+    zyx = torch.stack([idx // (H * W), (idx // W) % H, idx % W], dim=1).to(torch.int32)
+    limit = args[-1]
+    out, at = [], 0
+    for n in kept:
+        out.append(zyx[at:at + (min(n, limit) if limit else n)])
+        at += n
+    return (out, work) if return_rounds else out
+
+
+def peak_markers(image: torch.Tensor, min_distance: int = 1, threshold_abs=None, threshold_rel=None, exclude_border=True,
+                 num_peaks=None, rounds_per_batch: int = PEAKS_ROUNDS_PER_BATCH, **not_offered) -> torch.Tensor:
+    """The peaks of `peak_local_max` (the same arguments) as an int32 marker volume [N, D, H, W]: peak k of a sample's list
+    carries k + 1, everything else 0 (tem_peaks_seeds) -- seeds for `seeded_watershed`.  Nothing but the counters of the
+    spacing rounds is read back."""
+    args = _peak_args(image, min_distance, threshold_abs, threshold_rel, exclude_border, num_peaks, rounds_per_batch, not_offered)
+    idx, height, sample, kept, _ = _peaks_kept(image, args, rounds_per_batch)
+    N = int(image.shape[0])
+    V = image.numel() // N
+    idx, sample = _peaks_ordered(idx, height, sample)
+    start = _to_device(torch.tensor([0] + kept[:-1], dtype=torch.int64).cumsum(0).numpy(), image.device)
+    out = torch.empty(tuple(image.shape), dtype=torch.int32, device=image.device)
+    _lib.check(_lib.load().tem_peaks_seeds(_p(idx), _p(sample), _p(start), int(idx.numel()), args[-1], _p(out), N, V, _stream(image)),
+               "tem_peaks_seeds")
+    return out
+
+
 # ---- label overlaps and instance-segmentation scores (csrc/overlap.hip) ----
 _OV_LABELS = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
 

@@ -15,7 +15,8 @@ this was written), nor is the numbering of `bioimage_cpp.segmentation.label`: se
 The mutex watershed, `mutex_watershed_segmentation`, lives in `torch_em_amd.util.mutex_watershed` and is exported by
 `torch_em_amd.util`: a test of this module pins that it does not carry that name.
 
-Not provided: `watershed_from_maxima` (needs `peak_local_max` with greedy spacing)."""
+`watershed_from_maxima` (seeds from `ops.peak_markers`, the device's `peak_local_max`) lives in
+`torch_em_amd.util.peak_watershed` and is exported by `torch_em_amd.util` in the same way."""
 from typing import Optional
 
 import numpy as np
