@@ -1209,6 +1209,39 @@ int tem_peaks_compact(const float* image, const int64_t* base, int* idx, float* 
 int tem_peaks_seeds(const int* idx, const int* sample, const int64_t* start, int64_t T, int limit, int* out, int N, int64_t V,
                     tem_stream_t stream);
 
+/* ---- the Gaussian 2-jet feature bank (csrc/filters.hip; the definitions: DESIGN.md "Shallow2Deep front end") ----------------
+ * One scale of the bank of a float32 batch x [N][D][H][W] (2-D: D == 1), D*H*W < 2^31 - 1.  J_o = scipy.ndimage.
+ * gaussian_filter(x, sigma, order = o, mode = "mirror", truncate = 4); radius int(4 sigma + 0.5) <= TEM_FILTERS_MAX_RADIUS per axis
+ * (a 2-D sample: z radius 0); a radius may exceed its axis.
+ *   weights        DEVICE float32 [3 axes z, y, x][3 orders][TEM_FILTERS_MAX_TAPS]: the taps of the correlation
+ *                  out[i] = sum_t w[t] * in[i - r + t], t <= 2 r (scipy's kernel reversed); the rest is not read
+ *   radii          HOST int[3], z, y, x
+ *   outer_*        the same for the structure tensor's second smoothing (order 0 only is read); may be NULL when ch_st < 0
+ *   bank           [N][F][D][H][W]; ch_*: the channel a filter is written to, -1: not asked for.  ch_smooth J_0; ch_log
+ *                  sum_a J_2a; ch_ggm sqrt(sum_a J_a^2); ch_hess .. + ndim - 1: the eigenvalues of [J_ab], descending; ch_st ..
+ *                  + ndim - 1: the eigenvalues of [gaussian_filter(J_a J_b, outer_sigma)], descending
+ *   ws             tem_filters_ws bytes, 16-byte aligned
+ * tem_filters_fused: 1 when the x and y passes of these radii run fused over one LDS tile, 0 when they run apart (-1: radius
+ * beyond the cap); jet != 0: the first chain (three orders an axis), else the tensor's (order 0). */
+#define TEM_FILTERS_MAX_RADIUS 40
+#define TEM_FILTERS_MAX_TAPS 81
+int64_t tem_filters_ws(int N, int D, int H, int W);
+int tem_filters_fused(int ry, int rx, int jet);
+int tem_filters_scale(const float* x, int N, int D, int H, int W, const float* weights, const int* radii, const float* outer_weights,
+                      const int* outer_radii, float* bank, int F, int ch_smooth, int ch_log, int ch_ggm, int ch_hess, int ch_st,
+                      void* ws, int64_t ws_bytes, tem_stream_t stream);
+
+/* ---- random-forest predict_proba (csrc/forest.hip) ---------------------------------------------------------------------------
+ * bank: float32 [N][F][V], F <= TEM_FOREST_MAX_FEATURES; nodes: DEVICE int32 [nodes][4] = (feature, or -1 for a leaf; the bits
+ * of the float32 threshold; left child, or for a leaf its row of `leaves`; right child), 16-byte aligned; leaves: DEVICE float64
+ * [rows][C], C <= TEM_FOREST_MAX_CLASSES; roots: DEVICE int32 [T].  A voxel goes left when feature <= threshold in float32.
+ * out: float32 [N][n_sel][V], out[n][j] = float32(sum over trees, in order, of leaves[leaf][sel[j]] / T); sel: HOST int[n_sel].
+ * The tables are trusted: children and rows inside their arrays, features below F (ops.pack_forest checks them). */
+#define TEM_FOREST_MAX_FEATURES 64
+#define TEM_FOREST_MAX_CLASSES 8
+int tem_forest_predict(const float* bank, int N, int F, int64_t V, const int* nodes, const double* leaves, const int* roots, int T,
+                       int C, const int* sel, int n_sel, float* out, tem_stream_t stream);
+
 /* ---- label overlaps and instance-segmentation scores (csrc/overlap.hip; the definitions: DESIGN.md "Instance
  * segmentation scores") ------------------------------------------------------------------------------------------------
  * The contingency table of two label batches [N][V], V < 2^31 - 1 and N * V < 2^31 - 1, N <= 65535, whose ids a (first

@@ -260,6 +260,14 @@ SIGNATURES = {
     "tem_peaks_rounds": (c_int, [c_int] * 5 + [c_vp, c_i64, c_vp, c_int, c_int, c_vp]),
     "tem_peaks_compact": (c_int, [c_vp] * 5 + [c_int] * 4 + [c_vp, c_i64, c_vp]),
     "tem_peaks_seeds": (c_int, [c_vp, c_vp, c_vp, c_i64, c_int, c_vp, c_int, c_i64, c_vp]),
+    # the Gaussian 2-jet feature bank (csrc/filters.hip): (x, N, D, H, W, weights, radii (host), outer_weights, outer_radii (host),
+    # bank, F, ch_smooth, ch_log, ch_ggm, ch_hess, ch_st, ws, ws_bytes, stream)
+    "tem_filters_ws": (c_i64, [c_int] * 4),
+    "tem_filters_fused": (c_int, [c_int] * 3),
+    "tem_filters_scale": (c_int, [c_vp] + [c_int] * 4 + [c_vp, ctypes.POINTER(c_int), c_vp, ctypes.POINTER(c_int), c_vp] + [c_int] * 6
+                          + [c_vp, c_i64, c_vp]),
+    # random-forest predict_proba (csrc/forest.hip): (bank, N, F, V, nodes, leaves, roots, T, C, sel (host), n_sel, out, stream)
+    "tem_forest_predict": (c_int, [c_vp, c_int, c_int, c_i64, c_vp, c_vp, c_vp, c_int, c_int, ctypes.POINTER(c_int), c_int, c_vp, c_vp]),
     # label overlaps and instance-segmentation scores (csrc/overlap.hip): (sorted, flag, N, V, stream) /
     # (sorted, rank, pa, pb, n_ab, npairs, n_a, n_b, N, V, ws, ws_bytes, stream) /
     # (pa, pb, n_ab, npairs, n_a, n_b, threshold, rec, best_a, best_b, N, V, ws, ws_bytes, stream)

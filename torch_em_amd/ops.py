@@ -2294,6 +2294,229 @@ def peak_markers(image: torch.Tensor, min_distance: int = 1, threshold_abs=None,
     return out
 
 
+# ---- the Gaussian 2-jet feature bank (csrc/filters.hip; DESIGN.md "Shallow2Deep front end") ----
+FILTERS_MAX_RADIUS = 40
+_FLT_TAPS = 2 * FILTERS_MAX_RADIUS + 1
+FILTER_NAMES = ("gaussian_smoothing", "laplacian_of_gaussian", "gaussian_gradient_magnitude", "hessian_of_gaussian_eigenvalues",
+                "structure_tensor_eigenvalues")
+_FLT_SLOT = dict(zip(FILTER_NAMES, range(5)))
+
+
+def _flt_input(x, what):
+    if not torch.is_tensor(x) or x.dim() != 4 or x.dtype != torch.float32 or x.numel() == 0:
+        raise ValueError(f"{what}: expected a non-empty float32 tensor [N, D, H, W] (2-D: D = 1), got "
+                         f"{getattr(x, 'dtype', type(x))} {tuple(getattr(x, 'shape', ()))}")
+    N, D, H, W = (int(s) for s in x.shape)
+    if D > 1 and (H == 1 or W == 1):
+        raise ValueError(f"{what}: an axis of size 1 is only the dropped z axis of a 2-D sample, got {tuple(x.shape)}")
+    return x.contiguous(), (N, D, H, W), 3 if D > 1 else 2
+
+
+def _flt_sigma(sigma, ndim, what):
+    """a float or a per-axis tuple of ndim floats -> (sz, sy, sx), sz = None for a 2-D sample; the radius cap is checked"""
+    sig = tuple(float(s) for s in sigma) if isinstance(sigma, (tuple, list)) else (float(sigma),) * ndim
+    if len(sig) != ndim or not all(s > 0 and math.isfinite(s) for s in sig):
+        raise ValueError(f"{what}: sigma must be a positive number or {ndim} of them, got {sigma!r}")
+    for s in sig:
+        if int(4.0 * s + 0.5) > FILTERS_MAX_RADIUS:
+            raise ValueError(f"{what}: sigma {s} has radius {int(4.0 * s + 0.5)}, beyond the {FILTERS_MAX_RADIUS} supported")
+    return ((None,) + sig) if ndim == 2 else sig
+
+
+def _flt_weights(sig3, device):
+    """-> (device float32 [3, 3, 81]: per axis z, y, x and order the correlation taps, host int[3] radii)"""
+    from .transform.defect import gaussian_jet_weights
+    host = torch.zeros((3, 3, _FLT_TAPS), dtype=torch.float32)
+    radii = []
+    for a, s in enumerate(sig3):
+        if s is None:
+            host[a, 0, 0] = 1.0
+            radii.append(0)
+            continue
+        k = gaussian_jet_weights(s, truncate=4.0)[:, ::-1].astype("float32")
+        host[a, :, :k.shape[1]] = torch.from_numpy(k.copy())
+        radii.append(k.shape[1] // 2)
+    return _to_device(host.numpy(), device), (ctypes.c_int * 3)(*radii)
+
+
+def _flt_scale(x, dims, sig3, outer3, bank, ch):
+    """one scale: ch = [smooth, log, ggm, hess, st] channel indices of bank, -1 where not asked for"""
+    N, D, H, W = dims
+    lib = _lib.load()
+    w, r = _flt_weights(sig3, x.device)
+    ow, orr = _flt_weights(outer3, x.device) if ch[4] >= 0 else (None, None)
+    nbytes = int(lib.tem_filters_ws(N, D, H, W))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
+    _lib.check(lib.tem_filters_scale(_p(x), N, D, H, W, _p(w), r, _p(ow), orr, _p(bank), int(bank.shape[1]), *ch, _p(ws), nbytes,
+                                     _stream(x)), "tem_filters_scale")
+
+
+def _flt_entry(entry, ndim):
+    """(filter, sigma) of a filter list -> (slot, sigma, outer_sigma); the filter is a name of FILTER_NAMES, one of the filter
+    functions of this module or of `shallow2deep.filters`, or a functools.partial of one that binds outer_sigma"""
+    filt, sigma = entry
+    kw = getattr(filt, "keywords", None) or {}
+    name = filt if isinstance(filt, str) else getattr(getattr(filt, "func", filt), "tem_filter", None)
+    if name not in _FLT_SLOT or set(kw) - {"outer_sigma"}:
+        raise ValueError(f"feature_bank: {filt!r} is not a filter of the bank ({', '.join(FILTER_NAMES)})")
+    sig3 = _flt_sigma(sigma, ndim, name)
+    outer3 = None
+    if name == "structure_tensor_eigenvalues":
+        outer = kw.get("outer_sigma")
+        if outer is None:   # the string form of the reference: twice the inner scale
+            outer = tuple(2 * s for s in sigma) if isinstance(sigma, (tuple, list)) else 2 * sigma
+        outer3 = _flt_sigma(outer, ndim, name + " (outer_sigma)")
+    return _FLT_SLOT[name], sig3, outer3
+
+
+def feature_bank(x: torch.Tensor, filters_and_sigmas, out: Optional[torch.Tensor] = None) -> torch.Tensor:
+    """The filter responses of a float32 batch [N, D, H, W] (2-D: D = 1) as one feature-planar bank [N, F, D, H, W], in the
+    order of the list: one channel a scalar filter, ndim an eigenvalue filter (descending).  `filters_and_sigmas`: (filter,
+    sigma) pairs as `shallow2deep._get_filters` returns them.  Entries of one sigma share ONE computation of the 2-jet
+    (tem_filters_scale): the bank is bit for bit what the single-filter calls give."""
+    x, dims, ndim = _flt_input(x, "feature_bank")
+    entries = [_flt_entry(e, ndim) for e in filters_and_sigmas]
+    if not entries:
+        raise ValueError("feature_bank: an empty filter list")
+    _req_cuda(x)
+    groups, at = [], 0    # [sig3, outer3, channels]
+    for slot, sig3, outer3 in entries:
+        grp = next((g for g in groups if g[0] == sig3 and g[2][slot] < 0 and (slot != 4 or g[1] is None)), None)
+        if grp is None:
+            grp = [sig3, None, [-1] * 5]
+            groups.append(grp)
+        grp[2][slot] = at
+        if slot == 4:
+            grp[1] = outer3
+        at += ndim if slot >= 3 else 1
+    N, D, H, W = dims
+    if out is None:
+        out = torch.empty((N, at, D, H, W), dtype=torch.float32, device=x.device)
+    elif tuple(out.shape) != (N, at, D, H, W) or out.dtype != torch.float32 or not out.is_contiguous() or out.device != x.device:
+        raise ValueError(f"feature_bank: out must be a contiguous float32 {(N, at, D, H, W)} on the input's device")
+    for sig3, outer3, ch in groups:
+        _flt_scale(x, dims, sig3, outer3, out, ch)
+    return out
+
+
+def _single_filter(name):
+    def filt(x: torch.Tensor, sigma, **kw) -> torch.Tensor:
+        import functools
+        if set(kw) - ({"outer_sigma"} if name == "structure_tensor_eigenvalues" else set()):
+            raise TypeError(f"{name}: unexpected arguments {sorted(kw)}")
+        return feature_bank(x, [(functools.partial(filt, **kw) if kw else filt, sigma)])
+    filt.tem_filter = name
+    filt.__name__ = filt.__qualname__ = name
+    filt.__doc__ = (f"`{name}` of a float32 batch [N, D, H, W] (2-D: D = 1) -> [N, F, D, H, W], F = 1 or, for the eigenvalue "
+                    "filters, ndim (descending); sigma: a float or one per axis (DESIGN.md \"Shallow2Deep front end\").")
+    return filt
+
+
+gaussian_smoothing, laplacian_of_gaussian, gaussian_gradient_magnitude, hessian_of_gaussian_eigenvalues, \
+    structure_tensor_eigenvalues = (_single_filter(n) for n in FILTER_NAMES)
+
+
+# ---- random-forest predict_proba (csrc/forest.hip) ----
+FOREST_MAX_FEATURES, FOREST_MAX_CLASSES = 64, 8
+
+
+class Forest:
+    """A packed forest (pack_forest): host numpy tables and, per device, their copies."""
+
+    def __init__(self, nodes, leaves, roots, n_features, n_classes):
+        self.nodes, self.leaves, self.roots = nodes, leaves, roots       # int32 [nodes, 4], float64 [rows, C], int32 [T]
+        self.n_features, self.n_classes, self.n_trees = n_features, n_classes, len(roots)
+        self._dev = {}
+
+    def on(self, device):
+        key = str(device)
+        if key not in self._dev:
+            self._dev[key] = tuple(_to_device(a, device) for a in (self.nodes, self.leaves, self.roots))
+        return self._dev[key]
+
+
+def float32_floor(t):
+    """float64 thresholds -> the largest float32 <= each: `feature <= t` in float64 and `feature <= float32_floor(t)` in
+    float32 are the same decision for every float32 feature"""
+    import numpy as np
+    t = np.asarray(t, np.float64)
+    f = t.astype(np.float32)
+    return np.where(f.astype(np.float64) > t, np.nextafter(f, np.float32(-np.inf)), f).astype(np.float32)
+
+
+def pack_forest(rf) -> Forest:
+    """A fitted `sklearn.ensemble.RandomForestClassifier` -- or any object whose `estimators_[i].tree_` has children_left,
+    children_right, feature, threshold and value -- as the flat tables of tem_forest_predict.  Per node (feature or -1, the
+    float32 threshold's bits, left, right); a leaf's third word is its row of the float64 leaf table, the class fractions:
+    value / value.sum() for a row of counts (sklearn < 1.4 and hand-made forests), the row as stored when it already sums
+    to 1 within 1e-9 (sklearn >= 1.4 stores fractions and predict_proba does not divide again).  Thresholds become the largest float32 <= sklearn's float64 (`float32_floor`): sklearn compares a
+    float32 feature with the float64 threshold, so every decision is sklearn's.  Non-finite features are outside the
+    contract.  At most 64 features and 8 classes."""
+    import numpy as np
+    nodes, leaves, roots = [], [], []
+    n_feat = getattr(rf, "n_features_in_", None)
+    C, at, rows, fmax = None, 0, 0, -1
+    for est in rf.estimators_:
+        t = est.tree_
+        left, right = np.asarray(t.children_left, np.int64), np.asarray(t.children_right, np.int64)
+        feat, thr = np.asarray(t.feature, np.int64), np.asarray(t.threshold, np.float64)
+        value = np.asarray(t.value, np.float64).reshape(len(left), -1)
+        C = value.shape[1] if C is None else C
+        leaf = left < 0
+        inner = ~leaf
+        if value.shape[1] != C or len(left) == 0 or ((left[inner] >= len(left)) | (right[inner] >= len(left)) | (right[inner] < 0)
+                                                      | (feat[inner] < 0)).any():
+            raise ValueError("pack_forest: inconsistent tree tables")
+        if inner.any() and not np.isfinite(thr[inner]).all():
+            raise ValueError("pack_forest: a non-finite threshold")
+        fmax = max(fmax, int(feat[inner].max()) if inner.any() else -1)
+        rec = np.zeros((len(left), 4), np.int32)
+        rec[:, 0] = np.where(leaf, -1, feat)
+        rec[:, 1] = np.where(leaf, np.float32(0), float32_floor(np.where(leaf, 0.0, thr))).astype(np.float32).view(np.int32)
+        rec[:, 2] = np.where(leaf, rows + np.cumsum(leaf) - 1, left + at)
+        rec[:, 3] = np.where(leaf, 0, right + at)
+        tot = value[leaf].sum(axis=1, keepdims=True)
+        leaves.append(value[leaf] / np.where((tot == 0.0) | (np.abs(tot - 1.0) <= 1e-9), 1.0, tot))
+        nodes.append(rec)
+        roots.append(at)
+        at += len(left)
+        rows += int(leaf.sum())
+    if not roots:
+        raise ValueError("pack_forest: a forest without trees")
+    n_feat = fmax + 1 if n_feat is None else int(n_feat)
+    if not 1 <= n_feat <= FOREST_MAX_FEATURES or fmax >= n_feat:
+        raise ValueError(f"pack_forest: {n_feat} features (highest index used {fmax}); 1..{FOREST_MAX_FEATURES} supported")
+    if not 1 <= C <= FOREST_MAX_CLASSES:
+        raise ValueError(f"pack_forest: {C} classes; 1..{FOREST_MAX_CLASSES} supported")
+    return Forest(np.concatenate(nodes), np.ascontiguousarray(np.concatenate(leaves)), np.asarray(roots, np.int32), n_feat, C)
+
+
+def forest_predict(features: torch.Tensor, forest: Forest, output_channel=None) -> torch.Tensor:
+    """`predict_proba` of a packed forest at every voxel of a feature-planar bank [N, F, *spatial] -> float32 [N, C', *spatial]:
+    all C classes (`output_channel=None`), the listed ones (a tuple), or one with the channel axis dropped (an int).  Per
+    class the leaf rows are summed in float64 in tree order, divided by the tree count and rounded once: sklearn's float64
+    result cast to float32, bit for bit."""
+    if not torch.is_tensor(features) or features.dim() < 3 or features.dtype != torch.float32 or features.numel() == 0:
+        raise ValueError("forest_predict: expected a non-empty float32 bank [N, F, *spatial]")
+    N, F = int(features.shape[0]), int(features.shape[1])
+    if F != forest.n_features:
+        raise ValueError(f"forest_predict: the bank has {F} features, the forest was fitted on {forest.n_features}")
+    sel = list(range(forest.n_classes)) if output_channel is None else \
+        [output_channel] if isinstance(output_channel, numbers.Integral) else list(output_channel)
+    if not sel or any(isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 0 <= c < forest.n_classes for c in sel):
+        raise ValueError(f"forest_predict: output_channel {output_channel!r} outside the {forest.n_classes} classes")
+    _req_cuda(features)
+    features = features.contiguous()
+    spatial = tuple(features.shape[2:])
+    V = features.numel() // (N * F)
+    nodes, leaves, roots = forest.on(features.device)
+    out = torch.empty((N, len(sel)) + spatial, dtype=torch.float32, device=features.device)
+    _lib.check(_lib.load().tem_forest_predict(_p(features), N, F, V, _p(nodes), _p(leaves), _p(roots), forest.n_trees, forest.n_classes,
+                                              (ctypes.c_int * len(sel))(*[int(c) for c in sel]), len(sel), _p(out), _stream(features)),
+               "tem_forest_predict")
+    return out[:, 0] if isinstance(output_channel, numbers.Integral) else out
+
+
 # ---- label overlaps and instance-segmentation scores (csrc/overlap.hip) ----
 _OV_LABELS = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
 

@@ -111,6 +111,18 @@ def gaussian_weights(sigma: float = SIGMA, truncate: float = TRUNCATE) -> np.nda
     return phi / phi.sum()
 
 
+def gaussian_jet_weights(sigma: float, truncate: float = TRUNCATE) -> np.ndarray:
+    """scipy's `_gaussian_kernel1d(sigma, order, radius)` for the orders 0, 1 and 2, float64 [3, 2 * radius + 1]: the
+    normalised phi, phi * (-x / sigma^2) and phi * (x^2 / sigma^4 - 1 / sigma^2) -- the impulse responses of
+    `gaussian_filter1d(order=o)`; the taps of its correlation are these reversed."""
+    sigma = float(sigma)
+    phi = gaussian_weights(sigma, truncate)
+    radius = len(phi) // 2
+    x = np.arange(-radius, radius + 1, dtype=np.float64)
+    s2 = sigma * sigma
+    return np.stack([phi, phi * (-x / s2), phi * (x * x / (s2 * s2) - 1.0 / s2)])
+
+
 def spline_fir_weights(radius: int = SPLINE_RADIUS) -> np.ndarray:
     """The two-sided impulse response sqrt(3) * pole^|k| of the cubic B-spline prefilter (pole sqrt(3) - 2, gain 6), cut
     after `radius` taps a side; float64.  On the whole-sample mirror extension it gives `spline_filter(order=3,
