@@ -1177,6 +1177,33 @@ int tem_mws_run(const float* aff, const int* offsets, int n_attractive, int N, i
                 int64_t ws_bytes, uint64_t* table, int64_t slots, int first, int rounds, tem_stream_t stream);
 int tem_mws_labels(int* out, int N, int C, int D, int H, int W, void* ws, int64_t ws_bytes, tem_stream_t stream);
 
+/* ---- embedding mutex watershed (csrc/embmws.hip; the definition: DESIGN.md "Embedding mutex watershed") -----------------
+ * The two ends around tem_mws_*: embeddings to edge weights, and the background merge of the result.
+ *   tem_emb_edges    emb: float32 [N][E][D][H][W] (2-D: D == 1), contiguous, 1 <= E <= TEM_EMB_MAX_DIM, V = D*H*W < 2^31 - 1;
+ *                    offsets: HOST int32 [C][3] (dz, dy, dx), C <= TEM_MWS_MAX_CHANNELS; strides: HOST int32 [3] (z, y, x),
+ *                    each >= 1; delta > 0; distance_type TEM_EMB_L2 or TEM_EMB_L1.  Writes aff: float32 [N][C][V] and
+ *                    edge_valid: uint8 [N][C][V], both as tem_mws_init / tem_mws_run read them.  For voxel v and
+ *                    u = v + offsets[c] inside the sample: d = sqrt(sum_e (x_e(v) - x_e(u))^2) (L1: sum_e |x_e(v) - x_e(u)|),
+ *                    s = (max(2 delta - d, 0) / (2 delta))^2, aff = 1 - s; aff = 0 where u is outside.  float32 throughout,
+ *                    one rounding an operation, the sum over e ascending from 0, no fma, sqrt and / correctly rounded.
+ *                    edge_valid = 1 on the n_attractive leading channels; on the others 1 where z, y and x of v are
+ *                    multiples of strides[0], strides[1], strides[2].
+ *   tem_emb_bg_stats ids: int32 [N][V] in 0..V (0: not a segment; it stays 0), emb as above with V voxels a channel.  bg = the
+ *                    id >= 1 with the most voxels, ties to the lowest id; per segment k the mean embedding m_k (64-bit fixed
+ *                    point sums at 2^-28, so the result is one from run to run; |x| * voxels below 2^34), dist = ||m_k - m_bg||_2
+ *                    and p_k = (max(2 delta - dist, 0) / (2 delta))^2 in float64, channels ascending.  Writes keep: int32
+ *                    [N][V + 1], 1 for the ids that occur and have p_k <= 0.5, else 0 (slot 0 of a sample: 0) -- the input
+ *                    of tem_pod_size_apply after a prefix sum.  ws: tem_emb_bg_ws bytes, 16-byte aligned; N * (V + 1) < 2^31 - 1.
+ * One stream throughout; nothing is read back. */
+#define TEM_EMB_MAX_DIM 64
+#define TEM_EMB_L2 0
+#define TEM_EMB_L1 1
+int tem_emb_edges(const float* emb, const int* offsets, int n_attractive, const int* strides, float delta, int distance_type, int N,
+                  int E, int C, int D, int H, int W, float* aff, uint8_t* edge_valid, tem_stream_t stream);
+int64_t tem_emb_bg_ws(int N, int64_t V);
+int tem_emb_bg_stats(const int* ids, const float* emb, int N, int E, int64_t V, double delta, int* keep, void* ws, int64_t ws_bytes,
+                     tem_stream_t stream);
+
 /* ---- peak maxima (csrc/peaks.hip; the definition: DESIGN.md "Peak maxima") ------------------------------------------------
  * peak_local_max of a float32 batch [N][D][H][W] (2-D: D == 1), V = D*H*W < 2^31 - 1, N <= 65535, min_distance d within
  * 1..TEM_PEAKS_MAX_DISTANCE.  One stream throughout; ws: tem_peaks_ws bytes, 16-byte aligned, kept from call to call.

@@ -251,6 +251,11 @@ SIGNATURES = {
     "tem_mws_init": (c_int, [c_vp, c_vp, c_vp, c_int] + [c_int] * 5 + [c_vp, c_i64, c_vp]),
     "tem_mws_run": (c_int, [c_vp, c_vp, c_int] + [c_int] * 5 + [c_vp, c_i64, c_vp, c_i64, c_int, c_int, c_vp]),
     "tem_mws_labels": (c_int, [c_vp] + [c_int] * 5 + [c_vp, c_i64, c_vp]),
+    # embedding mutex watershed (csrc/embmws.hip): (emb, offsets (host), n_attractive, strides (host), delta, distance_type,
+    # N, E, C, D, H, W, aff, edge_valid, stream) / (N, V) / (ids, emb, N, E, V, delta, keep, ws, ws_bytes, stream)
+    "tem_emb_edges": (c_int, [c_vp, c_vp, c_int, c_vp, c_float, c_int] + [c_int] * 6 + [c_vp, c_vp, c_vp]),
+    "tem_emb_bg_ws": (c_i64, [c_int, c_i64]),
+    "tem_emb_bg_stats": (c_int, [c_vp, c_vp, c_int, c_int, c_i64, c_double, c_vp, c_vp, c_i64, c_vp]),
     # peak maxima (csrc/peaks.hip): (image, N, D, H, W, min_distance, has_abs, thr_abs, has_rel, thr_rel, border, ws, ws_bytes,
     # stream) / (N, D, H, W, min_distance, ws, ws_bytes, counts, first, rounds, stream) /
     # (image, base, idx, height, sample, N, D, H, W, ws, ws_bytes, stream) / (idx, sample, start, T, limit, out, N, V, stream)

@@ -13,15 +13,22 @@ nothing ignored), `matching` (label 0 ignored on both sides, objects matched one
 was compared with its output.  IoU thresholds below 0.5 are refused: there the matches no longer are isolated pairs and
 counting them needs an assignment solver.
 
-Not provided: the reference's `MWS*`, `EmbeddingMWS*`, `Multicut*` and `HDBScan*` classes (and their segmenters): the
-mutex watershed exists as a segmenter (util/mutex_watershed.py: `mutex_watershed_segmentation`) but its metric classes are not
-written, and there is no multicut solver and no HDBSCAN here.
-The prefab classes sit on the two watershed segmenters that exist: `Watershed{IOU,SBD,VOI,Rand}Metric`."""
+The mutex-watershed metrics sit on `ops.mutex_watershed`: `MWS{IOU,SBD,VOI,Rand}Metric` segment affinity predictions (`MWS`),
+`EmbeddingMWS{IOU,SBD,VOI,Rand}Metric` segment pixel embeddings (`EmbeddingMWS`: `util.segment_embeddings_mws`; DESIGN.md
+"Embedding mutex watershed").  The number of rounds of a mutex watershed depends on the data, so it reads two ints back per
+batch of rounds: these eight classes run with host synchronisation allowed (`sync_free = False`).  Constructor signatures,
+`init_kwargs` and the wiring are the reference's as it stands -- its `EmbeddingMWS*Metric` accept `strides` and do not hand
+them to their segmenter, and so do these.
+Not provided: the reference's `Multicut*` and `HDBScan*` classes (and their segmenters): there is no multicut solver and no
+HDBSCAN here.
+The other prefab classes sit on the two watershed segmenters: `Watershed{IOU,SBD,VOI,Rand}Metric`."""
 import torch
 import torch.nn as nn
 
 from .. import ops
 from ..util import segmentation as useg
+from ..util.embedding_mws import segment_embeddings_mws
+from ..util.mutex_watershed import repulsive_edge_subsampling
 
 _STATS = ("precision", "recall", "segmentation_accuracy", "f1")
 
@@ -136,6 +143,58 @@ class DistanceWatershed:
                                                                        **self.kwargs))
 
 
+def _mws_strides(offsets, strides):
+    strides = [4] * len(offsets[0]) if strides is None else strides
+    if len(strides) != len(offsets[0]):
+        raise ValueError(f"expected {len(offsets[0])} strides (one per entry of an offset), got {len(strides)}")
+    return strides
+
+
+class MWS:
+    """affinity channels, one per offset -> `ops.mutex_watershed` with the first ndim channels attractive and the others
+    subsampled at random at the rate of `strides` (default 4 per axis; reference `:57-84`).  `with_background`: channel 0
+    is the foreground and `foreground >= 0.5` the mask; the size filter (`min_seg_size > 0`) then only removes, without it
+    the removed voxels are refilled over the maximum of the affinities (`util.segmentation.size_filter`)."""
+    def __init__(self, offsets, with_background, min_seg_size, strides=None):
+        self.offsets = offsets
+        self.with_background = with_background
+        self.min_seg_size = min_seg_size
+        self.strides = _mws_strides(offsets, strides)
+
+    def __call__(self, input_):
+        C, nd = len(self.offsets), len(self.offsets[0])
+        if input_.dim() != nd + 2 or input_.shape[1] != C + int(bool(self.with_background)):
+            raise ValueError(f"MWS: expected [N, {C + int(bool(self.with_background))}, *spatial] with {nd} spatial axes"
+                             f"{' (foreground, affinities)' if self.with_background else ''}, got {tuple(input_.shape)}")
+        N, sp = input_.shape[0], tuple(input_.shape[2:])
+        s3 = (1,) * (3 - nd) + sp
+        aff = input_[:, 1:] if self.with_background else input_
+        mask = (input_[:, 0] >= 0.5).reshape((N,) + s3) if self.with_background else None
+        aff5 = aff.to(torch.float32).reshape((N, C) + s3).contiguous()
+        valid = repulsive_edge_subsampling(sp, C, nd, self.strides, True, None, batch=N, device=input_.device)
+        seg = ops.mutex_watershed(aff5, self.offsets, nd, mask, valid.reshape(aff5.shape))
+        if self.min_seg_size > 0:
+            hmap = None if self.with_background else aff5.amax(dim=1).reshape((N, 1) + sp)
+            seg = useg.size_filter(seg.reshape((N, 1) + sp), self.min_seg_size, hmap=hmap)
+        return seg.reshape((N,) + s3)
+
+
+class EmbeddingMWS:
+    """pixel embeddings -> `util.segment_embeddings_mws` (l2, `strides` default 4 per axis, on the grid; reference `:87-128`)"""
+    def __init__(self, delta, offsets, with_background, min_seg_size, strides=None):
+        self.delta = delta
+        self.offsets = offsets
+        self.with_background = with_background
+        self.min_seg_size = min_seg_size
+        self.strides = _mws_strides(offsets, strides)
+
+    def __call__(self, input_):
+        if input_.dim() != len(self.offsets[0]) + 2:
+            raise ValueError(f"EmbeddingMWS: expected [N, E, *spatial] with {len(self.offsets[0])} spatial axes, got {tuple(input_.shape)}")
+        return _ids4(segment_embeddings_mws(input_, self.offsets, self.delta, self.strides, "l2", self.with_background,
+                                            self.min_seg_size))
+
+
 _SEGMENTERS = {"distances": DistanceWatershed, "components": ComponentsWatershed}
 
 
@@ -149,7 +208,10 @@ class BaseInstanceSegmentationMetric(nn.Module):
     """segmenter: prediction batch [N, C, *spatial] -> ids; metric: (seg, target ids) -> per-sample scores.  forward
     segments the whole batch on the device, takes the ids from `target[:, -1]` (the reference's convention) and returns
     the mean of the per-sample scores as a 0-dim float64 device tensor.  The whole forward runs with host synchronisation
-    forbidden (`torch.cuda.set_sync_debug_mode("error")`).  `to_numpy` is kept for the signature and ignored."""
+    forbidden (`torch.cuda.set_sync_debug_mode("error")`) unless the class says `sync_free = False` (the mutex-watershed
+    metrics: their segmenter reads two ints back per batch of rounds).  `to_numpy` is kept for the signature and ignored."""
+    sync_free = True
+
     def __init__(self, segmenter, metric, to_numpy=False):
         super().__init__()
         self.segmenter = segmenter
@@ -162,7 +224,8 @@ class BaseInstanceSegmentationMetric(nn.Module):
                              f"{tuple(target.shape)}")
         ops._req_cuda(input_, target)
         before = torch.cuda.get_sync_debug_mode()
-        torch.cuda.set_sync_debug_mode("error")
+        if self.sync_free:
+            torch.cuda.set_sync_debug_mode("error")
         try:
             seg = self.segmenter(input_.detach())
             ids = target.detach()[:, -1]
@@ -209,3 +272,79 @@ class WatershedRandMetric(BaseInstanceSegmentationMetric):
     def __init__(self, segmenter="distances", **segmenter_kwargs):
         super().__init__(_segmenter(segmenter, segmenter_kwargs), AdaptedRandError())
         self.init_kwargs = {"segmenter": segmenter, **segmenter_kwargs}
+
+
+class _MWSMetric(BaseInstanceSegmentationMetric):
+    sync_free = False
+
+
+class MWSIOUMetric(_MWSMetric):
+    """1 - precision of the matching at `iou_threshold` of a mutex watershed of affinity predictions with a foreground
+    channel in front (reference `:410-432`).
+
+    Args:
+        offsets: the offsets of the affinity channels.
+        min_seg_size: segments with fewer voxels are removed.
+        iou_threshold: the IoU from which two objects match, in [0.5, 1].
+        strides: the strides of the repulsive-edge subsampling (default 4 per axis)."""
+    def __init__(self, offsets, min_seg_size, iou_threshold=0.5, strides=None):
+        super().__init__(MWS(offsets, with_background=True, min_seg_size=min_seg_size, strides=strides), IOUError(iou_threshold))
+        self.init_kwargs = {"offsets": offsets, "min_seg_size": min_seg_size, "iou_threshold": iou_threshold, "strides": strides}
+
+
+class MWSSBDMetric(_MWSMetric):
+    """1 - symmetric best Dice of a mutex watershed of affinity predictions with a foreground channel in front."""
+    def __init__(self, offsets, min_seg_size, strides=None):
+        super().__init__(MWS(offsets, with_background=True, min_seg_size=min_seg_size, strides=strides), SymmetricBestDice())
+        self.init_kwargs = {"offsets": offsets, "min_seg_size": min_seg_size, "strides": strides}
+
+
+class MWSVOIMetric(_MWSMetric):
+    """Variation of information of a mutex watershed of affinity predictions (no foreground channel)."""
+    def __init__(self, offsets, min_seg_size, strides=None):
+        super().__init__(MWS(offsets, with_background=False, min_seg_size=min_seg_size, strides=strides), VariationOfInformation())
+        self.init_kwargs = {"offsets": offsets, "min_seg_size": min_seg_size, "strides": strides}
+
+
+class MWSRandMetric(_MWSMetric):
+    """Adapted Rand error of a mutex watershed of affinity predictions (no foreground channel)."""
+    def __init__(self, offsets, min_seg_size, strides=None):
+        super().__init__(MWS(offsets, with_background=False, min_seg_size=min_seg_size, strides=strides), AdaptedRandError())
+        self.init_kwargs = {"offsets": offsets, "min_seg_size": min_seg_size, "strides": strides}
+
+
+class EmbeddingMWSIOUMetric(_MWSMetric):
+    """1 - precision of the matching at `iou_threshold` of an embedding mutex watershed with the background merged (reference
+    `:222-246`).  `strides` is recorded in `init_kwargs` and, as in the reference, not handed to the segmenter.
+
+    Args:
+        delta: the hinge distance of the contrastive loss the embeddings were trained with.
+        offsets: the offsets of the edges derived from the embeddings.
+        min_seg_size: segments with fewer voxels are removed.
+        iou_threshold: the IoU from which two objects match, in [0.5, 1].
+        strides: see above."""
+    def __init__(self, delta, offsets, min_seg_size, iou_threshold=0.5, strides=None):
+        super().__init__(EmbeddingMWS(delta, offsets, with_background=True, min_seg_size=min_seg_size), IOUError(iou_threshold))
+        self.init_kwargs = {"delta": delta, "offsets": offsets, "min_seg_size": min_seg_size, "iou_threshold": iou_threshold,
+                            "strides": strides}
+
+
+class EmbeddingMWSSBDMetric(_MWSMetric):
+    """1 - symmetric best Dice of an embedding mutex watershed with the background merged (arguments: `EmbeddingMWSIOUMetric`)."""
+    def __init__(self, delta, offsets, min_seg_size, strides=None):
+        super().__init__(EmbeddingMWS(delta, offsets, with_background=True, min_seg_size=min_seg_size), SymmetricBestDice())
+        self.init_kwargs = {"delta": delta, "offsets": offsets, "min_seg_size": min_seg_size, "strides": strides}
+
+
+class EmbeddingMWSVOIMetric(_MWSMetric):
+    """Variation of information of an embedding mutex watershed, no background merge (arguments: `EmbeddingMWSIOUMetric`)."""
+    def __init__(self, delta, offsets, min_seg_size, strides=None):
+        super().__init__(EmbeddingMWS(delta, offsets, with_background=False, min_seg_size=min_seg_size), VariationOfInformation())
+        self.init_kwargs = {"delta": delta, "offsets": offsets, "min_seg_size": min_seg_size, "strides": strides}
+
+
+class EmbeddingMWSRandMetric(_MWSMetric):
+    """Adapted Rand error of an embedding mutex watershed, no background merge (arguments: `EmbeddingMWSIOUMetric`)."""
+    def __init__(self, delta, offsets, min_seg_size, strides=None):
+        super().__init__(EmbeddingMWS(delta, offsets, with_background=False, min_seg_size=min_seg_size), AdaptedRandError())
+        self.init_kwargs = {"delta": delta, "offsets": offsets, "min_seg_size": min_seg_size, "strides": strides}

@@ -2164,6 +2164,115 @@ def mutex_watershed(aff: torch.Tensor, offsets, n_attractive: int, mask: Optiona
     return (ids, work) if return_rounds else ids
 
 
+# ---- embedding mutex watershed (csrc/embmws.hip) ----
+EMB_MAX_DIM = 64               # TEM_EMB_MAX_DIM
+_EMB_DISTANCE = {"l2": 0, "l1": 1}   # TEM_EMB_L2, TEM_EMB_L1
+
+
+def _emb_delta(delta, what):
+    if isinstance(delta, bool) or not isinstance(delta, numbers.Real) or not 0.0 < ctypes.c_float(float(delta)).value < math.inf:
+        raise ValueError(f"{what}: delta must be a positive number, got {delta!r}")
+    return float(delta)
+
+
+def _emb_args(emb, offsets, delta, n_attractive, strides, distance_type):
+    """the host-side checks of `embedding_edges` -> (offsets as C (dz, dy, dx), strides as (sz, sy, sx), the distance code)"""
+    what = "embedding_edges"
+    if not torch.is_tensor(emb) or emb.dim() != 5 or emb.dtype != torch.float32 or emb.numel() == 0:
+        raise ValueError(f"{what}: expected non-empty float32 embeddings [N, E, D, H, W], got "
+                         f"{getattr(emb, 'dtype', type(emb))} {tuple(getattr(emb, 'shape', ()))}")
+    N, E, D, H, W = (int(s) for s in emb.shape)
+    if E > EMB_MAX_DIM:
+        raise ValueError(f"{what}: {E} embedding channels, at most {EMB_MAX_DIM} supported")
+    if distance_type == "cosine":
+        raise NotImplementedError(f"{what}: the cosine distance is not implemented on the device (l2 and l1 are)")
+    if distance_type not in _EMB_DISTANCE:
+        raise ValueError(f"{what}: distance_type must be one of {sorted(_EMB_DISTANCE)}, got {distance_type!r}")
+    _emb_delta(delta, what)
+    try:
+        offs = [[int(x) for x in o] for o in offsets]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: offsets must be integer vectors of length 2 or 3") from None
+    if not offs:
+        raise ValueError(f"{what}: at least one offset is needed")
+    if len(offs) > MWS_MAX_CHANNELS:
+        raise ValueError(f"{what}: {len(offs)} offsets, at most {MWS_MAX_CHANNELS} supported")
+    if any(len(o) not in (2, 3) or len(o) != len(offs[0]) for o in offs):
+        raise ValueError(f"{what}: offsets must be integer vectors of one length, 2 or 3")
+    nd = len(offs[0])
+    if nd == 2 and D != 1:
+        raise ValueError(f"{what}: offsets of length 2 need D = 1, got D = {D}")
+    if any(abs(x) >= 2 ** 30 for o in offs for x in o):
+        raise ValueError(f"{what}: offsets must be below 2^30 in magnitude")
+    if isinstance(n_attractive, bool) or not isinstance(n_attractive, numbers.Integral) or not 0 <= n_attractive <= len(offs):
+        raise ValueError(f"{what}: n_attractive must be an integer within 0..{len(offs)}, got {n_attractive}")
+    try:
+        st = [1] * nd if strides is None else [int(s) for s in strides]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: strides must be {nd} integers >= 1") from None
+    if len(st) != nd or min(st) < 1 or max(st) >= 2 ** 30:
+        raise ValueError(f"{what}: expected {nd} strides >= 1 (one per offset entry), got {st}")
+    if D * H * W >= 2 ** 31 - 1:
+        raise ValueError(f"{what}: {D * H * W} voxels per sample, at most 2^31 - 2 supported")
+    return [[0] * (3 - nd) + o for o in offs], [1] * (3 - nd) + st, _EMB_DISTANCE[distance_type]
+
+
+def embedding_edges(emb: torch.Tensor, offsets, delta: float, n_attractive: int, strides=None, distance_type: str = "l2"):
+    """float32 embeddings [N, E, D, H, W] (2-D: D = 1; E <= 64) -> (aff float32 [N, C, D, H, W], edge_valid bool of that shape):
+    the inputs of `mutex_watershed` for the C `offsets` (integer vectors of length 2 or 3; tem_emb_edges; the definition:
+    DESIGN.md "Embedding mutex watershed").  For voxel v and u = v + offsets[c] inside the sample, d = ||x(v) - x(u)||_2
+    (`distance_type` "l1": the 1-norm), s = (max(2 delta - d, 0) / (2 delta))^2 and aff = 1 - s: a low value on an attractive
+    channel is a strong attraction, a high one on a repulsive channel a strong repulsion; aff = 0 where u is outside.  The
+    arithmetic is float32 with one rounding an operation and the channels summed in ascending order: numpy's float32
+    expression gives the same bits.  edge_valid is set on the `n_attractive` leading channels, and on the others where every
+    coordinate of v is a multiple of its stride (`strides`, one per axis of the offsets; None: 1 each)."""
+    offs, st, dist = _emb_args(emb, offsets, delta, n_attractive, strides, distance_type)
+    _req_cuda(emb)
+    N, E, D, H, W = (int(s) for s in emb.shape)
+    C = len(offs)
+    emb = emb.contiguous()
+    aff = torch.empty((N, C, D, H, W), dtype=torch.float32, device=emb.device)
+    valid = torch.empty((N, C, D, H, W), dtype=torch.bool, device=emb.device)
+    coffs = (ctypes.c_int * (3 * C))(*[x for o in offs for x in o])
+    cst = (ctypes.c_int * 3)(*st)
+    _lib.check(_lib.load().tem_emb_edges(_p(emb), coffs, int(n_attractive), cst, float(delta), dist, N, E, C, D, H, W, _p(aff),
+                                         _p(valid), _stream(emb)), "tem_emb_edges")
+    return aff, valid
+
+
+def merge_background_by_embedding_(ids: torch.Tensor, emb: torch.Tensor, delta: float) -> torch.Tensor:
+    """in place on contiguous int32 ids [N, D, H, W] in 0..D*H*W (the ids 1..n of `mutex_watershed`) with float32 embeddings
+    [N, E, D, H, W]: per sample the segment with the most voxels (ties: the lowest id) is the background; every segment k
+    whose mean embedding m_k has p_k = (max(2 delta - ||m_k - m_bg||_2, 0) / (2 delta))^2 > 0.5 -- the background itself
+    among them -- becomes 0 and the others are renumbered 1..n' in ascending order of their ids (tem_emb_bg_stats, then the
+    scan and tem_pod_size_apply of `size_filter_`).  The means are 64-bit fixed-point sums (2^-28; |value| * voxels of a
+    segment below 2^34), the rest is float64 in a fixed order: one result from run to run.  Id 0 stays 0 and counts for
+    nothing.  Nothing is read back."""
+    what = "merge_background_by_embedding_"
+    if not torch.is_tensor(ids) or ids.dim() != 4 or ids.dtype != torch.int32 or ids.numel() == 0 or not ids.is_contiguous():
+        raise ValueError(f"{what}: expected non-empty contiguous int32 ids [N, D, H, W], got "
+                         f"{getattr(ids, 'dtype', type(ids))} {tuple(getattr(ids, 'shape', ()))}")
+    if (not torch.is_tensor(emb) or emb.dim() != 5 or emb.dtype != torch.float32 or emb.shape[0] != ids.shape[0]
+            or emb.shape[2:] != ids.shape[1:] or not 1 <= emb.shape[1] <= EMB_MAX_DIM):
+        raise ValueError(f"{what}: expected float32 embeddings [N, E <= {EMB_MAX_DIM}, D, H, W] for ids {tuple(ids.shape)}, got "
+                         f"{getattr(emb, 'dtype', type(emb))} {tuple(getattr(emb, 'shape', ()))}")
+    delta = _emb_delta(delta, what)
+    N, E = int(emb.shape[0]), int(emb.shape[1])
+    V = ids.numel() // N
+    if N * (V + 1) >= 2 ** 31 - 1:
+        raise ValueError(f"{what}: {N} samples of {V} voxels; N * (V + 1) below 2^31 - 1 supported")
+    _req_cuda(ids, emb)
+    emb = emb.contiguous()
+    lib = _lib.load()
+    nbytes = int(lib.tem_emb_bg_ws(N, V))
+    ws = torch.empty((nbytes,), dtype=torch.uint8, device=ids.device)
+    keep = torch.empty((N * (V + 1),), dtype=torch.int32, device=ids.device)
+    _lib.check(lib.tem_emb_bg_stats(_p(ids), _p(emb), N, E, V, delta, _p(keep), _p(ws), nbytes, _stream(ids)), "tem_emb_bg_stats")
+    newid = _flat_cumsum(keep)
+    _lib.check(lib.tem_pod_size_apply(_p(ids), _p(keep), _p(newid), N, V, _stream(ids)), "tem_pod_size_apply")
+    return ids
+
+
 # ---- peak maxima (csrc/peaks.hip) ----
 PEAKS_MAX_DISTANCE = 31        # TEM_PEAKS_MAX_DISTANCE
 PEAKS_MAX_BATCH = 64           # TEM_PEAKS_MAX_BATCH

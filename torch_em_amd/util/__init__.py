@@ -1,5 +1,6 @@
 """Utilities of the MI355X path that sit next to the hot path (reference torch_em/util/)."""
-from . import mutex_watershed, peak_watershed, segmentation
+from . import embedding_mws, mutex_watershed, peak_watershed, segmentation
+from .embedding_mws import segment_embeddings_mws
 from .mutex_watershed import mutex_watershed_segmentation, repulsive_edge_subsampling
 from .peak_watershed import boundary_distance_map, watershed_from_maxima
 from .prediction import predict_with_halo, predict_with_halo_pipelined, predict_with_padding
