@@ -1374,6 +1374,24 @@ int tem_patch_hist_reduce(const int32_t* hist, int M, int n_ids, int mode, const
 int tem_patch_gather(const void* vols, const int32_t* boxes, int B, int C, int in_dtype, int pd, int ph, int pw, void* out,
                      int out_dtype, tem_stream_t stream);
 
+/* ---- fused multi-head self-attention over a 2-D token grid (model/vit.py; segment_anything's Attention with
+ * add_decomposed_rel_pos, equal query and key grids; csrc/attention.hip) -------------------------------------------------
+ * q, k, v, out: [B][nH][N = H W][D] views of the storage type `st` (TEM_ST_*), token n = h W + w, addressed by their four
+ * ELEMENT strides (batch, head, token, D) given as host arrays: the D stride is 1, the others are non-negative multiples of
+ * 16 bytes, the base pointers are 16-byte aligned -- the three views of a packed qkv-linear output [B][N][3][nH][D] and an out
+ * of layout [B][H][W][nH D] qualify.  D is 64 or 80, H and W are at most TEM_ATTN_MAX_GRID, B nH at most 65535.
+ *   S[i][j] = scale (q_i . k_j) + q_i . rel_h[hi - hj + H-1] + q_i . rel_w[wi - wj + W-1]     out = softmax_j(S) v
+ * rel_h [2H-1][D] and rel_w [2W-1][D] are dense tables of the same type, both or neither (NULL); with tables the call needs
+ * tem_attention_ws() bytes of 16-byte aligned workspace (the bias pre-pass result, fp32 [B][nH][N][H + W]).  The products
+ * run on the matrix cores with fp32 accumulation, `scale` multiplies the accumulated fp32 logits, P is rounded once to a 16-bit
+ * `st` (kept in fp32 for TEM_ST_F32); S and P never reach global memory; no atomics: the result is bitwise reproducible.
+ * Inference only.  tem_attention_ws is host logic (no device needed) and returns -1 for sizes the launch refuses. */
+#define TEM_ATTN_MAX_GRID 256
+int64_t tem_attention_ws(int B, int nH, int H, int W, int D, int has_rel_pos);
+int tem_attention_fwd(const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
+                      const int64_t* v_strides, void* out, const int64_t* out_strides, const void* rel_h, const void* rel_w,
+                      int B, int nH, int H, int W, int D, float scale, int st, void* ws, int64_t ws_bytes, tem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

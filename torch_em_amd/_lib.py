@@ -292,6 +292,10 @@ SIGNATURES = {
     "tem_patch_hist_path": (c_int, [c_int]),
     "tem_patch_hist_reduce": (c_int, [c_vp, c_int, c_int, c_int, c_vp, c_int, c_int, c_vp, c_vp]),
     "tem_patch_gather": (c_int, [c_vp, c_vp, c_int, c_int, c_int, c_int, c_int, c_int, c_vp, c_int, c_vp]),
+    # fused attention (csrc/attention.hip): (B, nH, H, W, D, has_rel_pos) / (q, q_strides (host int64[4]), k, k_strides, v, v_strides,
+    # out, out_strides, rel_h, rel_w, B, nH, H, W, D, scale, st, ws, ws_bytes, stream)
+    "tem_attention_ws": (c_i64, [c_int] * 6),
+    "tem_attention_fwd": (c_int, [c_vp, ctypes.POINTER(c_i64)] * 4 + [c_vp, c_vp] + [c_int] * 5 + [c_float, c_int, c_vp, c_i64, c_vp]),
 }
 
 _lib = None

@@ -2993,3 +2993,44 @@ def patch_gather(vols: PatchVolumes, boxes, patch_shape, dtype: torch.dtype = to
     _lib.check(_lib.load().tem_patch_gather(_p(vols.table), _p(bx.dev), bx.M, C, PT_DTYPE[vols.dtype], pd, ph, pw, _p(out),
                                             PT_DTYPE[dtype], _stream(out)), "tem_patch_gather")
     return out
+
+
+# ---- fused multi-head attention over a 2-D token grid (csrc/attention.hip) ----
+def _attn_strides(t: torch.Tensor):
+    return (ctypes.c_int64 * 4)(*[int(s) for s in t.stride()])
+
+
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, grid, scale=None, rel_pos=None, out=None) -> torch.Tensor:
+    """softmax(scale * q k^T + rel_h + rel_w) v over the tokens of an H x W grid, one launch that never materialises the
+    logits (segment_anything's Attention with add_decomposed_rel_pos; inference only).  q, k, v: [B, nH, N = H * W, D] views of
+    one 16-bit or float32 type with unit stride along D (D 64 or 80) -- the slices of a packed qkv-linear output are read in
+    place.  `rel_pos` = (Rh [2H-1, D], Rw [2W-1, D]) adds q_i . Rh[hi - hj + H-1] + q_i . Rw[wi - wj + W-1] (q unscaled) to
+    logit (i, j).  Returns [B, nH, N, D], or fills `out` (any view of that shape with unit stride along D)."""
+    H, W = (int(g) for g in grid)
+    if not all(torch.is_tensor(t) and t.dim() == 4 for t in (q, k, v)) or not (q.shape == k.shape == v.shape):
+        raise ValueError("attention: q, k, v are [B, nH, N, D] tensors of one shape")
+    B, nH, N, D = (int(s) for s in q.shape)
+    if N != H * W or N == 0:
+        raise ValueError(f"attention: {N} tokens do not make the grid {H} x {W}")
+    tables = (None, None) if rel_pos is None else tuple(rel_pos)
+    _req_cuda(q, k, v, out, *tables)
+    if q.dtype not in _ST:
+        raise ValueError(f"attention: {q.dtype} not supported (float32, float16, bfloat16)")
+    if out is None:
+        out = torch.empty((B, nH, N, D), dtype=q.dtype, device=q.device)
+    elif tuple(out.shape) != (B, nH, N, D):
+        raise ValueError(f"attention: out must have shape {(B, nH, N, D)}")
+    _same_st(q, k, v, out, *tables)
+    if rel_pos is not None:
+        if tuple(tables[0].shape) != (2 * H - 1, D) or tuple(tables[1].shape) != (2 * W - 1, D):
+            raise ValueError(f"attention: rel_pos tables must be [{2 * H - 1}, {D}] and [{2 * W - 1}, {D}]")
+        tables = tuple(t.contiguous() for t in tables)
+    lib = _lib.load()
+    nbytes = lib.tem_attention_ws(B, nH, H, W, D, int(rel_pos is not None))
+    if nbytes < 0:
+        _lib.check(-1, "tem_attention_ws")
+    ws = _workspace(nbytes, q.device) if nbytes else None
+    _lib.check(lib.tem_attention_fwd(_p(q), _attn_strides(q), _p(k), _attn_strides(k), _p(v), _attn_strides(v), _p(out), _attn_strides(out),
+                                     _p(tables[0]), _p(tables[1]), B, nH, H, W, D, float(D ** -0.5 if scale is None else scale), _st(q),
+                                     _p(ws), nbytes, _stream(q)), "tem_attention_fwd")
+    return out
