@@ -44,10 +44,9 @@ def bench_alignment(S, reps, warmup, dev, lines):
     g = torch.Generator().manual_seed(0)
     base = (torch.rand(2, 2, S, S, S, generator=g) ** 2).to(dev)
     source = torch.FloatTensor(SOURCE).to(dev)
-    lib = _lib.load()
     for dtype in (torch.float32, torch.float16):
         x = base.to(dtype)
-        n, st = x.numel(), ops._st(x)
+        n, st = x.numel(), ops.stype(x)
         thr = ops.round_to(0.5, dtype)
         partials, out = ops.label_count_partials(x), torch.empty_like(x)
 
@@ -58,11 +57,11 @@ def bench_alignment(S, reps, warmup, dev, lines):
             return composition(x, source)
 
         def count_launch():
-            _lib.check(lib.tem_label_count_st(ops._p(x), n, thr, ops._p(partials), partials.numel(), st, ops._stream(x)), "count")
+            _lib.launch("tem_label_count_st", x, _lib.ptr(x), n, thr, _lib.ptr(partials), partials.numel(), st)
 
         def align_launch():
-            _lib.check(lib.tem_distribution_align_st(ops._p(x), ops._p(out), n, thr, SOURCE[0], SOURCE[1], ops._p(partials),
-                                                     partials.numel(), st, ops._stream(x)), "align")
+            _lib.launch("tem_distribution_align_st", x, _lib.ptr(x), _lib.ptr(out), n, thr, SOURCE[0], SOURCE[1],
+                        _lib.ptr(partials), partials.numel(), st)
 
         # the kernels are pinned bit for bit to the reference on the CPU (tests/golden/g18_fixmatch.npz); torch's device
         # composition need not agree with torch's CPU one in the 16-bit types, so the difference is reported, not asserted

@@ -43,7 +43,6 @@ def torch_composition(x, codes):
 
 
 def bench_shape(shape, dtype, reps, warmup, inner, dev, lines):
-    lib = _lib.load()
     n = 1
     for s in shape:
         n *= s
@@ -60,7 +59,7 @@ def bench_shape(shape, dtype, reps, warmup, inner, dev, lines):
         dev_codes = torch.tensor(codes, dtype=torch.int32, device=dev)
 
         def run():
-            _lib.check(lib.tem_dihedral2d(ops._p(src), ops._p(out), ops._p(dev_codes), N, planes, H, W, eb, ops._stream(src)), "tem_dihedral2d")
+            _lib.launch("tem_dihedral2d", src, _lib.ptr(src), _lib.ptr(out), _lib.ptr(dev_codes), N, planes, H, W, eb)
         return run
 
     rows = [("device copy (the floor)", lambda: out.copy_(x), None)]

@@ -127,7 +127,6 @@ def test_block_kernels_against_the_reference_helpers():
     gather kernel (tem_block_load_reflect) and the masked inner-box scatter (tem_block_store_inner) reproduce them bit for bit."""
     import os
     from conftest import GOLDEN
-    from torch_em_amd import _lib
     from torch_em_amd.util.prediction import _load_block_device, _store_inner
     g = dict(np.load(os.path.join(GOLDEN, "g9_predict_helpers.npz")))
     for case in g["load_block_cases"]:
@@ -145,14 +144,13 @@ def test_block_kernels_against_the_reference_helpers():
     begin, end, halo = (list(map(int, r)) for r in g["wp.args"])
     size = [e - b for b, e in zip(begin, end)]
     pred = torch.from_numpy(g["wp.pred"]).to(DEV)
-    lib = _lib.load()
     out = torch.full((3, 7, 9, 11), -7.0, device=DEV)
-    _store_inner(lib, pred, out, None, halo, begin, size)
+    _store_inner(pred, out, None, halo, begin, size)
     assert np.array_equal(out.cpu().numpy(), g["wp.out_channels"])
     mask = torch.zeros((7, 9, 11), dtype=torch.uint8, device=DEV)
     mask[tuple(slice(b, e) for b, e in zip(begin, end))] = torch.from_numpy(g["wp.mask_block"].astype("uint8")).to(DEV)
     out = torch.full((3, 7, 9, 11), -7.0, device=DEV)
-    _store_inner(lib, pred, out, mask, halo, begin, size)
+    _store_inner(pred, out, mask, halo, begin, size)
     assert np.array_equal(out.cpu().numpy(), g["wp.out_masked"])
 
 

@@ -5,7 +5,6 @@ The reference has no native code; this is the binding a torch-em maintainer woul
 missing, every op raises.  `build()` compiles it in-tree with hipcc for gfx950.
 """
 import ctypes
-import threading
 import os
 import subprocess
 
@@ -371,27 +370,39 @@ def get_option(name):
     return int(out.value)
 
 
-_tls = threading.local()
+def ptr(t):
+    """the device pointer of a tensor (or of anything with `data_ptr()`) as a C-ABI argument; None stays None"""
+    return None if t is None else ctypes.c_void_p(t.data_ptr())
 
 
-def launch_on(idx):
-    """Make device `idx` current for the launch being assembled; `check()` -- which wraps every launch -- puts the
-    caller's device back, so an op on a `cuda:1` tensor does not move the process's current device for good."""
+def launch(name, on, *args):
+    """Enqueue entry point `name` with `args` + the stream, on the current stream of `on`'s device.
+
+    `on`: anything with a `.device` (a tensor, an `ops.Planar`).  Every int-returning entry point of SIGNATURES whose last
+    argument is a `c_vp` enqueues work and takes its stream there; the stream is torch's current stream of the TENSOR's
+    device.  A HIP launch is issued on the calling thread's current device, so when that is another one, `on`'s device is
+    current for the duration of this call only -- also when the call raises (one process drives one GPU in this design; a
+    process that touches several -- `DefaultTrainer(device="cuda:1")`, `predict_with_halo(gpu_ids=[1])` -- gets the device
+    of the tensors it passes, like a torch op would, and keeps its own current device).  The return code maps as in `check`."""
     import torch
+    fn = getattr(load(), name)
+    dev = on.device
     cur = torch.cuda.current_device()
-    if idx is not None and idx != cur:
-        if getattr(_tls, "restore", None) is None:
-            _tls.restore = cur
-        torch.cuda.set_device(idx)
+    switch = dev.index is not None and dev.index != cur
+    if switch:
+        torch.cuda.set_device(dev.index)
+    try:
+        rc = fn(*args, ctypes.c_void_p(torch.cuda.current_stream(dev).cuda_stream))
+    finally:
+        if switch:
+            torch.cuda.set_device(cur)
+    if rc:
+        check(rc, name)
 
 
 def check(rc, what=""):
-    """Map a C-ABI return code to the exception the reference raises for the same mistake."""
-    prev = getattr(_tls, "restore", None)
-    if prev is not None:
-        import torch
-        _tls.restore = None
-        torch.cuda.set_device(prev)
+    """Map a C-ABI return code to the exception the reference raises for the same mistake (the entry points that enqueue
+    nothing; `launch` for the others)."""
     if rc == 0:
         return
     msg = load().tem_last_error().decode("utf-8", "replace")

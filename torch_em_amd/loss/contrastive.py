@@ -26,12 +26,6 @@ def check_consecutive(labels: torch.Tensor) -> bool:
 class _ContrastiveFunction(torch.autograd.Function):
     @staticmethod
     def forward(ctx, emb, target, delta_var, delta_dist, alpha, beta, gamma):
-        # one stream handle serves every launch below: the embeddings' device stays current throughout
-        with torch.cuda.device(emb.device if emb.is_cuda else None):
-            return _ContrastiveFunction._forward(ctx, emb, target, delta_var, delta_dist, alpha, beta, gamma)
-
-    @staticmethod
-    def _forward(ctx, emb, target, delta_var, delta_dist, alpha, beta, gamma):
         e_all = _sp._prep(emb.detach())
         N, E = e_all.shape[0], e_all.shape[1]
         spatial = tuple(e_all.shape[2:])
@@ -41,13 +35,11 @@ class _ContrastiveFunction(torch.autograd.Function):
             raise RuntimeError("torch_em_amd.loss.contrastive runs on MI355X only (target on CPU); no CPU fallback")
         target = target.to(torch.int64).contiguous()
         dev = e_all.device
-        lib = _lib.load()
-        stream = ops._stream(e_all)
-        boot = ops._workspace(1 << 20, dev)
+        boot = ops.workspace(1 << 20, dev)
         stats = torch.empty(2 * N, dtype=torch.int64, device=dev)
         for b in range(N):
-            _lib.check(lib.tem_label_range(ops._p(target[b, 0]), V, ctypes.c_void_p(stats.data_ptr() + 16 * b), ops._p(boot),
-                                           boot.numel(), stream), "tem_label_range")
+            _lib.launch("tem_label_range", e_all, _lib.ptr(target[b, 0]), V, ctypes.c_void_p(stats.data_ptr() + 16 * b),
+                        _lib.ptr(boot), boot.numel())
         host = stats.tolist()  # the one host sync: instance counts set the shapes below
         need = emb.requires_grad
         grad = torch.zeros_like(e_all) if need else None
@@ -66,16 +58,15 @@ class _ContrastiveFunction(torch.autograd.Function):
 
             def vp(i):
                 return ctypes.c_void_p(vals.data_ptr() + 4 * (3 * b + i))
-            _lib.check(lib.tem_spoco_pull(ops._p(e), V, ops._p(lbl), V, E, C, ops._p(means), ops._p(counts),
-                                          float(delta_var), vp(0), ops._p(S), p, n, stream), "tem_spoco_pull")
-            _lib.check(lib.tem_spoco_means_terms(ops._p(means), C, E, float(delta_dist), 0, vp(1), ops._p(ddist),
-                                                 ops._p(dreg), p, n, stream), "tem_spoco_means_terms")
+            _lib.launch("tem_spoco_pull", e_all, _lib.ptr(e), V, _lib.ptr(lbl), V, E, C, _lib.ptr(means), _lib.ptr(counts),
+                        float(delta_var), vp(0), _lib.ptr(S), p, n)
+            _lib.launch("tem_spoco_means_terms", e_all, _lib.ptr(means), C, E, float(delta_dist), 0, vp(1), _lib.ptr(ddist),
+                        _lib.ptr(dreg), p, n)
             if need:
                 s = 1.0 / N
-                _lib.check(lib.tem_spoco_embed_grad(
-                    ops._p(e), V, ops._p(lbl), V, E, C, ops._p(means), ops._p(counts), ops._p(S), ops._p(ddist),
-                    ops._p(dreg), None, float(delta_var), float(C), s * alpha, s * beta, s * gamma, 0.0, ops._p(grad[b]),
-                    V, 0, p, n, stream), "tem_spoco_embed_grad")
+                _lib.launch("tem_spoco_embed_grad", e_all, _lib.ptr(e), V, _lib.ptr(lbl), V, E, C, _lib.ptr(means),
+                            _lib.ptr(counts), _lib.ptr(S), _lib.ptr(ddist), _lib.ptr(dreg), None, float(delta_var), float(C),
+                            s * alpha, s * beta, s * gamma, 0.0, _lib.ptr(grad[b]), V, 0, p, n)
             lb = alpha * vals[3 * b:3 * b + 1] / C + beta * vals[3 * b + 1:3 * b + 2] + gamma * vals[3 * b + 2:3 * b + 3]
             total = lb if total is None else total + lb
         ctx.grad = grad

@@ -51,24 +51,21 @@ def _prep(emb, what="embeddings"):
 
 
 class _Ctx:
-    """Per-call scratch: library handle, stream, workspace."""
+    """Per-call scratch: the workspace of the stream the launches on `ref` go to."""
 
     def __init__(self, ref: torch.Tensor, C, E, V, nz, A, K):
-        self.lib = _lib.load()
-        self.stream = ops._stream(ref)
-        n = int(self.lib.tem_spoco_ws(int(C), int(E), int(V), int(nz), int(A), int(K)))
-        self.ws = ops._workspace(n, ref.device)
+        n = int(_lib.load().tem_spoco_ws(int(C), int(E), int(V), int(nz), int(A), int(K)))
+        self.ws = ops.workspace(n, ref.device)
         self.nws = self.ws.numel()
         self.dev = ref.device
 
     def wsp(self):
-        return ops._p(self.ws), self.nws
+        return _lib.ptr(self.ws), self.nws
 
 
-def _label_stats(target_b: torch.Tensor, lib, stream, ws):
+def _label_stats(e, target_b: torch.Tensor, ws):
     out = torch.empty(2, dtype=torch.int64, device=target_b.device)
-    _lib.check(lib.tem_label_range(ops._p(target_b), target_b.numel(), ops._p(out), ops._p(ws), ws.numel(), stream),
-               "tem_label_range")
+    _lib.launch("tem_label_range", e, _lib.ptr(target_b), target_b.numel(), _lib.ptr(out), _lib.ptr(ws), ws.numel())
     return out
 
 
@@ -76,8 +73,7 @@ def _cluster_means(ctx, e, cs, lbl, V, E, C):
     means = torch.empty(C, E, dtype=torch.float32, device=ctx.dev)
     counts = torch.empty(C, dtype=torch.float32, device=ctx.dev)
     p, n = ctx.wsp()
-    _lib.check(ctx.lib.tem_spoco_cluster_means(ops._p(e), cs, ops._p(lbl), V, E, C, ops._p(means), ops._p(counts), p, n,
-                                               ctx.stream), "tem_spoco_cluster_means")
+    _lib.launch("tem_spoco_cluster_means", e, _lib.ptr(e), cs, _lib.ptr(lbl), V, E, C, _lib.ptr(means), _lib.ptr(counts), p, n)
     return means, counts
 
 
@@ -86,13 +82,12 @@ def compute_cluster_means(embeddings: torch.Tensor, target: torch.Tensor, n_inst
     e = _prep(embeddings.detach())
     lbl = target.to(torch.int64).contiguous()
     E, V = e.shape[0], lbl.numel()
-    with torch.cuda.device(e.device):   # the stream handle of _Ctx is used for two launches
-        ctx = _Ctx(e, n_instances, E, V, 1, 0, 0)
-        rng = _label_stats(lbl, ctx.lib, ctx.stream, ctx.ws).tolist()
-        assert rng[0] == 0, "The target min value has to be zero, otherwise this will lead to errors in scatter."
-        if rng[1] >= n_instances:
-            raise ValueError(f"target contains label {rng[1]} but n_instances is {n_instances}")
-        return _cluster_means(ctx, e, V, lbl, V, E, n_instances)[0]
+    ctx = _Ctx(e, n_instances, E, V, 1, 0, 0)
+    rng = _label_stats(e, lbl, ctx.ws).tolist()
+    assert rng[0] == 0, "The target min value has to be zero, otherwise this will lead to errors in scatter."
+    if rng[1] >= n_instances:
+        raise ValueError(f"target contains label {rng[1]} but n_instances is {n_instances}")
+    return _cluster_means(ctx, e, V, lbl, V, E, n_instances)[0]
 
 
 class GaussianKernel(nn.Module):
@@ -112,20 +107,11 @@ def _draw_offsets(offset_ranges, n_samples):
     return [[int(np.random.randint(r[0], r[1])) for r in offset_ranges] for _ in range(n_samples)]
 
 
-def _offsets_zyx(offsets, ndim):
-    arr = (ctypes.c_int * (3 * len(offsets)))()
-    for k, off in enumerate(offsets):
-        zyx = [0] + list(off) if ndim == 2 else list(off)
-        arr[3 * k], arr[3 * k + 1], arr[3 * k + 2] = zyx
-    return arr
-
-
 def _affinity_side(ctx, e, cs, lbl, D, H, W, E, offsets, ndim, delta, value, grad_scale, grad, gcs, eps=1e-7):
-    arr = _offsets_zyx(offsets, ndim)
+    arr = ops.c_offsets([[0] * (3 - ndim) + list(off) for off in offsets])
     p, n = ctx.wsp()
-    _lib.check(ctx.lib.tem_affinity_side(ops._p(e), cs, ops._p(lbl), D, H, W, E, arr, len(offsets), float(delta), eps,
-                                         ops._p(value), float(grad_scale), ops._p(grad), gcs, p, n, ctx.stream),
-               "tem_affinity_side")
+    _lib.launch("tem_affinity_side", e, _lib.ptr(e), cs, _lib.ptr(lbl), D, H, W, E, arr, len(offsets), float(delta), eps,
+                _lib.ptr(value), float(grad_scale), _lib.ptr(grad), gcs, p, n)
 
 
 class _SpocoFunction(torch.autograd.Function):
@@ -134,12 +120,7 @@ class _SpocoFunction(torch.autograd.Function):
 
     @staticmethod
     def forward(ctx, emb_q, emb_k, target, cfg):
-        need_grad = emb_q.requires_grad
-        # one stream handle serves all launches of the evaluation: the embeddings' device stays current for its whole
-        # duration (ops._stream() alone holds it only until the first _lib.check())
-        with torch.cuda.device(emb_q.device):
-            value, grad = _evaluate(emb_q.detach(), None if emb_k is None else emb_k.detach(), target, cfg, need_grad)
-        ctx.grad = grad
+        value, ctx.grad = _evaluate(emb_q.detach(), None if emb_k is None else emb_k.detach(), target, cfg, emb_q.requires_grad)
         return value
 
     @staticmethod
@@ -169,21 +150,19 @@ def _evaluate(emb_q, emb_k, target, cfg, need_grad):
     consistency = emb_k is not None
     A = cfg["max_anchors"] if consistency else 0
     K = cfg["n_samples"] if with_aff else 0
-    lib = _lib.load()
-    stream = ops._stream(emb_q)
 
     # ---- host-visible integers: label range of the last sample, unlabeled counts of every sample (ONE sync) ----
-    boot = ops._workspace(1 << 20, dev)
+    boot = ops.workspace(1 << 20, dev)
     nchunk = (V + _ZCH - 1) // _ZCH
     stats = torch.empty(2 + N, dtype=torch.int64, device=dev)
     last = target[N - 1, 0]
-    _lib.check(lib.tem_label_range(ops._p(last), V, ops._p(stats), ops._p(boot), boot.numel(), stream), "tem_label_range")
+    _lib.launch("tem_label_range", emb_q, _lib.ptr(last), V, _lib.ptr(stats), _lib.ptr(boot), boot.numel())
     chunk_counts = None
     if consistency:
         chunk_counts = torch.empty(N, nchunk, dtype=torch.int32, device=dev)
         for b in range(N):
-            _lib.check(lib.tem_zero_count(ops._p(target[b, 0]), V, ops._p(chunk_counts[b]),
-                                          ctypes.c_void_p(stats.data_ptr() + 8 * (2 + b)), stream), "tem_zero_count")
+            _lib.launch("tem_zero_count", emb_q, _lib.ptr(target[b, 0]), V, _lib.ptr(chunk_counts[b]),
+                        ctypes.c_void_p(stats.data_ptr() + 8 * (2 + b)))
     host = stats.tolist()
     lmin, lmax = host[0], host[1]
     assert lmin == 0, "The target min value has to be zero, otherwise this will lead to errors in scatter."
@@ -225,32 +204,29 @@ def _evaluate(emb_q, emb_k, target, cfg, need_grad):
     dreg = torch.empty(C, E, dtype=torch.float32, device=dev)
     dpush = None
     if n_inst > 0:
-        _lib.check(lib.tem_spoco_pull(ops._p(e), V, ops._p(last), V, E, C, ops._p(means), ops._p(counts),
-                                      float(cfg["delta_var"]), vptr(0), ops._p(S), p, n, stream), "tem_spoco_pull")
+        _lib.launch("tem_spoco_pull", emb_q, _lib.ptr(e), V, _lib.ptr(last), V, E, C, _lib.ptr(means), _lib.ptr(counts),
+                    float(cfg["delta_var"]), vptr(0), _lib.ptr(S), p, n)
     else:
         S.zero_()
-    _lib.check(lib.tem_spoco_means_terms(ops._p(means), C, E, float(cfg["delta_dist"]), int(ignore_zero), vptr(1),
-                                         ops._p(ddist), ops._p(dreg), p, n, stream), "tem_spoco_means_terms")
+    _lib.launch("tem_spoco_means_terms", emb_q, _lib.ptr(means), C, E, float(cfg["delta_dist"]), int(ignore_zero), vptr(1),
+                _lib.ptr(ddist), _lib.ptr(dreg), p, n)
     if with_dice:
-        _lib.check(lib.tem_spoco_instance_dice(ops._p(e), V, ops._p(last), V, nz, E, C, ops._p(means),
-                                               float(cfg["two_sigma"]), 1e-7, vptr(3), p, n, stream),
-                   "tem_spoco_instance_dice")
+        _lib.launch("tem_spoco_instance_dice", emb_q, _lib.ptr(e), V, _lib.ptr(last), V, nz, E, C, _lib.ptr(means),
+                    float(cfg["two_sigma"]), 1e-7, vptr(3), p, n)
     use_push = ignore_zero and C > 1
     if use_push:
         dpush = torch.empty(C, E, dtype=torch.float32, device=dev)
-        _lib.check(lib.tem_spoco_push(ops._p(e), V, ops._p(last), V, E, C, ops._p(means), ops._p(counts),
-                                      float(cfg["delta_dist"]), vptr(4), s * cfg["unlabeled_push_weight"], ops._p(gb), V,
-                                      ops._p(dpush), p, n, stream), "tem_spoco_push")
+        _lib.launch("tem_spoco_push", emb_q, _lib.ptr(e), V, _lib.ptr(last), V, E, C, _lib.ptr(means), _lib.ptr(counts),
+                    float(cfg["delta_dist"]), vptr(4), s * cfg["unlabeled_push_weight"], _lib.ptr(gb), V, _lib.ptr(dpush), p, n)
     inst_w_aff = 0.0
     if with_aff:
         inst_w_aff = cfg["instance_term_weight"] * (cfg["aff_weight"] if aux == "dice_aff" else 1.0)
         _affinity_side(c, e, V, last, D, H, W, E, offsets, ndim, cfg["delta_dist"], vals[5:6], s * inst_w_aff, gb, V)
     if need_grad:
-        _lib.check(lib.tem_spoco_embed_grad(
-            ops._p(e), V, ops._p(last), V, E, C, ops._p(means), ops._p(counts), ops._p(S), ops._p(ddist), ops._p(dreg),
-            ops._p(dpush), float(cfg["delta_var"]), float(max(n_inst, 1)), s * cfg["alpha"] if n_inst > 0 else 0.0,
-            s * cfg["beta"], s * cfg["gamma"], s * cfg["unlabeled_push_weight"] if use_push else 0.0, ops._p(gb), V, 1,
-            p, n, stream), "tem_spoco_embed_grad")
+        _lib.launch("tem_spoco_embed_grad", emb_q, _lib.ptr(e), V, _lib.ptr(last), V, E, C, _lib.ptr(means), _lib.ptr(counts),
+                    _lib.ptr(S), _lib.ptr(ddist), _lib.ptr(dreg), _lib.ptr(dpush), float(cfg["delta_var"]), float(max(n_inst, 1)),
+                    s * cfg["alpha"] if n_inst > 0 else 0.0, s * cfg["beta"], s * cfg["gamma"],
+                    s * cfg["unlabeled_push_weight"] if use_push else 0.0, _lib.ptr(gb), V, 1, p, n)
 
     # ---- consistency term for every sample with enough unlabeled voxels (reference :559-564) ----
     cw = []
@@ -262,12 +238,11 @@ def _evaluate(emb_q, emb_k, target, cfg, need_grad):
                 continue
             rk = torch.tensor(ranks[b], dtype=torch.int64, device=dev)
             idx = torch.empty(A, dtype=torch.int64, device=dev)
-            _lib.check(lib.tem_zero_select(ops._p(target[b, 0]), V, ops._p(chunk_counts[b]), ops._p(rk), A, ops._p(idx),
-                                           stream), "tem_zero_select")
-            _lib.check(lib.tem_spoco_consistency(
-                ops._p(emb_q[b]), ops._p(emb_k[b]), V, V, nz, E, ops._p(idx), A, float(cfg["two_sigma"]), 1e-7,
-                vptr(8 + b), float(cfg["consistency_term_weight"]), ops._p(grad[b]) if need_grad else None, V, p, n,
-                stream), "tem_spoco_consistency")
+            _lib.launch("tem_zero_select", emb_q, _lib.ptr(target[b, 0]), V, _lib.ptr(chunk_counts[b]), _lib.ptr(rk), A,
+                        _lib.ptr(idx))
+            _lib.launch("tem_spoco_consistency", emb_q, _lib.ptr(emb_q[b]), _lib.ptr(emb_k[b]), V, V, nz, E, _lib.ptr(idx), A,
+                        float(cfg["two_sigma"]), 1e-7, vptr(8 + b), float(cfg["consistency_term_weight"]),
+                        _lib.ptr(grad[b]) if need_grad else None, V, p, n)
             cw.append(8 + b)
 
     # ---- combine the device scalars (tiny elementwise ops) ----
@@ -393,17 +368,14 @@ class _ConsistencyFunction(torch.autograd.Function):
         need = emb_q.requires_grad
         grad = torch.zeros_like(q) if need else None
         vals = torch.zeros(N, dtype=torch.float32, device=q.device)
-        with torch.cuda.device(q.device):   # c.stream serves N launches: keep q's device current for all of them
-            c = _Ctx(q, 1, E, V, nz, max_anchors, 0)
-            p, n = c.wsp()
-            for b in range(N):
-                # the reference's mask is all ones (:598), so the rank IS the flat voxel index
-                idx = torch.tensor([int(np.random.randint(V)) for _ in range(max_anchors)], dtype=torch.int64,
-                                   device=q.device)
-                _lib.check(c.lib.tem_spoco_consistency(
-                    ops._p(q[b]), ops._p(k[b]), V, V, nz, E, ops._p(idx), max_anchors, float(two_sigma), 1e-7,
-                    ctypes.c_void_p(vals.data_ptr() + 4 * b), 1.0, ops._p(grad[b]) if need else None, V, p, n, c.stream),
-                    "tem_spoco_consistency")
+        c = _Ctx(q, 1, E, V, nz, max_anchors, 0)
+        p, n = c.wsp()
+        for b in range(N):
+            # the reference's mask is all ones (:598), so the rank IS the flat voxel index
+            idx = torch.tensor([int(np.random.randint(V)) for _ in range(max_anchors)], dtype=torch.int64, device=q.device)
+            _lib.launch("tem_spoco_consistency", q, _lib.ptr(q[b]), _lib.ptr(k[b]), V, V, nz, E, _lib.ptr(idx), max_anchors,
+                        float(two_sigma), 1e-7, ctypes.c_void_p(vals.data_ptr() + 4 * b), 1.0,
+                        _lib.ptr(grad[b]) if need else None, V, p, n)
         ctx.grad = grad
         return vals.sum()
 

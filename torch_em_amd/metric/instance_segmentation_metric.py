@@ -91,7 +91,7 @@ class IOUError:
     def __init__(self, threshold=0.5, metric="precision"):
         if metric not in _STATS:
             raise ValueError(f"IOUError: metric must be one of {_STATS}, got {metric!r}")
-        self.threshold = ops._ov_threshold(threshold)
+        self.threshold = ops.ov_threshold(threshold)
         self.metric = metric
 
     def __call__(self, seg, target):
@@ -222,14 +222,14 @@ class BaseInstanceSegmentationMetric(nn.Module):
         if input_.dim() != target.dim() or input_.dim() not in (4, 5) or len(input_) != len(target):
             raise ValueError(f"expected a prediction [N, C, *spatial] and a target [N, Ct, *spatial], got {tuple(input_.shape)} and "
                              f"{tuple(target.shape)}")
-        ops._req_cuda(input_, target)
+        ops.req_cuda(input_, target)
         before = torch.cuda.get_sync_debug_mode()
         if self.sync_free:
             torch.cuda.set_sync_debug_mode("error")
         try:
             seg = self.segmenter(input_.detach())
             ids = target.detach()[:, -1]
-            if ids.dtype not in ops._OV_LABELS:
+            if ids.dtype not in ops.OV_LABELS:
                 ids = ids.to(torch.int64)
             return self.metric(seg, ids.reshape(seg.shape)).mean()
         finally:

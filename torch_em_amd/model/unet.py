@@ -59,17 +59,16 @@ class AccumulateChannels(nn.Module):
         x = x.float()
         N, C = x.shape[:2]
         V = x[0, 0].numel()
-        nst = ops._ncv_strides(x)
+        nst = ops.ncv_strides(x)
         if nst is None:
             x = x.contiguous()
-            nst = ops._ncv_strides(x)
+            nst = ops.ncv_strides(x)
         sv = nst[2]
         i0, i1 = (0, 0) if self.invariant_channels is None else self.invariant_channels
         c0, c1 = self.accumulate_channels
         out = torch.empty((N, i1 - i0 + 1) + tuple(x.shape[2:]), dtype=torch.float32, device=x.device)
-        _lib.check(_lib.load().tem_accumulate_channels(
-            ops._p(x), x.stride(0), x.stride(1), sv, ops._p(out), N, C, V, i0, i1, c0, c1,
-            {"mean": 0, "min": 1, "max": 2}[self.accumulator], ops._stream(x)), "tem_accumulate_channels")
+        _lib.launch("tem_accumulate_channels", x, _lib.ptr(x), x.stride(0), x.stride(1), sv, _lib.ptr(out), N, C, V, i0, i1, c0, c1,
+                    {"mean": 0, "min": 1, "max": 2}[self.accumulator])
         return out
 
 

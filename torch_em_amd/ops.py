@@ -5,6 +5,12 @@ current HIP stream -- all arithmetic happens in libtem_hip.so.  Activations are 
 channels-last views `t[N, D, H, W, C]` with `t.stride(4) == 1`; `t.stride(3)` (the leading
 dimension `ld`) may exceed C so that a tensor can be a channel slice of a concat buffer.
 There is no CPU fallback: CPU tensors raise.
+
+Every launch is one `_lib.launch("tem_x", t, *args)`: it goes to torch's current stream of the device of `t`, with that
+device current for the call, and a non-zero return code raises.  The helpers without an underscore (`workspace`,
+`to_device`, `is_dense`, `ncv_strides`, `req_cuda`, `stype`, `c_offsets`, `ov_threshold`, `OV_LABELS`) also serve the
+modules that orchestrate their own launches (loss/spoco_loss.py, util/prediction.py, transform/).  `_p`, `_stream` and
+`_workspace` exist for the GPU suites that call the C-ABI themselves; the package does not use them.
 """
 import ctypes
 import math
@@ -14,6 +20,7 @@ from typing import NamedTuple, Optional, Sequence, Tuple
 import torch
 
 from . import _lib
+from ._lib import ptr
 from .arith import Arith, PackKind, pack_is_tiled
 
 ACT = {None: 0, "none": 0, "relu": 1, "sigmoid": 2}
@@ -68,32 +75,19 @@ class _Timed:
         PROFILER.append(((tag, f"{N}x{D}x{H}x{W} {cin}->{cout}"), 2.0 * N * D * H * W * cin * cout * k[0] * k[1] * k[2], self.ev0, ev1))
 
 
-def _stream(t: torch.Tensor):
-    """The stream the launch goes to: torch's current stream of the TENSOR's device.  A HIP launch is issued on the
-    calling thread's current device, so that device is made current for the launch and `_lib.check()` -- which wraps
-    every launch -- restores the caller's (one process drives one GPU in this design; a process that touches several --
-    `DefaultTrainer(device="cuda:1")`, `predict_with_halo(gpu_ids=[1])` -- gets the device of the tensors it passes,
-    like a torch op would, and keeps its own current device)."""
-    _lib.launch_on(t.device.index)
-    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
-
-
-def _p(t: Optional[torch.Tensor]):
-    return None if t is None else ctypes.c_void_p(t.data_ptr())
-
-
 # activation storage types of the C-ABI (TEM_ST_F32 / _F16 / _BF16, include/tem_hip.h): the element type of a tensor handed to
 # the `_st` entry points, and -- shifted into the high bits of `use_mfma` -- to the convolution entry points
 _ST = {torch.float32: 0, torch.float16: 1, torch.bfloat16: 2}
 
 
-def _st(t: Optional[torch.Tensor]) -> int:
+def stype(t: Optional[torch.Tensor]) -> int:
+    """the TEM_ST_* code of a tensor's element type (None: float32)"""
     return 0 if t is None else _ST[t.dtype]
 
 
 def _mode(mfma, x, y) -> int:
     """use_mfma | TEM_MFMA_STX(storage of x) | TEM_MFMA_STY(storage of y)"""
-    return int(mfma) | (_st(x) << 8) | (_st(y) << 12)
+    return int(mfma) | (stype(x) << 8) | (stype(y) << 12)
 
 
 def _same_st(*ts):
@@ -102,7 +96,8 @@ def _same_st(*ts):
         raise ValueError(f"tensors of one call must share their storage type, got {sorted(str(d) for d in sts)}")
 
 
-def _req_cuda(*ts):
+def req_cuda(*ts):
+    """RuntimeError for a tensor on the host (None entries pass)"""
     for t in ts:
         if t is not None and not t.is_cuda:
             raise RuntimeError(
@@ -195,7 +190,7 @@ class Probe:
 # ---------------------------------------------------------------- layout ----
 def nchw_to_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.Tensor:
     """[N, C, *spatial] contiguous -> NDHWC (spatial may be 2-D or 3-D; 2-D gets D == 1)."""
-    _req_cuda(x)
+    req_cuda(x)
     x = x.contiguous()
     N, C = x.shape[:2]
     sp = tuple(x.shape[2:])
@@ -205,17 +200,15 @@ def nchw_to_nhwc(x: torch.Tensor, out: Optional[torch.Tensor] = None) -> torch.T
     if out is None:
         out = new_act(N, D, H, W, C, x.device)
     _, _, _, _, _, ld = _act5(out)
-    lib = _lib.load()
-    _lib.check(lib.tem_nchw_to_nhwc(_p(x), _p(out), ld, N, C, D * H * W, _stream(x)), "tem_nchw_to_nhwc")
+    _lib.launch("tem_nchw_to_nhwc", x, ptr(x), ptr(out), ld, N, C, D * H * W)
     return out
 
 
 def nhwc_to_nchw(x: torch.Tensor) -> torch.Tensor:
-    _req_cuda(x)
+    req_cuda(x)
     N, D, H, W, C, ld = _act5(x)
     out = torch.empty((N, C, D, H, W), dtype=torch.float32, device=x.device)
-    lib = _lib.load()
-    _lib.check(lib.tem_nhwc_to_nchw(_p(x), ld, _p(out), N, C, D * H * W, _stream(x)), "tem_nhwc_to_nchw")
+    _lib.launch("tem_nhwc_to_nchw", x, ptr(x), ld, ptr(out), N, C, D * H * W)
     return out
 
 
@@ -233,15 +226,14 @@ def pack_weights(w: torch.Tensor, transpose: bool, mfma) -> torch.Tensor:
     """state_dict layout [Cout, Cin, (kd,) kh, kw] -> kernel layout (see tem_hip.h).
     mfma: the arithmetic mode whose layout is written (arith.Arith; False / True: VALU / exact fp32) -- a TEM_WL_* layout
     IS the mode it serves."""
-    _req_cuda(w)
+    req_cuda(w)
     w = w.detach().contiguous()
     cout, cin = w.shape[:2]
     k = tuple(w.shape[2:])
     k = (1,) * (3 - len(k)) + k
     lib = _lib.load()
     dst = torch.empty(lib.tem_conv_packed_size(cout, cin, k[0], k[1], k[2]), dtype=torch.float32, device=w.device)
-    _lib.check(lib.tem_conv_pack_weights(_p(w), _p(dst), cout, cin, k[0], k[1], k[2], int(transpose),
-                                         int(Arith(int(mfma))), _stream(w)), "tem_conv_pack_weights")
+    _lib.launch("tem_conv_pack_weights", w, ptr(w), ptr(dst), cout, cin, k[0], k[1], k[2], int(transpose), int(Arith(int(mfma))))
     return dst
 
 
@@ -274,13 +266,10 @@ def pack_table(jobs):
 
 
 def pack_weights_batch(tab):
-    lib = _lib.load()
     if tab["n_tiles"]:
-        _lib.check(lib.tem_conv_pack_weights_tiles(_p(tab["tiles"]), tab["n_tiles"], tab["total_tiles"],
-                                                   _stream(tab["tiles"])), "tem_conv_pack_weights_tiles")
+        _lib.launch("tem_conv_pack_weights_tiles", tab["tiles"], ptr(tab["tiles"]), tab["n_tiles"], tab["total_tiles"])
     if tab["n"]:
-        _lib.check(lib.tem_conv_pack_weights_batch(_p(tab["table"]), tab["n"], tab["total"], _stream(tab["table"])),
-                   "tem_conv_pack_weights_batch")
+        _lib.launch("tem_conv_pack_weights_batch", tab["table"], ptr(tab["table"]), tab["n"], tab["total"])
 
 
 def _launch_fwd(x, x_ld, w_packed, y, y_ld, ref, ref_ld, dims, cin, cout, k, mode, ws_mode, tag, scale=None, shift=None,
@@ -290,12 +279,11 @@ def _launch_fwd(x, x_ld, w_packed, y, y_ld, ref, ref_ld, dims, cin, cout, k, mod
     N, D, H, W = dims
     lib = _lib.load()
     nws = lib.tem_conv3d_fwd_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], ws_mode) if ws_mode is not None else 0
-    ws = _workspace(nws, x.device) if nws else None
+    ws = workspace(nws, x.device) if nws else None
     with _Timed(x, tag, dims, cin, cout, k):
-        _lib.check(lib.tem_conv3d_fwd_ex(_p(x), x_ld, _p(scale), _p(shift), _p(w_packed), _p(bias), _p(y), y_ld, _p(ref),
-                                         ref_ld, _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], ACT[act], mode,
-                                         _p(in_amax), _p(ref_coef), _p(part), part.shape[1] if part is not None else 0,
-                                         x_cs, y_cs, bp.ref() if bp is not None else None, _stream(x)), "tem_conv3d_fwd_ex")
+        _lib.launch("tem_conv3d_fwd_ex", x, ptr(x), x_ld, ptr(scale), ptr(shift), ptr(w_packed), ptr(bias), ptr(y), y_ld, ptr(ref),
+                    ref_ld, ptr(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], ACT[act], mode, ptr(in_amax), ptr(ref_coef),
+                    ptr(part), part.shape[1] if part is not None else 0, x_cs, y_cs, bp.ref() if bp is not None else None)
 
 
 def conv_fwd(x, w_packed, bias, y, k, cin, cout, scale=None, shift=None, act=None, ref=None, mfma=False,
@@ -305,7 +293,7 @@ def conv_fwd(x, w_packed, bias, y, k, cin, cout, scale=None, shift=None, act=Non
     bp: Byproducts of this call (tem_conv3d_fwd_ex), not together with want_stats."""
     if bp is not None and want_stats:
         raise ValueError("conv_fwd: by-products and want_stats exclude each other")
-    _req_cuda(x, w_packed, y)
+    req_cuda(x, w_packed, y)
     N, D, H, W, C, x_ld = _act5(x)
     Ny, Dy, Hy, Wy, Cy, y_ld = _act5(y)
     if C != cin or Cy != cout or (N, D, H, W) != (Ny, Dy, Hy, Wy):
@@ -336,7 +324,7 @@ def conv_fwd(x, w_packed, bias, y, k, cin, cout, scale=None, shift=None, act=Non
 _ws_cache = {}
 
 
-def _workspace(nbytes: int, device) -> torch.Tensor:
+def workspace(nbytes: int, device) -> torch.Tensor:
     """A per-(device, stream) scratch buffer (grown on demand, reused across calls on the same stream; kernels of
     different streams may run concurrently, so they never share one)."""
     device = torch.device(device)
@@ -349,6 +337,17 @@ def _workspace(nbytes: int, device) -> torch.Tensor:
     return buf
 
 
+# For the op-by-op GPU suites only: they call the C-ABI entry points themselves, to look at what one kernel leaves in
+# its buffers, and reach the pointer, the stream and the cached workspace of a tensor under these names.  Nothing in the
+# package uses them; `_stream` only names the stream, it does not touch the current device.
+_p = ptr
+_workspace = workspace
+
+
+def _stream(t: torch.Tensor):
+    return ctypes.c_void_p(torch.cuda.current_stream(t.device).cuda_stream)
+
+
 def conv_wgrad_gnorm_ok(k, cin, cout, mfma) -> bool:
     return bool(_lib.load().tem_conv3d_wgrad_gnorm_ok(cin, cout, k[0], k[1], k[2], int(mfma)))
 
@@ -356,18 +355,17 @@ def conv_wgrad_gnorm_ok(k, cin, cout, mfma) -> bool:
 def conv_wgrad_gnorm(x, g, y, coef, k, cin, cout, dw_out, db_out=None, scale=None, shift=None):
     """First-layer weight gradient with the backward of the norm behind this conv's ReLU applied to g on load
     (tem_conv3d_wgrad_gnorm_st): g raw data gradient, y this conv's output, coef from norm_bwd_coef."""
-    _req_cuda(x, g, y, coef, dw_out)
+    req_cuda(x, g, y, coef, dw_out)
     N, D, H, W, C, x_ld = _act5(x)
     g_ld, y_ld = _act5(g)[5], _act5(y)[5]
     _same_st(g, y)
     lib = _lib.load()
     nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], Arith.VALU)
-    ws = _workspace(nws, x.device)
+    ws = workspace(nws, x.device)
     kind = _wgrad_tag(Arith.VALU, k, cout) if PROFILER is not None else None
     with _Timed(x, kind, (N, D, H, W), cin, cout, k):
-        _lib.check(lib.tem_conv3d_wgrad_gnorm_st(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(y), y_ld, _p(coef), _p(dw_out),
-                                                 _p(db_out), _p(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], 1, _st(x), _st(g),
-                                                 _stream(x)), "tem_conv3d_wgrad_gnorm_st")
+        _lib.launch("tem_conv3d_wgrad_gnorm_st", x, ptr(x), x_ld, ptr(scale), ptr(shift), ptr(g), g_ld, ptr(y), y_ld, ptr(coef),
+                    ptr(dw_out), ptr(db_out), ptr(ws), nws, N, D, H, W, cin, cout, k[0], k[1], k[2], 1, stype(x), stype(g))
 
 
 def conv_wgrad_sums_ok(x, k, cin, cout, mfma) -> bool:
@@ -385,7 +383,7 @@ def _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, arith, mode,
         raise ValueError("conv_wgrad: channel mismatch")
     lib = _lib.load()
     nws = lib.tem_conv3d_wgrad_ws(N, D, H, W, cin, cout, k[0], k[1], k[2], mode)
-    ws = _workspace(nws, x.device)
+    ws = workspace(nws, x.device)
     w = gamma = beta = sums = None
     if sums_from is not None:
         w, gamma, beta = sums_from
@@ -393,10 +391,9 @@ def _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, arith, mode,
         sums = torch.empty((N, cin, 2), dtype=torch.float32, device=x.device)
     kind = _wgrad_tag(arith, k, cout) if PROFILER is not None else None
     with _Timed(x, kind, (N, D, H, W), cin, cout, k):
-        _lib.check(lib.tem_conv3d_wgrad_ex(_p(x), x_ld, _p(scale), _p(shift), _p(g), g_ld, _p(w), _p(gamma), _p(beta),
-                                           _p(dw_out), _p(db_out), _p(sums), _p(amax_in), _p(amax_out), _p(ws), nws, N, D, H, W,
-                                           cin, cout, k[0], k[1], k[2], mode, x_cs, bp.ref() if bp is not None else None,
-                                           _stream(x)), "tem_conv3d_wgrad_ex")
+        _lib.launch("tem_conv3d_wgrad_ex", x, ptr(x), x_ld, ptr(scale), ptr(shift), ptr(g), g_ld, ptr(w), ptr(gamma), ptr(beta),
+                    ptr(dw_out), ptr(db_out), ptr(sums), ptr(amax_in), ptr(amax_out), ptr(ws), nws, N, D, H, W, cin, cout, k[0],
+                    k[1], k[2], mode, x_cs, bp.ref() if bp is not None else None)
     return sums
 
 
@@ -410,13 +407,13 @@ def conv_wgrad(x, g, k, cin, cout, dw_out, db_out=None, scale=None, shift=None, 
 
 def _conv_wgrad(x, g, k, cin, cout, dw_out, db_out=None, scale=None, shift=None, mfma=False):
     """dw_out: flat [ntaps*cin*cout] in the reference's [Cout,Cin,kd,kh,kw] order; db_out: [cout]."""
-    _req_cuda(x, g, dw_out)
+    req_cuda(x, g, dw_out)
     _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, mfma, _mode(mfma, x, g), x_cs=_cs(x), match_channels=True)
     return dw_out
 
 
 def _conv_wgrad_sums(x, g, k, cin, cout, dw_out, db_out, scale, shift, mfma, sums_from, bp=None):
-    _req_cuda(x, g, dw_out, db_out)
+    req_cuda(x, g, dw_out, db_out)
     return _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, mfma, _mode(mfma, x, g), sums_from=sums_from,
                          x_cs=_cs(x), bp=bp)
 
@@ -429,7 +426,7 @@ def conv_wgrad_gmax_ok(x, k, cin, cout, mfma) -> bool:
 def conv_wgrad_gmax(x, g, k, cin, cout, dw_out, db_out, gmax, scale=None, shift=None, mfma=Arith.BF16X3, sums_from=None, bp=None):
     """conv_wgrad that also leaves the bit pattern of max |g| in `gmax` (int32[1], cleared by the caller) -- the prescale
     of the fp16 two-term data gradient (conv_fwd_gscaled).  sums_from as in conv_wgrad -> sums[N, cin, 2] or None."""
-    _req_cuda(x, g, dw_out, gmax)
+    req_cuda(x, g, dw_out, gmax)
     return _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, mfma, int(mfma), sums_from=sums_from, amax_out=gmax, bp=bp)
 
 
@@ -440,17 +437,16 @@ def conv1x1_out_bwd_ok(cin, cout) -> bool:
 def conv1x1_out_bwd(x, g, w, gx, dw_out, db_out=None, out_amax=None):
     """Backward of the output projection in one pass over its input x (tem_conv1x1_out_bwd_st): dw [cout, cin, 1, 1, 1]-ordered, db,
     and gx = (x > 0) * (g . w).  x, gx: [N, D, H, W, cin(ld)]; g: [N, D, H, W, cout(ld)]; w: the conv's weight (state_dict)."""
-    _req_cuda(x, g, w, gx, dw_out)
+    req_cuda(x, g, w, gx, dw_out)
     N, D, H, W, cin, x_ld = _act5(x)
     cout, g_ld = _act5(g)[4], _act5(g)[5]
     gx_ld = _act5(gx)[5]
     lib = _lib.load()
     nws = lib.tem_conv1x1_out_bwd_ws(cin, cout)
-    ws = _workspace(nws, x.device)
+    ws = workspace(nws, x.device)
     _same_st(x, gx)
-    _lib.check(lib.tem_conv1x1_out_bwd_st(_p(x), x_ld, _p(g), g_ld, _p(w.detach()), _p(gx), gx_ld, _p(dw_out), _p(db_out),
-                                          _p(ws), nws, N * D * H * W, cin, cout, _p(out_amax), _st(x), _st(g), _stream(x)),
-               "tem_conv1x1_out_bwd_st")
+    _lib.launch("tem_conv1x1_out_bwd_st", x, ptr(x), x_ld, ptr(g), g_ld, ptr(w.detach()), ptr(gx), gx_ld, ptr(dw_out), ptr(db_out),
+                ptr(ws), nws, N * D * H * W, cin, cout, ptr(out_amax), stype(x), stype(g))
     return gx
 
 
@@ -468,11 +464,11 @@ def conv_wgrad_cs_ok(x, k, cin, cout, x_cs) -> bool:
 def absmax(x, amax=None):
     """bit pattern of max |x| of an activation tensor [N, D, H, W, C(ld)] -> int32[1] on the device (tem_absmax);
     `amax` (cleared by the caller) accumulates when given."""
-    _req_cuda(x)
+    req_cuda(x)
     N, D, H, W, C, ld = _act5(x)
     if amax is None:
         amax = torch.zeros(1, dtype=torch.int32, device=x.device)
-    _lib.check(_lib.load().tem_absmax(_p(x), ld, C, N * D * H * W, _p(amax), _stream(x)), "tem_absmax")
+    _lib.launch("tem_absmax", x, ptr(x), ld, C, N * D * H * W, ptr(amax))
     return amax
 
 
@@ -488,14 +484,14 @@ class Byproducts:
     def __init__(self, out_amax=None, norm_coef=None, norm_sums=None):
         c = _lib.Byproducts()
         self._keep = (out_amax, norm_coef, norm_sums)
-        c.out_amax = _p(out_amax)
+        c.out_amax = ptr(out_amax)
         if norm_coef is not None:
             groups, mean, rstd, coef = norm_coef
-            c.coef_G, c.coef_mean, c.coef_rstd, c.coef = int(groups), _p(mean), _p(rstd), _p(coef)
+            c.coef_G, c.coef_mean, c.coef_rstd, c.coef = int(groups), ptr(mean), ptr(rstd), ptr(coef)
         if norm_sums is not None:
             x, groups, mean, rstd, part = norm_sums
-            c.sums_x, c.sums_x_ld, c.sums_mean, c.sums_rstd = _p(x), _act5(x)[5], _p(mean), _p(rstd)
-            c.sums_G, c.sums_part, c.sums_nblk = int(groups), _p(part), part.shape[1]
+            c.sums_x, c.sums_x_ld, c.sums_mean, c.sums_rstd = ptr(x), _act5(x)[5], ptr(mean), ptr(rstd)
+            c.sums_G, c.sums_part, c.sums_nblk = int(groups), ptr(part), part.shape[1]
         self.c = c
 
     def ref(self):
@@ -509,7 +505,7 @@ class Byproducts:
 def conv_wgrad_gscaled(x, g, k, cin, cout, dw_out, db_out, amax, scale=None, shift=None, sums_from=None, bp=None):
     """Weight gradient in the fp16 2x1 arithmetic (g_amax_in of tem_conv3d_wgrad_ex): x^ two fp16 terms, g one fp16 term prescaled
     from amax = int32[1] with the bit pattern of max |g| (absmax or a producer of g).  sums_from as in conv_wgrad."""
-    _req_cuda(x, g, dw_out, amax)
+    req_cuda(x, g, dw_out, amax)
     return _launch_wgrad(x, g, k, cin, cout, dw_out, db_out, scale, shift, Arith.F16X2, Arith.F16X2, sums_from=sums_from,
                          amax_in=amax, bp=bp)
 
@@ -517,7 +513,7 @@ def conv_wgrad_gscaled(x, g, k, cin, cout, dw_out, db_out, amax, scale=None, shi
 def conv_fwd_gscaled(x, w_packed, y, k, cin, cout, amax, ref=None, bp=None):
     """Data gradient with fp32-class products (in_amax of tem_conv3d_fwd_ex): x an unnormalised gradient, w_packed =
     pack_weights(w, transpose=True, mfma=Arith.F16X3), amax = int32[1] holding the bit pattern of max |x| (conv_wgrad_gmax)."""
-    _req_cuda(x, w_packed, y, amax)
+    req_cuda(x, w_packed, y, amax)
     N, D, H, W, C, x_ld = _act5(x)
     Ny, Dy, Hy, Wy, Cy, y_ld = _act5(y)
     if C != cin or Cy != cout or (N, D, H, W) != (Ny, Dy, Hy, Wy):
@@ -532,7 +528,7 @@ def conv_fwd_gscaled(x, w_packed, y, k, cin, cout, amax, ref=None, bp=None):
 def conv_fwd_refnorm(x, w_packed, y, k, cin, cout, ref, coef, mfma, bp=None):
     """Data gradient that lands behind a ReLU + norm (ref_coef of tem_conv3d_fwd_ex): y = ref > 0 ? a*conv(x) - m1 - (ref - mean)*m2r
     : 0, coef [N, cout, 4] from norm_bwd_coef.  Only where conv_fwd_family(...) == 3."""
-    _req_cuda(x, w_packed, y, ref, coef)
+    req_cuda(x, w_packed, y, ref, coef)
     N, D, H, W, C, x_ld = _act5(x)
     Ny, Dy, Hy, Wy, Cy, y_ld = _act5(y)
     if C != cin or Cy != cout or (N, D, H, W) != (Ny, Dy, Hy, Wy) or tuple(coef.shape) != (N, cout, 4) or \
@@ -584,16 +580,16 @@ def _stats_out(rows, groups, C, dev):
 
 def norm_stats(x, groups: int, gamma=None, beta=None, eps: float = 1e-5):
     """-> (mean[N,G], rstd[N,G], scale[N,C], shift[N,C])"""
-    _req_cuda(x)
+    req_cuda(x)
     N, D, H, W, C, ld = _act5(x)
     dev = x.device
     mean, rstd, scale, shift = _stats_out(N, groups, C, dev)
     lib = _lib.load()
     V = D * H * W
     nws = lib.tem_norm_ws(N, V, C)
-    ws = _workspace(nws, dev)
-    _lib.check(lib.tem_norm_stats_st(_p(x), ld, N, V, C, groups, _p(gamma), _p(beta), eps, _p(mean), _p(rstd), _p(scale),
-                                     _p(shift), _p(ws), nws, _st(x), _stream(x)), "tem_norm_stats_st")
+    ws = workspace(nws, dev)
+    _lib.launch("tem_norm_stats_st", x, ptr(x), ld, N, V, C, groups, ptr(gamma), ptr(beta), eps, ptr(mean), ptr(rstd), ptr(scale),
+                ptr(shift), ptr(ws), nws, stype(x))
     return mean, rstd, scale, shift
 
 
@@ -601,7 +597,7 @@ def norm_stats_from_partials(part, rows: int, voxels: int, C: int, groups: int, 
                              eps: float = 1e-5):
     """Second stage of norm_stats on partial sums written by conv_fwd(want_stats=True).  part: [N, nblk, C, 2];
     rows = N for per-sample statistics, 1 for BatchNorm (then every sample's blocks merge into one row)."""
-    _req_cuda(part)
+    req_cuda(part)
     N, nblk = part.shape[0], part.shape[1]
     if rows == 1:
         nblk, voxels = N * nblk, N * voxels
@@ -609,10 +605,8 @@ def norm_stats_from_partials(part, rows: int, voxels: int, C: int, groups: int, 
         raise ValueError("norm_stats_from_partials: rows must be N or 1")
     dev = part.device
     mean, rstd, scale, shift = _stats_out(rows, groups, C, dev)
-    lib = _lib.load()
-    _lib.check(lib.tem_norm_finalize_partials(_p(part), nblk, rows, voxels, C, groups, _p(gamma), _p(beta), eps,
-                                              _p(mean), _p(rstd), _p(scale), _p(shift), _stream(part)),
-               "tem_norm_finalize_partials")
+    _lib.launch("tem_norm_finalize_partials", part, ptr(part), nblk, rows, voxels, C, groups, ptr(gamma), ptr(beta), eps, ptr(mean),
+                ptr(rstd), ptr(scale), ptr(shift))
     return mean, rstd, scale, shift
 
 
@@ -621,16 +615,16 @@ def _launch_norm_bwd(gy, gy_ld, x, x_ld, N, V, C, groups, gamma, mean, rstd, rel
     [N, nblk, C, 2] from a data gradient (Byproducts.norm_sums); coef: reduction only -> coef [N, C, 4], gx is not written."""
     lib = _lib.load()
     nws = lib.tem_norm_ws(N, V, C)
-    ws = _workspace(nws, x.device)
+    ws = workspace(nws, x.device)
     nrow = 0 if sums is None else (sums.shape[1] if sums.dim() == 4 else 1)
-    _lib.check(lib.tem_norm_bwd_st(_p(gy), gy_ld, _p(x), x_ld, N, V, C, groups, _p(gamma), _p(mean), _p(rstd), int(relu_mask),
-                                   _p(gx), gx_ld, _p(dgamma), _p(dbeta), _p(sums), nrow, _p(coef), _p(out_amax), _p(ws), nws, _st(x),
-                                   _stream(x)), "tem_norm_bwd_st")
+    _lib.launch("tem_norm_bwd_st", x, ptr(gy), gy_ld, ptr(x), x_ld, N, V, C, groups, ptr(gamma), ptr(mean), ptr(rstd),
+                int(relu_mask), ptr(gx), gx_ld, ptr(dgamma), ptr(dbeta), ptr(sums), nrow, ptr(coef), ptr(out_amax), ptr(ws), nws,
+                stype(x))
 
 
 def norm_bwd_coef(gy, x, groups, gamma, mean, rstd, dgamma=None, dbeta=None, sums=None):
     """Reduction stage of norm_bwd only -> coef[N, C, 4] = (a, m1, m2r, mean) per (sample, channel)."""
-    _req_cuda(gy, x)
+    req_cuda(gy, x)
     if isinstance(x, Planar) and sums is None:
         # no producer delivered the sums: reduce each dense half on its own (groups never straddle the halves: 32 % (C / G) == 0)
         cg = 64 // groups
@@ -653,7 +647,7 @@ def norm_bwd_coef(gy, x, groups, gamma, mean, rstd, dgamma=None, dbeta=None, sum
 def norm_bwd(gy, x, groups, gamma, mean, rstd, relu_mask: bool, gx, dgamma=None, dbeta=None, sums=None, out_amax=None):
     """sums: [N, C, 2] from conv_wgrad(sums_from=...) -- skips the reduction pass over gy and x;
     out_amax: int32[1] (cleared by the caller) that receives the bit pattern of max |gx|"""
-    _req_cuda(gy, x, gx)
+    req_cuda(gy, x, gx)
     N, D, H, W, C, x_ld = _act5(x)
     gy_ld = _act5(gy)[5]
     gx_ld = _act5(gx)[5]
@@ -673,7 +667,7 @@ def maxpool_fwd(x, y, f, want_stats=False):
     """want_stats: also return (partials [N, nblk, C, 2], nblk) -- the first stage of the statistics of y (what
     conv_fwd(want_stats=True) returns for a conv output; stat_part of tem_maxpool3d_fwd_st) -- or None when this channel count
     cannot."""
-    _req_cuda(x, y)
+    req_cuda(x, y)
     N, D, H, W, C, x_ld = _act5(x)
     y_ld = _act5(y)[5]
     lib = _lib.load()
@@ -682,8 +676,8 @@ def maxpool_fwd(x, y, f, want_stats=False):
     part = None
     if nblk > 0 and _rows_vec4(x, x_ld, y, y_ld):
         part = torch.empty((N, nblk, C, 2), dtype=torch.float32, device=x.device)
-    _lib.check(lib.tem_maxpool3d_fwd_st(_p(x), x_ld, _p(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part),
-                                        nblk if part is not None else 0, _st(x), _stream(x)), "tem_maxpool3d_fwd_st")
+    _lib.launch("tem_maxpool3d_fwd_st", x, ptr(x), x_ld, ptr(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], ptr(part),
+                nblk if part is not None else 0, stype(x))
     if want_stats:
         return None if part is None else (part, nblk)
     return y
@@ -693,19 +687,17 @@ def maxpool_bwd(gy, x, gx, f, gskip=None, relu_mask=False, gskip_coef=None, gy_c
     """gskip_coef: [N, C, 4] view (row stride = multiple of 4 floats) of norm_bwd_coef() -- gskip is then the raw data
     gradient behind that norm and the norm backward is applied on the fly (gcoef of tem_maxpool3d_bwd_st).
     gy_coef: dense [N, C, 4] coefficients of the norm whose input is the pooled tensor (gy raw as well)."""
-    _req_cuda(gy, x, gx)
+    req_cuda(gy, x, gx)
     N, D, H, W, C, x_ld = _act5(x)
     gy_ld = _act5(gy)[5]
     gx_ld = _act5(gx)[5]
     gs_ld = _act5(gskip)[5] if gskip is not None else 0
-    lib = _lib.load()
     if gy_coef is not None and not gy_coef.is_contiguous():
         raise ValueError("maxpool_bwd: gy_coef must be contiguous")
     _same_st(gy, x, gx, gskip)
-    _lib.check(lib.tem_maxpool3d_bwd_st(_p(gy), gy_ld, _p(x), x_ld, _p(gskip), gs_ld, int(relu_mask), _p(gx), gx_ld,
-                                        N, D, H, W, C, f[0], f[1], f[2], _p(gskip_coef),
-                                        gskip_coef.stride(0) if gskip_coef is not None else 0, _p(gy_coef), _p(out_amax), _st(x),
-                                        _stream(x)), "tem_maxpool3d_bwd_st")
+    _lib.launch("tem_maxpool3d_bwd_st", x, ptr(gy), gy_ld, ptr(x), x_ld, ptr(gskip), gs_ld, int(relu_mask), ptr(gx), gx_ld, N, D, H,
+                W, C, f[0], f[1], f[2], ptr(gskip_coef), gskip_coef.stride(0) if gskip_coef is not None else 0, ptr(gy_coef),
+                ptr(out_amax), stype(x))
     return gx
 
 
@@ -713,7 +705,7 @@ def upsample_fwd(x, y, f, stats: bool = False):
     """y = interpolate(x, scale_factor=f, trilinear).  stats=True: also return the first stage of y's statistics,
     part [N, D*H, C, 2] (part of tem_upsample_fwd_st), or None when the factor-2 kernel does not take the shape -- then
     `upsample_stats` derives them from x."""
-    _req_cuda(x, y)
+    req_cuda(x, y)
     N, D, H, W, C, x_ld = _act5(x)
     y_ld = _act5(y)[5]
     lib = _lib.load()
@@ -721,8 +713,7 @@ def upsample_fwd(x, y, f, stats: bool = False):
     part = None
     if stats and lib.tem_upsample_fwd_stats_ok(C, f[0], f[1], f[2]) and _rows_vec4(x, x_ld, y, y_ld):
         part = torch.empty((N, D * H, C, 2), dtype=torch.float32, device=x.device)
-    _lib.check(lib.tem_upsample_fwd_st(_p(x), x_ld, _p(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part), _st(x),
-                                       _stream(x)), "tem_upsample_fwd_st")
+    _lib.launch("tem_upsample_fwd_st", x, ptr(x), x_ld, ptr(y), y_ld, N, D, H, W, C, f[0], f[1], f[2], ptr(part), stype(x))
     return part if stats else y
 
 
@@ -734,11 +725,10 @@ def upsample_stats_ok(u) -> bool:
 
 def upsample_stats(u, f):
     """First stage of the statistics of upsample(u, f), from u alone -> part [N, D*H, C, 2] (tem_upsample_stats_st)."""
-    _req_cuda(u)
+    req_cuda(u)
     N, D, H, W, C, u_ld = _act5(u)
     part = torch.empty((N, D * H, C, 2), dtype=torch.float32, device=u.device)
-    _lib.check(_lib.load().tem_upsample_stats_st(_p(u), u_ld, N, D, H, W, C, f[0], f[1], f[2], _p(part), _st(u), _stream(u)),
-               "tem_upsample_stats_st")
+    _lib.launch("tem_upsample_stats_st", u, ptr(u), u_ld, N, D, H, W, C, f[0], f[1], f[2], ptr(part), stype(u))
     return part
 
 
@@ -746,7 +736,7 @@ def norm_stats_from_partials2(part_a, part_b, rows: int, voxels: int, groups: in
                               eps: float = 1e-5):
     """norm_stats of a channel-concatenated tensor: channels [0, CA) summarised by part_a [N, nblkA, CA, 2], the rest by
     part_b [N, nblkB, CB, 2] (tem_norm_finalize_partials2).  rows = N, or 1 for BatchNorm."""
-    _req_cuda(part_a, part_b)
+    req_cuda(part_a, part_b)
     N, nba, ca = part_a.shape[0], part_a.shape[1], part_a.shape[2]
     nbb, cb = part_b.shape[1], part_b.shape[2]
     C = ca + cb
@@ -756,39 +746,35 @@ def norm_stats_from_partials2(part_a, part_b, rows: int, voxels: int, groups: in
         raise ValueError("norm_stats_from_partials2: rows must be N or 1")
     dev = part_a.device
     mean, rstd, scale, shift = _stats_out(rows, groups, C, dev)
-    lib = _lib.load()
-    _lib.check(lib.tem_norm_finalize_partials2(_p(part_a), nba, ca, _p(part_b), nbb, rows, voxels, C, groups, _p(gamma),
-                                               _p(beta), eps, _p(mean), _p(rstd), _p(scale), _p(shift), _stream(part_a)),
-               "tem_norm_finalize_partials2")
+    _lib.launch("tem_norm_finalize_partials2", part_a, ptr(part_a), nba, ca, ptr(part_b), nbb, rows, voxels, C, groups, ptr(gamma),
+                ptr(beta), eps, ptr(mean), ptr(rstd), ptr(scale), ptr(shift))
     return mean, rstd, scale, shift
 
 
 def upsample_bwd(gy, gx, f, norm=None):
     """gx has the low-resolution shape; gy = gx's shape scaled by f.
     norm = (u, coef[N, C, 4] view): gy is the raw data gradient behind a norm whose input was upsample(u)."""
-    _req_cuda(gy, gx)
+    req_cuda(gy, gx)
     N, D, H, W, C, gx_ld = _act5(gx)
     gy_ld = _act5(gy)[5]
     u, coef = norm if norm is not None else (None, None)
     _same_st(gy, gx, u)
-    _lib.check(_lib.load().tem_upsample_bwd_st(_p(gy), gy_ld, _p(gx), gx_ld, N, D, H, W, C, f[0], f[1], f[2], _p(u),
-                                               _act5(u)[5] if u is not None else 0, _p(coef), coef.stride(0) if coef is not None else 0,
-                                               _st(gy), _stream(gx)), "tem_upsample_bwd_st")
+    _lib.launch("tem_upsample_bwd_st", gx, ptr(gy), gy_ld, ptr(gx), gx_ld, N, D, H, W, C, f[0], f[1], f[2], ptr(u),
+                _act5(u)[5] if u is not None else 0, ptr(coef), coef.stride(0) if coef is not None else 0, stype(gy))
     return gx
 
 
 def act_bwd(gy, y, act: str):
-    _req_cuda(gy, y)
+    req_cuda(gy, y)
     gy = gy.contiguous()
     y = y.contiguous()
     gx = torch.empty_like(gy)
-    lib = _lib.load()
-    _lib.check(lib.tem_act_bwd(_p(gy), _p(y), _p(gx), gy.numel(), ACT[act], _stream(gy)), "tem_act_bwd")
+    _lib.launch("tem_act_bwd", gy, ptr(gy), ptr(y), ptr(gx), gy.numel(), ACT[act])
     return gx
 
 
 # ------------------------------------------------------------------ dice ----
-def _ncv_strides(t: torch.Tensor):
+def ncv_strides(t: torch.Tensor):
     """(sn, sc, sv, N, C, V) for a logical [N, C, *spatial] tensor whose spatial dims are
     jointly contiguous up to a common voxel stride; returns None if not expressible."""
     N, C = t.shape[:2]
@@ -809,26 +795,26 @@ def _ncv_strides(t: torch.Tensor):
 
 def dice_sums(p, t, mask=None) -> torch.Tensor:
     """-> double[C, 3] = (sum p*t, sum p*p, sum t*t) with optional multiplicative mask."""
-    _req_cuda(p, t)
-    ps = _ncv_strides(p)
+    req_cuda(p, t)
+    ps = ncv_strides(p)
     if ps is None:
         p = p.contiguous()
-        ps = _ncv_strides(p)
-    ts = _ncv_strides(t)
+        ps = ncv_strides(p)
+    ts = ncv_strides(t)
     if ts is None:
         t = t.contiguous()
-        ts = _ncv_strides(t)
+        ts = ncv_strides(t)
     if mask is not None:
-        ms = _ncv_strides(mask)
+        ms = ncv_strides(mask)
         if ms is None or ms[:3] != ts[:3]:
             raise ValueError("dice: mask must share the target's strides")
     N, C, V = ps[3:]
     sums = torch.empty((C, 3), dtype=torch.float64, device=p.device)
     lib = _lib.load()
     nws = lib.tem_dice_ws(N, V, C)
-    ws = _workspace(nws, p.device)
-    _lib.check(lib.tem_dice_sums(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], _p(mask), N, C, V,
-                                 _p(sums), _p(ws), nws, _stream(p)), "tem_dice_sums")
+    ws = workspace(nws, p.device)
+    _lib.launch("tem_dice_sums", p, ptr(p), ps[0], ps[1], ps[2], ptr(t), ts[0], ts[1], ts[2], ptr(mask), N, C, V, ptr(sums),
+                ptr(ws), nws)
     return sums, p, t
 
 
@@ -839,23 +825,23 @@ DICE_LOGITS, DICE_BCE = 1, 2
 def dice_sums2(p, t, flags: int):
     """dice_sums for the logits / BCE members of the family (tem_dice_sums2): double[C, 3] or, with DICE_BCE, [C, 4]
     (4th column: summed binary cross entropy of the channel)."""
-    _req_cuda(p, t)
-    ps = _ncv_strides(p)
+    req_cuda(p, t)
+    ps = ncv_strides(p)
     if ps is None:
         p = p.contiguous()
-        ps = _ncv_strides(p)
-    ts = _ncv_strides(t)
+        ps = ncv_strides(p)
+    ts = ncv_strides(t)
     if ts is None:
         t = t.contiguous()
-        ts = _ncv_strides(t)
+        ts = ncv_strides(t)
     N, C, V = ps[3:]
     ncol = 4 if flags & DICE_BCE else 3
     sums = torch.empty((C, ncol), dtype=torch.float64, device=p.device)
     lib = _lib.load()
     nws = lib.tem_dice_ws(N, V, C)
-    ws = _workspace(nws, p.device)
-    _lib.check(lib.tem_dice_sums2(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], N, C, V, _p(sums), _p(ws), nws,
-                                  int(flags), _stream(p)), "tem_dice_sums2")
+    ws = workspace(nws, p.device)
+    _lib.launch("tem_dice_sums2", p, ptr(p), ps[0], ps[1], ps[2], ptr(t), ts[0], ts[1], ts[2], N, C, V, ptr(sums), ptr(ws), nws,
+                int(flags))
     return sums, p, t
 
 
@@ -866,14 +852,14 @@ def dice_finalize2(sums, eps, channelwise, invert, reduce):
     out = torch.empty((n_out,), dtype=torch.float32, device=dev)
     ca = torch.empty((C,), dtype=torch.float32, device=dev)
     cb = torch.empty((C,), dtype=torch.float32, device=dev)
-    _lib.check(_lib.load().tem_dice_finalize2(_p(sums), ncol, C, float(eps), int(channelwise), int(invert), REDUCE[reduce],
-                                              _p(out), _p(ca), _p(cb), _stream(sums)), "tem_dice_finalize2")
+    _lib.launch("tem_dice_finalize2", sums, ptr(sums), ncol, C, float(eps), int(channelwise), int(invert), REDUCE[reduce], ptr(out),
+                ptr(ca), ptr(cb))
     return out, ca, cb
 
 
 def dice_grad2(p, t, ca, cb, gout, gout_per_channel, channels_last: bool, flags: int, w_dice: float, w_bce: float):
-    ps = _ncv_strides(p)
-    ts = _ncv_strides(t)
+    ps = ncv_strides(p)
+    ts = ncv_strides(t)
     N, C, V = ps[3:]
     if channels_last:
         gp_phys = torch.empty((N,) + tuple(p.shape[2:]) + (C,), dtype=torch.float32, device=p.device)
@@ -882,9 +868,8 @@ def dice_grad2(p, t, ca, cb, gout, gout_per_channel, channels_last: bool, flags:
     else:
         gp = torch.empty(p.shape, dtype=torch.float32, device=p.device)
         gs = (C * V, V, 1)
-    _lib.check(_lib.load().tem_dice_grad2(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], _p(ca), _p(cb), _p(gout),
-                                          int(gout_per_channel), _p(gp), gs[0], gs[1], gs[2], N, C, V, int(flags),
-                                          float(w_dice), float(w_bce), _stream(p)), "tem_dice_grad2")
+    _lib.launch("tem_dice_grad2", p, ptr(p), ps[0], ps[1], ps[2], ptr(t), ts[0], ts[1], ts[2], ptr(ca), ptr(cb), ptr(gout),
+                int(gout_per_channel), ptr(gp), gs[0], gs[1], gs[2], N, C, V, int(flags), float(w_dice), float(w_bce))
     return gp
 
 
@@ -895,16 +880,15 @@ def dice_finalize(sums, eps, channelwise, invert, reduce):
     out = torch.empty((n_out,), dtype=torch.float32, device=dev)
     ca = torch.empty((C,), dtype=torch.float32, device=dev)
     cb = torch.empty((C,), dtype=torch.float32, device=dev)
-    lib = _lib.load()
-    _lib.check(lib.tem_dice_finalize(_p(sums), C, float(eps), int(channelwise), int(invert), REDUCE[reduce], _p(out),
-                                     _p(ca), _p(cb), _stream(sums)), "tem_dice_finalize")
+    _lib.launch("tem_dice_finalize", sums, ptr(sums), C, float(eps), int(channelwise), int(invert), REDUCE[reduce], ptr(out),
+                ptr(ca), ptr(cb))
     return out, ca, cb
 
 
 def dice_grad(p, t, mask, ca, cb, gout, gout_per_channel, channels_last: bool):
     """d out / d p, laid out like p (channels_last_3d memory format when p has it)."""
-    ps = _ncv_strides(p)
-    ts = _ncv_strides(t)
+    ps = ncv_strides(p)
+    ts = ncv_strides(t)
     N, C, V = ps[3:]
     if channels_last:
         # physical [N, V, C]
@@ -914,35 +898,33 @@ def dice_grad(p, t, mask, ca, cb, gout, gout_per_channel, channels_last: bool):
     else:
         gp = torch.empty(p.shape, dtype=torch.float32, device=p.device)
         gs = (C * V, V, 1)
-    lib = _lib.load()
-    _lib.check(lib.tem_dice_grad(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], _p(mask), _p(ca), _p(cb),
-                                 _p(gout), int(gout_per_channel), _p(gp), gs[0], gs[1], gs[2], N, C, V, _stream(p)),
-               "tem_dice_grad")
+    _lib.launch("tem_dice_grad", p, ptr(p), ps[0], ps[1], ps[2], ptr(t), ts[0], ts[1], ts[2], ptr(mask), ptr(ca), ptr(cb),
+                ptr(gout), int(gout_per_channel), ptr(gp), gs[0], gs[1], gs[2], N, C, V)
     return gp
 
 
 def dice_sums_pair(p, t, mask):
     """-> (double[2, C, 3], p, t): `dice_sums(p, t, mask)[0]` and `dice_sums(p, t)[0]` from ONE pass over prediction, target
     and mask (tem_dice_sums_pair) -- bit for bit what the two calls give.  For passes that need no gradient."""
-    _req_cuda(p, t, mask)
-    ps = _ncv_strides(p)
+    req_cuda(p, t, mask)
+    ps = ncv_strides(p)
     if ps is None:
         p = p.contiguous()
-        ps = _ncv_strides(p)
-    ts = _ncv_strides(t)
+        ps = ncv_strides(p)
+    ts = ncv_strides(t)
     if ts is None:
         t = t.contiguous()
-        ts = _ncv_strides(t)
-    ms = _ncv_strides(mask)
+        ts = ncv_strides(t)
+    ms = ncv_strides(mask)
     if ms is None or ms[:3] != ts[:3]:
         raise ValueError("dice: mask must share the target's strides")
     N, C, V = ps[3:]
     sums = torch.empty((2, C, 3), dtype=torch.float64, device=p.device)
     lib = _lib.load()
     nws = 2 * lib.tem_dice_ws(N, V, C)
-    ws = _workspace(nws, p.device)
-    _lib.check(lib.tem_dice_sums_pair(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], _p(mask), N, C, V,
-                                      _p(sums), _p(ws), nws, _stream(p)), "tem_dice_sums_pair")
+    ws = workspace(nws, p.device)
+    _lib.launch("tem_dice_sums_pair", p, ptr(p), ps[0], ps[1], ps[2], ptr(t), ts[0], ts[1], ts[2], ptr(mask), N, C, V, ptr(sums),
+                ptr(ws), nws)
     return sums, p, t
 
 
@@ -950,7 +932,7 @@ def dice_sums_pair(p, t, mask):
 PL_MASK_NONE, PL_MASK_BOTH, PL_MASK_ONE = 0, 1, 2   # mask_mode of tem_pseudo_label_st (include/tem_hip.h)
 
 
-def _is_dense(t: torch.Tensor) -> bool:
+def is_dense(t: torch.Tensor) -> bool:
     """the elements of t fill one block of storage without gaps or overlap, in whatever order of the axes"""
     expect = 1
     for stride, size in sorted((st, sz) for st, sz in zip(t.stride(), t.shape) if sz != 1):
@@ -974,7 +956,7 @@ def pseudo_label(x: torch.Tensor, activation: Optional[str] = None, confidence_t
     as they are.  `mask_sample=k`: every sample gets sample k's mask (the reference's `mask_channel` slices the batch axis).
     `out=(labels, mask)` is a TEST HOOK (no library caller uses it): write into these tensors (x's shape and strides; an entry
     that is not produced is None), so a test can lay the outputs out between guard zones and poison them first."""
-    _req_cuda(x)
+    req_cuda(x)
     if x.dtype not in _ST:
         raise ValueError(f"pseudo_label: expected float32, float16 or bfloat16, got {x.dtype}")
     if activation not in (None, "sigmoid"):
@@ -989,7 +971,7 @@ def pseudo_label(x: torch.Tensor, activation: Optional[str] = None, confidence_t
     if mask_sample is not None and not 0 <= mask_sample < N:
         # the reference slices past the end of the batch axis and fails in expand()
         raise ValueError(f"pseudo_label: mask_channel {mask_sample} is out of range for a batch of {N}")
-    if not _is_dense(x) or (mask_sample is not None and N > 1 and x.stride(0) != x.numel() // N):
+    if not is_dense(x) or (mask_sample is not None and N > 1 and x.stride(0) != x.numel() // N):
         x = x.contiguous()
     mdtype = torch.float32 if threshold_from_both_sides else torch.bool
     if out is not None:
@@ -1003,9 +985,8 @@ def pseudo_label(x: torch.Tensor, activation: Optional[str] = None, confidence_t
         mode = PL_MASK_BOTH if threshold_from_both_sides else PL_MASK_ONE
         mask = out[1] if out is not None else torch.empty_like(x, dtype=mdtype)
         t_hi, t_lo = round_to(confidence_threshold, x.dtype), round_to(1.0 - confidence_threshold, x.dtype)
-    _lib.check(_lib.load().tem_pseudo_label_st(_p(x), _p(labels), _p(mask), N, x.numel() // N, ACT[activation], mode,
-                                               -1 if mask_sample is None else int(mask_sample), t_hi, t_lo, _st(x), _stream(x)),
-               "tem_pseudo_label_st")
+    _lib.launch("tem_pseudo_label_st", x, ptr(x), ptr(labels), ptr(mask), N, x.numel() // N, ACT[activation], mode,
+                -1 if mask_sample is None else int(mask_sample), t_hi, t_lo, stype(x))
     return (x if labels is None else labels), mask
 
 
@@ -1017,7 +998,7 @@ def _da_check(name: str, labels, threshold):
         raise ValueError(f"{name}: expected float32, float16 or bfloat16, got {labels.dtype}")
     if labels.numel() == 0:
         raise ValueError(f"{name}: expected a non-empty tensor, got shape {tuple(labels.shape)}")
-    if not _is_dense(labels):
+    if not is_dense(labels):
         raise ValueError(f"{name}: the labels must be dense (any permutation of a contiguous tensor), got strides {labels.stride()}")
     if not math.isfinite(float(threshold)):
         raise ValueError(f"{name}: the label threshold must be finite, got {threshold}")
@@ -1041,12 +1022,11 @@ def source_shares(source_distribution) -> Tuple[float, float]:
 def _label_count(lib, labels, threshold):
     """`threshold`: already rounded to the labels' dtype"""
     n = labels.numel()
-    parts = lib.tem_label_count_parts(n, _st(labels))
+    parts = lib.tem_label_count_parts(n, stype(labels))
     if parts <= 0:
         raise ValueError(f"label_count: {n} elements are out of range")
     partials = torch.empty((parts,), dtype=torch.int64, device=labels.device)
-    _lib.check(lib.tem_label_count_st(_p(labels), n, threshold, _p(partials), parts, _st(labels), _stream(labels)),
-               "tem_label_count_st")
+    _lib.launch("tem_label_count_st", labels, ptr(labels), n, threshold, ptr(partials), parts, stype(labels))
     return partials
 
 
@@ -1078,8 +1058,8 @@ def distribution_align(labels: torch.Tensor, source_distribution, label_threshol
     threshold = round_to(label_threshold, labels.dtype)
     partials = _label_count(lib, labels, threshold)
     res = torch.empty_like(labels) if out is None else out
-    _lib.check(lib.tem_distribution_align_st(_p(labels), _p(res), labels.numel(), threshold, s0, s1, _p(partials),
-                                             partials.numel(), _st(labels), _stream(labels)), "tem_distribution_align_st")
+    _lib.launch("tem_distribution_align_st", labels, ptr(labels), ptr(res), labels.numel(), threshold, s0, s1, ptr(partials),
+                partials.numel(), stype(labels))
     return res
 
 
@@ -1162,13 +1142,12 @@ def _dh_plan(x: torch.Tensor, codes, inverse: bool):
 
 
 def _dh_launch(x: torch.Tensor, codes, shape, out=None) -> torch.Tensor:
-    _req_cuda(x)
+    req_cuda(x)
     x = x.contiguous()
     dev = torch.tensor(codes, dtype=torch.int32).pin_memory().to(x.device, non_blocking=True)
     y = torch.empty(shape, dtype=x.dtype, device=x.device) if out is None else out
     N, H, W = x.shape[0], x.shape[-2], x.shape[-1]
-    _lib.check(_lib.load().tem_dihedral2d(_p(x), _p(y), _p(dev), N, x.numel() // (N * H * W), H, W, x.element_size(), _stream(x)),
-               "tem_dihedral2d")
+    _lib.launch("tem_dihedral2d", x, ptr(x), ptr(y), ptr(dev), N, x.numel() // (N * H * W), H, W, x.element_size())
     return y
 
 
@@ -1209,7 +1188,7 @@ def dihedral_path(x: torch.Tensor, code: int, out=None) -> int:
     DH_PATH_VEC, DH_PATH_SCALAR, DH_PATH_TILE or DH_PATH_TILE_PACKED"""
     N, H, W = x.shape[0], x.shape[-2], x.shape[-1]
     y = torch.empty_like(x) if out is None else out
-    rc = _lib.load().tem_dihedral2d_path(_p(x), _p(y), int(code), N, x.numel() // (N * H * W), H, W, x.element_size())
+    rc = _lib.load().tem_dihedral2d_path(ptr(x), ptr(y), int(code), N, x.numel() // (N * H * W), H, W, x.element_size())
     if rc < 0:
         _lib.check(-1, "tem_dihedral2d_path")
     return rc
@@ -1227,11 +1206,11 @@ def _cld_geo(x: torch.Tensor):
         raise ValueError(f"cldice: expected a 4d [N,C,H,W] or 5d [N,C,D,H,W] tensor, got {tuple(x.shape)}")
     if x.dtype != torch.float32:
         raise ValueError(f"cldice: expected float32, got {x.dtype}")
-    _req_cuda(x)
-    st = _ncv_strides(x)
+    req_cuda(x)
+    st = ncv_strides(x)
     if st is None:
         x = x.contiguous()
-        st = _ncv_strides(x)
+        st = ncv_strides(x)
     N, C = x.shape[:2]
     D = x.shape[2] if x.dim() == 5 else 1
     H, W = x.shape[-2:]
@@ -1242,13 +1221,13 @@ def _cld_geo(x: torch.Tensor):
 
 def _cld_scratch(count: int, like_shape, device, numel: int):
     """`count` planar fp32 tensors carved from the stream's static workspace"""
-    ws = _workspace(count * numel * 4, device)
+    ws = workspace(count * numel * 4, device)
     return [ws[i * numel * 4:(i + 1) * numel * 4].view(torch.float32).view(like_shape) for i in range(count)]
 
 
-def _cld_step(lib, e, st, geo, a_in, b_in, e_next, out, out2, mode):
-    _lib.check(lib.tem_cldice_step(_p(e), st[0], st[1], st[2], _p(a_in), _p(b_in), _p(e_next), _p(out), _p(out2), *geo,
-                                   mode, _stream(e)), "tem_cldice_step")
+def _cld_step(e, st, geo, a_in, b_in, e_next, out, out2, mode):
+    _lib.launch("tem_cldice_step", e, ptr(e), st[0], st[1], st[2], ptr(a_in), ptr(b_in), ptr(e_next), ptr(out), ptr(out2), *geo,
+                mode)
 
 
 def _planar_st(geo):
@@ -1262,16 +1241,15 @@ def cldice_morph(x: torch.Tensor, mode: int):
     backward of the opening (None otherwise)"""
     x, st, geo = _cld_geo(x)
     out = torch.empty(x.shape, dtype=torch.float32, device=x.device)
-    lib = _lib.load()
     e1 = None
     if mode == CLD_ERODE:
-        _cld_step(lib, x, st, geo, None, None, out, None, None, CLD_ERODE)
+        _cld_step(x, st, geo, None, None, out, None, None, CLD_ERODE)
     elif mode == CLD_OPEN:
         e1 = torch.empty_like(out)
-        _cld_step(lib, x, st, geo, None, None, e1, None, None, CLD_ERODE)
-        _cld_step(lib, x, st, geo, None, None, None, out, None, CLD_OPEN)
+        _cld_step(x, st, geo, None, None, e1, None, None, CLD_ERODE)
+        _cld_step(x, st, geo, None, None, None, out, None, CLD_OPEN)
     elif mode == CLD_DILATE:
-        _cld_step(lib, x, st, geo, None, None, None, out, None, CLD_DILATE)
+        _cld_step(x, st, geo, None, None, None, out, None, CLD_DILATE)
     else:
         raise ValueError(f"cldice_morph: mode {mode}")
     return out, e1
@@ -1291,22 +1269,19 @@ def cldice_morph_bwd(x: torch.Tensor, e1, g: torch.Tensor, mode: int, channels_l
     """gradient of cldice_morph's output w.r.t. x for the upstream g (gather form, PyTorch's tie rules)"""
     x, st, geo = _cld_geo(x)
     g = g.to(torch.float32).contiguous()
-    lib = _lib.load()
     out, os_ = _cld_out(x, channels_last)
     if mode == CLD_DILATE:
         if os_[2] != 1:   # the dilation backward writes planar
             out, os_ = _cld_out(x, False)
-        _lib.check(lib.tem_cldice_dilate_bwd(_p(x), st[0], st[1], st[2], _p(g), None, _p(out), *geo, _stream(x)),
-                   "tem_cldice_dilate_bwd")
+        _lib.launch("tem_cldice_dilate_bwd", x, ptr(x), st[0], st[1], st[2], ptr(g), None, ptr(out), *geo)
         return out
     if mode == CLD_OPEN:
         g1 = torch.empty_like(g)
         pst = _planar_st(geo)
-        _lib.check(lib.tem_cldice_dilate_bwd(_p(e1), pst[0], pst[1], pst[2], _p(g), None, _p(g1), *geo, _stream(x)),
-                   "tem_cldice_dilate_bwd")
+        _lib.launch("tem_cldice_dilate_bwd", x, ptr(e1), pst[0], pst[1], pst[2], ptr(g), None, ptr(g1), *geo)
         g = g1
-    _lib.check(lib.tem_cldice_erode_bwd(_p(x), st[0], st[1], st[2], _p(g), None, None, None, None, _p(out), os_[0], os_[1],
-                                        os_[2], *geo, _stream(x)), "tem_cldice_erode_bwd")
+    _lib.launch("tem_cldice_erode_bwd", x, ptr(x), st[0], st[1], st[2], ptr(g), None, None, None, None, ptr(out), os_[0], os_[1],
+                os_[2], *geo)
     return out
 
 
@@ -1318,7 +1293,6 @@ def cldice_skel_fwd(x: torch.Tensor, num_iter: int, save: bool):
     if K < 0:
         raise ValueError("cldice: num_iter must not be negative")
     x, st, geo = _cld_geo(x)
-    lib = _lib.load()
     pst = _planar_st(geo)
     skel = torch.empty(x.shape, dtype=torch.float32, device=x.device)
     if save:
@@ -1332,7 +1306,7 @@ def cldice_skel_fwd(x: torch.Tensor, num_iter: int, save: bool):
         souts = [skel] * (K + 1)                          # updated in place
     e, est = x, st
     for j in range(K + 1):
-        _cld_step(lib, e, est, geo, souts[j - 1] if j else None, None, enext[j], souts[j], None, CLD_ROUND if j else CLD_ROUND0)
+        _cld_step(e, est, geo, souts[j - 1] if j else None, None, enext[j], souts[j], None, CLD_ROUND if j else CLD_ROUND0)
         e, est = enext[j], pst
     return skel, ((x, estack, sstack) if save else None)
 
@@ -1344,7 +1318,6 @@ def cldice_skel_bwd(saved, gs: torch.Tensor, channels_last: bool, direct=None, c
     laid out like the prediction (channels-last memory when `channels_last`)."""
     x, estack, sstack = saved
     x, st, geo = _cld_geo(x)
-    lib = _lib.load()
     K = sstack.shape[0]
     pst = _planar_st(geo)
     n = x.numel()
@@ -1356,21 +1329,20 @@ def cldice_skel_bwd(saved, gs: torch.Tensor, channels_last: bool, direct=None, c
         gsb = bufs[3]
         gsb.copy_(gs.to(torch.float32))
     out, os_ = _cld_out(x, channels_last)
-    stream = _stream(x)
     for j in range(K, -1, -1):
         e, est = (estack[j - 1], pst) if j else (x, st)
         if j:
-            _cld_step(lib, e, est, geo, sstack[j - 1], gsb, None, h, gsb, CLD_BWD_POINT)
+            _cld_step(e, est, geo, sstack[j - 1], gsb, None, h, gsb, CLD_BWD_POINT)
         else:
-            _cld_step(lib, e, est, geo, None, gsb, None, h, None, CLD_BWD_POINT0)
-        _lib.check(lib.tem_cldice_dilate_bwd(_p(estack[j]), pst[0], pst[1], pst[2], _p(h), _p(b0) if j < K else None,
-                                             _p(b1), *geo, stream), "tem_cldice_dilate_bwd")
+            _cld_step(e, est, geo, None, gsb, None, h, None, CLD_BWD_POINT0)
+        _lib.launch("tem_cldice_dilate_bwd", x, ptr(estack[j]), pst[0], pst[1], pst[2], ptr(h), ptr(b0) if j < K else None, ptr(b1),
+                    *geo)
         if j:
-            _lib.check(lib.tem_cldice_erode_bwd(_p(e), est[0], est[1], est[2], _p(b1), _p(h), None, None, None, _p(b0),
-                                                pst[0], pst[1], pst[2], *geo, stream), "tem_cldice_erode_bwd")
+            _lib.launch("tem_cldice_erode_bwd", x, ptr(e), est[0], est[1], est[2], ptr(b1), ptr(h), None, None, None, ptr(b0),
+                        pst[0], pst[1], pst[2], *geo)
         else:
-            _lib.check(lib.tem_cldice_erode_bwd(_p(e), est[0], est[1], est[2], _p(b1), _p(h), _p(direct), _p(coef), _p(gout),
-                                                _p(out), os_[0], os_[1], os_[2], *geo, stream), "tem_cldice_erode_bwd")
+            _lib.launch("tem_cldice_erode_bwd", x, ptr(e), est[0], est[1], est[2], ptr(b1), ptr(h), ptr(direct), ptr(coef),
+                        ptr(gout), ptr(out), os_[0], os_[1], os_[2], *geo)
     return out
 
 
@@ -1382,14 +1354,13 @@ def cldice_score_fwd(x, t, skel_x, skel_t, eps: float, invert: bool):
     V = D * H * W
     lib = _lib.load()
     nws = lib.tem_cldice_ws(N, C, V, 0, 0)
-    ws = _workspace(nws, x.device)
+    ws = workspace(nws, x.device)
     sums = torch.empty((4,), dtype=torch.float64, device=x.device)
     out = torch.empty((1,), dtype=torch.float32, device=x.device)
     coef = torch.empty((4,), dtype=torch.float32, device=x.device)
-    _lib.check(lib.tem_cldice_sums(_p(skel_x), _p(skel_t), _p(x), xs[0], xs[1], xs[2], _p(t), ts[0], ts[1], ts[2], N, C, V,
-                                   _p(ws), nws, _stream(x)), "tem_cldice_sums")
-    _lib.check(lib.tem_cldice_finalize(_p(ws), float(eps), int(invert), _p(sums), _p(out), _p(coef), _stream(x)),
-               "tem_cldice_finalize")
+    _lib.launch("tem_cldice_sums", x, ptr(skel_x), ptr(skel_t), ptr(x), xs[0], xs[1], xs[2], ptr(t), ts[0], ts[1], ts[2], N, C, V,
+                ptr(ws), nws)
+    _lib.launch("tem_cldice_finalize", x, ptr(ws), float(eps), int(invert), ptr(sums), ptr(out), ptr(coef))
     return out, coef, sums
 
 
@@ -1401,8 +1372,7 @@ def cldice_score_bwd(saved, t, skel_t, coef, gout, channels_last: bool) -> torch
     N, C, D, H, W, _ = geo
     V = D * H * W
     gs = _cld_scratch(4, x.shape, x.device, x.numel())[3]
-    _lib.check(_lib.load().tem_cldice_grad(_p(t), ts[0], ts[1], ts[2], _p(coef), _p(gout), _p(gs), N, C, V, _stream(t)),
-               "tem_cldice_grad")
+    _lib.launch("tem_cldice_grad", t, ptr(t), ts[0], ts[1], ts[2], ptr(coef), ptr(gout), ptr(gs), N, C, V)
     return cldice_skel_bwd(saved, gs, channels_last, direct=skel_t, coef=coef, gout=gout, gs_is_scratch=True)
 
 
@@ -1423,10 +1393,9 @@ def bump_versions(tensors):
 
 
 def adamw_step(param, grad, exp_avg, exp_avg_sq, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
-    _req_cuda(param, grad, exp_avg, exp_avg_sq)
-    lib = _lib.load()
-    _lib.check(lib.tem_adamw_step(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), lr, beta1, beta2,
-                                  eps, weight_decay, int(step), grad_scale, _stream(param)), "tem_adamw_step")
+    req_cuda(param, grad, exp_avg, exp_avg_sq)
+    _lib.launch("tem_adamw_step", param, ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), lr, beta1, beta2, eps,
+                weight_decay, int(step), grad_scale)
 
 
 def adamw_hyper(host_buf, lr, beta1, beta2, eps, weight_decay, step, grad_scale=1.0):
@@ -1439,47 +1408,37 @@ def adamw_hyper(host_buf, lr, beta1, beta2, eps, weight_decay, step, grad_scale=
 
 def adamw_step_dev(param, grad, exp_avg, exp_avg_sq, hyper):
     """adamw_step with lr / bias corrections read from the device tensor `hyper` (HIP-graph capture)."""
-    _req_cuda(param, grad, exp_avg, exp_avg_sq, hyper)
-    lib = _lib.load()
-    _lib.check(lib.tem_adamw_step_dev(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(hyper),
-                                      _stream(param)), "tem_adamw_step_dev")
+    req_cuda(param, grad, exp_avg, exp_avg_sq, hyper)
+    _lib.launch("tem_adamw_step_dev", param, ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), ptr(hyper))
 
 
 def adamw_step_tab(param, grad, exp_avg, exp_avg_sq, table, sstate):
     """adamw_step with its scalars from the row of `table` that the device-side step count in `sstate` selects; skipped
     when sstate's overflow flag is up (tem_adamw_step_tab)."""
-    _req_cuda(param, grad, exp_avg, exp_avg_sq, table, sstate)
-    lib = _lib.load()
-    _lib.check(lib.tem_adamw_step_tab(_p(param), _p(grad), _p(exp_avg), _p(exp_avg_sq), param.numel(), _p(table),
-                                      _p(sstate), _stream(param)), "tem_adamw_step_tab")
+    req_cuda(param, grad, exp_avg, exp_avg_sq, table, sstate)
+    _lib.launch("tem_adamw_step_tab", param, ptr(param), ptr(grad), ptr(exp_avg), ptr(exp_avg_sq), param.numel(), ptr(table),
+                ptr(sstate))
 
 
 def amp_unscale_dev(grad, sstate):
-    _req_cuda(grad, sstate)
-    lib = _lib.load()
-    _lib.check(lib.tem_amp_unscale_dev(_p(grad), grad.numel(), _p(sstate), _stream(grad)), "tem_amp_unscale_dev")
+    req_cuda(grad, sstate)
+    _lib.launch("tem_amp_unscale_dev", grad, ptr(grad), grad.numel(), ptr(sstate))
 
 
 def amp_update_dev(sstate, growth, backoff, interval):
-    _req_cuda(sstate)
-    lib = _lib.load()
-    _lib.check(lib.tem_amp_update_dev(_p(sstate), float(growth), float(backoff), int(interval), _stream(sstate)),
-               "tem_amp_update_dev")
+    req_cuda(sstate)
+    _lib.launch("tem_amp_update_dev", sstate, ptr(sstate), float(growth), float(backoff), int(interval))
 
 
 def amp_unscale(grad, inv_scale, found_inf):
     """grad *= inv_scale in place; found_inf[0] = 1 if any element is not finite (GradScaler.unscale_)."""
-    _req_cuda(grad, found_inf)
-    lib = _lib.load()
-    _lib.check(lib.tem_amp_unscale(_p(grad), grad.numel(), float(inv_scale), _p(found_inf), _stream(grad)),
-               "tem_amp_unscale")
+    req_cuda(grad, found_inf)
+    _lib.launch("tem_amp_unscale", grad, ptr(grad), grad.numel(), float(inv_scale), ptr(found_inf))
 
 
 def ema_update(theta_k, theta_q, momentum):
-    _req_cuda(theta_k, theta_q)
-    lib = _lib.load()
-    _lib.check(lib.tem_ema_update(_p(theta_k), _p(theta_q), theta_k.numel(), momentum, _stream(theta_k)),
-               "tem_ema_update")
+    req_cuda(theta_k, theta_q)
+    _lib.launch("tem_ema_update", theta_k, ptr(theta_k), ptr(theta_q), theta_k.numel(), momentum)
 
 
 # ---------------------------------------------------------------- labels ----
@@ -1487,7 +1446,7 @@ BOUNDARY_MODES = {"thick": 0, "inner": 1, "outer": 2}
 
 
 def boundary_target(labels: torch.Tensor, add_binary_target: bool, mode: str = "thick") -> torch.Tensor:
-    _req_cuda(labels)
+    req_cuda(labels)
     if mode not in BOUNDARY_MODES:
         raise NotImplementedError(f"find_boundaries mode '{mode}': the MI355X kernel has {sorted(BOUNDARY_MODES)} "
                                   "('subpixel' returns a 2n-1 grid, which cannot be a training target)")
@@ -1496,15 +1455,13 @@ def boundary_target(labels: torch.Tensor, add_binary_target: bool, mode: str = "
     D, H, W = (1,) * (3 - len(sp)) + sp
     nch = 2 if add_binary_target else 1
     out = torch.empty((nch,) + sp, dtype=torch.float32, device=labels.device)
-    lib = _lib.load()
-    _lib.check(lib.tem_boundary_target_mode(_p(labels), _p(out), D, H, W, int(add_binary_target),
-                                            BOUNDARY_MODES[mode], _stream(labels)), "tem_boundary_target_mode")
+    _lib.launch("tem_boundary_target_mode", labels, ptr(labels), ptr(out), D, H, W, int(add_binary_target), BOUNDARY_MODES[mode])
     return out
 
 
 def affinity_target(labels, offsets, ignore_label=None, add_binary_target=False, add_mask=False,
                     include_ignore_transitions=False) -> torch.Tensor:
-    _req_cuda(labels)
+    req_cuda(labels)
     labels = labels.to(torch.int64).contiguous()
     sp = tuple(labels.shape)
     nd = len(sp)
@@ -1520,31 +1477,28 @@ def affinity_target(labels, offsets, ignore_label=None, add_binary_target=False,
     cb = 1 if add_binary_target else 0
     nch = (n_off + cb) * (2 if add_mask else 1)
     out = torch.empty((nch,) + sp, dtype=torch.float32, device=labels.device)
-    lib = _lib.load()
-    _lib.check(lib.tem_affinity_target(_p(labels), _p(out), D, H, W, arr, n_off, int(ignore_label is not None),
-                                       int(ignore_label or 0), int(add_binary_target), int(add_mask),
-                                       int(include_ignore_transitions), _stream(labels)), "tem_affinity_target")
+    _lib.launch("tem_affinity_target", labels, ptr(labels), ptr(out), D, H, W, arr, n_off, int(ignore_label is not None),
+                int(ignore_label or 0), int(add_binary_target), int(add_mask), int(include_ignore_transitions))
     return out
 
 
 def standardize(x: torch.Tensor, eps: float = 1e-7) -> torch.Tensor:
     """Per-sample (first axis) standardisation of a contiguous tensor."""
-    _req_cuda(x)
+    req_cuda(x)
     x = x.contiguous()
     N = x.shape[0]
     L = x.numel() // N
     y = torch.empty_like(x)
-    lib = _lib.load()
     nws = N * 256 * 16
-    ws = _workspace(nws, x.device)
-    _lib.check(lib.tem_standardize(_p(x), _p(y), N, L, eps, _p(ws), nws, _stream(x)), "tem_standardize")
+    ws = workspace(nws, x.device)
+    _lib.launch("tem_standardize", x, ptr(x), ptr(y), N, L, eps, ptr(ws), nws)
     return y
 
 
 # ---- min-max / percentile normalisation and contrast of raw data (csrc/rawnorm.hip) ----
 def _rows(x: torch.Tensor):
     """-> (x as contiguous float32, N, L): rows are the entries of the first axis"""
-    _req_cuda(x)
+    req_cuda(x)
     if x.dim() < 1 or x.numel() == 0:
         raise ValueError(f"expected a non-empty tensor of rows, got shape {tuple(x.shape)}")
     x = x.float().contiguous()
@@ -1563,7 +1517,7 @@ def _host_floats(values, n: int, what: str):
 def _fill(values, n: int, device, what: str) -> torch.Tensor:
     """host values -> a device float32 [n] without a copy or a synchronisation (tem_rawnorm_fill)"""
     out = torch.empty((n,), dtype=torch.float32, device=device)
-    _lib.check(_lib.load().tem_rawnorm_fill(_p(out), _host_floats(values, n, what), n, _stream(out)), "tem_rawnorm_fill")
+    _lib.launch("tem_rawnorm_fill", out, ptr(out), _host_floats(values, n, what), n)
     return out
 
 
@@ -1582,8 +1536,8 @@ def row_minmax(x: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     mx = torch.empty_like(mn)
     lib = _lib.load()
     nws = lib.tem_rawnorm_ws(N, L, 0)
-    ws = _workspace(nws, x.device)
-    _lib.check(lib.tem_row_minmax(_p(x), N, L, _p(mn), _p(mx), _p(ws), nws, _stream(x)), "tem_row_minmax")
+    ws = workspace(nws, x.device)
+    _lib.launch("tem_row_minmax", x, ptr(x), N, L, ptr(mn), ptr(mx), ptr(ws), nws)
     return mn, mx
 
 
@@ -1605,8 +1559,8 @@ def row_order_statistics(x: torch.Tensor, ranks) -> torch.Tensor:
         part = out if kk == K else torch.empty((N, kk), dtype=torch.float32, device=x.device)
         flat = (ctypes.c_int64 * (N * kk))(*[int(v) for r in ranks for v in r[k0:k0 + kk]])
         nws = lib.tem_rawnorm_ws(N, L, kk)
-        ws = _workspace(nws, x.device)
-        _lib.check(lib.tem_row_select(_p(x), N, L, flat, kk, _p(part), _p(ws), nws, _stream(x)), "tem_row_select")
+        ws = workspace(nws, x.device)
+        _lib.launch("tem_row_select", x, ptr(x), N, L, flat, kk, ptr(part), ptr(ws), nws)
         if part is not out:
             out[:, k0:k0 + kk] = part
     return out
@@ -1615,7 +1569,7 @@ def row_order_statistics(x: torch.Tensor, ranks) -> torch.Tensor:
 def _apply(x, N, L, sub, div, clip) -> torch.Tensor:
     y = torch.empty_like(x)
     flag, lo, hi = _clip(clip)
-    _lib.check(_lib.load().tem_rawnorm_apply(_p(x), _p(y), N, L, _p(sub), _p(div), flag, lo, hi, _stream(x)), "tem_rawnorm_apply")
+    _lib.launch("tem_rawnorm_apply", x, ptr(x), ptr(y), N, L, ptr(sub), ptr(div), flag, lo, hi)
     return y
 
 
@@ -1633,7 +1587,7 @@ def normalize(x: torch.Tensor, eps: float = 1e-7, clip=None, minval=None, maxval
     if maxval is not None:
         return _apply(x, N, L, mn, _fill(float(maxval) + float(eps), N, x.device, "maxval"), clip)
     sub, div = torch.empty_like(mn), torch.empty_like(mn)
-    _lib.check(_lib.load().tem_rawnorm_minmax_coef(_p(mn), _p(mx), N, eps, _p(sub), _p(div), _stream(x)), "tem_rawnorm_minmax_coef")
+    _lib.launch("tem_rawnorm_minmax_coef", x, ptr(mn), ptr(mx), N, eps, ptr(sub), ptr(div))
     return _apply(x, N, L, sub, div, clip)
 
 
@@ -1676,8 +1630,7 @@ def normalize_percentile(x: torch.Tensor, lower=1.0, upper=99.0, eps: float = 1e
     div = torch.empty_like(sub)
     v = torch.empty((N, 2), dtype=torch.float32, device=x.device) if return_percentiles else None
     t = (ctypes.c_float * (2 * N))(*weights)
-    _lib.check(_lib.load().tem_rawnorm_percentile_coef(_p(os_), t, N, eps, _p(sub), _p(div), _p(v), _stream(x)),
-               "tem_rawnorm_percentile_coef")
+    _lib.launch("tem_rawnorm_percentile_coef", x, ptr(os_), t, N, eps, ptr(sub), ptr(div), ptr(v))
     y = _apply(x, N, L, sub, div, clip)
     return (y, v) if return_percentiles else y
 
@@ -1689,8 +1642,7 @@ def contrast(x: torch.Tensor, alpha, mean: float, clip=None) -> torch.Tensor:
     a = _fill(alpha, N, x.device, "alpha")
     y = torch.empty_like(x)
     flag, lo, hi = _clip(clip)
-    _lib.check(_lib.load().tem_rawnorm_contrast(_p(x), _p(y), N, L, _p(a), float(mean), flag, lo, hi, _stream(x)),
-               "tem_rawnorm_contrast")
+    _lib.launch("tem_rawnorm_contrast", x, ptr(x), ptr(y), N, L, ptr(a), float(mean), flag, lo, hi)
     return y
 
 
@@ -1708,8 +1660,8 @@ def philox_words(seed: int, row: int, i0: int, rnd: int, n: int, device="cuda") 
     if n <= 0 or not (0 <= row < 2 ** 32 and 0 <= rnd < 2 ** 32 and 0 <= i0 and i0 + n <= 2 ** 64):
         raise ValueError("philox_words: n > 0, row and round within [0, 2^32), elements within [0, 2^64)")
     out = torch.empty((n, 4), dtype=torch.int32, device=device)
-    _req_cuda(out)
-    _lib.check(_lib.load().tem_rawaug_philox_words(_p(out), _seed(seed), row, i0, rnd, n, _stream(out)), "tem_rawaug_philox_words")
+    req_cuda(out)
+    _lib.launch("tem_rawaug_philox_words", out, ptr(out), _seed(seed), row, i0, rnd, n)
     return out
 
 
@@ -1720,8 +1672,7 @@ def gauss_noise(x: torch.Tensor, std, seed: int, clip=None, row0: int = 0) -> to
     s = _fill(std, N, x.device, "std")
     y = torch.empty_like(x)
     flag, lo, hi = _clip(clip)
-    _lib.check(_lib.load().tem_rawaug_gauss_noise(_p(x), _p(y), N, L, _p(s), _seed(seed), int(row0), flag, lo, hi, _stream(x)),
-               "tem_rawaug_gauss_noise")
+    _lib.launch("tem_rawaug_gauss_noise", x, ptr(x), ptr(y), N, L, ptr(s), _seed(seed), int(row0), flag, lo, hi)
     return y
 
 
@@ -1732,8 +1683,7 @@ def poisson_add(x: torch.Tensor, lam, seed: int, clip=None, row0: int = 0) -> to
     lm = _fill(lam, N, x.device, "lam")
     y = torch.empty_like(x)
     flag, lo, hi = _clip(clip)
-    _lib.check(_lib.load().tem_rawaug_poisson_add(_p(x), _p(y), N, L, _p(lm), _seed(seed), int(row0), flag, lo, hi, _stream(x)),
-               "tem_rawaug_poisson_add")
+    _lib.launch("tem_rawaug_poisson_add", x, ptr(x), ptr(y), N, L, ptr(lm), _seed(seed), int(row0), flag, lo, hi)
     return y
 
 
@@ -1750,8 +1700,7 @@ def poisson_scaled(x: torch.Tensor, mult, seed: int, clip=None, row0: int = 0, o
     m = _fill(mult, N, x.device, "mult")
     y = torch.empty_like(x)
     flag, lo, hi = _clip(clip)
-    _lib.check(_lib.load().tem_rawaug_poisson_scaled(_p(x), _p(y), N, L, _p(offset), _p(m), _seed(seed), int(row0), flag, lo, hi,
-                                                     _stream(x)), "tem_rawaug_poisson_scaled")
+    _lib.launch("tem_rawaug_poisson_scaled", x, ptr(x), ptr(y), N, L, ptr(offset), ptr(m), _seed(seed), int(row0), flag, lo, hi)
     return y
 
 
@@ -1759,7 +1708,7 @@ def blur2d(x: torch.Tensor, wy, wx=None) -> torch.Tensor:
     """The last two axes of x convolved with the 1-D weights wy (along H) and wx (along W; None: wy), reflect border without
     edge repeat; all other axes are independent planes (`GaussianBlur`, transform/raw.py:428-454).  Weights: HOST sequences
     of odd length <= 63 with len // 2 < the axis' size."""
-    _req_cuda(x)
+    req_cuda(x)
     if x.dim() < 2 or x.numel() == 0:
         raise ValueError(f"blur2d: expected a non-empty tensor of at least two axes, got shape {tuple(x.shape)}")
     x = x.float().contiguous()
@@ -1769,8 +1718,7 @@ def blur2d(x: torch.Tensor, wy, wx=None) -> torch.Tensor:
     dy = _fill(wy, len(wy), x.device, "wy")
     dx = dy if wx is wy else _fill(wx, len(wx), x.device, "wx")
     y = torch.empty_like(x)
-    _lib.check(_lib.load().tem_rawaug_blur2d(_p(x), _p(y), x.numel() // (H * W), H, W, _p(dy), _p(dx), len(wy), len(wx), _stream(x)),
-               "tem_rawaug_blur2d")
+    _lib.launch("tem_rawaug_blur2d", x, ptr(x), ptr(y), x.numel() // (H * W), H, W, ptr(dy), ptr(dx), len(wy), len(wx))
     return y
 
 
@@ -1779,7 +1727,7 @@ def blur3d(x: torch.Tensor, wz, wy, wx) -> torch.Tensor:
     every plane, then a pass that streams along the plane and takes its taps along z (tem_rawaug_blur_z), the same reflect
     border without edge repeat on all three axes.  Weights: HOST sequences of odd length <= 63 with len // 2 < the axis'
     size; the one tap [1.0] along z (all a volume of D = 1 admits) leaves `blur2d`."""
-    _req_cuda(x)
+    req_cuda(x)
     if x.dim() < 3 or x.numel() == 0:
         raise ValueError(f"blur3d: expected a non-empty tensor of at least three axes, got shape {tuple(x.shape)}")
     wz = [float(v) for v in wz]
@@ -1794,8 +1742,7 @@ def blur3d(x: torch.Tensor, wz, wy, wx) -> torch.Tensor:
     HW = int(x.shape[-2]) * int(x.shape[-1])
     dz = _fill(wz, len(wz), x.device, "wz")
     out = torch.empty_like(y)
-    _lib.check(_lib.load().tem_rawaug_blur_z(_p(y), _p(out), y.numel() // (D * HW), D, HW, _p(dz), len(wz), _stream(y)),
-               "tem_rawaug_blur_z")
+    _lib.launch("tem_rawaug_blur_z", y, ptr(y), ptr(out), y.numel() // (D * HW), D, HW, ptr(dz), len(wz))
     return out
 
 
@@ -1804,13 +1751,13 @@ DEFECT_KEEP, DEFECT_DROP, DEFECT_LOW, DEFECT_PASTE, DEFECT_DEFORM = range(5)
 DEFECT_KMAX = 33   # taps of the separable filter
 
 
-def _to_device(host, device) -> torch.Tensor:
+def to_device(host, device) -> torch.Tensor:
     """a small host numpy array -> the device, through pinned memory, on the current stream, without a synchronisation"""
     return torch.from_numpy(host).pin_memory().to(device, non_blocking=True)
 
 
 def _slices(x: torch.Tensor, what: str):
-    _req_cuda(x)
+    req_cuda(x)
     if x.dim() != 3 or x.dtype != torch.float32 or not x.is_contiguous() or x.numel() == 0:
         raise ValueError(f"{what}: expected a contiguous float32 tensor [S, H, W], got {x.dtype} {tuple(x.shape)}")
     return int(x.shape[0]), int(x.shape[1]), int(x.shape[2])
@@ -1847,9 +1794,9 @@ class DefectTables:
                 lo, hi = tables[off:off + n] & 0xffff, (tables[off:off + n] >> 16) & 0xffff
                 if (lo > hi).any() or hi.max() >= other:
                     raise ValueError("defect: an interval of a line leaves the slice")
-        self.plan = _to_device(plan, device)
-        self.rec = _to_device(rec, device) if self.D else None
-        self.tables = _to_device(tables if tables.size else np.zeros(1, np.int32), device)
+        self.plan = to_device(plan, device)
+        self.rec = to_device(rec, device) if self.D else None
+        self.tables = to_device(tables if tables.size else np.zeros(1, np.int32), device)
 
     def _geom(self, x, what):
         if _slices(x, what) != (self.S, self.H, self.W) or x.device != self.plan.device:
@@ -1860,7 +1807,7 @@ def defect_mean(x: torch.Tensor, tab: DefectTables) -> torch.Tensor:
     """float32 [S]: the mean of every slice the plan marks low contrast (summed in float64 in a fixed order), 0 elsewhere"""
     tab._geom(x, "defect_mean")
     mean = torch.empty((tab.S,), dtype=torch.float32, device=x.device)
-    _lib.check(_lib.load().tem_defect_mean(_p(x), tab.S, tab.H * tab.W, _p(tab.plan), _p(mean), _stream(x)), "tem_defect_mean")
+    _lib.launch("tem_defect_mean", x, ptr(x), tab.S, tab.H * tab.W, ptr(tab.plan), ptr(mean))
     return mean
 
 
@@ -1875,8 +1822,7 @@ def defect_apply(x: torch.Tensor, tab: DefectTables, mean: torch.Tensor, art=Non
         if t is not None and (_slices(t, "defect_apply: art / alpha") != (tab.planes, tab.H, tab.W) or t.device != x.device):
             raise ValueError(f"defect_apply: artifact and alpha planes must be [{tab.planes}, {tab.H}, {tab.W}] on {x.device}")
     y = torch.empty_like(x)
-    _lib.check(_lib.load().tem_defect_apply(_p(x), _p(y), tab.S, tab.H * tab.W, _p(tab.plan), _p(mean), _p(art), _p(alpha), _stream(x)),
-               "tem_defect_apply")
+    _lib.launch("tem_defect_apply", x, ptr(x), ptr(y), tab.S, tab.H * tab.W, ptr(tab.plan), ptr(mean), ptr(art), ptr(alpha))
     return y
 
 
@@ -1903,8 +1849,7 @@ def defect_flow(tab: DefectTables, seed: int, strength: float, weights, out=None
         raise ValueError("defect_flow: no slice is deformed")
     flow = _defect_out(out, (tab.D, 2, tab.H, tab.W), tab.plan.device, "defect_flow")
     w, k = _defect_weights(weights, flow.device)
-    _lib.check(_lib.load().tem_defect_flow(_p(flow), tab.D, tab.H, tab.W, _p(tab.rec), _seed(seed), float(strength), _p(w), k,
-                                           _stream(flow)), "tem_defect_flow")
+    _lib.launch("tem_defect_flow", flow, ptr(flow), tab.D, tab.H, tab.W, ptr(tab.rec), _seed(seed), float(strength), ptr(w), k)
     return flow
 
 
@@ -1916,8 +1861,7 @@ def defect_prefilter(x: torch.Tensor, tab: DefectTables, weights, out=None) -> t
         raise ValueError("defect_prefilter: no slice is deformed")
     coef = _defect_out(out, (tab.D, tab.H, tab.W), x.device, "defect_prefilter")
     w, k = _defect_weights(weights, x.device)
-    _lib.check(_lib.load().tem_defect_prefilter(_p(x), _p(coef), tab.D, tab.H, tab.W, _p(tab.rec), _p(w), k, _stream(x)),
-               "tem_defect_prefilter")
+    _lib.launch("tem_defect_prefilter", x, ptr(x), ptr(coef), tab.D, tab.H, tab.W, ptr(tab.rec), ptr(w), k)
     return coef
 
 
@@ -1929,8 +1873,8 @@ def defect_warp(coef: torch.Tensor, flow: torch.Tensor, y: torch.Tensor, tab: De
         raise ValueError("defect_warp: no slice is deformed")
     _defect_out(coef, (tab.D, tab.H, tab.W), y.device, "defect_warp: coef")
     _defect_out(flow, (tab.D, 2, tab.H, tab.W), y.device, "defect_warp: flow")
-    _lib.check(_lib.load().tem_defect_warp(_p(coef), _p(flow), _p(y), tab.D, tab.H, tab.W, _p(tab.rec), _p(tab.tables), _seed(seed),
-                                           float(noise_scale), _stream(y)), "tem_defect_warp")
+    _lib.launch("tem_defect_warp", y, ptr(coef), ptr(flow), ptr(y), tab.D, tab.H, tab.W, ptr(tab.rec), ptr(tab.tables), _seed(seed),
+                float(noise_scale))
     return y
 
 
@@ -1948,25 +1892,22 @@ def pod_ids(labels: torch.Tensor, apply_label: bool, min_size: int) -> torch.Ten
     """int64 [N, D, H, W] labels -> int32 object ids 1..n per sample (0 background): connected components in
     first-occurrence order (apply_label) or ascending original ids; objects below min_size voxels dropped, the rest
     renumbered in order (tem_pod_cc_* / tem_pod_seq_* / tem_pod_size_*)."""
-    _req_cuda(labels)
+    req_cuda(labels)
     labels = labels.to(torch.int64).contiguous()
     N, D, H, W = labels.shape
     V = D * H * W
-    lib = _lib.load()
     ids = torch.empty((N * V,), dtype=torch.int32, device=labels.device)
     flag = torch.empty((N * V,), dtype=torch.int32, device=labels.device)
     if apply_label:
         parent = torch.empty((N * V,), dtype=torch.int32, device=labels.device)
-        _lib.check(lib.tem_pod_cc_roots(_p(labels), _p(parent), _p(flag), N, D, H, W, _stream(labels)), "tem_pod_cc_roots")
+        _lib.launch("tem_pod_cc_roots", labels, ptr(labels), ptr(parent), ptr(flag), N, D, H, W)
         rank = _flat_cumsum(flag)
-        _lib.check(lib.tem_pod_cc_assign(_p(labels), _p(parent), _p(rank), _p(ids), N, V, _stream(labels)),
-                   "tem_pod_cc_assign")
+        _lib.launch("tem_pod_cc_assign", labels, ptr(labels), ptr(parent), ptr(rank), ptr(ids), N, V)
     else:
         srt, order = torch.sort(labels.view(N, V), dim=1)
-        _lib.check(lib.tem_pod_seq_flag(_p(srt), _p(flag), N, V, _stream(labels)), "tem_pod_seq_flag")
+        _lib.launch("tem_pod_seq_flag", labels, ptr(srt), ptr(flag), N, V)
         rank = _flat_cumsum(flag)
-        _lib.check(lib.tem_pod_seq_assign(_p(srt), _p(order), _p(rank), _p(ids), N, V, _stream(labels)),
-                   "tem_pod_seq_assign")
+        _lib.launch("tem_pod_seq_assign", labels, ptr(srt), ptr(order), ptr(rank), ptr(ids), N, V)
     ids = ids.view(N, D, H, W)
     if min_size > 0:
         size_filter_(ids, min_size)
@@ -1976,16 +1917,15 @@ def pod_ids(labels: torch.Tensor, apply_label: bool, min_size: int) -> torch.Ten
 def size_filter_(ids: torch.Tensor, min_size: int) -> torch.Tensor:
     """in place on contiguous int32 ids [N, D, H, W]: positive ids with fewer than min_size voxels become 0, the surviving
     ones are renumbered 1..n in ascending order, per sample (tem_pod_size_keep / tem_pod_size_apply); id 0 stays 0."""
-    _req_cuda(ids)
+    req_cuda(ids)
     assert ids.dtype == torch.int32 and ids.is_contiguous()
     N = ids.shape[0]
     V = ids.numel() // N
-    lib = _lib.load()
     cnt = torch.empty((N * (V + 1),), dtype=torch.int32, device=ids.device)
     keep = torch.empty_like(cnt)
-    _lib.check(lib.tem_pod_size_keep(_p(ids), _p(cnt), _p(keep), N, V, int(min_size), _stream(ids)), "tem_pod_size_keep")
+    _lib.launch("tem_pod_size_keep", ids, ptr(ids), ptr(cnt), ptr(keep), N, V, int(min_size))
     newid = _flat_cumsum(keep)
-    _lib.check(lib.tem_pod_size_apply(_p(ids), _p(keep), _p(newid), N, V, _stream(ids)), "tem_pod_size_apply")
+    _lib.launch("tem_pod_size_apply", ids, ptr(ids), ptr(keep), ptr(newid), N, V)
     return ids
 
 
@@ -2004,7 +1944,7 @@ def voxel_ranks(height: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     0.0 tie.  The heights are not read back: NaNs are not rejected and where they are ranked is not promised."""
     if height.dtype != torch.float32 or height.dim() < 2 or height.numel() == 0:
         raise ValueError(f"voxel_ranks: expected non-empty float32 heights [N, ...], got {height.dtype} {tuple(height.shape)}")
-    _req_cuda(height)
+    req_cuda(height)
     N = int(height.shape[0])
     V = height.numel() // N
     if V >= 2 ** 31 - 1:
@@ -2016,10 +1956,38 @@ def voxel_ranks(height: torch.Tensor) -> Tuple[torch.Tensor, torch.Tensor]:
     return rank, order.to(torch.int32)
 
 
+def _float32_arg(what, noun, t, rank):
+    """ValueError unless t is a non-empty float32 tensor of `rank` axes; noun: what it holds and its axes, for the message"""
+    if not torch.is_tensor(t) or t.dim() != rank or t.dtype != torch.float32 or t.numel() == 0:
+        raise ValueError(f"{what}: expected non-empty float32 {noun}, got "
+                         f"{getattr(t, 'dtype', type(t))} {tuple(getattr(t, 'shape', ()))}")
+
+
+def _offsets3(what, offsets, D):
+    """offsets: integer vectors of one length, 2 (then D = 1) or 3, below 2^30 in magnitude -> (the offsets padded to
+    (dz, dy, dx), their length as given; 0 for an empty list)"""
+    try:
+        offs = [[int(x) for x in o] for o in offsets]
+    except (TypeError, ValueError):
+        raise ValueError(f"{what}: offsets must be integer vectors of length 2 or 3") from None
+    if any(len(o) not in (2, 3) or len(o) != len(offs[0]) for o in offs):
+        raise ValueError(f"{what}: offsets must be integer vectors of one length, 2 or 3")
+    nd = len(offs[0]) if offs else 0
+    if nd == 2 and D != 1:
+        raise ValueError(f"{what}: offsets of length 2 need D = 1, got D = {D}")
+    if any(abs(x) >= 2 ** 30 for o in offs for x in o):
+        raise ValueError(f"{what}: offsets must be below 2^30 in magnitude")
+    return [[0] * (3 - nd) + o for o in offs], nd
+
+
+def c_offsets(offs):
+    """a list of (dz, dy, dx) -> the host int[3 * C] the entry points take as `offsets`"""
+    return (ctypes.c_int * (3 * len(offs)))(*[x for o in offs for x in o])
+
+
 def _ws_args(height, markers, mask, rounds_out):
     """the host-side checks of `seeded_watershed` (dtypes, shapes; the values of tensors that are still on the host)"""
-    if height.dim() != 4 or height.dtype != torch.float32 or height.numel() == 0:
-        raise ValueError(f"seeded_watershed: expected non-empty float32 heights [N, D, H, W], got {height.dtype} {tuple(height.shape)}")
+    _float32_arg("seeded_watershed", "heights [N, D, H, W]", height, 4)
     if markers.dtype not in _WS_MARKERS:
         raise ValueError(f"seeded_watershed: markers must be of an integer type, got {markers.dtype}")
     if markers.shape != height.shape:
@@ -2051,7 +2019,7 @@ def seeded_watershed(height: torch.Tensor, markers: torch.Tensor, mask: Optional
     refused like any host tensor).  rounds_out: a device int32 that receives the rounds that did work, at most
     `watershed_rounds(D * H * W)`."""
     _ws_args(height, markers, mask, rounds_out)
-    _req_cuda(height, markers, mask, rounds_out)
+    req_cuda(height, markers, mask, rounds_out)
     N, D, H, W = (int(s) for s in height.shape)
     V = D * H * W
     height = height.contiguous()
@@ -2064,8 +2032,8 @@ def seeded_watershed(height: torch.Tensor, markers: torch.Tensor, mask: Optional
     nbytes = int(lib.tem_watershed_ws(N, V))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=height.device)
     out = torch.empty((N, D, H, W), dtype=torch.int32, device=height.device)
-    _lib.check(lib.tem_watershed(_p(rank), _p(order), _p(markers), markers.element_size(), _p(mask), _p(out), _p(rounds_out),
-                                 N, D, H, W, _p(ws), nbytes, _stream(height)), "tem_watershed")
+    _lib.launch("tem_watershed", height, ptr(rank), ptr(order), ptr(markers), markers.element_size(), ptr(mask), ptr(out),
+                ptr(rounds_out), N, D, H, W, ptr(ws), nbytes)
     return out
 
 
@@ -2082,25 +2050,14 @@ def mws_table_slots(n_repulsive: int) -> int:
 
 def _mws_args(aff, offsets, n_attractive, mask, edge_valid, rounds_per_batch):
     """the host-side checks of `mutex_watershed` (dtypes, shapes, offsets) -> offsets as a list of C (dz, dy, dx)"""
-    if not torch.is_tensor(aff) or aff.dim() != 5 or aff.dtype != torch.float32 or aff.numel() == 0:
-        raise ValueError("mutex_watershed: expected non-empty float32 affinities [N, C, D, H, W], got "
-                         f"{getattr(aff, 'dtype', type(aff))} {tuple(getattr(aff, 'shape', ()))}")
+    _float32_arg("mutex_watershed", "affinities [N, C, D, H, W]", aff, 5)
     N, C, D, H, W = (int(s) for s in aff.shape)
     V = D * H * W
-    try:
-        offs = [[int(x) for x in o] for o in offsets]
-    except (TypeError, ValueError):
-        raise ValueError("mutex_watershed: offsets must be integer vectors of length 2 or 3") from None
+    offs, _ = _offsets3("mutex_watershed", offsets, D)
     if len(offs) != C:
         raise ValueError(f"mutex_watershed: {len(offs)} offsets do not match the {C} affinity channels")
     if C > MWS_MAX_CHANNELS:
         raise ValueError(f"mutex_watershed: {C} channels, at most {MWS_MAX_CHANNELS} supported")
-    if any(len(o) not in (2, 3) or len(o) != len(offs[0]) for o in offs):
-        raise ValueError("mutex_watershed: offsets must be integer vectors of one length, 2 or 3")
-    if len(offs[0]) == 2 and D != 1:
-        raise ValueError(f"mutex_watershed: offsets of length 2 need D = 1, got D = {D}")
-    if any(abs(x) >= 2 ** 30 for o in offs for x in o):
-        raise ValueError("mutex_watershed: offsets must be below 2^30 in magnitude")
     if isinstance(n_attractive, bool) or not isinstance(n_attractive, numbers.Integral) or not 0 <= n_attractive <= C:
         raise ValueError(f"mutex_watershed: n_attractive must be an integer within 0..{C}, got {n_attractive}")
     if mask is not None and (mask.dtype != torch.bool or tuple(mask.shape) != (N, D, H, W)):
@@ -2112,7 +2069,7 @@ def _mws_args(aff, offsets, n_attractive, mask, edge_valid, rounds_per_batch):
                          "N * V below 2^33 - 1 supported")
     if isinstance(rounds_per_batch, bool) or not isinstance(rounds_per_batch, numbers.Integral) or not 1 <= rounds_per_batch <= MWS_MAX_BATCH:
         raise ValueError(f"mutex_watershed: rounds_per_batch must be an integer within 1..{MWS_MAX_BATCH}, got {rounds_per_batch}")
-    return [[0] * (3 - len(o)) + o for o in offs]
+    return offs
 
 
 def mutex_watershed(aff: torch.Tensor, offsets, n_attractive: int, mask: Optional[torch.Tensor] = None,
@@ -2133,25 +2090,24 @@ def mutex_watershed(aff: torch.Tensor, offsets, n_attractive: int, mask: Optiona
     read back after each batch, plus the edge counts once at the start (they size the mutex set).  `return_rounds`: also
     the number of rounds that did work."""
     offs = _mws_args(aff, offsets, n_attractive, mask, edge_valid, rounds_per_batch)
-    _req_cuda(aff, mask, edge_valid)
+    req_cuda(aff, mask, edge_valid)
     N, C, D, H, W = (int(s) for s in aff.shape)
     aff = aff.contiguous()
     mask = None if mask is None else mask.contiguous()
     edge_valid = None if edge_valid is None else edge_valid.contiguous()
     dev = aff.device
     lib = _lib.load()
-    coffs = (ctypes.c_int * (3 * C))(*[x for o in offs for x in o])
+    coffs = c_offsets(offs)
     geom = (int(n_attractive), N, C, D, H, W)
     nbytes = int(lib.tem_mws_ws(N, C, D, H, W))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
-    _lib.check(lib.tem_mws_init(_p(mask), _p(edge_valid), coffs, *geom, _p(ws), nbytes, _stream(aff)), "tem_mws_init")
+    _lib.launch("tem_mws_init", aff, ptr(mask), ptr(edge_valid), coffs, *geom, ptr(ws), nbytes)
     n_edges, n_rep = ws[:16].view(torch.int64).tolist()
     slots = mws_table_slots(n_rep)
     table = torch.empty((slots,), dtype=torch.int64, device=dev)
     first, work = 1, 0
     while True:
-        _lib.check(lib.tem_mws_run(_p(aff), coffs, *geom, _p(ws), nbytes, _p(table), slots, first, int(rounds_per_batch),
-                                   _stream(aff)), "tem_mws_run")
+        _lib.launch("tem_mws_run", aff, ptr(aff), coffs, *geom, ptr(ws), nbytes, ptr(table), slots, first, int(rounds_per_batch))
         work, alive = ws[16:24].view(torch.int32).tolist()
         first = 0
         if work > n_edges + 1:
@@ -2159,7 +2115,7 @@ def mutex_watershed(aff: torch.Tensor, offsets, n_attractive: int, mask: Optiona
         if not alive:
             break
     first_voxel = torch.empty((N, D, H, W), dtype=torch.int32, device=dev)
-    _lib.check(lib.tem_mws_labels(_p(first_voxel), N, C, D, H, W, _p(ws), nbytes, _stream(aff)), "tem_mws_labels")
+    _lib.launch("tem_mws_labels", aff, ptr(first_voxel), N, C, D, H, W, ptr(ws), nbytes)
     ids = pod_ids(first_voxel, False, 0)       # 1 + first voxel, ascending -> 1..n in raster order of the first voxel
     return (ids, work) if return_rounds else ids
 
@@ -2178,9 +2134,7 @@ def _emb_delta(delta, what):
 def _emb_args(emb, offsets, delta, n_attractive, strides, distance_type):
     """the host-side checks of `embedding_edges` -> (offsets as C (dz, dy, dx), strides as (sz, sy, sx), the distance code)"""
     what = "embedding_edges"
-    if not torch.is_tensor(emb) or emb.dim() != 5 or emb.dtype != torch.float32 or emb.numel() == 0:
-        raise ValueError(f"{what}: expected non-empty float32 embeddings [N, E, D, H, W], got "
-                         f"{getattr(emb, 'dtype', type(emb))} {tuple(getattr(emb, 'shape', ()))}")
+    _float32_arg(what, "embeddings [N, E, D, H, W]", emb, 5)
     N, E, D, H, W = (int(s) for s in emb.shape)
     if E > EMB_MAX_DIM:
         raise ValueError(f"{what}: {E} embedding channels, at most {EMB_MAX_DIM} supported")
@@ -2189,21 +2143,11 @@ def _emb_args(emb, offsets, delta, n_attractive, strides, distance_type):
     if distance_type not in _EMB_DISTANCE:
         raise ValueError(f"{what}: distance_type must be one of {sorted(_EMB_DISTANCE)}, got {distance_type!r}")
     _emb_delta(delta, what)
-    try:
-        offs = [[int(x) for x in o] for o in offsets]
-    except (TypeError, ValueError):
-        raise ValueError(f"{what}: offsets must be integer vectors of length 2 or 3") from None
+    offs, nd = _offsets3(what, offsets, D)
     if not offs:
         raise ValueError(f"{what}: at least one offset is needed")
     if len(offs) > MWS_MAX_CHANNELS:
         raise ValueError(f"{what}: {len(offs)} offsets, at most {MWS_MAX_CHANNELS} supported")
-    if any(len(o) not in (2, 3) or len(o) != len(offs[0]) for o in offs):
-        raise ValueError(f"{what}: offsets must be integer vectors of one length, 2 or 3")
-    nd = len(offs[0])
-    if nd == 2 and D != 1:
-        raise ValueError(f"{what}: offsets of length 2 need D = 1, got D = {D}")
-    if any(abs(x) >= 2 ** 30 for o in offs for x in o):
-        raise ValueError(f"{what}: offsets must be below 2^30 in magnitude")
     if isinstance(n_attractive, bool) or not isinstance(n_attractive, numbers.Integral) or not 0 <= n_attractive <= len(offs):
         raise ValueError(f"{what}: n_attractive must be an integer within 0..{len(offs)}, got {n_attractive}")
     try:
@@ -2214,7 +2158,7 @@ def _emb_args(emb, offsets, delta, n_attractive, strides, distance_type):
         raise ValueError(f"{what}: expected {nd} strides >= 1 (one per offset entry), got {st}")
     if D * H * W >= 2 ** 31 - 1:
         raise ValueError(f"{what}: {D * H * W} voxels per sample, at most 2^31 - 2 supported")
-    return [[0] * (3 - nd) + o for o in offs], [1] * (3 - nd) + st, _EMB_DISTANCE[distance_type]
+    return offs, [1] * (3 - nd) + st, _EMB_DISTANCE[distance_type]
 
 
 def embedding_edges(emb: torch.Tensor, offsets, delta: float, n_attractive: int, strides=None, distance_type: str = "l2"):
@@ -2227,16 +2171,16 @@ def embedding_edges(emb: torch.Tensor, offsets, delta: float, n_attractive: int,
     expression gives the same bits.  edge_valid is set on the `n_attractive` leading channels, and on the others where every
     coordinate of v is a multiple of its stride (`strides`, one per axis of the offsets; None: 1 each)."""
     offs, st, dist = _emb_args(emb, offsets, delta, n_attractive, strides, distance_type)
-    _req_cuda(emb)
+    req_cuda(emb)
     N, E, D, H, W = (int(s) for s in emb.shape)
     C = len(offs)
     emb = emb.contiguous()
     aff = torch.empty((N, C, D, H, W), dtype=torch.float32, device=emb.device)
     valid = torch.empty((N, C, D, H, W), dtype=torch.bool, device=emb.device)
-    coffs = (ctypes.c_int * (3 * C))(*[x for o in offs for x in o])
+    coffs = c_offsets(offs)
     cst = (ctypes.c_int * 3)(*st)
-    _lib.check(_lib.load().tem_emb_edges(_p(emb), coffs, int(n_attractive), cst, float(delta), dist, N, E, C, D, H, W, _p(aff),
-                                         _p(valid), _stream(emb)), "tem_emb_edges")
+    _lib.launch("tem_emb_edges", emb, ptr(emb), coffs, int(n_attractive), cst, float(delta), dist, N, E, C, D, H, W, ptr(aff),
+                ptr(valid))
     return aff, valid
 
 
@@ -2261,15 +2205,15 @@ def merge_background_by_embedding_(ids: torch.Tensor, emb: torch.Tensor, delta: 
     V = ids.numel() // N
     if N * (V + 1) >= 2 ** 31 - 1:
         raise ValueError(f"{what}: {N} samples of {V} voxels; N * (V + 1) below 2^31 - 1 supported")
-    _req_cuda(ids, emb)
+    req_cuda(ids, emb)
     emb = emb.contiguous()
     lib = _lib.load()
     nbytes = int(lib.tem_emb_bg_ws(N, V))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=ids.device)
     keep = torch.empty((N * (V + 1),), dtype=torch.int32, device=ids.device)
-    _lib.check(lib.tem_emb_bg_stats(_p(ids), _p(emb), N, E, V, delta, _p(keep), _p(ws), nbytes, _stream(ids)), "tem_emb_bg_stats")
+    _lib.launch("tem_emb_bg_stats", ids, ptr(ids), ptr(emb), N, E, V, delta, ptr(keep), ptr(ws), nbytes)
     newid = _flat_cumsum(keep)
-    _lib.check(lib.tem_pod_size_apply(_p(ids), _p(keep), _p(newid), N, V, _stream(ids)), "tem_pod_size_apply")
+    _lib.launch("tem_pod_size_apply", ids, ptr(ids), ptr(keep), ptr(newid), N, V)
     return ids
 
 
@@ -2279,9 +2223,9 @@ PEAKS_MAX_BATCH = 64           # TEM_PEAKS_MAX_BATCH
 PEAKS_ROUNDS_PER_BATCH = 8     # the default: profiles/peaks_bench.txt
 
 
-def _int_arg(value, lo, hi, what):
+def _int_arg(prefix, value, lo, hi, what):
     if isinstance(value, bool) or not isinstance(value, numbers.Integral) or not lo <= value <= hi:
-        raise ValueError(f"peak_local_max: {what} must be an integer within {lo}..{hi}, got {value!r}")
+        raise ValueError(f"{prefix}: {what} must be an integer within {lo}..{hi}, got {value!r}")
     return int(value)
 
 
@@ -2297,13 +2241,13 @@ def _peak_args(image, min_distance, threshold_abs, threshold_rel, exclude_border
     V = image.numel() // N
     if V >= 2 ** 31 - 1 or N > 65535:
         raise ValueError(f"peak_local_max: {N} samples of {V} voxels; V below 2^31 - 1 and N at most 65535 supported")
-    d = _int_arg(min_distance, 1, PEAKS_MAX_DISTANCE, "min_distance")
+    d = _int_arg("peak_local_max", min_distance, 1, PEAKS_MAX_DISTANCE, "min_distance")
     if exclude_border is True or exclude_border is False:
         border = d if exclude_border else 0
     else:
-        border = _int_arg(exclude_border, 0, 2 ** 31 - 1, "exclude_border (or a bool)")
-    limit = 0 if num_peaks is None else _int_arg(num_peaks, 1, 2 ** 31 - 1, "num_peaks (or None)")
-    _int_arg(rounds_per_batch, 1, PEAKS_MAX_BATCH, "rounds_per_batch")
+        border = _int_arg("peak_local_max", exclude_border, 0, 2 ** 31 - 1, "exclude_border (or a bool)")
+    limit = 0 if num_peaks is None else _int_arg("peak_local_max", num_peaks, 1, 2 ** 31 - 1, "num_peaks (or None)")
+    _int_arg("peak_local_max", rounds_per_batch, 1, PEAKS_MAX_BATCH, "rounds_per_batch")
     thr = []
     for name, v in (("threshold_abs", threshold_abs), ("threshold_rel", threshold_rel)):
         if v is not None and (isinstance(v, bool) or not isinstance(v, numbers.Real) or math.isnan(v)):
@@ -2316,7 +2260,7 @@ def _peaks_kept(image, args, rounds_per_batch):
     """the filter, the peak test, the spacing rounds and the compaction -> (idx, height, sample: the kept peaks in raster
     order, sample after sample; counts: the kept peaks per sample, a host list; working rounds)"""
     d, has_abs, thr_abs, has_rel, thr_rel, border, _ = args
-    _req_cuda(image)
+    req_cuda(image)
     image = image.contiguous()
     N, D, H, W = (int(s) for s in image.shape)
     V = D * H * W
@@ -2325,12 +2269,11 @@ def _peaks_kept(image, args, rounds_per_batch):
     nbytes = int(lib.tem_peaks_ws(N, D, H, W))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     counts = torch.empty((N * int(lib.tem_peaks_chunks(V)),), dtype=torch.int32, device=dev)
-    _lib.check(lib.tem_peaks_candidates(_p(image), N, D, H, W, d, has_abs, thr_abs, has_rel, thr_rel, border, _p(ws), nbytes,
-                                        _stream(image)), "tem_peaks_candidates")
+    _lib.launch("tem_peaks_candidates", image, ptr(image), N, D, H, W, d, has_abs, thr_abs, has_rel, thr_rel, border, ptr(ws),
+                nbytes)
     first = 1
     while True:
-        _lib.check(lib.tem_peaks_rounds(N, D, H, W, d, _p(ws), nbytes, _p(counts), first, int(rounds_per_batch), _stream(image)),
-                   "tem_peaks_rounds")
+        _lib.launch("tem_peaks_rounds", image, N, D, H, W, d, ptr(ws), nbytes, ptr(counts), first, int(rounds_per_batch))
         head = ws[:16 + 4 * N].view(torch.int32).tolist()
         work, alive, cand = head[:3]
         first = 0
@@ -2345,8 +2288,8 @@ def _peaks_kept(image, args, rounds_per_batch):
     sample = torch.empty((T,), dtype=torch.int32, device=dev)
     if T:
         base = torch.cumsum(counts, dim=0, dtype=torch.int64) - counts
-        _lib.check(lib.tem_peaks_compact(_p(image), _p(base), _p(idx), _p(height), _p(sample), N, D, H, W, _p(ws), nbytes,
-                                         _stream(image)), "tem_peaks_compact")
+        _lib.launch("tem_peaks_compact", image, ptr(image), ptr(base), ptr(idx), ptr(height), ptr(sample), N, D, H, W, ptr(ws),
+                    nbytes)
     return idx, height, sample, kept, work
 
 
@@ -2396,10 +2339,9 @@ def peak_markers(image: torch.Tensor, min_distance: int = 1, threshold_abs=None,
     N = int(image.shape[0])
     V = image.numel() // N
     idx, sample = _peaks_ordered(idx, height, sample)
-    start = _to_device(torch.tensor([0] + kept[:-1], dtype=torch.int64).cumsum(0).numpy(), image.device)
+    start = to_device(torch.tensor([0] + kept[:-1], dtype=torch.int64).cumsum(0).numpy(), image.device)
     out = torch.empty(tuple(image.shape), dtype=torch.int32, device=image.device)
-    _lib.check(_lib.load().tem_peaks_seeds(_p(idx), _p(sample), _p(start), int(idx.numel()), args[-1], _p(out), N, V, _stream(image)),
-               "tem_peaks_seeds")
+    _lib.launch("tem_peaks_seeds", image, ptr(idx), ptr(sample), ptr(start), int(idx.numel()), args[-1], ptr(out), N, V)
     return out
 
 
@@ -2445,7 +2387,7 @@ def _flt_weights(sig3, device):
         k = gaussian_jet_weights(s, truncate=4.0)[:, ::-1].astype("float32")
         host[a, :, :k.shape[1]] = torch.from_numpy(k.copy())
         radii.append(k.shape[1] // 2)
-    return _to_device(host.numpy(), device), (ctypes.c_int * 3)(*radii)
+    return to_device(host.numpy(), device), (ctypes.c_int * 3)(*radii)
 
 
 def _flt_scale(x, dims, sig3, outer3, bank, ch):
@@ -2456,8 +2398,8 @@ def _flt_scale(x, dims, sig3, outer3, bank, ch):
     ow, orr = _flt_weights(outer3, x.device) if ch[4] >= 0 else (None, None)
     nbytes = int(lib.tem_filters_ws(N, D, H, W))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=x.device)
-    _lib.check(lib.tem_filters_scale(_p(x), N, D, H, W, _p(w), r, _p(ow), orr, _p(bank), int(bank.shape[1]), *ch, _p(ws), nbytes,
-                                     _stream(x)), "tem_filters_scale")
+    _lib.launch("tem_filters_scale", x, ptr(x), N, D, H, W, ptr(w), r, ptr(ow), orr, ptr(bank), int(bank.shape[1]), *ch, ptr(ws),
+                nbytes)
 
 
 def _flt_entry(entry, ndim):
@@ -2487,7 +2429,7 @@ def feature_bank(x: torch.Tensor, filters_and_sigmas, out: Optional[torch.Tensor
     entries = [_flt_entry(e, ndim) for e in filters_and_sigmas]
     if not entries:
         raise ValueError("feature_bank: an empty filter list")
-    _req_cuda(x)
+    req_cuda(x)
     groups, at = [], 0    # [sig3, outer3, channels]
     for slot, sig3, outer3 in entries:
         grp = next((g for g in groups if g[0] == sig3 and g[2][slot] < 0 and (slot != 4 or g[1] is None)), None)
@@ -2540,7 +2482,7 @@ class Forest:
     def on(self, device):
         key = str(device)
         if key not in self._dev:
-            self._dev[key] = tuple(_to_device(a, device) for a in (self.nodes, self.leaves, self.roots))
+            self._dev[key] = tuple(to_device(a, device) for a in (self.nodes, self.leaves, self.roots))
         return self._dev[key]
 
 
@@ -2614,20 +2556,20 @@ def forest_predict(features: torch.Tensor, forest: Forest, output_channel=None) 
         [output_channel] if isinstance(output_channel, numbers.Integral) else list(output_channel)
     if not sel or any(isinstance(c, bool) or not isinstance(c, numbers.Integral) or not 0 <= c < forest.n_classes for c in sel):
         raise ValueError(f"forest_predict: output_channel {output_channel!r} outside the {forest.n_classes} classes")
-    _req_cuda(features)
+    req_cuda(features)
     features = features.contiguous()
     spatial = tuple(features.shape[2:])
     V = features.numel() // (N * F)
     nodes, leaves, roots = forest.on(features.device)
     out = torch.empty((N, len(sel)) + spatial, dtype=torch.float32, device=features.device)
-    _lib.check(_lib.load().tem_forest_predict(_p(features), N, F, V, _p(nodes), _p(leaves), _p(roots), forest.n_trees, forest.n_classes,
-                                              (ctypes.c_int * len(sel))(*[int(c) for c in sel]), len(sel), _p(out), _stream(features)),
-               "tem_forest_predict")
+    _lib.launch("tem_forest_predict", features, ptr(features), N, F, V, ptr(nodes), ptr(leaves), ptr(roots), forest.n_trees,
+                forest.n_classes, (ctypes.c_int * len(sel))(*[int(c) for c in sel]), len(sel), ptr(out))
     return out[:, 0] if isinstance(output_channel, numbers.Integral) else out
 
 
 # ---- label overlaps and instance-segmentation scores (csrc/overlap.hip) ----
-_OV_LABELS = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
+# the label dtypes `label_overlaps` takes as they are
+OV_LABELS = (torch.uint8, torch.int8, torch.int16, torch.int32, torch.int64)
 
 
 class LabelOverlaps(NamedTuple):
@@ -2665,7 +2607,7 @@ class OverlapScores(NamedTuple):
 def _ov_args(seg, target):
     """the host-side checks of `label_overlaps` (dtypes and shapes; values are not looked at)"""
     for name, t in (("seg", seg), ("target", target)):
-        if not torch.is_tensor(t) or t.dtype not in _OV_LABELS:
+        if not torch.is_tensor(t) or t.dtype not in OV_LABELS:
             raise ValueError(f"label_overlaps: {name} must be a tensor of an integer type, got {getattr(t, 'dtype', type(t))}")
     if seg.shape != target.shape:
         raise ValueError(f"label_overlaps: seg {tuple(seg.shape)} and target {tuple(target.shape)} must have one shape")
@@ -2686,7 +2628,7 @@ def label_overlaps(seg: torch.Tensor, target: torch.Tensor) -> LabelOverlaps:
     tensors are not inspected -- a negative id is not refused, it is numbered like any other non-zero value; host tensors
     are refused like any host tensor."""
     N, V = _ov_args(seg, target)
-    _req_cuda(seg, target)
+    req_cuda(seg, target)
     a = pod_ids(seg, False, 0).view(N, V)
     b = pod_ids(target, False, 0).view(N, V)
     key = a.to(torch.int64).mul_(V + 1).add_(b)
@@ -2694,19 +2636,20 @@ def label_overlaps(seg: torch.Tensor, target: torch.Tensor) -> LabelOverlaps:
     dev = seg.device
     lib = _lib.load()
     flag = torch.empty((N * V,), dtype=torch.int32, device=dev)
-    _lib.check(lib.tem_overlap_flag(_p(srt), _p(flag), N, V, _stream(seg)), "tem_overlap_flag")
+    _lib.launch("tem_overlap_flag", seg, ptr(srt), ptr(flag), N, V)
     rank = _flat_cumsum(flag)
     nbytes = int(lib.tem_overlap_ws(N, V))
     ws = torch.empty((nbytes,), dtype=torch.uint8, device=dev)
     pa, pb, n_ab = (torch.empty((N, V), dtype=torch.int32, device=dev) for _ in range(3))
     n_a, n_b = (torch.empty((N, V + 1), dtype=torch.int32, device=dev) for _ in range(2))
     npairs = torch.empty((N,), dtype=torch.int32, device=dev)
-    _lib.check(lib.tem_overlap_table(_p(srt), _p(rank), _p(pa), _p(pb), _p(n_ab), _p(npairs), _p(n_a), _p(n_b), N, V, _p(ws),
-                                     nbytes, _stream(seg)), "tem_overlap_table")
+    _lib.launch("tem_overlap_table", seg, ptr(srt), ptr(rank), ptr(pa), ptr(pb), ptr(n_ab), ptr(npairs), ptr(n_a), ptr(n_b), N, V,
+                ptr(ws), nbytes)
     return LabelOverlaps(pa, pb, n_ab, npairs, n_a, n_b, ws)
 
 
-def _ov_threshold(threshold) -> float:
+def ov_threshold(threshold) -> float:
+    """the matching threshold of `overlap_scores` as a float; ValueError outside 0.5..1"""
     threshold = float(threshold)
     if not 0.5 <= threshold <= 1.0:
         raise ValueError(f"overlap_scores: threshold {threshold}: a threshold below 0.5 needs an assignment solver and is not "
@@ -2721,16 +2664,14 @@ def overlap_scores(ov: LabelOverlaps, threshold: float = 0.5) -> OverlapScores:
     side with two of them: the size of the maximum matching for 0.5 <= threshold <= 1; a threshold below
     0.5 is refused.  Integer fields are exact, the float64 sums are reduced in a fixed order: bit-identical from run to
     run.  Nothing is read back."""
-    threshold = _ov_threshold(threshold)
-    _req_cuda(*ov[:7])
+    threshold = ov_threshold(threshold)
+    req_cuda(*ov[:7])
     N, V = (int(s) for s in ov.pa.shape)
     dev = ov.pa.device
-    lib = _lib.load()
     rec = torch.empty((N, 10), dtype=torch.int64, device=dev)
     best = torch.empty((2, N, V + 1), dtype=torch.float64, device=dev)
-    _lib.check(lib.tem_overlap_scores(_p(ov.pa), _p(ov.pb), _p(ov.n_ab), _p(ov.npairs), _p(ov.n_a), _p(ov.n_b), threshold,
-                                      _p(rec), _p(best[0]), _p(best[1]), N, V, _p(ov.ws), ov.ws.numel(), _stream(ov.pa)),
-               "tem_overlap_scores")
+    _lib.launch("tem_overlap_scores", ov.pa, ptr(ov.pa), ptr(ov.pb), ptr(ov.n_ab), ptr(ov.npairs), ptr(ov.n_a), ptr(ov.n_b),
+                threshold, ptr(rec), ptr(best[0]), ptr(best[1]), N, V, ptr(ov.ws), ov.ws.numel())
     real = rec[:, 3:8].view(torch.float64)
     ints = rec[:, 8:10].view(torch.int32)
     return OverlapScores(rec[:, 0], rec[:, 1], rec[:, 2], real[:, 0], real[:, 1], real[:, 2], real[:, 3], real[:, 4],
@@ -2739,7 +2680,7 @@ def overlap_scores(ov: LabelOverlaps, threshold: float = 0.5) -> OverlapScores:
 
 def pod_targets(ids: torch.Tensor, ndim: int, sampling, flags: int, fill: float) -> torch.Tensor:
     """int32 ids [N, D, H, W] -> float32 [N, C, D, H, W] per-object distance targets (tem_pod_targets)."""
-    _req_cuda(ids)
+    req_cuda(ids)
     N, D, H, W = ids.shape
     V = D * H * W
     nch = (1 if flags & POD_DIST else 0) + (ndim if flags & POD_DIRECTED else 0) + (1 if flags & POD_BOUNDARY else 0)
@@ -2749,8 +2690,7 @@ def pod_targets(ids: torch.Tensor, ndim: int, sampling, flags: int, fill: float)
     nws = lib.tem_pod_ws(N, V, ndim, flags)
     ws = torch.empty((nws,), dtype=torch.uint8, device=ids.device)
     samp = (ctypes.c_float * 3)(*[float(s) for s in sampling])
-    _lib.check(lib.tem_pod_targets(_p(ids), _p(out), N, D, H, W, ndim, samp, int(flags), float(fill), _p(ws), nws,
-                                   _stream(ids)), "tem_pod_targets")
+    _lib.launch("tem_pod_targets", ids, ptr(ids), ptr(out), N, D, H, W, ndim, samp, int(flags), float(fill), ptr(ws), nws)
     return out
 
 
@@ -2762,15 +2702,14 @@ def vector_edt(labels: torch.Tensor, foreground_id: int):
     """int64 labels [N, D, H, W] (2-D: D == 1) -> (offsets int32 [N, 3, D, H, W] in (z, y, x) order, pointing from each
     voxel to a nearest voxel equal to foreground_id; their exact squared length int32 [N, D, H, W]; empty int32 [N], 1
     where a sample has no such voxel -- its offsets are 0 and its squared distances VDT_NONE).  tem_vector_edt."""
-    _req_cuda(labels)
+    req_cuda(labels)
     labels = labels.to(torch.int64).contiguous()
     N, D, H, W = labels.shape
     dev = labels.device
     vec = torch.empty((N, 3, D, H, W), dtype=torch.int32, device=dev)
     d2 = torch.empty((N, D, H, W), dtype=torch.int32, device=dev)
     empty = torch.empty((N,), dtype=torch.int32, device=dev)
-    _lib.check(_lib.load().tem_vector_edt(_p(labels), int(foreground_id), _p(vec), _p(d2), _p(empty), N, D, H, W,
-                                          _stream(labels)), "tem_vector_edt")
+    _lib.launch("tem_vector_edt", labels, ptr(labels), int(foreground_id), ptr(vec), ptr(d2), ptr(empty), N, D, H, W)
     return vec, d2, empty
 
 
@@ -2788,20 +2727,20 @@ def distance_targets(labels: torch.Tensor, ndim: int, foreground_id: int = 1, di
     lib = _lib.load()
     nws = lib.tem_distance_targets_ws(N, W)
     ws = torch.empty((nws,), dtype=torch.uint8, device=d2.device)
-    _lib.check(lib.tem_distance_targets(_p(vec), _p(d2), _p(empty), _p(out), N, D, H, W, ndim, flags,
-                                        float(max_distance or 0.0), _p(ws), nws, _stream(d2)), "tem_distance_targets")
+    _lib.launch("tem_distance_targets", d2, ptr(vec), ptr(d2), ptr(empty), ptr(out), N, D, H, W, ndim, flags,
+                float(max_distance or 0.0), ptr(ws), nws)
     return out
 
 
 def onehot_target(labels: torch.Tensor, class_ids) -> torch.Tensor:
     """int64 labels [N, *spatial] and a list of ids -> float32 [N, C, *spatial] (tem_onehot_target)."""
-    _req_cuda(labels)
+    req_cuda(labels)
     labels = labels.to(torch.int64).contiguous()
     ids = (ctypes.c_int64 * len(class_ids))(*[int(c) for c in class_ids])
     N, C = labels.shape[0], len(class_ids)
     V = labels.numel() // N
     out = torch.empty((N, C) + tuple(labels.shape[1:]), dtype=torch.float32, device=labels.device)
-    _lib.check(_lib.load().tem_onehot_target(_p(labels), ids, C, _p(out), N, V, _stream(labels)), "tem_onehot_target")
+    _lib.launch("tem_onehot_target", labels, ptr(labels), ids, C, ptr(out), N, V)
     return out
 
 
@@ -2809,31 +2748,30 @@ def boundary_target_masked(labels: torch.Tensor, mode: str, kind: int, key_label
                            add_binary_target: bool) -> torch.Tensor:
     """int64 labels [N, D, H, W] -> int8 [N, 1(+1), D, H, W]: boundaries with the boundaries of (labels != key_label)
     (kind 0) or (labels == key_label) (kind 1) set to mask_label (tem_boundary_target_masked)."""
-    _req_cuda(labels)
+    req_cuda(labels)
     if mode not in BOUNDARY_MODES:
         raise NotImplementedError(f"find_boundaries mode '{mode}': the MI355X kernel has {sorted(BOUNDARY_MODES)} "
                                   "('subpixel' returns a 2n-1 grid, which cannot be a training target)")
     labels = labels.to(torch.int64).contiguous()
     N, D, H, W = labels.shape
     out = torch.empty((N, 2 if add_binary_target else 1, D, H, W), dtype=torch.int8, device=labels.device)
-    _lib.check(_lib.load().tem_boundary_target_masked(_p(labels), _p(out), N, D, H, W, BOUNDARY_MODES[mode], int(kind),
-                                                      int(key_label), int(mask_label), int(add_binary_target),
-                                                      _stream(labels)), "tem_boundary_target_masked")
+    _lib.launch("tem_boundary_target_masked", labels, ptr(labels), ptr(out), N, D, H, W, BOUNDARY_MODES[mode], int(kind),
+                int(key_label), int(mask_label), int(add_binary_target))
     return out
 
 
 def _ncv_or_contiguous(t):
-    s = _ncv_strides(t)
+    s = ncv_strides(t)
     if s is None:
         t = t.contiguous()
-        s = _ncv_strides(t)
+        s = ncv_strides(t)
     return t, s
 
 
 def dist_loss_fwd(p, t, mask_bg: bool, mse: bool, eps_fg: float, eps_dist: float):
     """-> (loss float[], coef float[6], p, t) of DistanceLoss / DiceBasedDistanceLoss on [N, 3, *spatial]
     (tem_dist_loss_fwd: one pass over both tensors, fixed-order double sums)."""
-    _req_cuda(p, t)
+    req_cuda(p, t)
     p, ps = _ncv_or_contiguous(p)
     t, ts = _ncv_or_contiguous(t)
     N, C, V = ps[3:]
@@ -2843,23 +2781,22 @@ def dist_loss_fwd(p, t, mask_bg: bool, mse: bool, eps_fg: float, eps_dist: float
     coef = torch.empty((6,), dtype=torch.float32, device=dev)
     lib = _lib.load()
     nws = lib.tem_dist_loss_ws()
-    ws = _workspace(nws, dev)
-    _lib.check(lib.tem_dist_loss_fwd(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], N, V, int(mask_bg), int(mse),
-                                     float(eps_fg), float(eps_dist), _p(sums), _p(loss), _p(coef), _p(ws), nws,
-                                     _stream(p)), "tem_dist_loss_fwd")
+    ws = workspace(nws, dev)
+    _lib.launch("tem_dist_loss_fwd", p, ptr(p), ps[0], ps[1], ps[2], ptr(t), ts[0], ts[1], ts[2], N, V, int(mask_bg), int(mse),
+                float(eps_fg), float(eps_dist), ptr(sums), ptr(loss), ptr(coef), ptr(ws), nws)
     return loss, coef, p, t
 
 
 def dist_loss_grad(p, t, coef, gout, mask_bg: bool) -> torch.Tensor:
     """d loss / d p with p's strides (tem_dist_loss_grad); gout: device scalar"""
-    ps = _ncv_strides(p)
-    ts = _ncv_strides(t)
+    ps = ncv_strides(p)
+    ts = ncv_strides(t)
     gp = torch.empty_like(p)
-    if _ncv_strides(gp)[:3] != ps[:3]:
+    if ncv_strides(gp)[:3] != ps[:3]:
         raise RuntimeError("dist_loss_grad: the gradient does not share the prediction's strides")
     N, C, V = ps[3:]
-    _lib.check(_lib.load().tem_dist_loss_grad(_p(p), ps[0], ps[1], ps[2], _p(t), ts[0], ts[1], ts[2], _p(coef), _p(gout),
-                                              _p(gp), N, V, int(mask_bg), _stream(p)), "tem_dist_loss_grad")
+    _lib.launch("tem_dist_loss_grad", p, ptr(p), ps[0], ps[1], ps[2], ptr(t), ts[0], ts[1], ts[2], ptr(coef), ptr(gout), ptr(gp), N,
+                V, int(mask_bg))
     return gp
 
 
@@ -2883,7 +2820,7 @@ class PatchVolumes:
 
     def __init__(self, volumes):
         volumes = list(volumes)
-        _req_cuda(*volumes)
+        req_cuda(*volumes)
         if not volumes or any(v.dim() != 4 or v.numel() == 0 or not v.is_contiguous() for v in volumes):
             raise ValueError("PatchVolumes: expected non-empty contiguous tensors [C, D, H, W]")
         if len({v.dtype for v in volumes}) != 1 or volumes[0].dtype not in PT_DTYPE or len({v.device for v in volumes}) != 1:
@@ -2891,7 +2828,7 @@ class PatchVolumes:
         self.volumes, self.dtype, self.device = volumes, volumes[0].dtype, volumes[0].device
         self.shapes = [tuple(int(s) for s in v.shape) for v in volumes]
         import numpy as np
-        self.table = _to_device(np.array([[v.data_ptr(), PT_DTYPE[v.dtype], *v.shape] for v in volumes], dtype=np.int64), self.device)
+        self.table = to_device(np.array([[v.data_ptr(), PT_DTYPE[v.dtype], *v.shape] for v in volumes], dtype=np.int64), self.device)
 
     def boxes(self, boxes) -> PatchBoxes:
         """host integers [M, 7] (volume, z0, y0, x0, dz, dy, dx) -> PatchBoxes; raises for a box that leaves its volume"""
@@ -2911,7 +2848,7 @@ class PatchVolumes:
             raise ValueError("patch: a box holds 2^31 voxels or more")
         host = np.zeros((b.shape[0], 8), dtype=np.int32)
         host[:, :7] = b
-        return PatchBoxes(_to_device(host, self.device), host)
+        return PatchBoxes(to_device(host, self.device), host)
 
 
 def patch_count(vols: PatchVolumes, boxes, value: int) -> torch.Tensor:
@@ -2921,8 +2858,7 @@ def patch_count(vols: PatchVolumes, boxes, value: int) -> torch.Tensor:
         raise ValueError(f"patch_count: label volumes are uint8, uint16, int32 or int64, got {vols.dtype}")
     bx = vols.boxes(boxes)
     out = torch.empty((bx.M, 2), dtype=torch.int32, device=vols.device)
-    _lib.check(_lib.load().tem_patch_count(_p(vols.table), _p(bx.dev), bx.M, PT_DTYPE[vols.dtype], bx.max_vox, int(value), _p(out),
-                                           _stream(out)), "tem_patch_count")
+    _lib.launch("tem_patch_count", out, ptr(vols.table), ptr(bx.dev), bx.M, PT_DTYPE[vols.dtype], bx.max_vox, int(value), ptr(out))
     return out
 
 
@@ -2940,8 +2876,7 @@ def patch_hist(vols: PatchVolumes, boxes, n_ids: int) -> torch.Tensor:
         raise ValueError(f"patch_hist: n_ids >= 1, got {n_ids}")
     bx = vols.boxes(boxes)
     hist = torch.empty((bx.M, int(n_ids)), dtype=torch.int32, device=vols.device)
-    _lib.check(_lib.load().tem_patch_hist(_p(vols.table), _p(bx.dev), bx.M, bx.max_vox, int(n_ids), _p(hist), _stream(hist)),
-               "tem_patch_hist")
+    _lib.launch("tem_patch_hist", hist, ptr(vols.table), ptr(bx.dev), bx.M, bx.max_vox, int(n_ids), ptr(hist))
     return hist
 
 
@@ -2953,25 +2888,23 @@ def _pt_sel(sel, n, hist, what):
 
 def patch_hist_instances(hist: torch.Tensor, excluded: torch.Tensor, min_size: int = 1) -> torch.Tensor:
     """int32 [M]: ids with at least max(min_size, 1) voxels in the box whose entry of `excluded` (int32 [n_ids]) is 0"""
-    _req_cuda(hist, excluded)
+    req_cuda(hist, excluded)
     if hist.dim() != 2 or hist.dtype != torch.int32 or not hist.is_contiguous():
         raise ValueError("patch_hist_instances: expected the contiguous int32 [M, n_ids] of patch_hist")
     _pt_sel(excluded, hist.shape[1], hist, "patch_hist_instances: excluded")
     out = torch.empty((hist.shape[0],), dtype=torch.int32, device=hist.device)
-    _lib.check(_lib.load().tem_patch_hist_reduce(_p(hist), hist.shape[0], hist.shape[1], 0, _p(excluded), 0, int(min_size), _p(out),
-                                                 _stream(out)), "tem_patch_hist_reduce")
+    _lib.launch("tem_patch_hist_reduce", out, ptr(hist), hist.shape[0], hist.shape[1], 0, ptr(excluded), 0, int(min_size), ptr(out))
     return out
 
 
 def patch_hist_listed(hist: torch.Tensor, ids: torch.Tensor) -> torch.Tensor:
     """int32 [M, K]: the box's voxels of every dense id in `ids` (int32 [K]; an id outside the histogram counts 0)"""
-    _req_cuda(hist, ids)
+    req_cuda(hist, ids)
     if hist.dim() != 2 or hist.dtype != torch.int32 or not hist.is_contiguous():
         raise ValueError("patch_hist_listed: expected the contiguous int32 [M, n_ids] of patch_hist")
     _pt_sel(ids, None, hist, "patch_hist_listed: ids")
     out = torch.empty((hist.shape[0], ids.numel()), dtype=torch.int32, device=hist.device)
-    _lib.check(_lib.load().tem_patch_hist_reduce(_p(hist), hist.shape[0], hist.shape[1], 1, _p(ids), ids.numel(), 1, _p(out),
-                                                 _stream(out)), "tem_patch_hist_reduce")
+    _lib.launch("tem_patch_hist_reduce", out, ptr(hist), hist.shape[0], hist.shape[1], 1, ptr(ids), ids.numel(), 1, ptr(out))
     return out
 
 
@@ -2990,8 +2923,8 @@ def patch_gather(vols: PatchVolumes, boxes, patch_shape, dtype: torch.dtype = to
     if min(pd, ph, pw) < 1 or (bx.host[:, 4:7] > (pd, ph, pw)).any() or bx.M * C > 65535 or pd * ph * pw >= 2 ** 31:
         raise ValueError(f"patch_gather: boxes must fit the patch {(pd, ph, pw)}; at most 65535 planes of < 2^31 voxels")
     out = torch.empty((bx.M, C, pd, ph, pw), dtype=dtype, device=vols.device)
-    _lib.check(_lib.load().tem_patch_gather(_p(vols.table), _p(bx.dev), bx.M, C, PT_DTYPE[vols.dtype], pd, ph, pw, _p(out),
-                                            PT_DTYPE[dtype], _stream(out)), "tem_patch_gather")
+    _lib.launch("tem_patch_gather", out, ptr(vols.table), ptr(bx.dev), bx.M, C, PT_DTYPE[vols.dtype], pd, ph, pw, ptr(out),
+                PT_DTYPE[dtype])
     return out
 
 
@@ -3013,7 +2946,7 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, grid, scale=Non
     if N != H * W or N == 0:
         raise ValueError(f"attention: {N} tokens do not make the grid {H} x {W}")
     tables = (None, None) if rel_pos is None else tuple(rel_pos)
-    _req_cuda(q, k, v, out, *tables)
+    req_cuda(q, k, v, out, *tables)
     if q.dtype not in _ST:
         raise ValueError(f"attention: {q.dtype} not supported (float32, float16, bfloat16)")
     if out is None:
@@ -3029,8 +2962,8 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, grid, scale=Non
     nbytes = lib.tem_attention_ws(B, nH, H, W, D, int(rel_pos is not None))
     if nbytes < 0:
         _lib.check(-1, "tem_attention_ws")
-    ws = _workspace(nbytes, q.device) if nbytes else None
-    _lib.check(lib.tem_attention_fwd(_p(q), _attn_strides(q), _p(k), _attn_strides(k), _p(v), _attn_strides(v), _p(out), _attn_strides(out),
-                                     _p(tables[0]), _p(tables[1]), B, nH, H, W, D, float(D ** -0.5 if scale is None else scale), _st(q),
-                                     _p(ws), nbytes, _stream(q)), "tem_attention_fwd")
+    ws = workspace(nbytes, q.device) if nbytes else None
+    _lib.launch("tem_attention_fwd", q, ptr(q), _attn_strides(q), ptr(k), _attn_strides(k), ptr(v), _attn_strides(v), ptr(out),
+                _attn_strides(out), ptr(tables[0]), ptr(tables[1]), B, nH, H, W, D, float(D ** -0.5 if scale is None else scale),
+                stype(q), ptr(ws), nbytes)
     return out

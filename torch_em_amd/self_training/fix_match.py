@@ -79,7 +79,7 @@ class FixMatchTrainer(SelfTrainingTrainer):
         every label scaled by source share / predicted share of its class and clipped to [0, 1]"""
         if self.source_distribution is None:
             return pseudo_labels
-        if not ops._is_dense(pseudo_labels):
+        if not ops.is_dense(pseudo_labels):
             pseudo_labels = pseudo_labels.contiguous()
         return ops.distribution_align(pseudo_labels, self.source_distribution, label_threshold)
 

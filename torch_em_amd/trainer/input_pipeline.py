@@ -12,7 +12,7 @@ tensors to the GPU (`trainer/default_trainer.py:812`).  Here the loader ships th
 
 so neither the PCIe copy (16 MB + 16 MB for a cfg-2 batch instead of 16 MB + 64 MB of float targets) nor the pre-pass
 (one pass over each tensor, HBM-bound) sits on the step's critical path.  Every pre-pass kernel runs on torch's current
-stream, which inside `torch.cuda.stream(side)` is the side stream; workspaces are per stream (ops._workspace).
+stream, which inside `torch.cuda.stream(side)` is the side stream; workspaces are per stream (ops.workspace).
 """
 from typing import Callable, Iterable, Optional
 

@@ -20,7 +20,7 @@ from typing import List, Sequence, Tuple, Union
 import numpy as np
 import torch
 
-from .. import _lib, ops
+from .. import _lib
 
 
 def _as_batch(t: torch.Tensor, spatial: int) -> torch.Tensor:
@@ -277,14 +277,13 @@ class _ElasticBase(torch.nn.Module):
 
     def displacement(self, noise: torch.Tensor, device) -> torch.Tensor:
         """[1,2,H,W] noise -> [2,H,W] displacement field on the device (normalised grid units)."""
-        lib = _lib.load()
         noise = noise.to(device=device, dtype=torch.float32).reshape(2, *noise.shape[-2:]).contiguous()
         H, W = noise.shape[-2:]
         sigma, alpha = self.flags["sigma"], self.flags["alpha"]
         g = torch.stack([_gauss1d(self.kernel_size, sigma[0]), _gauss1d(self.kernel_size, sigma[1])]).to(device)
         disp = torch.empty_like(noise)
-        _lib.check(lib.tem_elastic_field(ops._p(noise), ops._p(g), self.kernel_size, H, W, float(alpha[0]),
-                                         float(alpha[1]), ops._p(disp), ops._stream(noise)), "tem_elastic_field")
+        _lib.launch("tem_elastic_field", noise, _lib.ptr(noise), _lib.ptr(g), self.kernel_size, H, W, float(alpha[0]),
+                    float(alpha[1]), _lib.ptr(disp))
         return disp
 
     def forward(self, input: torch.Tensor, params=None) -> torch.Tensor:
@@ -346,7 +345,6 @@ class KorniaAugmentationPipeline(torch.nn.Module):
             if not t.is_cuda:
                 raise RuntimeError("torch_em_amd augmentations run on MI355X only (got a CPU tensor); no CPU fallback")
             work.append(t.to(dtype))
-        lib = _lib.load()
         augs = list(self.augmentations)
         i = 0
         while i < len(augs):
@@ -371,8 +369,8 @@ class KorniaAugmentationPipeline(torch.nn.Module):
                     assert t.shape[0] == N and t.shape[2:] == shape[2:], "all tensors must share batch and spatial shape"
                     D = t.shape[2] if spatial == 3 else 1
                     dst = torch.empty_like(t)
-                    _lib.check(lib.tem_flip3d(ops._p(t), ops._p(dst), ops._p(fl), N, t.shape[1], D, t.shape[-2],
-                                              t.shape[-1], ops._stream(t)), "tem_flip3d")
+                    _lib.launch("tem_flip3d", t, _lib.ptr(t), _lib.ptr(dst), _lib.ptr(fl), N, t.shape[1], D, t.shape[-2],
+                                t.shape[-1])
                     out.append(dst)
                 work = out
             elif isinstance(aug, RandomAffine3D):
@@ -386,9 +384,8 @@ class KorniaAugmentationPipeline(torch.nn.Module):
                     nearest = not (ip and aug.flags["interpolation"] in ("bilinear", 1))
                     dst = torch.empty_like(t)
                     depth = t.shape[2] if spatial == 3 else 1   # 2-D images: one z-plane
-                    _lib.check(lib.tem_affine_warp3d(ops._p(t), ops._p(mats), ops._p(dst), N, t.shape[1], depth,
-                                                     t.shape[-2], t.shape[-1], int(nearest), ops._stream(t)),
-                               "tem_affine_warp3d")
+                    _lib.launch("tem_affine_warp3d", t, _lib.ptr(t), _lib.ptr(mats), _lib.ptr(dst), N, t.shape[1], depth,
+                                t.shape[-2], t.shape[-1], int(nearest))
                     out.append(dst)
                 work = out
                 i += 1
@@ -403,8 +400,8 @@ class KorniaAugmentationPipeline(torch.nn.Module):
                     assert (H, W) == tuple(disp.shape[-2:]), "all tensors must share the spatial shape"
                     nearest = not (ip and aug.flags["interpolation"] in ("bilinear", 1))
                     dst = torch.empty_like(t)
-                    _lib.check(lib.tem_elastic_warp2d(ops._p(t), ops._p(disp), ops._p(dst), t.numel() // (H * W), H, W,
-                                                      int(nearest), ops._stream(t)), "tem_elastic_warp2d")
+                    _lib.launch("tem_elastic_warp2d", t, _lib.ptr(t), _lib.ptr(disp), _lib.ptr(dst), t.numel() // (H * W), H, W,
+                                int(nearest))
                     out.append(dst)
                 work = out
                 i += 1

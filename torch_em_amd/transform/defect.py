@@ -375,14 +375,14 @@ class EMDefectAugmentation:
         art = alpha = None
         if chosen:
             pairs = [self._artifact(i, plan.shape) for i in chosen]
-            art = ops._to_device(np.stack([p[0] for p in pairs]).astype(np.float32), x.device)
-            alpha = ops._to_device(np.stack([p[1] for p in pairs]).astype(np.float32), x.device)
+            art = ops.to_device(np.stack([p[0] for p in pairs]).astype(np.float32), x.device)
+            alpha = ops.to_device(np.stack([p[1] for p in pairs]).astype(np.float32), x.device)
         y = ops.defect_apply(x, tab, ops.defect_mean(x, tab), art, alpha)
         if tab.D:
             seed = plan.seed if seed is None else seed
             if seed is None:
                 raise ValueError("a plan with deformed slices needs a seed")
-            ws = ops._workspace(3 * tab.D * H * W * 4, x.device)[:3 * tab.D * H * W * 4].view(torch.float32)
+            ws = ops.workspace(3 * tab.D * H * W * 4, x.device)[:3 * tab.D * H * W * 4].view(torch.float32)
             coef, flow = ws[:tab.D * H * W].view(tab.D, H, W), ws[tab.D * H * W:].view(tab.D, 2, H, W)
             strength = float(self.deformation_strength)
             ops.defect_prefilter(x, tab, spline_fir_weights(), out=coef)

@@ -69,10 +69,8 @@ def _load_block_device(vol, offset, block_shape, halo, ndim):
     out_shape = [bs + 2 * ha for bs, ha in zip(block_shape, halo)]
     C = vol.shape[0]
     dst = torch.empty([C] + _pad3(out_shape, 1), dtype=torch.float32, device=vol.device)
-    lib = _lib.load()
-    _lib.check(lib.tem_block_load_reflect(ops._p(vol), ops._p(dst), C, vol.shape[1], vol.shape[2], vol.shape[3],
-                                          _i3(_pad3(seg_start, 0)), _i3(_pad3(seg_len, 1)), _i3(_pad3(pad_left, 0)),
-                                          _i3(_pad3(out_shape, 1)), ops._stream(vol)), "tem_block_load_reflect")
+    _lib.launch("tem_block_load_reflect", vol, _lib.ptr(vol), _lib.ptr(dst), C, vol.shape[1], vol.shape[2], vol.shape[3],
+                _i3(_pad3(seg_start, 0)), _i3(_pad3(seg_len, 1)), _i3(_pad3(pad_left, 0)), _i3(_pad3(out_shape, 1)))
     return dst.reshape([C] + out_shape)
 
 
@@ -260,11 +258,10 @@ class _NoProgress:
         pass
 
 
-def _store_inner(lib, pred, out_dev, mask_dev, halo, begin, size):
-    _lib.check(lib.tem_block_store_inner(
-        ops._p(pred), _i3(_pad3(pred.shape[1:], 1)), ops._p(out_dev), pred.shape[0], out_dev.shape[1], out_dev.shape[2],
-        out_dev.shape[3], ops._p(mask_dev), _i3(_pad3(halo, 0)), _i3(_pad3(begin, 0)), _i3(_pad3(size, 1)),
-        ops._stream(pred)), "tem_block_store_inner")
+def _store_inner(pred, out_dev, mask_dev, halo, begin, size):
+    _lib.launch("tem_block_store_inner", pred, _lib.ptr(pred), _i3(_pad3(pred.shape[1:], 1)), _lib.ptr(out_dev), pred.shape[0],
+                out_dev.shape[1], out_dev.shape[2], out_dev.shape[3], _lib.ptr(mask_dev), _i3(_pad3(halo, 0)), _i3(_pad3(begin, 0)),
+                _i3(_pad3(size, 1)))
 
 
 def _gather_block(su, vol, mask_dev, block_id, block_shape, halo, preprocess, skip_block):
@@ -305,7 +302,6 @@ def predict_with_halo(input_, model: torch.nn.Module, gpu_ids: List[Union[str, i
     """Block-wise network prediction with a halo; see the module docstring (reference :145-330)."""
     su = _Setup(input_, model, gpu_ids, block_shape, halo, output, with_channels, mask, roi, iter_list, grid_shift,
                 disable_tqdm, tqdm_desc)
-    lib = _lib.load()
     ndim = su.ndim
 
     def run_on(device, my_blocks, my_model):
@@ -328,7 +324,7 @@ def predict_with_halo(input_, model: torch.nn.Module, gpu_ids: List[Union[str, i
                 pred = _postprocessed(pred.squeeze(0), postprocess, ndim)
                 if out_dev is None:
                     out_dev = torch.zeros([pred.shape[0]] + _pad3(su.shape_spatial, 1), dtype=torch.float32, device=device)
-                _store_inner(lib, pred, out_dev, mask_dev, halo, begin, size)
+                _store_inner(pred, out_dev, mask_dev, halo, begin, size)
                 written.append(tuple(slice(b, b + s) for b, s in zip(begin, size)))
             torch.cuda.current_stream(device).synchronize()
         return out_dev, written
@@ -364,7 +360,6 @@ def predict_with_halo_pipelined(input_, model: torch.nn.Module, gpu_ids: List[Un
     batch_size = max(1, int(batch_size))
     su = _Setup(input_, model, gpu_ids, block_shape, halo, output, with_channels, mask, roi, iter_list, None, disable_tqdm,
                 tqdm_desc)
-    lib = _lib.load()
     ndim = su.ndim
 
     def run_on(device, my_blocks, my_model):
@@ -414,7 +409,7 @@ def predict_with_halo_pipelined(input_, model: torch.nn.Module, gpu_ids: List[Un
                         pk = _postprocessed(pred[k], postprocess, ndim)
                         if out_dev is None:
                             out_dev = torch.zeros([pk.shape[0]] + _pad3(su.shape_spatial, 1), dtype=torch.float32, device=device)
-                        _store_inner(lib, pk, out_dev, mask_dev, halo, begin, size)
+                        _store_inner(pk, out_dev, mask_dev, halo, begin, size)
                         written.append(tuple(slice(b, b + s) for b, s in zip(begin, size)))
                     pred.record_stream(s_post)
             for st in (s_pre, s_main, s_post):
