@@ -7,6 +7,7 @@ Laid or a Flat, the device.
   Laid, Flat, lay         tensors the test lays out itself, between sentinels;  holds_values / holds_bits: still an input
   Ledger                  the worst figure and the case count per (key, quantity); `<PREFIX>_SUMMARY` rows at teardown
   judge                   the three-way assertion (exact / fp32 units / 16-bit interval) with a reference module's bound judge
+  wave_slot_rows          a label batch whose 64-voxel waves hold chosen mixes of ids, for the kernels that group lanes by id
 """
 import ctypes
 
@@ -20,6 +21,18 @@ PAD = 64                          # sentinel elements before and after (keeps th
 TORCH = {"f32": torch.float32, "f16": torch.float16, "bf16": torch.bfloat16}
 ST = {"f32": 0, "f16": 1, "bf16": 2}
 BITS = {torch.float32: torch.int32, torch.float16: torch.int16, torch.bfloat16: torch.int16}
+
+
+def wave_slot_rows():
+    """int64 [2, 389]: sample 0 in flat order is 64 voxels of one id; 64 split 1 + 63 between two ids; 64 in four runs;
+    64 in eight runs of 8; 64 distinct ids; 64 of background; a tail of 5 with two ids -- a wave that adds once, waves up
+    to and past the four ids a wave reduces before its lanes go alone, an idle wave and a partial one.  Sample 1 is the
+    row reversed: 389 is no multiple of 64, so it starts inside a wave that also holds ids of sample 0."""
+    runs = [(1, 64), (2, 1), (3, 63)] + [(4 + k, 16) for k in range(4)] + [(8 + k, 8) for k in range(8)]
+    runs += [(16 + k, 1) for k in range(64)] + [(0, 64), (80, 2), (81, 3)]
+    row = np.repeat([i for i, _ in runs], [n for _, n in runs]).astype(np.int64)
+    assert row.size == 389
+    return np.stack([row, row[::-1]])
 
 
 class Laid:

@@ -8,6 +8,7 @@ import pytest
 import torch
 
 from conftest import GOLDEN
+from oracle.gpu_kit import wave_slot_rows
 from test_distance_cpu import fixtures_2d, fixtures_3d, oracle_ids, pod_oracle, voronoi_3d
 
 pytestmark = pytest.mark.gpu
@@ -110,6 +111,24 @@ def test_batched_call_matches_per_sample_oracle():
     out2 = PerObjectDistanceTransform(**cfg)(torch.from_numpy(lab2d).to(DEV))
     for n in range(2):
         _compare(out2[n].cpu().numpy(), pod_oracle(lab2d[n, 0], **cfg), cfg)
+
+
+@pytest.mark.parametrize("min_size", [0, 8])
+def test_chosen_id_mixes_in_one_wave(min_size):
+    """ids, the size filter and the per-object statistics where a wave holds one id, up to and more than the ids it reduces
+    together, none, a partial tail and ids of two samples.  On a row every distance is an integer and every channel one
+    float64 division of integers rounded to float32, on both sides: equality."""
+    from torch_em_amd import ops
+    from torch_em_amd.transform import PerObjectDistanceTransform
+    rows = wave_slot_rows()[:, None, None]   # two 2-D samples [1, 389]
+    ids = ops.pod_ids(torch.from_numpy(rows).to(DEV), True, min_size).cpu().numpy()
+    cfg = dict(instances=True, directed_distances=True, min_size=min_size)
+    out = PerObjectDistanceTransform(**cfg)(torch.from_numpy(rows).to(DEV)).cpu().numpy()
+    for n in range(2):
+        want = oracle_ids(rows[n, 0], True, min_size)
+        assert want.max() == (14 if min_size else 81)
+        assert np.array_equal(ids[n, 0], want), n
+        assert np.array_equal(out[n], pod_oracle(rows[n, 0], **cfg)), n
 
 
 def test_transform_and_loss_make_no_host_sync():

@@ -8,7 +8,7 @@ import pytest
 import torch
 
 import mws_ref as M
-from oracle.gpu_kit import DEV
+from oracle.gpu_kit import DEV, wave_slot_rows
 
 pytestmark = pytest.mark.gpu
 
@@ -159,6 +159,30 @@ def test_background_merge_against_float64():
     zero[0][ids[0] == 1] = 0       # id 0 is no segment: it stays, and the others are numbered as before without it
     got0 = ops.merge_background_by_embedding_(dev(zero), dev(emb), DELTA)[0].cpu().numpy()
     assert np.array_equal(got0, np.where(ids[0] == 1, 0, np.maximum(cases[0][2] - 1, 0)))
+
+
+def test_background_merge_chosen_id_mixes_in_one_wave():
+    """the counts and sums where a wave holds one segment, several, none, a partial tail and segments of two samples;
+    segments 5, 20 and 81 lie 0.1 delta from the largest (segment 1) and go with it, the others 3 delta and more away"""
+    from torch_em_amd import ops
+    ids = wave_slot_rows()
+    rs = np.random.RandomState(5)
+    near = np.isin(np.arange(82), [1, 5, 20, 81])
+    centre = np.where(near, 0.1 * DELTA * (np.arange(82) % 2), 3 * DELTA * (1 + np.arange(82) % 3))
+    emb = np.stack([centre[ids], -centre[ids]], 1) + 0.02 * DELTA * rs.uniform(-1, 1, (2, 2, 389))
+    emb = emb.astype(np.float32)
+    want = np.zeros_like(ids)
+    for n in range(2):
+        counts = np.bincount(ids[n], minlength=82)
+        assert int(np.argmax(counts[1:])) + 1 == 1
+        seg = np.flatnonzero(counts[1:]) + 1
+        means = np.stack([[emb[n, e].astype(np.float64)[ids[n] == k].mean() for e in range(2)] for k in seg])
+        p = (np.maximum(2 * DELTA - np.sqrt(((means - means[0]) ** 2).sum(1)), 0) / (2 * DELTA)) ** 2
+        assert (np.abs(p - 0.5) > 0.3).all() and np.array_equal(seg[p > 0.5], [1, 5, 20, 81])
+        kept = seg[p <= 0.5]
+        want[n] = np.where(np.isin(ids[n], kept), np.searchsorted(kept, ids[n]) + 1, 0)
+    got = ops.merge_background_by_embedding_(dev(ids.astype(np.int32).reshape(2, 1, 1, 389)), dev(emb.reshape(2, 2, 1, 1, 389)), DELTA)
+    assert np.array_equal(got.cpu().numpy().reshape(2, 389), want)
 
 
 def boxes(shape, corners, size):

@@ -12,7 +12,7 @@ from scipy.ndimage import gaussian_filter, label
 
 import metric_ref as M
 import watershed_ref as R
-from oracle.gpu_kit import DEV
+from oracle.gpu_kit import DEV, wave_slot_rows
 from torch_em_amd import metric, ops
 
 pytestmark = pytest.mark.gpu
@@ -71,6 +71,9 @@ def build_cases():
     big = np.array([0, 2 ** 31 - 1, 2 ** 40, 2 ** 31 - 1, 2 ** 40, 5, 2 ** 40], np.int64)[np.minimum(t, 6)]
     for dt in (np.int32, np.uint8, np.int16):
         C["large_target_ids_" + np.dtype(dt).name] = (np.minimum(s, 100).astype(dt)[None], big[None], one)
+    # chosen mixes of ids in the waves that add the marginals and take the best Dice per object; the target: rolled by 3
+    rows = wave_slot_rows()
+    C["wave_slot_mix"] = (rows.reshape(2, 1, 1, -1), np.roll(rows, 3, axis=1).reshape(2, 1, 1, -1), one)
     return C
 
 

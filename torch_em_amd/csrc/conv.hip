@@ -1201,9 +1201,7 @@ __global__ __launch_bounds__(256) void k_absmax(const float* __restrict__ x, int
         m = __builtin_fmaxf(m, __builtin_fmaxf(__builtin_fmaxf(__builtin_fabsf(t.x), __builtin_fabsf(t.y)),
                                                __builtin_fmaxf(__builtin_fabsf(t.z), __builtin_fabsf(t.w))));
     }
-    unsigned u = __builtin_bit_cast(unsigned, m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o, 64));
+    const unsigned u = tem_wave_max(__builtin_bit_cast(unsigned, m));
     __shared__ unsigned red[4];
     if ((threadIdx.x & 63) == 0) red[threadIdx.x >> 6] = u;
     __syncthreads();

@@ -29,29 +29,8 @@
 #define POD_MAX_LINE 4096
 #define POD_BLOCKS 2048
 
-// ---------------------------------------------------------------------------------------------------------------
-// wave helpers: a wave walks its distinct object slots one at a time (objects are spatially coherent, so most waves
+// A wave walks its distinct object slots one at a time (tem_wave_by_slot; objects are spatially coherent, so most waves
 // see one or two), reducing the lanes of one slot before a single atomic.
-// ---------------------------------------------------------------------------------------------------------------
-__device__ __forceinline__ long long wave_sum_i64(long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ int wave_min_i32(int v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v = min(v, __shfl_xor(v, o, 64));
-    return v;
-}
-__device__ __forceinline__ unsigned long long wave_max_u64(unsigned long long v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        unsigned long long w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ int lane_id() { return threadIdx.x & 63; }
 
 __device__ __forceinline__ int uf_find(int* par, int x) {
     int p = __hip_atomic_load(&par[x], __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
@@ -149,13 +128,10 @@ __global__ __launch_bounds__(256) void k_size_count(const int* __restrict__ ids,
         const int64_t g = base + threadIdx.x;
         const int id = g < NV ? ids[g] : 0;
         const long long slot = id > 0 ? (g / V) * (V + 1) + id : -1;
-        unsigned long long pending = __ballot(slot >= 0);
-        while (pending) {
-            const long long s = __shfl(slot, __ffsll((long long)pending) - 1, 64);
-            const unsigned long long mine = __ballot(slot == s);
-            if (lane_id() == __ffsll((long long)pending) - 1) atomicAdd(&cnt[s], (int)__popcll(mine));
-            pending &= ~mine;
-        }
+        tem_wave_by_slot<0>(slot, slot >= 0, [&](long long s, bool mine, int leader) {   // a count: no butterfly needed
+            const int c = (int)__popcll(__ballot(mine));
+            if (tem_lane() == leader) atomicAdd(&cnt[s], c);
+        });
     }
 }
 
@@ -219,18 +195,14 @@ __global__ __launch_bounds__(256) void k_pod_init(const int* __restrict__ ids, f
             }
             f[g] = b ? 0.f : __builtin_inff();
         }
-        unsigned long long pending = __ballot(slot >= 0);
-        while (pending) {
-            const int leader = __ffsll((long long)pending) - 1;
-            const long long s = __shfl(slot, leader, 64);
-            const bool mine = slot == s;
-            const unsigned long long m = __ballot(mine);
-            const long long sz = wave_sum_i64(mine ? z : 0), sy = wave_sum_i64(mine ? y : 0),
-                            sx = wave_sum_i64(mine ? x : 0);
-            const int mz = wave_min_i32(mine ? z : INT_MAX), my = wave_min_i32(mine ? y : INT_MAX),
-                      mx = wave_min_i32(mine ? x : INT_MAX);
-            if (lane_id() == leader) {
-                atomicAdd(&ob.cnt[s], (int)__popcll(m));
+        tem_wave_by_slot<0>(slot, slot >= 0, [&](long long s, bool mine, int leader) {
+            const int c = (int)__popcll(__ballot(mine));
+            const long long sz = tem_wave_sum<long long>(mine ? z : 0), sy = tem_wave_sum<long long>(mine ? y : 0),
+                            sx = tem_wave_sum<long long>(mine ? x : 0);
+            const int mz = tem_wave_min(mine ? z : INT_MAX), my = tem_wave_min(mine ? y : INT_MAX),
+                      mx = tem_wave_min(mine ? x : INT_MAX);
+            if (tem_lane() == leader) {
+                atomicAdd(&ob.cnt[s], c);
                 atomicAdd((unsigned long long*)&ob.csum[3 * s + 0], (unsigned long long)sz);
                 atomicAdd((unsigned long long*)&ob.csum[3 * s + 1], (unsigned long long)sy);
                 atomicAdd((unsigned long long*)&ob.csum[3 * s + 2], (unsigned long long)sx);
@@ -238,8 +210,7 @@ __global__ __launch_bounds__(256) void k_pod_init(const int* __restrict__ ids, f
                 atomicMin(&ob.cmin[3 * s + 1], my);
                 atomicMin(&ob.cmin[3 * s + 2], mx);
             }
-            pending &= ~m;
-        }
+        });
     }
 }
 
@@ -302,15 +273,7 @@ __global__ __launch_bounds__(256) void k_pod_argmax(const int* __restrict__ ids,
                 key = ((unsigned long long)__float_as_uint(f[g]) << 32) | (0xffffffffu - (unsigned)(g % V));
             }
         }
-        unsigned long long pending = __ballot(slot >= 0);
-        while (pending) {
-            const int leader = __ffsll((long long)pending) - 1;
-            const long long s = __shfl(slot, leader, 64);
-            const bool mine = slot == s;
-            const unsigned long long k = wave_max_u64(mine ? key : 0ull);
-            if (lane_id() == leader) atomicMax(&ob.key[s], k);
-            pending &= ~__ballot(mine);
-        }
+        tem_wave_atomic_max<0>(ob.key, slot, slot >= 0, key);
     }
 }
 
@@ -374,17 +337,12 @@ __global__ __launch_bounds__(256) void k_pod_chmax(const int* __restrict__ ids, 
                 pod_values(ob, G, slot, g % V, f[g], val);
             }
         }
-        unsigned long long pending = __ballot(slot >= 0);
-        while (pending) {
-            const int leader = __ffsll((long long)pending) - 1;
-            const long long s = __shfl(slot, leader, 64);
-            const bool mine = slot == s;
+        tem_wave_by_slot<0>(slot, slot >= 0, [&](long long s, bool mine, int leader) {
             for (int c = 0; c < G.nch; ++c) {   // |value| >= 0: its double bits order as unsigned integers
-                const unsigned long long m = wave_max_u64(mine ? (unsigned long long)__double_as_longlong(fabs(val[c])) : 0ull);
-                if (lane_id() == leader) atomicMax(&ob.chmax[(int64_t)G.nch * s + c], m);
+                const unsigned long long m = tem_wave_max(mine ? (unsigned long long)__double_as_longlong(fabs(val[c])) : 0ull);
+                if (tem_lane() == leader) atomicMax(&ob.chmax[(int64_t)G.nch * s + c], m);
             }
-            pending &= ~__ballot(mine);
-        }
+        });
     }
 }
 
@@ -717,18 +675,15 @@ __global__ __launch_bounds__(256) void k_dt_max(const int* __restrict__ vec, con
         }
     }
     // whole-sample maxima: wave reduction, one atomic per wave (all lanes take part; idle lanes hold the identities)
+    md = tem_wave_max(md);
+    if (ndim == 2) {
 #pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        md = max(md, __shfl_xor(md, o, 64));
-        if (ndim == 2) {
-#pragma unroll
-            for (int c = 0; c < 3; ++c) {
-                ma[c] = max(ma[c], __shfl_xor(ma[c], o, 64));
-                ms[c] = max(ms[c], __shfl_xor(ms[c], o, 64));
-            }
+        for (int c = 0; c < 3; ++c) {
+            ma[c] = tem_wave_max(ma[c]);
+            ms[c] = tem_wave_max(ms[c]);
         }
     }
-    if (lane_id() == 0) {
+    if (tem_lane() == 0) {
         atomicMax(&m[0], md);
         if (ndim == 2) {
 #pragma unroll
@@ -866,7 +821,7 @@ __global__ __launch_bounds__(256) void k_dl_partial(const float* __restrict__ p,
 #pragma unroll
     for (int k = 0; k < DL_NS; ++k) {
         const double s = tem_wave_sum_d(acc[k]);
-        if (lane_id() == 0) sh[wv][k] = s;
+        if (tem_lane() == 0) sh[wv][k] = s;
     }
     __syncthreads();
     if (threadIdx.x < DL_NS)

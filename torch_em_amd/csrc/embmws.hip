@@ -185,17 +185,12 @@ struct EeBg {
     double* dist2;     // [N][V + 1]
 };
 
-__device__ __forceinline__ long long ee_shfl_xor_ll(long long v, int o) {
-    const int lo = __shfl_xor((int)(v & 0xffffffffll), o, 64), hi = __shfl_xor((int)(v >> 32), o, 64);
-    return ((long long)hi << 32) | (unsigned int)lo;
-}
-
 __global__ __launch_bounds__(256) void k_embg_zero(ee_u64* __restrict__ p, int64_t words) {
     for (int64_t i = (int64_t)blockIdx.x * 256 + threadIdx.x; i < words; i += (int64_t)gridDim.x * 256) p[i] = 0;
 }
 
-// cnt[slot of the voxel's id] += 1 (E_SUM: sum[slot] += the fixed-point value).  A wave whose 64 voxels share one segment
-// adds once; every lane of a wave makes the same number of trips.
+// cnt[slot of the voxel's id] += 1 (E_SUM: sum[slot] += the fixed-point value).  The lanes of a wave's first segment add
+// once (a wave inside one segment: one atomic), the others one each; every lane of a wave makes the same number of trips.
 template <bool E_SUM>
 __global__ __launch_bounds__(256) void k_embg_add(const int* __restrict__ ids, const float* __restrict__ emb, int e, int E,
                                                   int* __restrict__ cnt, long long* __restrict__ sum, int64_t V, int64_t NV) {
@@ -206,19 +201,8 @@ __global__ __launch_bounds__(256) void k_embg_add(const int* __restrict__ ids, c
         const int64_t slot = id > 0 && id <= V ? n * (V + 1) + id : -1;
         long long val = 1;
         if (E_SUM) val = slot >= 0 ? __double2ll_rn((double)emb[(n * E + e) * V + (gi - n * V)] * EE_FIX) : 0;
-        const int64_t first = __shfl((long long)slot, 0, 64);
-        if (__all(slot == first)) {
-            if (first < 0) continue;
-#pragma unroll
-            for (int o = 32; o > 0; o >>= 1) val += ee_shfl_xor_ll(val, o);
-            if ((threadIdx.x & 63) == 0) {
-                if (E_SUM) atomicAdd((ee_u64*)&sum[first], (ee_u64)val);
-                else atomicAdd(&cnt[first], (int)val);
-            }
-        } else if (slot >= 0) {
-            if (E_SUM) atomicAdd((ee_u64*)&sum[slot], (ee_u64)val);
-            else atomicAdd(&cnt[slot], 1);
-        }
+        if (E_SUM) tem_wave_atomic_add<1>((ee_u64*)sum, slot, slot >= 0, (ee_u64)val);
+        else tem_wave_atomic_add<1>(cnt, slot, slot >= 0, 1);
     }
 }
 

@@ -103,20 +103,6 @@ __device__ __forceinline__ uint64_t mws_hash(mws_u64 k) {   // the finaliser of 
     return k;
 }
 
-__device__ __forceinline__ mws_u64 mws_wave_max(mws_u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const mws_u64 w = __shfl_xor(v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-__device__ __forceinline__ mws_u64 mws_wave_sum(mws_u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-
 __global__ __launch_bounds__(256) void k_mws_init_voxels(const uint8_t* __restrict__ mask, int* __restrict__ comp, mws_u64* __restrict__ best,
                                                          uint8_t* __restrict__ has, uint8_t* __restrict__ veto, int* __restrict__ head,
                                                          int64_t V, int64_t NV) {
@@ -147,8 +133,8 @@ __global__ __launch_bounds__(256) void k_mws_init_edges(const uint8_t* __restric
         n_all += ok ? 1 : 0;
         n_rep += (ok && c >= geo.n_attr) ? 1 : 0;
     }
-    n_all = mws_wave_sum(n_all);
-    n_rep = mws_wave_sum(n_rep);
+    n_all = tem_wave_sum(n_all);
+    n_rep = tem_wave_sum(n_rep);
     if ((threadIdx.x & 63) == 0) {
         if (n_all) atomicAdd((mws_u64*)head, n_all);
         if (n_rep) atomicAdd((mws_u64*)head + 1, n_rep);
@@ -219,17 +205,7 @@ __device__ __forceinline__ void mws_offer(mws_u64* best, int64_t slot, mws_u64 k
     mws_u64* p = best + (active ? slot : 0);
     // an older (smaller) value may be read here: then the atomic below is merely not spared
     if (active && key <= __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) active = false;
-    for (int it = 0; it < MWS_WAVE_ROOTS; ++it) {
-        const mws_u64 ballot = __ballot(active);
-        if (ballot == 0) break;
-        const int leader = __ffsll((long long)ballot) - 1;
-        const int64_t lslot = __shfl((long long)slot, leader, 64);
-        const bool mine = active && slot == lslot;
-        const mws_u64 mm = mws_wave_max(mine ? key : 0);
-        if ((threadIdx.x & 63) == leader) atomicMax(p, mm);
-        if (mine) active = false;
-    }
-    if (active) atomicMax(p, key);
+    tem_wave_atomic_max<MWS_WAVE_ROOTS>(best, slot, active, key);
 }
 
 __global__ __launch_bounds__(256) void k_mws_pick(const float* __restrict__ aff, uint8_t* __restrict__ state, const int* __restrict__ comp,

@@ -453,9 +453,7 @@ __global__ __launch_bounds__(1024) void k_norm_bwd_apply(const T* __restrict__ g
         }
     }
     if (amax) {   // launch-uniform: one atomic per block
-        unsigned u = __builtin_bit_cast(unsigned, amx);
-#pragma unroll
-        for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o, 64));
+        unsigned u = tem_wave_max(__builtin_bit_cast(unsigned, amx));
         if ((threadIdx.x & 63) == 0) smax[threadIdx.x >> 6] = u;
         __syncthreads();
         if (threadIdx.x == 0) {

@@ -27,67 +27,9 @@ enum { OV_SUM_AB = 0, OV_S_AB, OV_MATCHED, OV_SUM_A, OV_SUM_B, OV_S_A, OV_S_B, O
 
 static int ov_blocks(int64_t items) { return (int)(tem_cdiv(items, 256) < OV_BLOCKS ? tem_cdiv(items, 256) : OV_BLOCKS); }
 
-__device__ __forceinline__ int ov_lane() { return threadIdx.x & 63; }
-
-__device__ __forceinline__ ov_u64 ov_wave_sum(ov_u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += (ov_u64)__shfl_xor((long long)v, o, 64);
-    return v;
-}
-__device__ __forceinline__ ov_u64 ov_wave_max(ov_u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const ov_u64 w = (ov_u64)__shfl_xor((long long)v, o, 64);
-        v = w > v ? w : v;
-    }
-    return v;
-}
-
-// the sum of v over the 256 threads of the block, in every thread; the order is fixed: butterfly per wave, then wave 0..3
-__device__ __forceinline__ ov_u64 ov_block_sum(ov_u64 v, ov_u64* sh) {
-    v = ov_wave_sum(v);
-    __syncthreads();
-    if (ov_lane() == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-__device__ __forceinline__ double ov_block_sum(double v, double* sh) {
-    v = tem_wave_sum_d(v);
-    __syncthreads();
-    if (ov_lane() == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return ((sh[0] + sh[1]) + sh[2]) + sh[3];
-}
-
-// cnt[slot] += val for every lane with slot >= 0 (all 64 lanes call): lanes that share a slot send one atomic
-__device__ __forceinline__ void ov_wave_add(int* cnt, long long slot, int val) {
-    ov_u64 pending = __ballot(slot >= 0);
-    for (int it = 0; it < OV_WAVE_IDS && pending; ++it) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const long long s = __shfl(slot, leader, 64);
-        const bool mine = slot == s;
-        const int sum = (int)ov_wave_sum(mine ? (ov_u64)val : 0ull);
-        if (ov_lane() == leader) atomicAdd(&cnt[s], sum);
-        pending &= ~__ballot(mine);
-        if (mine) slot = -1;
-    }
-    if (slot >= 0) atomicAdd(&cnt[slot], val);
-}
-
-// best[slot] = max(best[slot], val) on the bit patterns of non-negative doubles (they order as unsigned integers)
-__device__ __forceinline__ void ov_wave_best(ov_u64* best, long long slot, ov_u64 val) {
-    ov_u64 pending = __ballot(slot >= 0);
-    for (int it = 0; it < OV_WAVE_IDS && pending; ++it) {
-        const int leader = __ffsll((long long)pending) - 1;
-        const long long s = __shfl(slot, leader, 64);
-        const bool mine = slot == s;
-        const ov_u64 m = ov_wave_max(mine ? val : 0ull);
-        if (ov_lane() == leader) atomicMax(&best[s], m);
-        pending &= ~__ballot(mine);
-        if (mine) slot = -1;
-    }
-    if (slot >= 0) atomicMax(&best[slot], val);
-}
+// the sum of v over the 256 threads of the block, in every thread; the order is fixed: butterfly per wave, then wave 0..3.
+// The barrier in front: a kernel calls this several times on one sh.
+template <class T> __device__ __forceinline__ T ov_block_sum(T v, T* sh) { return tem_block_reduce<4, true>(v, sh, tem_op_sum()); }
 
 __device__ __forceinline__ int ov_prev_total(const int* __restrict__ rank, int64_t n, int64_t V) { return n > 0 ? rank[n * V - 1] : 0; }
 
@@ -138,8 +80,8 @@ __global__ __launch_bounds__(256) void k_ov_counts(const int* __restrict__ pa, c
             a = pa[i], b = pb[i];
             a = a > V ? -1 : a, b = b > V ? -1 : b;   // rows a consistent rank fills never hold such ids
         }
-        ov_wave_add(n_a, a, c);
-        ov_wave_add(n_b, b, c);
+        tem_wave_atomic_add<OV_WAVE_IDS>(n_a, a, a >= 0, c);
+        tem_wave_atomic_add<OV_WAVE_IDS>(n_b, b, b >= 0, c);
     }
 }
 
@@ -179,8 +121,9 @@ __global__ __launch_bounds__(256) void k_ov_pairs(const int* __restrict__ pa, co
                 dice = (ov_u64)__double_as_longlong(2.0 * (double)c / (double)(na + nb));
             }
         }
-        ov_wave_best(best_a + off, a, dice);
-        ov_wave_best(best_b + off, b, dice);
+        // max on the bit patterns of non-negative doubles (they order as unsigned integers)
+        tem_wave_atomic_max<OV_WAVE_IDS>(best_a + off, a, a >= 0, dice);
+        tem_wave_atomic_max<OV_WAVE_IDS>(best_b + off, b, b >= 0, dice);
     }
     ov_u64* p = part + (n * OV_BLOCKS + blockIdx.x) * OV_SLOTS;
     const ov_u64 t_sum = ov_block_sum(sum, sh), t_matched = ov_block_sum(matched, sh);

@@ -41,11 +41,8 @@ struct PtBox {
 // one workgroup's (c0, c1) -> out[0], out[1]: all 256 threads call
 __device__ __forceinline__ void pt_commit2(int c0, int c1, int* out) {
     __shared__ int part[4][2];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        c0 += __shfl_xor(c0, o, 64);
-        c1 += __shfl_xor(c1, o, 64);
-    }
+    c0 = tem_wave_sum(c0);
+    c1 = tem_wave_sum(c1);
     if ((threadIdx.x & 63) == 0) {
         part[threadIdx.x >> 6][0] = c0;
         part[threadIdx.x >> 6][1] = c1;
@@ -163,11 +160,8 @@ __global__ __launch_bounds__(256) void k_pt_reduce_instances(const int* __restri
     const int* h = hist + (int64_t)m * n_ids;
     int c = 0;
     for (int i = threadIdx.x; i < n_ids; i += 256) c += (h[i] >= min_size && excluded[i] == 0) ? 1 : 0;
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
-    if (threadIdx.x == 0) out[m] = part[0] + part[1] + part[2] + part[3];
+    c = tem_block_reduce<4>(c, part, tem_op_sum());
+    if (threadIdx.x == 0) out[m] = c;
 }
 
 // out[m][k] = hist[m][ids[k]] (0 for ids[k] < 0: a label the volumes do not hold)

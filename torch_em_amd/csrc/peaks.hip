@@ -113,11 +113,8 @@ __global__ __launch_bounds__(256) void k_pk_minmax(const float* __restrict__ img
             mx = __builtin_fmaxf(mx, v[u]);
         }
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        mn = __builtin_fminf(mn, __shfl_xor(mn, o, 64));
-        mx = __builtin_fmaxf(mx, __shfl_xor(mx, o, 64));
-    }
+    mn = tem_wave_reduce(mn, [](float a, float b) { return __builtin_fminf(a, b); });
+    mx = tem_wave_reduce(mx, [](float a, float b) { return __builtin_fmaxf(a, b); });
     __shared__ float part[2][4];
     if ((threadIdx.x & 63) == 0) part[0][threadIdx.x >> 6] = mn, part[1][threadIdx.x >> 6] = mx;
     __syncthreads();
@@ -214,8 +211,7 @@ __global__ __launch_bounds__(256) void k_pk_xy(const float* __restrict__ src, co
         }
         __syncthreads();   // the tile is reloaded for the next plane
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) found += __shfl_xor(found, o, 64);
+    found = tem_wave_sum(found);
     if ((tid & 63) == 0 && found) atomicAdd(&head[PK_H_CAND], found);
 }
 
@@ -325,12 +321,8 @@ __global__ __launch_bounds__(256) void k_pk_count(const uint8_t* __restrict__ st
     for (int k = 0; k < 4; ++k)
         if (v0 + k < V) c += S[v0 + k] == PK_KEPT ? 1 : 0;
     __shared__ int part[4];
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) c += __shfl_xor(c, o, 64);
-    if ((threadIdx.x & 63) == 0) part[threadIdx.x >> 6] = c;
-    __syncthreads();
+    const int total = tem_block_reduce<4>(c, part, tem_op_sum());
     if (threadIdx.x == 0) {
-        const int total = part[0] + part[1] + part[2] + part[3];
         counts[(int64_t)n * gridDim.x + blockIdx.x] = total;
         if (total) atomicAdd(&head[PK_H_KEPT + n], total);
     }

@@ -98,12 +98,8 @@ __global__ __launch_bounds__(256) void k_rn_minmax_partial(const float* __restri
         mn = v < mn ? v : mn;
         mx = v > mx ? v : mx;
     });
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float a = __shfl_xor(mn, o, 64), b = __shfl_xor(mx, o, 64);
-        mn = a < mn ? a : mn;
-        mx = b > mx ? b : mx;
-    }
+    mn = tem_wave_min(mn);
+    mx = tem_wave_max(mx);
     __shared__ float sh[2][4];
     const int w = threadIdx.x >> 6;
     if ((threadIdx.x & 63) == 0) { sh[0][w] = mn; sh[1][w] = mx; }
@@ -127,12 +123,8 @@ __global__ __launch_bounds__(64) void k_rn_minmax_final(const float* __restrict_
         mn = a < mn ? a : mn;
         mx = c > mx ? c : mx;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const float a = __shfl_xor(mn, o, 64), b = __shfl_xor(mx, o, 64);
-        mn = a < mn ? a : mn;
-        mx = b > mx ? b : mx;
-    }
+    mn = tem_wave_min(mn);
+    mx = tem_wave_max(mx);
     if (threadIdx.x == 0) { mn_out[n] = mn; mx_out[n] = mx; }
 }
 

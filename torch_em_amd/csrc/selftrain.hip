@@ -149,19 +149,6 @@ extern "C" int tem_pseudo_label_st(const void* x, void* labels, void* mask, int 
 
 static int da_parts(int64_t n, int st) { return tem_grid_1d(tem_cdiv(n, 16 / tem_st_size(st)), 256, DA_MAX_PARTS); }
 
-// the block's sum of one 64-bit value per thread (256 threads), in every thread: over the wave, then over the four waves
-// (each kernel calls it once: sh is written once per block)
-__device__ __forceinline__ unsigned long long da_block_sum(unsigned long long v, unsigned long long* sh /*[4]*/) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {   // a 64-bit value travels as two 32-bit shuffles
-        const unsigned lo = (unsigned)__shfl_xor((int)(unsigned)v, o, 64), hi = (unsigned)__shfl_xor((int)(unsigned)(v >> 32), o, 64);
-        v += ((unsigned long long)hi << 32) | lo;
-    }
-    if ((threadIdx.x & 63) == 0) sh[threadIdx.x >> 6] = v;
-    __syncthreads();
-    return sh[0] + sh[1] + sh[2] + sh[3];
-}
-
 template <typename T>
 __global__ __launch_bounds__(256) void k_label_count(const T* __restrict__ x, int64_t n, int64_t nvec, float thr,
                                                      unsigned long long* __restrict__ partials) {
@@ -176,7 +163,8 @@ __global__ __launch_bounds__(256) void k_label_count(const T* __restrict__ x, in
         for (int k = 0; k < VEC; ++k) cnt += l[k] >= thr ? 1u : 0u;
     }
     for (int64_t i = nvec * VEC + first; i < n; i += step) cnt += act_ld1(x + i) >= thr ? 1u : 0u;
-    const unsigned long long total = da_block_sum(cnt, sh);
+    // the block's sum in every thread: over the wave, then over the four waves (called once: sh is written once per block)
+    const unsigned long long total = tem_block_reduce<4>((unsigned long long)cnt, sh, tem_op_sum());
     if (threadIdx.x == 0) partials[blockIdx.x] = total;   // every block, zero included: the buffer is never cleared
 }
 
@@ -194,7 +182,7 @@ __global__ __launch_bounds__(256) void k_distribution_align(const T* __restrict_
     __shared__ unsigned long long sh[4];
     unsigned long long mine = 0;
     for (int i = threadIdx.x; i < parts; i += 256) mine += partials[i];
-    const unsigned long long c1 = da_block_sum(mine, sh), c0 = (unsigned long long)n - c1;
+    const unsigned long long c1 = tem_block_reduce<4>(mine, sh, tem_op_sum()), c0 = (unsigned long long)n - c1;
     // the reference's order: counts / counts.sum() in fp32, then source / that.  An empty class is never selected -- with a
     // NaN label it can be (NaN is not < thr); the label is NaN then whatever the ratio -- so its ratio is a plain 0, not inf
     const float fn = (float)n;

@@ -28,11 +28,6 @@ __device__ __forceinline__ void fix_add(u64* p, float v) {
 }
 __device__ __forceinline__ float fix_get(u64 v) { return (float)((double)(long long)v * (1.0 / 268435456.0)); }
 
-__device__ __forceinline__ long long shfl_xor_ll(long long v, int o) {
-    int lo = __shfl_xor((int)(v & 0xffffffffll), o, 64), hi = __shfl_xor((int)(v >> 32), o, 64);
-    return ((long long)hi << 32) | (unsigned int)lo;
-}
-
 // block sum of NV floats per thread; result valid in the first NV threads (as out[i]); deterministic order.
 template <int NV>
 __device__ __forceinline__ void block_sum(float (&v)[NV], float* sh /*[nwaves*NV]*/, float* out /*[NV] in LDS*/) {
@@ -98,12 +93,8 @@ __global__ void k_label_range(const int64_t* __restrict__ lbl, int64_t V, long l
         mn = l < mn ? l : mn;
         mx = l > mx ? l : mx;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        long long a = shfl_xor_ll(mn, o), b = shfl_xor_ll(mx, o);
-        mn = a < mn ? a : mn;
-        mx = b > mx ? b : mx;
-    }
+    mn = tem_wave_min(mn);
+    mx = tem_wave_max(mx);
     __shared__ long long sh[2][16];
     const int lane = threadIdx.x & 63, wv = threadIdx.x >> 6;
     if (lane == 0) {
@@ -127,12 +118,8 @@ __global__ __launch_bounds__(256) void k_label_range_final(const long long* __re
         mn = part[b * 2] < mn ? part[b * 2] : mn;
         mx = part[b * 2 + 1] > mx ? part[b * 2 + 1] : mx;
     }
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        long long a = shfl_xor_ll(mn, o), b = shfl_xor_ll(mx, o);
-        mn = a < mn ? a : mn;
-        mx = b > mx ? b : mx;
-    }
+    mn = tem_wave_min(mn);
+    mx = tem_wave_max(mx);
     __shared__ long long sh[2][4];
     if ((threadIdx.x & 63) == 0) {
         sh[0][threadIdx.x >> 6] = mn;

@@ -69,6 +69,7 @@ static inline int tem_grid_1d(int64_t work_items, int block, int max_blocks = 25
 }
 
 #define TEM_WAVE 64
+#include "tem_wave.h"
 
 // "output amax": max |y| of the tensor a launch writes, as a by-product (TEM_BP_OUT_AMAX).  A launch site that supports it
 // takes the caller's device word from its call descriptor (conv_internal.h: TemConvCall::take_output_amax(); NULL: not asked
@@ -79,21 +80,8 @@ __device__ __forceinline__ float tem_amax4(float m, float a, float b, float c, f
                            __builtin_fmaxf(__builtin_fabsf(c), __builtin_fabsf(d)));
 }
 __device__ __forceinline__ void tem_amax_commit(unsigned* amax, float m) {   // all lanes of a wave; amax wave-uniform, non-null
-    unsigned u = __builtin_bit_cast(unsigned, m);
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) u = max(u, (unsigned)__shfl_xor((int)u, o, 64));
-    if ((threadIdx.x & 63) == 0 && u > __atomic_load_n(amax, __ATOMIC_RELAXED)) atomicMax(amax, u);
-}
-
-__device__ __forceinline__ float tem_wave_sum(float v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
-}
-__device__ __forceinline__ double tem_wave_sum_d(double v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) v += __shfl_xor(v, o, 64);
-    return v;
+    const unsigned u = tem_wave_max(__builtin_bit_cast(unsigned, m));
+    if (tem_lane() == 0 && u > __atomic_load_n(amax, __ATOMIC_RELAXED)) atomicMax(amax, u);
 }
 
 // XCD-aware bijective remap of a linear workgroup id: consecutive logical ids

@@ -51,15 +51,6 @@ __device__ __forceinline__ int ws_local(int64_t g, int64_t V, int64_t& base) {
     return (int)(g - base);
 }
 
-__device__ __forceinline__ ws_u64 ws_wave_min(ws_u64 v) {
-#pragma unroll
-    for (int o = 32; o > 0; o >>= 1) {
-        const ws_u64 w = __shfl_xor(v, o, 64);
-        v = w < v ? w : v;
-    }
-    return v;
-}
-
 // markers: int32 or int64 (marker64); a negative marker and a marker outside the mask count as none
 __global__ __launch_bounds__(256) void k_ws_init(const void* __restrict__ markers, int marker64, const uint8_t* __restrict__ mask,
                                                  int* __restrict__ comp, int* __restrict__ lab, ws_u64* __restrict__ best,
@@ -121,17 +112,7 @@ __global__ __launch_bounds__(256) void k_ws_pick(const int* __restrict__ rank, c
         // an older (larger) value may be read here: then the atomic below is merely not spared
         if (active && m >= __hip_atomic_load(slot, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT)) active = false;
         // lanes that share a root: one atomic for all of them (components are spatially coherent)
-        for (int it = 0; it < WS_WAVE_ROOTS; ++it) {
-            const ws_u64 ballot = __ballot(active);
-            if (ballot == 0) break;
-            const int leader = __ffsll((long long)ballot) - 1;
-            const int64_t lslot = __shfl((long long)(base + r), leader, 64);
-            const bool mine = active && base + r == lslot;
-            const ws_u64 mm = ws_wave_min(mine ? m : WS_NONE);
-            if ((threadIdx.x & 63) == leader) atomicMin(slot, mm);
-            if (mine) active = false;
-        }
-        if (active) atomicMin(slot, m);
+        tem_wave_atomic_min<WS_WAVE_ROOTS>(best, base + r, active, m);
     }
     // one word for the whole grid: stores to one address queue up behind each other, so a block stores only while it reads 0
     if (__syncthreads_or(any) && threadIdx.x == 0 && ws_ld(&flags[round]) == 0) ws_st(&flags[round], 1);
