@@ -1385,12 +1385,41 @@ int tem_patch_gather(const void* vols, const int32_t* boxes, int B, int C, int i
  * tem_attention_ws() bytes of 16-byte aligned workspace (the bias pre-pass result, fp32 [B][nH][N][H + W]).  The products
  * run on the matrix cores with fp32 accumulation, `scale` multiplies the accumulated fp32 logits, P is rounded once to a 16-bit
  * `st` (kept in fp32 for TEM_ST_F32); S and P never reach global memory; no atomics: the result is bitwise reproducible.
- * Inference only.  tem_attention_ws is host logic (no device needed) and returns -1 for sizes the launch refuses. */
+ * tem_attention_ws is host logic (no device needed) and returns -1 for sizes the launch refuses.
+ * tem_attention_fwd_ex: the same call that also stores lse [B][nH][N] (fp32, dense), the log-sum-exp of every logit row, which
+ * the backward needs; lse NULL is tem_attention_fwd itself (the same kernel, the same bits). */
 #define TEM_ATTN_MAX_GRID 256
 int64_t tem_attention_ws(int B, int nH, int H, int W, int D, int has_rel_pos);
 int tem_attention_fwd(const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
                       const int64_t* v_strides, void* out, const int64_t* out_strides, const void* rel_h, const void* rel_w,
                       int B, int nH, int H, int W, int D, float scale, int st, void* ws, int64_t ws_bytes, tem_stream_t stream);
+int tem_attention_fwd_ex(const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
+                         const int64_t* v_strides, void* out, const int64_t* out_strides, const void* rel_h, const void* rel_w,
+                         int B, int nH, int H, int W, int D, float scale, int st, void* ws, int64_t ws_bytes, float* lse,
+                         tem_stream_t stream);
+/* The gradients (csrc/attention_bwd.hip).  q, k, v, out, lse, the tables, B .. st as the forward call had them (out and lse its
+ * results), dout the gradient of out; dq, dk, dv are written (every element), drel_h [2H-1][D] and drel_w [2W-1][D] are fp32,
+ * dense, both or neither (NULL: not computed).  All eight tensors are addressed by element strides under the forward's rules
+ * (unit stride along D, 16-byte multiples, 16-byte aligned bases; rows of dq, dk, dv do not overlap): the three views of one
+ * packed [B][N][3][nH][D] gradient buffer and a dout that is a view of [B][H][W][nH D] are used in place.
+ *   P = exp(S - lse)   delta_i = dout_i . out_i   dS = P (dout v^T - delta)   dv = P^T dout   dk = scale dS^T q
+ *   dB[i][x] = sum_{j: hj = x} dS[i][j] (x < H), sum_{j: wj = x - H} dS[i][j] (x >= H)
+ *   dq_i = scale (dS k)_i + sum_x dB[i][x] rel_h[hi - x + H-1] + sum_y dB[i][H + y] rel_w[wi - y + W-1]
+ *   drel_h[r] = sum over batch, head and the (i, x) with hi - x + H-1 = r of dB[i][x] q_i      drel_w likewise
+ * S, P and dS never reach global memory; P and dS are rounded once to a 16-bit `st` as MFMA operands (fp32 for TEM_ST_F32),
+ * every sum is fp32; no atomics: bitwise reproducible.  The grid is limited to H + W <= TEM_ATTN_BWD_MAX_HW (the LDS rows of
+ * dB); D and B nH as the forward.  The call needs a 16-byte aligned workspace of
+ *   tem_attention_bwd_ws = 4 B nH N + (tables ? 2 * 4 B nH N (H + W) + 4 B nH (2H-1 + 2W-1) D : 0) bytes
+ * (delta; the bias pre-pass result and dB; the per-(batch, head) partial sums of the table gradients); the query is host logic and
+ * returns -1 for sizes the launch refuses. */
+#define TEM_ATTN_BWD_MAX_HW 320
+int64_t tem_attention_bwd_ws(int B, int nH, int H, int W, int D, int has_rel_pos);
+int tem_attention_bwd(const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
+                      const int64_t* v_strides, const void* out, const int64_t* out_strides, const void* dout,
+                      const int64_t* dout_strides, const float* lse, const void* rel_h, const void* rel_w, void* dq,
+                      const int64_t* dq_strides, void* dk, const int64_t* dk_strides, void* dv, const int64_t* dv_strides,
+                      float* drel_h, float* drel_w, int B, int nH, int H, int W, int D, float scale, int st, void* ws,
+                      int64_t ws_bytes, tem_stream_t stream);
 
 #ifdef __cplusplus
 }

@@ -72,14 +72,77 @@ def composition(q, k, v, H, W, Rh, Rw, scale):
     return attn @ v
 
 
+def backward_mode(args):
+    """forward + backward of one attention call (gradients of q, k, v and both tables), device events; peak allocated memory
+    above what is resident before the call, for ops.attention plus its cached workspace.  Yardsticks: the plain composition (logits materialised in both passes) and SDPA
+    with a prebuilt bias leaf [B, nH, N, N] as attn_mask (autograd produces its gradient; building the bias is timed apart)."""
+    lines = [f"ops.attention forward + backward (csrc/attention.hip, csrc/attention_bwd.hip) with relative-position tables; {args.reps} "
+             f"repetitions after {args.warmup} warm-up, device events", f"device: {torch.cuda.get_device_name(0)}"]
+    g = torch.Generator(device=DEV).manual_seed(0)
+    for name, B, nH, H, W, D in SHAPES:
+        N = H * W
+        lines.append(f"{name}: B={B} nH={nH} {H}x{W} D={D}; logits [B, nH, N, N] in fp32: {4e-6 * B * nH * N * N:.0f} MB; backward workspace "
+                     f"(tem_attention_bwd_ws): {ops._lib.load().tem_attention_bwd_ws(B, nH, H, W, D, 1) / 1e6:.0f} MB")
+        for dt in DTYPES:
+            qkv = torch.randn((B, N, 3, nH, D), generator=g, device=DEV).to(dt).requires_grad_()
+            views = lambda: tuple(qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))      # fresh view nodes for every backward
+            Rh, Rw = ((0.5 * torch.randn((2 * s - 1, D), generator=g, device=DEV)).to(dt).requires_grad_() for s in (H, W))
+            dO = torch.randn((B, nH, N, D), generator=g, device=DEV).to(dt)
+            scale = D ** -0.5
+            bias = rel_bias(views()[0], H, W, Rh, Rw).detach().requires_grad_()
+            leaves = (qkv, Rh, Rw, bias)
+
+            def step(fn):
+                for t in leaves:
+                    t.grad = None
+                fn().backward(dO)
+
+            def run(fn):
+                st = measure(lambda: step(fn), args.warmup, args.reps)
+                for t in leaves:
+                    t.grad = None
+                torch.cuda.synchronize()
+                base = torch.cuda.memory_allocated()
+                torch.cuda.reset_peak_memory_stats()
+                step(fn)
+                torch.cuda.synchronize()
+                return st, (torch.cuda.max_memory_allocated() - base) / 1e6
+
+            ours, m0 = run(lambda: ops.attention(*views(), (H, W), rel_pos=(Rh, Rw)))
+            # ops.workspace() is a cached per-stream buffer the warm-up already allocated: it is inside the baseline, so its size
+            # (the backward's query, the larger of the two passes, at least the cache's 1 MiB) is added to the peak
+            ws_mb = max(ops._lib.load().tem_attention_bwd_ws(B, nH, H, W, D, 1), 1 << 20) / 1e6
+            m0 += ws_mb
+            comp, m1 = run(lambda: composition(*views(), H, W, Rh, Rw, scale))
+            sdpa, m2 = run(lambda: F.scaled_dot_product_attention(*views(), attn_mask=bias, scale=scale))
+            with torch.no_grad():
+                mask = measure(lambda: rel_bias(views()[0], H, W, Rh, Rw), args.warmup, args.reps)
+            verdict = ", ".join(f"{'faster' if ours['median'] < o['median'] else 'SLOWER'} than {n} x{o['median'] / ours['median']:.2f}"
+                                for n, o in (("the composition", comp), ("SDPA", sdpa)))
+            lines += [f"  {str(dt).split('.')[-1]:8s} ops.attention            {fmt(ours)}; peak {m0:.0f} MB (of which workspace {ws_mb:.0f} MB)",
+                      f"           torch composition        {fmt(comp)}; peak {m1:.0f} MB",
+                      f"           SDPA, bias as attn_mask  {fmt(sdpa)}; peak {m2:.0f} MB (+ building the bias: {mask['median']:.3f} ms)",
+                      f"           -> {verdict}"]
+    return lines
+
+
 def main():
     ap = argparse.ArgumentParser()
     ap.add_argument("--reps", type=int, default=9)
     ap.add_argument("--warmup", type=int, default=3)
     ap.add_argument("--out", default=None)
+    ap.add_argument("--backward", action="store_true", help="time forward + backward (with gradients of the tables) instead of the forward")
     args = ap.parse_args()
     if not torch.cuda.is_available():
         sys.exit("bench_attention.py needs the GPU: a CPU run gives no timing")
+    if args.backward:
+        text = "\n".join(backward_mode(args))
+        print(text)
+        if args.out:
+            os.makedirs(os.path.dirname(os.path.abspath(args.out)), exist_ok=True)
+            with open(args.out, "w") as f:
+                f.write(text + "\n")
+        return
     lines = [f"ops.attention (csrc/attention.hip) with relative-position tables; {args.reps} repetitions after {args.warmup} warm-up, device events",
              f"device: {torch.cuda.get_device_name(0)}; fraction: of {SUSTAINED_MFMA16_TFLOPS:.0f} TF, the sustained 16-bit MFMA rate"]
     g = torch.Generator(device=DEV).manual_seed(0)

@@ -295,6 +295,12 @@ SIGNATURES = {
     # out, out_strides, rel_h, rel_w, B, nH, H, W, D, scale, st, ws, ws_bytes, stream)
     "tem_attention_ws": (c_i64, [c_int] * 6),
     "tem_attention_fwd": (c_int, [c_vp, ctypes.POINTER(c_i64)] * 4 + [c_vp, c_vp] + [c_int] * 5 + [c_float, c_int, c_vp, c_i64, c_vp]),
+    # the same + lse before the stream / the gradients (csrc/attention_bwd.hip): (q, k, v, out, dout each with strides, lse, rel_h,
+    # rel_w, dq, dk, dv each with strides, drel_h, drel_w, B, nH, H, W, D, scale, st, ws, ws_bytes, stream)
+    "tem_attention_fwd_ex": (c_int, [c_vp, ctypes.POINTER(c_i64)] * 4 + [c_vp, c_vp] + [c_int] * 5 + [c_float, c_int, c_vp, c_i64, c_vp, c_vp]),
+    "tem_attention_bwd_ws": (c_i64, [c_int] * 6),
+    "tem_attention_bwd": (c_int, [c_vp, ctypes.POINTER(c_i64)] * 5 + [c_vp] * 3 + [c_vp, ctypes.POINTER(c_i64)] * 3 + [c_vp, c_vp]
+                          + [c_int] * 5 + [c_float, c_int, c_vp, c_i64, c_vp]),
 }
 
 _lib = None

@@ -26,114 +26,13 @@
 // Masking: a key column >= N gets -inf before the maximum, so it contributes exp(-inf) = 0 exactly; its K and V rows are
 // ZEROS in LDS (0 x garbage could be NaN); the maximum used in the exponent is replaced by 0 while it is still -inf, so a
 // fully masked tile gives exp(-inf - 0) = 0, never -inf - (-inf); query rows >= N compute on zeros and are not stored.
-// No atomics anywhere: same input, same bits.
-#include "tem_common.h"
-#include <type_traits>
-
-typedef float at_fx16 __attribute__((ext_vector_type(16)));
-typedef _Float16 at_h8 __attribute__((ext_vector_type(8)));
-typedef _Float16 at_h2 __attribute__((ext_vector_type(2)));
-typedef __bf16 at_b8 __attribute__((ext_vector_type(8)));
-typedef __bf16 at_b2 __attribute__((ext_vector_type(2)));
-typedef short at_s4 __attribute__((ext_vector_type(4)));
-typedef __attribute__((address_space(3))) at_s4* at_lds_p;
-
-#define AT_LDS_MAX (160 * 1024)   // LDS of a gfx950 compute unit
-#define AT_NW4_MAX_HW 81          // with tables, 4-wave workgroups up to this H + W (K, V and 128 bias rows within 64 KB)
-
-struct AtArgs {
-    const void *q, *k, *v;
-    void* o;
-    int64_t qs[3], ks[3], vs[3], os[3];   // element strides of (batch, head, token); unit stride along D
-    const float* bias;                    // [B][nH][N][H + W] of k_attn_relpos, or NULL
-    int nH, N, H, W;
-    float scale;
-};
-
-template <typename T>
-struct AtTile {
-    static constexpr bool F32 = std::is_same<T, float>::value;
-    static constexpr int NT = F32 ? 1 : 2;   // 32-key blocks of a key tile
-    static constexpr int BN = 32 * NT;
-};
-template <typename T, int D>
-struct AtLds {
-    static constexpr bool F32 = AtTile<T>::F32;
-    static constexpr int DP = (D + 31) / 32 * 32;                        // channels of the O^T tiles
-    static constexpr int KS = F32 ? 4 * (D + 2) : 2 * D + 16;            // bytes between K rows
-    static constexpr int VS = F32 ? 4 * (DP + 8) : 192;                  // bytes between V rows
-    static constexpr int KV = AtTile<T>::BN * (KS + VS);
-};
-static inline int at_bias_stride(int H, int W) { return (H + W) | 1; }
-
-template <typename T>
-__device__ __forceinline__ at_fx16 at_mfma16(uint4 a, uint4 b, at_fx16 c) {
-    if constexpr (std::is_same<T, _Float16>::value)
-        return __builtin_amdgcn_mfma_f32_32x32x16_f16(__builtin_bit_cast(at_h8, a), __builtin_bit_cast(at_h8, b), c, 0, 0, 0);
-    else
-        return __builtin_amdgcn_mfma_f32_32x32x16_bf16(__builtin_bit_cast(at_b8, a), __builtin_bit_cast(at_b8, b), c, 0, 0, 0);
-}
-template <typename T>
-__device__ __forceinline__ unsigned at_pk(float a, float b) {   // two values rounded to nearest even, one register
-    if constexpr (std::is_same<T, _Float16>::value) {
-        const at_h2 v = {(_Float16)a, (_Float16)b};
-        return __builtin_bit_cast(unsigned, v);
-    } else {
-        const at_b2 v = {(__bf16)a, (__bf16)b};
-        return __builtin_bit_cast(unsigned, v);
-    }
-}
-__device__ __forceinline__ uint2 at_tr_read(const unsigned char* p) {
-    const at_s4 v = __builtin_amdgcn_ds_read_tr16_b64_v4i16((at_lds_p)(p));
-    return __builtin_bit_cast(uint2, v);
-}
-// 4 consecutive elements as floats (p aligned to 4 elements)
-template <typename T>
-__device__ __forceinline__ float4 at_ld4(const T* p) {
-    if constexpr (std::is_same<T, float>::value) {
-        return *(const float4*)p;
-    } else {
-        const uint2 u = *(const uint2*)p;
-        if constexpr (std::is_same<T, _Float16>::value) {
-            const at_h2 a = __builtin_bit_cast(at_h2, u.x), b = __builtin_bit_cast(at_h2, u.y);
-            return make_float4((float)a.x, (float)a.y, (float)b.x, (float)b.y);
-        } else {
-            return make_float4(__builtin_bit_cast(float, u.x << 16), __builtin_bit_cast(float, u.x & 0xffff0000u),
-                               __builtin_bit_cast(float, u.y << 16), __builtin_bit_cast(float, u.y & 0xffff0000u));
-        }
-    }
-}
-
-// ---- pre-pass: bias[b][a][i][x] = q_i . Rh[hi - x + H-1] (x < H), q_i . Rw[wi - (x - H) + W-1] (x >= H); q UNscaled; fp32
-// fma chain in channel order.  One output a thread; the threads of a query read the same q row and neighbouring table rows.
-template <typename T, int D>
-__global__ __launch_bounds__(256) void k_attn_relpos(const T* __restrict__ q, int64_t qs0, int64_t qs1, int64_t qs2, const T* __restrict__ rh,
-                                                     const T* __restrict__ rw, int nH, int N, int H, int W, int64_t total,
-                                                     float* __restrict__ bias) {
-    const int HW = H + W;
-    for (int64_t idx = (int64_t)blockIdx.x * 256 + threadIdx.x; idx < total; idx += (int64_t)gridDim.x * 256) {
-        const int x = (int)(idx % HW);
-        const int64_t row = idx / HW;   // (b nH + a) N + i
-        const int i = (int)(row % N);
-        const int64_t bh = row / N;
-        const int hi = i / W, wi = i - hi * W;
-        const T* qp = q + (bh / nH) * qs0 + (bh % nH) * qs1 + (int64_t)i * qs2;
-        const T* rp = x < H ? rh + (int64_t)(hi - x + H - 1) * D : rw + (int64_t)(wi - (x - H) + W - 1) * D;
-        float acc = 0.f;
-#pragma unroll
-        for (int c = 0; c < D; c += 4) {
-            const float4 a = at_ld4<T>(qp + c), r = at_ld4<T>(rp + c);
-            acc = fmaf(a.x, r.x, acc);
-            acc = fmaf(a.y, r.y, acc);
-            acc = fmaf(a.z, r.z, acc);
-            acc = fmaf(a.w, r.w, acc);
-        }
-        bias[idx] = acc;
-    }
-}
+// No atomics anywhere: same input, same bits.  The gradients are attention_bwd.hip; what both files share is attention.h.
+#include "attention.h"
 
 // ---- the streaming-softmax kernel: grid (query tiles, B nH), 64 NW threads, dynamic LDS = K tile | V tile | bias rows
-template <typename T, int D, int NW>
+// LSE (compile time): also store L[i] = m + log(sum) of every logit row, fp32 [B][nH][N], for the backward (attention_bwd.hip);
+// without the flag the kernel is instruction for instruction the one it was (profiles/attention_fwd_asm_equal.txt).
+template <typename T, int D, int NW, bool LSE>
 __global__ __launch_bounds__(64 * NW) void k_attn_fwd(AtArgs a) {
     typedef AtLds<T, D> L;
     constexpr bool F32 = L::F32;
@@ -321,6 +220,9 @@ __global__ __launch_bounds__(64 * NW) void k_attn_fwd(AtArgs a) {
     if (!wave_live) return;
     lsum += __shfl_xor(lsum, 32, 64);   // the two halves hold disjoint keys of the same query; at least key 0 is valid: lsum > 0
     if (qi >= N) return;
+    if constexpr (LSE) {
+        if (h == 0) a.lse[(int64_t)bh * N + qi] = m + logf(lsum);   // m is finite: key 0 is valid
+    }
     T* op = (T*)a.o + bb * a.os[0] + hd * a.os[1] + (int64_t)qi * a.os[2];
 #pragma unroll
     for (int cb = 0; cb < NCB; ++cb)
@@ -337,14 +239,6 @@ __global__ __launch_bounds__(64 * NW) void k_attn_fwd(AtArgs a) {
 }
 
 // ---------------------------------------------------------------------------------------------------------------- host
-static int at_check_dims(const char* who, int B, int nH, int H, int W, int D) {
-    TEM_REQUIRE(B > 0 && nH > 0 && H > 0 && W > 0, "%s: B, nH, H, W must be positive", who);
-    TEM_REQUIRE(H <= TEM_ATTN_MAX_GRID && W <= TEM_ATTN_MAX_GRID, "%s: grid %d x %d exceeds %d a side", who, H, W, TEM_ATTN_MAX_GRID);
-    TEM_REQUIRE(D == 64 || D == 80, "%s: head width %d not supported (64 or 80)", who, D);
-    TEM_REQUIRE((int64_t)B * nH <= 65535, "%s: B * nH = %lld exceeds 65535", who, (long long)B * nH);
-    return TEM_OK;
-}
-
 extern "C" int64_t tem_attention_ws(int B, int nH, int H, int W, int D, int has_rel_pos) {
     if (at_check_dims("tem_attention_ws", B, nH, H, W, D) != TEM_OK) return -1;
     return has_rel_pos ? (int64_t)B * nH * H * W * (H + W) * 4 : 0;
@@ -355,14 +249,15 @@ static int at_launch_fwd(const AtArgs& a, int B, bool bias, hipStream_t stream) 
     const char* who = "tem_attention_fwd";
     const size_t lds = AtLds<T, D>::KV + (bias ? (size_t)32 * NW * at_bias_stride(a.H, a.W) * 4 : 0);
     TEM_REQUIRE(lds <= AT_LDS_MAX, "%s: %zu bytes of LDS needed, %d available", who, lds, AT_LDS_MAX);
+    void (*const kern)(AtArgs) = a.lse ? k_attn_fwd<T, D, NW, true> : k_attn_fwd<T, D, NW, false>;
     if (lds > 48 * 1024) {
-        const hipError_t e = hipFuncSetAttribute((const void*)k_attn_fwd<T, D, NW>, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
+        const hipError_t e = hipFuncSetAttribute((const void*)kern, hipFuncAttributeMaxDynamicSharedMemorySize, (int)lds);
         if (e != hipSuccess) {
             tem_set_error("%s: cannot reserve %zu bytes of LDS: %s", who, lds, hipGetErrorString(e));
             return TEM_ELAUNCH;
         }
     }
-    hipLaunchKernelGGL((k_attn_fwd<T, D, NW>), dim3((unsigned)tem_cdiv(a.N, 32 * NW), (unsigned)(B * a.nH)), dim3(64 * NW), lds, stream, a);
+    hipLaunchKernelGGL(kern, dim3((unsigned)tem_cdiv(a.N, 32 * NW), (unsigned)(B * a.nH)), dim3(64 * NW), lds, stream, a);
     TEM_CHECK_LAUNCH(who);
     return TEM_OK;
 }
@@ -390,7 +285,15 @@ static int at_run_d(const AtArgs& a, int B, int D, const void* rel_h, const void
 extern "C" int tem_attention_fwd(const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
                                  const int64_t* v_strides, void* out, const int64_t* out_strides, const void* rel_h, const void* rel_w,
                                  int B, int nH, int H, int W, int D, float scale, int st, void* ws, int64_t ws_bytes, tem_stream_t stream) {
-    const char* who = "tem_attention_fwd";
+    return tem_attention_fwd_ex(q, q_strides, k, k_strides, v, v_strides, out, out_strides, rel_h, rel_w, B, nH, H, W, D, scale, st, ws,
+                                ws_bytes, nullptr, stream);
+}
+
+extern "C" int tem_attention_fwd_ex(const void* q, const int64_t* q_strides, const void* k, const int64_t* k_strides, const void* v,
+                                    const int64_t* v_strides, void* out, const int64_t* out_strides, const void* rel_h, const void* rel_w,
+                                    int B, int nH, int H, int W, int D, float scale, int st, void* ws, int64_t ws_bytes, float* lse,
+                                    tem_stream_t stream) {
+    const char* who = lse ? "tem_attention_fwd_ex" : "tem_attention_fwd";
     TEM_REQUIRE(q && k && v && out && q_strides && k_strides && v_strides && out_strides, "%s: null pointer", who);
     TEM_TRY(at_check_dims(who, B, nH, H, W, D));
     TEM_REQUIRE(st == TEM_ST_F32 || st == TEM_ST_F16 || st == TEM_ST_BF16, "%s: unknown storage type %d", who, st);
@@ -423,6 +326,7 @@ extern "C" int tem_attention_fwd(const void* q, const int64_t* q_strides, const 
     }
     a.q = q, a.k = k, a.v = v, a.o = out;
     a.bias = nullptr;
+    a.lse = lse;
     a.nH = nH, a.N = H * W, a.H = H, a.W = W, a.scale = scale;
     hipStream_t s = (hipStream_t)stream;
     if (st == TEM_ST_F32) return at_run_d<float>(a, B, D, rel_h, rel_w, (float*)ws, s);

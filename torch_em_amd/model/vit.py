@@ -7,21 +7,55 @@ import torch.nn.functional as F
 from .. import ops
 
 
-def resample_rel_pos(table: torch.Tensor, size: int) -> torch.Tensor:
+def resample_rel_pos(table: torch.Tensor, size: int, keep_graph: bool = False) -> torch.Tensor:
     """A relative-position table [L, D] at the length 2 * size - 1 a grid side of `size` tokens needs: itself, or its linear
-    interpolation along L (segment_anything's get_rel_pos)."""
+    interpolation along L (segment_anything's get_rel_pos).  `keep_graph`: differentiable with respect to `table`."""
     need = 2 * size - 1
     if table.shape[0] == need:
         return table
-    res = F.interpolate(table.detach().float().reshape(1, table.shape[0], -1).permute(0, 2, 1), size=need, mode="linear")
+    src = table if keep_graph else table.detach()
+    res = F.interpolate(src.float().reshape(1, table.shape[0], -1).permute(0, 2, 1), size=need, mode="linear")
     return res.reshape(-1, need).permute(1, 0).to(table.dtype).contiguous()
+
+
+class _PackedAttention(torch.autograd.Function):
+    """ops.attention on the three views of a packed qkv-linear output [B, N, 3, nH, D] -> [B, H, W, nH D]; the backward
+    writes dq, dk, dv through strides into ONE packed buffer, the single gradient of the qkv output."""
+
+    @staticmethod
+    def forward(ctx, qkv, rel_h, rel_w, H, W, scale):
+        B, N, _, nH, D = qkv.shape
+        q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        y = torch.empty((B, H, W, nH * D), dtype=qkv.dtype, device=qkv.device)
+        lse = torch.empty((B, nH, N), dtype=torch.float32, device=qkv.device)
+        ops._attn_fwd(q, k, v, H, W, scale, (rel_h, rel_w), y.view(B, N, nH, D).permute(0, 2, 1, 3), lse)
+        ctx.save_for_backward(qkv, y, lse, rel_h, rel_w)
+        ctx.conf = (H, W, scale)
+        return y
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        qkv, y, lse, rel_h, rel_w = ctx.saved_tensors
+        B, N, _, nH, D = qkv.shape
+        heads = lambda t: t.reshape(B, N, nH, D).permute(0, 2, 1, 3)
+        q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        dqkv = torch.empty(qkv.shape, dtype=qkv.dtype, device=qkv.device)
+        dq, dk, dv = (dqkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))
+        want = rel_h is not None and (ctx.needs_input_grad[1] or ctx.needs_input_grad[2])
+        drh, drw = ops._attn_bwd(q, k, v, heads(y), heads(dy), lse, *ctx.conf, (rel_h, rel_w), dq, dk, dv, want)
+        if want:
+            drh, drw = drh.to(rel_h.dtype), drw.to(rel_w.dtype)
+        return dqkv, drh, drw, None, None, None
 
 
 class Attention(nn.Module):
     """segment_anything's multi-head attention block with decomposed relative position embeddings: same signature, same
     state_dict keys (qkv.weight/bias, proj.weight/bias, rel_pos_h, rel_pos_w).  forward(x [B, H, W, C]) -> [B, H, W, C]:
     the qkv linear, ops.attention on the three views of its packed output, writing [B, H, W, heads * D] in place for the
-    proj linear.  Inference only."""
+    proj linear.  In training mode (module.train()) under grad the fused backward of ops.attention runs: one packed gradient
+    for the qkv output, and rel_pos_h / rel_pos_w get theirs through the resampling (no table cache in that path).  In eval
+    mode the module is inference only: under grad it raises NotImplementedError; call it under torch.no_grad()."""
 
     def __init__(self, dim, num_heads=8, qkv_bias=True, use_rel_pos=False, rel_pos_zero_init=True, input_size=None):
         super().__init__()
@@ -45,11 +79,19 @@ class Attention(nn.Module):
         return self._tables[1]
 
     def forward(self, x: torch.Tensor) -> torch.Tensor:
-        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
-            raise NotImplementedError("model.vit.Attention is inference only: the backward kernel of ops.attention (k_attn_bwd) does "
-                                      "not exist yet; call it under torch.no_grad()")
         B, H, W, C = x.shape
         nH, D = self.num_heads, C // self.num_heads
+        if torch.is_grad_enabled() and (x.requires_grad or any(p.requires_grad for p in self.parameters())):
+            if not self.training:
+                raise NotImplementedError("model.vit.Attention in eval mode is inference only: the backward pass runs in training mode "
+                                          "(module.train()); call it under torch.no_grad()")
+            qkv = self.qkv(x).reshape(B, H * W, 3, nH, D)
+            tables = (None, None)
+            if self.use_rel_pos:
+                tables = tuple(resample_rel_pos(t, s, keep_graph=True).to(qkv.dtype).contiguous()
+                               for t, s in zip((self.rel_pos_h, self.rel_pos_w), (H, W)))
+            ops._attn_ws_bytes("tem_attention_bwd_ws", qkv[:, :, 0].permute(0, 2, 1, 3), H, W, self.use_rel_pos)   # refuse before the forward
+            return self.proj(_PackedAttention.apply(qkv.contiguous(), tables[0], tables[1], H, W, self.scale))
         qkv = self.qkv(x).reshape(B, H * W, 3, nH, D)
         q, k, v = (qkv[:, :, i].permute(0, 2, 1, 3) for i in range(3))          # [B, nH, N, D] views, read in place
         y = torch.empty((B, H, W, C), dtype=qkv.dtype, device=qkv.device)

@@ -2928,17 +2928,13 @@ def patch_gather(vols: PatchVolumes, boxes, patch_shape, dtype: torch.dtype = to
     return out
 
 
-# ---- fused multi-head attention over a 2-D token grid (csrc/attention.hip) ----
+# ---- fused multi-head attention over a 2-D token grid (csrc/attention.hip, csrc/attention_bwd.hip) ----
 def _attn_strides(t: torch.Tensor):
     return (ctypes.c_int64 * 4)(*[int(s) for s in t.stride()])
 
 
-def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, grid, scale=None, rel_pos=None, out=None) -> torch.Tensor:
-    """softmax(scale * q k^T + rel_h + rel_w) v over the tokens of an H x W grid, one launch that never materialises the
-    logits (segment_anything's Attention with add_decomposed_rel_pos; inference only).  q, k, v: [B, nH, N = H * W, D] views of
-    one 16-bit or float32 type with unit stride along D (D 64 or 80) -- the slices of a packed qkv-linear output are read in
-    place.  `rel_pos` = (Rh [2H-1, D], Rw [2W-1, D]) adds q_i . Rh[hi - hj + H-1] + q_i . Rw[wi - wj + W-1] (q unscaled) to
-    logit (i, j).  Returns [B, nH, N, D], or fills `out` (any view of that shape with unit stride along D)."""
+def _attn_check(q, k, v, grid, rel_pos, out):
+    """the argument checks of one attention call -> (H, W, tables), the tables contiguous"""
     H, W = (int(g) for g in grid)
     if not all(torch.is_tensor(t) and t.dim() == 4 for t in (q, k, v)) or not (q.shape == k.shape == v.shape):
         raise ValueError("attention: q, k, v are [B, nH, N, D] tensors of one shape")
@@ -2949,21 +2945,105 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, grid, scale=Non
     req_cuda(q, k, v, out, *tables)
     if q.dtype not in _ST:
         raise ValueError(f"attention: {q.dtype} not supported (float32, float16, bfloat16)")
-    if out is None:
-        out = torch.empty((B, nH, N, D), dtype=q.dtype, device=q.device)
-    elif tuple(out.shape) != (B, nH, N, D):
+    if out is not None and tuple(out.shape) != (B, nH, N, D):
         raise ValueError(f"attention: out must have shape {(B, nH, N, D)}")
     _same_st(q, k, v, out, *tables)
     if rel_pos is not None:
         if tuple(tables[0].shape) != (2 * H - 1, D) or tuple(tables[1].shape) != (2 * W - 1, D):
             raise ValueError(f"attention: rel_pos tables must be [{2 * H - 1}, {D}] and [{2 * W - 1}, {D}]")
         tables = tuple(t.contiguous() for t in tables)
-    lib = _lib.load()
-    nbytes = lib.tem_attention_ws(B, nH, H, W, D, int(rel_pos is not None))
+    return H, W, tables
+
+
+def _attn_ws_bytes(query, q, H, W, has_tables) -> int:
+    """the answer of a workspace query (host logic, nothing allocated); a size the launch refuses raises here"""
+    B, nH, _, D = (int(s) for s in q.shape)
+    nbytes = getattr(_lib.load(), query)(B, nH, H, W, D, int(has_tables))
     if nbytes < 0:
-        _lib.check(-1, "tem_attention_ws")
-    ws = workspace(nbytes, q.device) if nbytes else None
-    _lib.launch("tem_attention_fwd", q, ptr(q), _attn_strides(q), ptr(k), _attn_strides(k), ptr(v), _attn_strides(v), ptr(out),
-                _attn_strides(out), ptr(tables[0]), ptr(tables[1]), B, nH, H, W, D, float(D ** -0.5 if scale is None else scale),
-                stype(q), ptr(ws), nbytes)
+        _lib.check(-1, query)
+    return nbytes
+
+
+def _attn_ws(query, q, H, W, has_tables):
+    nbytes = _attn_ws_bytes(query, q, H, W, has_tables)
+    return (workspace(nbytes, q.device) if nbytes else None), nbytes
+
+
+def _attn_fwd(q, k, v, H, W, scale, tables, out, lse=None):
+    """the forward launch into `out`; with `lse` ([B, nH, N] float32) the entry point that also stores the rows' log-sum-exp"""
+    B, nH, N, D = (int(s) for s in q.shape)
+    ws, nbytes = _attn_ws("tem_attention_ws", q, H, W, tables[0] is not None)
+    args = (ptr(q), _attn_strides(q), ptr(k), _attn_strides(k), ptr(v), _attn_strides(v), ptr(out), _attn_strides(out), ptr(tables[0]),
+            ptr(tables[1]), B, nH, H, W, D, float(D ** -0.5 if scale is None else scale), stype(q), ptr(ws), nbytes)
+    if lse is None:
+        _lib.launch("tem_attention_fwd", q, *args)
+    else:
+        _lib.launch("tem_attention_fwd_ex", q, *args, ptr(lse))
     return out
+
+
+def _attn_usable(t: torch.Tensor) -> torch.Tensor:
+    """`t` itself where the kernels can address it (unit stride along D, the others multiples of 16 bytes, aligned base), else a copy"""
+    vec = 16 // t.element_size()
+    ok = t.stride(3) == 1 and all(s % vec == 0 for s in t.stride()[:3]) and t.data_ptr() % 16 == 0
+    return t if ok else t.contiguous()
+
+
+def _attn_bwd(q, k, v, out, dout, lse, H, W, scale, tables, dq, dk, dv, table_grads):
+    """one tem_attention_bwd call: fills dq, dk, dv (views of [B, nH, N, D]); -> (dRh, dRw) in float32, or (None, None)"""
+    B, nH, N, D = (int(s) for s in q.shape)
+    dout = _attn_usable(dout)
+    drel = (None, None)
+    if table_grads:
+        drel = tuple(torch.empty(t.shape, dtype=torch.float32, device=q.device) for t in tables)
+    ws, nbytes = _attn_ws("tem_attention_bwd_ws", q, H, W, tables[0] is not None)
+    _lib.launch("tem_attention_bwd", q, ptr(q), _attn_strides(q), ptr(k), _attn_strides(k), ptr(v), _attn_strides(v), ptr(out),
+                _attn_strides(out), ptr(dout), _attn_strides(dout), ptr(lse), ptr(tables[0]), ptr(tables[1]), ptr(dq), _attn_strides(dq),
+                ptr(dk), _attn_strides(dk), ptr(dv), _attn_strides(dv), ptr(drel[0]), ptr(drel[1]), B, nH, H, W, D,
+                float(D ** -0.5 if scale is None else scale), stype(q), ptr(ws), nbytes)
+    return drel
+
+
+class _Attention(torch.autograd.Function):
+    """ops.attention under grad: tem_attention_fwd_ex keeps the rows' log-sum-exp, tem_attention_bwd gives every gradient"""
+
+    @staticmethod
+    def forward(ctx, q, k, v, rel_h, rel_w, H, W, scale):
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+        lse = torch.empty(q.shape[:3], dtype=torch.float32, device=q.device)
+        _attn_fwd(q, k, v, H, W, scale, (rel_h, rel_w), out, lse)
+        ctx.save_for_backward(q, k, v, out, lse, rel_h, rel_w)
+        ctx.conf = (H, W, scale)
+        return out
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dout):
+        q, k, v, out, lse, rel_h, rel_w = ctx.saved_tensors
+        dq, dk, dv = (torch.empty(q.shape, dtype=q.dtype, device=q.device) for _ in range(3))
+        want = rel_h is not None and (ctx.needs_input_grad[3] or ctx.needs_input_grad[4])   # dq, dk, dv come from one pair of kernels
+        drh, drw = _attn_bwd(q, k, v, out, dout, lse, *ctx.conf, (rel_h, rel_w), dq, dk, dv, want)
+        if want:
+            drh, drw = drh.to(rel_h.dtype), drw.to(rel_w.dtype)
+        return dq, dk, dv, drh, drw, None, None, None
+
+
+def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, grid, scale=None, rel_pos=None, out=None) -> torch.Tensor:
+    """softmax(scale * q k^T + rel_h + rel_w) v over the tokens of an H x W grid, one launch that never materialises the
+    logits (segment_anything's Attention with add_decomposed_rel_pos).  q, k, v: [B, nH, N = H * W, D] views of
+    one 16-bit or float32 type with unit stride along D (D 64 or 80) -- the slices of a packed qkv-linear output are read in
+    place.  `rel_pos` = (Rh [2H-1, D], Rw [2W-1, D]) adds q_i . Rh[hi - hj + H-1] + q_i . Rw[wi - wj + W-1] (q unscaled) to
+    logit (i, j).  Returns [B, nH, N, D], or fills `out` (any view of that shape with unit stride along D).
+    Differentiable: when grad is enabled and q, k, v or a table requires grad, the result carries the fused backward
+    (csrc/attention_bwd.hip: no [N, N] tensor in either pass; grids with H + W <= 320; table gradients are computed in float32 and
+    cast to the tables' type); `out=` cannot be combined with that (ValueError).  Without a need for gradients it is the
+    same launch with the same bits."""
+    H, W, tables = _attn_check(q, k, v, grid, rel_pos, out)
+    if torch.is_grad_enabled() and any(t is not None and t.requires_grad for t in (q, k, v, *tables)):
+        if out is not None:
+            raise ValueError("attention: out= cannot be combined with gradients (an input requires grad)")
+        _attn_ws_bytes("tem_attention_bwd_ws", q, H, W, rel_pos is not None)   # a grid the backward refuses is refused here
+        return _Attention.apply(q, k, v, tables[0], tables[1], H, W, scale)
+    if out is None:
+        out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
+    return _attn_fwd(q, k, v, H, W, scale, tables, out)
