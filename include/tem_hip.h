@@ -1421,6 +1421,46 @@ int tem_attention_bwd(const void* q, const int64_t* q_strides, const void* k, co
                       float* drel_h, float* drel_w, int B, int nH, int H, int W, int D, float scale, int st, void* ws,
                       int64_t ws_bytes, tem_stream_t stream);
 
+/* ---- the rest of a SAM transformer block (model/vit.py: Block; csrc/vit_block.hip) -----------------------------------------
+ * Tokens are rows of C channels, channels-last, dense; every tensor of a call has the storage type `st` (TEM_ST_*), statistics
+ * and parameter gradients are fp32; every pointer is 16-byte aligned.  Row operations: C % 8 == 0, C <= TEM_VB_MAX_C; window
+ * size ws >= 0 (0: no windows), Hp = ceil(H / ws) ws, Wp likewise, B Hp Wp < 2^31.  The window tensor is
+ * [B (Hp / ws) (Wp / ws)][ws][ws][C], segment_anything's window_partition of the zero-padded [B][Hp][Wp][C].
+ *   tem_ln_windows_fwd       xw = window_partition(pad(LayerNorm(x) gamma + beta)): pad tokens are +0.0; mean, rstd [B][H][W] of
+ *                            x are stored when given (both or neither).
+ *   tem_window_merge_ln_fwd  x1 = shortcut + crop(window_unpartition(y)), stored rounded to `st`; xn = LayerNorm(x1) gamma + beta
+ *                            computed from the fp32 sum before that rounding; mean, rstd of x1 as above.
+ *   tem_ln_windows_bwd       g: gradient of xw (window layout; its pad tokens are not read).  dx [B][H][W][C], dgamma, dbeta [C].
+ *   tem_window_merge_ln_bwd  dx1, dxn: gradients of x1 and xn.  t = dx1 + LNbwd(dxn) is written as dshortcut [B][H][W][C] and,
+ *                            in window layout with +0.0 in the padding, as dy; dgamma, dbeta [C].  xhat is recomputed from the
+ *                            stored x1, mean and rstd.
+ *   tem_bias_gelu_fwd        y = gelu(h + bias), exact erf form, h and y [M][C4], bias [C4], C4 % 8 == 0 (no upper limit).
+ *   tem_bias_gelu_bwd        dh = dy (Phi(z) + z phi(z)), z = h + bias recomputed; dbias [C4] fp32.
+ * The backward calls sum the parameter gradients in two stages (per-workgroup partials in the workspace -- a workgroup owns
+ * TEM_VB_SLAB tokens, or every n-th row of the GELU with n = min(ceil(M / TEM_VB_GELU_ROWS), 1024) -- then a sum in index order): no atomics, bitwise
+ * reproducible.  tem_vit_block_ws(op, B, H, W, C, ws) is their one workspace query (host logic; -1 for sizes the launch refuses):
+ *   TEM_VB_LN_WINDOWS_BWD    8 C ceil(B H W / TEM_VB_SLAB) bytes          TEM_VB_WINDOW_MERGE_BWD  8 C ceil(B Hp Wp / TEM_VB_SLAB) bytes
+ *   TEM_VB_BIAS_GELU_BWD     (B = M, C = C4; H, W, ws ignored)  4 C4 min(ceil(M / TEM_VB_GELU_ROWS), 1024) bytes */
+#define TEM_VB_MAX_C 2048
+#define TEM_VB_SLAB 32
+#define TEM_VB_GELU_ROWS 16
+#define TEM_VB_LN_WINDOWS_BWD 0
+#define TEM_VB_WINDOW_MERGE_BWD 1
+#define TEM_VB_BIAS_GELU_BWD 2
+int64_t tem_vit_block_ws(int op, int64_t B, int H, int W, int C, int ws);
+int tem_ln_windows_fwd(const void* x, const void* gamma, const void* beta, void* xw, float* mean, float* rstd, int B, int H, int W,
+                       int C, int ws, float eps, int st, tem_stream_t stream);
+int tem_window_merge_ln_fwd(const void* y, const void* shortcut, const void* gamma, const void* beta, void* x1, void* xn, float* mean,
+                            float* rstd, int B, int H, int W, int C, int ws, float eps, int st, tem_stream_t stream);
+int tem_ln_windows_bwd(const void* g, const void* x, const void* gamma, const float* mean, const float* rstd, void* dx, float* dgamma,
+                       float* dbeta, int B, int H, int W, int C, int ws, int st, void* wsp, int64_t ws_bytes, tem_stream_t stream);
+int tem_window_merge_ln_bwd(const void* dx1, const void* dxn, const void* x1, const void* gamma, const float* mean, const float* rstd,
+                            void* dy, void* dshortcut, float* dgamma, float* dbeta, int B, int H, int W, int C, int ws, int st, void* wsp,
+                            int64_t ws_bytes, tem_stream_t stream);
+int tem_bias_gelu_fwd(const void* h, const void* bias, void* y, int64_t M, int C4, int st, tem_stream_t stream);
+int tem_bias_gelu_bwd(const void* dy, const void* h, const void* bias, void* dh, float* dbias, int64_t M, int C4, int st, void* wsp,
+                      int64_t ws_bytes, tem_stream_t stream);
+
 #ifdef __cplusplus
 }
 #endif

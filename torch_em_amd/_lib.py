@@ -301,6 +301,15 @@ SIGNATURES = {
     "tem_attention_bwd_ws": (c_i64, [c_int] * 6),
     "tem_attention_bwd": (c_int, [c_vp, ctypes.POINTER(c_i64)] * 5 + [c_vp] * 3 + [c_vp, ctypes.POINTER(c_i64)] * 3 + [c_vp, c_vp]
                           + [c_int] * 5 + [c_float, c_int, c_vp, c_i64, c_vp]),
+    # the rest of the transformer block (csrc/vit_block.hip): (op, B, H, W, C, ws) / pointers, then B, H, W, C, ws, [eps,] st,
+    # [workspace, bytes,] stream / bias + GELU: pointers, M, C4, st, [workspace, bytes,] stream
+    "tem_vit_block_ws": (c_i64, [c_int, c_i64] + [c_int] * 4),
+    "tem_ln_windows_fwd": (c_int, [c_vp] * 6 + [c_int] * 5 + [c_float, c_int, c_vp]),
+    "tem_window_merge_ln_fwd": (c_int, [c_vp] * 8 + [c_int] * 5 + [c_float, c_int, c_vp]),
+    "tem_ln_windows_bwd": (c_int, [c_vp] * 8 + [c_int] * 6 + [c_vp, c_i64, c_vp]),
+    "tem_window_merge_ln_bwd": (c_int, [c_vp] * 10 + [c_int] * 6 + [c_vp, c_i64, c_vp]),
+    "tem_bias_gelu_fwd": (c_int, [c_vp] * 3 + [c_i64, c_int, c_int, c_vp]),
+    "tem_bias_gelu_bwd": (c_int, [c_vp] * 5 + [c_i64, c_int, c_int, c_vp, c_i64, c_vp]),
 }
 
 _lib = None

@@ -1,5 +1,6 @@
 """Building blocks of the SAM vision transformer on the MI355X path (reference: torch_em/model/vit.py, which wraps
-segment_anything's ImageEncoderViT).  So far the attention layer: its hot path is ops.attention, the linears are torch's."""
+segment_anything's ImageEncoderViT): the attention layer and the transformer block.  Their hot paths are ops.attention and the
+fused row kernels of csrc/vit_block.hip; the linears are torch's."""
 import torch
 import torch.nn as nn
 import torch.nn.functional as F
@@ -98,3 +99,49 @@ class Attention(nn.Module):
         ops.attention(q, k, v, (H, W), scale=self.scale, rel_pos=self._rel_pos(H, W, qkv.dtype) if self.use_rel_pos else None,
                       out=y.view(B, H * W, nH, D).permute(0, 2, 1, 3))
         return self.proj(y)
+
+
+class MLPBlock(nn.Module):
+    """segment_anything's MLPBlock (lin1, GELU, lin2; state_dict keys lin1.weight/bias, lin2.weight/bias).  lin1 runs without
+    its bias, which ops.bias_gelu adds in the same pass as the exact GELU; `act` must be nn.GELU in its erf form."""
+
+    def __init__(self, embedding_dim, mlp_dim, act=nn.GELU):
+        super().__init__()
+        self.lin1 = nn.Linear(embedding_dim, mlp_dim)
+        self.lin2 = nn.Linear(mlp_dim, embedding_dim)
+        self.act = act()
+        if not isinstance(self.act, nn.GELU) or self.act.approximate != "none":
+            raise ValueError("MLPBlock: the fused kernel computes the exact (erf) nn.GELU; other activations are not supported")
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        return self.lin2(ops.bias_gelu(F.linear(x, self.lin1.weight), self.lin1.bias))
+
+
+class Block(nn.Module):
+    """segment_anything's transformer block: same signature, same state_dict keys (norm1.*, attn.*, norm2.*, mlp.lin1.*,
+    mlp.lin2.*).  forward(x [B, H, W, C]) -> [B, H, W, C]:
+        xw = ops.layer_norm_windows(x, norm1, window_size)        LayerNorm + pad + window partition, one pass
+        a = attn(xw)                                              on the windows, or on the whole grid for window_size 0
+        x1, xn = ops.window_merge_norm(a, x, norm2, window_size)  un-partition + crop + residual add + LayerNorm, one pass
+        out = x1 + lin2(ops.bias_gelu(lin1_without_bias(xn), lin1.bias))
+    Padded windows carry their zero tokens through attention unmasked, as SAM does.  norm_layer must build an affine
+    nn.LayerNorm and act_layer the exact nn.GELU (ValueError otherwise).  Training: as Attention (module.train() under grad)."""
+
+    def __init__(self, dim, num_heads, mlp_ratio=4.0, qkv_bias=True, norm_layer=nn.LayerNorm, act_layer=nn.GELU, use_rel_pos=False,
+                 rel_pos_zero_init=True, window_size=0, input_size=None):
+        super().__init__()
+        self.norm1 = norm_layer(dim)
+        self.attn = Attention(dim, num_heads=num_heads, qkv_bias=qkv_bias, use_rel_pos=use_rel_pos, rel_pos_zero_init=rel_pos_zero_init,
+                              input_size=input_size if window_size == 0 else (window_size, window_size))
+        self.norm2 = norm_layer(dim)
+        for n in (self.norm1, self.norm2):
+            if not isinstance(n, nn.LayerNorm) or not n.elementwise_affine or n.bias is None or tuple(n.normalized_shape) != (dim,):
+                raise ValueError("Block: norm_layer must build an affine nn.LayerNorm over the channels")
+        self.mlp = MLPBlock(embedding_dim=dim, mlp_dim=int(dim * mlp_ratio), act=act_layer)
+        self.window_size = window_size
+
+    def forward(self, x: torch.Tensor) -> torch.Tensor:
+        ws = self.window_size
+        xw = ops.layer_norm_windows(x, self.norm1.weight, self.norm1.bias, self.norm1.eps, ws)
+        x1, xn = ops.window_merge_norm(self.attn(xw), x, self.norm2.weight, self.norm2.bias, self.norm2.eps, ws)
+        return x1 + self.mlp(xn)

@@ -3047,3 +3047,179 @@ def attention(q: torch.Tensor, k: torch.Tensor, v: torch.Tensor, grid, scale=Non
     if out is None:
         out = torch.empty(q.shape, dtype=q.dtype, device=q.device)
     return _attn_fwd(q, k, v, H, W, scale, tables, out)
+
+
+# ---- the rest of the transformer block (csrc/vit_block.hip): LayerNorm + window partition, un-partition + residual + LayerNorm,
+# bias + GELU; model/vit.py: Block ----
+VB_LN_WINDOWS_BWD, VB_WINDOW_MERGE_BWD, VB_BIAS_GELU_BWD = 0, 1, 2
+
+
+def _vb_ws(op, on, B, H, W, C, window):
+    """the workspace of a backward call -> (buffer, bytes); a size the launch refuses raises here"""
+    nbytes = _lib.load().tem_vit_block_ws(op, B, H, W, C, window)
+    if nbytes < 0:
+        _lib.check(-1, "tem_vit_block_ws")
+    return workspace(nbytes, on.device), nbytes
+
+
+def _vb_rows_check(who, x, weight, bias, window, *more):
+    """the argument checks of a row operation -> (B, H, W, C, window, windows-shape)"""
+    if not (torch.is_tensor(x) and x.dim() == 4):
+        raise ValueError(f"{who}: the tokens are a [B, H, W, C] tensor")
+    B, H, W, C = (int(s) for s in x.shape)
+    window = int(window)
+    req_cuda(x, weight, bias, *more)
+    if x.dtype not in _ST:
+        raise ValueError(f"{who}: {x.dtype} not supported (float32, float16, bfloat16)")
+    _same_st(x, weight, bias, *more)
+    if tuple(weight.shape) != (C,) or tuple(bias.shape) != (C,):
+        raise ValueError(f"{who}: weight and bias must have shape ({C},)")
+    if window > 0:
+        nh, nw = -(-H // window), -(-W // window)
+        wshape = (B * nh * nw, window, window, C)
+    else:
+        wshape = (B, H, W, C)
+    return B, H, W, C, window, wshape
+
+
+def _ln_win_fwd(x, weight, bias, eps, window, wshape, stats):
+    B, H, W, C = x.shape
+    xw = torch.empty(wshape, dtype=x.dtype, device=x.device)
+    mean = rstd = None
+    if stats:
+        mean, rstd = (torch.empty((B, H, W), dtype=torch.float32, device=x.device) for _ in range(2))
+    _lib.launch("tem_ln_windows_fwd", x, ptr(x), ptr(weight), ptr(bias), ptr(xw), ptr(mean), ptr(rstd), B, H, W, C, window, float(eps), stype(x))
+    return xw, mean, rstd
+
+
+class _LayerNormWindows(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, x, weight, bias, eps, window, wshape):
+        xw, mean, rstd = _ln_win_fwd(x, weight, bias, eps, window, wshape, True)
+        ctx.save_for_backward(x, weight, mean, rstd)
+        ctx.conf = (window, bias.dtype)
+        return xw
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, g):
+        x, weight, mean, rstd = ctx.saved_tensors
+        window, bias_dtype = ctx.conf
+        B, H, W, C = x.shape
+        g = g.contiguous()
+        dx = torch.empty_like(x)
+        dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=x.device) for _ in range(2))
+        ws, nbytes = _vb_ws(VB_LN_WINDOWS_BWD, x, B, H, W, C, window)
+        _lib.launch("tem_ln_windows_bwd", x, ptr(g), ptr(x), ptr(weight), ptr(mean), ptr(rstd), ptr(dx), ptr(dgamma), ptr(dbeta), B, H, W, C,
+                    window, stype(x), ptr(ws), nbytes)
+        return dx, dgamma.to(weight.dtype), dbeta.to(bias_dtype), None, None, None
+
+
+def layer_norm_windows(x: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, window: int = 0) -> torch.Tensor:
+    """LayerNorm over the channels of x [B, H, W, C] fused with segment_anything's window_partition: -> the windows
+    [B nWh nWw, window, window, C] of the normalised tokens, padded AFTER the norm (pad tokens are +0.0, not `bias`), or
+    [B, H, W, C] for window = 0.  One launch, every output byte written once.  C % 8 == 0, C <= 2048; float32, float16 or
+    bfloat16, weight and bias of the same type.  Differentiable (x, weight, bias): the fused backward writes dx and sums the
+    parameter gradients in float32 without atomics, cast to the parameters' type.  Without a need for gradients: the same
+    launch, the same bits."""
+    B, H, W, C, window, wshape = _vb_rows_check("layer_norm_windows", x, weight, bias, window)
+    x, weight, bias = x.contiguous(), weight.contiguous(), bias.contiguous()
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (x, weight, bias)):
+        _vb_ws(VB_LN_WINDOWS_BWD, x, B, H, W, C, window)
+        return _LayerNormWindows.apply(x, weight, bias, eps, window, wshape)
+    return _ln_win_fwd(x, weight, bias, eps, window, wshape, False)[0]
+
+
+def _win_merge_fwd(y, shortcut, weight, bias, eps, window, stats):
+    B, H, W, C = shortcut.shape
+    x1, xn = torch.empty_like(shortcut), torch.empty_like(shortcut)
+    mean = rstd = None
+    if stats:
+        mean, rstd = (torch.empty((B, H, W), dtype=torch.float32, device=y.device) for _ in range(2))
+    _lib.launch("tem_window_merge_ln_fwd", y, ptr(y), ptr(shortcut), ptr(weight), ptr(bias), ptr(x1), ptr(xn), ptr(mean), ptr(rstd), B, H, W, C,
+                window, float(eps), stype(y))
+    return x1, xn, mean, rstd
+
+
+class _WindowMergeNorm(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, y, shortcut, weight, bias, eps, window):
+        x1, xn, mean, rstd = _win_merge_fwd(y, shortcut, weight, bias, eps, window, True)
+        ctx.save_for_backward(x1, weight, mean, rstd)
+        ctx.conf = (window, bias.dtype, y.shape)
+        return x1, xn
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dx1, dxn):
+        x1, weight, mean, rstd = ctx.saved_tensors
+        window, bias_dtype, yshape = ctx.conf
+        B, H, W, C = x1.shape
+        dx1, dxn = dx1.contiguous(), dxn.contiguous()
+        dy = torch.empty(yshape, dtype=x1.dtype, device=x1.device)
+        dshortcut = torch.empty_like(x1)
+        dgamma, dbeta = (torch.empty((C,), dtype=torch.float32, device=x1.device) for _ in range(2))
+        ws, nbytes = _vb_ws(VB_WINDOW_MERGE_BWD, x1, B, H, W, C, window)
+        _lib.launch("tem_window_merge_ln_bwd", x1, ptr(dx1), ptr(dxn), ptr(x1), ptr(weight), ptr(mean), ptr(rstd), ptr(dy), ptr(dshortcut),
+                    ptr(dgamma), ptr(dbeta), B, H, W, C, window, stype(x1), ptr(ws), nbytes)
+        return dy, dshortcut, dgamma.to(weight.dtype), dbeta.to(bias_dtype), None, None
+
+
+def window_merge_norm(y: torch.Tensor, shortcut: torch.Tensor, weight: torch.Tensor, bias: torch.Tensor, eps: float, window: int = 0):
+    """segment_anything's window_unpartition + crop + residual add fused with the block's second LayerNorm: y is the window
+    tensor [B nWh nWw, window, window, C] (or [B, H, W, C] for window = 0), shortcut [B, H, W, C] ->
+    (x1 = shortcut + merged y, xn = LayerNorm(x1) weight + bias), both [B, H, W, C].  xn comes from the float32 sum, BEFORE x1 is
+    rounded to a 16-bit type.  Pad tokens of y are never read.  Limits, types and gradients as layer_norm_windows (y, shortcut,
+    weight, bias; the gradient of y has +0.0 in its pad tokens)."""
+    B, H, W, C, window, wshape = _vb_rows_check("window_merge_norm", shortcut, weight, bias, window, y)
+    if tuple(y.shape) != wshape:
+        raise ValueError(f"window_merge_norm: y must have shape {wshape} for tokens {tuple(shortcut.shape)} and window {window}")
+    y, shortcut, weight, bias = y.contiguous(), shortcut.contiguous(), weight.contiguous(), bias.contiguous()
+    if torch.is_grad_enabled() and any(t.requires_grad for t in (y, shortcut, weight, bias)):
+        _vb_ws(VB_WINDOW_MERGE_BWD, y, B, H, W, C, window)
+        return _WindowMergeNorm.apply(y, shortcut, weight, bias, eps, window)
+    return _win_merge_fwd(y, shortcut, weight, bias, eps, window, False)[:2]
+
+
+def _bias_gelu_fwd(h, bias):
+    y = torch.empty_like(h)
+    _lib.launch("tem_bias_gelu_fwd", h, ptr(h), ptr(bias), ptr(y), h.numel() // h.shape[-1], h.shape[-1], stype(h))
+    return y
+
+
+class _BiasGelu(torch.autograd.Function):
+    @staticmethod
+    def forward(ctx, h, bias):
+        ctx.save_for_backward(h, bias)
+        return _bias_gelu_fwd(h, bias)
+
+    @staticmethod
+    @torch.autograd.function.once_differentiable
+    def backward(ctx, dy):
+        h, bias = ctx.saved_tensors
+        M, C4 = h.numel() // h.shape[-1], h.shape[-1]
+        dy = dy.contiguous()
+        dh = torch.empty_like(h)
+        db = torch.empty((C4,), dtype=torch.float32, device=h.device)
+        ws, nbytes = _vb_ws(VB_BIAS_GELU_BWD, h, M, 1, 1, C4, 0)
+        _lib.launch("tem_bias_gelu_bwd", h, ptr(dy), ptr(h), ptr(bias), ptr(dh), ptr(db), M, C4, stype(h), ptr(ws), nbytes)
+        return dh, db.to(bias.dtype)
+
+
+def bias_gelu(h: torch.Tensor, bias: torch.Tensor) -> torch.Tensor:
+    """gelu(h + bias) with the exact erf form (nn.GELU's default) in one pass: h [..., C4], bias [C4], C4 % 8 == 0; float32,
+    float16 or bfloat16.  Differentiable (h, bias): dh is recomputed from h and bias, the bias gradient is summed in float32
+    without atomics and cast to the bias's type.  Without a need for gradients: the same launch, the same bits."""
+    if not (torch.is_tensor(h) and h.dim() >= 1 and torch.is_tensor(bias) and tuple(bias.shape) == (int(h.shape[-1]),)):
+        raise ValueError("bias_gelu: h is [..., C4] and bias [C4]")
+    req_cuda(h, bias)
+    if h.dtype not in _ST:
+        raise ValueError(f"bias_gelu: {h.dtype} not supported (float32, float16, bfloat16)")
+    _same_st(h, bias)
+    if h.numel() == 0:
+        raise ValueError("bias_gelu: h is empty")
+    h, bias = h.contiguous(), bias.contiguous()
+    if torch.is_grad_enabled() and (h.requires_grad or bias.requires_grad):
+        _vb_ws(VB_BIAS_GELU_BWD, h, h.numel() // h.shape[-1], 1, 1, int(h.shape[-1]), 0)
+        return _BiasGelu.apply(h, bias)
+    return _bias_gelu_fwd(h, bias)
